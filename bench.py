@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks NB]
                     [--shard time|channels] [--no-cpu] [--no-extra] [--settle-steps S]
+                    [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[2] with an acquisition search in front of it): a
 resident batch of NB 32-ms blocks of synthetic 2.048 Msps IQ (NB x 65536
@@ -54,6 +55,13 @@ uint16 next to complex64), all timed on this GPU after the timed region.  Round 
 from the committed profiles/round3/pmc_counters.txt), `closed_loop.batched` (R independent
 receivers on one handle) and, at N > 1, `multi_gpu` (RCCL's own rank count, per-rank
 rates, the gather alone, the channel-sharded split beside the time-sharded headline).
+
+--dump-outputs DIR writes what the timed path handed its caller in the last timed step (rank 0):
+the acquisition peak table (acq_<field>.npy; at N > 1 the gathered shard tables) and the
+tracking records of the batch (track_<field>.npy, [NB, channels, ...]), float32 fields as they
+are, integer and float64 fields as float64, which holds them exactly.  The IQ is a pure function
+of the arguments, so two builds can be compared file by file.  Past DUMP_BYTES in all, a fixed,
+seeded sample of blocks is written, their indices in track_rows.npy.
 """
 import argparse
 import json
@@ -79,6 +87,7 @@ PMC_FILE = os.path.join('profiles', 'round4', 'pmc_counters.txt')
 ISSUE_CYCLES = 4.9             # measured cycles per packed-fp32 VALU instruction of one wave's stream
                                # (tools/probe/hazard_probe.hip); the FFT kernels are made of those
 ISSUE_CLOCK_GHZ = 2.2          # the clock DESIGN section 4.4 priced its 78 us floor at
+DUMP_BYTES = 60 * 10**6        # --dump-outputs: array bytes in all (under 64 MB with the headers)
 
 
 def csrc_sha256():
@@ -164,6 +173,32 @@ def issue_roofline(kernels, duration_ms, label):
             'issue_cycles_per_instruction': ISSUE_CYCLES, 'clock_ghz': ISSUE_CLOCK_GHZ,
             'floor_ms': round(floor_ms, 4), 'duration_ms': round(duration_ms, 4),
             'frac': round(floor_ms / duration_ms, 4), 'counter_source': PMC_FILE}
+
+
+def _as_float(v):
+    """float32 fields as they are; integer and float64 fields as float64 (exact for both)."""
+    return v.astype(np.float32 if v.dtype == np.float32 else np.float64)
+
+
+def dump_outputs(path, records):
+    """--dump-outputs: one <prefix>_<field>.npy per field of each structured array in
+    `records` ({prefix: array}).  Past DUMP_BYTES in all, a fixed sample of the tracking blocks
+    (seeded, sorted) is written instead of all of them, the block indices in track_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    size = {p: sum(_as_float(r[n]).nbytes for n in r.dtype.names) for p, r in records.items()}
+    track = records['track']
+    if sum(size.values()) > DUMP_BYTES:
+        keep = (DUMP_BYTES - size['acq']) // (size['track'] // track.shape[0] + 8)
+        rows = np.sort(np.random.default_rng(SEED).choice(track.shape[0], keep, replace=False))
+        records = dict(records, track=track[rows])
+        np.save(os.path.join(path, 'track_rows.npy'), rows.astype(np.float64))
+    total = 0
+    for p, r in records.items():
+        for n in r.dtype.names:
+            v = _as_float(r[n])
+            np.save(os.path.join(path, f'{p}_{n}.npy'), v)
+            total += v.nbytes
+    print(f'bench: outputs of the last timed step -> {path} ({total / 2**20:.1f} MiB)', file=sys.stderr)
 
 
 # ---------------------------------------------------------------- input data
@@ -667,6 +702,8 @@ def main():
                     help='N > 1: how the tracking work is split over the ranks')
     ap.add_argument('--rehearse', action='store_true',
                     help='N > 1 on a box with fewer GPUs: ranks share devices, RCCL skipped')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the last timed step\'s outputs to DIR/<name>.npy (module docstring)')
     a = ap.parse_args()
 
     rank = int(os.environ.get('RANK', '0'))
@@ -934,6 +971,11 @@ def main():
     trk.wait()                              # ... its kernels and its copy
     barrier()
     dt = time.perf_counter() - t0
+    # what the last timed step handed its caller (the passes below reuse these buffers)
+    last_out = None
+    if a.dump_outputs and rank == 0:
+        last_out = {'acq': (acq_pin.array if world == 1 else gathered).copy(),
+                    'track': pins[(a.steps - 1) & 1].array.copy()}
     record_last('overlapped' if overlap else False, full=(a.steps - 1) % TIMED_EVERY == 0)
     recording[0] = False
     # the other pipeline, OVL_STEPS steps (untimed for `value`)
@@ -1145,6 +1187,8 @@ def main():
             line['cpu_baseline'] = cpu
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(line) + '\n').encode())
+        if last_out is not None:
+            dump_outputs(a.dump_outputs, last_out)
         if not (same and chained) or checks.get('gathered_search_equals_unsharded') is False \
                 or checks.get('all_ranks_replay_ok') is False:
             sys.exit('bench: a result check failed: ' + json.dumps(checks))
