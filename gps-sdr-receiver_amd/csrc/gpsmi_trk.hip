@@ -1479,9 +1479,14 @@ static int trk_build(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk* h) {
         {"done_by_dispatch", h->done_by_dispatch}, {"corr_overlap", h->corr_overlap},
         {"stream_thread", h->stream_thread}, {"stream_depth", h->stream_depth}, {"fold_chunk", h->fold_chunk},
         {"epilogue_form", h->epilogue_form}};
+    // A default the handle refuses (out of range, or "corr_overlap" on the general path) is ignored,
+    // and so is the error text of that refusal: the caller's last error stays what it was.
+    char prev_err[512];
+    snprintf(prev_err, sizeof(prev_err), "%s", last_error_buf());
     for (const auto& t : tun) {
         default_opt(t.key, &v, t.fallback);
-        if (v != t.fallback) (void)gpsmi_trk_set_option(h, t.key, v);   // (an out-of-range default is ignored)
+        if (v != t.fallback && gpsmi_trk_set_option(h, t.key, v) != GPSMI_OK)
+            snprintf(last_error_buf(), 512, "%s", prev_err);
     }
     long long s1 = h->corr_small1, s2 = h->corr_small2;                 // (a pair: taken together)
     default_opt("corr_small1", &s1, s1);
@@ -2137,6 +2142,12 @@ int gpsmi_trk_set_option(gpsmi_trk* h, const char* key, long long value) {
     } else if (!strcmp(key, "done_by_dispatch")) {
         h->done_by_dispatch = value != 0;
     } else if (!strcmp(key, "corr_overlap")) {
+        // The general path (CODE_SAMPLES != 2048) keeps its fold / pfa_corr / stats scratch once per
+        // handle, not per result slot: two batches in flight on two streams would overwrite each
+        // other's intermediates.
+        if (value != 0 && h->general)
+            return fail(GPSMI_E_STATE, "gpsmi_trk_set_option: corr_overlap needs CODE_SAMPLES = %d "
+                        "(the general path's scratch is per handle)", kFftN);
         h->corr_overlap = value != 0;
     } else if (!strcmp(key, "fold_chunk")) {
         if (value < 0 || value > (1 << 20)) return bad();

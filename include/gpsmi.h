@@ -97,7 +97,10 @@ int gpsmi_abi_sizeof(int which);
  *                       four-wave workgroups).  Same bits; DESIGN.md 4.5
  *   "corr_overlap"      1: gpsmi_trk_replay_run_async queues a batch's code-phase correlation on a
  *                       second stream, so that it runs beside the previous batch's correlator
- *                       (throughput mode; 0, the default, keeps every kernel alone on the chip)
+ *                       (throughput mode; 0, the default, keeps every kernel alone on the chip).
+ *                       CODE_SAMPLES = 2048 only: a handle of the general path keeps its
+ *                       correlation scratch once per handle, refuses 1 with GPSMI_E_STATE and
+ *                       ignores a default of 1 (the option reads 0)
  *   "stream_thread"     1 (default): the launches of a gpsmi_trk_process_stream step are made by a
  *                       submission thread of the handle while the caller prepares its next block
  *                       (they cost as much host time as the step takes on the GPU); 0: by the caller
@@ -315,8 +318,9 @@ int gpsmi_trk_set_streams(gpsmi_trk* h, int n_streams);
  * GPSMI_IQ_C64).  GPSMI_IQ_U8: the raw recording format of streamData (gpsrecv.py:162-173),
  * uint16 (Q << 8 | I) per sample, 2 bytes instead of 8 over PCIe and from HBM; the kernels
  * that read IQ decode on load, bit for bit what gpsmi_dev_unpack_u8iq writes, so every
- * output equals the complex64 path's.  CODE_SAMPLES = 2048 and N_CYC = 32 only
- * (GPSMI_E_UNSUPPORTED otherwise); block sizes are still counted in samples.           */
+ * output equals the complex64 path's.  CODE_SAMPLES = 2048 with the span correlator only
+ * (N_CYC = 32, 16 or 8; GPSMI_E_UNSUPPORTED otherwise); block sizes are still counted in
+ * samples.                                                                             */
 int gpsmi_trk_set_input_format(gpsmi_trk* h, int fmt);
 
 /* Replay (open loop): nb blocks resident in device memory, the state at the

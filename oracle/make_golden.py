@@ -10,9 +10,11 @@ under ``tests/golden/``.  Inputs are NOT stored: the scene is regenerated from
 its seed, and a sha256 of the raw IQ is stored so that generator drift is
 detected.
 
-    python oracle/make_golden.py            # all fixtures (two sub-processes)
+    python oracle/make_golden.py            # all fixtures (one sub-process each)
     python oracle/make_golden.py default    # CODE_SAMPLES=2048,  N_CYC=32
     python oracle/make_golden.py hirate     # CODE_SAMPLES=16368, N_CYC=8
+    python oracle/make_golden.py ncyc16     # CODE_SAMPLES=2048,  N_CYC=16
+    python oracle/make_golden.py ncyc8      # CODE_SAMPLES=2048,  N_CYC=8
     python oracle/make_golden.py navbits    # Subframe / evalGpsBits on constructed frames
     python oracle/make_golden.py position   # SatOrbit / SatPos / leastSquaresPos4 / ecefToGeo
     python oracle/make_golden.py resweep    # SatStream.initSweep / sweepFrequency / restoreFreq
@@ -51,11 +53,20 @@ def _import_reference(code_samples, n_cyc):
     return gpsglob, gpslib, gpsrecv
 
 
+# (CODE_SAMPLES, N_CYC) of each tracking fixture
+CONFIGS = {'default': (2048, 32), 'hirate': (16368, 8),
+           'ncyc16': (2048, 16), 'ncyc8': (2048, 8)}
+
+
 def scene_for(config):
     """The fixture scenes; tests rebuild them with the same call."""
     from gpsmi import synth
     if config == 'default':
         return synth.default_scene(12, seed=7, code_samples=2048, n_cyc=32)
+    if config == 'ncyc16':
+        return synth.default_scene(12, seed=23, code_samples=2048, n_cyc=16)
+    if config == 'ncyc8':
+        return synth.default_scene(12, seed=29, code_samples=2048, n_cyc=8)
     return synth.default_scene(12, seed=11, code_samples=16368, n_cyc=8)
 
 
@@ -87,13 +98,14 @@ def ref_table(gpsrecv, np, data, freqs, prns, n_avg, cs):
 
 def run(config):
     import numpy as np
-    cs, n_cyc = (2048, 32) if config == 'default' else (16368, 8)
+    cs, n_cyc = CONFIGS[config]
     gpsglob, gpslib, gpsrecv = _import_reference(cs, n_cyc)
     ngps = cs * n_cyc
     scene = scene_for(config)
     out = {'numpy': np.__version__, 'code_samples': cs, 'n_cyc': n_cyc}
     n_acq_blocks = 5
-    n_trk_blocks = 48 if config == 'default' else 40
+    # ncyc16 / ncyc8 track the same 1.536 s as default (48 x 32 ms)
+    n_trk_blocks = {'default': 48, 'hirate': 40}.get(config, 1536 // n_cyc)
     blocks = [scene.block(b) for b in range(n_acq_blocks + n_trk_blocks)]
     h = hashlib.sha256()
     for b in range(n_acq_blocks + n_trk_blocks):
@@ -117,7 +129,7 @@ def run(config):
     out['sweep_calls'] = np.array(calls, dtype=np.float64)
     out['sweep_found'] = np.array(found, dtype=np.float64)   # norm, sv, f, delay
 
-    # full surfaces
+    # full surfaces (they do not depend on N_CYC: ncyc16 / ncyc8 skip them)
     if config == 'default':
         prn31 = list(range(2, 33))
         f50 = [gpsglob.MIN_FREQ + gpsglob.STEP_FREQ * i for i in range(50)]
@@ -134,7 +146,7 @@ def run(config):
         for k, v in ref_table(gpsrecv, np, blocks[0], f201, prn32, 10,
                               cs).items():
             out[f'cfg4_{k}'] = v
-    else:
+    elif config == 'hirate':
         prn32 = list(range(1, 33))
         f41 = [-5000.0 + 250.0 * i for i in range(41)]
         for k, v in ref_table(gpsrecv, np, blocks[0], f41, prn32, 1, cs).items():
@@ -631,6 +643,6 @@ if __name__ == '__main__':
         subprocess.check_call([sys.executable, os.path.abspath(__file__), 'position'])
         subprocess.check_call([sys.executable, os.path.abspath(__file__), 'resweep'])
         subprocess.check_call([sys.executable, os.path.abspath(__file__), 'handoff'])
-        for cfg in ('default', 'hirate'):
+        for cfg in ('default', 'hirate', 'ncyc16', 'ncyc8'):
             subprocess.check_call([sys.executable, os.path.abspath(__file__),
                                    cfg])

@@ -127,7 +127,7 @@ def test_unpack_formula_matches_numpy_for_all_bytes():
     assert np.array_equal(ref.imag, v[::-1].astype(np.float32) * scl - np.float32(1))
 
 
-@pytest.mark.parametrize('nblocks', [1, 7, 8, 9, 1024])
+@pytest.mark.parametrize('nblocks', [1, 7, 8, 9, 1024, 2048, 4095, 4096])
 @pytest.mark.parametrize('ng', [1, 3, 12])
 def test_codephase_correlation_workgroup_map(nblocks, ng):
     """csrc/gpsmi_wgmap.h through gpsmi_trk_corr_grid / gpsmi_trk_corr_wg_map (the function the

@@ -199,6 +199,31 @@ def test_hirate_sweep_all_sats_loop(acq_hirate, golden_hirate):
     np.testing.assert_allclose(mine[:, 0], ref[:, 0], rtol=RTOL)
 
 
+@pytest.mark.parametrize('cfg', ['ncyc16', 'ncyc8'])
+def test_other_block_length_sweep_all_sats_loop(cfg):
+    """The first-hit loop at N_CYC = 16 and 8 (CODE_SAMPLES = 2048) on the scenes of
+    ref_ncyc16.npz / ref_ncyc8.npz: the same calls and the same (SV, Doppler, delay) list."""
+    from gpsmi.acquisition import Acquisition
+    from gpsmi.engine import Config
+    from test_oracle import CFG, ncyc_blocks, ncyc_golden
+    g = ncyc_golden(cfg)
+    acq = Acquisition(Config(**CFG[cfg]))
+    sat_lst, found, freq = list(range(2, 33)), [], acq.cfg.min_freq
+    blocks = ncyc_blocks(cfg, 0, 5)
+    try:
+        for b in range(5):
+            ready, freq, found = acq.sweepAllSats(blocks[b], freq, sat_lst, found,
+                                                  itSweep=acq.cfg.it_sweep_all)
+            assert (float(ready), freq, len(found)) == tuple(g['sweep_calls'][b])
+    finally:
+        acq.engine.close()
+    mine = np.array(found, dtype=np.float64)
+    ref = g['sweep_found']
+    assert np.array_equal(mine[:, 1:], ref[:, 1:])
+    np.testing.assert_allclose(mine[:, 0], ref[:, 0], rtol=RTOL)
+    assert len(sat_lst) == 31 - len(found)
+
+
 def test_rccl_gather_of_peak_records_single_rank(acq, golden_default):
     """The multi-GPU exchange with a world of one: unique id -> communicator -> a search that
     leaves its peak records in device memory -> gpsmi_comm_allgather_peaks (RCCL all-gather

@@ -10,21 +10,38 @@ pytestmark = pytest.mark.gpu
 
 
 def test_pool_flow_matches_reference(golden_default):
+    nb = golden_default['trk_delay'].shape[1]
+    _pool_flow(golden_default, scene_blocks('default', 5, nb), 32)
+
+
+@pytest.mark.parametrize('n_cyc', [16, 8])
+def test_pool_flow_matches_reference_other_block_lengths(n_cyc):
+    """N_CYC = 16 and 8 (CODE_SAMPLES = 2048) on ref_ncyc16.npz / ref_ncyc8.npz, whose scenes
+    test_oracle.ncyc_scene builds."""
+    from test_oracle import ncyc_blocks, ncyc_golden
+    g = ncyc_golden(f'ncyc{n_cyc}')
+    _pool_flow(g, ncyc_blocks(f'ncyc{n_cyc}', 5, g['trk_delay'].shape[1]), n_cyc)
+
+
+def _pool_flow(g, blocks, n_cyc):
     from gpsmi import receiver as R
-    g = golden_default
+    from gpsmi.engine import Config
+    cfg = Config(n_cyc=n_cyc)
     nch, nb = g['trk_delay'].shape
     found = [tuple(r) for r in g['sweep_found']]
     found = [(n, int(s), f, int(d)) for n, s, f, d in found]
-    pool, pool_no, worker = R.initMultiProcPool(nch)
+    pool, pool_no, worker = R.initMultiProcPool(nch, cfg)
     act = set()
     new = {s for _, s, _, _ in found[:nch]}
     worker, act = R.initPoolStreams(pool, pool_no, worker, act, set(new), found)
     assert act == new and sorted(worker) == sorted(new)
     init_sv = [int(s) for s in g['trk_init'][:, 0]]
-    blocks = scene_blocks('default', 5, nb)
+    ngps = cfg.ngps
+    no_sec = 1024 // n_cyc                      # report blocks: streamNo % NO_SEC == 0
+    n_reports = 0
     co_ph = {s: [] for s in act}
     for i in range(nb):
-        smp = np.int64((5 + i + 1) * 65536)
+        smp = np.int64((5 + i + 1) * ngps)
         res = R.satCalc(act, pool, worker, blocks[i], smp)
         assert len(res) == nch
         for sw, sat, frames, cp, (cq, cl) in res:
@@ -40,18 +57,20 @@ def test_pool_flow_matches_reference(golden_default):
             hc = pool.chan[worker.index(sat)]
             assert hc.MS_TIME == g['trk_ms_time'][c, i], (c, i)
             assert len(hc.EDGES) == g['trk_n_edges'][c, i], (c, i)
-            if (smp // 65536) % 32 == 0:
+            if (smp // ngps) % no_sec == 0:
+                n_reports += 1
                 assert len(frames) == 1 and frames[0]['SAT'] == sat
                 assert abs(frames[0]['FRQ'] - g['trk_freq'][c, i - 1]) < 0.05
                 assert abs(frames[0]['AMP'] - g['trk_amplitude'][c, i]) < 2e-2
             else:
                 assert frames == []
             co_ph[sat].append(cp)
+    assert n_reports == nch                     # one report block in the 1.536 s
     # drop two satellites, as getNewSats would ask
     drop = set(list(act)[:2])
     worker, act = R.delPoolStreams(pool, pool_no, worker, act, drop)
     assert len(act) == nch - 2 and worker.count(0) == 2
-    res = R.satCalc(act, pool, worker, blocks[0], np.int64((5 + nb + 1) * 65536))
+    res = R.satCalc(act, pool, worker, blocks[0], np.int64((5 + nb + 1) * ngps))
     assert {r[1] for r in res} == act
     R.closeMultiProcPool(pool)
 

@@ -23,12 +23,13 @@ def _open_all(eng, g):
     return len(g['trk_init'])
 
 
-def _run_closed_loop(g, config, cfg=None):
+def _run_closed_loop(g, config, cfg=None, blocks=None):
     from gpsmi.engine import TrkEngine, STATE_DTYPE
     nch, nb = g['trk_delay'].shape
     eng = TrkEngine(cfg, max_ch=nch)
     _open_all(eng, g)
-    blocks = scene_blocks(config, 5, nb)
+    if blocks is None:
+        blocks = scene_blocks(config, 5, nb)
     outs, states = [], []
     for i in range(nb):
         st = np.zeros(nch, dtype=STATE_DTYPE)
@@ -78,6 +79,106 @@ def test_hirate_replay_reproduces_closed_loop(closed_loop_hirate):
     buf.free()
     assert rep.tobytes() == outs.tobytes()
     assert rep2.tobytes() == outs[:6].tobytes()
+
+
+def _closed_loop_ncyc(cfg):
+    """N_CYC = 16 / 8 at CODE_SAMPLES = 2048 against their reference fixtures (ref_ncyc16.npz,
+    ref_ncyc8.npz; scenes of test_oracle.ncyc_scene): the span correlator's NC = 16 / 8."""
+    from gpsmi.engine import Config
+    from test_oracle import CFG, ncyc_blocks, ncyc_golden
+    g = ncyc_golden(cfg)
+    nb = g['trk_delay'].shape[1]
+    r = _run_closed_loop(g, cfg, Config(**CFG[cfg]), ncyc_blocks(cfg, 5, nb))
+    assert r[0].get_option('correlator') == 1                  # the matrix-pipe (span) form
+    return g, r
+
+
+@pytest.fixture(scope='module')
+def closed_loop_ncyc16():
+    g, r = _closed_loop_ncyc('ncyc16')
+    yield g, r
+    r[0].close()
+
+
+@pytest.fixture(scope='module')
+def closed_loop_ncyc8():
+    g, r = _closed_loop_ncyc('ncyc8')
+    yield g, r
+    r[0].close()
+
+
+NCYC_CFGS = ('ncyc16', 'ncyc8')
+
+
+@pytest.mark.parametrize('cfg', NCYC_CFGS)
+def test_other_block_length_closed_loop_matches_reference(request, cfg):
+    g, (_, outs, _, _) = request.getfixturevalue(f'closed_loop_{cfg}')
+    assert outs.shape == g['trk_delay'].shape[::-1]
+    _check_closed_loop(outs, g)
+
+
+def _tiled_replay_rows(eng, nb, nch, span_ch=12):
+    """Block rows of a replay tiled from nb recorded blocks until the launch is past
+    span_single_max, the size up to which the span correlator takes its single-block form."""
+    units = (nch + span_ch - 1) // span_ch
+    reps = eng.get_option('span_single_max') // (nb * units) + 1
+    rows = np.arange(reps * nb) % nb
+    assert len(rows) * units > eng.get_option('span_single_max')
+    return rows
+
+
+@pytest.mark.parametrize('cfg', NCYC_CFGS)
+def test_other_block_length_replay_reproduces_closed_loop(request, cfg):
+    """Replay of the recorded trajectory, tiled into one launch past span_single_max (the batch
+    form of the span correlator and the batch epilogue), and its first six blocks (single-block
+    form): bytewise the closed loop's outputs; the end-of-block states equal the next row."""
+    from gpsmi.engine import DeviceBuffer
+    _, (eng, outs, states, blocks) = request.getfixturevalue(f'closed_loop_{cfg}')
+    nb, nch = outs.shape
+    rows = _tiled_replay_rows(eng, nb, nch)
+    buf = DeviceBuffer(len(rows) * blocks[0].nbytes)
+    for i, r in enumerate(rows):
+        buf.upload(blocks[r], i * blocks[0].nbytes)
+    rep = eng.replay(buf.ptr, len(rows), states[rows], outs['delay_used'][rows])
+    nxt = eng.replay_states(len(rows))
+    rep6 = eng.replay(buf.ptr, 6, states[:6], None)
+    buf.free()
+    for t in range(len(rows) // nb):
+        assert rep[t * nb:(t + 1) * nb].tobytes() == outs.tobytes(), t
+    assert rep6.tobytes() == outs[:6].tobytes()
+    for k in ('prn', 'delay', 'freq', 'phase', 'phase_locked', 'nps', 'prev_sum_re', 'prev_sum_im',
+              'df_len', 'omega0', 'edge_state', 'prev_signal', 'std_dev'):
+        assert nxt[:nb - 1][k].tobytes() == states[1:][k].tobytes(), k
+    for i in range(nb - 1):
+        for c in range(nch):
+            n = int(states[i + 1, c]['df_len'])
+            assert nxt[i, c]['df'][:n].tobytes() == states[i + 1, c]['df'][:n].tobytes()
+
+
+@pytest.mark.parametrize('cfg', NCYC_CFGS)
+def test_other_block_length_raw_u8_equals_complex64(request, cfg):
+    """Raw uint16 blocks of the fixture scene through the closed loop and through the tiled
+    replay: bytewise the complex64 closed loop's outputs."""
+    from gpsmi.engine import Config, TrkEngine, DeviceBuffer
+    from test_oracle import CFG, ncyc_scene
+    g, (eng, outs, states, _) = request.getfixturevalue(f'closed_loop_{cfg}')
+    nb, nch = outs.shape
+    sc = ncyc_scene(cfg)
+    raw = [sc.block_raw(5 + i) for i in range(nb)]
+    e8 = TrkEngine(Config(**CFG[cfg]), max_ch=nch)
+    e8.set_input_format(True)
+    _open_all(e8, g)
+    got = np.array([e8.process(raw[i]) for i in range(nb)])
+    assert got.tobytes() == outs.tobytes()
+    rows = _tiled_replay_rows(e8, nb, nch)
+    buf = DeviceBuffer(len(rows) * raw[0].nbytes)
+    for i, r in enumerate(rows):
+        buf.upload(raw[r], i * raw[0].nbytes)
+    rep = e8.replay(buf.ptr, len(rows), states[rows], outs['delay_used'][rows])
+    buf.free()
+    e8.close()
+    for t in range(len(rows) // nb):
+        assert rep[t * nb:(t + 1) * nb].tobytes() == outs.tobytes(), t
 
 
 def _check_closed_loop(outs, g):
@@ -503,8 +604,21 @@ def test_overlapped_pipelines_return_the_isolated_results(closed_loop, mode):
     IQ in a mixed order, the batch
     kernels forced (span_single_max = 1), timing modes mixed: every read-back equals the blocking
     replay of the same input on a fresh handle; then back to the isolated pipeline on the same handle."""
-    from gpsmi.engine import TrkEngine, DeviceBuffer, PinnedArray, OUT_DTYPE
+    _overlapped_vs_isolated(closed_loop, mode, 32)
+
+
+@pytest.mark.parametrize('n_cyc', [16, 8])
+def test_overlapped_pipelines_return_the_isolated_results_other_block_lengths(request, n_cyc):
+    """The same at N_CYC = 16 and 8 (CODE_SAMPLES = 2048): every buffer of these paths is per
+    result slot too."""
+    _, r = request.getfixturevalue(f'closed_loop_ncyc{n_cyc}')
+    _overlapped_vs_isolated(r, 1, n_cyc)
+
+
+def _overlapped_vs_isolated(closed_loop, mode, n_cyc):
+    from gpsmi.engine import Config, TrkEngine, DeviceBuffer, PinnedArray, OUT_DTYPE
     _, outs, states, blocks = closed_loop
+    cfg = Config(n_cyc=n_cyc)
     nch = outs.shape[1]
     nb = 20
     bufs = []
@@ -514,12 +628,12 @@ def test_overlapped_pipelines_return_the_isolated_results(closed_loop, mode):
             buf.upload(blocks[first + i], i * blocks[0].nbytes)
         bufs.append(buf)
     table, forced = states[:nb], outs['delay_used'][:nb]
-    ref_eng = TrkEngine(max_ch=nch)
+    ref_eng = TrkEngine(cfg, max_ch=nch)
     ref_eng.set_option('span_single_max', 1)
     want = [ref_eng.replay(b.ptr, nb, table, forced).tobytes() for b in bufs]
     ref_eng.close()
     assert want[0] != want[1]
-    eng = TrkEngine(max_ch=nch)
+    eng = TrkEngine(cfg, max_ch=nch)
     eng.set_option('span_single_max', 1)
     eng.replay_load(nb, table, forced)
     pins = [PinnedArray((nb, nch), OUT_DTYPE) for _ in range(2)]
@@ -548,6 +662,37 @@ def test_overlapped_pipelines_return_the_isolated_results(closed_loop, mode):
         b.free()
     for p_ in pins:
         p_.free()
+
+
+def test_corr_overlap_is_refused_where_scratch_is_per_handle():
+    """The general path (CODE_SAMPLES != 2048) keeps its fold / correlation / statistics scratch
+    once per handle, so two batches in flight would overwrite each other's intermediates: a
+    16368 handle refuses corr_overlap = 1 (GPSMI_E_STATE) and a default of 1 does not reach it,
+    without leaving an error text behind; a 2048 handle takes both."""
+    from gpsmi import _lib
+    from gpsmi import engine as E
+    from gpsmi.engine import Config, EngineError, TrkEngine
+    hr = TrkEngine(Config(code_samples=16368, n_cyc=8), max_ch=2)
+    with pytest.raises(EngineError, match='corr_overlap'):
+        hr.set_option('corr_overlap', 1)
+    assert hr.get_option('corr_overlap') == 0
+    hr.set_option('corr_overlap', 0)                     # (0 is always taken)
+    hr.close()
+    lib = _lib.load()
+    E.set_default('corr_overlap', 1)
+    try:
+        assert lib.gpsmi_set_default(b'no_such_option', 1) != 0   # a known last error first
+        before = lib.gpsmi_last_error()
+        assert b'no_such_option' in before
+        hr = TrkEngine(Config(code_samples=16368, n_cyc=8), max_ch=2)
+        assert lib.gpsmi_last_error() == before          # the refused default leaves no error text
+        ok = TrkEngine(Config(n_cyc=8), max_ch=2)
+    finally:
+        E.clear_default('corr_overlap')
+    assert hr.get_option('corr_overlap') == 0
+    assert ok.get_option('corr_overlap') == 1
+    hr.close()
+    ok.close()
 
 
 def test_search_ordered_behind_replay_batches(closed_loop):

@@ -7,20 +7,67 @@ import numpy as np
 import pytest
 
 import gps_oracle as orc
-from conftest import scene_blocks, scene_for
+from conftest import load_golden, scene_blocks, scene_for
 
 CFG = {'default': dict(code_samples=2048, n_cyc=32),
-       'hirate': dict(code_samples=16368, n_cyc=8)}
+       'hirate': dict(code_samples=16368, n_cyc=8),
+       'ncyc16': dict(code_samples=2048, n_cyc=16),
+       'ncyc8': dict(code_samples=2048, n_cyc=8)}
+
+# The N_CYC = 16 / 8 fixtures at CODE_SAMPLES = 2048 (ref_ncyc16.npz, ref_ncyc8.npz).
+# conftest.scene_for maps every config but 'default' to the hirate scene, so their
+# scenes are built here, with the same calls as oracle/make_golden.py:scene_for;
+# test_scene_generator_is_stable catches any drift.
+NCYC_CFGS = ('ncyc16', 'ncyc8')
+_NCYC_SEED = {'ncyc16': 23, 'ncyc8': 29}
+_NCYC_BLOCKS = {}
+
+
+def ncyc_scene(cfg):
+    from gpsmi import synth
+    return synth.default_scene(12, seed=_NCYC_SEED[cfg], code_samples=2048,
+                               n_cyc=CFG[cfg]['n_cyc'])
+
+
+def ncyc_golden(cfg):
+    return load_golden(f'ref_{cfg}.npz')
+
+
+def ncyc_blocks(cfg, first, count):
+    """complex64 blocks [first, first+count) of an N_CYC 16 / 8 fixture scene (memoised)."""
+    sc = None
+    out = []
+    for b in range(first, first + count):
+        if (cfg, b) not in _NCYC_BLOCKS:
+            sc = sc or ncyc_scene(cfg)
+            _NCYC_BLOCKS[cfg, b] = sc.block(b)
+        out.append(_NCYC_BLOCKS[cfg, b])
+    return out
 
 
 def _golden(cfg, golden_default, golden_hirate):
+    if cfg in NCYC_CFGS:
+        return ncyc_golden(cfg)
     return golden_default if cfg == 'default' else golden_hirate
 
 
-@pytest.mark.parametrize('cfg', ['default', 'hirate'])
+def _scene(cfg):
+    return ncyc_scene(cfg) if cfg in NCYC_CFGS else scene_for(cfg)
+
+
+def _blocks(cfg, first, count):
+    if cfg in NCYC_CFGS:
+        return ncyc_blocks(cfg, first, count)
+    return scene_blocks(cfg, first, count)
+
+
+ALL_CFGS = ['default', 'hirate', *NCYC_CFGS]
+
+
+@pytest.mark.parametrize('cfg', ALL_CFGS)
 def test_scene_generator_is_stable(cfg, golden_default, golden_hirate):
     g = _golden(cfg, golden_default, golden_hirate)
-    sc = scene_for(cfg)
+    sc = _scene(cfg)
     n = 5 + g['trk_delay'].shape[1]
     h = hashlib.sha256()
     for b in range(n):
@@ -28,7 +75,7 @@ def test_scene_generator_is_stable(cfg, golden_default, golden_hirate):
     assert h.hexdigest() == str(g['iq_sha256'])
 
 
-@pytest.mark.parametrize('cfg', ['default', 'hirate'])
+@pytest.mark.parametrize('cfg', ALL_CFGS)
 def test_sweep_all_sats_first_hit_loop(cfg, golden_default, golden_hirate):
     """gpsrecv.py:241-274 over 5 blocks with reference defaults."""
     g = _golden(cfg, golden_default, golden_hirate)
@@ -36,7 +83,7 @@ def test_sweep_all_sats_first_hit_loop(cfg, golden_default, golden_hirate):
     t = orc.sec_time(p)
     spectra = {s: orc.fft_cacode(s, p.code_samples) for s in range(2, 33)}
     sat_lst, found, freq = list(range(2, 33)), [], p.min_freq
-    blocks = scene_blocks(cfg, 0, 5)
+    blocks = _blocks(cfg, 0, 5)
     for b in range(5):
         ready, freq, found = orc.sweep_all_sats(blocks[b], freq, sat_lst, found,
                                                 p.it_sweep_all, p, spectra, t)
@@ -86,13 +133,13 @@ def test_acq_surface_cfg4(golden_default):
     _check_table(t, golden_default, 'cfg4_')
 
 
-@pytest.mark.parametrize('cfg', ['default', 'hirate'])
+@pytest.mark.parametrize('cfg', ALL_CFGS)
 def test_satstream_process(cfg, golden_default, golden_hirate):
     """gpslib.py:1141-1210 closed loop, every recorded quantity of every block."""
     g = _golden(cfg, golden_default, golden_hirate)
     p = orc.Params(**CFG[cfg])
     nch, nb = g['trk_delay'].shape
-    blocks = scene_blocks(cfg, 5, nb)
+    blocks = _blocks(cfg, 5, nb)
     for c in range(nch):
         sv, f0, d0 = g['trk_init'][c]
         ss = orc.SatStream(int(sv), float(f0), p, delay=int(d0))

@@ -4,6 +4,7 @@ list, millisecond counter, correlation-quality averages and report frames must
 come out exactly as gpslib.SatStream produced them (gpslib.py:1124-1138,
 :1331-1339, :1394-1398, :1421-1436, :1451-1492).  No GPU involved."""
 import numpy as np
+import pytest
 
 import gps_oracle as orc
 from gpsmi._lib import OUT_DTYPE
@@ -77,8 +78,17 @@ def _record(g, c, i):
 
 
 def test_host_channel_reproduces_reference_control_state(golden_default):
-    g = golden_default
-    cfg = Config()
+    _host_channel_control_state(golden_default, Config())
+
+
+@pytest.mark.parametrize('n_cyc', [16, 8])
+def test_host_channel_reproduces_reference_control_state_other_block_lengths(n_cyc):
+    """N_CYC = 16 and 8 at CODE_SAMPLES = 2048 (ref_ncyc16.npz / ref_ncyc8.npz)."""
+    from test_oracle import ncyc_golden
+    _host_channel_control_state(ncyc_golden(f'ncyc{n_cyc}'), Config(n_cyc=n_cyc))
+
+
+def _host_channel_control_state(g, cfg):
     nch, nb = g['trk_delay'].shape
     frames_ref = eval(str(g['trk_frames_repr']), {'np': np})
     for c in range(nch):
