@@ -14,6 +14,9 @@
 //                         (findCodePhase, :217-223) by wave64 shuffles.  The
 //                         nbins x nsv x 2048 correlation surface never reaches
 //                         HBM; 16 bytes per cell do.
+//   acq_spectrum_nc_kernel, acq_nc_corr_kernel, acq_fold_nc_kernel + pfa_corr_kernel<2>
+//                         the non-coherent search (gpsmi_acq_search_nc): the
+//                         mean of |corr| over n_seg segments, summed in registers per cell.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -160,6 +163,140 @@ __global__ void acq_peaks_kernel(const DirStats* __restrict__ st, gpsmi_peak* __
     if (nbr) nbr[c] = make_float2(st[c].lo, st[c].hi);
 }
 
+// ---- non-coherent search (gpsmi_acq_search_nc) ------------------------------
+// Segment s of a bin is acq_spectrum_kernel's fold on iq advanced by s * n_coh * 2048 samples (the
+// wipe-off restarts at phase 0 and SEC_TIME[0] in every segment).  Grid (bins, segments); the
+// spectrum of (bin b, segment s) goes to spectra[(b * nseg + s) * 2048].  The arithmetic per
+// workgroup is acq_spectrum_kernel's, operation for operation.
+template <int G, int FMT>
+__global__ __launch_bounds__(256 * G) void acq_spectrum_nc_kernel(
+    const void* __restrict__ iq, const float* __restrict__ t32,
+    const float* __restrict__ omega, int n_coh, int nseg, float2* __restrict__ spectra,
+    const float2* __restrict__ tw) {
+    __shared__ __attribute__((aligned(16))) float lds[kFftLdsFloats];
+    __shared__ __attribute__((aligned(16))) float lds_tw[kFftTwFloats];
+    __shared__ float2 part[G > 1 ? G - 1 : 1][G > 1 ? kFftN : 1];
+    const int t = threadIdx.x & 255, grp = threadIdx.x >> 8, bin = blockIdx.x, seg = blockIdx.y;
+    const FftTw ftw = fft_setup(lds_tw, tw, t);
+    const float om = omega[bin];
+    const size_t base = (size_t)seg * n_coh * kFftN;
+    float2 v[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) v[r] = make_float2(0.f, 0.f);
+    for (int i = grp; i < n_coh; i += G) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            int k = i * kFftN + t + 256 * r;
+            float2 x = load_iq<FMT>(iq, base + k);
+            float p = mul_rn(om, t32[k]);
+            float s, c;
+            sincosf(p, &s, &c);
+            v[r].x += c * x.x + s * x.y;
+            v[r].y += c * x.y - s * x.x;
+        }
+    }
+    if (G > 1) {
+        if (grp > 0) {
+#pragma unroll
+            for (int r = 0; r < 8; ++r) part[grp - 1][t + 256 * r] = v[r];
+        }
+        __syncthreads();
+        if (grp > 0) return;
+#pragma unroll
+        for (int g = 1; g < G; ++g)
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const float2 o = part[g - 1][t + 256 * r];
+                v[r].x += o.x; v[r].y += o.y;
+            }
+    }
+    __syncthreads();
+    fft2048(v, lds, ftw, t);
+    const float sc = 1.0f / (float)n_coh;
+    float2* out = spectra + ((size_t)bin * nseg + seg) * kFftN;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) out[t + 256 * q] = make_float2(v[q].x * sc, v[q].y * sc);
+}
+
+// One workgroup per (SV, bin): acq_corr_kernel's product, inverse transform and |.| for every
+// segment, the magnitudes summed in registers in ascending segment order, scaled by 1 / nseg, then
+// the statistics once.  The next segment's spectrum is requested before the current one is
+// transformed (the cells are latency-bound chains).  With nseg = 1 every operation
+// is acq_corr_kernel's (0 + m = m, m * 1 = m).  spectra: this launch's bins, [bin][nseg][2048];
+// out / nbr: [bin0 + bin][sv].
+__global__ __launch_bounds__(256) void acq_nc_corr_kernel(
+    const float2* __restrict__ spectra, const float2* __restrict__ rep,
+    const int* __restrict__ slot, gpsmi_peak* __restrict__ out, int nsv, int nseg, int bin0,
+    const float2* __restrict__ tw, float2* __restrict__ nbr) {
+    __shared__ __attribute__((aligned(16))) float lds[kFftLdsFloats];
+    __shared__ float red[kStatsRedFloats];
+    __shared__ __attribute__((aligned(16))) float lds_tw[kFftTwFloats];
+    float* magbuf = lds + 2 * kFftPlane;
+    const int t = threadIdx.x, sv = blockIdx.x, bin = blockIdx.y;
+    const FftTw ftw = fft_setup(lds_tw, tw, t);
+    const float2* X = spectra + (size_t)bin * nseg * kFftN;
+    const float2* R = rep + (size_t)slot[sv] * kFftN;
+    float2 r[8], x[8];
+    float acc[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        r[q] = R[t + 256 * q];
+        x[q] = X[t + 256 * q];
+        acc[q] = 0.f;
+    }
+#pragma unroll 1
+    for (int s = 0; s < nseg; ++s) {
+        float2 v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            v[q] = make_float2(x[q].x * r[q].x + x[q].y * r[q].y, x[q].x * r[q].y - x[q].y * r[q].x);
+        // the next segment (past the last one the last again, never used: no branch around the loads)
+        const float2* Xn = X + (size_t)(s + 1 < nseg ? s + 1 : s) * kFftN;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x[q] = Xn[t + 256 * q];
+        __syncthreads();                       // (the previous transform's last LDS reads are done)
+        fft2048(v, lds, ftw, t);
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            acc[q] += __builtin_amdgcn_sqrtf(v[q].x * v[q].x + v[q].y * v[q].y) * (1.0f / kFftN);
+    }
+    const float sc = 1.0f / (float)nseg;
+    float mag[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) mag[q] = acc[q] * sc;
+    int amax; float peak, mean, sd, lo, hi;
+    corr_stats8(mag, t, magbuf, red, amax, peak, mean, sd, lo, hi);
+    if (t == 0) {
+        const size_t c = (size_t)(bin0 + bin) * nsv + sv;
+        gpsmi_peak p; p.argmax = amax; p.peak = peak; p.mean = mean; p.std = sd;
+        out[c] = p;
+        if (nbr) nbr[c] = make_float2(lo, hi);
+    }
+}
+
+// Native 16368 path: the fold of segment s of a bin, acq_fold_kernel's arithmetic on iq advanced by
+// s * n_coh * L samples.  Grid (lag blocks, bins of this launch, segments); xout [bin][nseg][L].
+template <int FMT>
+__global__ __launch_bounds__(256) void acq_fold_nc_kernel(
+    const void* __restrict__ iq, const float* __restrict__ t32,
+    const float* __restrict__ omega, int n_coh, int nseg, int L, float2* __restrict__ xout) {
+    const int m = blockIdx.x * 256 + threadIdx.x, bin = blockIdx.y, seg = blockIdx.z;
+    if (m >= L) return;
+    const float om = omega[bin];
+    const size_t base = (size_t)seg * n_coh * L;
+    float ar = 0.f, ai = 0.f;
+    for (int i = 0; i < n_coh; ++i) {
+        const int k = i * L + m;
+        const float2 v = load_iq<FMT>(iq, base + k);
+        float sn, co;
+        sincosf(mul_rn(om, t32[k]), &sn, &co);
+        ar += co * v.x + sn * v.y;
+        ai += co * v.y - sn * v.x;
+    }
+    const float sc = 1.0f / (float)n_coh;
+    xout[((size_t)bin * nseg + seg) * L + m] = make_float2(ar * sc, ai * sc);
+}
+
 }  // namespace gpsmi
 
 using namespace gpsmi;
@@ -201,6 +338,9 @@ struct gpsmi_acq {
     // ... or natively in LDS when the code period is 16368 = 16 * 3 * 11 * 31 samples (gpsmi_pfa.h)
     bool pfa = false;
     float2* d_RSp = nullptr;                // [GPSMI_MAX_PRN + 1][16368] replica spectra, P3's order
+    // non-coherent search: the per-(bin, segment) spectra (CS = 2048) or folded samples (16368) of
+    // one chunk of bins, sized per call (gpsmi_acq_search_nc)
+    float2* d_nc = nullptr; size_t nc_cap = 0;
     int iq_fmt = GPSMI_IQ_C64;              // what the iq pointers of the search calls point to
     float last_ms = 0.f;
     bool pending = false;
@@ -319,7 +459,7 @@ int gpsmi_acq_destroy(gpsmi_acq* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* bufs[] = {h->d_tw, h->d_t32, h->d_rep, h->d_iq, h->d_spec, h->d_omega, h->d_slot,
                     h->d_peaks, h->d_nbr, h->d_rep_time, h->d_fold, h->d_mag, h->d_stats,
-                    h->d_xsel, h->d_rsel, h->d_twN, h->d_RS, h->d_S, h->d_RSp};
+                    h->d_xsel, h->d_rsel, h->d_twN, h->d_RS, h->d_S, h->d_RSp, h->d_nc};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (int k = 0; k < 2; ++k) {
@@ -365,6 +505,36 @@ int gpsmi_acq_set_replica(gpsmi_acq* h, int prn, const float* spectrum) {
     return GPSMI_OK;
 }
 
+// parameter uploads: the caller's arrays are consumed before this function returns
+// (copied into page-locked staging), the device copies are ordered on the stream
+static int acq_stage(gpsmi_acq* h, const int32_t* prn, int nsv, const double* freqs, int nbins) {
+    const int sg = h->stage ^= 1;
+    if (h->staged_used[sg]) GPSMI_HIP(hipEventSynchronize(h->staged[sg]));
+    for (int b = 0; b < nbins; ++b) h->h_om[sg][b] = (float)(2.0 * M_PI * freqs[b]);
+    for (int i = 0; i < nsv; ++i) h->h_slot[sg][i] = prn[i];
+    GPSMI_HIP(hipMemcpyAsync(h->d_omega, h->h_om[sg], nbins * sizeof(float), hipMemcpyHostToDevice,
+                             h->stream));
+    GPSMI_HIP(hipMemcpyAsync(h->d_slot, h->h_slot[sg], nsv * sizeof(int), hipMemcpyHostToDevice,
+                             h->stream));
+    GPSMI_HIP(hipEventRecord(h->staged[sg], h->stream));
+    h->staged_used[sg] = true;
+    return GPSMI_OK;
+}
+
+// the table of a search (and the neighbours) to where the caller wants it, behind the kernels
+static int acq_copy_out(gpsmi_acq* h, int nbins, int nsv, gpsmi_peak* out, void* out_dev, float* nbr) {
+    size_t bytes = (size_t)nbins * nsv * sizeof(gpsmi_peak);
+    if (out_dev)
+        GPSMI_HIP(hipMemcpyAsync(out_dev, h->d_peaks, bytes, hipMemcpyDeviceToDevice, h->stream));
+    if (out)
+        GPSMI_HIP(hipMemcpyAsync(out, h->d_peaks, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (nbr)
+        GPSMI_HIP(hipMemcpyAsync(nbr, h->d_nbr, (size_t)nbins * nsv * sizeof(float2),
+                                 hipMemcpyDeviceToHost, h->stream));
+    h->pending = true;
+    return GPSMI_OK;
+}
+
 static int acq_search_impl(gpsmi_acq* h, const void* d_iq, size_t n, const int32_t* prn, int nsv,
                            const double* freqs, int nbins, int n_avg, gpsmi_peak* out,
                            void* out_dev, float* nbr, bool wait = true) {
@@ -385,18 +555,8 @@ static int acq_search_impl(gpsmi_acq* h, const void* d_iq, size_t n, const int32
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     int rc = acq_reserve(h, nbins, nsv);
     if (rc) return rc;
-    // parameter uploads: the caller's arrays are consumed before this function returns
-    // (copied into page-locked staging), the device copies are ordered on the stream
-    const int sg = h->stage ^= 1;
-    if (h->staged_used[sg]) GPSMI_HIP(hipEventSynchronize(h->staged[sg]));
-    for (int b = 0; b < nbins; ++b) h->h_om[sg][b] = (float)(2.0 * M_PI * freqs[b]);
-    for (int i = 0; i < nsv; ++i) h->h_slot[sg][i] = prn[i];
-    GPSMI_HIP(hipMemcpyAsync(h->d_omega, h->h_om[sg], nbins * sizeof(float), hipMemcpyHostToDevice,
-                             h->stream));
-    GPSMI_HIP(hipMemcpyAsync(h->d_slot, h->h_slot[sg], nsv * sizeof(int), hipMemcpyHostToDevice,
-                             h->stream));
-    GPSMI_HIP(hipEventRecord(h->staged[sg], h->stream));
-    h->staged_used[sg] = true;
+    rc = acq_stage(h, prn, nsv, freqs, nbins);
+    if (rc) return rc;
     if (h->direct) {
         const size_t cells = (size_t)nbins * nsv;
         if ((size_t)nbins > h->dir_bins) {
@@ -464,16 +624,126 @@ static int acq_search_impl(gpsmi_acq* h, const void* d_iq, size_t n, const int32
     }
     GPSMI_HIP(hipGetLastError());
     GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
-    size_t bytes = (size_t)nbins * nsv * sizeof(gpsmi_peak);
-    if (out_dev)
-        GPSMI_HIP(hipMemcpyAsync(out_dev, h->d_peaks, bytes, hipMemcpyDeviceToDevice, h->stream));
-    if (out)
-        GPSMI_HIP(hipMemcpyAsync(out, h->d_peaks, bytes, hipMemcpyDeviceToHost, h->stream));
-    if (nbr)
-        GPSMI_HIP(hipMemcpyAsync(nbr, h->d_nbr, (size_t)nbins * nsv * sizeof(float2),
-                                 hipMemcpyDeviceToHost, h->stream));
-    h->pending = true;
-    if (!wait) return GPSMI_OK;
+    rc = acq_copy_out(h, nbins, nsv, out, out_dev, nbr);
+    if (rc || !wait) return rc;
+    return gpsmi_acq_wait(h);
+}
+
+// Device memory for the non-coherent search.  An allocation the device cannot serve is
+// GPSMI_E_NOMEM, and the handle stays usable (the buffer is simply absent until a later call).
+static int nc_grow(void** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return GPSMI_OK;
+    if (*p) GPSMI_HIP(hipFree(*p));
+    *p = nullptr; *cap = 0;
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return fail(GPSMI_E_NOMEM, "gpsmi_acq_search_nc: no device memory for %zu bytes of scratch", bytes);
+    }
+    if (e != hipSuccess)
+        return fail(GPSMI_E_HIP, "hipMalloc: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+    *cap = bytes;
+    return GPSMI_OK;
+}
+
+// Scratch of one chunk of bins of a non-coherent search: the spectra / folded samples of all its
+// segments.  Longer searches take the bins in chunks; the magnitude sums stay in registers.
+constexpr size_t kNcScratchMax = size_t(512) << 20;
+
+static int acq_search_nc_impl(gpsmi_acq* h, const void* d_iq, size_t n, const int32_t* prn, int nsv,
+                              const double* freqs, int nbins, int n_coh, int n_seg, gpsmi_peak* out,
+                              void* out_dev, float* nbr) {
+    GPSMI_REQUIRE(h && d_iq && prn && freqs, "null argument");
+    GPSMI_REQUIRE(out || out_dev, "no output requested");
+    GPSMI_REQUIRE(nsv >= 0 && nsv <= GPSMI_MAX_PRN, "nsv out of range");
+    GPSMI_REQUIRE(nbins >= 0 && nbins <= 65535, "nbins out of range");
+    GPSMI_REQUIRE(n_coh >= 1 && n_coh <= h->cfg.n_cyc, "n_coh out of range 1..n_cyc");
+    GPSMI_REQUIRE(n_seg >= 1 && n_seg <= 65535, "n_seg out of range 1..65535");
+    const int cs = h->cfg.code_samples;
+    GPSMI_REQUIRE(n / ((size_t)n_coh * cs) >= (size_t)n_seg, "iq shorter than n_seg * n_coh code periods");
+    for (int i = 0; i < nsv; ++i) {
+        GPSMI_REQUIRE(prn[i] >= 1 && prn[i] <= GPSMI_MAX_PRN, "prn out of range 1..37");
+        if (!(h->direct ? h->have_time[prn[i]] : h->have_rep[prn[i]]))
+            return fail(GPSMI_E_STATE, "no replica set for PRN %d", (int)prn[i]);
+    }
+    if (h->direct && !h->pfa)
+        return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_search_nc: code_samples 2048 or the native 16368 "
+                                         "correlation only (not the \"codephase\" time-domain paths)");
+    // one segment of the 16368 path: the coherent search itself (MODE 0 forms its statistics from the
+    // unscaled squares; MODE 2's would differ in the last bits of std)
+    if (h->pfa && n_seg == 1)
+        return acq_search_impl(h, d_iq, n, prn, nsv, freqs, nbins, n_coh, out, out_dev, nbr);
+    h->last_ms = 0.f;
+    if (nsv == 0 || nbins == 0) return GPSMI_OK;
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    int rc = acq_reserve(h, nbins, nsv);
+    if (rc) return rc;
+    const size_t per_bin = (size_t)n_seg * cs * sizeof(float2);
+    size_t nbc = kNcScratchMax / per_bin;
+    nbc = nbc < 1 ? 1 : nbc > (size_t)nbins ? (size_t)nbins : nbc;
+    rc = nc_grow((void**)&h->d_nc, &h->nc_cap, nbc * per_bin);
+    if (rc) return rc;
+    const size_t cells = (size_t)nbins * nsv;
+    if (h->pfa && cells > h->dir_cells) {
+        void* olds[] = {h->d_mag, h->d_stats, h->d_xsel, h->d_rsel};
+        for (void* p : olds)
+            if (p) GPSMI_HIP(hipFree(p));
+        h->d_mag = nullptr; h->d_stats = nullptr; h->d_xsel = h->d_rsel = nullptr;
+        h->dir_cells = 0;
+        size_t c0 = 0, c1 = 0, c2 = 0;
+        if ((rc = nc_grow((void**)&h->d_stats, &c0, cells * sizeof(DirStats))) ||
+            (rc = nc_grow((void**)&h->d_xsel, &c1, cells * sizeof(int))) ||
+            (rc = nc_grow((void**)&h->d_rsel, &c2, cells * sizeof(int))))
+            return rc;
+        h->dir_cells = cells;
+    }
+    rc = acq_stage(h, prn, nsv, freqs, nbins);
+    if (rc) return rc;
+    const bool u8 = h->iq_fmt == GPSMI_IQ_U8;
+    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
+    for (int b0 = 0; b0 < nbins; b0 += (int)nbc) {
+        const int nb = nbins - b0 < (int)nbc ? nbins - b0 : (int)nbc;
+        const float* om = h->d_omega + b0;
+        if (h->pfa) {
+            const dim3 grid((cs + 255) / 256, nb, n_seg);
+            if (u8)
+                hipLaunchKernelGGL(acq_fold_nc_kernel<1>, grid, dim3(256), 0, h->stream, d_iq, h->d_t32,
+                                   om, n_coh, n_seg, cs, h->d_nc);
+            else
+                hipLaunchKernelGGL(acq_fold_nc_kernel<0>, grid, dim3(256), 0, h->stream, d_iq, h->d_t32,
+                                   om, n_coh, n_seg, cs, h->d_nc);
+            const int c0 = b0 * nsv, ncc = nb * nsv;
+            hipLaunchKernelGGL(acq_cells_kernel, dim3((ncc + 255) / 256), dim3(256), 0, h->stream,
+                               h->d_xsel + c0, h->d_rsel + c0, h->d_slot, nsv, ncc);
+            pfa_nc_corr_launch(h->stream, h->d_nc, h->d_xsel + c0, h->d_rsel + c0, ncc, n_seg, h->d_RSp,
+                               h->d_stats + c0);
+        } else {
+            const dim3 grid(nb, n_seg);
+            if (n_coh >= 4 && u8)
+                hipLaunchKernelGGL((acq_spectrum_nc_kernel<4, 1>), grid, dim3(1024), 0, h->stream, d_iq,
+                                   h->d_t32, om, n_coh, n_seg, h->d_nc, h->d_tw);
+            else if (n_coh >= 4)
+                hipLaunchKernelGGL((acq_spectrum_nc_kernel<4, 0>), grid, dim3(1024), 0, h->stream, d_iq,
+                                   h->d_t32, om, n_coh, n_seg, h->d_nc, h->d_tw);
+            else if (u8)
+                hipLaunchKernelGGL((acq_spectrum_nc_kernel<1, 1>), grid, dim3(256), 0, h->stream, d_iq,
+                                   h->d_t32, om, n_coh, n_seg, h->d_nc, h->d_tw);
+            else
+                hipLaunchKernelGGL((acq_spectrum_nc_kernel<1, 0>), grid, dim3(256), 0, h->stream, d_iq,
+                                   h->d_t32, om, n_coh, n_seg, h->d_nc, h->d_tw);
+            hipLaunchKernelGGL(acq_nc_corr_kernel, dim3(nsv, nb), dim3(256), 0, h->stream, h->d_nc,
+                               h->d_rep, h->d_slot, h->d_peaks, nsv, n_seg, b0, h->d_tw,
+                               nbr ? h->d_nbr : nullptr);
+        }
+    }
+    if (h->pfa)
+        hipLaunchKernelGGL(acq_peaks_kernel, dim3(((int)cells + 255) / 256), dim3(256), 0, h->stream,
+                           h->d_stats, h->d_peaks, nbr ? h->d_nbr : nullptr, (int)cells);
+    GPSMI_HIP(hipGetLastError());
+    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
+    rc = acq_copy_out(h, nbins, nsv, out, out_dev, nbr);
+    if (rc) return rc;
     return gpsmi_acq_wait(h);
 }
 
@@ -521,6 +791,33 @@ int gpsmi_acq_search_ex(gpsmi_acq* h, const float* iq, size_t n, const int32_t* 
     GPSMI_HIP(hipMemcpyAsync(h->d_iq, iq, need * (h->iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)),
                              hipMemcpyHostToDevice, h->stream));
     return acq_search_impl(h, h->d_iq, need, prn, nsv, freqs, nbins, n_avg, out, nullptr, nbr);
+}
+
+int gpsmi_acq_search_nc_dev(gpsmi_acq* h, const void* d_iq, size_t n, const int32_t* prn, int nsv,
+                            const double* freqs_hz, int nbins, int n_coh, int n_seg, gpsmi_peak* out,
+                            void* out_dev) {
+    return acq_search_nc_impl(h, d_iq, n, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, out_dev, nullptr);
+}
+
+int gpsmi_acq_search_nc(gpsmi_acq* h, const void* iq, size_t n, const int32_t* prn, int nsv,
+                        const double* freqs_hz, int nbins, int n_coh, int n_seg, gpsmi_peak* out,
+                        float* nbr) {
+    GPSMI_REQUIRE(h && iq && out, "null argument");
+    GPSMI_REQUIRE(n_coh >= 1 && n_coh <= h->cfg.n_cyc, "n_coh out of range 1..n_cyc");
+    GPSMI_REQUIRE(n_seg >= 1 && n_seg <= 65535, "n_seg out of range 1..65535");
+    GPSMI_REQUIRE(n / ((size_t)n_coh * h->cfg.code_samples) >= (size_t)n_seg,
+                  "iq shorter than n_seg * n_coh code periods");
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    const size_t need = (size_t)n_seg * n_coh * h->cfg.code_samples;
+    if (need > h->iq_cap) {                  // (iq_cap counts complex64 samples)
+        size_t bytes = h->iq_cap * sizeof(float2);
+        const int rc = nc_grow((void**)&h->d_iq, &bytes, need * sizeof(float2));
+        h->iq_cap = h->d_iq ? need : 0;
+        if (rc) return rc;
+    }
+    GPSMI_HIP(hipMemcpyAsync(h->d_iq, iq, need * (h->iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)),
+                             hipMemcpyHostToDevice, h->stream));
+    return acq_search_nc_impl(h, h->d_iq, need, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, nullptr, nbr);
 }
 
 int gpsmi_acq_set_input_format(gpsmi_acq* h, int fmt) {

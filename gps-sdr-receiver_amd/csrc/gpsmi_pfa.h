@@ -199,6 +199,12 @@ __device__ __forceinline__ void pfa_slab33(fft_c* base) {
 //         cell c uses x[xsel[cell0 + c]] and the spectrum RS[rsel[cell0 + c]]; out[cell0 + c].
 // MODE 1: spectrum of the real replica rep[slot][L] into RS[slot] (P3's thread order:
 //         RS[slot][q * 528 + line], q the Z_31 frequency).
+// MODE 2: non-coherent search (gpsmi_acq_search_nc): cell0 is the segment count nseg and the cells of
+//         the launch are numbered from 0.  Cell c runs MODE 0's correlation on x[xsel[c] * nseg + s] for
+//         s = 0 .. nseg - 1; each thread sums the magnitudes of its 16 lags c + 1023 j over the segments
+//         in registers (ascending s), scales the sums by 1 / nseg, and the statistics run once, on
+//         them (the sum of squares then of the scaled values).  The next segment's samples are
+//         requested at the start of P5.
 template <int MODE>
 __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
     const float2* __restrict__ x, const float* __restrict__ rep, const int* __restrict__ xsel,
@@ -211,11 +217,20 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
     // take every gridDim-th cell; the samples of the next cell are requested before the statistics
     // of the current one, so only a workgroup's first cell waits for memory at its start
     int cell = MODE == 0 ? cell0 + (int)blockIdx.x : cell0;
-    const int cell_end = MODE == 0 ? cell0 + ncell : cell0 + 1;
+    int cell_end = MODE == 0 ? cell0 + ncell : cell0 + 1;
+    int seg = 0, nseg = 1;
+    float acc[16];
+    if constexpr (MODE == 2) {
+        nseg = cell0;
+        cell = (int)blockIdx.x;
+        cell_end = ncell;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+    }
     __shared__ fft_c tw16[16];                    // exp(+2 pi i m / 16)
     __shared__ fft_c trig31[31];                  // (cos, sin)(2 pi m / 31) for P3's split lines
     if (t < 16) tw16[t] = pfa_w16(t, false);
-    if (MODE == 0 && t >= 32 && t < 63) {
+    if (MODE != 1 && t >= 32 && t < 63) {
         float sn, cs;
         sincospif(2.0f * (float)(t - 32) / 31.0f, &sn, &cs);
         trig31[t - 32] = fft_c{cs, sn};
@@ -228,10 +243,11 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
     // (unconditional: past the last cell the last one is requested again and never used -- under a
     // condition the sixteen pairs would have to survive the whole loop body for the case that no
     // request overwrites them, and spill)
-    auto request = [&](int c) {
-        if (MODE == 0) {
-            c = c < cell_end ? c : cell_end - 1;
-            const int sel = __builtin_amdgcn_readfirstlane(xsel[c]);
+    auto request = [&](int c, int sg) {
+        if (MODE != 1) {
+            if (c >= cell_end) { c = cell_end - 1; sg = 0; }
+            const int sel = MODE == 2 ? __builtin_amdgcn_readfirstlane(xsel[c] * nseg + sg)
+                                      : __builtin_amdgcn_readfirstlane(xsel[c]);
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
                 const_cast<float2*>(x) + (size_t)sel * kPfaL, 0, kPfaL * (int)sizeof(float2), 0x00020000);
             const int voff = (t < kPfaC ? t : kPfaL) * (int)sizeof(float2);
@@ -265,7 +281,7 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
             }
         }
     };
-    request(cell);
+    request(cell, 0);
     PFA_STAMP(0);
     p1();
     // (the loop body starts behind P1: the samples requested for the next cell are live through P5
@@ -387,7 +403,37 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
     // per thread are requested right here and arrive under the reductions and barriers.
     float sm = 0.f, s2 = 0.f, bv = -1.f;
     int bi = 0x7fffffff;
-    if (t < kPfaC) {
+    if constexpr (MODE == 2) {
+        const bool last = seg + 1 == nseg;
+        request(last ? cell + (int)gridDim.x : cell, last ? 0 : seg + 1);
+        if (t < kPfaC) {
+            fft_c v[16];
+            v[0] = data[sig];
+#pragma unroll
+            for (int k = 1; k < 16; ++k) v[k] = cmulp(data[k * kPfaPitch + sig], tw16[(t * k) & 15]);
+            pfa_fft16(v);
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                acc[j] += __builtin_amdgcn_sqrtf(v[j].x * v[j].x + v[j].y * v[j].y) * (1.0f / kPfaL);
+        }
+        if (!last) {                            // (P1 writes only this thread's own slots, P5 read)
+            ++seg;
+            p1();
+            continue;
+        }
+        if (t < kPfaC) {
+            const float sc = 1.0f / (float)nseg;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const float m = acc[j] * sc;
+                acc[j] = 0.f;
+                sm += m;
+                s2 += m * m;
+                if (m > bv) { bv = m; bi = t + kPfaC * j; }
+                data[j * kPfaPitch + sig].x = m;
+            }
+        }
+    } else if (t < kPfaC) {
         fft_c v[16];
         v[0] = data[sig];
 #pragma unroll
@@ -404,7 +450,7 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
         }
     }
     PFA_STAMP(5);
-    request(cell + (MODE == 0 ? (int)gridDim.x : 1));
+    if constexpr (MODE != 2) request(cell + (MODE == 0 ? (int)gridDim.x : 1), 0);
     PFA_STAMP(8);
     sm = wave_sum_dpp(sm);
     s2 = wave_sum_dpp(s2);
@@ -435,7 +481,9 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
                 const double inv_l = 1.0 / (double)kPfaL;
                 // population variance from the two sums (the squares were summed unscaled)
                 const double mean = dsm * inv_l;
-                const double var = ds2 * (inv_l * inv_l * inv_l) - mean * mean;
+                // (MODE 2 summed the squares of the scaled values)
+                const double var = MODE == 2 ? ds2 * inv_l - mean * mean
+                                             : ds2 * (inv_l * inv_l * inv_l) - mean * mean;
                 DirStats r;
                 r.argmax = pi;
                 r.peak = pv;
@@ -450,7 +498,8 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
     PFA_STAMP(11);
     lds_barrier();                              // (the neighbours are read: the next cell may write `data`)
     PFA_STAMP(6);
-    cell += MODE == 0 ? (int)gridDim.x : 1;
+    cell += MODE != 1 ? (int)gridDim.x : 1;
+    seg = 0;
     if (cell >= cell_end) break;
     PFA_STAMP(0);
     p1();
@@ -467,6 +516,19 @@ inline void pfa_corr_launch(hipStream_t stream, const float2* x, const int* xsel
     const int grid = ncell < n_cu ? ncell : n_cu;
     hipLaunchKernelGGL(pfa_corr_kernel<0>, dim3(grid), dim3(kPfaThreads), 0, stream, x,
                        (const float*)nullptr, xsel, rsel, RS, cell0, ncell, stats);
+}
+
+// the non-coherent form (MODE 2): ncell cells of nseg segments each, x [xsel][nseg][L]; xsel, rsel and
+// stats point at the launch's first cell
+inline void pfa_nc_corr_launch(hipStream_t stream, const float2* x, const int* xsel, const int* rsel,
+                               int ncell, int nseg, float2* RS, DirStats* stats) {
+    if (ncell <= 0) return;
+    int dev = 0, n_cu = 256;
+    if (hipGetDevice(&dev) == hipSuccess)
+        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+    const int grid = ncell < n_cu ? ncell : n_cu;
+    hipLaunchKernelGGL(pfa_corr_kernel<2>, dim3(grid), dim3(kPfaThreads), 0, stream, x,
+                       (const float*)nullptr, xsel, rsel, RS, nseg, ncell, stats);
 }
 
 // spectrum of the replica in slot `slot` (rep_slot0 = table of real replicas [slots][L])

@@ -70,6 +70,32 @@ class Acquisition:
                     satLst.remove(s)
         return ready, freq_next, sorted(satFound, reverse=True)
 
+    def sweepWeakSats(self, data, freqs, satLst, satFound, n_coh=4, n_seg=25):
+        """sweepAllSats's first-hit contract over the non-coherent surface
+        (AcqEngine.search_noncoherent: mean |corr| of n_seg segments of n_coh ms each): the
+        bins `freqs` are scanned in order, the first normMaxCorr > CORR_MIN claims an SV;
+        ``satLst`` and ``satFound`` are mutated in place, entries are
+        ``(normMaxCorr, satNo, freq, delay)`` with the code phase at the start of `data`;
+        returns ``sorted(satFound, reverse=True)``.  `data` holds at least
+        n_seg * n_coh code periods (several blocks of the stream, concatenated)."""
+        c = self.cfg
+        freqs = list(freqs)
+        if freqs and satLst:
+            prns = list(satLst)
+            table = self.engine.search_noncoherent(data, prns, freqs, n_coh, n_seg)
+            for b, f in enumerate(freqs):
+                hit = []
+                for j, s in enumerate(prns):
+                    if s not in satLst:
+                        continue
+                    nmc = norm_max_corr(table[b, j])
+                    if nmc > c.corr_min:
+                        satFound.append((nmc, s, f, int(table[b, j]['argmax'])))
+                        hit.append(s)
+                for s in hit:
+                    satLst.remove(s)
+        return sorted(satFound, reverse=True)
+
     def search_table(self, data, prns, freqs, n_avg):
         """The whole surface, no pruning (BASELINE configs 2 and 4)."""
         return self.engine.search(data, prns, freqs, n_avg)

@@ -202,6 +202,32 @@ class AcqEngine:
                 len(f_a), n_avg, ptr(out)), 'gpsmi_acq_search')
         return out
 
+    def search_noncoherent(self, iq, prns, freqs, n_coh, n_seg, out_dev=None, nbr=False):
+        """Non-coherent search (gpsmi_acq_search_nc): per cell the mean of the correlation
+        magnitudes of n_seg consecutive segments of n_coh code periods, each segment searched as
+        search() does with n_avg = n_coh.  iq: host array in the input format, or a
+        (c_void_p, n) device pair.  Returns the PEAK_DTYPE table [nbins, nsv] of that mean
+        surface, and with nbr=True also its values left / right of every argmax
+        (float32 [nbins, nsv, 2]; host input only)."""
+        prn_a = np.ascontiguousarray(prns, dtype=np.int32)
+        f_a = np.ascontiguousarray(freqs, dtype=np.float64)
+        out = np.zeros((len(f_a), len(prn_a)), dtype=PEAK_DTYPE)
+        nb = np.zeros((len(f_a), len(prn_a), 2), dtype=np.float32) if nbr else None
+        if isinstance(iq, tuple):
+            if nbr:
+                raise ValueError('nbr is returned for host input only')
+            d_iq, n = iq
+            check(self.lib.gpsmi_acq_search_nc_dev(
+                self.h, d_iq, n, ptr(prn_a), len(prn_a), ptr(f_a), len(f_a),
+                int(n_coh), int(n_seg), ptr(out), out_dev), 'gpsmi_acq_search_nc_dev')
+        else:
+            iq = self._host_iq(iq)
+            check(self.lib.gpsmi_acq_search_nc(
+                self.h, ptr(iq), iq.size, ptr(prn_a), len(prn_a), ptr(f_a), len(f_a),
+                int(n_coh), int(n_seg), ptr(out), ptr(nb) if nbr else None),
+                'gpsmi_acq_search_nc')
+        return (out, nb) if nbr else out
+
     def search_async(self, d_iq, n, prns, freqs, n_avg, out, out_dev=None):
         """Enqueue a search on device-resident iq; `out` is a pinned PEAK_DTYPE
         array [nbins, nsv] filled when wait() returns."""

@@ -189,6 +189,33 @@ int gpsmi_acq_search_dev_async(gpsmi_acq* h, const void* d_iq, size_t n,
                                const double* freqs_hz, int nbins, int n_avg,
                                gpsmi_peak* out, void* out_dev);
 int gpsmi_acq_wait(gpsmi_acq* h);
+/* Non-coherent search for weak signals: the mean of the correlation magnitudes of n_seg
+ * consecutive segments of n_coh code periods each (the reference integrates coherently only,
+ * gpsrecv.py:249-259).  Segment s is what gpsmi_acq_search computes with n_avg = n_coh on iq
+ * advanced by s * n_coh * code_samples samples: the carrier wipe-off restarts at phase 0 with
+ * SEC_TIME[0 : n_coh * code_samples] in every segment (only magnitudes are kept, so the segment's
+ * carrier phase does not matter).  Per cell
+ *     S[lag] = (1 / n_seg) * sum_s |corr_s[lag]|      (float32, ascending s)
+ * and out / nbr are gpsmi_acq_search_ex's records of S: first-index argmax, peak, mean, population
+ * std, and S[argmax -+ 1] circularly (nbr may be NULL).  n_seg = 1 gives gpsmi_acq_search's bits.
+ * n >= n_seg * n_coh * code_samples; iq in the handle's input format (gpsmi_acq_set_input_format),
+ * host memory for gpsmi_acq_search_nc, device memory for gpsmi_acq_search_nc_dev (out_dev as in
+ * gpsmi_acq_search_dev).  gpsmi_acq_last_ms reports the call.
+ * The argmax is the code phase at the start of segment 0: code Doppler moves the code by
+ * |f| / 1575.42e6 * fs * span samples over the span searched -- 0.65 samples per 100 ms at 5 kHz and
+ * 2.048 Msps, 8 times that at 16.368 Msps -- which smears the peak and is not compensated.
+ * code_samples = 2048 and the native 16368 correlation only: a handle forced onto a time-domain
+ * path (option "codephase" 1 or 2, or another code length) returns GPSMI_E_UNSUPPORTED.  Scratch is
+ * sized per call (bins are taken in chunks of at most 512 MiB of spectra); an allocation the device
+ * cannot serve returns GPSMI_E_NOMEM and leaves the handle usable.                              */
+int gpsmi_acq_search_nc(gpsmi_acq* h, const void* iq, size_t n,
+                        const int32_t* prn, int nsv,
+                        const double* freqs_hz, int nbins, int n_coh, int n_seg,
+                        gpsmi_peak* out, float* nbr);
+int gpsmi_acq_search_nc_dev(gpsmi_acq* h, const void* d_iq, size_t n,
+                            const int32_t* prn, int nsv,
+                            const double* freqs_hz, int nbins, int n_coh, int n_seg,
+                            gpsmi_peak* out, void* out_dev);
 /* Input format of the iq pointers of the search calls that follow (host or device), as
  * gpsmi_trk_set_input_format below: GPSMI_IQ_U8 = the raw recording of streamData
  * (gpsrecv.py:162-173), decoded where the carrier wipe-off reads it; same bits out.   */
