@@ -1,0 +1,442 @@
+// Narrowband interference excision ahead of acquisition and tracking (gpsmi_ifx_*, include/gpsmi.h;
+// DESIGN.md 4.2b; numpy restatement: tests/ifx_ref.py).
+//
+// A block of n complex samples is cut into frames of L = 2048 at hop H = 1024: frame m covers block
+// samples [m H - H, m H + H), frame 0 starts in the carry (the previous block's last H samples).
+// Periodic Hann window, except the last frame, whose second half is weighted 1: the frames sum to 1
+// at every sample of the block and the output of block k depends on input blocks k - 1 and k only.
+//
+//   ifx_psd_kernel    one workgroup per (block, group of kPsdGroup frames): sum of |FFT(w x_m)|^2
+//                     over the group's frames in ascending order -> partial[block][group][2048].
+//                     Frames 0 .. n/H - 2 take part (the flat-window last frame does not).
+//   ifx_mask_kernel   one workgroup per block: P = (sum of the partials in group order) / (n/H - 1),
+//                     floor = median(P) (bitonic sort of the 2048 values in LDS, the mean of the two
+//                     middle ones), flag P > floor * 10^(thresh_db / 10), widen by +-dilate bins
+//                     circularly, count; more than max_bins: count -1 and an empty mask.
+//   ifx_apply_kernel  one workgroup per (block, run of consecutive output segments [s H, s H + H)):
+//                     transforms the frames s0 .. s0 + S in order, zeroes the masked bins, transforms
+//                     back (ifft(Y) = conj(fft(conj Y)) / L) and writes segment s = frame s's second
+//                     half + frame s + 1's first half, in that order.  A thread holds samples
+//                     t + 256 r of a frame (gpsmi_fft.h), so the two halves of a segment meet in the
+//                     same thread's registers: every output sample is written once, by one add whose
+//                     operands do not depend on the grid.  A block with count -1 is copied through.
+//   ifx_carry_kernel  the last block's final H input samples (decoded) -> the handle's carry.
+//
+// No atomics: every sum has a fixed order, so the output bits do not depend on the grid, on the
+// number of blocks per call or on the run.
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "gpsmi_common.h"
+#include "gpsmi_fft.h"
+
+namespace gpsmi {
+
+constexpr int kIfxL = kFftN;             // frame length
+constexpr int kIfxH = kFftN / 2;         // hop
+constexpr int kPsdGroup = 8;             // frames per workgroup of the PSD pass (fixes the sum order)
+constexpr int kMaskWords = kIfxL / 32;
+
+// frame sample i (thread t holds i = t + 256 r) of frame `f` of block `b`; negative block offsets of
+// block 0 of a call come from the carry, those of later blocks from the block before (contiguous)
+template <int FMT>
+__device__ __forceinline__ float2 ifx_load(const void* iq, const float2* carry, int b, int n, int g) {
+    if (b == 0 && g < 0) return carry[g + kIfxH];
+    return load_iq<FMT>(iq, (size_t)b * n + g);
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void ifx_psd_kernel(const void* __restrict__ iq,
+                                                      const float2* __restrict__ carry,
+                                                      const float* __restrict__ win, int n, int groups,
+                                                      float* __restrict__ partial,
+                                                      const float2* __restrict__ tw) {
+    __shared__ __attribute__((aligned(16))) float lds[kFftLdsFloats];
+    __shared__ __attribute__((aligned(16))) float lds_tw[kFftTwFloats];
+    const int t = threadIdx.x;
+    const int b = blockIdx.x / groups, grp = blockIdx.x % groups;
+    const FftTw ftw = fft_setup(lds_tw, tw, t);
+    float w[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) w[r] = win[t + 256 * r];
+    const int f_end = min((grp + 1) * kPsdGroup, n / kIfxH - 1);
+    float acc[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[q] = 0.f;
+    __syncthreads();
+    for (int f = grp * kPsdGroup; f < f_end; ++f) {
+        float2 v[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const float2 x = ifx_load<FMT>(iq, carry, b, n, f * kIfxH - kIfxH + t + 256 * r);
+            v[r] = make_float2(x.x * w[r], x.y * w[r]);
+        }
+        fft2048(v, lds, ftw, t);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[q] += v[q].x * v[q].x + v[q].y * v[q].y;
+        lds_barrier();               // (the next transform overwrites buffer 0)
+    }
+    float* out = partial + (size_t)blockIdx.x * kIfxL;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) out[t + 256 * q] = acc[q];
+}
+
+__global__ __launch_bounds__(256) void ifx_mask_kernel(const float* __restrict__ partial, int groups,
+                                                       int nframes, float scale, int dilate,
+                                                       int max_bins, int32_t* __restrict__ counts,
+                                                       uint32_t* __restrict__ masks) {
+    __shared__ float P[kIfxL];
+    __shared__ float srt[kIfxL];
+    __shared__ int flag[kIfxL];
+    __shared__ uint32_t words[kMaskWords];
+    const int t = threadIdx.x, b = blockIdx.x;
+    const float* src = partial + (size_t)b * groups * kIfxL;
+    const float inv = (float)nframes;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int k = t + 256 * q;
+        float s = 0.f;
+        for (int g = 0; g < groups; ++g) s += src[(size_t)g * kIfxL + k];
+        s = s / inv;
+        P[k] = s;
+        srt[k] = s;
+    }
+    __syncthreads();
+    // bitonic sort, ascending: 1024 compare-exchanges per stage, four per thread
+    for (int k = 2; k <= kIfxL; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int p = t + 256 * q;
+                const int i = 2 * j * (p / j) + (p % j), l = i + j;
+                const bool up = (i & k) == 0;
+                const float a = srt[i], c = srt[l];
+                if ((a > c) == up) { srt[i] = c; srt[l] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    const float thr = 0.5f * (srt[kIfxL / 2 - 1] + srt[kIfxL / 2]) * scale;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) flag[t + 256 * q] = P[t + 256 * q] > thr ? 1 : 0;
+    __syncthreads();
+    const int lane = t & 63, wave = t >> 6;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int k = t + 256 * q;
+        int f = 0;
+        for (int d = -dilate; d <= dilate; ++d) f |= flag[(k + d) & (kIfxL - 1)];
+        const unsigned long long bal = __ballot(f);       // bins 256 q + 64 wave + lane
+        if (lane == 0) {
+            const int w0 = (256 * q + 64 * wave) / 32;
+            words[w0] = (uint32_t)bal;
+            words[w0 + 1] = (uint32_t)(bal >> 32);
+        }
+    }
+    __syncthreads();
+    int count = 0;
+    for (int w = 0; w < kMaskWords; ++w) count += __popc(words[w]);   // (every thread, same value)
+    const bool wide = count > max_bins;
+    if (t < kMaskWords) masks[(size_t)b * kMaskWords + t] = wide ? 0u : words[t];
+    if (t == 0) counts[b] = wide ? -1 : count;
+}
+
+// grid: nb * runs workgroups, run = S consecutive segments of one block
+template <int FMT>
+__global__ __launch_bounds__(256) void ifx_apply_kernel(const void* __restrict__ iq,
+                                                        const float2* __restrict__ carry,
+                                                        const float* __restrict__ win, int n, int runs,
+                                                        int S, const int32_t* __restrict__ counts,
+                                                        const uint32_t* __restrict__ masks,
+                                                        float2* __restrict__ out,
+                                                        const float2* __restrict__ tw) {
+    __shared__ __attribute__((aligned(16))) float lds[kFftLdsFloats];
+    __shared__ __attribute__((aligned(16))) float lds_tw[kFftTwFloats];
+    const int t = threadIdx.x;
+    const int b = blockIdx.x / runs, run = blockIdx.x % runs;
+    const int nf = n / kIfxH;
+    const int s0 = run * S, s1 = min(s0 + S, nf);            // segments [s0, s1)
+    float2* o = out + (size_t)b * n;
+    if (counts[b] < 0) {                                      // wideband: the block passes through
+        for (int i = s0 * kIfxH + t; i < s1 * kIfxH; i += 256) o[i] = load_iq<FMT>(iq, (size_t)b * n + i);
+        return;
+    }
+    const FftTw ftw = fft_setup(lds_tw, tw, t);
+    float w[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) w[r] = win[t + 256 * r];
+    unsigned keep = 0;                                        // bit q: bin t + 256 q survives
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int k = t + 256 * q;
+        keep |= ((masks[(size_t)b * kMaskWords + (k >> 5)] >> (k & 31)) & 1u) ? 0u : (1u << q);
+    }
+    const float sc = 1.0f / (float)kIfxL;
+    __syncthreads();
+    float2 prev[4];
+    const int f_end = min(s1, nf - 1);                        // last frame transformed
+    for (int f = s0; f <= f_end; ++f) {
+        const bool last = f == nf - 1;
+        float2 v[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const float2 x = ifx_load<FMT>(iq, carry, b, n, f * kIfxH - kIfxH + t + 256 * r);
+            const float wr = (last && r >= 4) ? 1.0f : w[r];
+            v[r] = make_float2(x.x * wr, x.y * wr);
+        }
+        fft2048(v, lds, ftw, t);
+#pragma unroll
+        for (int q = 0; q < 8; ++q)          // zero the masked bins, conjugate for the inverse
+            v[q] = ((keep >> q) & 1u) ? make_float2(v[q].x, -v[q].y) : make_float2(0.f, 0.f);
+        lds_barrier();
+        fft2048(v, lds, ftw, t);
+        lds_barrier();
+#pragma unroll
+        for (int r = 0; r < 8; ++r) v[r] = make_float2(v[r].x * sc, -v[r].y * sc);
+        if (f > s0) {                                         // segment f - 1 is complete
+            float2* d = o + (size_t)(f - 1) * kIfxH;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                d[t + 256 * r] = make_float2(prev[r].x + v[r].x, prev[r].y + v[r].y);
+        }
+        if (last && f < s1) {                                 // the last segment: frame nf - 1 alone
+            float2* d = o + (size_t)f * kIfxH;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) d[t + 256 * r] = v[r + 4];
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) prev[r] = v[r + 4];
+    }
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void ifx_carry_kernel(const void* __restrict__ iq, size_t tail,
+                                                        float2* __restrict__ carry) {
+    for (int i = threadIdx.x; i < kIfxH; i += 256) carry[i] = load_iq<FMT>(iq, tail + i);
+}
+
+}  // namespace gpsmi
+
+using namespace gpsmi;
+
+struct gpsmi_ifx {
+    gpsmi_ifx_cfg cfg;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float2* d_tw = nullptr;
+    float* d_win = nullptr;                  // periodic Hann, float32 of the double value
+    float2* d_carry = nullptr;               // [H] complex64
+    float* d_partial = nullptr; size_t partial_cap = 0;     // [nb][groups][2048]
+    int32_t* d_counts = nullptr; uint32_t* d_masks = nullptr; size_t res_cap = 0;   // blocks
+    void* d_in = nullptr; size_t in_cap = 0;                // host entry: staged input (bytes)
+    void* d_out = nullptr; size_t out_cap = 0;              //             and output (bytes)
+    int fmt = GPSMI_IQ_C64;
+    float scale = 0.f;                       // 10^(thresh_db / 10) as float32
+    float last_ms = 0.f;
+};
+
+static int ifx_grow(void** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return GPSMI_OK;
+    if (*p) GPSMI_HIP(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) {
+        *p = nullptr;
+        if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
+            (void)hipGetLastError();
+            return fail(GPSMI_E_NOMEM, "excision scratch: %zu bytes not available", bytes);
+        }
+        return fail(GPSMI_E_HIP, "hipMalloc: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+    }
+    *cap = bytes;
+    return GPSMI_OK;
+}
+
+static bool ifx_block_ok(int32_t n) { return n >= 4 * kIfxH && n <= (1 << 24) && n % kIfxH == 0; }
+
+static int ifx_build(gpsmi_ifx* h) {
+    GPSMI_HIP(hipStreamCreate(&h->stream));
+    GPSMI_HIP(hipEventCreate(&h->ev0));
+    GPSMI_HIP(hipEventCreate(&h->ev1));
+    std::vector<float2> tw;
+    make_twiddles(tw);
+    GPSMI_HIP(hipMalloc((void**)&h->d_tw, tw.size() * sizeof(float2)));
+    GPSMI_HIP(hipMemcpy(h->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
+    std::vector<float> win(kIfxL);
+    for (int i = 0; i < kIfxL; ++i) {
+        const double s = sin(M_PI * (double)i / (double)kIfxL);
+        win[i] = (float)(s * s);
+    }
+    GPSMI_HIP(hipMalloc((void**)&h->d_win, kIfxL * sizeof(float)));
+    GPSMI_HIP(hipMemcpy(h->d_win, win.data(), kIfxL * sizeof(float), hipMemcpyHostToDevice));
+    GPSMI_HIP(hipMalloc((void**)&h->d_carry, kIfxH * sizeof(float2)));
+    GPSMI_HIP(hipMemset(h->d_carry, 0, kIfxH * sizeof(float2)));
+    h->scale = (float)pow(10.0, (double)h->cfg.thresh_db / 10.0);
+    return GPSMI_OK;
+}
+
+// Runs the four passes over nb blocks at d_iq (device, the handle's input format) into d_out.
+static int ifx_run(gpsmi_ifx* h, const void* d_iq, void* d_out, int nb) {
+    const int n = h->cfg.block_samples, nf = n / kIfxH;
+    const int groups = (nf - 1 + kPsdGroup - 1) / kPsdGroup;
+    int rc = ifx_grow((void**)&h->d_partial, &h->partial_cap, (size_t)nb * groups * kIfxL * sizeof(float));
+    if (rc) return rc;
+    if ((size_t)nb > h->res_cap) {
+        if (h->d_counts) GPSMI_HIP(hipFree(h->d_counts));
+        if (h->d_masks) GPSMI_HIP(hipFree(h->d_masks));
+        h->d_counts = nullptr; h->d_masks = nullptr; h->res_cap = 0;
+        GPSMI_HIP(hipMalloc((void**)&h->d_counts, (size_t)nb * sizeof(int32_t)));
+        GPSMI_HIP(hipMalloc((void**)&h->d_masks, (size_t)nb * kMaskWords * sizeof(uint32_t)));
+        h->res_cap = nb;
+    }
+    // segments per apply workgroup: one frame transform pair per segment plus one per workgroup;
+    // runs of up to 8 segments once the grid has some 2048 workgroups anyway (same bits either way)
+    const long long segs = (long long)nb * nf;
+    const int S = segs >= 16384 ? 8 : segs >= 8192 ? 4 : segs >= 4096 ? 2 : 1;
+    const int runs = (nf + S - 1) / S;
+    const bool u8 = h->fmt == GPSMI_IQ_U8;
+    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
+    if (u8)
+        hipLaunchKernelGGL(ifx_psd_kernel<1>, dim3((unsigned)(nb * groups)), dim3(256), 0, h->stream, d_iq,
+                           h->d_carry, h->d_win, n, groups, h->d_partial, h->d_tw);
+    else
+        hipLaunchKernelGGL(ifx_psd_kernel<0>, dim3((unsigned)(nb * groups)), dim3(256), 0, h->stream, d_iq,
+                           h->d_carry, h->d_win, n, groups, h->d_partial, h->d_tw);
+    hipLaunchKernelGGL(ifx_mask_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, h->d_partial, groups,
+                       nf - 1, h->scale, h->cfg.dilate, h->cfg.max_bins, h->d_counts, h->d_masks);
+    const size_t tail = (size_t)nb * n - kIfxH;
+    if (u8) {
+        hipLaunchKernelGGL(ifx_apply_kernel<1>, dim3((unsigned)(nb * runs)), dim3(256), 0, h->stream, d_iq,
+                           h->d_carry, h->d_win, n, runs, S, h->d_counts, h->d_masks, (float2*)d_out,
+                           h->d_tw);
+        hipLaunchKernelGGL(ifx_carry_kernel<1>, dim3(1), dim3(256), 0, h->stream, d_iq, tail, h->d_carry);
+    } else {
+        hipLaunchKernelGGL(ifx_apply_kernel<0>, dim3((unsigned)(nb * runs)), dim3(256), 0, h->stream, d_iq,
+                           h->d_carry, h->d_win, n, runs, S, h->d_counts, h->d_masks, (float2*)d_out,
+                           h->d_tw);
+        hipLaunchKernelGGL(ifx_carry_kernel<0>, dim3(1), dim3(256), 0, h->stream, d_iq, tail, h->d_carry);
+    }
+    GPSMI_HIP(hipGetLastError());
+    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
+    return GPSMI_OK;
+}
+
+static int ifx_finish(gpsmi_ifx* h, int nb, int32_t* counts, uint32_t* masks) {
+    if (counts)
+        GPSMI_HIP(hipMemcpyAsync(counts, h->d_counts, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                 h->stream));
+    if (masks)
+        GPSMI_HIP(hipMemcpyAsync(masks, h->d_masks, (size_t)nb * kMaskWords * sizeof(uint32_t),
+                                 hipMemcpyDeviceToHost, h->stream));
+    GPSMI_HIP(hipStreamSynchronize(h->stream));
+    GPSMI_HIP(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return GPSMI_OK;
+}
+
+static size_t ifx_in_bytes(const gpsmi_ifx* h, int nb) {
+    return (size_t)nb * h->cfg.block_samples * (h->fmt == GPSMI_IQ_U8 ? sizeof(uint16_t) : sizeof(float2));
+}
+
+extern "C" {
+
+int gpsmi_ifx_destroy(gpsmi_ifx* h);
+
+int gpsmi_ifx_create(const gpsmi_ifx_cfg* cfg, gpsmi_ifx** out) {
+    GPSMI_REQUIRE(cfg && out, "null argument");
+    *out = nullptr;
+    GPSMI_REQUIRE(!std::isnan(cfg->thresh_db), "thresh_db is NaN");
+    GPSMI_REQUIRE(cfg->dilate >= 0 && cfg->dilate <= 64, "dilate out of range 0..64");
+    GPSMI_REQUIRE(cfg->max_bins >= 0 && cfg->max_bins <= kIfxL, "max_bins out of range 0..2048");
+    if (!ifx_block_ok(cfg->block_samples))
+        return fail(GPSMI_E_UNSUPPORTED,
+                    "gpsmi_ifx_create: block_samples %d is not a multiple of 1024 in 4096..2^24",
+                    (int)cfg->block_samples);
+    GPSMI_HIP(hipSetDevice(cfg->device));
+    gpsmi_ifx* h = new (std::nothrow) gpsmi_ifx();
+    if (!h) return fail(GPSMI_E_NOMEM, "out of host memory");
+    h->cfg = *cfg;
+    const int rc = ifx_build(h);
+    if (rc) {
+        (void)gpsmi_ifx_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return GPSMI_OK;
+}
+
+int gpsmi_ifx_destroy(gpsmi_ifx* h) {
+    if (!h) return GPSMI_OK;
+    (void)hipSetDevice(h->cfg.device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    void* bufs[] = {h->d_tw, h->d_win, h->d_carry, h->d_partial, h->d_counts, h->d_masks, h->d_in, h->d_out};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    if (h->ev0) (void)hipEventDestroy(h->ev0);
+    if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+    return GPSMI_OK;
+}
+
+int gpsmi_ifx_set_input_format(gpsmi_ifx* h, int fmt) {
+    GPSMI_REQUIRE(h, "null handle");
+    GPSMI_REQUIRE(fmt == GPSMI_IQ_C64 || fmt == GPSMI_IQ_U8, "unknown input format");
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    GPSMI_HIP(hipStreamSynchronize(h->stream));
+    h->fmt = fmt;
+    return GPSMI_OK;
+}
+
+int gpsmi_ifx_reset(gpsmi_ifx* h) {
+    GPSMI_REQUIRE(h, "null handle");
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    GPSMI_HIP(hipMemsetAsync(h->d_carry, 0, kIfxH * sizeof(float2), h->stream));
+    GPSMI_HIP(hipStreamSynchronize(h->stream));
+    return GPSMI_OK;
+}
+
+int gpsmi_ifx_apply_dev(gpsmi_ifx* h, const void* d_iq, void* d_out, int nb, int32_t* counts,
+                        uint32_t* masks) {
+    GPSMI_REQUIRE(h && d_iq && d_out, "null argument");
+    GPSMI_REQUIRE(nb >= 1 && (size_t)nb * h->cfg.block_samples <= ((size_t)1 << 31),
+                  "nb out of range: 1 .. 2^31 samples per call");
+    {   // the output of one block is made of the input of the block before: no overlap at all
+        const char* i0 = static_cast<const char*>(d_iq);
+        const char* o0 = static_cast<const char*>(d_out);
+        const size_t ib = ifx_in_bytes(h, nb), ob = (size_t)nb * h->cfg.block_samples * sizeof(float2);
+        GPSMI_REQUIRE(o0 + ob <= i0 || i0 + ib <= o0, "input and output overlap (no in-place excision)");
+    }
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    int rc = ifx_run(h, d_iq, d_out, nb);
+    if (rc) return rc;
+    return ifx_finish(h, nb, counts, masks);
+}
+
+int gpsmi_ifx_apply(gpsmi_ifx* h, const void* iq, float* out, int nb, int32_t* counts, uint32_t* masks) {
+    GPSMI_REQUIRE(h && iq && out, "null argument");
+    GPSMI_REQUIRE(nb >= 1 && (size_t)nb * h->cfg.block_samples <= ((size_t)1 << 31),
+                  "nb out of range: 1 .. 2^31 samples per call");
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    const size_t ib = ifx_in_bytes(h, nb), ob = (size_t)nb * h->cfg.block_samples * sizeof(float2);
+    int rc = ifx_grow(&h->d_in, &h->in_cap, ib);
+    if (rc) return rc;
+    rc = ifx_grow(&h->d_out, &h->out_cap, ob);
+    if (rc) return rc;
+    GPSMI_HIP(hipMemcpyAsync(h->d_in, iq, ib, hipMemcpyHostToDevice, h->stream));
+    rc = ifx_run(h, h->d_in, h->d_out, nb);
+    if (rc) return rc;
+    GPSMI_HIP(hipMemcpyAsync(out, h->d_out, ob, hipMemcpyDeviceToHost, h->stream));
+    return ifx_finish(h, nb, counts, masks);
+}
+
+int gpsmi_ifx_last_ms(gpsmi_ifx* h, float* ms) {
+    GPSMI_REQUIRE(h && ms, "null argument");
+    *ms = h->last_ms;
+    return GPSMI_OK;
+}
+
+}  // extern "C"

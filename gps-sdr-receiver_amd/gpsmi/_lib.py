@@ -22,6 +22,11 @@ class EngineError(RuntimeError):
     pass
 
 
+class IfxCfg(C.Structure):
+    _fields_ = [('block_samples', C.c_int32), ('thresh_db', C.c_float), ('dilate', C.c_int32),
+                ('max_bins', C.c_int32), ('device', C.c_int32)]
+
+
 class Cfg(C.Structure):
     _fields_ = [('code_samples', C.c_int32), ('n_cyc', C.c_int32),
                 ('corr_avg', C.c_int32), ('sweep_corr_avg', C.c_int32),
@@ -83,6 +88,8 @@ EXPORTS = [
     'gpsmi_comm_allgather_peaks', 'gpsmi_comm_count',
     'gpsmi_set_default', 'gpsmi_clear_default', 'gpsmi_trk_set_option', 'gpsmi_trk_get_option',
     'gpsmi_trk_corr_grid', 'gpsmi_trk_corr_wg_map',
+    'gpsmi_ifx_create', 'gpsmi_ifx_destroy', 'gpsmi_ifx_set_input_format', 'gpsmi_ifx_reset',
+    'gpsmi_ifx_apply', 'gpsmi_ifx_apply_dev', 'gpsmi_ifx_last_ms',
 ]
 
 _lib = None
@@ -174,6 +181,13 @@ def load():
         'gpsmi_trk_get_option': [vp, C.c_char_p, P(C.c_longlong)],
         'gpsmi_trk_corr_grid': [C.c_int, C.c_int],
         'gpsmi_trk_corr_wg_map': [C.c_int, C.c_int, C.c_int, P(C.c_int), P(C.c_int)],
+        'gpsmi_ifx_create': [P(IfxCfg), P(vp)],
+        'gpsmi_ifx_destroy': [vp],
+        'gpsmi_ifx_set_input_format': [vp, C.c_int],
+        'gpsmi_ifx_reset': [vp],
+        'gpsmi_ifx_apply': [vp, vp, vp, C.c_int, vp, vp],
+        'gpsmi_ifx_apply_dev': [vp, vp, vp, C.c_int, vp, vp],
+        'gpsmi_ifx_last_ms': [vp, P(f32)],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -23,14 +23,28 @@ UDP_PORT = 61431                # gpsglob.py:82
 
 
 class Receiver:
-    def __init__(self, cfg=None, sat_all=None, raw_u8=False, report_lag=0):
+    def __init__(self, cfg=None, sat_all=None, raw_u8=False, report_lag=0, excise=None):
         """raw_u8: feed() takes the recorder's uint16 (Q << 8 | I) blocks exactly as streamData
         reads them from the file (gpsrecv.py:162-173); the decode to complex64 happens inside
         the GPU kernels, every datagram is byte-identical to the complex64 path's.
         report_lag = L: feed() returns a datagram L blocks after the block the reference sends it
         on (0, the default: on that block) -- the once-a-second host work then runs while the GPU
-        has L newer blocks queued instead of idling through it; the datagrams are the same."""
+        has L newer blocks queued instead of idling through it; the datagrams are the same.
+        excise = True or an excision.Excision: feed() first removes narrowband interference from
+        each block on the GPU into a page-locked complex64 block, which then takes the complex64
+        path unchanged (with raw_u8 the excision decodes, the engines run in complex64).  None, the
+        default: no excision, everything as without the argument."""
         self.cfg = cfg or Config()
+        self.excision, self._clean = None, None
+        if excise is not None and excise is not False:
+            from .engine import PinnedArray
+            from .excision import Excision
+            self._own_excision = excise is True
+            self.excision = Excision(self.cfg, raw_u8=raw_u8) if excise is True else excise
+            if self.excision.raw_u8 != bool(raw_u8) or self.excision.n != self.cfg.ngps:
+                raise ValueError('the Excision does not match raw_u8 / the block length')
+            self._clean = PinnedArray((self.cfg.ngps,), np.complex64)
+            raw_u8 = False                           # (the engines see the excision's complex64)
         self.raw_u8 = bool(raw_u8)
         self.sat_all = list(SAT_ALL if sat_all is None else sat_all)
         self.acq = Acquisition(self.cfg, raw_u8=self.raw_u8)
@@ -64,6 +78,10 @@ class Receiver:
         """One block (complex64[NGPS], or uint16[NGPS] when raw_u8); `skip` = streams lost before it
         (gpsrecv.py:469-471).  Returns the pickled hand-off or None."""
         c = self.cfg
+        if self.excision is not None:
+            # (one page-locked block serves every call: the acquisition reads it before it returns,
+            # the tracking pool copies it into its own input ring)
+            data = self.excision.apply(data, out=self._clean.array)
         self.skipped_data += skip * c.ngps
         self.smp_time += (1 + skip) * c.ngps
         if self.sweep_all_freq:
@@ -135,6 +153,11 @@ class Receiver:
         self.drain()
         R.closeMultiProcPool(self.pool)
         self.acq.engine.close()
+        if self._clean is not None:
+            self._clean.free()
+            self._clean = None
+            if self._own_excision:
+                self.excision.close()
 
 
 def send_udp(sock, res, ip=UDP_IP, port=UDP_PORT):

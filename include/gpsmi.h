@@ -418,6 +418,51 @@ int gpsmi_trk_last_ms(gpsmi_trk* h, float* total_ms, float* correlator_ms);
 int gpsmi_trk_last_codephase_ms(gpsmi_trk* h, float* ms);
 
 /* ========================================================================
+ * Narrowband interference excision: an opt-in input filter ahead of acquisition and tracking
+ * (DESIGN.md 4.2b).  A continuous-wave tone some 30 dB above the noise defeats the C/A code's
+ * processing gain; this finds such tones in the spectrum of each block and removes their bins.
+ * One block of block_samples complex samples (a multiple of 1024, >= 4096: CODE_SAMPLES 2048 at
+ * N_CYC 32 / 16 / 8; anything else, the 16368-sample configs among them, is GPSMI_E_UNSUPPORTED)
+ * is cut into frames of 2048 samples at hop 1024, frame m covering block samples
+ * [1024 m - 1024, 1024 m + 1024); frame 0 starts in the carry, the previous block's last 1024
+ * input samples (zero after create / reset).  Window: periodic Hann sin^2(pi i / 2048), except
+ * the last frame, whose second half is weighted 1, so that the frames sum to 1 everywhere and
+ * output block k depends on input blocks k - 1 and k only (no latency, same sample bookkeeping).
+ * Detection: P[k] = mean over frames 0 .. n/1024 - 2 of |FFT(w x_m)|^2; a bin is flagged when
+ * P[k] > median(P) * 10^(thresh_db / 10) (median: the mean of the two middle values), then widened
+ * by +-dilate bins circularly.  More than max_bins flagged bins: wideband interference, the block
+ * passes through unchanged (bit for bit), its count is -1 and its mask empty.  Otherwise every frame
+ * is transformed, the flagged bins zeroed, transformed back and overlap-added; out is complex64.
+ * Every sum has a fixed order: the bits do not depend on nb or on the run.
+ * counts: int32 [nb] (flagged bins, -1 wideband); masks: uint32 [nb * 64], bin k of block b in
+ * bit k % 32 of masks[b * 64 + k / 32] (the bins removed).  Both optional host arrays.
+ * nb consecutive blocks in order: block b's carry is block b - 1's tail (the handle's carry for
+ * b = 0), and the handle's carry is the last block's tail afterwards.  Input and output must not
+ * overlap (GPSMI_E_ARG: no in-place excision).  Both calls return when the work is done;
+ * gpsmi_ifx_last_ms reports its device time.  thresh_db = +inf flags nothing.
+ * ======================================================================== */
+typedef struct gpsmi_ifx gpsmi_ifx;
+typedef struct gpsmi_ifx_cfg {
+    int32_t block_samples;   /* n, multiple of 1024, >= 4096               */
+    float   thresh_db;       /* 6.0 (not NaN)                              */
+    int32_t dilate;          /* 2 (0 .. 64)                                */
+    int32_t max_bins;        /* 256 (0 .. 2048)                            */
+    int32_t device;
+} gpsmi_ifx_cfg;
+int gpsmi_ifx_create(const gpsmi_ifx_cfg* cfg, gpsmi_ifx** out);
+int gpsmi_ifx_destroy(gpsmi_ifx* h);
+/* GPSMI_IQ_C64 (default) or GPSMI_IQ_U8 (the recorder's uint16, decoded on load) */
+int gpsmi_ifx_set_input_format(gpsmi_ifx* h, int fmt);
+int gpsmi_ifx_reset(gpsmi_ifx* h);                            /* carry := 0 */
+/* host iq (nb * n samples in the input format) -> host out (complex64 [nb * n])               */
+int gpsmi_ifx_apply(gpsmi_ifx* h, const void* iq, float* out, int nb,
+                    int32_t* counts, uint32_t* masks);
+/* the same from device memory to device memory                                                */
+int gpsmi_ifx_apply_dev(gpsmi_ifx* h, const void* d_iq, void* d_out, int nb,
+                        int32_t* counts, uint32_t* masks);
+int gpsmi_ifx_last_ms(gpsmi_ifx* h, float* ms);
+
+/* ========================================================================
  * Multi-GPU: one process per GPU; SVs / blocks are sharded by the host and
  * the only exchange is a gather of fixed-size peak records over RCCL.
  * ======================================================================== */

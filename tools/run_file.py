@@ -4,7 +4,7 @@ gpsglob.LIVE_MEAS = False / BIN_DATA; gpsrecv.streamData -> processData -> UDP /
 gpseval) as one command on the GPU path.
 
     python tools/run_file.py <recording.bin> [--seconds S] [--start-stream K] [--save-pickle P]
-                             [--ephemeris gpsEphem.json] [--cpu-acq] [--json]
+                             [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--json]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -18,7 +18,9 @@ the second half of the fixes is printed as latitude / longitude / height.  --sav
 writes the datagram list exactly as SAVE_PICKLE does (gpsrecv.py:205-212): an unmodified
 gpseval.py replays it with LOAD_PICKLE.  --cpu-acq times BASELINE configs[0] beside it: the
 cold acquisition of the reference's numpy path (oracle restatement, test infrastructure) on
-the first five blocks of the same file, on one host core.
+the first five blocks of the same file, on one host core.  --excise removes narrowband
+interference (continuous-wave tones) from every block on the GPU before the receiver sees it
+(pipeline.Receiver(excise=True)).
 
 There is no recording in this repository (data/test.bin is absent from the reference
 checkout, SURVEY F2, and too short for a fix even upstream): tests/test_run_file.py writes a
@@ -58,14 +60,15 @@ def cpu_cold_acquisition(path, n_blocks=5):
             'found': [(int(s), float(f), int(d)) for _, s, f, d in found]}
 
 
-def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, cpu_acq=False, report_lag=16):
+def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, cpu_acq=False, report_lag=16,
+        excise=False):
     from gpsmi import ingest, position as P
     from gpsmi.engine import Config
     from gpsmi.pipeline import Receiver, save_results
     cfg = Config()
     # (a recording: the datagrams may come out `report_lag` blocks behind the block they belong to, the
     # reader then runs ahead of the GPU instead of stalling it once a second -- pipeline.Receiver)
-    rx = Receiver(cfg, raw_u8=True, report_lag=report_lag)
+    rx = Receiver(cfg, raw_u8=True, report_lag=report_lag, excise=True if excise else None)
     solver = P.PositionSolver(cfg.code_samples, cfg.n_cyc, ephemerides=ephemerides)
     max_blocks = None if seconds is None else int(seconds * 1000 // cfg.n_cyc)
     fixes, n_dg, n_blocks, found = [], 0, 0, None
@@ -118,13 +121,15 @@ def main():
     ap.add_argument('--cpu-acq', action='store_true', help='time the CPU cold acquisition (configs[0]) too')
     ap.add_argument('--report-lag', type=int, default=16,
                     help='blocks a datagram may trail the block it belongs to (0: none, as a live receiver)')
+    ap.add_argument('--excise', action='store_true',
+                    help='remove narrowband interference (CW tones) from every block first (DESIGN.md 4.2b)')
     ap.add_argument('--json', action='store_true', help='one JSON line instead of text')
     a = ap.parse_args()
     eph = None
     if a.ephemeris:
         with open(a.ephemeris) as f:
             eph = {int(k): v for k, v in json.load(f).items()}
-    out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag)
+    out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise)
     if a.json:
         print(json.dumps(out))
         return
