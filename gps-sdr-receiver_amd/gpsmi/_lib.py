@@ -27,6 +27,12 @@ class IfxCfg(C.Structure):
                 ('max_bins', C.c_int32), ('device', C.c_int32)]
 
 
+class FeCfg(C.Structure):
+    _fields_ = [('fs_in_hz', C.c_int64), ('fs_out_hz', C.c_int64), ('if_hz', C.c_double),
+                ('passband_hz', C.c_float), ('atten_db', C.c_float), ('format', C.c_int32),
+                ('flags', C.c_int32), ('max_out', C.c_int32), ('device', C.c_int32)]
+
+
 class Cfg(C.Structure):
     _fields_ = [('code_samples', C.c_int32), ('n_cyc', C.c_int32),
                 ('corr_avg', C.c_int32), ('sweep_corr_avg', C.c_int32),
@@ -90,6 +96,8 @@ EXPORTS = [
     'gpsmi_trk_corr_grid', 'gpsmi_trk_corr_wg_map',
     'gpsmi_ifx_create', 'gpsmi_ifx_destroy', 'gpsmi_ifx_set_input_format', 'gpsmi_ifx_reset',
     'gpsmi_ifx_apply', 'gpsmi_ifx_apply_dev', 'gpsmi_ifx_last_ms',
+    'gpsmi_fe_design', 'gpsmi_fe_create', 'gpsmi_fe_destroy', 'gpsmi_fe_reset', 'gpsmi_fe_push',
+    'gpsmi_fe_push_dev', 'gpsmi_fe_flush', 'gpsmi_fe_last_ms',
 ]
 
 _lib = None
@@ -188,6 +196,14 @@ def load():
         'gpsmi_ifx_apply': [vp, vp, vp, C.c_int, vp, vp],
         'gpsmi_ifx_apply_dev': [vp, vp, vp, C.c_int, vp, vp],
         'gpsmi_ifx_last_ms': [vp, P(f32)],
+        'gpsmi_fe_design': [P(FeCfg), P(C.c_int), P(C.c_int), vp],
+        'gpsmi_fe_create': [P(FeCfg), P(vp)],
+        'gpsmi_fe_destroy': [vp],
+        'gpsmi_fe_reset': [vp],
+        'gpsmi_fe_push': [vp, vp, sz, vp, sz, P(sz)],
+        'gpsmi_fe_push_dev': [vp, vp, sz, vp, sz, P(sz)],
+        'gpsmi_fe_flush': [vp, vp, sz, P(sz)],
+        'gpsmi_fe_last_ms': [vp, P(f32)],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -196,6 +212,8 @@ def load():
     want = [C.sizeof(Cfg), PEAK_DTYPE.itemsize, STATE_DTYPE.itemsize,
             OUT_DTYPE.itemsize, OUT_DTYPE.fields['code_phase'][1]]
     got = [lib.gpsmi_abi_sizeof(i) for i in range(5)]
+    want.append(C.sizeof(FeCfg))
+    got.append(lib.gpsmi_abi_sizeof(5))
     if want != got:
         raise EngineError(f'ABI mismatch between gpsmi/_lib.py {want} and '
                           f'libgpsmi.so {got}')

@@ -58,6 +58,22 @@ def read_raw_blocks(path, ngps=65536, start_stream=0):
             yield raw
 
 
+def read_frontend_blocks(path, fe, chunk_samples=1 << 20):
+    """A recording of another front end (frontend.FrontEnd's format and rate) -> complex64 blocks of
+    fe.cfg.ngps samples at the engine's rate: the file in chunks of `chunk_samples` input samples,
+    each through fe.blocks.  Every block is yielded in the same page-locked buffer (use it before the
+    next one); a short last block ends the stream."""
+    per = fe.per_sample * int(chunk_samples)
+    with open(path, 'rb') as f:
+        while True:
+            x = np.fromfile(f, dtype=fe.dtype, count=per)
+            x = x[:x.size - x.size % fe.per_sample]
+            if x.size:
+                yield from fe.blocks(x)
+            if x.size < per:
+                return
+
+
 def decode_host(raw):
     """The reference's own decode on the host (numpy)."""
     return raw_to_c64(raw)

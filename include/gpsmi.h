@@ -60,7 +60,7 @@ typedef struct gpsmi_cfg {
 const char* gpsmi_last_error(void);
 const char* gpsmi_version(void);
 /* sizeof() of the ABI structs as compiled: 0 cfg, 1 peak, 2 trk_state, 3 trk_out,
- * 4 offsetof(trk_out, code_phase); -1 otherwise.  Lets a binding verify its
+ * 4 offsetof(trk_out, code_phase), 5 fe_cfg; -1 otherwise.  Lets a binding verify its
  * own struct declarations before the first real call.                        */
 int gpsmi_abi_sizeof(int which);
 /* Kernel-variant selection and tuning thresholds, visible through the ABI (round 4: they used to
@@ -461,6 +461,68 @@ int gpsmi_ifx_apply(gpsmi_ifx* h, const void* iq, float* out, int nb,
 int gpsmi_ifx_apply_dev(gpsmi_ifx* h, const void* d_iq, void* d_out, int nb,
                         int32_t* counts, uint32_t* masks);
 int gpsmi_ifx_last_ms(gpsmi_ifx* h, float* ms);
+
+/* ========================================================================
+ * Front end: recordings of other SDR front ends -> complex64 at the engine's rate.
+ * A streaming stage ahead of acquisition, excision and tracking: decode the samples, mix the IF
+ * or tuner offset to 0 Hz, band-limit and resample from fs_in to fs_out (whole Hz, fs_in / fs_out
+ * in 0.5 .. 64); the output is complex64 at fs_out (1000 * CODE_SAMPLES for the engines).
+ * Decode: GPSMI_FE_C64 complex64; GPSMI_FE_U8IQ the recorder's uint16 (Q << 8 | I), the arithmetic
+ * of gpsmi_dev_unpack_u8iq; GPSMI_FE_SC8 int8 I, Q / 128; GPSMI_FE_SC16 int16 little-endian I, Q
+ * / 32768; GPSMI_FE_R8 real int8 / 128, times 2 (a cosine of amplitude A at IF + f becomes a
+ * complex tone of amplitude A at f).  flags GPSMI_FE_CONJUGATE mirrors complex input.
+ * Mix: x[i] exp(-j 2 pi if_hz i / fs_in), i the absolute input index since create / reset; the
+ * phase is i * inc mod 2^64 in integers (inc = if_hz / fs_in in 0.64 fixed point), its top 24 bits
+ * give the sine and cosine: exact at any offset, whatever the cut of the input into calls.
+ * Resample: output n is the band-limited input at t_n = n fs_in / fs_out input samples, kept as
+ * exact integers (no drift); the filter is centred on t_n (no group delay: output n and a scene
+ * rendered at fs_out share one time base); input before index 0 is zero.  Filter: a Kaiser-windowed
+ * sinc designed in double at create time, K taps, tabulated at L phases per input sample (table
+ * [(L + 1) * K], row j = h(j / L + K/2 - 1 - m)), the two rows around t_n's fraction combined
+ * linearly.  Passband |f| <= passband_hz (0: 0.44 min(fs_in, fs_out)), ripple <= 0.1 dB; anything
+ * that aliases (or, real input, images) into the passband is attenuated by >= atten_db (0: 60).
+ * A configuration that cannot meet this is GPSMI_E_UNSUPPORTED with the reason in
+ * gpsmi_last_error (e.g. the real-input image inside the passband: pass a narrower passband_hz).
+ * push emits every output whose filter support (floor(t_n) - K/2 + 1 .. floor(t_n) + K/2) is in,
+ * so the outputs over a sequence of calls depend only on the total input; a call that would emit
+ * more than max_out is GPSMI_E_ARG and changes nothing.  flush takes zeros past the end and emits
+ * the outputs up to the last input sample; push / flush after it are GPSMI_E_ARG until reset.
+ * Every output is one fixed-order sum computed by one thread (no atomics): the bits do not depend
+ * on the cut of the input, the batch size or the run.  The calls return when the work is done;
+ * gpsmi_fe_last_ms reports the device time of the last one.
+ * ======================================================================== */
+#define GPSMI_FE_C64       0
+#define GPSMI_FE_U8IQ      1
+#define GPSMI_FE_SC8       2
+#define GPSMI_FE_SC16      3
+#define GPSMI_FE_R8        4
+#define GPSMI_FE_CONJUGATE 1    /* gpsmi_fe_cfg.flags bit 0 */
+typedef struct gpsmi_fe gpsmi_fe;
+typedef struct gpsmi_fe_cfg {   /* no implicit padding: 48 bytes                        */
+    int64_t fs_in_hz;           /* input rate, 1 .. 2^31 - 1                           */
+    int64_t fs_out_hz;          /* output rate (1000 * CODE_SAMPLES for the engines)   */
+    double  if_hz;              /* IF (real input) or tuner offset (complex); sign = sideband */
+    float   passband_hz;        /* 0: 0.44 min(fs_in, fs_out)                          */
+    float   atten_db;           /* 0: 60 (20 .. 120)                                   */
+    int32_t format;             /* GPSMI_FE_*                                          */
+    int32_t flags;              /* GPSMI_FE_CONJUGATE (complex input only)             */
+    int32_t max_out;            /* largest output count of one host call (scratch)     */
+    int32_t device;
+} gpsmi_fe_cfg;
+/* host only, no GPU: validates cfg (max_out and device aside) and returns the filter; table
+ * (optional) receives (n_phases + 1) * n_taps floats, row-major as above                       */
+int gpsmi_fe_design(const gpsmi_fe_cfg* cfg, int* n_taps, int* n_phases, float* table);
+int gpsmi_fe_create(const gpsmi_fe_cfg* cfg, gpsmi_fe** out);
+int gpsmi_fe_destroy(gpsmi_fe* h);
+int gpsmi_fe_reset(gpsmi_fe* h);                 /* input index := 0, carry := 0, not flushed */
+/* host in (n_in samples of the format) -> host out (complex64, *n_out of at most max_out)      */
+int gpsmi_fe_push(gpsmi_fe* h, const void* in, size_t n_in, float* out, size_t max_out, size_t* n_out);
+/* the same from device memory to device memory (no max_out limit of the handle)                */
+int gpsmi_fe_push_dev(gpsmi_fe* h, const void* d_in, size_t n_in, void* d_out, size_t max_out,
+                      size_t* n_out);
+/* end of stream: zeros past the last sample; the outputs up to it -> host out                  */
+int gpsmi_fe_flush(gpsmi_fe* h, float* out, size_t max_out, size_t* n_out);
+int gpsmi_fe_last_ms(gpsmi_fe* h, float* ms);
 
 /* ========================================================================
  * Multi-GPU: one process per GPU; SVs / blocks are sharded by the host and

@@ -5,6 +5,7 @@ gpseval) as one command on the GPU path.
 
     python tools/run_file.py <recording.bin> [--seconds S] [--start-stream K] [--save-pickle P]
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--json]
+                             [--format FMT --fs HZ --if HZ --conjugate]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -20,7 +21,11 @@ gpseval.py replays it with LOAD_PICKLE.  --cpu-acq times BASELINE configs[0] bes
 cold acquisition of the reference's numpy path (oracle restatement, test infrastructure) on
 the first five blocks of the same file, on one host core.  --excise removes narrowband
 interference (continuous-wave tones) from every block on the GPU before the receiver sees it
-(pipeline.Receiver(excise=True)).
+(pipeline.Receiver(excise=True)).  --format (c64, u8iq, sc8, sc16, r8), --fs (the
+input rate in Hz), --if (the IF of real input or the tuner offset of complex input, Hz) and
+--conjugate read a recording of another front end: frontend.FrontEnd decodes, mixes, filters and
+resamples it on the GPU to complex64 blocks at 2.048 Msps, which Receiver(raw_u8=False) takes
+(DESIGN.md 4.2c); --start-stream then skips output blocks.  Without them the path above is unchanged.
 
 There is no recording in this repository (data/test.bin is absent from the reference
 checkout, SURVEY F2, and too short for a fix even upstream): tests/test_run_file.py writes a
@@ -61,19 +66,29 @@ def cpu_cold_acquisition(path, n_blocks=5):
 
 
 def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, cpu_acq=False, report_lag=16,
-        excise=False):
+        excise=False, frontend=None):
+    """frontend: None (the recorder's u8 format at 2.048 Msps) or a dict of frontend.FrontEnd's
+    keyword arguments (fs_in, fmt, if_hz, conjugate)."""
     from gpsmi import ingest, position as P
     from gpsmi.engine import Config
     from gpsmi.pipeline import Receiver, save_results
     cfg = Config()
     # (a recording: the datagrams may come out `report_lag` blocks behind the block they belong to, the
     # reader then runs ahead of the GPU instead of stalling it once a second -- pipeline.Receiver)
-    rx = Receiver(cfg, raw_u8=True, report_lag=report_lag, excise=True if excise else None)
+    fe = None
+    if frontend is None:
+        rx = Receiver(cfg, raw_u8=True, report_lag=report_lag, excise=True if excise else None)
+        source = ingest.read_raw_blocks(path, cfg.ngps, start_stream)
+    else:
+        from gpsmi.frontend import FrontEnd
+        fe = FrontEnd(cfg, **frontend)
+        rx = Receiver(cfg, raw_u8=False, report_lag=report_lag, excise=True if excise else None)
+        source = (b for k, b in enumerate(ingest.read_frontend_blocks(path, fe)) if k >= start_stream)
     solver = P.PositionSolver(cfg.code_samples, cfg.n_cyc, ephemerides=ephemerides)
     max_blocks = None if seconds is None else int(seconds * 1000 // cfg.n_cyc)
     fixes, n_dg, n_blocks, found = [], 0, 0, None
     t0 = time.perf_counter()
-    for raw in ingest.read_raw_blocks(path, cfg.ngps, start_stream):
+    for raw in source:
         rx.feed(raw)
         n_blocks += 1
         if found is None and not rx.sweep_all_freq:
@@ -92,6 +107,8 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
         save_results(save_pickle, rx.result_list)
     sats = sorted(rx.act_sat_set)
     rx.close()
+    if fe is not None:
+        fe.close()
     out = {'file': os.path.basename(path), 'blocks': n_blocks, 'signal_s': round(n_blocks * cfg.n_cyc / 1000.0, 3),
            'wall_s': round(wall, 3), 'x_realtime': round(n_blocks * cfg.n_cyc / 1000.0 / wall, 1) if wall else None,
            'acquired': [(int(s), float(f), int(d)) for _, s, f, d in (found or [])],
@@ -123,13 +140,24 @@ def main():
                     help='blocks a datagram may trail the block it belongs to (0: none, as a live receiver)')
     ap.add_argument('--excise', action='store_true',
                     help='remove narrowband interference (CW tones) from every block first (DESIGN.md 4.2b)')
+    ap.add_argument('--format', default=None, choices=['c64', 'u8iq', 'sc8', 'sc16', 'r8'],
+                    help='sample format of another front end (DESIGN.md 4.2c); default u8iq when --fs / --if is given')
+    ap.add_argument('--fs', type=int, default=None, help='input sample rate in Hz (default 2048000)')
+    ap.add_argument('--if', dest='if_hz', type=float, default=None,
+                    help='IF of real input or tuner offset of complex input in Hz (sign: sideband)')
+    ap.add_argument('--conjugate', action='store_true', help='mirror the spectrum of complex input')
     ap.add_argument('--json', action='store_true', help='one JSON line instead of text')
     a = ap.parse_args()
+    frontend = None
+    if a.format is not None or a.fs is not None or a.if_hz is not None or a.conjugate:
+        frontend = {'fmt': a.format or 'u8iq', 'fs_in': a.fs or 2048000, 'if_hz': a.if_hz or 0.0,
+                    'conjugate': a.conjugate}
     eph = None
     if a.ephemeris:
         with open(a.ephemeris) as f:
             eph = {int(k): v for k, v in json.load(f).items()}
-    out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise)
+    out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise,
+              frontend)
     if a.json:
         print(json.dumps(out))
         return
