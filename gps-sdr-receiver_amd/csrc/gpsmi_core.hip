@@ -133,6 +133,7 @@ int gpsmi_abi_sizeof(int which) {
         case 3: return (int)sizeof(gpsmi_trk_out);
         case 4: return (int)offsetof(gpsmi_trk_out, code_phase);
         case 5: return (int)sizeof(gpsmi_fe_cfg);
+        case 6: return (int)sizeof(gpsmi_pb_cfg);
         default: return -1;
     }
 }

@@ -33,6 +33,11 @@ class FeCfg(C.Structure):
                 ('flags', C.c_int32), ('max_out', C.c_int32), ('device', C.c_int32)]
 
 
+class PbCfg(C.Structure):
+    _fields_ = [('block_samples', C.c_int32), ('thresh_db', C.c_float), ('pre', C.c_int32),
+                ('post', C.c_int32), ('max_frac', C.c_float), ('device', C.c_int32)]
+
+
 class Cfg(C.Structure):
     _fields_ = [('code_samples', C.c_int32), ('n_cyc', C.c_int32),
                 ('corr_avg', C.c_int32), ('sweep_corr_avg', C.c_int32),
@@ -98,6 +103,8 @@ EXPORTS = [
     'gpsmi_ifx_apply', 'gpsmi_ifx_apply_dev', 'gpsmi_ifx_last_ms',
     'gpsmi_fe_design', 'gpsmi_fe_create', 'gpsmi_fe_destroy', 'gpsmi_fe_reset', 'gpsmi_fe_push',
     'gpsmi_fe_push_dev', 'gpsmi_fe_flush', 'gpsmi_fe_last_ms',
+    'gpsmi_pb_create', 'gpsmi_pb_destroy', 'gpsmi_pb_set_input_format', 'gpsmi_pb_reset',
+    'gpsmi_pb_apply', 'gpsmi_pb_apply_dev', 'gpsmi_pb_last_ms',
 ]
 
 _lib = None
@@ -204,6 +211,13 @@ def load():
         'gpsmi_fe_push_dev': [vp, vp, sz, vp, sz, P(sz)],
         'gpsmi_fe_flush': [vp, vp, sz, P(sz)],
         'gpsmi_fe_last_ms': [vp, P(f32)],
+        'gpsmi_pb_create': [P(PbCfg), P(vp)],
+        'gpsmi_pb_destroy': [vp],
+        'gpsmi_pb_set_input_format': [vp, C.c_int],
+        'gpsmi_pb_reset': [vp],
+        'gpsmi_pb_apply': [vp, vp, vp, C.c_int, vp, vp, vp],
+        'gpsmi_pb_apply_dev': [vp, vp, vp, C.c_int, vp, vp, vp],
+        'gpsmi_pb_last_ms': [vp, P(f32)],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -212,8 +226,8 @@ def load():
     want = [C.sizeof(Cfg), PEAK_DTYPE.itemsize, STATE_DTYPE.itemsize,
             OUT_DTYPE.itemsize, OUT_DTYPE.fields['code_phase'][1]]
     got = [lib.gpsmi_abi_sizeof(i) for i in range(5)]
-    want.append(C.sizeof(FeCfg))
-    got.append(lib.gpsmi_abi_sizeof(5))
+    want += [C.sizeof(FeCfg), C.sizeof(PbCfg)]
+    got += [lib.gpsmi_abi_sizeof(5), lib.gpsmi_abi_sizeof(6)]
     if want != got:
         raise EngineError(f'ABI mismatch between gpsmi/_lib.py {want} and '
                           f'libgpsmi.so {got}')

@@ -525,6 +525,58 @@ int gpsmi_fe_flush(gpsmi_fe* h, float* out, size_t max_out, size_t* n_out);
 int gpsmi_fe_last_ms(gpsmi_fe* h, float* ms);
 
 /* ========================================================================
+ * Pulse blanking: an opt-in input stage against pulsed and swept (chirp) interference, ahead of
+ * acquisition and tracking.  Works in the time domain, at any block length.
+ * Per block of n = block_samples samples x (complex64, or the recorder's uint16 decoded as
+ * gpsmi_dev_unpack_u8iq does), every step exact in float32 or in integers:
+ *   power      p_i = re*re + im*im in float32 (two products and one add, never fused);
+ *   floor      m = the order statistic of rank (n - 1) / 2 (from 0, ascending) of the block's p,
+ *              ties and zeros included (the lower median);
+ *   threshold  f = (float)10^(thresh_db / 10) in double on the host, T = m * f in float32; sample j
+ *              is a detection when p_j > T (thresh_db = +inf, an all-zero block: none);
+ *   guard      sample i is blanked when a detection j of the same block has i - post <= j <= i + pre,
+ *              or when i < carry, carry = max(0, j + post - n + 1) over the previous block's
+ *              detections (0 after create / reset): output block k depends on input blocks k - 1
+ *              and k only;
+ *   output     blanked samples are 0 + 0j, every other sample is the input bit for bit (complex64);
+ *   too much   more than floor(max_frac * n) blanked samples: the block passes through (the input,
+ *              decoded for u8), count -1, mask empty; its floor is still reported and its carry
+ *              still taken from its detections.
+ * counts int32 [nb] (blanked samples, -1 passed through), floors float32 [nb] (m) and masks uint32
+ * [nb * n / 32] (sample i of block b in bit i % 32 of masks[b * n / 32 + i / 32]) are host arrays;
+ * floors and masks may be null.  nb consecutive blocks in order: block b's carry comes from block
+ * b - 1 (the handle's for b = 0), the handle keeps the last block's.  Input and output must not
+ * overlap (GPSMI_E_ARG); device complex64 input and the output must be 16-byte aligned, device u8
+ * input 4-byte aligned.  Every output word is written by one thread: the bits do not depend on the
+ * grid, the batch size or the cut of the input into calls.  Both calls return when the work is
+ * done; gpsmi_pb_last_ms reports its device time.  Argument errors (a null cfg or handle, a bad n,
+ * pre / post out of range, a NaN threshold, max_frac outside [0, 1], nb <= 0) are GPSMI_E_ARG and
+ * need no GPU; a failed allocation is GPSMI_E_NOMEM and leaves the handle usable.  Tuning only:
+ * the environment variable GPSMI_PB_CHUNK_MIB (read at create; default 0 = the whole call) sets
+ * the input bytes the passes run over at a time; it changes no result.
+ * ======================================================================== */
+typedef struct gpsmi_pb gpsmi_pb;
+typedef struct gpsmi_pb_cfg {
+    int32_t block_samples;      /* n: multiple of 32, >= 2048 (65536, 130944, ...)      */
+    float   thresh_db;          /* 10.0; not NaN; +inf detects nothing                   */
+    int32_t pre, post;          /* guard samples before / after a detection, 0 .. 1024   */
+    float   max_frac;           /* 0.5; in [0, 1]                                        */
+    int32_t device;
+} gpsmi_pb_cfg;
+int gpsmi_pb_create(const gpsmi_pb_cfg* cfg, gpsmi_pb** out);
+int gpsmi_pb_destroy(gpsmi_pb* h);
+/* GPSMI_IQ_C64 (default) or GPSMI_IQ_U8 (the recorder's uint16, decoded on load) */
+int gpsmi_pb_set_input_format(gpsmi_pb* h, int fmt);
+int gpsmi_pb_reset(gpsmi_pb* h);                              /* carry := 0 */
+/* host iq (nb * n samples in the input format) -> host out (complex64 [nb * n])                */
+int gpsmi_pb_apply(gpsmi_pb* h, const void* iq, float* out, int nb, int32_t* counts, float* floors,
+                   uint32_t* masks);
+/* the same from device memory to device memory (the result arrays are host memory)             */
+int gpsmi_pb_apply_dev(gpsmi_pb* h, const void* d_iq, void* d_out, int nb, int32_t* counts,
+                       float* floors, uint32_t* masks);
+int gpsmi_pb_last_ms(gpsmi_pb* h, float* ms);
+
+/* ========================================================================
  * Multi-GPU: one process per GPU; SVs / blocks are sharded by the host and
  * the only exchange is a gather of fixed-size peak records over RCCL.
  * ======================================================================== */

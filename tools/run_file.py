@@ -4,7 +4,7 @@ gpsglob.LIVE_MEAS = False / BIN_DATA; gpsrecv.streamData -> processData -> UDP /
 gpseval) as one command on the GPU path.
 
     python tools/run_file.py <recording.bin> [--seconds S] [--start-stream K] [--save-pickle P]
-                             [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--json]
+                             [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--blank] [--json]
                              [--format FMT --fs HZ --if HZ --conjugate]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
@@ -21,7 +21,9 @@ gpseval.py replays it with LOAD_PICKLE.  --cpu-acq times BASELINE configs[0] bes
 cold acquisition of the reference's numpy path (oracle restatement, test infrastructure) on
 the first five blocks of the same file, on one host core.  --excise removes narrowband
 interference (continuous-wave tones) from every block on the GPU before the receiver sees it
-(pipeline.Receiver(excise=True)).  --format (c64, u8iq, sc8, sc16, r8), --fs (the
+(pipeline.Receiver(excise=True)).  --blank zeroes pulsed and swept (chirp)
+interference sample by sample on the GPU (pipeline.Receiver(blank=True)); with
+--excise the tones are removed first, then the pulses.  --format (c64, u8iq, sc8, sc16, r8), --fs (the
 input rate in Hz), --if (the IF of real input or the tuner offset of complex input, Hz) and
 --conjugate read a recording of another front end: frontend.FrontEnd decodes, mixes, filters and
 resamples it on the GPU to complex64 blocks at 2.048 Msps, which Receiver(raw_u8=False) takes
@@ -66,7 +68,7 @@ def cpu_cold_acquisition(path, n_blocks=5):
 
 
 def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, cpu_acq=False, report_lag=16,
-        excise=False, frontend=None):
+        excise=False, frontend=None, blank=False):
     """frontend: None (the recorder's u8 format at 2.048 Msps) or a dict of frontend.FrontEnd's
     keyword arguments (fs_in, fmt, if_hz, conjugate)."""
     from gpsmi import ingest, position as P
@@ -77,12 +79,14 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
     # reader then runs ahead of the GPU instead of stalling it once a second -- pipeline.Receiver)
     fe = None
     if frontend is None:
-        rx = Receiver(cfg, raw_u8=True, report_lag=report_lag, excise=True if excise else None)
+        rx = Receiver(cfg, raw_u8=True, report_lag=report_lag, excise=True if excise else None,
+                      blank=True if blank else None)
         source = ingest.read_raw_blocks(path, cfg.ngps, start_stream)
     else:
         from gpsmi.frontend import FrontEnd
         fe = FrontEnd(cfg, **frontend)
-        rx = Receiver(cfg, raw_u8=False, report_lag=report_lag, excise=True if excise else None)
+        rx = Receiver(cfg, raw_u8=False, report_lag=report_lag, excise=True if excise else None,
+                      blank=True if blank else None)
         source = (b for k, b in enumerate(ingest.read_frontend_blocks(path, fe)) if k >= start_stream)
     solver = P.PositionSolver(cfg.code_samples, cfg.n_cyc, ephemerides=ephemerides)
     max_blocks = None if seconds is None else int(seconds * 1000 // cfg.n_cyc)
@@ -140,6 +144,8 @@ def main():
                     help='blocks a datagram may trail the block it belongs to (0: none, as a live receiver)')
     ap.add_argument('--excise', action='store_true',
                     help='remove narrowband interference (CW tones) from every block first (DESIGN.md 4.2b)')
+    ap.add_argument('--blank', action='store_true',
+                    help='zero pulsed / chirp interference in every block (after --excise, DESIGN.md 4.2d)')
     ap.add_argument('--format', default=None, choices=['c64', 'u8iq', 'sc8', 'sc16', 'r8'],
                     help='sample format of another front end (DESIGN.md 4.2c); default u8iq when --fs / --if is given')
     ap.add_argument('--fs', type=int, default=None, help='input sample rate in Hz (default 2048000)')
@@ -157,7 +163,7 @@ def main():
         with open(a.ephemeris) as f:
             eph = {int(k): v for k, v in json.load(f).items()}
     out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise,
-              frontend)
+              frontend, a.blank)
     if a.json:
         print(json.dumps(out))
         return
