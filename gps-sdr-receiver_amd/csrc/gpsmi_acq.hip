@@ -17,6 +17,9 @@
 //   acq_spectrum_nc_kernel, acq_nc_corr_kernel, acq_fold_nc_kernel + pfa_corr_kernel<2>
 //                         the non-coherent search (gpsmi_acq_search_nc): the
 //                         mean of |corr| over n_seg segments, summed in registers per cell.
+//   acq_deep_corr_kernel + pfa_corr_kernel<3>
+//                         the deep search (gpsmi_acq_search_deep): the same mean
+//                         with every segment's magnitudes rotated by the code-Doppler slide.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -274,6 +277,74 @@ __global__ __launch_bounds__(256) void acq_nc_corr_kernel(
     }
 }
 
+// Deep search (gpsmi_acq_search_deep): acq_nc_corr_kernel with the magnitudes of
+// segment s added at the lag they had at the start of the data, S[i] += |corr_s[(i + m) mod 2048]|,
+// m = shift[bin][s] in 0 .. 2047 (the code-Doppler slide, one integer per bin and segment from the
+// host).  The magnitude a sum needs now comes from another thread: a segment's 2048 magnitudes go
+// through LDS once, unscaled, in the plane the statistics use as their copy (the transform's buffer
+// 1, free once its last exchange barrier is passed), and thread t picks up its eight lags at
+// (t + 256 q + m) mod 2048 -- consecutive lanes read consecutive floats, rotated as a whole: no bank
+// conflicts.  The scale 1 / 2048 is applied where acq_nc_corr_kernel applies it, in the addition,
+// so with m = 0 every sum sees that kernel's operations on the same bits.  m is uniform per
+// workgroup and segment (a scalar load, issued ahead of the transform like the next spectrum).
+// Barriers per segment: the loop's own (the reads of the previous segment's magnitudes are done
+// before the next transform's second pass overwrites the plane) and one between writing and reading.
+__global__ __launch_bounds__(256) void acq_deep_corr_kernel(
+    const float2* __restrict__ spectra, const float2* __restrict__ rep,
+    const int* __restrict__ slot, gpsmi_peak* __restrict__ out, int nsv, int nseg, int bin0,
+    const float2* __restrict__ tw, float2* __restrict__ nbr, const int* __restrict__ shift) {
+    __shared__ __attribute__((aligned(16))) float lds[kFftLdsFloats];
+    __shared__ float red[kStatsRedFloats];
+    __shared__ __attribute__((aligned(16))) float lds_tw[kFftTwFloats];
+    float* magbuf = lds + 2 * kFftPlane;
+    const int t = threadIdx.x, sv = blockIdx.x, bin = blockIdx.y;
+    const FftTw ftw = fft_setup(lds_tw, tw, t);
+    const float2* X = spectra + (size_t)bin * nseg * kFftN;
+    const float2* R = rep + (size_t)slot[sv] * kFftN;
+    const int* M = shift + (size_t)bin * nseg;
+    float2 r[8], x[8];
+    float acc[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        r[q] = R[t + 256 * q];
+        x[q] = X[t + 256 * q];
+        acc[q] = 0.f;
+    }
+#pragma unroll 1
+    for (int s = 0; s < nseg; ++s) {
+        float2 v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            v[q] = make_float2(x[q].x * r[q].x + x[q].y * r[q].y, x[q].x * r[q].y - x[q].y * r[q].x);
+        const float2* Xn = X + (size_t)(s + 1 < nseg ? s + 1 : s) * kFftN;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x[q] = Xn[t + 256 * q];
+        const int m = __builtin_amdgcn_readfirstlane(M[s]);
+        lds_barrier();                         // (the previous segment's LDS reads are done)
+        fft2048(v, lds, ftw, t);
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            magbuf[t + 256 * q] = __builtin_amdgcn_sqrtf(v[q].x * v[q].x + v[q].y * v[q].y);
+        lds_barrier();
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            acc[q] += magbuf[(t + 256 * q + m) & (kFftN - 1)] * (1.0f / kFftN);
+    }
+    lds_barrier();                             // (the statistics write the plane the sums just read)
+    const float sc = 1.0f / (float)nseg;
+    float mag[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) mag[q] = acc[q] * sc;
+    int amax; float peak, mean, sd, lo, hi;
+    corr_stats8(mag, t, magbuf, red, amax, peak, mean, sd, lo, hi);
+    if (t == 0) {
+        const size_t c = (size_t)(bin0 + bin) * nsv + sv;
+        gpsmi_peak p; p.argmax = amax; p.peak = peak; p.mean = mean; p.std = sd;
+        out[c] = p;
+        if (nbr) nbr[c] = make_float2(lo, hi);
+    }
+}
+
 // Native 16368 path: the fold of segment s of a bin, acq_fold_kernel's arithmetic on iq advanced by
 // s * n_coh * L samples.  Grid (lag blocks, bins of this launch, segments); xout [bin][nseg][L].
 template <int FMT>
@@ -341,6 +412,8 @@ struct gpsmi_acq {
     // non-coherent search: the per-(bin, segment) spectra (CS = 2048) or folded samples (16368) of
     // one chunk of bins, sized per call (gpsmi_acq_search_nc)
     float2* d_nc = nullptr; size_t nc_cap = 0;
+    // deep search: the lag rotation of every (bin, segment) of a call (gpsmi_acq_search_deep)
+    int* d_shift = nullptr; size_t shift_cap = 0;
     int iq_fmt = GPSMI_IQ_C64;              // what the iq pointers of the search calls point to
     float last_ms = 0.f;
     bool pending = false;
@@ -459,7 +532,8 @@ int gpsmi_acq_destroy(gpsmi_acq* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* bufs[] = {h->d_tw, h->d_t32, h->d_rep, h->d_iq, h->d_spec, h->d_omega, h->d_slot,
                     h->d_peaks, h->d_nbr, h->d_rep_time, h->d_fold, h->d_mag, h->d_stats,
-                    h->d_xsel, h->d_rsel, h->d_twN, h->d_RS, h->d_S, h->d_RSp, h->d_nc};
+                    h->d_xsel, h->d_rsel, h->d_twN, h->d_RS, h->d_S, h->d_RSp, h->d_nc,
+                    h->d_shift};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (int k = 0; k < 2; ++k) {
@@ -651,10 +725,34 @@ static int nc_grow(void** p, size_t* cap, size_t bytes) {
 // segments.  Longer searches take the bins in chunks; the magnitude sums stay in registers.
 constexpr size_t kNcScratchMax = size_t(512) << 20;
 
+// The deep search (gpsmi_acq_search_deep) is the non-coherent one plus a lag rotation per (bin,
+// segment): what the rotation is computed from.
+struct DeepShift { double carrier_hz, f_offset_hz; };
+
+// m[b][s] mod cs of gpsmi.h, in 0 .. cs - 1: float64 in the order written there, ties to even
+static int deep_shift(double f_hz, const DeepShift& d, int s, int n_coh, int cs) {
+    const double m = std::nearbyint(-(f_hz - d.f_offset_hz) / d.carrier_hz * (double)s * (double)n_coh *
+                                    (double)cs);
+    const double r = std::fmod(m, (double)cs);           // exact: both are integers
+    return (int)(r < 0.0 ? r + (double)cs : r);
+}
+
+// a bin's rotated sums need all its segments in one launch: no chunking over segments
+static int deep_span_check(int n_seg, int cs) {
+    if ((size_t)n_seg * cs * sizeof(float2) > kNcScratchMax)
+        return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_search_deep: the %d segments of one bin exceed the "
+                                         "%zu MiB of scratch", n_seg, kNcScratchMax >> 20);
+    return GPSMI_OK;
+}
+
 static int acq_search_nc_impl(gpsmi_acq* h, const void* d_iq, size_t n, const int32_t* prn, int nsv,
                               const double* freqs, int nbins, int n_coh, int n_seg, gpsmi_peak* out,
-                              void* out_dev, float* nbr) {
+                              void* out_dev, float* nbr, const DeepShift* deep = nullptr) {
     GPSMI_REQUIRE(h && d_iq && prn && freqs, "null argument");
+    if (deep) {
+        GPSMI_REQUIRE(std::isfinite(deep->carrier_hz) && deep->carrier_hz > 0.0, "carrier_hz must be positive");
+        GPSMI_REQUIRE(std::isfinite(deep->f_offset_hz), "f_offset_hz must be finite");
+    }
     GPSMI_REQUIRE(out || out_dev, "no output requested");
     GPSMI_REQUIRE(nsv >= 0 && nsv <= GPSMI_MAX_PRN, "nsv out of range");
     GPSMI_REQUIRE(nbins >= 0 && nbins <= 65535, "nbins out of range");
@@ -668,8 +766,15 @@ static int acq_search_nc_impl(gpsmi_acq* h, const void* d_iq, size_t n, const in
             return fail(GPSMI_E_STATE, "no replica set for PRN %d", (int)prn[i]);
     }
     if (h->direct && !h->pfa)
-        return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_search_nc: code_samples 2048 or the native 16368 "
-                                         "correlation only (not the \"codephase\" time-domain paths)");
+        return fail(GPSMI_E_UNSUPPORTED, "%s: code_samples 2048 or the native 16368 "
+                                         "correlation only (not the \"codephase\" time-domain paths)",
+                    deep ? "gpsmi_acq_search_deep" : "gpsmi_acq_search_nc");
+    const size_t per_bin = (size_t)n_seg * cs * sizeof(float2);
+    if (deep) {
+        for (int b = 0; b < nbins; ++b)
+            GPSMI_REQUIRE(std::isfinite(freqs[b]), "freqs_hz must be finite");
+        if (deep_span_check(n_seg, cs)) return GPSMI_E_UNSUPPORTED;
+    }
     // one segment of the 16368 path: the coherent search itself (MODE 0 forms its statistics from the
     // unscaled squares; MODE 2's would differ in the last bits of std)
     if (h->pfa && n_seg == 1)
@@ -679,7 +784,6 @@ static int acq_search_nc_impl(gpsmi_acq* h, const void* d_iq, size_t n, const in
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     int rc = acq_reserve(h, nbins, nsv);
     if (rc) return rc;
-    const size_t per_bin = (size_t)n_seg * cs * sizeof(float2);
     size_t nbc = kNcScratchMax / per_bin;
     nbc = nbc < 1 ? 1 : nbc > (size_t)nbins ? (size_t)nbins : nbc;
     rc = nc_grow((void**)&h->d_nc, &h->nc_cap, nbc * per_bin);
@@ -700,6 +804,23 @@ static int acq_search_nc_impl(gpsmi_acq* h, const void* d_iq, size_t n, const in
     }
     rc = acq_stage(h, prn, nsv, freqs, nbins);
     if (rc) return rc;
+    if (deep) {
+        std::vector<int> shift;
+        const size_t ns = (size_t)nbins * n_seg;
+        try { shift.resize(ns); } catch (const std::bad_alloc&) {
+            return fail(GPSMI_E_NOMEM, "gpsmi_acq_search_deep: out of host memory");
+        }
+        for (int b = 0; b < nbins; ++b)
+            for (int s = 0; s < n_seg; ++s)
+                shift[(size_t)b * n_seg + s] = deep_shift(freqs[b], *deep, s, n_coh, cs);
+        size_t bytes = h->shift_cap * sizeof(int);
+        rc = nc_grow((void**)&h->d_shift, &bytes, ns * sizeof(int));
+        h->shift_cap = h->d_shift ? (bytes / sizeof(int)) : 0;
+        if (rc) return rc;
+        GPSMI_HIP(hipMemcpyAsync(h->d_shift, shift.data(), ns * sizeof(int), hipMemcpyHostToDevice,
+                                 h->stream));
+        GPSMI_HIP(hipStreamSynchronize(h->stream));      // (the table is pageable and leaves scope here)
+    }
     const bool u8 = h->iq_fmt == GPSMI_IQ_U8;
     GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
     for (int b0 = 0; b0 < nbins; b0 += (int)nbc) {
@@ -716,8 +837,12 @@ static int acq_search_nc_impl(gpsmi_acq* h, const void* d_iq, size_t n, const in
             const int c0 = b0 * nsv, ncc = nb * nsv;
             hipLaunchKernelGGL(acq_cells_kernel, dim3((ncc + 255) / 256), dim3(256), 0, h->stream,
                                h->d_xsel + c0, h->d_rsel + c0, h->d_slot, nsv, ncc);
-            pfa_nc_corr_launch(h->stream, h->d_nc, h->d_xsel + c0, h->d_rsel + c0, ncc, n_seg, h->d_RSp,
-                               h->d_stats + c0);
+            if (deep)
+                pfa_deep_corr_launch(h->stream, h->d_nc, h->d_xsel + c0, h->d_rsel + c0, ncc, n_seg,
+                                     h->d_RSp, h->d_stats + c0, h->d_shift + (size_t)b0 * n_seg);
+            else
+                pfa_nc_corr_launch(h->stream, h->d_nc, h->d_xsel + c0, h->d_rsel + c0, ncc, n_seg, h->d_RSp,
+                                   h->d_stats + c0);
         } else {
             const dim3 grid(nb, n_seg);
             if (n_coh >= 4 && u8)
@@ -732,9 +857,14 @@ static int acq_search_nc_impl(gpsmi_acq* h, const void* d_iq, size_t n, const in
             else
                 hipLaunchKernelGGL((acq_spectrum_nc_kernel<1, 0>), grid, dim3(256), 0, h->stream, d_iq,
                                    h->d_t32, om, n_coh, n_seg, h->d_nc, h->d_tw);
-            hipLaunchKernelGGL(acq_nc_corr_kernel, dim3(nsv, nb), dim3(256), 0, h->stream, h->d_nc,
-                               h->d_rep, h->d_slot, h->d_peaks, nsv, n_seg, b0, h->d_tw,
-                               nbr ? h->d_nbr : nullptr);
+            if (deep)
+                hipLaunchKernelGGL(acq_deep_corr_kernel, dim3(nsv, nb), dim3(256), 0, h->stream, h->d_nc,
+                                   h->d_rep, h->d_slot, h->d_peaks, nsv, n_seg, b0, h->d_tw,
+                                   nbr ? h->d_nbr : nullptr, h->d_shift + (size_t)b0 * n_seg);
+            else
+                hipLaunchKernelGGL(acq_nc_corr_kernel, dim3(nsv, nb), dim3(256), 0, h->stream, h->d_nc,
+                                   h->d_rep, h->d_slot, h->d_peaks, nsv, n_seg, b0, h->d_tw,
+                                   nbr ? h->d_nbr : nullptr);
         }
     }
     if (h->pfa)
@@ -799,14 +929,16 @@ int gpsmi_acq_search_nc_dev(gpsmi_acq* h, const void* d_iq, size_t n, const int3
     return acq_search_nc_impl(h, d_iq, n, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, out_dev, nullptr);
 }
 
-int gpsmi_acq_search_nc(gpsmi_acq* h, const void* iq, size_t n, const int32_t* prn, int nsv,
-                        const double* freqs_hz, int nbins, int n_coh, int n_seg, gpsmi_peak* out,
-                        float* nbr) {
+// host input of the non-coherent and the deep search: upload, then the search on the copy
+static int acq_search_nc_host(gpsmi_acq* h, const void* iq, size_t n, const int32_t* prn, int nsv,
+                              const double* freqs_hz, int nbins, int n_coh, int n_seg, gpsmi_peak* out,
+                              float* nbr, const DeepShift* deep) {
     GPSMI_REQUIRE(h && iq && out, "null argument");
     GPSMI_REQUIRE(n_coh >= 1 && n_coh <= h->cfg.n_cyc, "n_coh out of range 1..n_cyc");
     GPSMI_REQUIRE(n_seg >= 1 && n_seg <= 65535, "n_seg out of range 1..65535");
     GPSMI_REQUIRE(n / ((size_t)n_coh * h->cfg.code_samples) >= (size_t)n_seg,
                   "iq shorter than n_seg * n_coh code periods");
+    if (deep && deep_span_check(n_seg, h->cfg.code_samples)) return GPSMI_E_UNSUPPORTED;   // (before the upload)
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     const size_t need = (size_t)n_seg * n_coh * h->cfg.code_samples;
     if (need > h->iq_cap) {                  // (iq_cap counts complex64 samples)
@@ -817,7 +949,28 @@ int gpsmi_acq_search_nc(gpsmi_acq* h, const void* iq, size_t n, const int32_t* p
     }
     GPSMI_HIP(hipMemcpyAsync(h->d_iq, iq, need * (h->iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)),
                              hipMemcpyHostToDevice, h->stream));
-    return acq_search_nc_impl(h, h->d_iq, need, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, nullptr, nbr);
+    return acq_search_nc_impl(h, h->d_iq, need, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, nullptr, nbr,
+                              deep);
+}
+
+int gpsmi_acq_search_nc(gpsmi_acq* h, const void* iq, size_t n, const int32_t* prn, int nsv,
+                        const double* freqs_hz, int nbins, int n_coh, int n_seg, gpsmi_peak* out,
+                        float* nbr) {
+    return acq_search_nc_host(h, iq, n, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, nbr, nullptr);
+}
+
+int gpsmi_acq_search_deep(gpsmi_acq* h, const void* iq, size_t n, const int32_t* prn, int nsv,
+                          const double* freqs_hz, int nbins, int n_coh, int n_seg, double carrier_hz,
+                          double f_offset_hz, gpsmi_peak* out, float* nbr) {
+    const DeepShift d{carrier_hz, f_offset_hz};
+    return acq_search_nc_host(h, iq, n, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, nbr, &d);
+}
+
+int gpsmi_acq_search_deep_dev(gpsmi_acq* h, const void* d_iq, size_t n, const int32_t* prn, int nsv,
+                              const double* freqs_hz, int nbins, int n_coh, int n_seg, double carrier_hz,
+                              double f_offset_hz, gpsmi_peak* out, void* out_dev) {
+    const DeepShift d{carrier_hz, f_offset_hz};
+    return acq_search_nc_impl(h, d_iq, n, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, out_dev, nullptr, &d);
 }
 
 int gpsmi_acq_set_input_format(gpsmi_acq* h, int fmt) {

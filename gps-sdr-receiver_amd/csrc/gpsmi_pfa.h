@@ -205,6 +205,16 @@ __device__ __forceinline__ void pfa_slab33(fft_c* base) {
 //         in registers (ascending s), scales the sums by 1 / nseg, and the statistics run once, on
 //         them (the sum of squares then of the scaled values).  The next segment's samples are
 //         requested at the start of P5.
+// MODE 3: deep search (gpsmi_acq_search_deep): MODE 2 with the magnitudes of segment s added at the lag
+//         they had at the start of the data, S[n] += |corr_s[(n + m) mod L]|, m = shift[xsel[c] * nseg + s]
+//         in 0 .. L - 1 (the table arrives in the parameter `rep`, which MODE 2 leaves unused: the
+//         kernel's signature, and with it the code of the other modes, stays as it was).  A rotation
+//         moves a lag to another thread, so every segment's magnitudes go to the thread's own LDS
+//         slots (unscaled: the scale is applied in the addition, where MODE 2 applies it), a barrier
+//         follows, the thread adds its 16 lags from where they now are, and a second barrier keeps
+//         the next P1 (or the final sums) from overwriting slots still being read.  With
+//         m = 1023 mj + mc the lag t + 1023 j + m lies at column c' = (t + mc) mod 1023 -- one sigma
+//         per thread and segment -- in row (j + mj + carry) mod 16.
 template <int MODE>
 __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
     const float2* __restrict__ x, const float* __restrict__ rep, const int* __restrict__ xsel,
@@ -220,7 +230,7 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
     int cell_end = MODE == 0 ? cell0 + ncell : cell0 + 1;
     int seg = 0, nseg = 1;
     float acc[16];
-    if constexpr (MODE == 2) {
+    if constexpr (MODE >= 2) {
         nseg = cell0;
         cell = (int)blockIdx.x;
         cell_end = ncell;
@@ -246,7 +256,7 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
     auto request = [&](int c, int sg) {
         if (MODE != 1) {
             if (c >= cell_end) { c = cell_end - 1; sg = 0; }
-            const int sel = MODE == 2 ? __builtin_amdgcn_readfirstlane(xsel[c] * nseg + sg)
+            const int sel = MODE >= 2 ? __builtin_amdgcn_readfirstlane(xsel[c] * nseg + sg)
                                       : __builtin_amdgcn_readfirstlane(xsel[c]);
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
                 const_cast<float2*>(x) + (size_t)sel * kPfaL, 0, kPfaL * (int)sizeof(float2), 0x00020000);
@@ -403,7 +413,49 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
     // per thread are requested right here and arrive under the reductions and barriers.
     float sm = 0.f, s2 = 0.f, bv = -1.f;
     int bi = 0x7fffffff;
-    if constexpr (MODE == 2) {
+    if constexpr (MODE == 3) {
+        const bool last = seg + 1 == nseg;
+        const int m = __builtin_amdgcn_readfirstlane(
+            reinterpret_cast<const int*>(rep)[xsel[cell] * nseg + seg]);
+        request(last ? cell + (int)gridDim.x : cell, last ? 0 : seg + 1);
+        if (t < kPfaC) {
+            fft_c v[16];
+            v[0] = data[sig];
+#pragma unroll
+            for (int k = 1; k < 16; ++k) v[k] = cmulp(data[k * kPfaPitch + sig], tw16[(t * k) & 15]);
+            pfa_fft16(v);
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                data[j * kPfaPitch + sig].x = __builtin_amdgcn_sqrtf(v[j].x * v[j].x + v[j].y * v[j].y);
+        }
+        lds_barrier();
+        if (t < kPfaC) {
+            const int mj = m / kPfaC, c1 = t + (m - mj * kPfaC);
+            const bool carry = c1 >= kPfaC;
+            const int sigr = pfa_sigma(carry ? c1 - kPfaC : c1), jr = mj + (carry ? 1 : 0);
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                acc[j] += data[((j + jr) & 15) * kPfaPitch + sigr].x * (1.0f / kPfaL);
+        }
+        lds_barrier();                          // (every rotated read is done: the slots may be written)
+        if (!last) {
+            ++seg;
+            p1();
+            continue;
+        }
+        if (t < kPfaC) {
+            const float sc = 1.0f / (float)nseg;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const float m = acc[j] * sc;
+                acc[j] = 0.f;
+                sm += m;
+                s2 += m * m;
+                if (m > bv) { bv = m; bi = t + kPfaC * j; }
+                data[j * kPfaPitch + sig].x = m;
+            }
+        }
+    } else if constexpr (MODE == 2) {
         const bool last = seg + 1 == nseg;
         request(last ? cell + (int)gridDim.x : cell, last ? 0 : seg + 1);
         if (t < kPfaC) {
@@ -450,7 +502,7 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
         }
     }
     PFA_STAMP(5);
-    if constexpr (MODE != 2) request(cell + (MODE == 0 ? (int)gridDim.x : 1), 0);
+    if constexpr (MODE < 2) request(cell + (MODE == 0 ? (int)gridDim.x : 1), 0);
     PFA_STAMP(8);
     sm = wave_sum_dpp(sm);
     s2 = wave_sum_dpp(s2);
@@ -481,8 +533,8 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
                 const double inv_l = 1.0 / (double)kPfaL;
                 // population variance from the two sums (the squares were summed unscaled)
                 const double mean = dsm * inv_l;
-                // (MODE 2 summed the squares of the scaled values)
-                const double var = MODE == 2 ? ds2 * inv_l - mean * mean
+                // (MODES 2 and 3 summed the squares of the scaled values)
+                const double var = MODE >= 2 ? ds2 * inv_l - mean * mean
                                              : ds2 * (inv_l * inv_l * inv_l) - mean * mean;
                 DirStats r;
                 r.argmax = pi;
@@ -529,6 +581,19 @@ inline void pfa_nc_corr_launch(hipStream_t stream, const float2* x, const int* x
     const int grid = ncell < n_cu ? ncell : n_cu;
     hipLaunchKernelGGL(pfa_corr_kernel<2>, dim3(grid), dim3(kPfaThreads), 0, stream, x,
                        (const float*)nullptr, xsel, rsel, RS, nseg, ncell, stats);
+}
+
+// the deep form (MODE 3): pfa_nc_corr_launch plus shift [xsel][nseg], the lag rotation of every
+// (bin, segment) of the launch, each in 0 .. L - 1
+inline void pfa_deep_corr_launch(hipStream_t stream, const float2* x, const int* xsel, const int* rsel,
+                                 int ncell, int nseg, float2* RS, DirStats* stats, const int* shift) {
+    if (ncell <= 0) return;
+    int dev = 0, n_cu = 256;
+    if (hipGetDevice(&dev) == hipSuccess)
+        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+    const int grid = ncell < n_cu ? ncell : n_cu;
+    hipLaunchKernelGGL(pfa_corr_kernel<3>, dim3(grid), dim3(kPfaThreads), 0, stream, x,
+                       reinterpret_cast<const float*>(shift), xsel, rsel, RS, nseg, ncell, stats);
 }
 
 // spectrum of the replica in slot `slot` (rep_slot0 = table of real replicas [slots][L])

@@ -84,6 +84,7 @@ EXPORTS = [
     'gpsmi_acq_search', 'gpsmi_acq_search_dev', 'gpsmi_acq_search_ex',
     'gpsmi_acq_search_dev_async', 'gpsmi_acq_wait',
     'gpsmi_acq_search_nc', 'gpsmi_acq_search_nc_dev',
+    'gpsmi_acq_search_deep', 'gpsmi_acq_search_deep_dev',
     'gpsmi_acq_last_ms',
     'gpsmi_trk_create', 'gpsmi_trk_destroy', 'gpsmi_trk_set_replica',
     'gpsmi_trk_open', 'gpsmi_trk_close', 'gpsmi_trk_get_state',
@@ -154,6 +155,10 @@ def load():
                                 vp, vp],
         'gpsmi_acq_search_nc_dev': [vp, vp, sz, vp, C.c_int, vp, C.c_int, C.c_int,
                                     C.c_int, vp, vp],
+        'gpsmi_acq_search_deep': [vp, vp, sz, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                  C.c_double, C.c_double, vp, vp],
+        'gpsmi_acq_search_deep_dev': [vp, vp, sz, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                      C.c_double, C.c_double, vp, vp],
         'gpsmi_acq_last_ms': [vp, P(f32)],
         'gpsmi_trk_create': [P(Cfg), C.c_int, P(vp)],
         'gpsmi_trk_destroy': [vp],

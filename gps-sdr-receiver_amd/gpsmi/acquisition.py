@@ -96,6 +96,32 @@ class Acquisition:
                     satLst.remove(s)
         return sorted(satFound, reverse=True)
 
+    def sweepDeepSats(self, data, freqs, satLst, satFound, n_coh=4, n_seg=250, f_offset=0.0):
+        """sweepWeakSats's first-hit contract over the deep surface (AcqEngine.search_deep: the
+        non-coherent mean with every segment's magnitudes moved back by the code-Doppler slide
+        of its bin, so that spans of seconds keep their peak): bins scanned in order, the first
+        normMaxCorr > CORR_MIN claims an SV; ``satLst`` and ``satFound`` are mutated in place,
+        entries are ``(normMaxCorr, satNo, freq, delay)`` with the code phase at the start of
+        `data`; returns ``sorted(satFound, reverse=True)``.  `f_offset`: what the bin frequencies
+        differ from the true Doppler by (a tuner's frequency error), 0 when they are Dopplers."""
+        c = self.cfg
+        freqs = list(freqs)
+        if freqs and satLst:
+            prns = list(satLst)
+            table = self.engine.search_deep(data, prns, freqs, n_coh, n_seg, f_offset=f_offset)
+            for b, f in enumerate(freqs):
+                hit = []
+                for j, s in enumerate(prns):
+                    if s not in satLst:
+                        continue
+                    nmc = norm_max_corr(table[b, j])
+                    if nmc > c.corr_min:
+                        satFound.append((nmc, s, f, int(table[b, j]['argmax'])))
+                        hit.append(s)
+                for s in hit:
+                    satLst.remove(s)
+        return sorted(satFound, reverse=True)
+
     def search_table(self, data, prns, freqs, n_avg):
         """The whole surface, no pruning (BASELINE configs 2 and 4)."""
         return self.engine.search(data, prns, freqs, n_avg)

@@ -228,6 +228,36 @@ class AcqEngine:
                 'gpsmi_acq_search_nc')
         return (out, nb) if nbr else out
 
+    L1_HZ = 1575.42e6
+
+    def search_deep(self, iq, prns, freqs, n_coh, n_seg, f_offset=0.0, carrier_hz=L1_HZ,
+                    out_dev=None, nbr=False):
+        """Deep search (gpsmi_acq_search_deep): search_noncoherent with the code Doppler
+        compensated, for spans of seconds.  The magnitudes of segment s of bin f are added at the
+        lag they had at the start of iq: rotated by rint(-(f - f_offset) / carrier_hz * s * n_coh *
+        code_samples) samples.  f_offset: what the bin frequencies differ from the true Doppler
+        by (a tuner's frequency error).  Arguments and returns otherwise as search_noncoherent;
+        the argmax is the code phase at the start of iq."""
+        prn_a = np.ascontiguousarray(prns, dtype=np.int32)
+        f_a = np.ascontiguousarray(freqs, dtype=np.float64)
+        out = np.zeros((len(f_a), len(prn_a)), dtype=PEAK_DTYPE)
+        nb = np.zeros((len(f_a), len(prn_a), 2), dtype=np.float32) if nbr else None
+        if isinstance(iq, tuple):
+            if nbr:
+                raise ValueError('nbr is returned for host input only')
+            d_iq, n = iq
+            check(self.lib.gpsmi_acq_search_deep_dev(
+                self.h, d_iq, n, ptr(prn_a), len(prn_a), ptr(f_a), len(f_a),
+                int(n_coh), int(n_seg), float(carrier_hz), float(f_offset), ptr(out), out_dev),
+                'gpsmi_acq_search_deep_dev')
+        else:
+            iq = self._host_iq(iq)
+            check(self.lib.gpsmi_acq_search_deep(
+                self.h, ptr(iq), iq.size, ptr(prn_a), len(prn_a), ptr(f_a), len(f_a),
+                int(n_coh), int(n_seg), float(carrier_hz), float(f_offset), ptr(out),
+                ptr(nb) if nbr else None), 'gpsmi_acq_search_deep')
+        return (out, nb) if nbr else out
+
     def search_async(self, d_iq, n, prns, freqs, n_avg, out, out_dev=None):
         """Enqueue a search on device-resident iq; `out` is a pinned PEAK_DTYPE
         array [nbins, nsv] filled when wait() returns."""

@@ -203,7 +203,8 @@ int gpsmi_acq_wait(gpsmi_acq* h);
  * gpsmi_acq_search_dev).  gpsmi_acq_last_ms reports the call.
  * The argmax is the code phase at the start of segment 0: code Doppler moves the code by
  * |f| / 1575.42e6 * fs * span samples over the span searched -- 0.65 samples per 100 ms at 5 kHz and
- * 2.048 Msps, 8 times that at 16.368 Msps -- which smears the peak and is not compensated.
+ * 2.048 Msps, 8 times that at 16.368 Msps -- which smears the peak and is not compensated (by this
+ * call: gpsmi_acq_search_deep below compensates it).
  * code_samples = 2048 and the native 16368 correlation only: a handle forced onto a time-domain
  * path (option "codephase" 1 or 2, or another code length) returns GPSMI_E_UNSUPPORTED.  Scratch is
  * sized per call (bins are taken in chunks of at most 512 MiB of spectra); an allocation the device
@@ -216,6 +217,42 @@ int gpsmi_acq_search_nc_dev(gpsmi_acq* h, const void* d_iq, size_t n,
                             const int32_t* prn, int nsv,
                             const double* freqs_hz, int nbins, int n_coh, int n_seg,
                             gpsmi_peak* out, void* out_dev);
+/* Deep search: the non-coherent search with the code Doppler compensated, for spans of seconds.
+ * The code slides against the sample clock by -f / carrier_hz samples per sample (f the Doppler),
+ * so over s segments a satellite's correlation peak has moved by that times s * n_coh *
+ * code_samples lags; the magnitudes of segment s are therefore added at the lag they had at the
+ * start of iq.  Arguments as gpsmi_acq_search_nc[_dev], plus
+ *   carrier_hz   the carrier the Doppler scales with (1575.42e6 for L1), finite and > 0;
+ *   f_offset_hz  what the caller's bin frequencies differ from the true Doppler by (a tuner's ppm
+ *                error appears as a common offset of every bin but does not move the code), finite;
+ *                0 when freqs_hz are true Dopplers.
+ * Segment s of bin b is computed exactly as in gpsmi_acq_search_nc (same wipe-off restart at phase
+ * 0, same float32 arithmetic, same scaling).  With the integer circular shift
+ *     m[b][s] = rint(-(freqs_hz[b] - f_offset_hz) / carrier_hz * s * n_coh * code_samples)
+ * (float64, evaluated left to right, ties to even; computed on the host and uploaded as a table)
+ *     S[i] = (1 / n_seg) * sum_s |corr_s[(i + m[b][s]) mod code_samples]|   (float32, ascending s)
+ * and out / nbr / out_dev are gpsmi_acq_search_nc's records of S.  The argmax is the code phase at
+ * the START of iq (segment 0 is never shifted), as in gpsmi_acq_search_nc.  Where every m is 0 -- a
+ * 0 Hz bin, or a span too short to slide half a sample -- the records are gpsmi_acq_search_nc's,
+ * byte for byte; the results of a bin do not depend on which other bins share the call.
+ * n_seg 1..65535 as long as the segments of ONE bin fit the scratch of 512 MiB (n_seg *
+ * code_samples * 8 bytes: 32768 segments at 2048, 4100 at 16368); beyond that GPSMI_E_UNSUPPORTED
+ * (no chunking over segments).  Bins are taken in chunks as in gpsmi_acq_search_nc.
+ * code_samples 2048 and the native 16368 correlation only: another length or a handle forced onto
+ * a time-domain path (option "codephase" 1 or 2) returns GPSMI_E_UNSUPPORTED.  iq in the handle's
+ * input format (GPSMI_IQ_U8 gives the same bytes as complex64); allocation failures as in
+ * gpsmi_acq_search_nc; gpsmi_acq_last_ms reports the call.  Not compensated: fractions of a
+ * sample, and a Doppler that changes over the span.                                           */
+int gpsmi_acq_search_deep(gpsmi_acq* h, const void* iq, size_t n,
+                          const int32_t* prn, int nsv,
+                          const double* freqs_hz, int nbins, int n_coh, int n_seg,
+                          double carrier_hz, double f_offset_hz,
+                          gpsmi_peak* out, float* nbr);
+int gpsmi_acq_search_deep_dev(gpsmi_acq* h, const void* d_iq, size_t n,
+                              const int32_t* prn, int nsv,
+                              const double* freqs_hz, int nbins, int n_coh, int n_seg,
+                              double carrier_hz, double f_offset_hz,
+                              gpsmi_peak* out, void* out_dev);
 /* Input format of the iq pointers of the search calls that follow (host or device), as
  * gpsmi_trk_set_input_format below: GPSMI_IQ_U8 = the raw recording of streamData
  * (gpsrecv.py:162-173), decoded where the carrier wipe-off reads it; same bits out.   */

@@ -5,7 +5,7 @@ gpseval) as one command on the GPU path.
 
     python tools/run_file.py <recording.bin> [--seconds S] [--start-stream K] [--save-pickle P]
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--blank] [--json]
-                             [--format FMT --fs HZ --if HZ --conjugate]
+                             [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -28,6 +28,10 @@ input rate in Hz), --if (the IF of real input or the tuner offset of complex inp
 --conjugate read a recording of another front end: frontend.FrontEnd decodes, mixes, filters and
 resamples it on the GPU to complex64 blocks at 2.048 Msps, which Receiver(raw_u8=False) takes
 (DESIGN.md 4.2c); --start-stream then skips output blocks.  Without them the path above is unchanged.
+--deep-acq SECONDS adds a second acquisition pass at the end, over the first SECONDS of the recording
+and for the PRNs the 4-ms sweep did not acquire: Acquisition.sweepDeepSats, the non-coherent search
+with the code Doppler compensated.  It prints PRN, Doppler bin, code delay and
+normMaxCorr of what it finds and changes nothing else: the satellites are not handed to tracking.
 
 There is no recording in this repository (data/test.bin is absent from the reference
 checkout, SURVEY F2, and too short for a fix even upstream): tests/test_run_file.py writes a
@@ -67,10 +71,54 @@ def cpu_cold_acquisition(path, n_blocks=5):
             'found': [(int(s), float(f), int(d)) for _, s, f, d in found]}
 
 
+def deep_acquisition(path, seconds, start_stream, skip_prns, frontend=None, n_coh=4):
+    """--deep-acq: Acquisition.sweepDeepSats (code-Doppler-compensated non-coherent search, DESIGN.md
+    4.2e) over the first `seconds` of the recording, n_coh-ms segments, the reference's 50 bins, for
+    the PRNs not in `skip_prns`.  Reports only: nothing is handed to tracking."""
+    from gpsmi import ingest
+    from gpsmi.acquisition import Acquisition, SAT_ALL
+    from gpsmi.engine import Config
+    cfg = Config()
+    n_seg = int(round(seconds * 1000)) // n_coh
+    if not 1 <= n_seg <= 32768:
+        sys.exit(f'--deep-acq: {n_coh}-ms segments of {seconds} s: {n_seg}, must be 1..32768')
+    need = n_seg * n_coh * cfg.code_samples
+    fe = None
+    if frontend is None:
+        source = ingest.read_raw_blocks(path, cfg.ngps, start_stream)
+    else:
+        from gpsmi.frontend import FrontEnd
+        fe = FrontEnd(cfg, **frontend)
+        source = (b for k, b in enumerate(ingest.read_frontend_blocks(path, fe)) if k >= start_stream)
+    blocks, have = [], 0
+    for blk in source:
+        blocks.append(blk)
+        have += len(blk)
+        if have >= need:
+            break
+    if fe is not None:
+        fe.close()
+    if have < need:
+        sys.exit(f'--deep-acq: the recording holds {have} samples after stream {start_stream}, '
+                 f'{seconds} s need {need}')
+    data = np.concatenate(blocks)[:need]
+    acq = Acquisition(cfg, raw_u8=frontend is None)
+    freqs = [cfg.min_freq + cfg.step_freq * i
+             for i in range(int(round((cfg.max_freq - cfg.min_freq) / cfg.step_freq)))]
+    sat_lst = [s for s in SAT_ALL if s not in skip_prns]
+    res = acq.sweepDeepSats(data, freqs, sat_lst, [], n_coh=n_coh, n_seg=n_seg)
+    ms = acq.engine.last_ms()
+    acq.engine.close()
+    return {'seconds': n_seg * n_coh / 1000.0, 'n_coh': n_coh, 'n_seg': n_seg, 'device_ms': round(ms, 3),
+            'searched': sat_lst,
+            'found': [(int(s), float(f), int(d), round(float(nmc), 2)) for nmc, s, f, d in res]}
+
+
 def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, cpu_acq=False, report_lag=16,
-        excise=False, frontend=None, blank=False):
+        excise=False, frontend=None, blank=False, deep_acq=None):
     """frontend: None (the recorder's u8 format at 2.048 Msps) or a dict of frontend.FrontEnd's
-    keyword arguments (fs_in, fmt, if_hz, conjugate)."""
+    keyword arguments (fs_in, fmt, if_hz, conjugate).  deep_acq: None, or the seconds of the
+    recording's start that deep_acquisition searches for the PRNs the sweep did not acquire."""
     from gpsmi import ingest, position as P
     from gpsmi.engine import Config
     from gpsmi.pipeline import Receiver, save_results
@@ -129,6 +177,9 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
                            'sd_of_mean_m': round(float(np.linalg.norm(late.std(axis=0)) / np.sqrt(len(late))), 2)}
     if cpu_acq:
         out['cpu_cold_acquisition'] = cpu_cold_acquisition(path)
+    if deep_acq:
+        out['deep_acquisition'] = deep_acquisition(path, deep_acq, start_stream,
+                                                   {s for s, _, _ in out['acquired']}, frontend)
     return out
 
 
@@ -152,6 +203,9 @@ def main():
     ap.add_argument('--if', dest='if_hz', type=float, default=None,
                     help='IF of real input or tuner offset of complex input in Hz (sign: sideband)')
     ap.add_argument('--conjugate', action='store_true', help='mirror the spectrum of complex input')
+    ap.add_argument('--deep-acq', type=float, default=None, metavar='SECONDS',
+                    help='afterwards search the first SECONDS for the PRNs the sweep missed, code Doppler '
+                         'compensated (DESIGN.md 4.2e); printed only')
     ap.add_argument('--json', action='store_true', help='one JSON line instead of text')
     a = ap.parse_args()
     frontend = None
@@ -163,7 +217,7 @@ def main():
         with open(a.ephemeris) as f:
             eph = {int(k): v for k, v in json.load(f).items()}
     out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise,
-              frontend, a.blank)
+              frontend, a.blank, a.deep_acq)
     if a.json:
         print(json.dumps(out))
         return
@@ -180,6 +234,12 @@ def main():
     if 'cpu_cold_acquisition' in out:
         c = out['cpu_cold_acquisition']
         print(f"CPU cold acquisition (configs[0], numpy path, {c['cores']} core): {c['wall_ms']} ms, {len(c['found'])} satellites")
+    if 'deep_acquisition' in out:
+        d = out['deep_acquisition']
+        print(f"deep acquisition over {d['seconds']} s ({d['n_seg']} x {d['n_coh']} ms, {len(d['searched'])} PRNs, "
+              f"{d['device_ms']} ms on the device): {len(d['found'])} more satellites")
+        for s, f, dly, nmc in d['found']:
+            print(f'  PRN {s:2d}  bin {f:+6.0f} Hz  delay {dly:4d}  normMaxCorr {nmc:.2f}')
 
 
 if __name__ == '__main__':
