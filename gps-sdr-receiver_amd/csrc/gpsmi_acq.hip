@@ -20,6 +20,9 @@
 //   acq_deep_corr_kernel + pfa_corr_kernel<3>
 //                         the deep search (gpsmi_acq_search_deep): the same mean
 //                         with every segment's magnitudes rotated by the code-Doppler slide.
+//   refine_prompt_kernel, refine_grid_kernel, refine_final_kernel (gpsmi_refine.h)
+//                         refinement of weak / deep hits (gpsmi_acq_refine): fine
+//                         Doppler, bit edge, sub-sample code phase, C/N0.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -31,6 +34,7 @@
 #include "gpsmi_direct.h"
 #include "gpsmi_fft.h"
 #include "gpsmi_stats.h"
+#include "gpsmi_refine.h"
 
 namespace gpsmi {
 
@@ -414,6 +418,12 @@ struct gpsmi_acq {
     float2* d_nc = nullptr; size_t nc_cap = 0;
     // deep search: the lag rotation of every (bin, segment) of a call (gpsmi_acq_search_deep)
     int* d_shift = nullptr; size_t shift_cap = 0;
+    // refinement (gpsmi_acq_refine): prompts [nhits][3][n_ms], grid [nhits][n_df][20], the per-call
+    // tables (hits, window starts, df increments, df) in one block, the records
+    float2* d_rp = nullptr; size_t rp_cap = 0;
+    float* d_rm = nullptr; size_t rm_cap = 0;
+    char* d_rt = nullptr; size_t rt_cap = 0;
+    gpsmi_refine_out* d_ro = nullptr;
     int iq_fmt = GPSMI_IQ_C64;              // what the iq pointers of the search calls point to
     float last_ms = 0.f;
     bool pending = false;
@@ -533,7 +543,7 @@ int gpsmi_acq_destroy(gpsmi_acq* h) {
     void* bufs[] = {h->d_tw, h->d_t32, h->d_rep, h->d_iq, h->d_spec, h->d_omega, h->d_slot,
                     h->d_peaks, h->d_nbr, h->d_rep_time, h->d_fold, h->d_mag, h->d_stats,
                     h->d_xsel, h->d_rsel, h->d_twN, h->d_RS, h->d_S, h->d_RSp, h->d_nc,
-                    h->d_shift};
+                    h->d_shift, h->d_rp, h->d_rm, h->d_rt, h->d_ro};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (int k = 0; k < 2; ++k) {
@@ -552,8 +562,16 @@ int gpsmi_acq_destroy(gpsmi_acq* h) {
 int gpsmi_acq_set_replica_time(gpsmi_acq* h, int prn, const float* replica) {
     GPSMI_REQUIRE(h && replica, "null argument");
     GPSMI_REQUIRE(prn >= 1 && prn <= GPSMI_MAX_PRN, "prn out of range 1..37");
-    if (!h->direct) return GPSMI_OK;         // the FFT path has no use for it
     GPSMI_HIP(hipSetDevice(h->cfg.device));
+    if (!h->direct) {                        // the FFT path has no use for it: kept for gpsmi_acq_refine
+        if (!h->d_rep_time)
+            GPSMI_HIP(hipMalloc((void**)&h->d_rep_time,
+                                (size_t)(GPSMI_MAX_PRN + 1) * h->cfg.code_samples * sizeof(float)));
+        GPSMI_HIP(hipMemcpy(h->d_rep_time + (size_t)prn * h->cfg.code_samples, replica,
+                            (size_t)h->cfg.code_samples * sizeof(float), hipMemcpyHostToDevice));
+        h->have_time[prn] = true;
+        return GPSMI_OK;
+    }
     GPSMI_HIP(hipMemcpy(h->d_rep_time + (size_t)prn * h->cfg.code_samples, replica,
                         (size_t)h->cfg.code_samples * sizeof(float), hipMemcpyHostToDevice));
     if (h->big)
@@ -703,7 +721,7 @@ static int acq_search_impl(gpsmi_acq* h, const void* d_iq, size_t n, const int32
     return gpsmi_acq_wait(h);
 }
 
-// Device memory for the non-coherent search.  An allocation the device cannot serve is
+// Device memory for the non-coherent and deep searches and the refinement.  An allocation the device cannot serve is
 // GPSMI_E_NOMEM, and the handle stays usable (the buffer is simply absent until a later call).
 static int nc_grow(void** p, size_t* cap, size_t bytes) {
     if (bytes <= *cap) return GPSMI_OK;
@@ -713,7 +731,7 @@ static int nc_grow(void** p, size_t* cap, size_t bytes) {
     if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
         (void)hipGetLastError();
         *p = nullptr;
-        return fail(GPSMI_E_NOMEM, "gpsmi_acq_search_nc: no device memory for %zu bytes of scratch", bytes);
+        return fail(GPSMI_E_NOMEM, "gpsmi_acq: no device memory for %zu bytes of scratch", bytes);
     }
     if (e != hipSuccess)
         return fail(GPSMI_E_HIP, "hipMalloc: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
@@ -971,6 +989,102 @@ int gpsmi_acq_search_deep_dev(gpsmi_acq* h, const void* d_iq, size_t n, const in
                               double f_offset_hz, gpsmi_peak* out, void* out_dev) {
     const DeepShift d{carrier_hz, f_offset_hz};
     return acq_search_nc_impl(h, d_iq, n, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, out_dev, nullptr, &d);
+}
+
+// ---- refinement of weak / deep hits (kernels and plan: gpsmi_refine.h) ------------------------
+static int acq_refine_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n,
+                           const gpsmi_refine_hit* hits, int nhits, const gpsmi_refine_cfg* cfg,
+                           gpsmi_refine_out* out, float* grid, float* prompts) {
+    GPSMI_REQUIRE(h && iq && hits && cfg && out, "null argument");
+    RefPlan pl;
+    int rc = ref_plan(h->cfg.code_samples, n, hits, nhits, cfg, &pl);
+    if (rc) return rc;
+    for (int i = 0; i < nhits; ++i)
+        if (!h->have_time[hits[i].prn])
+            return fail(GPSMI_E_STATE, "gpsmi_acq_refine: no time-domain replica set for PRN %d "
+                                       "(gpsmi_acq_set_replica_time)", (int)hits[i].prn);
+    const int cs = pl.cs, n_ms = pl.n_ms, n_df = pl.n_df;
+    h->last_ms = 0.f;
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    const void* d_iq = iq;
+    if (on_host) {                           // only what the windows read is uploaded
+        if (pl.hi > h->iq_cap) {             // (iq_cap counts complex64 samples)
+            size_t bytes = h->iq_cap * sizeof(float2);
+            rc = nc_grow((void**)&h->d_iq, &bytes, pl.hi * sizeof(float2));
+            h->iq_cap = h->d_iq ? pl.hi : 0;
+            if (rc) return rc;
+        }
+        GPSMI_HIP(hipMemcpyAsync(h->d_iq, iq, pl.hi * (h->iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)),
+                                 hipMemcpyHostToDevice, h->stream));
+        d_iq = h->d_iq;
+    }
+    // the tables of the call, 8-byte items first
+    const size_t b_start = pl.start.size() * sizeof(long long), b_inc = (size_t)n_df * sizeof(unsigned long long),
+                 b_df = (size_t)n_df * sizeof(double), b_hit = (size_t)nhits * sizeof(RefHit);
+    const size_t np = (size_t)nhits * 3 * n_ms, nm = (size_t)nhits * n_df * kRefEdges;
+    if ((rc = nc_grow((void**)&h->d_rt, &h->rt_cap, b_start + b_inc + b_df + b_hit)) ||
+        (rc = nc_grow((void**)&h->d_rp, &h->rp_cap, np * sizeof(float2))) ||
+        (rc = nc_grow((void**)&h->d_rm, &h->rm_cap, nm * sizeof(float))))
+        return rc;
+    if (!h->d_ro) {
+        size_t cap = 0;
+        if ((rc = nc_grow((void**)&h->d_ro, &cap, kRefMaxHits * sizeof(gpsmi_refine_out)))) return rc;
+    }
+    long long* d_start = reinterpret_cast<long long*>(h->d_rt);
+    unsigned long long* d_inc = reinterpret_cast<unsigned long long*>(h->d_rt + b_start);
+    double* d_df = reinterpret_cast<double*>(h->d_rt + b_start + b_inc);
+    RefHit* d_hit = reinterpret_cast<RefHit*>(h->d_rt + b_start + b_inc + b_df);
+    GPSMI_HIP(hipMemcpyAsync(d_start, pl.start.data(), b_start, hipMemcpyHostToDevice, h->stream));
+    GPSMI_HIP(hipMemcpyAsync(d_inc, pl.dfinc.data(), b_inc, hipMemcpyHostToDevice, h->stream));
+    GPSMI_HIP(hipMemcpyAsync(d_df, pl.dfs.data(), b_df, hipMemcpyHostToDevice, h->stream));
+    GPSMI_HIP(hipMemcpyAsync(d_hit, pl.hits.data(), b_hit, hipMemcpyHostToDevice, h->stream));
+    GPSMI_HIP(hipStreamSynchronize(h->stream));          // (the tables are pageable and leave scope here)
+    const size_t lds_p = ((size_t)cs + kRefMsPerWg * 4 * 6) * sizeof(float);
+    const size_t lds_g = (size_t)n_ms * sizeof(float2);
+    const bool u8 = h->iq_fmt == GPSMI_IQ_U8;
+    if (lds_p > 64 * 1024)
+        GPSMI_HIP(hipFuncSetAttribute(u8 ? (const void*)refine_prompt_kernel<1> : (const void*)refine_prompt_kernel<0>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
+    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
+    const dim3 gp((n_ms + kRefMsPerWg - 1) / kRefMsPerWg, nhits);
+    if (u8)
+        hipLaunchKernelGGL(refine_prompt_kernel<1>, gp, dim3(256), lds_p, h->stream, d_iq, h->d_rep_time, d_hit,
+                           d_start, cs, pl.tap, n_ms, h->d_rp);
+    else
+        hipLaunchKernelGGL(refine_prompt_kernel<0>, gp, dim3(256), lds_p, h->stream, d_iq, h->d_rep_time, d_hit,
+                           d_start, cs, pl.tap, n_ms, h->d_rp);
+    hipLaunchKernelGGL(refine_grid_kernel, dim3((n_df + 3) / 4, nhits), dim3(256), lds_g, h->stream, h->d_rp,
+                       d_inc, n_df, n_ms, h->d_rm);
+    hipLaunchKernelGGL(refine_final_kernel, dim3(nhits), dim3(256), 0, h->stream, h->d_rp, h->d_rm, d_inc, d_df,
+                       d_hit, n_df, n_ms, pl.tap, pl.step, pl.min_ratio, h->d_ro);
+    GPSMI_HIP(hipGetLastError());
+    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
+    GPSMI_HIP(hipMemcpyAsync(out, h->d_ro, (size_t)nhits * sizeof(gpsmi_refine_out), hipMemcpyDeviceToHost,
+                             h->stream));
+    if (grid)
+        GPSMI_HIP(hipMemcpyAsync(grid, h->d_rm, nm * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (prompts)
+        GPSMI_HIP(hipMemcpyAsync(prompts, h->d_rp, np * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+    h->pending = true;
+    return gpsmi_acq_wait(h);
+}
+
+int gpsmi_acq_refine(gpsmi_acq* h, const void* iq, size_t n, const gpsmi_refine_hit* hits, int nhits,
+                     const gpsmi_refine_cfg* cfg, gpsmi_refine_out* out, float* grid, float* prompts) {
+    return acq_refine_impl(h, iq, true, n, hits, nhits, cfg, out, grid, prompts);
+}
+
+int gpsmi_acq_refine_dev(gpsmi_acq* h, const void* d_iq, size_t n, const gpsmi_refine_hit* hits, int nhits,
+                         const gpsmi_refine_cfg* cfg, gpsmi_refine_out* out, float* grid, float* prompts) {
+    return acq_refine_impl(h, d_iq, false, n, hits, nhits, cfg, out, grid, prompts);
+}
+
+int gpsmi_acq_refine_plan(int code_samples, size_t n, const gpsmi_refine_hit* hits, int nhits,
+                          const gpsmi_refine_cfg* cfg, int* n_df) {
+    RefPlan pl;
+    const int rc = ref_plan(code_samples, n, hits, nhits, cfg, &pl);
+    if (rc == GPSMI_OK && n_df) *n_df = pl.n_df;
+    return rc;
 }
 
 int gpsmi_acq_set_input_format(gpsmi_acq* h, int fmt) {

@@ -134,6 +134,9 @@ int gpsmi_abi_sizeof(int which) {
         case 4: return (int)offsetof(gpsmi_trk_out, code_phase);
         case 5: return (int)sizeof(gpsmi_fe_cfg);
         case 6: return (int)sizeof(gpsmi_pb_cfg);
+        case 7: return (int)sizeof(gpsmi_refine_hit);
+        case 8: return (int)sizeof(gpsmi_refine_cfg);
+        case 9: return (int)sizeof(gpsmi_refine_out);
         default: return -1;
     }
 }

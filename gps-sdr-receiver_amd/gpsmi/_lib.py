@@ -12,6 +12,7 @@ MAX_PRN = 37
 MAX_DUMPS = 33
 MAX_DF = 128
 COMM_ID_BYTES = 128
+REFINE_MAX_MS = 8000          # GPSMI_REFINE_MAX_MS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (GPSMI_LIB_PATH: another build of the same library, e.g. `make asan`'s host-sanitizer build)
@@ -38,6 +39,16 @@ class PbCfg(C.Structure):
                 ('post', C.c_int32), ('max_frac', C.c_float), ('device', C.c_int32)]
 
 
+class RefineHit(C.Structure):
+    _fields_ = [('prn', C.c_int32), ('delay', C.c_int32), ('freq_hz', C.c_double)]
+
+
+class RefineCfg(C.Structure):
+    _fields_ = [('n_ms', C.c_int32), ('tap_samples', C.c_int32), ('df_step_hz', C.c_double),
+                ('df_half_hz', C.c_double), ('carrier_hz', C.c_double), ('f_offset_hz', C.c_double),
+                ('min_ratio', C.c_float), ('reserved', C.c_int32)]
+
+
 class Cfg(C.Structure):
     _fields_ = [('code_samples', C.c_int32), ('n_cyc', C.c_int32),
                 ('corr_avg', C.c_int32), ('sweep_corr_avg', C.c_int32),
@@ -48,6 +59,14 @@ class Cfg(C.Structure):
 # numpy views of the C structs (same layout; checked against ctypes below)
 PEAK_DTYPE = np.dtype([('argmax', np.int32), ('peak', np.float32),
                        ('mean', np.float32), ('std', np.float32)])
+
+REFINE_HIT_DTYPE = np.dtype([('prn', np.int32), ('delay', np.int32), ('freq_hz', np.float64)])
+
+REFINE_OUT_DTYPE = np.dtype([
+    ('prn', np.int32), ('edge_ms', np.int32), ('n_bits', np.int32), ('confirmed', np.int32),
+    ('f_hz', np.float64), ('code_phase', np.float64),
+    ('peak', np.float32), ('median', np.float32), ('ratio', np.float32), ('mu', np.float32),
+    ('cn0_dbhz', np.float32), ('tap_metric', np.float32, (3,))])
 
 STATE_DTYPE = np.dtype([
     ('prn', np.int32), ('delay', np.int32), ('freq', np.float32),
@@ -85,6 +104,7 @@ EXPORTS = [
     'gpsmi_acq_search_dev_async', 'gpsmi_acq_wait',
     'gpsmi_acq_search_nc', 'gpsmi_acq_search_nc_dev',
     'gpsmi_acq_search_deep', 'gpsmi_acq_search_deep_dev',
+    'gpsmi_acq_refine', 'gpsmi_acq_refine_dev', 'gpsmi_acq_refine_plan',
     'gpsmi_acq_last_ms',
     'gpsmi_trk_create', 'gpsmi_trk_destroy', 'gpsmi_trk_set_replica',
     'gpsmi_trk_open', 'gpsmi_trk_close', 'gpsmi_trk_get_state',
@@ -159,6 +179,9 @@ def load():
                                   C.c_double, C.c_double, vp, vp],
         'gpsmi_acq_search_deep_dev': [vp, vp, sz, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                       C.c_double, C.c_double, vp, vp],
+        'gpsmi_acq_refine': [vp, vp, sz, vp, C.c_int, P(RefineCfg), vp, vp, vp],
+        'gpsmi_acq_refine_dev': [vp, vp, sz, vp, C.c_int, P(RefineCfg), vp, vp, vp],
+        'gpsmi_acq_refine_plan': [C.c_int, sz, vp, C.c_int, P(RefineCfg), P(C.c_int)],
         'gpsmi_acq_last_ms': [vp, P(f32)],
         'gpsmi_trk_create': [P(Cfg), C.c_int, P(vp)],
         'gpsmi_trk_destroy': [vp],
@@ -233,6 +256,8 @@ def load():
     got = [lib.gpsmi_abi_sizeof(i) for i in range(5)]
     want += [C.sizeof(FeCfg), C.sizeof(PbCfg)]
     got += [lib.gpsmi_abi_sizeof(5), lib.gpsmi_abi_sizeof(6)]
+    want += [REFINE_HIT_DTYPE.itemsize, C.sizeof(RefineCfg), REFINE_OUT_DTYPE.itemsize]
+    got += [lib.gpsmi_abi_sizeof(i) for i in (7, 8, 9)]
     if want != got:
         raise EngineError(f'ABI mismatch between gpsmi/_lib.py {want} and '
                           f'libgpsmi.so {got}')

@@ -9,9 +9,11 @@ the result list is the one the reference builds.
 """
 import numpy as np
 
+from ._lib import REFINE_MAX_MS
 from .engine import AcqEngine, Config
 
 SAT_ALL = list(range(2, 33))          # gpsrecv.py:36
+L1_HZ = 1575.42e6
 
 
 def norm_max_corr(cell):
@@ -122,9 +124,37 @@ class Acquisition:
                     satLst.remove(s)
         return sorted(satFound, reverse=True)
 
+    def refineHits(self, data, found, n_ms=None, f_offset=0.0, **cfg):
+        """Refines the ``(normMaxCorr, satNo, freq, delay)`` entries that sweepWeakSats /
+        sweepDeepSats return (AcqEngine.refine: fine Doppler, bit edge, sub-sample code phase,
+        C/N0 and a detection ratio of its own): one record per entry, in the same order.  `data`
+        is the data the sweep searched; `n_ms` defaults to the largest multiple of 20 it holds
+        (two code periods and the early / late spacing are kept in hand for the code slide)."""
+        cs = self.cfg.code_samples
+        n = data[1] if isinstance(data, tuple) else len(data)
+        if n_ms is None:
+            tap = cfg.get('tap_samples') or (1 if cs == 2048 else 8)
+            n_ms = min((n - tap) // cs - 2, REFINE_MAX_MS) // 20 * 20
+        hits = [(s, f, d) for _, s, f, d in found]
+        return self.engine.refine(data, hits, n_ms, f_offset=f_offset, **cfg)
+
     def search_table(self, data, prns, freqs, n_avg):
         """The whole surface, no pruning (BASELINE configs 2 and 4)."""
         return self.engine.search(data, prns, freqs, n_avg)
+
+
+def hit_at(rec, sample, cfg, carrier_hz=L1_HZ):
+    """What ``initInst`` needs to open a channel on a refined hit (a record of refineHits) at a
+    later sample index of the stream the hit was refined on: ``(freq, delay)`` with the refined
+    Doppler and the code phase moved by the code slide -f / carrier_hz samples per sample,
+    modulo ``code_samples`` and rounded to a whole sample as findCodePhase delivers delays.
+    Host only.  `sample` counts from the first sample of the refined data."""
+    cs = cfg.code_samples
+    if rec['code_phase'] < 0:
+        raise ValueError('the record has no code phase (its prompt tap was not the largest)')
+    f = float(rec['f_hz'])
+    phase = float(rec['code_phase']) - f / carrier_hz * float(sample)
+    return f, int(np.rint(phase)) % cs
 
 
 def getNewSats(actSatSet, foundSats, cpQLst, max_sat=11):

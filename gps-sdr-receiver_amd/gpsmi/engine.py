@@ -7,8 +7,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib, codes
-from ._lib import (EngineError, OUT_DTYPE, PEAK_DTYPE, STATE_DTYPE, check,  # noqa: F401
-                   ptr)
+from ._lib import (EngineError, OUT_DTYPE, PEAK_DTYPE, REFINE_HIT_DTYPE,  # noqa: F401
+                   REFINE_OUT_DTYPE, STATE_DTYPE, check, ptr)
 
 
 @dataclass
@@ -155,6 +155,7 @@ class AcqEngine:
         check(self.lib.gpsmi_acq_create(C.byref(cs), C.byref(h)),
               'gpsmi_acq_create')
         self.h = h
+        self._have_time = set()        # PRNs whose GPSCacode a 2048 handle holds (refine)
         for p in prns:
             if self.cfg.code_samples == 2048:
                 spec = _spectrum_c64(p, self.cfg.code_samples)
@@ -257,6 +258,46 @@ class AcqEngine:
                 int(n_coh), int(n_seg), float(carrier_hz), float(f_offset), ptr(out),
                 ptr(nb) if nbr else None), 'gpsmi_acq_search_deep')
         return (out, nb) if nbr else out
+
+    def refine(self, iq, hits, n_ms, df_step=2.0, df_half=120.0, tap_samples=0, f_offset=0.0,
+               carrier_hz=L1_HZ, min_ratio=2.5, want_grid=False, want_prompts=False):
+        """Refinement of weak / deep hits (gpsmi_acq_refine): per hit (prn, freq, delay) -- the SV,
+        the bin and the argmax a non-coherent or deep search returned for the start of iq -- the
+        fine Doppler, the bit edge, a sub-sample code phase, C/N0 and a detection ratio from n_ms
+        milliseconds (a multiple of 20) of 1-ms prompts summed coherently over each data bit.
+        iq as in search_deep.  Returns a REFINE_OUT_DTYPE array [nhits]; with want_grid /
+        want_prompts a tuple with the grid float32 [nhits, n_df, 20] and / or the prompts
+        complex64 [nhits, 3, n_ms] (early, prompt, late) behind it."""
+        cs = self.cfg.code_samples
+        h_a = np.zeros(len(hits), dtype=REFINE_HIT_DTYPE)
+        for i, (prn, freq, delay) in enumerate(hits):
+            h_a[i] = (int(prn), int(delay), float(freq))
+        if cs == 2048:                 # the FFT searches never needed GPSCacode itself
+            for p in sorted({int(x) for x in h_a['prn']} - self._have_time):
+                if 1 <= p <= 37:
+                    rep = np.ascontiguousarray(codes.code_replica(p, cs).astype(np.float32))
+                    check(self.lib.gpsmi_acq_set_replica_time(self.h, p, ptr(rep)),
+                          'gpsmi_acq_set_replica_time')
+                    self._have_time.add(p)
+        cfg = _lib.RefineCfg(int(n_ms), int(tap_samples), float(df_step), float(df_half),
+                             float(carrier_hz), float(f_offset), float(min_ratio), 0)
+        host = not isinstance(iq, tuple)
+        if host:
+            iq = self._host_iq(iq)
+            d_iq, n = ptr(iq), iq.size
+        else:
+            d_iq, n = iq
+        n_df = C.c_int(0)
+        check(self.lib.gpsmi_acq_refine_plan(cs, n, ptr(h_a), len(h_a), C.byref(cfg),
+                                             C.byref(n_df)), 'gpsmi_acq_refine_plan')
+        out = np.zeros(len(h_a), dtype=REFINE_OUT_DTYPE)
+        grid = np.zeros((len(h_a), n_df.value, 20), np.float32) if want_grid else None
+        prompts = np.zeros((len(h_a), 3, int(n_ms)), np.complex64) if want_prompts else None
+        fn = self.lib.gpsmi_acq_refine if host else self.lib.gpsmi_acq_refine_dev
+        check(fn(self.h, d_iq, n, ptr(h_a), len(h_a), C.byref(cfg), ptr(out), ptr(grid),
+                 ptr(prompts)), 'gpsmi_acq_refine' if host else 'gpsmi_acq_refine_dev')
+        extra = [a for a in (grid, prompts) if a is not None]
+        return (out, *extra) if extra else out
 
     def search_async(self, d_iq, n, prns, freqs, n_avg, out, out_dev=None):
         """Enqueue a search on device-resident iq; `out` is a pinned PEAK_DTYPE

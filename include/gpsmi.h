@@ -60,8 +60,8 @@ typedef struct gpsmi_cfg {
 const char* gpsmi_last_error(void);
 const char* gpsmi_version(void);
 /* sizeof() of the ABI structs as compiled: 0 cfg, 1 peak, 2 trk_state, 3 trk_out,
- * 4 offsetof(trk_out, code_phase), 5 fe_cfg; -1 otherwise.  Lets a binding verify its
- * own struct declarations before the first real call.                        */
+ * 4 offsetof(trk_out, code_phase), 5 fe_cfg, 6 pb_cfg, 7 refine_hit, 8 refine_cfg, 9 refine_out;
+ * -1 otherwise.  Lets a binding verify its own struct declarations before the first real call.  */
 int gpsmi_abi_sizeof(int which);
 /* Kernel-variant selection and tuning thresholds, visible through the ABI (round 4: they used to
  * be environment variables read inside gpsmi_*_create, invisible to a C caller; the variables
@@ -156,7 +156,9 @@ int gpsmi_acq_destroy(gpsmi_acq* h);
  * complex64 [code_samples]; the host computes it once (gpsmi.codes).         */
 int gpsmi_acq_set_replica(gpsmi_acq* h, int prn, const float* spectrum_c64);
 /* GPSCacode(prn) itself, float32 [code_samples]: needed when code_samples is not
- * 2048 (the correlation is then done in the time domain).       */
+ * 2048 (the correlation is then done in the time domain), and at 2048 by
+ * gpsmi_acq_refine alone: there the first call allocates a table of 38 * 2048 floats on the device
+ * and each call copies one row (it used to return at once; it can now return GPSMI_E_HIP).  */
 int gpsmi_acq_set_replica_time(gpsmi_acq* h, int prn, const float* replica_f32);
 /* Search nbins Doppler bins x nsv satellites on the first n_avg code periods of
  * iq.  freqs_hz[b] are the bin frequencies exactly as the reference steps them
@@ -253,6 +255,81 @@ int gpsmi_acq_search_deep_dev(gpsmi_acq* h, const void* d_iq, size_t n,
                               const double* freqs_hz, int nbins, int n_coh, int n_seg,
                               double carrier_hz, double f_offset_hz,
                               gpsmi_peak* out, void* out_dev);
+/* Refinement of the hits of gpsmi_acq_search_nc / gpsmi_acq_search_deep: what a
+ * high-sensitivity receiver runs between such a search and its loops.  Per hit (prn, delay = the
+ * argmax the search returned, the code start at the start of iq; freq_hz = the bin) it integrates
+ * coherently over each 20-ms data bit at the code phase found, over a fine frequency grid and all
+ * 20 bit-edge positions, and returns Doppler to a few Hz, the bit edge, a sub-sample code phase, a
+ * C/N0 estimate and a detection statistic of its own.
+ * Stage 1, prompts.  cs = code_samples, fs = 1000 cs.  The window of millisecond k starts at
+ *     n_k = k cs + delay + m[k],   m[k] = rint(-(freq_hz - f_offset_hz) / carrier_hz * k * cs)
+ * (float64, left to right, ties to even; on the host, uploaded as a table); a hit with delay <
+ * tap_samples takes delay + cs instead (its first window is the second code period; nothing else
+ * changes).  For the taps tau = -tap_samples, 0, +tap_samples (early, prompt, late)
+ *     P[tau][k] = sum_{i < cs} x[n_k + tau + i] exp(-j 2 pi freq_hz (n_k + tau + i) / fs) replica[i]
+ * with replica = GPSCacode(prn) (gpsmi_acq_set_replica_time, which a handle of 2048 samples keeps
+ * for this call alone).  The carrier phase is an integer: sample index * (freq_hz / fs in 0.64
+ * fixed point) mod 2^64, its top 24 bits give sine and cosine (as gpsmi_fe's mixer): exact at any
+ * index.  float32 sums in one fixed order.
+ * Stage 2, grid.  df_d = -df_half_hz + d df_step_hz for d < n_df = floor(2 half / step) + 1,
+ * B = n_ms / 20 - 1 bits, edges e = 0 .. 19:
+ *     M[d][e] = sum_{b < B} | sum_{k = e + 20 b}^{e + 20 b + 19} P[0][k] exp(-j 2 pi df_d k / 1000) |^2
+ * (the phase again an integer, k * (df_d / 1000 in 0.64 fixed point)).  The peak is the first-index
+ * argmax over (d, e) in that order.
+ * n >= (n_ms + 2) cs + tap_samples, and every window of the slide must lie inside iq (GPSMI_E_ARG).
+ * nhits 1 .. 64; n_ms a multiple of 20, 40 .. GPSMI_REFINE_MAX_MS (what the grid kernel's LDS
+ * holds; beyond it GPSMI_E_UNSUPPORTED); code_samples 2048 and 16368 only (GPSMI_E_UNSUPPORTED).
+ * A hit's record depends on that hit alone, not on what shares the call, and two calls give the
+ * same bytes.  iq in the handle's input format (GPSMI_IQ_U8 gives the same bytes as complex64),
+ * host memory for gpsmi_acq_refine, device memory for gpsmi_acq_refine_dev.  Optional host arrays:
+ * grid float [nhits][n_df][20] (M), prompts complex64 [nhits][3][n_ms] (P; early, prompt, late).
+ * Argument errors are GPSMI_E_ARG and need no GPU (gpsmi_acq_refine_plan makes the same checks
+ * without a handle); GPSMI_E_STATE: no time-domain replica for a PRN; GPSMI_E_NOMEM leaves the
+ * handle usable.  The call returns when the work is done; gpsmi_acq_last_ms reports it.
+ * Degenerate input: a bit whose 20 prompts are all exactly zero adds 0 to mu; all-zero iq therefore
+ * gives mu = 0 and cn0_dbhz = NaN, and, the median being 0, ratio = 0 / 0 = NaN with confirmed = 0.   */
+#define GPSMI_REFINE_MAX_MS 8000
+typedef struct gpsmi_refine_hit {   /* no implicit padding: 16 bytes */
+    int32_t prn;
+    int32_t delay;                  /* 0 .. code_samples - 1 */
+    double  freq_hz;
+} gpsmi_refine_hit;
+typedef struct gpsmi_refine_cfg {   /* no implicit padding: 48 bytes */
+    int32_t n_ms;                   /* multiple of 20, >= 40 */
+    int32_t tap_samples;            /* early / late spacing, >= 1; 0: 1 at 2048, 8 at 16368 */
+    double  df_step_hz;             /* 0: 2 */
+    double  df_half_hz;             /* 0: 120; below 500; at most 1024 grid points */
+    double  carrier_hz;             /* 1575.42e6 for L1; finite, > 0 */
+    double  f_offset_hz;            /* as in gpsmi_acq_search_deep; finite */
+    float   min_ratio;              /* 0: 2.5 */
+    int32_t reserved;               /* 0 */
+} gpsmi_refine_cfg;
+typedef struct gpsmi_refine_out {   /* no implicit padding: 64 bytes */
+    int32_t prn;
+    int32_t edge_ms;                /* e of the peak: milliseconds from the first window to the first bit boundary */
+    int32_t n_bits;                 /* B */
+    int32_t confirmed;              /* ratio > min_ratio */
+    double  f_hz;                   /* freq_hz + df of the peak + the vertex of the parabola through
+                                     * M[d - 1 .. d + 1][e] (dropped at a grid end) */
+    double  code_phase;             /* delay + the vertex of the parabola through tap_metric, in samples;
+                                     * -1.0 when the prompt tap is not the largest */
+    float   peak;                   /* M at the peak */
+    float   median;                 /* lower median of all M: rank (20 n_df - 1) / 2 from 0 */
+    float   ratio;                  /* peak / median */
+    float   mu;                     /* mean over the B bits of |sum P|^2 / sum |P|^2 at the peak */
+    float   cn0_dbhz;               /* 10 log10(1000 (mu - 1) / (20 - mu)); NaN when mu <= 1 */
+    float   tap_metric[3];          /* the bit sums of the peak's (d, e) for early, prompt, late */
+} gpsmi_refine_out;
+int gpsmi_acq_refine(gpsmi_acq* h, const void* iq, size_t n,
+                     const gpsmi_refine_hit* hits, int nhits, const gpsmi_refine_cfg* cfg,
+                     gpsmi_refine_out* out, float* grid, float* prompts);
+int gpsmi_acq_refine_dev(gpsmi_acq* h, const void* d_iq, size_t n,
+                         const gpsmi_refine_hit* hits, int nhits, const gpsmi_refine_cfg* cfg,
+                         gpsmi_refine_out* out, float* grid, float* prompts);
+/* host only, no GPU: the argument checks of gpsmi_acq_refine for a handle of code_samples, and the
+ * number of grid points (n_df, optional) the grid array is sized by                            */
+int gpsmi_acq_refine_plan(int code_samples, size_t n, const gpsmi_refine_hit* hits, int nhits,
+                          const gpsmi_refine_cfg* cfg, int* n_df);
 /* Input format of the iq pointers of the search calls that follow (host or device), as
  * gpsmi_trk_set_input_format below: GPSMI_IQ_U8 = the raw recording of streamData
  * (gpsrecv.py:162-173), decoded where the carrier wipe-off reads it; same bits out.   */

@@ -5,7 +5,7 @@ gpseval) as one command on the GPU path.
 
     python tools/run_file.py <recording.bin> [--seconds S] [--start-stream K] [--save-pickle P]
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--blank] [--json]
-                             [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS]
+                             [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine]]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -32,6 +32,10 @@ resamples it on the GPU to complex64 blocks at 2.048 Msps, which Receiver(raw_u8
 and for the PRNs the 4-ms sweep did not acquire: Acquisition.sweepDeepSats, the non-coherent search
 with the code Doppler compensated.  It prints PRN, Doppler bin, code delay and
 normMaxCorr of what it finds and changes nothing else: the satellites are not handed to tracking.
+--refine (with --deep-acq) refines what the second pass found on the same data: Acquisition.refineHits
+ integrates coherently over each 20-ms data bit and prints the fine Doppler, the bit
+edge, the sub-sample code phase, C/N0 and its own detection ratio per satellite -- what a tracking
+channel for such a signal would be opened with (acquisition.hit_at); opening one is still not done.
 
 There is no recording in this repository (data/test.bin is absent from the reference
 checkout, SURVEY F2, and too short for a fix even upstream): tests/test_run_file.py writes a
@@ -71,10 +75,12 @@ def cpu_cold_acquisition(path, n_blocks=5):
             'found': [(int(s), float(f), int(d)) for _, s, f, d in found]}
 
 
-def deep_acquisition(path, seconds, start_stream, skip_prns, frontend=None, n_coh=4):
+def deep_acquisition(path, seconds, start_stream, skip_prns, frontend=None, n_coh=4, refine=False):
     """--deep-acq: Acquisition.sweepDeepSats (code-Doppler-compensated non-coherent search, DESIGN.md
     4.2e) over the first `seconds` of the recording, n_coh-ms segments, the reference's 50 bins, for
-    the PRNs not in `skip_prns`.  Reports only: nothing is handed to tracking."""
+    the PRNs not in `skip_prns`.  Reports only: nothing is handed to tracking.  refine: the hits
+    are refined on the blocks read (Acquisition.refineHits) and reported under
+    'refined'."""
     from gpsmi import ingest
     from gpsmi.acquisition import Acquisition, SAT_ALL
     from gpsmi.engine import Config
@@ -101,24 +107,39 @@ def deep_acquisition(path, seconds, start_stream, skip_prns, frontend=None, n_co
     if have < need:
         sys.exit(f'--deep-acq: the recording holds {have} samples after stream {start_stream}, '
                  f'{seconds} s need {need}')
-    data = np.concatenate(blocks)[:need]
+    whole = np.concatenate(blocks)
+    data = whole[:need]
     acq = Acquisition(cfg, raw_u8=frontend is None)
     freqs = [cfg.min_freq + cfg.step_freq * i
              for i in range(int(round((cfg.max_freq - cfg.min_freq) / cfg.step_freq)))]
     sat_lst = [s for s in SAT_ALL if s not in skip_prns]
     res = acq.sweepDeepSats(data, freqs, sat_lst, [], n_coh=n_coh, n_seg=n_seg)
     ms = acq.engine.last_ms()
+    out = {'seconds': n_seg * n_coh / 1000.0, 'n_coh': n_coh, 'n_seg': n_seg, 'device_ms': round(ms, 3),
+           'searched': sat_lst,
+           'found': [(int(s), float(f), int(d), round(float(nmc), 2)) for nmc, s, f, d in res]}
+    if refine and res:
+        if len(whole) < 43 * cfg.code_samples:
+            sys.exit(f'--refine: {len(whole)} samples are too few for 40 ms and the code slide')
+        rec = acq.refineHits(whole, res)
+        out['refined'] = {'n_ms': int(20 * (rec['n_bits'][0] + 1)), 'device_ms': round(acq.engine.last_ms(), 3),
+                          'records': [{'prn': int(r['prn']), 'f_hz': round(float(r['f_hz']), 2),
+                                       'edge_ms': int(r['edge_ms']), 'code_phase': round(float(r['code_phase']), 3),
+                                       'cn0_dbhz': None if np.isnan(r['cn0_dbhz']) else round(float(r['cn0_dbhz']), 2),
+                                       'ratio': round(float(r['ratio']), 3), 'confirmed': bool(r['confirmed'])}
+                                      for r in rec]}
+    elif refine:
+        out['refined'] = {'n_ms': 0, 'device_ms': 0.0, 'records': []}
     acq.engine.close()
-    return {'seconds': n_seg * n_coh / 1000.0, 'n_coh': n_coh, 'n_seg': n_seg, 'device_ms': round(ms, 3),
-            'searched': sat_lst,
-            'found': [(int(s), float(f), int(d), round(float(nmc), 2)) for nmc, s, f, d in res]}
+    return out
 
 
 def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, cpu_acq=False, report_lag=16,
-        excise=False, frontend=None, blank=False, deep_acq=None):
+        excise=False, frontend=None, blank=False, deep_acq=None, refine=False):
     """frontend: None (the recorder's u8 format at 2.048 Msps) or a dict of frontend.FrontEnd's
     keyword arguments (fs_in, fmt, if_hz, conjugate).  deep_acq: None, or the seconds of the
-    recording's start that deep_acquisition searches for the PRNs the sweep did not acquire."""
+    recording's start that deep_acquisition searches for the PRNs the sweep did not acquire; refine:
+    its hits are refined as well."""
     from gpsmi import ingest, position as P
     from gpsmi.engine import Config
     from gpsmi.pipeline import Receiver, save_results
@@ -179,7 +200,7 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
         out['cpu_cold_acquisition'] = cpu_cold_acquisition(path)
     if deep_acq:
         out['deep_acquisition'] = deep_acquisition(path, deep_acq, start_stream,
-                                                   {s for s, _, _ in out['acquired']}, frontend)
+                                                   {s for s, _, _ in out['acquired']}, frontend, refine=refine)
     return out
 
 
@@ -206,8 +227,12 @@ def main():
     ap.add_argument('--deep-acq', type=float, default=None, metavar='SECONDS',
                     help='afterwards search the first SECONDS for the PRNs the sweep missed, code Doppler '
                          'compensated (DESIGN.md 4.2e); printed only')
+    ap.add_argument('--refine', action='store_true',
+                    help='with --deep-acq: refine its hits (fine Doppler, bit edge, code phase, C/N0; DESIGN.md 4.2f)')
     ap.add_argument('--json', action='store_true', help='one JSON line instead of text')
     a = ap.parse_args()
+    if a.refine and not a.deep_acq:
+        ap.error('--refine needs --deep-acq SECONDS')
     frontend = None
     if a.format is not None or a.fs is not None or a.if_hz is not None or a.conjugate:
         frontend = {'fmt': a.format or 'u8iq', 'fs_in': a.fs or 2048000, 'if_hz': a.if_hz or 0.0,
@@ -217,7 +242,7 @@ def main():
         with open(a.ephemeris) as f:
             eph = {int(k): v for k, v in json.load(f).items()}
     out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise,
-              frontend, a.blank, a.deep_acq)
+              frontend, a.blank, a.deep_acq, a.refine)
     if a.json:
         print(json.dumps(out))
         return
@@ -240,6 +265,13 @@ def main():
               f"{d['device_ms']} ms on the device): {len(d['found'])} more satellites")
         for s, f, dly, nmc in d['found']:
             print(f'  PRN {s:2d}  bin {f:+6.0f} Hz  delay {dly:4d}  normMaxCorr {nmc:.2f}')
+        if 'refined' in d:
+            r = d['refined']
+            print(f"refined over {r['n_ms']} ms ({r['device_ms']} ms on the device):")
+            for q in r['records']:
+                cn0 = 'n/a' if q['cn0_dbhz'] is None else f"{q['cn0_dbhz']:.1f}"
+                print(f"  PRN {q['prn']:2d}  f_hz {q['f_hz']:+9.2f}  edge_ms {q['edge_ms']:2d}  code_phase {q['code_phase']:8.3f}  "
+                      f"cn0_dbhz {cn0}  ratio {q['ratio']:.2f}  confirmed {q['confirmed']}")
 
 
 if __name__ == '__main__':
