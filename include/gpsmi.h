@@ -83,7 +83,11 @@ int gpsmi_abi_sizeof(int which);
  *                       and the null stream a process has four (env GPSMI_COPY_STREAM)
  * keys a live tracking handle accepts as well (see DESIGN.md for the measurements behind them):
  *   "corr_cg"           channels per code-phase-correlation workgroup in batches: 2, 4 (default), 6
- *   "corr_small1/2"     jobs per launch up to which 1 / 2 channels per workgroup are taken (384, 1536)
+ *   "corr_small1/2"     jobs per launch up to which 1 / 2 channels per workgroup are taken (384, 1536;
+ *                       0 <= corr_small1 <= corr_small2 <= 2^24 at every moment, so raise corr_small2
+ *                       first and lower corr_small1 first).  These three change no result: a job's
+ *                       record has the same bytes whichever of 1, 2, 4 or 6 channels share its
+ *                       workgroup (tests/test_gpu_trk_corr.py)
  *   "span_single_max"   (block, channel group) units up to which the span correlator runs one wave
  *                       per span (80)
  *   "stream_inline_max" bytes up to which gpsmi_trk_process_stream uploads in front of the step's

@@ -901,10 +901,19 @@ def test_other_corr_avg_matches_the_oracle(corr_avg):
     buf = DeviceBuffer(nb * blocks[0].nbytes)
     for i, b in enumerate(blocks):
         buf.upload(b, i * b.nbytes)
+    # 30 jobs take the one-channel form of the kernel by themselves (as the closed loop above did):
+    # the job-count thresholds at 0 give the four-channel form, then the two-channel one
+    eng.set_option('corr_small1', 0)
+    eng.set_option('corr_small2', 0)
+    assert (eng.get_option('corr_small1'), eng.get_option('corr_small2'), eng.get_option('corr_cg')) == (0, 0, 4)
     rep = eng.replay(buf.ptr, nb, states, outs['delay_used'])      # four-channel form of the kernel
+    eng.set_option('corr_small2', 1 << 24)
+    assert (eng.get_option('corr_small1'), eng.get_option('corr_small2')) == (0, 1 << 24)
+    rep2 = eng.replay(buf.ptr, nb, states, outs['delay_used'])     # two-channel form
     buf.free()
     eng.close()
     assert rep.tobytes() == outs.tobytes()
+    assert rep2.tobytes() == outs.tobytes()
 
 
 def test_twenty_channels_four_groups():
