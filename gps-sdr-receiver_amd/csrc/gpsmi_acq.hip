@@ -21,6 +21,8 @@
 //                         the deep search (gpsmi_acq_search_deep): the same mean
 //                         with every segment's magnitudes rotated by the code-Doppler slide.
 //   refine_prompt_kernel, refine_grid_kernel, refine_final_kernel (gpsmi_refine.h)
+//   wtrk_kernel (gpsmi_wtrk.h)
+//                         bit-synchronous tracking of refined hits (gpsmi_acq_track)
 //                         refinement of weak / deep hits (gpsmi_acq_refine): fine
 //                         Doppler, bit edge, sub-sample code phase, C/N0.
 #include <cmath>
@@ -35,6 +37,7 @@
 #include "gpsmi_fft.h"
 #include "gpsmi_stats.h"
 #include "gpsmi_refine.h"
+#include "gpsmi_wtrk.h"
 
 namespace gpsmi {
 
@@ -424,6 +427,9 @@ struct gpsmi_acq {
     float* d_rm = nullptr; size_t rm_cap = 0;
     char* d_rt = nullptr; size_t rt_cap = 0;
     gpsmi_refine_out* d_ro = nullptr;
+    // bit-synchronous tracking (gpsmi_acq_track): the states of a call, its bit records
+    gpsmi_wtrk_state* d_ws = nullptr;
+    gpsmi_wtrk_bit* d_wb = nullptr; size_t wb_cap = 0;
     int iq_fmt = GPSMI_IQ_C64;              // what the iq pointers of the search calls point to
     float last_ms = 0.f;
     bool pending = false;
@@ -543,7 +549,7 @@ int gpsmi_acq_destroy(gpsmi_acq* h) {
     void* bufs[] = {h->d_tw, h->d_t32, h->d_rep, h->d_iq, h->d_spec, h->d_omega, h->d_slot,
                     h->d_peaks, h->d_nbr, h->d_rep_time, h->d_fold, h->d_mag, h->d_stats,
                     h->d_xsel, h->d_rsel, h->d_twN, h->d_RS, h->d_S, h->d_RSp, h->d_nc,
-                    h->d_shift, h->d_rp, h->d_rm, h->d_rt, h->d_ro};
+                    h->d_shift, h->d_rp, h->d_rm, h->d_rt, h->d_ro, h->d_ws, h->d_wb};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (int k = 0; k < 2; ++k) {
@@ -1085,6 +1091,80 @@ int gpsmi_acq_refine_plan(int code_samples, size_t n, const gpsmi_refine_hit* hi
     const int rc = ref_plan(code_samples, n, hits, nhits, cfg, &pl);
     if (rc == GPSMI_OK && n_df) *n_df = pl.n_df;
     return rc;
+}
+
+// ---- bit-synchronous tracking of refined hits (kernel and plan: gpsmi_wtrk.h) ------------------
+static int acq_track_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n, gpsmi_wtrk_state* states,
+                          int nhits, const gpsmi_wtrk_cfg* cfg, gpsmi_wtrk_bit* bits) {
+    GPSMI_REQUIRE(h && iq && states && cfg && bits, "null argument");
+    WtrkPar par;
+    int rc = wtrk_plan(h->cfg.code_samples, n, states, nhits, cfg, &par);
+    if (rc) return rc;
+    for (int i = 0; i < nhits; ++i)
+        if (!h->have_time[states[i].prn])
+            return fail(GPSMI_E_STATE, "gpsmi_acq_track: no time-domain replica set for PRN %d "
+                                       "(gpsmi_acq_set_replica_time)", (int)states[i].prn);
+    h->last_ms = 0.f;
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    const bool u8 = h->iq_fmt == GPSMI_IQ_U8;
+    const void* d_iq = iq;
+    if (on_host) {
+        if (n > h->iq_cap) {                 // (iq_cap counts complex64 samples)
+            size_t bytes = h->iq_cap * sizeof(float2);
+            rc = nc_grow((void**)&h->d_iq, &bytes, n * sizeof(float2));
+            h->iq_cap = h->d_iq ? n : 0;
+            if (rc) return rc;
+        }
+        GPSMI_HIP(hipMemcpyAsync(h->d_iq, iq, n * (u8 ? 2 : sizeof(float2)), hipMemcpyHostToDevice, h->stream));
+        d_iq = h->d_iq;
+    }
+    const size_t nb = (size_t)nhits * par.n_bits * sizeof(gpsmi_wtrk_bit);
+    if ((rc = nc_grow((void**)&h->d_wb, &h->wb_cap, nb))) return rc;
+    if (!h->d_ws) {
+        size_t cap = 0;
+        if ((rc = nc_grow((void**)&h->d_ws, &cap, kWtrkMaxHits * sizeof(gpsmi_wtrk_state)))) return rc;
+    }
+    GPSMI_HIP(hipMemcpyAsync(h->d_ws, states, (size_t)nhits * sizeof(gpsmi_wtrk_state), hipMemcpyHostToDevice,
+                             h->stream));
+    GPSMI_HIP(hipMemsetAsync(h->d_wb, 0, nb, h->stream));
+    const size_t lds = wtrk_lds_bytes(par.cs);
+    if (lds > 64 * 1024)
+        GPSMI_HIP(hipFuncSetAttribute(u8 ? (const void*)wtrk_kernel<1> : (const void*)wtrk_kernel<0>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
+    if (u8)
+        hipLaunchKernelGGL(wtrk_kernel<1>, dim3(nhits), dim3(256), lds, h->stream, d_iq, h->d_rep_time, par,
+                           h->d_ws, h->d_wb);
+    else
+        hipLaunchKernelGGL(wtrk_kernel<0>, dim3(nhits), dim3(256), lds, h->stream, d_iq, h->d_rep_time, par,
+                           h->d_ws, h->d_wb);
+    GPSMI_HIP(hipGetLastError());
+    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
+    GPSMI_HIP(hipMemcpyAsync(states, h->d_ws, (size_t)nhits * sizeof(gpsmi_wtrk_state), hipMemcpyDeviceToHost,
+                             h->stream));
+    GPSMI_HIP(hipMemcpyAsync(bits, h->d_wb, nb, hipMemcpyDeviceToHost, h->stream));
+    h->pending = true;
+    return gpsmi_acq_wait(h);
+}
+
+int gpsmi_acq_track(gpsmi_acq* h, const void* iq, size_t n, gpsmi_wtrk_state* states, int nhits,
+                    const gpsmi_wtrk_cfg* cfg, gpsmi_wtrk_bit* bits) {
+    return acq_track_impl(h, iq, true, n, states, nhits, cfg, bits);
+}
+
+int gpsmi_acq_track_dev(gpsmi_acq* h, const void* d_iq, size_t n, gpsmi_wtrk_state* states, int nhits,
+                        const gpsmi_wtrk_cfg* cfg, gpsmi_wtrk_bit* bits) {
+    return acq_track_impl(h, d_iq, false, n, states, nhits, cfg, bits);
+}
+
+int gpsmi_acq_track_plan(int code_samples, size_t n, const gpsmi_wtrk_state* states, int nhits,
+                         const gpsmi_wtrk_cfg* cfg) {
+    return wtrk_plan(code_samples, n, states, nhits, cfg, nullptr);
+}
+
+int gpsmi_wtrk_open(const gpsmi_refine_out* rec, int code_samples, int refine_tap_samples, int64_t data_start,
+                    double carrier_hz, double f_offset_hz, gpsmi_wtrk_state* st) {
+    return wtrk_open(rec, code_samples, refine_tap_samples, data_start, carrier_hz, f_offset_hz, st);
 }
 
 int gpsmi_acq_set_input_format(gpsmi_acq* h, int fmt) {

@@ -137,6 +137,9 @@ int gpsmi_abi_sizeof(int which) {
         case 7: return (int)sizeof(gpsmi_refine_hit);
         case 8: return (int)sizeof(gpsmi_refine_cfg);
         case 9: return (int)sizeof(gpsmi_refine_out);
+        case 10: return (int)sizeof(gpsmi_wtrk_cfg);
+        case 11: return (int)sizeof(gpsmi_wtrk_state);
+        case 12: return (int)sizeof(gpsmi_wtrk_bit);
         default: return -1;
     }
 }

@@ -49,6 +49,13 @@ class RefineCfg(C.Structure):
                 ('min_ratio', C.c_float), ('reserved', C.c_int32)]
 
 
+class WtrkCfg(C.Structure):
+    _fields_ = [('n_bits', C.c_int32), ('tap_samples', C.c_int32), ('pll_bw_hz', C.c_double),
+                ('fll_bw_hz', C.c_double), ('dll_bw_hz', C.c_double), ('carrier_hz', C.c_double),
+                ('f_offset_hz', C.c_double), ('first_sample', C.c_int64), ('pull_in_bits', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
 class Cfg(C.Structure):
     _fields_ = [('code_samples', C.c_int32), ('n_cyc', C.c_int32),
                 ('corr_avg', C.c_int32), ('sweep_corr_avg', C.c_int32),
@@ -67,6 +74,20 @@ REFINE_OUT_DTYPE = np.dtype([
     ('f_hz', np.float64), ('code_phase', np.float64),
     ('peak', np.float32), ('median', np.float32), ('ratio', np.float32), ('mu', np.float32),
     ('cn0_dbhz', np.float32), ('tap_metric', np.float32, (3,))])
+
+WTRK_RING = 50                # GPSMI_WTRK_RING
+WTRK_DATA_END = 1             # GPSMI_WTRK_DATA_END
+
+WTRK_STATE_DTYPE = np.dtype([
+    ('prn', np.int32), ('bit_no', np.int32), ('tau', np.float64), ('f_hz', np.float64),
+    ('theta', np.uint64), ('f_acc', np.float64), ('lock', np.float64), ('flags', np.uint32),
+    ('reserved', np.int32), ('mu_ring', np.float32, (WTRK_RING,))])
+
+WTRK_BIT_DTYPE = np.dtype([
+    ('p_i', np.float32), ('p_q', np.float32), ('abs_e', np.float32), ('abs_l', np.float32),
+    ('h0_i', np.float32), ('h0_q', np.float32), ('h1_i', np.float32), ('h1_q', np.float32),
+    ('f_hz', np.float64), ('tau', np.float64), ('cn0_dbhz', np.float32), ('lock', np.float32),
+    ('dll_err', np.float32), ('bit_no', np.int32)])
 
 STATE_DTYPE = np.dtype([
     ('prn', np.int32), ('delay', np.int32), ('freq', np.float32),
@@ -105,6 +126,7 @@ EXPORTS = [
     'gpsmi_acq_search_nc', 'gpsmi_acq_search_nc_dev',
     'gpsmi_acq_search_deep', 'gpsmi_acq_search_deep_dev',
     'gpsmi_acq_refine', 'gpsmi_acq_refine_dev', 'gpsmi_acq_refine_plan',
+    'gpsmi_acq_track', 'gpsmi_acq_track_dev', 'gpsmi_acq_track_plan', 'gpsmi_wtrk_open',
     'gpsmi_acq_last_ms',
     'gpsmi_trk_create', 'gpsmi_trk_destroy', 'gpsmi_trk_set_replica',
     'gpsmi_trk_open', 'gpsmi_trk_close', 'gpsmi_trk_get_state',
@@ -182,6 +204,10 @@ def load():
         'gpsmi_acq_refine': [vp, vp, sz, vp, C.c_int, P(RefineCfg), vp, vp, vp],
         'gpsmi_acq_refine_dev': [vp, vp, sz, vp, C.c_int, P(RefineCfg), vp, vp, vp],
         'gpsmi_acq_refine_plan': [C.c_int, sz, vp, C.c_int, P(RefineCfg), P(C.c_int)],
+        'gpsmi_acq_track': [vp, vp, sz, vp, C.c_int, P(WtrkCfg), vp],
+        'gpsmi_acq_track_dev': [vp, vp, sz, vp, C.c_int, P(WtrkCfg), vp],
+        'gpsmi_acq_track_plan': [C.c_int, sz, vp, C.c_int, P(WtrkCfg)],
+        'gpsmi_wtrk_open': [vp, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_double, vp],
         'gpsmi_acq_last_ms': [vp, P(f32)],
         'gpsmi_trk_create': [P(Cfg), C.c_int, P(vp)],
         'gpsmi_trk_destroy': [vp],
@@ -258,6 +284,8 @@ def load():
     got += [lib.gpsmi_abi_sizeof(5), lib.gpsmi_abi_sizeof(6)]
     want += [REFINE_HIT_DTYPE.itemsize, C.sizeof(RefineCfg), REFINE_OUT_DTYPE.itemsize]
     got += [lib.gpsmi_abi_sizeof(i) for i in (7, 8, 9)]
+    want += [C.sizeof(WtrkCfg), WTRK_STATE_DTYPE.itemsize, WTRK_BIT_DTYPE.itemsize]
+    got += [lib.gpsmi_abi_sizeof(i) for i in (10, 11, 12)]
     if want != got:
         raise EngineError(f'ABI mismatch between gpsmi/_lib.py {want} and '
                           f'libgpsmi.so {got}')

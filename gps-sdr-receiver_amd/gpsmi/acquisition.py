@@ -9,7 +9,8 @@ the result list is the one the reference builds.
 """
 import numpy as np
 
-from ._lib import REFINE_MAX_MS
+from . import _lib
+from ._lib import REFINE_MAX_MS, REFINE_OUT_DTYPE, WTRK_STATE_DTYPE, check, ptr
 from .engine import AcqEngine, Config
 
 SAT_ALL = list(range(2, 33))          # gpsrecv.py:36
@@ -138,6 +139,21 @@ class Acquisition:
         hits = [(s, f, d) for _, s, f, d in found]
         return self.engine.refine(data, hits, n_ms, f_offset=f_offset, **cfg)
 
+    def trackHits(self, data, refined, n_bits=None, data_start=0, first_sample=0, refine_tap=0,
+                  f_offset=0.0, **cfg):
+        """Opens a bit-synchronous tracking channel on every record of refineHits
+        (open_weak_channels; `data_start` is the stream index of the first sample of the data they
+        were refined on) and tracks it through `data`, whose first sample has stream index
+        `first_sample` (AcqEngine.track_weak).  `n_bits` defaults to what `data`
+        can hold.  Returns (records, states); go on with engine.track_weak(next_data, states, ...,
+        first_sample=...) for the chunks that follow."""
+        states = open_weak_channels(refined, self.cfg, data_start, refine_tap, f_offset=f_offset)
+        n = data[1] if isinstance(data, tuple) else len(data)
+        if n_bits is None:
+            n_bits = max(1, n // (20 * self.cfg.code_samples))
+        return self.engine.track_weak(data, states, n_bits, first_sample=first_sample,
+                                      f_offset=f_offset, **cfg)
+
     def search_table(self, data, prns, freqs, n_avg):
         """The whole surface, no pruning (BASELINE configs 2 and 4)."""
         return self.engine.search(data, prns, freqs, n_avg)
@@ -155,6 +171,31 @@ def hit_at(rec, sample, cfg, carrier_hz=L1_HZ):
     f = float(rec['f_hz'])
     phase = float(rec['code_phase']) - f / carrier_hz * float(sample)
     return f, int(np.rint(phase)) % cs
+
+
+def open_weak_channels(refined, cfg, data_start=0, refine_tap=0, carrier_hz=L1_HZ, f_offset=0.0):
+    """Fresh tracking states (WTRK_STATE_DTYPE) for records of refineHits: gpsmi_wtrk_open per
+    record -- tau = data_start + code_phase + edge_ms code periods, f_hz the refined Doppler,
+    theta 0.  Host only.  `data_start`: the stream index of the first sample of the refined data;
+    `refine_tap`: the tap_samples refinement ran with (0: its default)."""
+    lib = _lib.load()
+    rec = np.ascontiguousarray(np.array(refined, dtype=REFINE_OUT_DTYPE, ndmin=1))
+    out = np.zeros(len(rec), WTRK_STATE_DTYPE)
+    for i in range(len(rec)):
+        check(lib.gpsmi_wtrk_open(ptr(rec[i:i + 1]), cfg.code_samples, int(refine_tap), int(data_start),
+                                  float(carrier_hz), float(f_offset), ptr(out[i:i + 1])), 'gpsmi_wtrk_open')
+    return out
+
+
+def weak_bits(records):
+    """Hard decisions on the bit records of one channel or of several ([..., n_bits],
+    WTRK_BIT_DTYPE): ``(bits, transitions)``, bits = sign Re P_b as +-1 (valid up to one global
+    sign, and only under phase lock), transitions[b - 1] = sign Re(P_b conj(P_{b-1})) as +-1
+    (-1: the data bit changed), which needs frequency lock alone.  Host only."""
+    p = records['p_i'].astype(np.float64) + 1j * records['p_q'].astype(np.float64)
+    bits = np.where(p.real >= 0, 1, -1).astype(np.int8)
+    d = (p[..., 1:] * np.conj(p[..., :-1])).real
+    return bits, np.where(d >= 0, 1, -1).astype(np.int8)
 
 
 def getNewSats(actSatSet, foundSats, cpQLst, max_sat=11):

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib, codes
 from ._lib import (EngineError, OUT_DTYPE, PEAK_DTYPE, REFINE_HIT_DTYPE,  # noqa: F401
-                   REFINE_OUT_DTYPE, STATE_DTYPE, check, ptr)
+                   REFINE_OUT_DTYPE, STATE_DTYPE, WTRK_BIT_DTYPE, WTRK_STATE_DTYPE, check, ptr)
 
 
 @dataclass
@@ -272,13 +272,7 @@ class AcqEngine:
         h_a = np.zeros(len(hits), dtype=REFINE_HIT_DTYPE)
         for i, (prn, freq, delay) in enumerate(hits):
             h_a[i] = (int(prn), int(delay), float(freq))
-        if cs == 2048:                 # the FFT searches never needed GPSCacode itself
-            for p in sorted({int(x) for x in h_a['prn']} - self._have_time):
-                if 1 <= p <= 37:
-                    rep = np.ascontiguousarray(codes.code_replica(p, cs).astype(np.float32))
-                    check(self.lib.gpsmi_acq_set_replica_time(self.h, p, ptr(rep)),
-                          'gpsmi_acq_set_replica_time')
-                    self._have_time.add(p)
+        self._need_time_replicas(h_a['prn'])   # the FFT searches never needed GPSCacode itself
         cfg = _lib.RefineCfg(int(n_ms), int(tap_samples), float(df_step), float(df_half),
                              float(carrier_hz), float(f_offset), float(min_ratio), 0)
         host = not isinstance(iq, tuple)
@@ -298,6 +292,45 @@ class AcqEngine:
                  ptr(prompts)), 'gpsmi_acq_refine' if host else 'gpsmi_acq_refine_dev')
         extra = [a for a in (grid, prompts) if a is not None]
         return (out, *extra) if extra else out
+
+    def _need_time_replicas(self, prns):
+        """A 2048 handle holds GPSCacode only for the PRNs refine / track_weak have met."""
+        cs = self.cfg.code_samples
+        if cs != 2048:
+            return
+        for p in sorted({int(x) for x in prns} - self._have_time):
+            if 1 <= p <= 37:
+                rep = np.ascontiguousarray(codes.code_replica(p, cs).astype(np.float32))
+                check(self.lib.gpsmi_acq_set_replica_time(self.h, p, ptr(rep)),
+                      'gpsmi_acq_set_replica_time')
+                self._have_time.add(p)
+
+    def track_weak(self, iq, states, n_bits, first_sample=0, tap_samples=0, pll_bw=0.0, fll_bw=0.0,
+                   dll_bw=0.0, pull_in_bits=0, f_offset=0.0, carrier_hz=L1_HZ):
+        """Bit-synchronous tracking of refined hits (gpsmi_acq_track): every channel of `states`
+        (WTRK_STATE_DTYPE, from acquisition.open_weak_channels or an earlier call) is tracked over
+        up to n_bits 20-ms data bits of iq, whose first sample has stream index first_sample.
+        Bandwidths of 0 take the defaults; a negative pll_bw / fll_bw switches that term off.  iq
+        as in search_deep.  Returns (records WTRK_BIT_DTYPE [nhits, n_bits], states): the records
+        past a channel's last bit are zero, and states['bit_no'] tells how far each channel got."""
+        st = np.array(states, dtype=WTRK_STATE_DTYPE, ndmin=1, copy=True)
+        st = np.ascontiguousarray(st)
+        self._need_time_replicas(st['prn'])
+        cfg = _lib.WtrkCfg(int(n_bits), int(tap_samples), float(pll_bw), float(fll_bw), float(dll_bw),
+                           float(carrier_hz), float(f_offset), int(first_sample), int(pull_in_bits), 0)
+        host = not isinstance(iq, tuple)
+        if host:
+            iq = self._host_iq(iq)
+            d_iq, n = ptr(iq), iq.size
+        else:
+            d_iq, n = iq
+        check(self.lib.gpsmi_acq_track_plan(self.cfg.code_samples, n, ptr(st), len(st), C.byref(cfg)),
+              'gpsmi_acq_track_plan')
+        bits = np.zeros((len(st), int(n_bits)), dtype=WTRK_BIT_DTYPE)
+        fn = self.lib.gpsmi_acq_track if host else self.lib.gpsmi_acq_track_dev
+        check(fn(self.h, d_iq, n, ptr(st), len(st), C.byref(cfg), ptr(bits)),
+              'gpsmi_acq_track' if host else 'gpsmi_acq_track_dev')
+        return bits, st
 
     def search_async(self, d_iq, n, prns, freqs, n_avg, out, out_dev=None):
         """Enqueue a search on device-resident iq; `out` is a pinned PEAK_DTYPE

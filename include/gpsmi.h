@@ -60,8 +60,8 @@ typedef struct gpsmi_cfg {
 const char* gpsmi_last_error(void);
 const char* gpsmi_version(void);
 /* sizeof() of the ABI structs as compiled: 0 cfg, 1 peak, 2 trk_state, 3 trk_out,
- * 4 offsetof(trk_out, code_phase), 5 fe_cfg, 6 pb_cfg, 7 refine_hit, 8 refine_cfg, 9 refine_out;
- * -1 otherwise.  Lets a binding verify its own struct declarations before the first real call.  */
+ * 4 offsetof(trk_out, code_phase), 5 fe_cfg, 6 pb_cfg, 7 refine_hit, 8 refine_cfg, 9 refine_out,
+ * 10 wtrk_cfg, 11 wtrk_state, 12 wtrk_bit; -1 otherwise.  Lets a binding verify its own struct declarations before the first real call.  */
 int gpsmi_abi_sizeof(int which);
 /* Kernel-variant selection and tuning thresholds, visible through the ABI (round 4: they used to
  * be environment variables read inside gpsmi_*_create, invisible to a C caller; the variables
@@ -334,6 +334,109 @@ int gpsmi_acq_refine_dev(gpsmi_acq* h, const void* d_iq, size_t n,
  * number of grid points (n_df, optional) the grid array is sized by                            */
 int gpsmi_acq_refine_plan(int code_samples, size_t n, const gpsmi_refine_hit* hits, int nhits,
                           const gpsmi_refine_cfg* cfg, int* n_df);
+/* Bit-synchronous tracking of refined hits (float64 restatement: tests/wtrk_ref.py):
+ * what takes a record of gpsmi_acq_refine on.  Per channel it integrates coherently over each 20-ms
+ * data bit between the edges refinement found, closes a carrier loop (second-order PLL assisted by a
+ * first-order FLL) and a code loop (first-order, carrier-aided DLL) once per bit, and returns one
+ * record per bit and the state to go on from.  cs = code_samples, fs = 1000 cs, T = 0.020 s.
+ * Positions are STREAM positions: sample iq[0] of a call has stream index cfg.first_sample, so a
+ * recording is tracked in chunks by calling again with the states returned and each chunk's own
+ * first_sample; nothing else is remembered between calls.
+ * Windows.  For the next bit of a state (tau, f_hz, theta):
+ *     Tc  = cs / (1 + (f_hz - f_offset_hz) / carrier_hz)             (the code period in samples)
+ *     s_k = tau + k * Tc,  n_k = floor(s_k),  a_k = s_k - n_k         k = 0 .. 19, float64, unfused
+ * The bit is tracked if min(n_0, n_19) - tap >= first_sample and max(n_0, n_19) + cs + tap <=
+ * first_sample + n; otherwise the channel stops there, keeps its state for the next chunk and sets
+ * GPSMI_WTRK_DATA_END in flags (cleared on entry).  A channel that fits no bit is not an error.
+ * Replica.  R = GPSCacode(prn) (gpsmi_acq_set_replica_time, as gpsmi_acq_refine), interpolated
+ * linearly between its samples: with the code start at n_k + a_k the replica at stream sample
+ * n_k + o + i, i < cs, of the tap at offset o = -tap, 0, +tap (early, prompt, late) is
+ * a_k R[(i - 1) mod cs] + (1 - a_k) R[i].  The device forms only the whole-sample float32 sums
+ *     D[o][sh][k] = sum_{i < cs} x[n_k + o + i] c[n_k + o + i] R[(i - sh) mod cs],   sh = 0, 1
+ * each in one fixed order; the tap value of millisecond k is a_k D[o][1][k] + (1 - a_k) D[o][0][k]
+ * in float64, and E, P, L are its sums over k = 0 .. 19, H0 / H1 those of the prompt tap over k < 10
+ * / k >= 10 (P = H0 + H1), all in ascending k.
+ * Carrier.  c[n] = exp(-j 2 pi ph / 2^64), ph = theta + (n - floor(tau)) * inc mod 2^64 with inc =
+ * f_hz / fs mod 1 in 0.64 fixed point; the top 24 bits of ph give sine and cosine, as in
+ * gpsmi_acq_refine.  theta of the next bit is theta + (floor(tau') - floor(tau)) * inc: the NCO is
+ * phase-continuous and the loops act on f_hz alone.
+ * Update, float64, in this order, once per bit (b = bit_no before the bit):
+ *     e_f = atan2(H0.re H1.im - H0.im H1.re, H0.re H1.re + H0.im H1.im) / (2 pi 0.010)         [Hz]
+ *     e_p = atan(P.im / P.re) / (2 pi)   (P.re = 0: 0.25 sign(P.im))                        [cycles]
+ *     e_d = (cs / 1023 - tap) (|L| - |E|) / (|E| + |L|)   (0 when |E| + |L| = 0)           [samples]
+ *           e_d > 0: the late tap is the larger, the code start lies LATER than tau
+ *     the PLL term is off (e_p taken as 0) while b < pull_in_bits and when pll_bw_hz < 0, the FLL
+ *     term when fll_bw_hz < 0
+ *     f_acc += w_p^2 T e_p + w_f T e_f          w_p = pll_bw_hz / 0.53, w_f = fll_bw_hz / 0.25
+ *     f_hz'  = f_acc + 1.414 w_p e_p            (Kaplan & Hegarty ch. 5, table of loop filters;
+ *     tau'   = (tau + 20 Tc) + 4 dll_bw_hz T e_d   w = B / 0.25 first order, B / 0.53 and a2 = 1.414
+ *                                                  second order; plain, not bilinear, integrators)
+ *     mu_ring[b mod 50] = |P|^2 / sum_k |prompt tap of k|^2 (0 for an all-zero bit); cn0_dbhz is
+ *     gpsmi_acq_refine's estimator on the mean of the first min(b + 1, 50) ring entries, in index order
+ *     lock  += 0.05 ((P.re^2 - P.im^2) / |P|^2 - lock)      (the term 0 when P = 0)
+ * The record holds tau and f_hz as the bit USED them; the state holds tau', f_hz', theta'.
+ * One workgroup per channel, no atomics, every sum in one order: a channel's records and final
+ * state are the same bytes alone or among others, in any order, from complex64 or GPSMI_IQ_U8,
+ * from host (gpsmi_acq_track) or device memory (gpsmi_acq_track_dev), in one call or in chunks.
+ * bits is host memory [nhits][cfg.n_bits]; the records past a channel's last bit of the call are
+ * zero.  nhits 1 .. 64, n_bits 1 .. 2^20; code_samples 2048 and 16368 only (GPSMI_E_UNSUPPORTED).
+ * Argument errors are GPSMI_E_ARG and need no GPU (gpsmi_acq_track_plan makes the same checks without
+ * a handle): among them a state whose next bit starts before the data, floor(tau) - tap <
+ * first_sample.  GPSMI_E_STATE: no time-domain replica for a PRN; GPSMI_E_NOMEM leaves the handle
+ * usable.  The call returns when the work is done; gpsmi_acq_last_ms reports it.                 */
+#define GPSMI_WTRK_DATA_END 1u      /* flags: the channel stopped before n_bits because the data ended */
+#define GPSMI_WTRK_RING 50
+typedef struct gpsmi_wtrk_cfg {     /* no implicit padding: 64 bytes */
+    int32_t n_bits;                 /* bits to track in this call, >= 1 */
+    int32_t tap_samples;            /* early / late spacing; 0: 1 at 2048, 8 at 16368 */
+    double  pll_bw_hz;              /* noise bandwidths; 0: the default (4, 1, 0.5); */
+    double  fll_bw_hz;              /*   a negative pll_bw_hz / fll_bw_hz switches that term off; */
+    double  dll_bw_hz;              /*   dll_bw_hz >= 0 */
+    double  carrier_hz;             /* as in gpsmi_acq_refine */
+    double  f_offset_hz;
+    int64_t first_sample;           /* the stream index of iq[0] */
+    int32_t pull_in_bits;           /* FLL-only bits of a fresh channel; 0: the default (10); < 0: none */
+    int32_t reserved;               /* 0 */
+} gpsmi_wtrk_cfg;
+typedef struct gpsmi_wtrk_state {   /* no implicit padding: 256 bytes */
+    int32_t  prn;
+    int32_t  bit_no;                /* bits tracked so far */
+    double   tau;                   /* stream position (samples) of the next bit's first code start */
+    double   f_hz;                  /* NCO frequency of the next bit */
+    uint64_t theta;                 /* carrier phase at sample floor(tau), cycles in 0.64 fixed point */
+    double   f_acc;                 /* the carrier loop's integrator, Hz */
+    double   lock;                  /* the phase-lock indicator, smoothed */
+    uint32_t flags;                 /* GPSMI_WTRK_DATA_END */
+    int32_t  reserved;              /* 0 */
+    float    mu_ring[GPSMI_WTRK_RING];   /* the C/N0 estimator's last <= 50 bits */
+} gpsmi_wtrk_state;
+typedef struct gpsmi_wtrk_bit {     /* no implicit padding: 64 bytes */
+    float   p_i, p_q;               /* P, the prompt of the bit */
+    float   abs_e, abs_l;           /* |E|, |L| */
+    float   h0_i, h0_q, h1_i, h1_q; /* H0, H1: the prompts of the two 10-ms halves */
+    double  f_hz;                   /* as the bit used them */
+    double  tau;
+    float   cn0_dbhz;               /* running; NaN while the mean mu <= 1 */
+    float   lock;                   /* after this bit */
+    float   dll_err;                /* e_d, samples */
+    int32_t bit_no;                 /* b */
+} gpsmi_wtrk_bit;
+int gpsmi_acq_track(gpsmi_acq* h, const void* iq, size_t n, gpsmi_wtrk_state* states, int nhits,
+                    const gpsmi_wtrk_cfg* cfg, gpsmi_wtrk_bit* bits);
+int gpsmi_acq_track_dev(gpsmi_acq* h, const void* d_iq, size_t n, gpsmi_wtrk_state* states, int nhits,
+                        const gpsmi_wtrk_cfg* cfg, gpsmi_wtrk_bit* bits);
+/* host only, no GPU: the argument checks of gpsmi_acq_track for a handle of code_samples */
+int gpsmi_acq_track_plan(int code_samples, size_t n, const gpsmi_wtrk_state* states, int nhits,
+                         const gpsmi_wtrk_cfg* cfg);
+/* host only: a fresh channel from a record of gpsmi_acq_refine.  data_start is the stream index of
+ * the first sample of the data that was refined, refine_tap_samples the tap_samples of that call (0:
+ * its default).  The integer delay the hit was refined at is rint(code_phase - v), v the vertex the
+ * record's tap_metric gives; as refinement does, a delay below the tap spacing counts from the next
+ * code period (e = edge_ms + 1 then, else edge_ms).  tau = data_start + code_phase + e * Tc with Tc of
+ * rec.f_hz as above, f_hz = f_acc = rec.f_hz, theta = 0, everything else 0.  GPSMI_E_ARG for a record
+ * without a code phase (-1).                                                                    */
+int gpsmi_wtrk_open(const gpsmi_refine_out* rec, int code_samples, int refine_tap_samples,
+                    int64_t data_start, double carrier_hz, double f_offset_hz, gpsmi_wtrk_state* st);
 /* Input format of the iq pointers of the search calls that follow (host or device), as
  * gpsmi_trk_set_input_format below: GPSMI_IQ_U8 = the raw recording of streamData
  * (gpsrecv.py:162-173), decoded where the carrier wipe-off reads it; same bits out.   */

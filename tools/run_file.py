@@ -5,7 +5,7 @@ gpseval) as one command on the GPU path.
 
     python tools/run_file.py <recording.bin> [--seconds S] [--start-stream K] [--save-pickle P]
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--blank] [--json]
-                             [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine]]
+                             [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track]]]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -35,7 +35,13 @@ normMaxCorr of what it finds and changes nothing else: the satellites are not ha
 --refine (with --deep-acq) refines what the second pass found on the same data: Acquisition.refineHits
  integrates coherently over each 20-ms data bit and prints the fine Doppler, the bit
 edge, the sub-sample code phase, C/N0 and its own detection ratio per satellite -- what a tracking
-channel for such a signal would be opened with (acquisition.hit_at); opening one is still not done.
+channel of the reference's kind would be opened with (acquisition.hit_at).
+--track (with --refine) opens a bit-synchronous tracking channel on every confirmed hit
+(Acquisition.trackHits / AcqEngine.track_weak) and follows it through the recording in
+chunks: 20-ms coherent sums between the bit edges refinement found, carrier and code loops closed at
+50 Hz.  It prints, per PRN, the bits tracked, the Doppler (mean of the last 20 bits), the code phase,
+C/N0 and the phase-lock indicator at the end, and the device time.  The bits are not fed into the
+position fix.
 
 There is no recording in this repository (data/test.bin is absent from the reference
 checkout, SURVEY F2, and too short for a fix even upstream): tests/test_run_file.py writes a
@@ -75,12 +81,67 @@ def cpu_cold_acquisition(path, n_blocks=5):
             'found': [(int(s), float(f), int(d)) for _, s, f, d in found]}
 
 
-def deep_acquisition(path, seconds, start_stream, skip_prns, frontend=None, n_coh=4, refine=False):
+TRACK_CHUNK_BLOCKS = 16
+
+
+def track_refined(acq, rec, whole, source, cfg):
+    """--track: channels on the confirmed records of refineHits, followed through `whole` (the data
+    they were refined on, stream index 0) and the blocks `source` still yields, in chunks of
+    TRACK_CHUNK_BLOCKS blocks; between chunks the samples before the earliest channel's next bit are
+    dropped and first_sample moves up."""
+    from gpsmi.acquisition import open_weak_channels
+    cs = cfg.code_samples
+    tap = 1 if cs == 2048 else 8
+    good = rec[(rec['confirmed'] == 1) & (rec['code_phase'] >= 0)]
+    if not len(good):
+        return {'device_ms': 0.0, 'chunks': 0, 'channels': []}
+    states = open_weak_channels(good, cfg)
+    hist = [[] for _ in good]                       # (f_hz, cn0, lock) of every bit
+    buf, first, ms, chunks = whole, 0, 0.0, 0
+    step = TRACK_CHUNK_BLOCKS * cfg.ngps
+    pos = 0                                          # samples of `whole` handed on so far
+    pending = whole[:0]
+    done = False
+    while not done:
+        if pos < len(whole):
+            pending = np.concatenate([pending, whole[pos:pos + step]])
+            pos += step
+        else:
+            got = [b for _, b in zip(range(TRACK_CHUNK_BLOCKS), source)]
+            done = len(got) < TRACK_CHUNK_BLOCKS
+            if got:
+                pending = np.concatenate([pending] + got)
+        n_bits = len(pending) // (20 * cs) + 1
+        bits, new = acq.engine.track_weak(pending, states, n_bits, first_sample=first)
+        ms += acq.engine.last_ms()
+        chunks += 1
+        for h in range(len(good)):
+            k = int(new['bit_no'][h] - states['bit_no'][h])
+            hist[h] += [(float(r['f_hz']), float(r['cn0_dbhz']), float(r['lock'])) for r in bits[h, :k]]
+        states = new
+        lo = int(np.floor(states['tau']).min()) - tap
+        if lo > first:
+            pending = pending[lo - first:]
+            first = lo
+    chans = []
+    for h, st in enumerate(states):
+        f = [x[0] for x in hist[h][-20:]]
+        cn0 = hist[h][-1][1] if hist[h] else float('nan')
+        chans.append({'prn': int(st['prn']), 'bits': int(st['bit_no']),
+                      'f_hz': round(float(np.mean(f)), 2) if f else round(float(st['f_hz']), 2),
+                      'code_phase': round(float(st['tau'] % cs), 3),
+                      'cn0_dbhz': None if np.isnan(cn0) else round(cn0, 2),
+                      'lock': round(hist[h][-1][2], 3) if hist[h] else 0.0})
+    return {'device_ms': round(ms, 3), 'chunks': chunks, 'channels': chans}
+
+
+def deep_acquisition(path, seconds, start_stream, skip_prns, frontend=None, n_coh=4, refine=False, track=False):
     """--deep-acq: Acquisition.sweepDeepSats (code-Doppler-compensated non-coherent search, DESIGN.md
     4.2e) over the first `seconds` of the recording, n_coh-ms segments, the reference's 50 bins, for
-    the PRNs not in `skip_prns`.  Reports only: nothing is handed to tracking.  refine: the hits
-    are refined on the blocks read (Acquisition.refineHits) and reported under
-    'refined'."""
+    the PRNs not in `skip_prns`.  refine: the hits are refined on the blocks read
+    (Acquisition.refineHits) and reported under 'refined'; track: the confirmed ones
+    are then tracked through the rest of the recording (track_refined) and reported under 'tracked'.
+    Nothing is handed to the receiver's own tracking."""
     from gpsmi import ingest
     from gpsmi.acquisition import Acquisition, SAT_ALL
     from gpsmi.engine import Config
@@ -102,9 +163,9 @@ def deep_acquisition(path, seconds, start_stream, skip_prns, frontend=None, n_co
         have += len(blk)
         if have >= need:
             break
-    if fe is not None:
-        fe.close()
     if have < need:
+        if fe is not None:
+            fe.close()
         sys.exit(f'--deep-acq: the recording holds {have} samples after stream {start_stream}, '
                  f'{seconds} s need {need}')
     whole = np.concatenate(blocks)
@@ -128,18 +189,24 @@ def deep_acquisition(path, seconds, start_stream, skip_prns, frontend=None, n_co
                                        'cn0_dbhz': None if np.isnan(r['cn0_dbhz']) else round(float(r['cn0_dbhz']), 2),
                                        'ratio': round(float(r['ratio']), 3), 'confirmed': bool(r['confirmed'])}
                                       for r in rec]}
+        if track:
+            out['tracked'] = track_refined(acq, rec, whole, source, cfg)
     elif refine:
         out['refined'] = {'n_ms': 0, 'device_ms': 0.0, 'records': []}
+        if track:
+            out['tracked'] = {'device_ms': 0.0, 'chunks': 0, 'channels': []}
+    if fe is not None:
+        fe.close()
     acq.engine.close()
     return out
 
 
 def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, cpu_acq=False, report_lag=16,
-        excise=False, frontend=None, blank=False, deep_acq=None, refine=False):
+        excise=False, frontend=None, blank=False, deep_acq=None, refine=False, track=False):
     """frontend: None (the recorder's u8 format at 2.048 Msps) or a dict of frontend.FrontEnd's
     keyword arguments (fs_in, fmt, if_hz, conjugate).  deep_acq: None, or the seconds of the
     recording's start that deep_acquisition searches for the PRNs the sweep did not acquire; refine:
-    its hits are refined as well."""
+    its hits are refined as well; track: the confirmed ones are tracked bit-synchronously."""
     from gpsmi import ingest, position as P
     from gpsmi.engine import Config
     from gpsmi.pipeline import Receiver, save_results
@@ -200,7 +267,8 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
         out['cpu_cold_acquisition'] = cpu_cold_acquisition(path)
     if deep_acq:
         out['deep_acquisition'] = deep_acquisition(path, deep_acq, start_stream,
-                                                   {s for s, _, _ in out['acquired']}, frontend, refine=refine)
+                                                   {s for s, _, _ in out['acquired']}, frontend, refine=refine,
+                                                   track=track)
     return out
 
 
@@ -229,10 +297,14 @@ def main():
                          'compensated (DESIGN.md 4.2e); printed only')
     ap.add_argument('--refine', action='store_true',
                     help='with --deep-acq: refine its hits (fine Doppler, bit edge, code phase, C/N0; DESIGN.md 4.2f)')
+    ap.add_argument('--track', action='store_true',
+                    help='with --refine: track the confirmed hits bit-synchronously through the recording (DESIGN.md 4.2g)')
     ap.add_argument('--json', action='store_true', help='one JSON line instead of text')
     a = ap.parse_args()
     if a.refine and not a.deep_acq:
         ap.error('--refine needs --deep-acq SECONDS')
+    if a.track and not a.refine:
+        ap.error('--track needs --refine')
     frontend = None
     if a.format is not None or a.fs is not None or a.if_hz is not None or a.conjugate:
         frontend = {'fmt': a.format or 'u8iq', 'fs_in': a.fs or 2048000, 'if_hz': a.if_hz or 0.0,
@@ -242,7 +314,7 @@ def main():
         with open(a.ephemeris) as f:
             eph = {int(k): v for k, v in json.load(f).items()}
     out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise,
-              frontend, a.blank, a.deep_acq, a.refine)
+              frontend, a.blank, a.deep_acq, a.refine, a.track)
     if a.json:
         print(json.dumps(out))
         return
@@ -272,6 +344,13 @@ def main():
                 cn0 = 'n/a' if q['cn0_dbhz'] is None else f"{q['cn0_dbhz']:.1f}"
                 print(f"  PRN {q['prn']:2d}  f_hz {q['f_hz']:+9.2f}  edge_ms {q['edge_ms']:2d}  code_phase {q['code_phase']:8.3f}  "
                       f"cn0_dbhz {cn0}  ratio {q['ratio']:.2f}  confirmed {q['confirmed']}")
+        if 'tracked' in d:
+            t = d['tracked']
+            print(f"tracked {len(t['channels'])} channels in {t['chunks']} chunks ({t['device_ms']} ms on the device):")
+            for q in t['channels']:
+                cn0 = 'n/a' if q['cn0_dbhz'] is None else f"{q['cn0_dbhz']:.1f}"
+                print(f"  PRN {q['prn']:2d}  bits {q['bits']:5d}  f_hz {q['f_hz']:+9.2f}  code_phase {q['code_phase']:8.3f}  "
+                      f"cn0_dbhz {cn0}  lock {q['lock']:+.2f}")
 
 
 if __name__ == '__main__':
