@@ -21,16 +21,17 @@
 //                         the deep search (gpsmi_acq_search_deep): the same mean
 //                         with every segment's magnitudes rotated by the code-Doppler slide.
 //   refine_prompt_kernel, refine_grid_kernel, refine_final_kernel (gpsmi_refine.h)
-//   wtrk_kernel (gpsmi_wtrk.h)
-//                         bit-synchronous tracking of refined hits (gpsmi_acq_track, DESIGN.md 4.2g)
 //                         refinement of weak / deep hits (gpsmi_acq_refine): fine
 //                         Doppler, bit edge, sub-sample code phase, C/N0.
+//   wtrk_kernel (gpsmi_wtrk.h)
+//                         bit-synchronous tracking of refined hits (gpsmi_acq_track, DESIGN.md 4.2g)
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "gpsmi_common.h"
+#include "gpsmi_devmem.h"
 #include "gpsmi_bigfft.h"
 #include "gpsmi_pfa.h"
 #include "gpsmi_direct.h"
@@ -387,15 +388,17 @@ struct gpsmi_acq {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t order = nullptr;        // orders other handles' streams behind this one
-    float2* d_tw = nullptr;
-    float* d_t32 = nullptr;
-    float2* d_rep = nullptr;          // [GPSMI_MAX_PRN + 1][cs]
+    // device memory: every buffer is a DevBuf (gpsmi_devmem.h) with a capacity of its own, in elements
+    DevBuf<float2> d_tw;
+    DevBuf<float> d_t32;
+    DevBuf<float2> d_rep;             // [GPSMI_MAX_PRN + 1][cs]
     bool have_rep[GPSMI_MAX_PRN + 1] = {};
-    float2* d_iq = nullptr;  size_t iq_cap = 0;
-    float2* d_spec = nullptr; size_t spec_cap = 0;   // bins
-    float* d_omega = nullptr; int* d_slot = nullptr; gpsmi_peak* d_peaks = nullptr;
-    size_t cell_cap = 0;
-    float2* d_nbr = nullptr;
+    DevBuf<float2> d_iq;              // host input of any entry point, sized as complex64 (acq_upload)
+    DevBuf<float2> d_spec;            // [bins][2048]
+    DevBuf<float> d_omega;            // [bins]
+    DevBuf<int> d_slot;
+    DevBuf<gpsmi_peak> d_peaks;       // [bins][nsv]
+    DevBuf<float2> d_nbr;
     // page-locked staging of the per-call parameters (two sets: a search can be enqueued
     // while the previous one still runs; no blocking copy, no use of the null stream)
     float* h_om[2] = {nullptr, nullptr};
@@ -405,31 +408,32 @@ struct gpsmi_acq {
     int stage = 0;
     // direct (time-domain) path for code_samples != 2048
     bool direct = false;
-    float* d_rep_time = nullptr;            // [GPSMI_MAX_PRN + 1][cs]
+    DevBuf<float> d_rep_time;               // [GPSMI_MAX_PRN + 1][cs]
     bool have_time[GPSMI_MAX_PRN + 1] = {};
-    float2* d_fold = nullptr; float* d_mag = nullptr; DirStats* d_stats = nullptr;
-    int* d_xsel = nullptr; int* d_rsel = nullptr;
-    size_t dir_bins = 0, dir_cells = 0;
+    DevBuf<float2> d_fold;                  // [bins][cs]
+    DevBuf<float> d_mag;                    // [cells][cs], the paths without the native correlation
+    DevBuf<DirStats> d_stats;               // [cells], as d_xsel and d_rsel
+    DevBuf<int> d_xsel, d_rsel;
     // ... through one 32768-point FFT pair when the code period fits (gpsmi_bigfft.h)
     bool big = false;
-    float2* d_twN = nullptr; float2* d_RS = nullptr; float2* d_S = nullptr;
+    DevBuf<float2> d_twN, d_RS, d_S;
     // ... or natively in LDS when the code period is 16368 = 16 * 3 * 11 * 31 samples (gpsmi_pfa.h)
     bool pfa = false;
-    float2* d_RSp = nullptr;                // [GPSMI_MAX_PRN + 1][16368] replica spectra, P3's order
+    DevBuf<float2> d_RSp;                   // [GPSMI_MAX_PRN + 1][16368] replica spectra, P3's order
     // non-coherent search: the per-(bin, segment) spectra (CS = 2048) or folded samples (16368) of
     // one chunk of bins, sized per call (gpsmi_acq_search_nc)
-    float2* d_nc = nullptr; size_t nc_cap = 0;
+    DevBuf<float2> d_nc;
     // deep search: the lag rotation of every (bin, segment) of a call (gpsmi_acq_search_deep)
-    int* d_shift = nullptr; size_t shift_cap = 0;
+    DevBuf<int> d_shift;
     // refinement (gpsmi_acq_refine): prompts [nhits][3][n_ms], grid [nhits][n_df][20], the per-call
     // tables (hits, window starts, df increments, df) in one block, the records
-    float2* d_rp = nullptr; size_t rp_cap = 0;
-    float* d_rm = nullptr; size_t rm_cap = 0;
-    char* d_rt = nullptr; size_t rt_cap = 0;
-    gpsmi_refine_out* d_ro = nullptr;
+    DevBuf<float2> d_rp;
+    DevBuf<float> d_rm;
+    DevBuf<char> d_rt;
+    DevBuf<gpsmi_refine_out> d_ro;          // [kRefMaxHits]
     // bit-synchronous tracking (gpsmi_acq_track): the states of a call, its bit records
-    gpsmi_wtrk_state* d_ws = nullptr;
-    gpsmi_wtrk_bit* d_wb = nullptr; size_t wb_cap = 0;
+    DevBuf<gpsmi_wtrk_state> d_ws;          // [kWtrkMaxHits]
+    DevBuf<gpsmi_wtrk_bit> d_wb;
     int iq_fmt = GPSMI_IQ_C64;              // what the iq pointers of the search calls point to
     float last_ms = 0.f;
     bool pending = false;
@@ -441,24 +445,31 @@ namespace gpsmi {
 HandleSync acq_sync(gpsmi_acq* h) { return HandleSync{h->stream, h->order, h->cfg.device, nullptr}; }
 }  // namespace gpsmi
 
+// the buffers every search needs: per bin, per cell
 static int acq_reserve(gpsmi_acq* h, int nbins, int nsv) {
-    if ((size_t)nbins > h->spec_cap) {
-        if (h->d_spec) GPSMI_HIP(hipFree(h->d_spec));
-        if (h->d_omega) GPSMI_HIP(hipFree(h->d_omega));
-        h->d_spec = nullptr; h->d_omega = nullptr; h->spec_cap = 0;
-        GPSMI_HIP(hipMalloc((void**)&h->d_spec, (size_t)nbins * kFftN * sizeof(float2)));
-        GPSMI_HIP(hipMalloc((void**)&h->d_omega, (size_t)nbins * sizeof(float)));
-        h->spec_cap = nbins;
-    }
-    size_t cells = (size_t)nbins * nsv;
-    if (cells > h->cell_cap) {
-        if (h->d_peaks) GPSMI_HIP(hipFree(h->d_peaks));
-        if (h->d_nbr) GPSMI_HIP(hipFree(h->d_nbr));
-        h->d_peaks = nullptr; h->d_nbr = nullptr; h->cell_cap = 0;
-        GPSMI_HIP(hipMalloc((void**)&h->d_peaks, cells * sizeof(gpsmi_peak)));
-        GPSMI_HIP(hipMalloc((void**)&h->d_nbr, cells * sizeof(float2)));
-        h->cell_cap = cells;
-    }
+    const size_t cells = (size_t)nbins * nsv;
+    int rc = h->d_spec.reserve((size_t)nbins * kFftN, "gpsmi_acq spectra");
+    if (!rc) rc = h->d_omega.reserve(nbins, "gpsmi_acq bin table");
+    if (!rc) rc = h->d_peaks.reserve(cells, "gpsmi_acq peak table");
+    if (!rc) rc = h->d_nbr.reserve(cells, "gpsmi_acq neighbour table");
+    return rc;
+}
+
+// the cells of the time-domain and native-length paths (d_mag: not with the native correlation)
+static int acq_reserve_cells(gpsmi_acq* h, size_t cells) {
+    int rc = h->d_stats.reserve(cells, "gpsmi_acq cell statistics");
+    if (!rc) rc = h->d_xsel.reserve(cells, "gpsmi_acq cell table");
+    if (!rc) rc = h->d_rsel.reserve(cells, "gpsmi_acq cell table");
+    return rc;
+}
+
+// host input of a search, a refinement or a tracking call: `count` samples in the handle's input
+// format into d_iq on the handle's stream (d_iq is sized for complex64; raw input fills a quarter)
+static int acq_upload(gpsmi_acq* h, const void* iq, size_t count) {
+    const int rc = h->d_iq.reserve(count, "gpsmi_acq input block");
+    if (rc) return rc;
+    GPSMI_HIP(hipMemcpyAsync(h->d_iq.p, iq, count * (h->iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)),
+                             hipMemcpyHostToDevice, h->stream));
     return GPSMI_OK;
 }
 
@@ -496,17 +507,17 @@ static int acq_build(const gpsmi_cfg* cfg, gpsmi_acq* h) {
     GPSMI_HIP(hipEventCreate(&h->ev1));
     std::vector<float2> tw;
     make_twiddles(tw);
-    GPSMI_HIP(hipMalloc((void**)&h->d_tw, tw.size() * sizeof(float2)));
-    GPSMI_HIP(hipMemcpy(h->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
+    int rc = h->d_tw.upload(tw, "gpsmi_acq twiddles");
+    if (rc) return rc;
     // SEC_TIME (gpsrecv.py:32-33): float32(k+1) / SAMPLE_RATE in float32
     const int ngps = cfg->n_cyc * cfg->code_samples;
     const float fs = (float)(1000 * cfg->code_samples);
     std::vector<float> t32(ngps);
     for (int k = 0; k < ngps; ++k) t32[k] = (float)(k + 1) / fs;
-    GPSMI_HIP(hipMalloc((void**)&h->d_t32, ngps * sizeof(float)));
-    GPSMI_HIP(hipMemcpy(h->d_t32, t32.data(), ngps * sizeof(float), hipMemcpyHostToDevice));
-    GPSMI_HIP(hipMalloc((void**)&h->d_rep, (size_t)(GPSMI_MAX_PRN + 1) * kFftN * sizeof(float2)));
-    GPSMI_HIP(hipMalloc((void**)&h->d_slot, (GPSMI_MAX_PRN + 1) * sizeof(int)));
+    if ((rc = h->d_t32.upload(t32, "gpsmi_acq time base")) ||
+        (rc = h->d_rep.reserve((size_t)(GPSMI_MAX_PRN + 1) * kFftN, "gpsmi_acq replica spectra")) ||
+        (rc = h->d_slot.reserve(GPSMI_MAX_PRN + 1, "gpsmi_acq PRN table")))
+        return rc;
     for (int k = 0; k < 2; ++k) {
         GPSMI_HIP(hipHostMalloc((void**)&h->h_om[k], 65536 * sizeof(float), hipHostMallocDefault));
         GPSMI_HIP(hipHostMalloc((void**)&h->h_slot[k], (GPSMI_MAX_PRN + 1) * sizeof(int32_t),
@@ -514,27 +525,24 @@ static int acq_build(const gpsmi_cfg* cfg, gpsmi_acq* h) {
         GPSMI_HIP(hipEventCreateWithFlags(&h->staged[k], hipEventDisableTiming));
     }
     if (h->direct) {
-        GPSMI_HIP(hipMalloc((void**)&h->d_rep_time,
-                            (size_t)(GPSMI_MAX_PRN + 1) * cfg->code_samples * sizeof(float)));
+        if ((rc = h->d_rep_time.reserve((size_t)(GPSMI_MAX_PRN + 1) * cfg->code_samples, "gpsmi_acq replicas")))
+            return rc;
         long long forced = 0;                    // option "codephase": 1 keeps the time-domain kernel,
         default_opt("codephase", &forced, 0);    // 2 the zero-padded 32768-point pair
         h->pfa = cfg->code_samples == kPfaL && forced == 0;
         h->big = !h->pfa && 2 * cfg->code_samples - 1 <= kBigN && forced != 1;
-        if (h->pfa) {
-            const size_t b = (size_t)(GPSMI_MAX_PRN + 1) * kPfaL * sizeof(float2);
-            GPSMI_HIP(hipMalloc((void**)&h->d_RSp, b));
-            GPSMI_HIP(hipMemset(h->d_RSp, 0, b));
-        }
+        if (h->pfa && (rc = h->d_RSp.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * kPfaL, "gpsmi_acq replica spectra")))
+            return rc;
         if (h->big) {
             std::vector<float2> twn(kBigN);
             for (int k = 0; k < kBigN; ++k) {
                 const double a = -2.0 * M_PI * (double)k / (double)kBigN;
                 twn[k] = make_float2((float)cos(a), (float)sin(a));
             }
-            GPSMI_HIP(hipMalloc((void**)&h->d_twN, kBigN * sizeof(float2)));
-            GPSMI_HIP(hipMemcpy(h->d_twN, twn.data(), kBigN * sizeof(float2), hipMemcpyHostToDevice));
-            GPSMI_HIP(hipMalloc((void**)&h->d_RS, (size_t)(GPSMI_MAX_PRN + 1) * kBigN * sizeof(float2)));
-            GPSMI_HIP(hipMalloc((void**)&h->d_S, (size_t)kBigChunkCells * kBigN * sizeof(float2)));
+            if ((rc = h->d_twN.upload(twn, "gpsmi_acq twiddles")) ||
+                (rc = h->d_RS.reserve((size_t)(GPSMI_MAX_PRN + 1) * kBigN, "gpsmi_acq replica spectra")) ||
+                (rc = h->d_S.reserve((size_t)kBigChunkCells * kBigN, "gpsmi_acq correlation scratch")))
+                return rc;
         }
     }
     return GPSMI_OK;
@@ -546,12 +554,6 @@ int gpsmi_acq_destroy(gpsmi_acq* h) {
     if (!h) return GPSMI_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* bufs[] = {h->d_tw, h->d_t32, h->d_rep, h->d_iq, h->d_spec, h->d_omega, h->d_slot,
-                    h->d_peaks, h->d_nbr, h->d_rep_time, h->d_fold, h->d_mag, h->d_stats,
-                    h->d_xsel, h->d_rsel, h->d_twN, h->d_RS, h->d_S, h->d_RSp, h->d_nc,
-                    h->d_shift, h->d_rp, h->d_rm, h->d_rt, h->d_ro, h->d_ws, h->d_wb};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
     for (int k = 0; k < 2; ++k) {
         if (h->h_om[k]) (void)hipHostFree(h->h_om[k]);
         if (h->h_slot[k]) (void)hipHostFree(h->h_slot[k]);
@@ -561,7 +563,7 @@ int gpsmi_acq_destroy(gpsmi_acq* h) {
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                                // (releases the device buffers)
     return GPSMI_OK;
 }
 
@@ -570,20 +572,19 @@ int gpsmi_acq_set_replica_time(gpsmi_acq* h, int prn, const float* replica) {
     GPSMI_REQUIRE(prn >= 1 && prn <= GPSMI_MAX_PRN, "prn out of range 1..37");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     if (!h->direct) {                        // the FFT path has no use for it: kept for gpsmi_acq_refine
-        if (!h->d_rep_time)
-            GPSMI_HIP(hipMalloc((void**)&h->d_rep_time,
-                                (size_t)(GPSMI_MAX_PRN + 1) * h->cfg.code_samples * sizeof(float)));
-        GPSMI_HIP(hipMemcpy(h->d_rep_time + (size_t)prn * h->cfg.code_samples, replica,
+        const int rc = h->d_rep_time.reserve((size_t)(GPSMI_MAX_PRN + 1) * h->cfg.code_samples, "gpsmi_acq replicas");
+        if (rc) return rc;
+        GPSMI_HIP(hipMemcpy(h->d_rep_time.p + (size_t)prn * h->cfg.code_samples, replica,
                             (size_t)h->cfg.code_samples * sizeof(float), hipMemcpyHostToDevice));
         h->have_time[prn] = true;
         return GPSMI_OK;
     }
-    GPSMI_HIP(hipMemcpy(h->d_rep_time + (size_t)prn * h->cfg.code_samples, replica,
+    GPSMI_HIP(hipMemcpy(h->d_rep_time.p + (size_t)prn * h->cfg.code_samples, replica,
                         (size_t)h->cfg.code_samples * sizeof(float), hipMemcpyHostToDevice));
     if (h->big)
-        big_replica_launch(h->stream, h->d_rep_time, prn, h->cfg.code_samples, h->d_RS, h->d_tw,
-                           h->d_twN);
-    if (h->pfa) pfa_replica_launch(h->stream, h->d_rep_time, prn, h->d_RSp);
+        big_replica_launch(h->stream, h->d_rep_time.p, prn, h->cfg.code_samples, h->d_RS.p, h->d_tw.p,
+                           h->d_twN.p);
+    if (h->pfa) pfa_replica_launch(h->stream, h->d_rep_time.p, prn, h->d_RSp.p);
     if (h->big || h->pfa) {
         GPSMI_HIP(hipGetLastError());
         GPSMI_HIP(hipStreamSynchronize(h->stream));
@@ -597,7 +598,7 @@ int gpsmi_acq_set_replica(gpsmi_acq* h, int prn, const float* spectrum) {
     GPSMI_REQUIRE(prn >= 1 && prn <= GPSMI_MAX_PRN, "prn out of range 1..37");
     if (h->direct) return fail(GPSMI_E_STATE, "code_samples != 2048: use gpsmi_acq_set_replica_time");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    GPSMI_HIP(hipMemcpy(h->d_rep + (size_t)prn * kFftN, spectrum, kFftN * sizeof(float2),
+    GPSMI_HIP(hipMemcpy(h->d_rep.p + (size_t)prn * kFftN, spectrum, kFftN * sizeof(float2),
                         hipMemcpyHostToDevice));
     h->have_rep[prn] = true;
     return GPSMI_OK;
@@ -610,9 +611,9 @@ static int acq_stage(gpsmi_acq* h, const int32_t* prn, int nsv, const double* fr
     if (h->staged_used[sg]) GPSMI_HIP(hipEventSynchronize(h->staged[sg]));
     for (int b = 0; b < nbins; ++b) h->h_om[sg][b] = (float)(2.0 * M_PI * freqs[b]);
     for (int i = 0; i < nsv; ++i) h->h_slot[sg][i] = prn[i];
-    GPSMI_HIP(hipMemcpyAsync(h->d_omega, h->h_om[sg], nbins * sizeof(float), hipMemcpyHostToDevice,
+    GPSMI_HIP(hipMemcpyAsync(h->d_omega.p, h->h_om[sg], nbins * sizeof(float), hipMemcpyHostToDevice,
                              h->stream));
-    GPSMI_HIP(hipMemcpyAsync(h->d_slot, h->h_slot[sg], nsv * sizeof(int), hipMemcpyHostToDevice,
+    GPSMI_HIP(hipMemcpyAsync(h->d_slot.p, h->h_slot[sg], nsv * sizeof(int), hipMemcpyHostToDevice,
                              h->stream));
     GPSMI_HIP(hipEventRecord(h->staged[sg], h->stream));
     h->staged_used[sg] = true;
@@ -623,11 +624,11 @@ static int acq_stage(gpsmi_acq* h, const int32_t* prn, int nsv, const double* fr
 static int acq_copy_out(gpsmi_acq* h, int nbins, int nsv, gpsmi_peak* out, void* out_dev, float* nbr) {
     size_t bytes = (size_t)nbins * nsv * sizeof(gpsmi_peak);
     if (out_dev)
-        GPSMI_HIP(hipMemcpyAsync(out_dev, h->d_peaks, bytes, hipMemcpyDeviceToDevice, h->stream));
+        GPSMI_HIP(hipMemcpyAsync(out_dev, h->d_peaks.p, bytes, hipMemcpyDeviceToDevice, h->stream));
     if (out)
-        GPSMI_HIP(hipMemcpyAsync(out, h->d_peaks, bytes, hipMemcpyDeviceToHost, h->stream));
+        GPSMI_HIP(hipMemcpyAsync(out, h->d_peaks.p, bytes, hipMemcpyDeviceToHost, h->stream));
     if (nbr)
-        GPSMI_HIP(hipMemcpyAsync(nbr, h->d_nbr, (size_t)nbins * nsv * sizeof(float2),
+        GPSMI_HIP(hipMemcpyAsync(nbr, h->d_nbr.p, (size_t)nbins * nsv * sizeof(float2),
                                  hipMemcpyDeviceToHost, h->stream));
     h->pending = true;
     return GPSMI_OK;
@@ -657,92 +658,51 @@ static int acq_search_impl(gpsmi_acq* h, const void* d_iq, size_t n, const int32
     if (rc) return rc;
     if (h->direct) {
         const size_t cells = (size_t)nbins * nsv;
-        if ((size_t)nbins > h->dir_bins) {
-            if (h->d_fold) GPSMI_HIP(hipFree(h->d_fold));
-            h->d_fold = nullptr; h->dir_bins = 0;
-            GPSMI_HIP(hipMalloc((void**)&h->d_fold, (size_t)nbins * cs * sizeof(float2)));
-            h->dir_bins = nbins;
-        }
-        if (cells > h->dir_cells) {
-            void* olds[] = {h->d_mag, h->d_stats, h->d_xsel, h->d_rsel};
-            for (void* p : olds)
-                if (p) GPSMI_HIP(hipFree(p));
-            h->d_mag = nullptr; h->d_stats = nullptr; h->d_xsel = h->d_rsel = nullptr;
-            h->dir_cells = 0;
-            if (!h->pfa) GPSMI_HIP(hipMalloc((void**)&h->d_mag, cells * cs * sizeof(float)));
-            GPSMI_HIP(hipMalloc((void**)&h->d_stats, cells * sizeof(DirStats)));
-            GPSMI_HIP(hipMalloc((void**)&h->d_xsel, cells * sizeof(int)));
-            GPSMI_HIP(hipMalloc((void**)&h->d_rsel, cells * sizeof(int)));
-            h->dir_cells = cells;
-        }
+        if ((rc = h->d_fold.reserve((size_t)nbins * cs, "gpsmi_acq folded samples")) ||
+            (!h->pfa && (rc = h->d_mag.reserve(cells * cs, "gpsmi_acq magnitudes"))) ||
+            (rc = acq_reserve_cells(h, cells)))
+            return rc;
     }
     GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
     if (h->direct) {
         const int ncell = nbins * nsv;
-        if (h->iq_fmt == GPSMI_IQ_U8)
-            hipLaunchKernelGGL(acq_fold_kernel<1>, dim3((cs + 255) / 256, nbins), dim3(256), 0, h->stream,
-                               d_iq, h->d_t32, h->d_omega, n_avg, cs, h->d_fold);
-        else
-            hipLaunchKernelGGL(acq_fold_kernel<0>, dim3((cs + 255) / 256, nbins), dim3(256), 0, h->stream,
-                               d_iq, h->d_t32, h->d_omega, n_avg, cs, h->d_fold);
+        with_fmt(h->iq_fmt, [&](auto fmt) {
+            hipLaunchKernelGGL(acq_fold_kernel<decltype(fmt)::value>, dim3((cs + 255) / 256, nbins), dim3(256), 0,
+                               h->stream, d_iq, h->d_t32.p, h->d_omega.p, n_avg, cs, h->d_fold.p);
+        });
         hipLaunchKernelGGL(acq_cells_kernel, dim3((ncell + 255) / 256), dim3(256), 0, h->stream,
-                           h->d_xsel, h->d_rsel, h->d_slot, nsv, ncell);
+                           h->d_xsel.p, h->d_rsel.p, h->d_slot.p, nsv, ncell);
         if (h->pfa)              // transform, product, transform and statistics in one launch
-            pfa_corr_launch(h->stream, h->d_fold, h->d_xsel, h->d_rsel, ncell, h->d_RSp, h->d_stats);
+            pfa_corr_launch(h->stream, h->d_fold.p, h->d_xsel.p, h->d_rsel.p, ncell, h->d_RSp.p, h->d_stats.p);
         else if (h->big)
-            big_corr_launch(h->stream, h->d_fold, h->d_xsel, h->d_rsel, ncell, cs, h->d_RS, h->d_S,
-                            h->d_tw, h->d_twN, h->d_mag);
+            big_corr_launch(h->stream, h->d_fold.p, h->d_xsel.p, h->d_rsel.p, ncell, cs, h->d_RS.p, h->d_S.p,
+                            h->d_tw.p, h->d_twN.p, h->d_mag.p);
         else
             hipLaunchKernelGGL(circ_corr_direct_kernel,
                                dim3((cs + kDirLagsPerWg - 1) / kDirLagsPerWg, ncell), dim3(256), 0,
-                               h->stream, h->d_fold, h->d_rep_time, h->d_xsel, h->d_rsel, cs,
-                               h->d_mag);
+                               h->stream, h->d_fold.p, h->d_rep_time.p, h->d_xsel.p, h->d_rsel.p, cs,
+                               h->d_mag.p);
         if (!h->pfa)
-            hipLaunchKernelGGL(corr_stats_kernel, dim3(ncell), dim3(256), 0, h->stream, h->d_mag, cs,
-                               h->d_stats);
+            hipLaunchKernelGGL(corr_stats_kernel, dim3(ncell), dim3(256), 0, h->stream, h->d_mag.p, cs,
+                               h->d_stats.p);
         hipLaunchKernelGGL(acq_peaks_kernel, dim3((ncell + 255) / 256), dim3(256), 0, h->stream,
-                           h->d_stats, h->d_peaks, nbr ? h->d_nbr : nullptr, ncell);
+                           h->d_stats.p, h->d_peaks.p, nbr ? h->d_nbr.p : nullptr, ncell);
     } else {
-        const bool u8 = h->iq_fmt == GPSMI_IQ_U8;
-        if (n_avg >= 4 && u8)
-            hipLaunchKernelGGL((acq_spectrum_kernel<4, 1>), dim3(nbins), dim3(1024), 0, h->stream,
-                               d_iq, h->d_t32, h->d_omega, n_avg, h->d_spec, h->d_tw);
-        else if (n_avg >= 4)
-            hipLaunchKernelGGL((acq_spectrum_kernel<4, 0>), dim3(nbins), dim3(1024), 0, h->stream,
-                               d_iq, h->d_t32, h->d_omega, n_avg, h->d_spec, h->d_tw);
-        else if (u8)
-            hipLaunchKernelGGL((acq_spectrum_kernel<1, 1>), dim3(nbins), dim3(256), 0, h->stream,
-                               d_iq, h->d_t32, h->d_omega, n_avg, h->d_spec, h->d_tw);
-        else
-            hipLaunchKernelGGL((acq_spectrum_kernel<1, 0>), dim3(nbins), dim3(256), 0, h->stream,
-                               d_iq, h->d_t32, h->d_omega, n_avg, h->d_spec, h->d_tw);
-        hipLaunchKernelGGL(acq_corr_kernel, dim3(nsv, nbins), dim3(256), 0, h->stream, h->d_spec,
-                           h->d_rep, h->d_slot, h->d_peaks, nsv, h->d_tw,
-                           nbr ? h->d_nbr : nullptr);
+        // four groups of 256 threads for the long coherent searches (acq_spectrum_kernel)
+        with_value<4, 1>(n_avg >= 4 ? 4 : 1, [&](auto g) { with_fmt(h->iq_fmt, [&](auto fmt) {
+            constexpr int G = decltype(g)::value;
+            hipLaunchKernelGGL((acq_spectrum_kernel<G, decltype(fmt)::value>), dim3(nbins), dim3(256 * G), 0,
+                               h->stream, d_iq, h->d_t32.p, h->d_omega.p, n_avg, h->d_spec.p, h->d_tw.p);
+        }); });
+        hipLaunchKernelGGL(acq_corr_kernel, dim3(nsv, nbins), dim3(256), 0, h->stream, h->d_spec.p,
+                           h->d_rep.p, h->d_slot.p, h->d_peaks.p, nsv, h->d_tw.p,
+                           nbr ? h->d_nbr.p : nullptr);
     }
     GPSMI_HIP(hipGetLastError());
     GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
     rc = acq_copy_out(h, nbins, nsv, out, out_dev, nbr);
     if (rc || !wait) return rc;
     return gpsmi_acq_wait(h);
-}
-
-// Device memory for the non-coherent and deep searches and the refinement.  An allocation the device cannot serve is
-// GPSMI_E_NOMEM, and the handle stays usable (the buffer is simply absent until a later call).
-static int nc_grow(void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return GPSMI_OK;
-    if (*p) GPSMI_HIP(hipFree(*p));
-    *p = nullptr; *cap = 0;
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        return fail(GPSMI_E_NOMEM, "gpsmi_acq: no device memory for %zu bytes of scratch", bytes);
-    }
-    if (e != hipSuccess)
-        return fail(GPSMI_E_HIP, "hipMalloc: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-    *cap = bytes;
-    return GPSMI_OK;
 }
 
 // Scratch of one chunk of bins of a non-coherent search: the spectra / folded samples of all its
@@ -810,22 +770,10 @@ static int acq_search_nc_impl(gpsmi_acq* h, const void* d_iq, size_t n, const in
     if (rc) return rc;
     size_t nbc = kNcScratchMax / per_bin;
     nbc = nbc < 1 ? 1 : nbc > (size_t)nbins ? (size_t)nbins : nbc;
-    rc = nc_grow((void**)&h->d_nc, &h->nc_cap, nbc * per_bin);
+    rc = h->d_nc.reserve(nbc * n_seg * cs, "gpsmi_acq segment scratch");
     if (rc) return rc;
     const size_t cells = (size_t)nbins * nsv;
-    if (h->pfa && cells > h->dir_cells) {
-        void* olds[] = {h->d_mag, h->d_stats, h->d_xsel, h->d_rsel};
-        for (void* p : olds)
-            if (p) GPSMI_HIP(hipFree(p));
-        h->d_mag = nullptr; h->d_stats = nullptr; h->d_xsel = h->d_rsel = nullptr;
-        h->dir_cells = 0;
-        size_t c0 = 0, c1 = 0, c2 = 0;
-        if ((rc = nc_grow((void**)&h->d_stats, &c0, cells * sizeof(DirStats))) ||
-            (rc = nc_grow((void**)&h->d_xsel, &c1, cells * sizeof(int))) ||
-            (rc = nc_grow((void**)&h->d_rsel, &c2, cells * sizeof(int))))
-            return rc;
-        h->dir_cells = cells;
-    }
+    if (h->pfa && (rc = acq_reserve_cells(h, cells))) return rc;
     rc = acq_stage(h, prn, nsv, freqs, nbins);
     if (rc) return rc;
     if (deep) {
@@ -837,63 +785,50 @@ static int acq_search_nc_impl(gpsmi_acq* h, const void* d_iq, size_t n, const in
         for (int b = 0; b < nbins; ++b)
             for (int s = 0; s < n_seg; ++s)
                 shift[(size_t)b * n_seg + s] = deep_shift(freqs[b], *deep, s, n_coh, cs);
-        size_t bytes = h->shift_cap * sizeof(int);
-        rc = nc_grow((void**)&h->d_shift, &bytes, ns * sizeof(int));
-        h->shift_cap = h->d_shift ? (bytes / sizeof(int)) : 0;
-        if (rc) return rc;
-        GPSMI_HIP(hipMemcpyAsync(h->d_shift, shift.data(), ns * sizeof(int), hipMemcpyHostToDevice,
+        if ((rc = h->d_shift.reserve(ns, "gpsmi_acq lag rotations"))) return rc;
+        GPSMI_HIP(hipMemcpyAsync(h->d_shift.p, shift.data(), ns * sizeof(int), hipMemcpyHostToDevice,
                                  h->stream));
         GPSMI_HIP(hipStreamSynchronize(h->stream));      // (the table is pageable and leaves scope here)
     }
-    const bool u8 = h->iq_fmt == GPSMI_IQ_U8;
     GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
     for (int b0 = 0; b0 < nbins; b0 += (int)nbc) {
         const int nb = nbins - b0 < (int)nbc ? nbins - b0 : (int)nbc;
-        const float* om = h->d_omega + b0;
+        const float* om = h->d_omega.p + b0;
         if (h->pfa) {
             const dim3 grid((cs + 255) / 256, nb, n_seg);
-            if (u8)
-                hipLaunchKernelGGL(acq_fold_nc_kernel<1>, grid, dim3(256), 0, h->stream, d_iq, h->d_t32,
-                                   om, n_coh, n_seg, cs, h->d_nc);
-            else
-                hipLaunchKernelGGL(acq_fold_nc_kernel<0>, grid, dim3(256), 0, h->stream, d_iq, h->d_t32,
-                                   om, n_coh, n_seg, cs, h->d_nc);
+            with_fmt(h->iq_fmt, [&](auto fmt) {
+                hipLaunchKernelGGL(acq_fold_nc_kernel<decltype(fmt)::value>, grid, dim3(256), 0, h->stream, d_iq,
+                                   h->d_t32.p, om, n_coh, n_seg, cs, h->d_nc.p);
+            });
             const int c0 = b0 * nsv, ncc = nb * nsv;
             hipLaunchKernelGGL(acq_cells_kernel, dim3((ncc + 255) / 256), dim3(256), 0, h->stream,
-                               h->d_xsel + c0, h->d_rsel + c0, h->d_slot, nsv, ncc);
+                               h->d_xsel.p + c0, h->d_rsel.p + c0, h->d_slot.p, nsv, ncc);
             if (deep)
-                pfa_deep_corr_launch(h->stream, h->d_nc, h->d_xsel + c0, h->d_rsel + c0, ncc, n_seg,
-                                     h->d_RSp, h->d_stats + c0, h->d_shift + (size_t)b0 * n_seg);
+                pfa_deep_corr_launch(h->stream, h->d_nc.p, h->d_xsel.p + c0, h->d_rsel.p + c0, ncc, n_seg,
+                                     h->d_RSp.p, h->d_stats.p + c0, h->d_shift.p + (size_t)b0 * n_seg);
             else
-                pfa_nc_corr_launch(h->stream, h->d_nc, h->d_xsel + c0, h->d_rsel + c0, ncc, n_seg, h->d_RSp,
-                                   h->d_stats + c0);
+                pfa_nc_corr_launch(h->stream, h->d_nc.p, h->d_xsel.p + c0, h->d_rsel.p + c0, ncc, n_seg, h->d_RSp.p,
+                                   h->d_stats.p + c0);
         } else {
             const dim3 grid(nb, n_seg);
-            if (n_coh >= 4 && u8)
-                hipLaunchKernelGGL((acq_spectrum_nc_kernel<4, 1>), grid, dim3(1024), 0, h->stream, d_iq,
-                                   h->d_t32, om, n_coh, n_seg, h->d_nc, h->d_tw);
-            else if (n_coh >= 4)
-                hipLaunchKernelGGL((acq_spectrum_nc_kernel<4, 0>), grid, dim3(1024), 0, h->stream, d_iq,
-                                   h->d_t32, om, n_coh, n_seg, h->d_nc, h->d_tw);
-            else if (u8)
-                hipLaunchKernelGGL((acq_spectrum_nc_kernel<1, 1>), grid, dim3(256), 0, h->stream, d_iq,
-                                   h->d_t32, om, n_coh, n_seg, h->d_nc, h->d_tw);
-            else
-                hipLaunchKernelGGL((acq_spectrum_nc_kernel<1, 0>), grid, dim3(256), 0, h->stream, d_iq,
-                                   h->d_t32, om, n_coh, n_seg, h->d_nc, h->d_tw);
+            with_value<4, 1>(n_coh >= 4 ? 4 : 1, [&](auto g) { with_fmt(h->iq_fmt, [&](auto fmt) {
+                constexpr int G = decltype(g)::value;
+                hipLaunchKernelGGL((acq_spectrum_nc_kernel<G, decltype(fmt)::value>), grid, dim3(256 * G), 0,
+                                   h->stream, d_iq, h->d_t32.p, om, n_coh, n_seg, h->d_nc.p, h->d_tw.p);
+            }); });
             if (deep)
-                hipLaunchKernelGGL(acq_deep_corr_kernel, dim3(nsv, nb), dim3(256), 0, h->stream, h->d_nc,
-                                   h->d_rep, h->d_slot, h->d_peaks, nsv, n_seg, b0, h->d_tw,
-                                   nbr ? h->d_nbr : nullptr, h->d_shift + (size_t)b0 * n_seg);
+                hipLaunchKernelGGL(acq_deep_corr_kernel, dim3(nsv, nb), dim3(256), 0, h->stream, h->d_nc.p,
+                                   h->d_rep.p, h->d_slot.p, h->d_peaks.p, nsv, n_seg, b0, h->d_tw.p,
+                                   nbr ? h->d_nbr.p : nullptr, h->d_shift.p + (size_t)b0 * n_seg);
             else
-                hipLaunchKernelGGL(acq_nc_corr_kernel, dim3(nsv, nb), dim3(256), 0, h->stream, h->d_nc,
-                                   h->d_rep, h->d_slot, h->d_peaks, nsv, n_seg, b0, h->d_tw,
-                                   nbr ? h->d_nbr : nullptr);
+                hipLaunchKernelGGL(acq_nc_corr_kernel, dim3(nsv, nb), dim3(256), 0, h->stream, h->d_nc.p,
+                                   h->d_rep.p, h->d_slot.p, h->d_peaks.p, nsv, n_seg, b0, h->d_tw.p,
+                                   nbr ? h->d_nbr.p : nullptr);
         }
     }
     if (h->pfa)
         hipLaunchKernelGGL(acq_peaks_kernel, dim3(((int)cells + 255) / 256), dim3(256), 0, h->stream,
-                           h->d_stats, h->d_peaks, nbr ? h->d_nbr : nullptr, (int)cells);
+                           h->d_stats.p, h->d_peaks.p, nbr ? h->d_nbr.p : nullptr, (int)cells);
     GPSMI_HIP(hipGetLastError());
     GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
     rc = acq_copy_out(h, nbins, nsv, out, out_dev, nbr);
@@ -934,17 +869,10 @@ int gpsmi_acq_search_ex(gpsmi_acq* h, const float* iq, size_t n, const int32_t* 
     GPSMI_REQUIRE(n_avg >= 1 && n_avg <= h->cfg.n_cyc, "n_avg out of range 1..n_cyc");
     GPSMI_REQUIRE(n >= (size_t)n_avg * h->cfg.code_samples, "iq shorter than n_avg code periods");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    size_t need = (size_t)n_avg * h->cfg.code_samples;
-    if (need > h->iq_cap) {
-        if (h->d_iq) GPSMI_HIP(hipFree(h->d_iq));
-        h->d_iq = nullptr; h->iq_cap = 0;
-        GPSMI_HIP(hipMalloc((void**)&h->d_iq, need * sizeof(float2)));
-        h->iq_cap = need;
-    }
-    // (the staging buffer is sized for complex64; raw input uploads a quarter of it)
-    GPSMI_HIP(hipMemcpyAsync(h->d_iq, iq, need * (h->iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)),
-                             hipMemcpyHostToDevice, h->stream));
-    return acq_search_impl(h, h->d_iq, need, prn, nsv, freqs, nbins, n_avg, out, nullptr, nbr);
+    const size_t need = (size_t)n_avg * h->cfg.code_samples;
+    const int rc = acq_upload(h, iq, need);
+    if (rc) return rc;
+    return acq_search_impl(h, h->d_iq.p, need, prn, nsv, freqs, nbins, n_avg, out, nullptr, nbr);
 }
 
 int gpsmi_acq_search_nc_dev(gpsmi_acq* h, const void* d_iq, size_t n, const int32_t* prn, int nsv,
@@ -965,15 +893,9 @@ static int acq_search_nc_host(gpsmi_acq* h, const void* iq, size_t n, const int3
     if (deep && deep_span_check(n_seg, h->cfg.code_samples)) return GPSMI_E_UNSUPPORTED;   // (before the upload)
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     const size_t need = (size_t)n_seg * n_coh * h->cfg.code_samples;
-    if (need > h->iq_cap) {                  // (iq_cap counts complex64 samples)
-        size_t bytes = h->iq_cap * sizeof(float2);
-        const int rc = nc_grow((void**)&h->d_iq, &bytes, need * sizeof(float2));
-        h->iq_cap = h->d_iq ? need : 0;
-        if (rc) return rc;
-    }
-    GPSMI_HIP(hipMemcpyAsync(h->d_iq, iq, need * (h->iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)),
-                             hipMemcpyHostToDevice, h->stream));
-    return acq_search_nc_impl(h, h->d_iq, need, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, nullptr, nbr,
+    const int rc = acq_upload(h, iq, need);
+    if (rc) return rc;
+    return acq_search_nc_impl(h, h->d_iq.p, need, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, nullptr, nbr,
                               deep);
 }
 
@@ -1014,32 +936,22 @@ static int acq_refine_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n,
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     const void* d_iq = iq;
     if (on_host) {                           // only what the windows read is uploaded
-        if (pl.hi > h->iq_cap) {             // (iq_cap counts complex64 samples)
-            size_t bytes = h->iq_cap * sizeof(float2);
-            rc = nc_grow((void**)&h->d_iq, &bytes, pl.hi * sizeof(float2));
-            h->iq_cap = h->d_iq ? pl.hi : 0;
-            if (rc) return rc;
-        }
-        GPSMI_HIP(hipMemcpyAsync(h->d_iq, iq, pl.hi * (h->iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)),
-                                 hipMemcpyHostToDevice, h->stream));
-        d_iq = h->d_iq;
+        if ((rc = acq_upload(h, iq, pl.hi))) return rc;
+        d_iq = h->d_iq.p;
     }
     // the tables of the call, 8-byte items first
     const size_t b_start = pl.start.size() * sizeof(long long), b_inc = (size_t)n_df * sizeof(unsigned long long),
                  b_df = (size_t)n_df * sizeof(double), b_hit = (size_t)nhits * sizeof(RefHit);
     const size_t np = (size_t)nhits * 3 * n_ms, nm = (size_t)nhits * n_df * kRefEdges;
-    if ((rc = nc_grow((void**)&h->d_rt, &h->rt_cap, b_start + b_inc + b_df + b_hit)) ||
-        (rc = nc_grow((void**)&h->d_rp, &h->rp_cap, np * sizeof(float2))) ||
-        (rc = nc_grow((void**)&h->d_rm, &h->rm_cap, nm * sizeof(float))))
+    if ((rc = h->d_rt.reserve(b_start + b_inc + b_df + b_hit, "gpsmi_acq_refine tables")) ||
+        (rc = h->d_rp.reserve(np, "gpsmi_acq_refine prompts")) ||
+        (rc = h->d_rm.reserve(nm, "gpsmi_acq_refine grid")) ||
+        (rc = h->d_ro.reserve(kRefMaxHits, "gpsmi_acq_refine records")))
         return rc;
-    if (!h->d_ro) {
-        size_t cap = 0;
-        if ((rc = nc_grow((void**)&h->d_ro, &cap, kRefMaxHits * sizeof(gpsmi_refine_out)))) return rc;
-    }
-    long long* d_start = reinterpret_cast<long long*>(h->d_rt);
-    unsigned long long* d_inc = reinterpret_cast<unsigned long long*>(h->d_rt + b_start);
-    double* d_df = reinterpret_cast<double*>(h->d_rt + b_start + b_inc);
-    RefHit* d_hit = reinterpret_cast<RefHit*>(h->d_rt + b_start + b_inc + b_df);
+    long long* d_start = reinterpret_cast<long long*>(h->d_rt.p);
+    unsigned long long* d_inc = reinterpret_cast<unsigned long long*>(h->d_rt.p + b_start);
+    double* d_df = reinterpret_cast<double*>(h->d_rt.p + b_start + b_inc);
+    RefHit* d_hit = reinterpret_cast<RefHit*>(h->d_rt.p + b_start + b_inc + b_df);
     GPSMI_HIP(hipMemcpyAsync(d_start, pl.start.data(), b_start, hipMemcpyHostToDevice, h->stream));
     GPSMI_HIP(hipMemcpyAsync(d_inc, pl.dfinc.data(), b_inc, hipMemcpyHostToDevice, h->stream));
     GPSMI_HIP(hipMemcpyAsync(d_df, pl.dfs.data(), b_df, hipMemcpyHostToDevice, h->stream));
@@ -1053,24 +965,22 @@ static int acq_refine_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
     GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
     const dim3 gp((n_ms + kRefMsPerWg - 1) / kRefMsPerWg, nhits);
-    if (u8)
-        hipLaunchKernelGGL(refine_prompt_kernel<1>, gp, dim3(256), lds_p, h->stream, d_iq, h->d_rep_time, d_hit,
-                           d_start, cs, pl.tap, n_ms, h->d_rp);
-    else
-        hipLaunchKernelGGL(refine_prompt_kernel<0>, gp, dim3(256), lds_p, h->stream, d_iq, h->d_rep_time, d_hit,
-                           d_start, cs, pl.tap, n_ms, h->d_rp);
-    hipLaunchKernelGGL(refine_grid_kernel, dim3((n_df + 3) / 4, nhits), dim3(256), lds_g, h->stream, h->d_rp,
-                       d_inc, n_df, n_ms, h->d_rm);
-    hipLaunchKernelGGL(refine_final_kernel, dim3(nhits), dim3(256), 0, h->stream, h->d_rp, h->d_rm, d_inc, d_df,
-                       d_hit, n_df, n_ms, pl.tap, pl.step, pl.min_ratio, h->d_ro);
+    with_fmt(h->iq_fmt, [&](auto fmt) {
+        hipLaunchKernelGGL(refine_prompt_kernel<decltype(fmt)::value>, gp, dim3(256), lds_p, h->stream, d_iq,
+                           h->d_rep_time.p, d_hit, d_start, cs, pl.tap, n_ms, h->d_rp.p);
+    });
+    hipLaunchKernelGGL(refine_grid_kernel, dim3((n_df + 3) / 4, nhits), dim3(256), lds_g, h->stream, h->d_rp.p,
+                       d_inc, n_df, n_ms, h->d_rm.p);
+    hipLaunchKernelGGL(refine_final_kernel, dim3(nhits), dim3(256), 0, h->stream, h->d_rp.p, h->d_rm.p, d_inc, d_df,
+                       d_hit, n_df, n_ms, pl.tap, pl.step, pl.min_ratio, h->d_ro.p);
     GPSMI_HIP(hipGetLastError());
     GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
-    GPSMI_HIP(hipMemcpyAsync(out, h->d_ro, (size_t)nhits * sizeof(gpsmi_refine_out), hipMemcpyDeviceToHost,
+    GPSMI_HIP(hipMemcpyAsync(out, h->d_ro.p, (size_t)nhits * sizeof(gpsmi_refine_out), hipMemcpyDeviceToHost,
                              h->stream));
     if (grid)
-        GPSMI_HIP(hipMemcpyAsync(grid, h->d_rm, nm * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        GPSMI_HIP(hipMemcpyAsync(grid, h->d_rm.p, nm * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (prompts)
-        GPSMI_HIP(hipMemcpyAsync(prompts, h->d_rp, np * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+        GPSMI_HIP(hipMemcpyAsync(prompts, h->d_rp.p, np * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
     h->pending = true;
     return gpsmi_acq_wait(h);
 }
@@ -1109,40 +1019,30 @@ static int acq_track_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n, 
     const bool u8 = h->iq_fmt == GPSMI_IQ_U8;
     const void* d_iq = iq;
     if (on_host) {
-        if (n > h->iq_cap) {                 // (iq_cap counts complex64 samples)
-            size_t bytes = h->iq_cap * sizeof(float2);
-            rc = nc_grow((void**)&h->d_iq, &bytes, n * sizeof(float2));
-            h->iq_cap = h->d_iq ? n : 0;
-            if (rc) return rc;
-        }
-        GPSMI_HIP(hipMemcpyAsync(h->d_iq, iq, n * (u8 ? 2 : sizeof(float2)), hipMemcpyHostToDevice, h->stream));
-        d_iq = h->d_iq;
+        if ((rc = acq_upload(h, iq, n))) return rc;
+        d_iq = h->d_iq.p;
     }
     const size_t nb = (size_t)nhits * par.n_bits * sizeof(gpsmi_wtrk_bit);
-    if ((rc = nc_grow((void**)&h->d_wb, &h->wb_cap, nb))) return rc;
-    if (!h->d_ws) {
-        size_t cap = 0;
-        if ((rc = nc_grow((void**)&h->d_ws, &cap, kWtrkMaxHits * sizeof(gpsmi_wtrk_state)))) return rc;
-    }
-    GPSMI_HIP(hipMemcpyAsync(h->d_ws, states, (size_t)nhits * sizeof(gpsmi_wtrk_state), hipMemcpyHostToDevice,
+    if ((rc = h->d_wb.reserve((size_t)nhits * par.n_bits, "gpsmi_acq_track bit records")) ||
+        (rc = h->d_ws.reserve(kWtrkMaxHits, "gpsmi_acq_track states")))
+        return rc;
+    GPSMI_HIP(hipMemcpyAsync(h->d_ws.p, states, (size_t)nhits * sizeof(gpsmi_wtrk_state), hipMemcpyHostToDevice,
                              h->stream));
-    GPSMI_HIP(hipMemsetAsync(h->d_wb, 0, nb, h->stream));
+    GPSMI_HIP(hipMemsetAsync(h->d_wb.p, 0, nb, h->stream));
     const size_t lds = wtrk_lds_bytes(par.cs);
     if (lds > 64 * 1024)
         GPSMI_HIP(hipFuncSetAttribute(u8 ? (const void*)wtrk_kernel<1> : (const void*)wtrk_kernel<0>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
-    if (u8)
-        hipLaunchKernelGGL(wtrk_kernel<1>, dim3(nhits), dim3(256), lds, h->stream, d_iq, h->d_rep_time, par,
-                           h->d_ws, h->d_wb);
-    else
-        hipLaunchKernelGGL(wtrk_kernel<0>, dim3(nhits), dim3(256), lds, h->stream, d_iq, h->d_rep_time, par,
-                           h->d_ws, h->d_wb);
+    with_fmt(h->iq_fmt, [&](auto fmt) {
+        hipLaunchKernelGGL(wtrk_kernel<decltype(fmt)::value>, dim3(nhits), dim3(256), lds, h->stream, d_iq,
+                           h->d_rep_time.p, par, h->d_ws.p, h->d_wb.p);
+    });
     GPSMI_HIP(hipGetLastError());
     GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
-    GPSMI_HIP(hipMemcpyAsync(states, h->d_ws, (size_t)nhits * sizeof(gpsmi_wtrk_state), hipMemcpyDeviceToHost,
+    GPSMI_HIP(hipMemcpyAsync(states, h->d_ws.p, (size_t)nhits * sizeof(gpsmi_wtrk_state), hipMemcpyDeviceToHost,
                              h->stream));
-    GPSMI_HIP(hipMemcpyAsync(bits, h->d_wb, nb, hipMemcpyDeviceToHost, h->stream));
+    GPSMI_HIP(hipMemcpyAsync(bits, h->d_wb.p, nb, hipMemcpyDeviceToHost, h->stream));
     h->pending = true;
     return gpsmi_acq_wait(h);
 }

@@ -4,6 +4,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gpsmi.h"
@@ -45,6 +46,21 @@ void make_twiddles(std::vector<float2>& tw);
 struct HandleSync { hipStream_t stream; hipEvent_t order; int device; hipEvent_t tail; };
 
 inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+
+// A run-time value as a template argument: f(std::integral_constant<int, V>{}) for the V of the list
+// that equals v, the LAST of the list when none does.  f is a generic lambda that holds one launch,
+// written once: `[&](auto nc) { constexpr int NC = decltype(nc)::value; ...kernel<NC>... }`.  Only the
+// listed values are instantiated.
+template <int V, int... Rest, typename F>
+inline void with_value(int v, F&& f) {
+    if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, V>{});
+    else if (v == V) f(std::integral_constant<int, V>{});
+    else with_value<Rest...>(v, f);
+}
+// the FMT template argument of a kernel that reads the input block (load_iq below) from a handle's
+// input format: 1 for GPSMI_IQ_U8, else 0
+template <typename F>
+inline void with_fmt(int iq_fmt, F&& f) { with_value<1, 0>(iq_fmt == GPSMI_IQ_U8 ? 1 : 0, f); }
 
 // Single float32 operations that are never fused into a multiply-add, for code that
 // restates the reference's numpy float32 arithmetic step by step.  (HIP's

@@ -1,0 +1,80 @@
+// DevBuf<T>: the one owner of a device allocation in libgpsmi ("How a handle owns
+// memory").  Every device buffer of a handle is a DevBuf member: it is released when the handle is
+// deleted, and its capacity travels with it, in elements of T.
+#pragma once
+#include "gpsmi_common.h"
+
+namespace gpsmi {
+
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;                        // capacity in elements of T
+
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+        return *this;
+    }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+
+    // Room for `count` elements: nothing when there is, else the old block is freed and exactly
+    // `count` allocated (the contents are not kept).  A failure leaves the buffer empty and the
+    // handle usable: GPSMI_E_NOMEM when the device cannot serve the request, `what` names the
+    // buffer in the error text.
+    int reserve(size_t count, const char* what) {
+        if (count <= n) return GPSMI_OK;
+        if (p) GPSMI_HIP(hipFree(p));
+        p = nullptr; n = 0;
+        const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+        if (e != hipSuccess) {
+            p = nullptr;
+            if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
+                (void)hipGetLastError();     // (the error is sticky: the next GPSMI_HIP would see it)
+                return fail(GPSMI_E_NOMEM, "%s: no device memory for %zu bytes", what, count * sizeof(T));
+            }
+            return fail(GPSMI_E_HIP, "hipMalloc: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+        }
+        n = count;
+        return GPSMI_OK;
+    }
+
+    // reserve, then all bytes zero (a blocking memset, at create time)
+    int reserve_zeroed(size_t count, const char* what) {
+        const int rc = reserve(count, what);
+        if (rc) return rc;
+        GPSMI_HIP(hipMemset(p, 0, count * sizeof(T)));
+        return GPSMI_OK;
+    }
+
+    // reserve, then a blocking copy of a host table (at create time)
+    int upload(const std::vector<T>& v, const char* what) {
+        const int rc = reserve(v.size(), what);
+        if (rc) return rc;
+        GPSMI_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        return GPSMI_OK;
+    }
+
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr; n = 0;
+    }
+};
+
+// Device copies of the input and the output of a host entry point that works block by block
+// (gpsmi_pb_apply, gpsmi_ifx_apply): room for both, then the input on its way up on `stream`.
+struct StagedIO {
+    DevBuf<char> in, out;
+    int upload(const void* src, size_t in_bytes, size_t out_bytes, hipStream_t stream, const char* what) {
+        int rc = in.reserve(in_bytes, what);
+        if (!rc) rc = out.reserve(out_bytes, what);
+        if (rc) return rc;
+        GPSMI_HIP(hipMemcpyAsync(in.p, src, in_bytes, hipMemcpyHostToDevice, stream));
+        return GPSMI_OK;
+    }
+};
+
+}  // namespace gpsmi

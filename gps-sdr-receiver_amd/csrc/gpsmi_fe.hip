@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "gpsmi_common.h"
+#include "gpsmi_devmem.h"
 
 namespace gpsmi {
 
@@ -266,11 +267,11 @@ struct gpsmi_fe {
     FePlan plan;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float* d_table = nullptr;
-    float2* d_carry = nullptr;                              // [kc]
-    float2* d_vbuf = nullptr; size_t vbuf_cap = 0;          // [kc + n_in] (bytes)
-    void* d_in = nullptr; size_t in_cap = 0;                // host entry: staged input (bytes)
-    float2* d_out = nullptr;                                // host entry: [max_out]
+    DevBuf<float> d_table;
+    DevBuf<float2> d_carry;                                 // [kc]
+    DevBuf<float2> d_vbuf;                                  // [kc + n_in]
+    DevBuf<char> d_in;                                      // host entry: staged input (bytes: five formats)
+    DevBuf<float2> d_out;                                   // host entry: [max_out], fixed at create
     long long taken = 0;                                    // input samples since create / reset
     long long emitted = 0;                                  // outputs since create / reset
     bool flushed = false;
@@ -287,24 +288,6 @@ static size_t fe_sample_bytes(int fmt) {
     }
 }
 
-static int fe_grow(void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return GPSMI_OK;
-    if (*p) GPSMI_HIP(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
-            (void)hipGetLastError();
-            return fail(GPSMI_E_NOMEM, "front-end scratch: %zu bytes not available", bytes);
-        }
-        return fail(GPSMI_E_HIP, "hipMalloc: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-    }
-    *cap = bytes;
-    return GPSMI_OK;
-}
-
 // outputs complete once `total` input samples are in: n with floor(n P / Q) + K / 2 <= total - 1
 static long long fe_complete(const FePlan& pl, long long total) {
     const long long M = total - 1 - pl.K / 2;
@@ -317,14 +300,14 @@ template <int FMT>
 static void fe_launch_stage(gpsmi_fe* h, const void* in, long long n_in) {
     const long long n = h->plan.kc + n_in;
     hipLaunchKernelGGL(fe_stage_kernel<FMT>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, in,
-                       h->d_carry, h->plan.kc, n_in, h->taken, h->plan.inc,
-                       (h->cfg.flags & GPSMI_FE_CONJUGATE) ? 1 : 0, h->d_vbuf);
+                       h->d_carry.p, h->plan.kc, n_in, h->taken, h->plan.inc,
+                       (h->cfg.flags & GPSMI_FE_CONJUGATE) ? 1 : 0, h->d_vbuf.p);
 }
 
 // One call: n_in samples at d_in (device, the handle's format; null: zeros) -> n_out outputs at d_out.
 static int fe_run(gpsmi_fe* h, const void* d_in, long long n_in, float2* d_out, long long n_out) {
     const FePlan& pl = h->plan;
-    int rc = fe_grow((void**)&h->d_vbuf, &h->vbuf_cap, (size_t)(pl.kc + n_in) * sizeof(float2));
+    int rc = h->d_vbuf.reserve((size_t)(pl.kc + n_in), "front-end sample scratch");
     if (rc) return rc;
     GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
     if (!d_in) fe_launch_stage<kFeZero>(h, nullptr, n_in);
@@ -340,10 +323,10 @@ static int fe_run(gpsmi_fe* h, const void* d_in, long long n_in, float2* d_out, 
         const long long I0 = (long long)(t0 / pl.Q), r0 = (long long)(t0 % pl.Q);
         const long long vbase = h->taken - pl.kc;
         const unsigned groups = (unsigned)((n_out + pl.R - 1) / pl.R);
-        hipLaunchKernelGGL(fe_filter_kernel, dim3(groups), dim3((unsigned)pl.R), pl.lds, h->stream, h->d_vbuf,
-                           vbase, I0, r0, pl.P, pl.Q, pl.K, pl.L, h->d_table, pl.tab_floats, pl.R, n_out, d_out);
+        hipLaunchKernelGGL(fe_filter_kernel, dim3(groups), dim3((unsigned)pl.R), pl.lds, h->stream, h->d_vbuf.p,
+                           vbase, I0, r0, pl.P, pl.Q, pl.K, pl.L, h->d_table.p, pl.tab_floats, pl.R, n_out, d_out);
     }
-    hipLaunchKernelGGL(fe_carry_kernel, dim3(1), dim3(256), 0, h->stream, h->d_vbuf, n_in, pl.kc, h->d_carry);
+    hipLaunchKernelGGL(fe_carry_kernel, dim3(1), dim3(256), 0, h->stream, h->d_vbuf.p, n_in, pl.kc, h->d_carry.p);
     GPSMI_HIP(hipGetLastError());
     GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
     return GPSMI_OK;
@@ -402,12 +385,10 @@ int gpsmi_fe_create(const gpsmi_fe_cfg* cfg, gpsmi_fe** out) {
         if (p.lds > kFeLdsBudget)
             GPSMI_HIP(hipFuncSetAttribute((const void*)fe_filter_kernel,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-        GPSMI_HIP(hipMalloc((void**)&h->d_table, p.table.size() * sizeof(float)));
-        GPSMI_HIP(hipMemcpy(h->d_table, p.table.data(), p.table.size() * sizeof(float), hipMemcpyHostToDevice));
-        GPSMI_HIP(hipMalloc((void**)&h->d_carry, (size_t)p.kc * sizeof(float2)));
-        GPSMI_HIP(hipMemset(h->d_carry, 0, (size_t)p.kc * sizeof(float2)));
-        GPSMI_HIP(hipMalloc((void**)&h->d_out, (size_t)h->cfg.max_out * sizeof(float2)));
-        return GPSMI_OK;
+        int rc = h->d_table.upload(p.table, "front-end filter table");
+        if (!rc) rc = h->d_carry.reserve_zeroed(p.kc, "front-end carry");
+        if (!rc) rc = h->d_out.reserve(h->cfg.max_out, "front-end output block");
+        return rc;
     }();
     if (rc) {
         (void)gpsmi_fe_destroy(h);
@@ -421,20 +402,17 @@ int gpsmi_fe_destroy(gpsmi_fe* h) {
     if (!h) return GPSMI_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* bufs[] = {h->d_table, h->d_carry, h->d_vbuf, h->d_in, h->d_out};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                                // (releases the device buffers)
     return GPSMI_OK;
 }
 
 int gpsmi_fe_reset(gpsmi_fe* h) {
     GPSMI_REQUIRE(h, "null handle");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    GPSMI_HIP(hipMemsetAsync(h->d_carry, 0, (size_t)h->plan.kc * sizeof(float2), h->stream));
+    GPSMI_HIP(hipMemsetAsync(h->d_carry.p, 0, (size_t)h->plan.kc * sizeof(float2), h->stream));
     GPSMI_HIP(hipStreamSynchronize(h->stream));
     h->taken = 0;
     h->emitted = 0;
@@ -472,13 +450,13 @@ int gpsmi_fe_push(gpsmi_fe* h, const void* in, size_t n_in, float* out, size_t m
     if (n_in == 0) return GPSMI_OK;
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     const size_t ib = n_in * fe_sample_bytes(h->cfg.format);
-    rc = fe_grow(&h->d_in, &h->in_cap, ib);
+    rc = h->d_in.reserve(ib, "front-end staging");
     if (rc) return rc;
-    GPSMI_HIP(hipMemcpyAsync(h->d_in, in, ib, hipMemcpyHostToDevice, h->stream));
-    rc = fe_run(h, h->d_in, (long long)n_in, h->d_out, n);
+    GPSMI_HIP(hipMemcpyAsync(h->d_in.p, in, ib, hipMemcpyHostToDevice, h->stream));
+    rc = fe_run(h, h->d_in.p, (long long)n_in, h->d_out.p, n);
     if (rc) return rc;
     if (n > 0)
-        GPSMI_HIP(hipMemcpyAsync(out, h->d_out, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+        GPSMI_HIP(hipMemcpyAsync(out, h->d_out.p, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
     rc = fe_finish(h, (long long)n_in, n);
     if (rc) return rc;
     *n_out = (size_t)n;
@@ -496,10 +474,10 @@ int gpsmi_fe_flush(gpsmi_fe* h, float* out, size_t max_out, size_t* n_out) {
         return fail(GPSMI_E_ARG, "gpsmi_fe_flush: emits %lld samples, the handle's max_out is %d", n,
                     (int)h->cfg.max_out);
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    rc = fe_run(h, nullptr, pad, h->d_out, n);
+    rc = fe_run(h, nullptr, pad, h->d_out.p, n);
     if (rc) return rc;
     if (n > 0)
-        GPSMI_HIP(hipMemcpyAsync(out, h->d_out, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+        GPSMI_HIP(hipMemcpyAsync(out, h->d_out.p, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
     rc = fe_finish(h, pad, n);
     if (rc) return rc;
     h->flushed = true;

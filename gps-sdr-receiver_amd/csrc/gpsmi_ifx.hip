@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "gpsmi_common.h"
+#include "gpsmi_devmem.h"
 #include "gpsmi_fft.h"
 
 namespace gpsmi {
@@ -226,35 +227,17 @@ struct gpsmi_ifx {
     gpsmi_ifx_cfg cfg;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float2* d_tw = nullptr;
-    float* d_win = nullptr;                  // periodic Hann, float32 of the double value
-    float2* d_carry = nullptr;               // [H] complex64
-    float* d_partial = nullptr; size_t partial_cap = 0;     // [nb][groups][2048]
-    int32_t* d_counts = nullptr; uint32_t* d_masks = nullptr; size_t res_cap = 0;   // blocks
-    void* d_in = nullptr; size_t in_cap = 0;                // host entry: staged input (bytes)
-    void* d_out = nullptr; size_t out_cap = 0;              //             and output (bytes)
+    DevBuf<float2> d_tw;
+    DevBuf<float> d_win;                     // periodic Hann, float32 of the double value
+    DevBuf<float2> d_carry;                  // [H] complex64
+    DevBuf<float> d_partial;                 // [nb][groups][2048]
+    DevBuf<int32_t> d_counts;                // [nb]
+    DevBuf<uint32_t> d_masks;                // [nb][kMaskWords]
+    StagedIO io;                             // host entry: staged input and output
     int fmt = GPSMI_IQ_C64;
     float scale = 0.f;                       // 10^(thresh_db / 10) as float32
     float last_ms = 0.f;
 };
-
-static int ifx_grow(void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return GPSMI_OK;
-    if (*p) GPSMI_HIP(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
-            (void)hipGetLastError();
-            return fail(GPSMI_E_NOMEM, "excision scratch: %zu bytes not available", bytes);
-        }
-        return fail(GPSMI_E_HIP, "hipMalloc: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-    }
-    *cap = bytes;
-    return GPSMI_OK;
-}
 
 static bool ifx_block_ok(int32_t n) { return n >= 4 * kIfxH && n <= (1 << 24) && n % kIfxH == 0; }
 
@@ -264,17 +247,15 @@ static int ifx_build(gpsmi_ifx* h) {
     GPSMI_HIP(hipEventCreate(&h->ev1));
     std::vector<float2> tw;
     make_twiddles(tw);
-    GPSMI_HIP(hipMalloc((void**)&h->d_tw, tw.size() * sizeof(float2)));
-    GPSMI_HIP(hipMemcpy(h->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
+    int rc = h->d_tw.upload(tw, "excision twiddles");
+    if (rc) return rc;
     std::vector<float> win(kIfxL);
     for (int i = 0; i < kIfxL; ++i) {
         const double s = sin(M_PI * (double)i / (double)kIfxL);
         win[i] = (float)(s * s);
     }
-    GPSMI_HIP(hipMalloc((void**)&h->d_win, kIfxL * sizeof(float)));
-    GPSMI_HIP(hipMemcpy(h->d_win, win.data(), kIfxL * sizeof(float), hipMemcpyHostToDevice));
-    GPSMI_HIP(hipMalloc((void**)&h->d_carry, kIfxH * sizeof(float2)));
-    GPSMI_HIP(hipMemset(h->d_carry, 0, kIfxH * sizeof(float2)));
+    if ((rc = h->d_win.upload(win, "excision window")) || (rc = h->d_carry.reserve_zeroed(kIfxH, "excision carry")))
+        return rc;
     h->scale = (float)pow(10.0, (double)h->cfg.thresh_db / 10.0);
     return GPSMI_OK;
 }
@@ -283,43 +264,28 @@ static int ifx_build(gpsmi_ifx* h) {
 static int ifx_run(gpsmi_ifx* h, const void* d_iq, void* d_out, int nb) {
     const int n = h->cfg.block_samples, nf = n / kIfxH;
     const int groups = (nf - 1 + kPsdGroup - 1) / kPsdGroup;
-    int rc = ifx_grow((void**)&h->d_partial, &h->partial_cap, (size_t)nb * groups * kIfxL * sizeof(float));
+    int rc = h->d_partial.reserve((size_t)nb * groups * kIfxL, "excision spectra");
+    if (!rc) rc = h->d_counts.reserve(nb, "excision results");
+    if (!rc) rc = h->d_masks.reserve((size_t)nb * kMaskWords, "excision results");
     if (rc) return rc;
-    if ((size_t)nb > h->res_cap) {
-        if (h->d_counts) GPSMI_HIP(hipFree(h->d_counts));
-        if (h->d_masks) GPSMI_HIP(hipFree(h->d_masks));
-        h->d_counts = nullptr; h->d_masks = nullptr; h->res_cap = 0;
-        GPSMI_HIP(hipMalloc((void**)&h->d_counts, (size_t)nb * sizeof(int32_t)));
-        GPSMI_HIP(hipMalloc((void**)&h->d_masks, (size_t)nb * kMaskWords * sizeof(uint32_t)));
-        h->res_cap = nb;
-    }
     // segments per apply workgroup: one frame transform pair per segment plus one per workgroup;
     // runs of up to 8 segments once the grid has some 2048 workgroups anyway (same bits either way)
     const long long segs = (long long)nb * nf;
     const int S = segs >= 16384 ? 8 : segs >= 8192 ? 4 : segs >= 4096 ? 2 : 1;
     const int runs = (nf + S - 1) / S;
-    const bool u8 = h->fmt == GPSMI_IQ_U8;
-    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
-    if (u8)
-        hipLaunchKernelGGL(ifx_psd_kernel<1>, dim3((unsigned)(nb * groups)), dim3(256), 0, h->stream, d_iq,
-                           h->d_carry, h->d_win, n, groups, h->d_partial, h->d_tw);
-    else
-        hipLaunchKernelGGL(ifx_psd_kernel<0>, dim3((unsigned)(nb * groups)), dim3(256), 0, h->stream, d_iq,
-                           h->d_carry, h->d_win, n, groups, h->d_partial, h->d_tw);
-    hipLaunchKernelGGL(ifx_mask_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, h->d_partial, groups,
-                       nf - 1, h->scale, h->cfg.dilate, h->cfg.max_bins, h->d_counts, h->d_masks);
     const size_t tail = (size_t)nb * n - kIfxH;
-    if (u8) {
-        hipLaunchKernelGGL(ifx_apply_kernel<1>, dim3((unsigned)(nb * runs)), dim3(256), 0, h->stream, d_iq,
-                           h->d_carry, h->d_win, n, runs, S, h->d_counts, h->d_masks, (float2*)d_out,
-                           h->d_tw);
-        hipLaunchKernelGGL(ifx_carry_kernel<1>, dim3(1), dim3(256), 0, h->stream, d_iq, tail, h->d_carry);
-    } else {
-        hipLaunchKernelGGL(ifx_apply_kernel<0>, dim3((unsigned)(nb * runs)), dim3(256), 0, h->stream, d_iq,
-                           h->d_carry, h->d_win, n, runs, S, h->d_counts, h->d_masks, (float2*)d_out,
-                           h->d_tw);
-        hipLaunchKernelGGL(ifx_carry_kernel<0>, dim3(1), dim3(256), 0, h->stream, d_iq, tail, h->d_carry);
-    }
+    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
+    with_fmt(h->fmt, [&](auto fmt) {
+        constexpr int FMT = decltype(fmt)::value;
+        hipLaunchKernelGGL(ifx_psd_kernel<FMT>, dim3((unsigned)(nb * groups)), dim3(256), 0, h->stream, d_iq,
+                           h->d_carry.p, h->d_win.p, n, groups, h->d_partial.p, h->d_tw.p);
+        hipLaunchKernelGGL(ifx_mask_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, h->d_partial.p, groups,
+                           nf - 1, h->scale, h->cfg.dilate, h->cfg.max_bins, h->d_counts.p, h->d_masks.p);
+        hipLaunchKernelGGL(ifx_apply_kernel<FMT>, dim3((unsigned)(nb * runs)), dim3(256), 0, h->stream, d_iq,
+                           h->d_carry.p, h->d_win.p, n, runs, S, h->d_counts.p, h->d_masks.p, (float2*)d_out,
+                           h->d_tw.p);
+        hipLaunchKernelGGL(ifx_carry_kernel<FMT>, dim3(1), dim3(256), 0, h->stream, d_iq, tail, h->d_carry.p);
+    });
     GPSMI_HIP(hipGetLastError());
     GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
     return GPSMI_OK;
@@ -327,10 +293,10 @@ static int ifx_run(gpsmi_ifx* h, const void* d_iq, void* d_out, int nb) {
 
 static int ifx_finish(gpsmi_ifx* h, int nb, int32_t* counts, uint32_t* masks) {
     if (counts)
-        GPSMI_HIP(hipMemcpyAsync(counts, h->d_counts, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost,
+        GPSMI_HIP(hipMemcpyAsync(counts, h->d_counts.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost,
                                  h->stream));
     if (masks)
-        GPSMI_HIP(hipMemcpyAsync(masks, h->d_masks, (size_t)nb * kMaskWords * sizeof(uint32_t),
+        GPSMI_HIP(hipMemcpyAsync(masks, h->d_masks.p, (size_t)nb * kMaskWords * sizeof(uint32_t),
                                  hipMemcpyDeviceToHost, h->stream));
     GPSMI_HIP(hipStreamSynchronize(h->stream));
     GPSMI_HIP(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
@@ -372,13 +338,10 @@ int gpsmi_ifx_destroy(gpsmi_ifx* h) {
     if (!h) return GPSMI_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* bufs[] = {h->d_tw, h->d_win, h->d_carry, h->d_partial, h->d_counts, h->d_masks, h->d_in, h->d_out};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                                // (releases the device buffers)
     return GPSMI_OK;
 }
 
@@ -394,7 +357,7 @@ int gpsmi_ifx_set_input_format(gpsmi_ifx* h, int fmt) {
 int gpsmi_ifx_reset(gpsmi_ifx* h) {
     GPSMI_REQUIRE(h, "null handle");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    GPSMI_HIP(hipMemsetAsync(h->d_carry, 0, kIfxH * sizeof(float2), h->stream));
+    GPSMI_HIP(hipMemsetAsync(h->d_carry.p, 0, kIfxH * sizeof(float2), h->stream));
     GPSMI_HIP(hipStreamSynchronize(h->stream));
     return GPSMI_OK;
 }
@@ -422,14 +385,11 @@ int gpsmi_ifx_apply(gpsmi_ifx* h, const void* iq, float* out, int nb, int32_t* c
                   "nb out of range: 1 .. 2^31 samples per call");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     const size_t ib = ifx_in_bytes(h, nb), ob = (size_t)nb * h->cfg.block_samples * sizeof(float2);
-    int rc = ifx_grow(&h->d_in, &h->in_cap, ib);
+    int rc = h->io.upload(iq, ib, ob, h->stream, "excision staging");
     if (rc) return rc;
-    rc = ifx_grow(&h->d_out, &h->out_cap, ob);
+    rc = ifx_run(h, h->io.in.p, h->io.out.p, nb);
     if (rc) return rc;
-    GPSMI_HIP(hipMemcpyAsync(h->d_in, iq, ib, hipMemcpyHostToDevice, h->stream));
-    rc = ifx_run(h, h->d_in, h->d_out, nb);
-    if (rc) return rc;
-    GPSMI_HIP(hipMemcpyAsync(out, h->d_out, ob, hipMemcpyDeviceToHost, h->stream));
+    GPSMI_HIP(hipMemcpyAsync(out, h->io.out.p, ob, hipMemcpyDeviceToHost, h->stream));
     return ifx_finish(h, nb, counts, masks);
 }
 

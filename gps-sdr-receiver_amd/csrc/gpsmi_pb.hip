@@ -39,6 +39,7 @@
 #include <new>
 
 #include "gpsmi_common.h"
+#include "gpsmi_devmem.h"
 
 namespace gpsmi {
 
@@ -311,38 +312,19 @@ struct gpsmi_pb {
     gpsmi_pb_cfg cfg;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int* d_state = nullptr;                               // the carry into the next call's block 0
-    uint32_t* d_hist = nullptr; size_t hist_cap = 0;      // [chunk blocks][slices][2048]
-    uint2* d_sel = nullptr; float* d_floors = nullptr; float* d_thr = nullptr;
-    int* d_carries = nullptr; int32_t* d_counts = nullptr; size_t res_cap = 0;   // blocks
-    int* d_scount = nullptr; size_t scount_cap = 0;       // bytes
-    uint32_t* d_masks = nullptr; size_t masks_cap = 0;    // bytes
-    void* d_in = nullptr; size_t in_cap = 0;              // host entry: staged input (bytes)
-    void* d_out = nullptr; size_t out_cap = 0;            //             and output (bytes)
+    DevBuf<int> d_state;                                  // the carry into the next call's block 0
+    DevBuf<uint32_t> d_hist;                              // [chunk blocks][slices][2048]
+    DevBuf<uint2> d_sel; DevBuf<float> d_floors, d_thr;   // [blocks]
+    DevBuf<int> d_carries; DevBuf<int32_t> d_counts;      // [blocks + 1], [blocks]
+    DevBuf<int> d_scount;                                 // [blocks][slices]
+    DevBuf<uint32_t> d_masks;                             // [blocks][n / 32]
+    StagedIO io;                                          // host entry: staged input and output
     int fmt = GPSMI_IQ_C64;
     float f = 0.f;                                        // 10^(thresh_db / 10) as float32
     int limit = 0;                                        // floor(max_frac * n)
     size_t chunk_bytes = 0;                               // input bytes per chunk (0: one chunk)
     float last_ms = 0.f;
 };
-
-static int pb_grow(void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return GPSMI_OK;
-    if (*p) GPSMI_HIP(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
-            (void)hipGetLastError();
-            return fail(GPSMI_E_NOMEM, "pulse blanking scratch: %zu bytes not available", bytes);
-        }
-        return fail(GPSMI_E_HIP, "hipMalloc: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-    }
-    *cap = bytes;
-    return GPSMI_OK;
-}
 
 static size_t pb_in_bytes(const gpsmi_pb* h, int nb) {
     return (size_t)nb * h->cfg.block_samples * (h->fmt == GPSMI_IQ_U8 ? sizeof(uint16_t) : sizeof(float2));
@@ -352,8 +334,8 @@ static int pb_build(gpsmi_pb* h) {
     GPSMI_HIP(hipStreamCreate(&h->stream));
     GPSMI_HIP(hipEventCreate(&h->ev0));
     GPSMI_HIP(hipEventCreate(&h->ev1));
-    GPSMI_HIP(hipMalloc((void**)&h->d_state, sizeof(int)));
-    GPSMI_HIP(hipMemset(h->d_state, 0, sizeof(int)));
+    const int rc = h->d_state.reserve_zeroed(1, "pulse blanking carry");
+    if (rc) return rc;
     h->f = (float)pow(10.0, (double)h->cfg.thresh_db / 10.0);
     h->limit = (int)floor((double)h->cfg.max_frac * (double)h->cfg.block_samples);
     if (const char* e = getenv("GPSMI_PB_CHUNK_MIB")) h->chunk_bytes = (size_t)strtoull(e, nullptr, 10) << 20;
@@ -362,19 +344,11 @@ static int pb_build(gpsmi_pb* h) {
 
 // per-block result arrays for nb blocks (the carries: nb + 1)
 static int pb_results(gpsmi_pb* h, int nb) {
-    if ((size_t)nb <= h->res_cap) return GPSMI_OK;
-    void* bufs[] = {h->d_sel, h->d_floors, h->d_thr, h->d_carries, h->d_counts};
-    for (void* p : bufs)
-        if (p) GPSMI_HIP(hipFree(p));
-    h->d_sel = nullptr; h->d_floors = nullptr; h->d_thr = nullptr; h->d_carries = nullptr; h->d_counts = nullptr;
-    h->res_cap = 0;
-    size_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;
-    int rc = pb_grow((void**)&h->d_sel, &c0, (size_t)nb * sizeof(uint2));
-    if (!rc) rc = pb_grow((void**)&h->d_floors, &c1, (size_t)nb * sizeof(float));
-    if (!rc) rc = pb_grow((void**)&h->d_thr, &c2, (size_t)nb * sizeof(float));
-    if (!rc) rc = pb_grow((void**)&h->d_carries, &c3, (size_t)(nb + 1) * sizeof(int));
-    if (!rc) rc = pb_grow((void**)&h->d_counts, &c4, (size_t)nb * sizeof(int32_t));
-    if (!rc) h->res_cap = nb;
+    int rc = h->d_sel.reserve(nb, "pulse blanking results");
+    if (!rc) rc = h->d_floors.reserve(nb, "pulse blanking results");
+    if (!rc) rc = h->d_thr.reserve(nb, "pulse blanking results");
+    if (!rc) rc = h->d_carries.reserve((size_t)nb + 1, "pulse blanking results");
+    if (!rc) rc = h->d_counts.reserve(nb, "pulse blanking results");
     return rc;
 }
 
@@ -388,45 +362,39 @@ static int pb_run(gpsmi_pb* h, const void* d_iq, void* d_out, int nb, bool want_
     int cb = h->chunk_bytes ? (int)std::max<size_t>(1, h->chunk_bytes / blk_bytes) : nb;
     cb = std::min(cb, nb);
     int rc = pb_results(h, nb);
-    if (!rc) rc = pb_grow((void**)&h->d_hist, &h->hist_cap, (size_t)cb * ns * 2048 * sizeof(uint32_t));
-    if (!rc) rc = pb_grow((void**)&h->d_scount, &h->scount_cap, (size_t)nb * ns * sizeof(int));
-    if (!rc && want_masks) rc = pb_grow((void**)&h->d_masks, &h->masks_cap, (size_t)nb * (n / 32) * sizeof(uint32_t));
+    if (!rc) rc = h->d_hist.reserve((size_t)cb * ns * 2048, "pulse blanking histograms");
+    if (!rc) rc = h->d_scount.reserve((size_t)nb * ns, "pulse blanking slice counts");
+    if (!rc && want_masks) rc = h->d_masks.reserve((size_t)nb * (n / 32), "pulse blanking masks");
     if (rc) return rc;
-    uint32_t* masks = want_masks ? h->d_masks : nullptr;
+    uint32_t* masks = want_masks ? h->d_masks.p : nullptr;
     float2* out = static_cast<float2*>(d_out);
     const int pre = h->cfg.pre, post = h->cfg.post;
     GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
     for (int b0 = 0; b0 < nb; b0 += cb) {
         const int m = std::min(cb, nb - b0);
         const dim3 g((unsigned)(m * ns)), gb((unsigned)m), blk(256);
-#define PB_CHUNK(FMT)                                                                                      \
-    hipLaunchKernelGGL((pb_hist_kernel<FMT, 0>), g, blk, 0, h->stream, d_iq, n, ns, S, b0, h->d_sel,        \
-                       h->d_hist);                                                                         \
-    hipLaunchKernelGGL((pb_select_kernel<FMT, 0>), gb, blk, 0, h->stream, h->d_hist, ns, n, b0, h->d_sel,   \
-                       h->f, d_iq, post, h->d_floors, h->d_thr, h->d_carries);                             \
-    hipLaunchKernelGGL((pb_hist_kernel<FMT, 1>), g, blk, 0, h->stream, d_iq, n, ns, S, b0, h->d_sel,        \
-                       h->d_hist);                                                                         \
-    hipLaunchKernelGGL((pb_select_kernel<FMT, 1>), gb, blk, 0, h->stream, h->d_hist, ns, n, b0, h->d_sel,   \
-                       h->f, d_iq, post, h->d_floors, h->d_thr, h->d_carries);                             \
-    hipLaunchKernelGGL((pb_hist_kernel<FMT, 2>), g, blk, 0, h->stream, d_iq, n, ns, S, b0, h->d_sel,        \
-                       h->d_hist);                                                                         \
-    hipLaunchKernelGGL((pb_select_kernel<FMT, 2>), gb, blk, 0, h->stream, h->d_hist, ns, n, b0, h->d_sel,   \
-                       h->f, d_iq, post, h->d_floors, h->d_thr, h->d_carries);                             \
-    hipLaunchKernelGGL((pb_apply_kernel<FMT>), g, blk, 0, h->stream, d_iq, n, ns, S, b0, pre, post,         \
-                       h->d_thr, h->d_carries, h->d_state, out, masks, h->d_scount)
-        if (h->fmt == GPSMI_IQ_U8) {
-            PB_CHUNK(1);
-        } else {
-            PB_CHUNK(0);
-        }
-#undef PB_CHUNK
+        with_fmt(h->fmt, [&](auto fmt) {
+            constexpr int FMT = decltype(fmt)::value;
+            hipLaunchKernelGGL((pb_hist_kernel<FMT, 0>), g, blk, 0, h->stream, d_iq, n, ns, S, b0, h->d_sel.p,
+                               h->d_hist.p);
+            hipLaunchKernelGGL((pb_select_kernel<FMT, 0>), gb, blk, 0, h->stream, h->d_hist.p, ns, n, b0, h->d_sel.p,
+                               h->f, d_iq, post, h->d_floors.p, h->d_thr.p, h->d_carries.p);
+            hipLaunchKernelGGL((pb_hist_kernel<FMT, 1>), g, blk, 0, h->stream, d_iq, n, ns, S, b0, h->d_sel.p,
+                               h->d_hist.p);
+            hipLaunchKernelGGL((pb_select_kernel<FMT, 1>), gb, blk, 0, h->stream, h->d_hist.p, ns, n, b0, h->d_sel.p,
+                               h->f, d_iq, post, h->d_floors.p, h->d_thr.p, h->d_carries.p);
+            hipLaunchKernelGGL((pb_hist_kernel<FMT, 2>), g, blk, 0, h->stream, d_iq, n, ns, S, b0, h->d_sel.p,
+                               h->d_hist.p);
+            hipLaunchKernelGGL((pb_select_kernel<FMT, 2>), gb, blk, 0, h->stream, h->d_hist.p, ns, n, b0, h->d_sel.p,
+                               h->f, d_iq, post, h->d_floors.p, h->d_thr.p, h->d_carries.p);
+            hipLaunchKernelGGL((pb_apply_kernel<FMT>), g, blk, 0, h->stream, d_iq, n, ns, S, b0, pre, post,
+                               h->d_thr.p, h->d_carries.p, h->d_state.p, out, masks, h->d_scount.p);
+        });
     }
-    if (h->fmt == GPSMI_IQ_U8)
-        hipLaunchKernelGGL(pb_fixup_kernel<1>, dim3((unsigned)nb), dim3(256), 0, h->stream, d_iq, n, ns, nb,
-                           h->limit, h->d_scount, h->d_carries, h->d_state, h->d_counts, out, masks);
-    else
-        hipLaunchKernelGGL(pb_fixup_kernel<0>, dim3((unsigned)nb), dim3(256), 0, h->stream, d_iq, n, ns, nb,
-                           h->limit, h->d_scount, h->d_carries, h->d_state, h->d_counts, out, masks);
+    with_fmt(h->fmt, [&](auto fmt) {
+        hipLaunchKernelGGL(pb_fixup_kernel<decltype(fmt)::value>, dim3((unsigned)nb), dim3(256), 0, h->stream, d_iq,
+                           n, ns, nb, h->limit, h->d_scount.p, h->d_carries.p, h->d_state.p, h->d_counts.p, out, masks);
+    });
     GPSMI_HIP(hipGetLastError());
     GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
     return GPSMI_OK;
@@ -435,13 +403,13 @@ static int pb_run(gpsmi_pb* h, const void* d_iq, void* d_out, int nb, bool want_
 static int pb_finish(gpsmi_pb* h, int nb, int32_t* counts, float* floors, uint32_t* masks) {
     const int n = h->cfg.block_samples;
     if (counts)
-        GPSMI_HIP(hipMemcpyAsync(counts, h->d_counts, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost,
+        GPSMI_HIP(hipMemcpyAsync(counts, h->d_counts.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost,
                                  h->stream));
     if (floors)
-        GPSMI_HIP(hipMemcpyAsync(floors, h->d_floors, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost,
+        GPSMI_HIP(hipMemcpyAsync(floors, h->d_floors.p, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost,
                                  h->stream));
     if (masks)
-        GPSMI_HIP(hipMemcpyAsync(masks, h->d_masks, (size_t)nb * (n / 32) * sizeof(uint32_t),
+        GPSMI_HIP(hipMemcpyAsync(masks, h->d_masks.p, (size_t)nb * (n / 32) * sizeof(uint32_t),
                                  hipMemcpyDeviceToHost, h->stream));
     GPSMI_HIP(hipStreamSynchronize(h->stream));
     GPSMI_HIP(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
@@ -492,14 +460,10 @@ int gpsmi_pb_destroy(gpsmi_pb* h) {
     if (!h) return GPSMI_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* bufs[] = {h->d_state, h->d_hist,  h->d_sel,    h->d_floors, h->d_thr, h->d_carries,
-                    h->d_counts, h->d_scount, h->d_masks, h->d_in,     h->d_out};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                                // (releases the device buffers)
     return GPSMI_OK;
 }
 
@@ -515,7 +479,7 @@ int gpsmi_pb_set_input_format(gpsmi_pb* h, int fmt) {
 int gpsmi_pb_reset(gpsmi_pb* h) {
     GPSMI_REQUIRE(h, "null handle");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    GPSMI_HIP(hipMemsetAsync(h->d_state, 0, sizeof(int), h->stream));
+    GPSMI_HIP(hipMemsetAsync(h->d_state.p, 0, sizeof(int), h->stream));
     GPSMI_HIP(hipStreamSynchronize(h->stream));
     return GPSMI_OK;
 }
@@ -538,14 +502,11 @@ int gpsmi_pb_apply(gpsmi_pb* h, const void* iq, float* out, int nb, int32_t* cou
     if (rc) return rc;
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     const size_t ib = pb_in_bytes(h, nb), ob = (size_t)nb * h->cfg.block_samples * sizeof(float2);
-    rc = pb_grow(&h->d_in, &h->in_cap, ib);
+    rc = h->io.upload(iq, ib, ob, h->stream, "pulse blanking staging");
     if (rc) return rc;
-    rc = pb_grow(&h->d_out, &h->out_cap, ob);
+    rc = pb_run(h, h->io.in.p, h->io.out.p, nb, masks != nullptr);
     if (rc) return rc;
-    GPSMI_HIP(hipMemcpyAsync(h->d_in, iq, ib, hipMemcpyHostToDevice, h->stream));
-    rc = pb_run(h, h->d_in, h->d_out, nb, masks != nullptr);
-    if (rc) return rc;
-    GPSMI_HIP(hipMemcpyAsync(out, h->d_out, ob, hipMemcpyDeviceToHost, h->stream));
+    GPSMI_HIP(hipMemcpyAsync(out, h->io.out.p, ob, hipMemcpyDeviceToHost, h->stream));
     return pb_finish(h, nb, counts, floors, masks);
 }
 

@@ -34,11 +34,13 @@
 #include <deque>
 #include <mutex>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include <hip/hip_ext.h>
 
 #include "gpsmi_common.h"
+#include "gpsmi_devmem.h"
 #include "gpsmi_fft.h"
 
 // Code that restates the reference's float32 arithmetic step by step (the phase
@@ -773,8 +775,7 @@ struct gpsmi_trk {
     // streaming from host memory (gpsmi_trk_process_stream): two staging blocks filled on a stream
     // of their own, so that the upload of block k + 1 runs under the kernels of block k
     hipStream_t up_stream = nullptr;
-    void* d_stage[2] = {nullptr, nullptr};
-    size_t stage_bytes = 0;
+    DevBuf<char> d_stage[2];
     hipEvent_t up_done[2] = {nullptr, nullptr}, stage_free[2] = {nullptr, nullptr};
     hipEvent_t in_done[2] = {nullptr, nullptr};   // end of a streamed step (its iq read, its out written)
     bool in_pending[2] = {false, false};
@@ -788,17 +789,17 @@ struct gpsmi_trk {
     hipEvent_t main_tail = nullptr;      // the event recorded behind the last work on `stream`, if any
     // two result slots: a replay run writes one while the other is still being copied out
     struct Slot {
-        gpsmi_trk_out* d_out = nullptr;
+        DevBuf<gpsmi_trk_out> d_out;
         hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // start, corr done, correlator done, end
         hipEvent_t ready = nullptr, copied = nullptr;
         hipEvent_t corr_stop = nullptr;      // the event that carries the end stamp of the slot's timed correlator
         hipEvent_t corr_done = nullptr, epi_done = nullptr;   // correlator / epilogue of the slot's run
         bool copy_pending = false, epi_pending = false;
         int timing_pending = 0;              // the timing mode of the slot's run, until its times are taken
-        JobMid* d_mid = nullptr;             // per-job descriptors and window sums of the slot's run
-        float2* d_partial = nullptr;
+        DevBuf<JobMid> d_mid;                // per-job descriptors and window sums of the slot's run
+        DevBuf<float2> d_partial;
         hipStream_t run_stream = nullptr;    // "corr_overlap": the stream the slot's runs are enqueued on (null: h->stream)
-        float* d_rec = nullptr;              // raw sums of the single-block span correlator (gpsmi_trk_span.h):
+        DevBuf<float> d_rec;                 // raw sums of the single-block span correlator (gpsmi_trk_span.h):
                                              // per slot, the epilogue of run k reads them on its own stream
                                              // while run k + 1 writes the other slot's
     } slot[2];
@@ -806,21 +807,22 @@ struct gpsmi_trk {
     int timing = 1;                      // 1: record the four kernel-timing events per launch; 2: only the
                                          // begin / end stamps of the batch correlator's own dispatch (no
                                          // packet in the queue); 0: none
-    float2* d_tw = nullptr;
-    float* d_t32 = nullptr;
-    float2* d_rep = nullptr;         // [GPSMI_MAX_PRN + 1][cs] spectra
-    float* d_code = nullptr;         // [GPSMI_MAX_PRN + 1][cs] replica
+    // device memory: every buffer is a DevBuf (gpsmi_devmem.h) with a capacity of its own, in elements
+    DevBuf<float2> d_tw;
+    DevBuf<float> d_t32;
+    DevBuf<float2> d_rep;            // [GPSMI_MAX_PRN + 1][cs] spectra
+    DevBuf<float> d_code;            // [GPSMI_MAX_PRN + 1][cs] replica
     bool have_rep[GPSMI_MAX_PRN + 1] = {};
-    float2* d_block = nullptr;       // staging for host blocks
+    DevBuf<float2> d_block;          // staging for host blocks
     // closed loop (max_ch jobs)
-    gpsmi_trk_state* d_state = nullptr;
+    DevBuf<gpsmi_trk_state> d_state;
     std::vector<gpsmi_trk_state> h_state;
     bool state_dirty_host = false;   // host copy newer than device
-    // job buffers, sized for njobs_cap
+    // job buffers (trk_reserve).  njobs_cap is no allocation size -- each buffer has its own -- but the
+    // job count the tables and both slots were last sized for, all of them together
     size_t njobs_cap = 0;
-    gpsmi_trk_state* d_tab_in = nullptr;
-    gpsmi_trk_state* d_tab_out = nullptr;
-    int* d_forced = nullptr;
+    DevBuf<gpsmi_trk_state> d_tab_in, d_tab_out;
+    DevBuf<int> d_forced;
     float last_total_ms = 0.f, last_corr_ms = 0.f, last_cp_ms = 0.f;
     int replay_nb = 0;
     bool replay_forced = false;
@@ -837,19 +839,19 @@ struct gpsmi_trk {
     int fold_chunk = 0;              // option "fold_chunk": blocks per fold -> correlation piece at CS = 16368
     int epilogue_form = 1;           // option "epilogue_form": 1 = eight lanes per job in the batch epilogue
                                      // (trk_epilogue8_kernel), 0 = a wave per job (trk_epilogue_kernel); same bits
-    float* d_code_eo = nullptr;      // [GPSMI_MAX_PRN + 1][...]: the replica re-cut for the matrix correlators.  Span form
+    DevBuf<float> d_code_eo;         // [GPSMI_MAX_PRN + 1][...]: the replica re-cut for the matrix correlators.  Span form
                                      // (2048): four planes by index mod 4, entry h of plane e = replica[(4 h + e) mod 2048],
                                      // 1024 entries each (a lane's run never wraps); span8 form: two planes by index
                                      // parity, each twice over
     int n_cu = 256;                  // compute units of the device
     int iq_fmt = GPSMI_IQ_C64;       // what the iq pointers of process / replay point to
     int nchunks = 1;                 // spans of 256 * stream_j positions per code period
-    float2* d_fold = nullptr; float* d_mag = nullptr; DirStats* d_stats = nullptr;
-    int* d_xsel = nullptr; int* d_rsel = nullptr; float2* d_partial_g = nullptr;
+    DevBuf<float2> d_fold; DevBuf<float> d_mag; DevBuf<DirStats> d_stats;
+    DevBuf<int> d_xsel, d_rsel; DevBuf<float2> d_partial_g;
     bool big = false;                // correlation through the 32768-point FFT pair
-    float2* d_twN = nullptr; float2* d_RS = nullptr; float2* d_S = nullptr;
+    DevBuf<float2> d_twN, d_RS, d_S;
     bool pfa = false;                // ... or natively in LDS at 16368 samples (gpsmi_pfa.h)
-    float2* d_RSp = nullptr;
+    DevBuf<float2> d_RSp;
     bool span8 = false;              // the matrix-pipe correlator for CS = 16368, N_CYC = 8 (gpsmi_trk_span8.h)
     TrkParams P;
     // gpsmi_trk_process_stream's submission thread (option "stream_thread", default on): the four
@@ -885,48 +887,42 @@ struct gpsmi_trk {
 
 constexpr int kSpanUnitsMax = 256;   // (block, channel group) units the single-block span form can serve (records)
 
+// Everything sized by the job count, for njobs jobs.  A larger count reallocates all of it (a
+// DevBuf whose size grows; the records of the single-block span form, of one fixed size, by hand).
 static int trk_reserve(gpsmi_trk* h, size_t njobs) {
     if (njobs <= h->njobs_cap) return GPSMI_OK;
-    void* olds[] = {h->d_tab_in, h->d_tab_out, h->d_forced, h->slot[0].d_mid, h->slot[1].d_mid,
-                    h->slot[0].d_partial, h->slot[1].d_partial, h->slot[0].d_out, h->slot[1].d_out,
-                    h->d_fold, h->d_mag, h->d_stats, h->d_xsel, h->d_rsel, h->d_partial_g,
-                    h->slot[0].d_rec, h->slot[1].d_rec};
-    for (void* p : olds)
-        if (p) GPSMI_HIP(hipFree(p));
-    h->d_tab_in = h->d_tab_out = nullptr; h->d_forced = nullptr;
-    for (auto& sl : h->slot) { sl.d_mid = nullptr; sl.d_partial = nullptr; sl.d_out = nullptr; sl.d_rec = nullptr; }
     h->njobs_cap = 0;
-    h->d_fold = nullptr; h->d_mag = nullptr; h->d_stats = nullptr; h->d_xsel = h->d_rsel = nullptr;
-    h->d_partial_g = nullptr;
+    const size_t cs = h->cfg.code_samples, per_job = h->cfg.n_cyc + 1;
+    int rc = GPSMI_OK;
     if (h->mfma == 4)       // 32 records per (block, channel group) of the single-block span form
-        for (auto& sl : h->slot)
-            GPSMI_HIP(hipMalloc((void**)&sl.d_rec, (size_t)kSpanUnitsMax * 32 * kSpRecFloats * sizeof(float)));
+        for (auto& sl : h->slot) {
+            sl.d_rec.release();
+            if (!rc) rc = sl.d_rec.reserve((size_t)kSpanUnitsMax * 32 * kSpRecFloats, "gpsmi_trk span records");
+        }
     if (h->general) {
-        const size_t cs = h->cfg.code_samples;
-        GPSMI_HIP(hipMalloc((void**)&h->d_fold, njobs * cs * sizeof(float2)));
-        if (!h->pfa) GPSMI_HIP(hipMalloc((void**)&h->d_mag, njobs * cs * sizeof(float)));
-        GPSMI_HIP(hipMalloc((void**)&h->d_stats, njobs * sizeof(DirStats)));
-        GPSMI_HIP(hipMalloc((void**)&h->d_xsel, njobs * sizeof(int)));
-        GPSMI_HIP(hipMalloc((void**)&h->d_rsel, njobs * sizeof(int)));
+        if (!rc) rc = h->d_fold.reserve(njobs * cs, "gpsmi_trk folded samples");
+        if (!rc && !h->pfa) rc = h->d_mag.reserve(njobs * cs, "gpsmi_trk magnitudes");
+        if (!rc) rc = h->d_stats.reserve(njobs, "gpsmi_trk job statistics");
+        if (!rc) rc = h->d_xsel.reserve(njobs, "gpsmi_trk job table");
+        if (!rc) rc = h->d_rsel.reserve(njobs, "gpsmi_trk job table");
     }
     if (h->span8) {         // one 2 KiB record per range of every (block, channel group)
         const size_t units = ((njobs + h->max_ch - 1) / h->max_ch) * ((h->max_ch + kSpCh - 1) / kSpCh);
         for (auto& sl : h->slot)
-            GPSMI_HIP(hipMalloc((void**)&sl.d_rec, units * kS8Ranges * kS8RecFloats * sizeof(float)));
+            if (!rc) rc = sl.d_rec.reserve(units * kS8Ranges * kS8RecFloats, "gpsmi_trk span records");
     }
-    if (h->nchunks > 1 && !h->span8)
-        GPSMI_HIP(hipMalloc((void**)&h->d_partial_g,
-                            njobs * h->nchunks * (h->cfg.n_cyc + 1) * sizeof(float2)));
-    GPSMI_HIP(hipMalloc((void**)&h->d_tab_in, njobs * sizeof(gpsmi_trk_state)));
-    GPSMI_HIP(hipMalloc((void**)&h->d_tab_out, njobs * sizeof(gpsmi_trk_state)));
-    GPSMI_HIP(hipMalloc((void**)&h->d_forced, njobs * sizeof(int)));
+    if (!rc && h->nchunks > 1 && !h->span8)
+        rc = h->d_partial_g.reserve(njobs * h->nchunks * per_job, "gpsmi_trk partial sums");
+    if (!rc) rc = h->d_tab_in.reserve(njobs, "gpsmi_trk job table");
+    if (!rc) rc = h->d_tab_out.reserve(njobs, "gpsmi_trk job table");
+    if (!rc) rc = h->d_forced.reserve(njobs, "gpsmi_trk job table");
     for (auto& sl : h->slot) {
-        GPSMI_HIP(hipMalloc((void**)&sl.d_mid, njobs * sizeof(JobMid)));
-        GPSMI_HIP(hipMalloc((void**)&sl.d_partial, njobs * (h->cfg.n_cyc + 1) * sizeof(float2)));
-        GPSMI_HIP(hipMalloc((void**)&sl.d_out, njobs * sizeof(gpsmi_trk_out)));
+        if (!rc) rc = sl.d_mid.reserve(njobs, "gpsmi_trk job descriptors");
+        if (!rc) rc = sl.d_partial.reserve(njobs * per_job, "gpsmi_trk window sums");
+        if (!rc) rc = sl.d_out.reserve(njobs, "gpsmi_trk results");
     }
-    h->njobs_cap = njobs;
-    return GPSMI_OK;
+    if (!rc) h->njobs_cap = njobs;
+    return rc;
 }
 
 // the three kernels over njobs jobs on the handle's stream, events around them
@@ -945,7 +941,6 @@ static int trk_launch(gpsmi_trk* h, gpsmi_trk::Slot& sl, const void* d_iq_v,
     hipStream_t rs = sl.run_stream ? sl.run_stream : h->stream;
     h->main_tail = nullptr;
     const float2* d_iq = static_cast<const float2*>(d_iq_v);       // (raw uint16 when iq_fmt says so)
-    const bool u8 = h->iq_fmt == GPSMI_IQ_U8;
     sl.corr_stop = sl.ev[2];
     const bool timed = h->timing == 1;   // each event record is a barrier packet (~5 us of bubble)
     const bool corr_stamps = h->timing == 2;
@@ -969,25 +964,25 @@ static int trk_launch(gpsmi_trk* h, gpsmi_trk::Slot& sl, const void* d_iq_v,
         for (int b0 = 0; b0 < nblocks; b0 += chunk) {
             const int nbc = nblocks - b0 < chunk ? nblocks - b0 : chunk;
             hipLaunchKernelGGL(trk_fold_general_kernel, dim3((cs + 255) / 256, nbc), dim3(256), 0,
-                               rs, d_iq, h->d_t32, st_in, P, h->d_fold, h->d_xsel, h->d_rsel,
-                               sl.d_mid, b0);
+                               rs, d_iq, h->d_t32.p, st_in, P, h->d_fold.p, h->d_xsel.p, h->d_rsel.p,
+                               sl.d_mid.p, b0);
             if (h->pfa)              // transform, product, transform and statistics in one launch
-                pfa_corr_launch(rs, h->d_fold, h->d_xsel, h->d_rsel, nbc * nch, h->d_RSp, h->d_stats, b0 * nch);
+                pfa_corr_launch(rs, h->d_fold.p, h->d_xsel.p, h->d_rsel.p, nbc * nch, h->d_RSp.p, h->d_stats.p, b0 * nch);
         }
         if (h->pfa) {
         } else if (h->big)
-            big_corr_launch(rs, h->d_fold, h->d_xsel, h->d_rsel, njobs, cs, h->d_RS, h->d_S,
-                            h->d_tw, h->d_twN, h->d_mag);
+            big_corr_launch(rs, h->d_fold.p, h->d_xsel.p, h->d_rsel.p, njobs, cs, h->d_RS.p, h->d_S.p,
+                            h->d_tw.p, h->d_twN.p, h->d_mag.p);
         else
             hipLaunchKernelGGL(circ_corr_direct_kernel,
                                dim3((cs + kDirLagsPerWg - 1) / kDirLagsPerWg, njobs), dim3(256), 0,
-                               rs, h->d_fold, h->d_code, h->d_xsel, h->d_rsel, cs,
-                               h->d_mag);
+                               rs, h->d_fold.p, h->d_code.p, h->d_xsel.p, h->d_rsel.p, cs,
+                               h->d_mag.p);
         if (!h->pfa)
-            hipLaunchKernelGGL(corr_stats_kernel, dim3(njobs), dim3(256), 0, rs, h->d_mag, cs,
-                               h->d_stats);
+            hipLaunchKernelGGL(corr_stats_kernel, dim3(njobs), dim3(256), 0, rs, h->d_mag.p, cs,
+                               h->d_stats.p);
         hipLaunchKernelGGL(trk_decide_kernel, dim3((njobs + 255) / 256), dim3(256), 0, rs,
-                           h->d_stats, forced, P, njobs, sl.d_out, sl.d_mid);
+                           h->d_stats.p, forced, P, njobs, sl.d_out.p, sl.d_mid.p);
     } else {
         // channels per correlation workgroup: fewer channels = fewer live accumulators
         // = more workgroups per CU for the barrier-heavy FFT phase (GPSMI_CORR_CG to tune)
@@ -998,20 +993,10 @@ static int trk_launch(gpsmi_trk* h, gpsmi_trk::Slot& sl, const void* d_iq_v,
         const int cg = jobs_all <= h->corr_small1 ? 1 : (jobs_all <= h->corr_small2 ? 2 : h->corr_cg);
         const int ng = (nch + cg - 1) / cg;
         const dim3 cgrid(corr_grid(nblocks, ng));
-#define GPSMI_LAUNCH_CORR(CGV)                                                                          \
-    do {                                                                                              \
-        if (u8)                                                                                       \
-            hipLaunchKernelGGL((trk_corr_kernel<CGV, 1>), cgrid, dim3(256), 0, rs, d_iq_v,     \
-                               st_in, forced, h->d_rep, h->d_tw, P, ng, nblocks, sl.d_out, sl.d_mid); \
-        else                                                                                          \
-            hipLaunchKernelGGL((trk_corr_kernel<CGV, 0>), cgrid, dim3(256), 0, rs, d_iq_v,     \
-                               st_in, forced, h->d_rep, h->d_tw, P, ng, nblocks, sl.d_out, sl.d_mid); \
-    } while (0)
-        if (cg == 6) GPSMI_LAUNCH_CORR(6);
-        else if (cg == 4) GPSMI_LAUNCH_CORR(4);
-        else if (cg == 2) GPSMI_LAUNCH_CORR(2);
-        else GPSMI_LAUNCH_CORR(1);
-#undef GPSMI_LAUNCH_CORR
+        with_value<6, 4, 2, 1>(cg, [&](auto cgv) { with_fmt(h->iq_fmt, [&](auto fmt) {
+            hipLaunchKernelGGL((trk_corr_kernel<decltype(cgv)::value, decltype(fmt)::value>), cgrid, dim3(256), 0,
+                               rs, d_iq_v, st_in, forced, h->d_rep.p, h->d_tw.p, P, ng, nblocks, sl.d_out.p, sl.d_mid.p);
+        }); });
     }
     // ---- the correlator.  When a launch is timed, the two events of the batch form of the span
     // correlator are the dispatch's own begin / end stamps (hipExtLaunchKernel: what a kernel
@@ -1027,31 +1012,8 @@ static int trk_launch(gpsmi_trk* h, gpsmi_trk::Slot& sl, const void* d_iq_v,
     if (timed && !ext_timed) GPSMI_HIP(hipEventRecord(sl.ev[1], rs));
     if (h->mfma) {                         // the correlator on the matrix pipe (span form, N_CYC = 32 / 16 / 8)
         const int ng12 = (nch + kSpCh - 1) / kSpCh;
-        const JobMid* cmid = sl.d_mid;
-        const float* ceo = h->d_code_eo;
-        // one launch of trk_span_kernel<NSPANS, WAVES, FMT, 0, NC>: with the dispatch's own begin / end
-        // stamps (ext, both events), with its completion signal as `stop` alone, or plainly
-#define GPSMI_LAUNCH_SPAN(NSP, WV, FMTV, NCV, GRID, BLOCK)                                                     \
-    do {                                                                                                      \
-        if (ext_timed && (NSP) == 8)                                                                          \
-            hipExtLaunchKernelGGL((trk_span_kernel<NSP, WV, FMTV, 0, NCV>), GRID, BLOCK, 0, rs, sl.ev[1],     \
-                                  sl.corr_stop, 0, d_iq_v, cmid, ceo, P, ng12, nblocks, sl.d_rec,             \
-                                  sl.d_partial);                                                              \
-        else if (by_dispatch && (NSP) == 8)                                                                   \
-            hipExtLaunchKernelGGL((trk_span_kernel<NSP, WV, FMTV, 0, NCV>), GRID, BLOCK, 0, rs, nullptr,      \
-                                  sl.corr_done, 0, d_iq_v, cmid, ceo, P, ng12, nblocks, sl.d_rec,             \
-                                  sl.d_partial);                                                              \
-        else                                                                                                  \
-            hipLaunchKernelGGL((trk_span_kernel<NSP, WV, FMTV, 0, NCV>), GRID, BLOCK, 0, rs, d_iq_v, cmid,    \
-                               ceo, P, ng12, nblocks, sl.d_rec, sl.d_partial);                                \
-    } while (0)
-#define GPSMI_LAUNCH_SPAN_NC(NCV)                                                                       \
-    do {                                                                                               \
-        if (span_single && u8) GPSMI_LAUNCH_SPAN(1, 1, 1, NCV, dim3(nblocks * ng12 * 32), dim3(64));   \
-        else if (span_single) GPSMI_LAUNCH_SPAN(1, 1, 0, NCV, dim3(nblocks * ng12 * 32), dim3(64));    \
-        else if (u8) GPSMI_LAUNCH_SPAN(8, 4, 1, NCV, span_grid, dim3(256));                            \
-        else GPSMI_LAUNCH_SPAN(8, 4, 0, NCV, span_grid, dim3(256));                                    \
-    } while (0)
+        const JobMid* cmid = sl.d_mid.p;
+        const float* ceo = h->d_code_eo.p;
         // replay: the event the epilogue stream (and a search) waits for is the completion signal of
         // this very dispatch, not a record behind it - a record is one more barrier packet between
         // this kernel and the next batch's first one
@@ -1059,23 +1021,39 @@ static int trk_launch(gpsmi_trk* h, gpsmi_trk::Slot& sl, const void* d_iq_v,
         // (a timed launch that is also the one the epilogue stream waits for: ONE stop event serves
         // both -- the dispatch's completion signal -- instead of a record packet behind the kernel)
         sl.corr_stop = (ext_timed && by_dispatch) ? sl.corr_done : sl.ev[2];
-        if (P.n_cyc == 32) GPSMI_LAUNCH_SPAN_NC(32);
-        else if (P.n_cyc == 16) GPSMI_LAUNCH_SPAN_NC(16);
-        else GPSMI_LAUNCH_SPAN_NC(8);
-#undef GPSMI_LAUNCH_SPAN_NC
-#undef GPSMI_LAUNCH_SPAN
+        // One launch of trk_span_kernel<NSPANS, WAVES, FMT, 0, NC>.  The single-block form goes out plainly.
+        // The batch form goes out with the dispatch's own begin / end stamps when it is timed (both events),
+        // with its completion signal as the stop event alone when the epilogue stream waits for this very
+        // dispatch, and plainly otherwise.
+        with_value<32, 16, 8>(P.n_cyc, [&](auto ncv) { with_fmt(h->iq_fmt, [&](auto fmt) {
+            constexpr int NC = decltype(ncv)::value, FMT = decltype(fmt)::value;
+            if (span_single)
+                hipLaunchKernelGGL((trk_span_kernel<1, 1, FMT, 0, NC>), dim3(nblocks * ng12 * 32), dim3(64), 0, rs,
+                                   d_iq_v, cmid, ceo, P, ng12, nblocks, sl.d_rec.p, sl.d_partial.p);
+            else if (ext_timed)
+                hipExtLaunchKernelGGL((trk_span_kernel<8, 4, FMT, 0, NC>), span_grid, dim3(256), 0, rs, sl.ev[1],
+                                      sl.corr_stop, 0, d_iq_v, cmid, ceo, P, ng12, nblocks, sl.d_rec.p,
+                                      sl.d_partial.p);
+            else if (by_dispatch)
+                hipExtLaunchKernelGGL((trk_span_kernel<8, 4, FMT, 0, NC>), span_grid, dim3(256), 0, rs, nullptr,
+                                      sl.corr_done, 0, d_iq_v, cmid, ceo, P, ng12, nblocks, sl.d_rec.p,
+                                      sl.d_partial.p);
+            else
+                hipLaunchKernelGGL((trk_span_kernel<8, 4, FMT, 0, NC>), span_grid, dim3(256), 0, rs, d_iq_v, cmid,
+                                   ceo, P, ng12, nblocks, sl.d_rec.p, sl.d_partial.p);
+        }); });
         corr_done_recorded = by_dispatch;
     } else if (h->span8) {                 // CS = 16368, N_CYC = 8 on the matrix pipe
         const int ng12 = (nch + kSpCh - 1) / kSpCh;
         const int nwaves = nblocks * ng12 * kS8Ranges;
         hipLaunchKernelGGL(trk_span8_kernel, dim3((nwaves + 3) / 4), dim3(256), 0, rs, d_iq,
-                           sl.d_mid, h->d_code_eo, P, ng12, nblocks, sl.d_rec);
+                           sl.d_mid.p, h->d_code_eo.p, P, ng12, nblocks, sl.d_rec.p);
     } else {                               // the vector correlator (other block / code lengths)
         const dim3 grid(sgrid.x, h->nchunks), block(kStreamThreads);
-        float2* pdst = h->nchunks > 1 ? h->d_partial_g : sl.d_partial;
+        float2* pdst = h->nchunks > 1 ? h->d_partial_g.p : sl.d_partial.p;
 #define GPSMI_LAUNCH_STREAM(NC, POW2, J)                                                        \
     hipLaunchKernelGGL((trk_stream_kernel<NC, POW2, J>), grid, block, 0, rs, d_iq, st_in, \
-                       sl.d_mid, h->d_code, P, ngroups, nblocks, pdst)
+                       sl.d_mid.p, h->d_code.p, P, ngroups, nblocks, pdst)
 #define GPSMI_LAUNCH_STREAM_NC(POW2, J)                 \
     do {                                                \
         if (P.n_cyc == 32) GPSMI_LAUNCH_STREAM(32, POW2, J);      \
@@ -1089,8 +1067,8 @@ static int trk_launch(gpsmi_trk* h, gpsmi_trk::Slot& sl, const void* d_iq_v,
         if (h->nchunks > 1) {
             const int per_job = P.n_cyc + 1;
             hipLaunchKernelGGL(trk_partial_reduce_kernel, dim3((njobs * per_job + 255) / 256),
-                               dim3(256), 0, rs, h->d_partial_g, h->nchunks, per_job, njobs,
-                               sl.d_mid, sl.d_partial);
+                               dim3(256), 0, rs, h->d_partial_g.p, h->nchunks, per_job, njobs,
+                               sl.d_mid.p, sl.d_partial.p);
         }
     }
     if (timed && !ext_timed) GPSMI_HIP(hipEventRecord(sl.ev[2], rs));
@@ -1104,24 +1082,24 @@ static int trk_launch(gpsmi_trk* h, gpsmi_trk::Slot& sl, const void* d_iq_v,
         GPSMI_HIP(hipStreamWaitEvent(es, sl.corr_done, 0));
     }
     const gpsmi_trk_state* c_in = st_in;
-    const JobMid* c_mid = sl.d_mid;
-    const float* c_rec = sl.d_rec;
-    const float2* c_partial = sl.d_partial;
+    const JobMid* c_mid = sl.d_mid.p;
+    const float* c_rec = sl.d_rec.p;
+    const float2* c_partial = sl.d_partial.p;
     bool stop_used = false;
 #define GPSMI_LAUNCH_EPI_SPAN(NCV)                                                                         \
     do {                                                                                                  \
         if (tail_stop) {                                                                                  \
             hipExtLaunchKernelGGL(trk_epilogue_span_kernel<NCV>, dim3(njobs), dim3(256), 0, es, nullptr,  \
-                                  tail_stop, 0, c_in, st_out, c_mid, c_rec, ng_span, P, njobs, sl.d_out); \
+                                  tail_stop, 0, c_in, st_out, c_mid, c_rec, ng_span, P, njobs, sl.d_out.p); \
             stop_used = true;                                                                             \
         } else {                                                                                          \
             hipLaunchKernelGGL(trk_epilogue_span_kernel<NCV>, dim3(njobs), dim3(256), 0, es, c_in,        \
-                               st_out, c_mid, c_rec, ng_span, P, njobs, sl.d_out);                        \
+                               st_out, c_mid, c_rec, ng_span, P, njobs, sl.d_out.p);                        \
         }                                                                                                 \
     } while (0)
     if (h->span8)
         hipLaunchKernelGGL(trk_epilogue_span8_kernel, dim3((njobs + 3) / 4), dim3(256), 0, es, st_in,
-                           st_out, sl.d_mid, sl.d_rec, ng_span, P, njobs, sl.d_out);
+                           st_out, sl.d_mid.p, sl.d_rec.p, ng_span, P, njobs, sl.d_out.p);
     else if (span_single && P.n_cyc == 32)
         GPSMI_LAUNCH_EPI_SPAN(32);
     else if (span_single && P.n_cyc == 16)
@@ -1131,22 +1109,22 @@ static int trk_launch(gpsmi_trk* h, gpsmi_trk::Slot& sl, const void* d_iq_v,
     else if (h->epilogue_form == 0) {        // a wave per job
         if (tail_stop) {
             hipExtLaunchKernelGGL(trk_epilogue_kernel, dim3((njobs + 3) / 4), dim3(256), 0, es, nullptr,
-                                  tail_stop, 0, c_in, st_out, c_mid, c_partial, P, njobs, sl.d_out);
+                                  tail_stop, 0, c_in, st_out, c_mid, c_partial, P, njobs, sl.d_out.p);
             stop_used = true;
         } else
             hipLaunchKernelGGL(trk_epilogue_kernel, dim3((njobs + 3) / 4), dim3(256), 0, es, st_in,
-                               st_out, sl.d_mid, sl.d_partial, P, njobs, sl.d_out);
+                               st_out, sl.d_mid.p, sl.d_partial.p, P, njobs, sl.d_out.p);
     } else {                                 // eight lanes per job (the default)
 #define GPSMI_LAUNCH_EPI8(NCV)                                                                           \
     do {                                                                                                \
         if (tail_stop) {                                                                                \
             hipExtLaunchKernelGGL(trk_epilogue8_kernel<NCV>, dim3((njobs + 7) / 8), dim3(64), 0, es,    \
                                   nullptr, tail_stop, 0, c_in, st_out, c_mid, c_partial, P, njobs,      \
-                                  sl.d_out);                                                            \
+                                  sl.d_out.p);                                                            \
             stop_used = true;                                                                           \
         } else {                                                                                        \
             hipLaunchKernelGGL(trk_epilogue8_kernel<NCV>, dim3((njobs + 7) / 8), dim3(64), 0, es, c_in, \
-                               st_out, c_mid, c_partial, P, njobs, sl.d_out);                           \
+                               st_out, c_mid, c_partial, P, njobs, sl.d_out.p);                           \
         }                                                                                               \
     } while (0)
         if (P.n_cyc == 32) GPSMI_LAUNCH_EPI8(32);
@@ -1204,7 +1182,7 @@ static int trk_settle(gpsmi_trk* h) {
 static int trk_push_state(gpsmi_trk* h) {
     if (!h->state_dirty_host) return GPSMI_OK;
     h->main_tail = nullptr;              // (new work on `stream`: the recorded tail no longer covers it)
-    GPSMI_HIP(hipMemcpyAsync(h->d_state, h->h_state.data(), h->rows() * sizeof(gpsmi_trk_state),
+    GPSMI_HIP(hipMemcpyAsync(h->d_state.p, h->h_state.data(), h->rows() * sizeof(gpsmi_trk_state),
                              hipMemcpyHostToDevice, h->stream));
     GPSMI_HIP(hipStreamSynchronize(h->stream));
     h->state_dirty_host = false;
@@ -1213,7 +1191,7 @@ static int trk_push_state(gpsmi_trk* h) {
 
 static int trk_pull_state(gpsmi_trk* h) {
     if (h->state_dirty_host) return GPSMI_OK;        // host copy is the newest
-    GPSMI_HIP(hipMemcpyAsync(h->h_state.data(), h->d_state, h->rows() * sizeof(gpsmi_trk_state),
+    GPSMI_HIP(hipMemcpyAsync(h->h_state.data(), h->d_state.p, h->rows() * sizeof(gpsmi_trk_state),
                              hipMemcpyDeviceToHost, h->stream));
     GPSMI_HIP(hipStreamSynchronize(h->stream));
     return GPSMI_OK;
@@ -1400,29 +1378,25 @@ static int trk_build(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk* h) {
     }
     std::vector<float2> tw;
     make_twiddles(tw);
-    GPSMI_HIP(hipMalloc((void**)&h->d_tw, tw.size() * sizeof(float2)));
-    GPSMI_HIP(hipMemcpy(h->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
+    int rc = h->d_tw.upload(tw, "gpsmi_trk twiddles");
+    if (rc) return rc;
     const int ngps = cfg->n_cyc * cfg->code_samples;
     const float fs = (float)(1000 * cfg->code_samples);
     std::vector<float> t32(ngps);
     for (int k = 0; k < ngps; ++k) t32[k] = (float)(k + 1) / fs;   // gpslib.py:1053-1054
-    GPSMI_HIP(hipMalloc((void**)&h->d_t32, ngps * sizeof(float)));
-    GPSMI_HIP(hipMemcpy(h->d_t32, t32.data(), ngps * sizeof(float), hipMemcpyHostToDevice));
-    GPSMI_HIP(hipMalloc((void**)&h->d_rep, (size_t)(GPSMI_MAX_PRN + 1) * kFftN * sizeof(float2)));
-    const size_t code_bytes = (size_t)(GPSMI_MAX_PRN + 1) * cfg->code_samples * sizeof(float);
-    GPSMI_HIP(hipMalloc((void**)&h->d_code, code_bytes));
-    GPSMI_HIP(hipMemset(h->d_code, 0, code_bytes));          // slot 0: closed channels
+    if ((rc = h->d_t32.upload(t32, "gpsmi_trk time base")) ||
+        (rc = h->d_rep.reserve((size_t)(GPSMI_MAX_PRN + 1) * kFftN, "gpsmi_trk replica spectra")) ||
+        // (zeroed for slot 0: closed channels)
+        (rc = h->d_code.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * cfg->code_samples, "gpsmi_trk replicas")))
+        return rc;
     long long want_matrix = 1;           // option "correlator": 0 keeps the vector kernel (gpsmi_trk_stream.h)
     default_opt("correlator", &want_matrix, 1);
     {
         // default for CS = 2048, N_CYC = 32: the span form of the MFMA correlator.  One form per handle:
         // the closed loop and the replay of a handle sum in the same order (bytewise equal results).
         h->mfma = (!h->general && want_matrix != 0) ? 4 : 0;          // (N_CYC = 32, 16 and 8: template parameter NC)
-        if (h->mfma) {
-            const size_t b2 = (size_t)(GPSMI_MAX_PRN + 1) * 2 * kFftN * sizeof(float);
-            GPSMI_HIP(hipMalloc((void**)&h->d_code_eo, b2));
-            GPSMI_HIP(hipMemset(h->d_code_eo, 0, b2));
-        }
+        if (h->mfma && (rc = h->d_code_eo.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * 2 * kFftN, "gpsmi_trk replica planes")))
+            return rc;
     }
     if (h->general) {
         long long forced = 0;                    // option "codephase": 1 keeps the time-domain kernel,
@@ -1431,18 +1405,12 @@ static int trk_build(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk* h) {
         h->pfa = cfg->code_samples == kPfaL && forced == 0;
         h->big = !h->pfa && 2 * cfg->code_samples - 1 <= kBigN && forced != 1;
     }
-    if (h->pfa) {
-        const size_t b = (size_t)(GPSMI_MAX_PRN + 1) * kPfaL * sizeof(float2);
-        GPSMI_HIP(hipMalloc((void**)&h->d_RSp, b));
-        GPSMI_HIP(hipMemset(h->d_RSp, 0, b));                // slot 0: closed channels
-    }
+    if (h->pfa && (rc = h->d_RSp.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * kPfaL, "gpsmi_trk replica spectra")))
+        return rc;                                           // (zeroed for slot 0: closed channels)
     {
         h->span8 = h->general && cfg->code_samples == kS8Cs && cfg->n_cyc == kS8Rows && want_matrix != 0;
-        if (h->span8) {
-            const size_t b2 = (size_t)(GPSMI_MAX_PRN + 1) * 2 * kS8Cs * sizeof(float);
-            GPSMI_HIP(hipMalloc((void**)&h->d_code_eo, b2));
-            GPSMI_HIP(hipMemset(h->d_code_eo, 0, b2));
-        }
+        if (h->span8 && (rc = h->d_code_eo.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * 2 * kS8Cs, "gpsmi_trk replica planes")))
+            return rc;
     }
     if (h->big) {
         std::vector<float2> twn(kBigN);
@@ -1450,17 +1418,16 @@ static int trk_build(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk* h) {
             const double a = -2.0 * M_PI * (double)k / (double)kBigN;
             twn[k] = make_float2((float)cos(a), (float)sin(a));
         }
-        GPSMI_HIP(hipMalloc((void**)&h->d_twN, kBigN * sizeof(float2)));
-        GPSMI_HIP(hipMemcpy(h->d_twN, twn.data(), kBigN * sizeof(float2), hipMemcpyHostToDevice));
-        const size_t rs_bytes = (size_t)(GPSMI_MAX_PRN + 1) * kBigN * sizeof(float2);
-        GPSMI_HIP(hipMalloc((void**)&h->d_RS, rs_bytes));
-        GPSMI_HIP(hipMemset(h->d_RS, 0, rs_bytes));          // slot 0: closed channels
-        GPSMI_HIP(hipMalloc((void**)&h->d_S, (size_t)kBigChunkCells * kBigN * sizeof(float2)));
+        if ((rc = h->d_twN.upload(twn, "gpsmi_trk twiddles")) ||
+            // (zeroed for slot 0: closed channels)
+            (rc = h->d_RS.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * kBigN, "gpsmi_trk replica spectra")) ||
+            (rc = h->d_S.reserve((size_t)kBigChunkCells * kBigN, "gpsmi_trk correlation scratch")))
+            return rc;
     }
-    GPSMI_HIP(hipMalloc((void**)&h->d_block, (size_t)ngps * sizeof(float2)));
-    GPSMI_HIP(hipMalloc((void**)&h->d_state, max_ch * sizeof(gpsmi_trk_state)));
+    if ((rc = h->d_block.reserve(ngps, "gpsmi_trk input block")) ||
+        (rc = h->d_state.reserve_zeroed(max_ch, "gpsmi_trk states")))
+        return rc;
     h->h_state.assign(max_ch, gpsmi_trk_state{});
-    GPSMI_HIP(hipMemset(h->d_state, 0, max_ch * sizeof(gpsmi_trk_state)));
     TrkParams& P = h->P;
     P.cs = cfg->code_samples; P.n_cyc = cfg->n_cyc;
     P.corr_avg = cfg->corr_avg < cfg->n_cyc ? cfg->corr_avg : cfg->n_cyc;   // gpslib.py:1071
@@ -1514,14 +1481,6 @@ int gpsmi_trk_destroy(gpsmi_trk* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->copy_stream && h->own_copy_stream) (void)hipStreamSynchronize(h->copy_stream);
     if (h->epi_stream) (void)hipStreamSynchronize(h->epi_stream);
-    void* bufs[] = {h->d_tw, h->d_t32, h->d_rep, h->d_code, h->d_block, h->d_state, h->d_tab_in,
-                    h->d_tab_out, h->d_forced, h->slot[0].d_mid, h->slot[1].d_mid, h->slot[0].d_partial,
-                    h->slot[1].d_partial, h->slot[0].d_out,
-                    h->slot[1].d_out, h->d_fold,
-                    h->d_mag, h->d_stats, h->d_xsel, h->d_rsel, h->d_partial_g, h->d_twN, h->d_RS,
-                    h->d_S, h->d_code_eo, h->slot[0].d_rec, h->slot[1].d_rec, h->d_RSp};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
     for (auto& sl : h->slot) {
         for (auto e : sl.ev)
             if (e) (void)hipEventDestroy(e);
@@ -1533,7 +1492,6 @@ int gpsmi_trk_destroy(gpsmi_trk* h) {
     if (h->order) (void)hipEventDestroy(h->order);
     if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
     for (int k = 0; k < 2; ++k) {
-        if (h->d_stage[k]) (void)hipFree(h->d_stage[k]);
         if (h->up_done[k]) (void)hipEventDestroy(h->up_done[k]);
         if (h->stage_free[k]) (void)hipEventDestroy(h->stage_free[k]);
         if (h->in_done[k]) (void)hipEventDestroy(h->in_done[k]);
@@ -1543,7 +1501,7 @@ int gpsmi_trk_destroy(gpsmi_trk* h) {
     if (h->alt_stream) { (void)hipStreamSynchronize(h->alt_stream); (void)hipStreamDestroy(h->alt_stream); }
     if (h->epi_stream) (void)hipStreamDestroy(h->epi_stream);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                                // (releases the device buffers)
     return GPSMI_OK;
 }
 
@@ -1553,27 +1511,27 @@ int gpsmi_trk_set_replica(gpsmi_trk* h, int prn, const float* replica, const flo
     GPSMI_QUIESCE(h);
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     const size_t cs = h->cfg.code_samples;
-    GPSMI_HIP(hipMemcpy(h->d_code + (size_t)prn * cs, replica, cs * sizeof(float),
+    GPSMI_HIP(hipMemcpy(h->d_code.p + (size_t)prn * cs, replica, cs * sizeof(float),
                         hipMemcpyHostToDevice));
     if (h->mfma) {
         std::vector<float> eo(2 * kFftN);          // plane e of four, entry h = replica[(4 h + e) mod 2048], 1024 entries
         for (int e = 0; e < 4; ++e)
             for (int i = 0; i < kFftN / 2; ++i) eo[e * (kFftN / 2) + i] = replica[(4 * i + e) % kFftN];
-        GPSMI_HIP(hipMemcpy(h->d_code_eo + (size_t)prn * 2 * kFftN, eo.data(), eo.size() * sizeof(float),
+        GPSMI_HIP(hipMemcpy(h->d_code_eo.p + (size_t)prn * 2 * kFftN, eo.data(), eo.size() * sizeof(float),
                             hipMemcpyHostToDevice));
     }
     if (h->span8) {                        // plane e, entry s = replica[2 (s mod cs / 2) + e], each plane twice
         std::vector<float> eo(2 * cs);
         for (int e = 0; e < 2; ++e)
             for (size_t i = 0; i < cs; ++i) eo[e * cs + i] = replica[2 * (i % (cs / 2)) + e];
-        GPSMI_HIP(hipMemcpy(h->d_code_eo + (size_t)prn * 2 * cs, eo.data(), eo.size() * sizeof(float),
+        GPSMI_HIP(hipMemcpy(h->d_code_eo.p + (size_t)prn * 2 * cs, eo.data(), eo.size() * sizeof(float),
                             hipMemcpyHostToDevice));
     }
     if (!h->general)                       // the other path needs no 2048-point spectrum
-        GPSMI_HIP(hipMemcpy(h->d_rep + (size_t)prn * kFftN, spectrum, kFftN * sizeof(float2),
+        GPSMI_HIP(hipMemcpy(h->d_rep.p + (size_t)prn * kFftN, spectrum, kFftN * sizeof(float2),
                             hipMemcpyHostToDevice));
-    if (h->big) big_replica_launch(h->stream, h->d_code, prn, (int)cs, h->d_RS, h->d_tw, h->d_twN);
-    if (h->pfa) pfa_replica_launch(h->stream, h->d_code, prn, h->d_RSp);
+    if (h->big) big_replica_launch(h->stream, h->d_code.p, prn, (int)cs, h->d_RS.p, h->d_tw.p, h->d_twN.p);
+    if (h->pfa) pfa_replica_launch(h->stream, h->d_code.p, prn, h->d_RSp.p);
     if (h->big || h->pfa) {
         GPSMI_HIP(hipGetLastError());
         GPSMI_HIP(hipStreamSynchronize(h->stream));
@@ -1678,10 +1636,10 @@ int gpsmi_trk_process_dev(gpsmi_trk* h, const void* d_iq, size_t n, gpsmi_trk_ou
     sl.run_stream = nullptr;
     // the streams of a handle are the "blocks" of one launch: stream r reads block r of d_iq and
     // owns the state rows r * max_ch ..., updated in place
-    rc = trk_launch(h, sl, d_iq, h->d_state, h->d_state, nullptr, h->rows(), h->max_ch);
+    rc = trk_launch(h, sl, d_iq, h->d_state.p, h->d_state.p, nullptr, h->rows(), h->max_ch);
     if (rc) return rc;
     if (out)
-        GPSMI_HIP(hipMemcpyAsync(out, sl.d_out, h->rows() * sizeof(gpsmi_trk_out),
+        GPSMI_HIP(hipMemcpyAsync(out, sl.d_out.p, h->rows() * sizeof(gpsmi_trk_out),
                                  hipMemcpyDeviceToHost, h->stream));
     // nothing to hand back: the block is enqueued, the state stays on the device and the
     // next call queues behind it (get_state / wait / a call with `out` synchronise)
@@ -1702,9 +1660,9 @@ int gpsmi_trk_process(gpsmi_trk* h, const float* iq, size_t n, gpsmi_trk_out* ou
                   "input must hold one block of NGPS samples per stream");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     h->main_tail = nullptr;
-    GPSMI_HIP(hipMemcpyAsync(h->d_block, iq, n * (h->iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)),
+    GPSMI_HIP(hipMemcpyAsync(h->d_block.p, iq, n * (h->iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)),
                              hipMemcpyHostToDevice, h->stream));
-    return gpsmi_trk_process_dev(h, h->d_block, n, out);
+    return gpsmi_trk_process_dev(h, h->d_block.p, n, out);
 }
 
 // One streamed step: everything gpsmi_trk_process_stream promises, made by whichever thread works
@@ -1722,17 +1680,13 @@ static int trk_stream_step(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out
             GPSMI_HIP(hipEventCreate(&h->in_done[k]));       // (also a dispatch's stop event)
         }
     }
-    if (bytes > h->stage_bytes) {
+    if (bytes > h->d_stage[0].n || bytes > h->d_stage[1].n) {
         int rc = trk_settle(h);
         if (rc) return rc;
         for (int k = 0; k < 2; ++k) {
-            if (h->d_stage[k]) GPSMI_HIP(hipFree(h->d_stage[k]));
-            h->d_stage[k] = nullptr;
             h->stage_used[k] = false;
+            if ((rc = h->d_stage[k].reserve(bytes, "gpsmi_trk staging block"))) return rc;
         }
-        h->stage_bytes = 0;
-        for (int k = 0; k < 2; ++k) GPSMI_HIP(hipMalloc(&h->d_stage[k], bytes));
-        h->stage_bytes = bytes;
     }
     int rc = trk_push_state(h);
     if (rc) return rc;
@@ -1783,9 +1737,9 @@ static int trk_stream_step(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out
         const size_t n16 = bytes / 16;
         const unsigned grid = (unsigned)((n16 + 255) / 256 < 512 ? (n16 + 255) / 256 : 512);
         hipLaunchKernelGGL(stage_copy_kernel, dim3(grid), dim3(256), 0, us,
-                           static_cast<stage_u4*>(h->d_stage[s]), static_cast<const stage_u4*>(iq_dev), n16);
+                           static_cast<stage_u4*>(static_cast<void*>(h->d_stage[s].p)), static_cast<const stage_u4*>(iq_dev), n16);
     } else {
-        GPSMI_HIP(hipMemcpyAsync(h->d_stage[s], iq, bytes, hipMemcpyHostToDevice, us));
+        GPSMI_HIP(hipMemcpyAsync(h->d_stage[s].p, iq, bytes, hipMemcpyHostToDevice, us));
     }
     if (!in_line) {
         GPSMI_HIP(hipEventRecord(h->up_done[s], h->up_stream));
@@ -1796,15 +1750,15 @@ static int trk_stream_step(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out
     sl.run_stream = nullptr;
     const int timing = h->timing;
     h->timing = 0;                          // (no kernel-timing events in a streaming loop)
-    gpsmi_trk_out* const d_out_keep = sl.d_out;
-    if (out_direct) sl.d_out = static_cast<gpsmi_trk_out*>(out_dev);
+    gpsmi_trk_out* const d_out_keep = sl.d_out.p;
+    if (out_direct) sl.d_out.p = static_cast<gpsmi_trk_out*>(out_dev);
     // the step's completion event = the completion signal of its last kernel, when nothing is
     // queued behind that kernel (no record copy, no upload-stream bookkeeping)
     const bool want_tail = in_line && (!out || out_direct);
     bool tail_used = false;
-    rc = trk_launch(h, sl, direct_in ? iq_dev : h->d_stage[s], h->d_state, h->d_state, nullptr, h->rows(), h->max_ch,
+    rc = trk_launch(h, sl, direct_in ? iq_dev : h->d_stage[s].p, h->d_state.p, h->d_state.p, nullptr, h->rows(), h->max_ch,
                     /*side_epilogue=*/false, want_tail ? h->in_done[s] : nullptr, &tail_used);
-    sl.d_out = d_out_keep;
+    sl.d_out.p = d_out_keep;
     h->timing = timing;
     if (rc) return rc;
     if (!in_line) {
@@ -1814,7 +1768,7 @@ static int trk_stream_step(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out
         h->stage_used[s] = false;           // (same stream: the next writer of this block queues behind its readers)
     }
     if (out && !out_direct)
-        GPSMI_HIP(hipMemcpyAsync(out, sl.d_out, h->rows() * sizeof(gpsmi_trk_out),
+        GPSMI_HIP(hipMemcpyAsync(out, sl.d_out.p, h->rows() * sizeof(gpsmi_trk_out),
                                  hipMemcpyDeviceToHost, h->stream));
     if (!tail_used) GPSMI_HIP(hipEventRecord(h->in_done[s], h->stream));
     h->in_pending[s] = true;
@@ -1901,10 +1855,10 @@ int gpsmi_trk_replay_load(gpsmi_trk* h, int nb, const gpsmi_trk_state* table,
     rc = trk_reserve(h, njobs);
     if (rc) return rc;
     h->main_tail = nullptr;
-    GPSMI_HIP(hipMemcpyAsync(h->d_tab_in, table, njobs * sizeof(gpsmi_trk_state),
+    GPSMI_HIP(hipMemcpyAsync(h->d_tab_in.p, table, njobs * sizeof(gpsmi_trk_state),
                              hipMemcpyHostToDevice, h->stream));
     if (delay_used)
-        GPSMI_HIP(hipMemcpyAsync(h->d_forced, delay_used, njobs * sizeof(int),
+        GPSMI_HIP(hipMemcpyAsync(h->d_forced.p, delay_used, njobs * sizeof(int),
                                  hipMemcpyHostToDevice, h->stream));
     GPSMI_HIP(hipStreamSynchronize(h->stream));
     h->replay_nb = nb;
@@ -1945,8 +1899,8 @@ int gpsmi_trk_replay_run_async(gpsmi_trk* h, const void* d_iq, int nb) {
     // (mode 2 needs the batch form of the span correlator: its dispatch carries the stamps)
     sl.timing_pending = (h->timing == 2 && !(h->mfma == 4 && nb * ((nch + kSpCh - 1) / kSpCh) > h->span_single_max))
                             ? 0 : h->timing;
-    return trk_launch(h, sl, d_iq, h->d_tab_in, h->d_tab_out,
-                      h->replay_forced ? h->d_forced : nullptr, nb * nch, nch, /*side_epilogue=*/true);
+    return trk_launch(h, sl, d_iq, h->d_tab_in.p, h->d_tab_out.p,
+                      h->replay_forced ? h->d_forced.p : nullptr, nb * nch, nch, /*side_epilogue=*/true);
 }
 
 int gpsmi_trk_wait(gpsmi_trk* h) {
@@ -2010,7 +1964,7 @@ int gpsmi_trk_replay_fetch_async(gpsmi_trk* h, gpsmi_trk_out* out, size_t n) {
         GPSMI_HIP(hipEventRecord(sl.ready, sl.run_stream ? sl.run_stream : h->stream));
         GPSMI_HIP(hipStreamWaitEvent(h->copy_stream, sl.ready, 0));
     }
-    GPSMI_HIP(hipMemcpyAsync(out, sl.d_out, n * sizeof(gpsmi_trk_out), hipMemcpyDeviceToHost,
+    GPSMI_HIP(hipMemcpyAsync(out, sl.d_out.p, n * sizeof(gpsmi_trk_out), hipMemcpyDeviceToHost,
                              h->copy_stream));
     GPSMI_HIP(hipEventRecord(sl.copied, h->copy_stream));
     sl.copy_pending = true;
@@ -2041,7 +1995,7 @@ int gpsmi_trk_replay_states(gpsmi_trk* h, gpsmi_trk_state* states, size_t n) {
     GPSMI_REQUIRE(n <= (size_t)h->replay_nb * h->max_ch,
                   "more states requested than the last replay produced");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    GPSMI_HIP(hipMemcpy(states, h->d_tab_out, n * sizeof(gpsmi_trk_state), hipMemcpyDeviceToHost));
+    GPSMI_HIP(hipMemcpy(states, h->d_tab_out.p, n * sizeof(gpsmi_trk_state), hipMemcpyDeviceToHost));
     return GPSMI_OK;
 }
 
@@ -2091,25 +2045,15 @@ int gpsmi_trk_set_streams(gpsmi_trk* h, int n_streams) {
     const size_t rows = (size_t)n_streams * h->max_ch;
     const size_t ngps = (size_t)h->cfg.n_cyc * h->cfg.code_samples;
     // new buffers first, then the swap: a failed allocation leaves the handle as it was
-    gpsmi_trk_state* d_state = nullptr;
-    float2* d_block = nullptr;
-    if (hipMalloc((void**)&d_state, rows * sizeof(gpsmi_trk_state)) != hipSuccess ||
-        hipMalloc((void**)&d_block, (size_t)n_streams * ngps * sizeof(float2)) != hipSuccess) {
-        if (d_state) (void)hipFree(d_state);
-        (void)hipGetLastError();
+    DevBuf<gpsmi_trk_state> d_state;
+    DevBuf<float2> d_block;
+    if (d_state.reserve(rows, "gpsmi_trk states") || d_block.reserve((size_t)n_streams * ngps, "gpsmi_trk input block"))
         return fail(GPSMI_E_NOMEM, "out of device memory for %d streams", n_streams);
-    }
-    rc = hipMemset(d_state, 0, rows * sizeof(gpsmi_trk_state)) == hipSuccess ? trk_reserve(h, rows)
-                                                                              : fail(GPSMI_E_HIP, "hipMemset of the state rows failed");
-    if (rc) {
-        (void)hipFree(d_state);
-        (void)hipFree(d_block);
-        return rc;
-    }
-    if (h->d_state) (void)hipFree(h->d_state);
-    if (h->d_block) (void)hipFree(h->d_block);
-    h->d_state = d_state;
-    h->d_block = d_block;
+    rc = hipMemset(d_state.p, 0, rows * sizeof(gpsmi_trk_state)) == hipSuccess ? trk_reserve(h, rows)
+                                                                                : fail(GPSMI_E_HIP, "hipMemset of the state rows failed");
+    if (rc) return rc;
+    h->d_state = std::move(d_state);
+    h->d_block = std::move(d_block);
     h->h_state.assign(rows, gpsmi_trk_state{});
     h->state_dirty_host = false;
     h->n_streams = n_streams;

@@ -34,7 +34,11 @@ extern "C" {
 #define GPSMI_E_ARG        -1   /* bad argument (null, range, size)              */
 #define GPSMI_E_HIP        -2   /* a HIP runtime call failed; see last_error     */
 #define GPSMI_E_STATE      -3   /* channel not open / handle not configured      */
-#define GPSMI_E_NOMEM      -4
+#define GPSMI_E_NOMEM      -4   /* out of host memory, or a device allocation the GPU cannot
+                                 * serve (hipErrorOutOfMemory), from EVERY entry point that
+                                 * sizes a buffer of its handle: the buffer is then absent,
+                                 * the handle stays usable and a later, smaller call works.
+                                 * (Any other failure of an allocation is GPSMI_E_HIP.)      */
 #define GPSMI_E_UNSUPPORTED -5  /* e.g. code_samples that is not a power of two  */
 #define GPSMI_E_COMM       -6   /* RCCL failure                                  */
 
