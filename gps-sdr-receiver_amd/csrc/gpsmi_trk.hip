@@ -19,7 +19,8 @@
 //                     (decodeData :1400-1401), summed per code-period window
 //                     (:1408-1420) including the partial first window and the
 //                     carry into the next block (:1403-1405, :1440).
-//   trk_epilogue_kernel  one wave per job, lane = prompt dump: window means,
+//   trk_epilogue_kernel  (gpsmi_trk_epilogue.h) one wave per job, lane = prompt
+//                     dump: window means,
 //                     amplitude statistics (:1186-1188), phaseLockedLoop
 //                     (:1215-1262) and the state update (:1178, :1205-1208).
 //
@@ -135,609 +136,7 @@ __device__ inline double fit_code_phase(double lo, double pk, double hi, int mx)
 #pragma clang fp contract(off)
 #include "gpsmi_trk_span.h"
 #include "gpsmi_trk_span8.h"
-
-namespace gpsmi {
-
-// np.mean of a float32 array of n <= 128 elements: numpy's pairwise kernel
-// (eight strided accumulators, tree-combined, tail added in order).
-__device__ inline float np_sum_f32(const float* a, int n) {
-    if (n < 8) {
-        float r = 0.f;
-        for (int i = 0; i < n; ++i) r = add_rn(r, a[i]);
-        return r;
-    }
-    float r[8];
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8)
-        for (int j = 0; j < 8; ++j) r[j] = add_rn(r[j], a[i + j]);
-    float res = add_rn(add_rn(add_rn(r[0], r[1]), add_rn(r[2], r[3])),
-                          add_rn(add_rn(r[4], r[5]), add_rn(r[6], r[7])));
-    for (; i < n; ++i) res = add_rn(res, a[i]);
-    return res;
-}
-
-// The same sum by one wave, every lane returning it: lanes 0..7 each carry one of numpy's eight
-// strided accumulators (n / 8 - 1 dependent adds instead of n), the tree ((r0+r1)+(r2+r3)) +
-// ((r4+r5)+(r6+r7)) is three DPP steps (the adds commute, so the partners of a step hold the same
-// bits), the tail is added in order.  a: LDS, n <= 128.
-__device__ __forceinline__ float np_sum_f32_wave(const float* a, int n, int lane) {
-    if (n < 8) return np_sum_f32(a, n);
-    const int j = lane & 7, body = n - (n % 8);
-    float r = a[j];
-    for (int i = 8; i < body; i += 8) r = add_rn(r, a[i + j]);
-    r = dpp_add0<0xB1, 0xF>(r);          // quad_perm [1,0,3,2]: r0+r1 | r2+r3 | r4+r5 | r6+r7
-    r = dpp_add0<0x4E, 0xF>(r);          // quad_perm [2,3,0,1]: (r0+r1)+(r2+r3) | (r4+r5)+(r6+r7)
-    r = dpp_add0<0x141, 0xF>(r);         // row_half_mirror: lane j with lane 7 - j
-    for (int i = body; i < n; ++i) r = add_rn(r, a[i]);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, r)));
-}
-
-// The per-job part of a block behind the correlator, one wave, lane i = prompt dump i.
-// Element-wise work (windows, |g|, atan, phase unwrapping by a lane prefix sum) is spread
-// over the lanes; the few float32 sums are evaluated redundantly by every lane over small
-// LDS arrays in numpy's own order (np_sum_f32), so the result does not depend on how lanes
-// are scheduled.  S[0] head, S[q+1] window q, S[nc] tail (global memory or LDS).
-__device__ __forceinline__ void epilogue_job(const gpsmi_trk_state& si, gpsmi_trk_state& so, int d,
-                                             const float2* S, const TrkParams& P, gpsmi_trk_out& o,
-                                             int lane, float* s_mag_w, float* s_dev_w, float* s_real_w,
-                                             float* s_df_w) {
-    const int cs = P.cs, nc = P.n_cyc;
-    // scalar state (same address in every lane: one broadcast load each)
-    const int nps = si.nps, df_len = si.df_len, was_locked = si.phase_locked;
-    const float freq0 = si.freq, phase0 = si.phase, omega0 = si.omega0;
-    const float prev_r = si.prev_sum_re, prev_i = si.prev_sum_im;
-    const int edge_state0 = si.edge_state;
-    const float prev_signal0 = si.prev_signal, std_dev0 = si.std_dev;
-    for (int i = lane; i < df_len; i += 64) s_df_w[i] = si.df[i];
-
-    // ---- prompt dumps: windows of decodeData (gpslib.py:1403-1420, :1440)
-    const int n1 = nps + d;
-    int nd;
-    float gr = 0.f, gi = 0.f, car_r = 0.f, car_i = 0.f;
-    int nps_new = 0;
-    if (n1 == 0) {                       // no carry, delay 0: the rows are the windows
-        nd = nc;
-        if (lane < nd) { gr = S[lane + 1].x / (float)cs; gi = S[lane + 1].y / (float)cs; }
-    } else {
-        nd = (d == 0) ? nc + 1 : nc;     // delay 0: the last code period is complete
-        if (lane == 0) {
-            gr = (prev_r + S[0].x) / (float)n1;
-            gi = (prev_i + S[0].y) / (float)n1;
-        } else if (lane < nd) {
-            gr = S[lane].x / (float)cs;
-            gi = S[lane].y / (float)cs;
-        }
-        if (d != 0) { car_r = S[nc].x; car_i = S[nc].y; nps_new = cs - d; }
-    }
-    if (lane < GPSMI_MAX_DUMPS) {
-        o.dumps[2 * lane] = lane < nd ? gr : 0.f;
-        o.dumps[2 * lane + 1] = lane < nd ? gi : 0.f;
-    }
-
-    // ---- edge scan of decodeData (gpslib.py:1394-1398, :1421-1436): while PHASE_LOCKED (the flag
-    // before this block's PLL), a dump is an edge when its sign differs from prevSign, the dump
-    // before it carried prevSign's sign (prevSign * PREV_SIGNAL > 0) and the step between the two
-    // exceeds MIN_EDGE_AMP = 3 * STD_DEV (of the block before).  prevSign only changes at an edge,
-    // so the scan jumps from edge to edge over three wave-wide bit masks (scalar arithmetic, the
-    // same in every lane): P / N = dump positive / negative, B = step large enough.
-    unsigned long long edge_mask = 0;
-    int edge_sign0 = 0, edge_state = edge_state0, ms_count = 0;
-    float prev_signal = prev_signal0;
-    if (was_locked) {
-        const unsigned long long V = (1ull << nd) - 1;             // nd <= 33
-        const float thr = mul_rn(3.0f, std_dev0);
-        const float re_up = __shfl_up(gr, 1, 64);
-        const float re_prev = lane == 0 ? prev_signal0 : re_up;
-        const unsigned long long Pm = __ballot(gr > 0.f) & V, Nm = __ballot(gr < 0.f) & V;
-        const unsigned long long Bm = __ballot(fabsf(sub_rn(gr, re_prev)) > thr) & V;
-        const unsigned long long Pp = (Pm << 1) | (prev_signal0 > 0.f ? 1ull : 0ull);   // the dump before
-        const unsigned long long Np = (Nm << 1) | (prev_signal0 < 0.f ? 1ull : 0ull);
-        unsigned long long todo = V;
-        int p = edge_state0 == 2 ? 0 : edge_state0;
-        if (edge_state0 == 0) {            // EDGES[0] == 0: every dump stores its sign until one is non-zero
-            const unsigned long long nz = Pm | Nm;
-            if (nz == 0) {
-                todo = 0;
-            } else {
-                const int j = __builtin_ctzll(nz);
-                p = ((Pm >> j) & 1) ? 1 : -1;
-                edge_sign0 = p;
-                todo = V & ~((2ull << j) - 1);
-            }
-        }
-        while (p != 0 && todo != 0) {
-            const unsigned long long cand = (p > 0 ? (Pp & ~Pm) : (Np & ~Nm)) & Bm & todo;
-            if (cand == 0) break;
-            const int i = __builtin_ctzll(cand);
-            edge_mask |= 1ull << i;
-            p = ((Pm >> i) & 1) ? 1 : (((Nm >> i) & 1) ? -1 : 0);
-            todo &= ~((2ull << i) - 1);
-        }
-        if (edge_state0 != 0 || edge_sign0 != 0) edge_state = p == 0 ? 2 : p;
-        prev_signal = __shfl(gr, nd - 1, 64);                      // PREV_SIGNAL = m.real of the last dump
-        ms_count = nd;
-    }
-
-    // ---- amplitude statistics (gpslib.py:1186-1187), float32 like numpy
-    const float mag = hypotf(gr, gi);
-    if (lane < nd) s_mag_w[lane] = mag;
-    __builtin_amdgcn_wave_barrier();
-    const float mmean = np_sum_f32_wave(s_mag_w, nd, lane) / (float)nd;
-    {
-        const float e = sub_rn(mag, mmean);
-        if (lane < nd) s_dev_w[lane] = mul_rn(e, e);
-    }
-    __builtin_amdgcn_wave_barrier();
-    const float sdev = sqrtf(np_sum_f32_wave(s_dev_w, nd, lane) / (float)nd);
-
-    // ---- phaseLockedLoop (gpslib.py:1215-1262): unwrap by a lane prefix sum
-    const float ph = atanf(gi / gr);
-    const float ph_prev = __shfl_up(ph, 1, 64);
-    float jump = 0.f;
-    if (lane >= 1 && lane < nd) {
-        const float delta = sub_rn(ph, ph_prev);
-        if (fabsf(delta) > 2.0f) jump = (delta > 0.f) ? -1.f : 1.f;
-    }
-#pragma unroll
-    for (int o2 = 1; o2 < 64; o2 <<= 1) {            // inclusive scan (small integers: exact)
-        const float v = __shfl_up(jump, o2, 64);
-        if (lane >= o2) jump += v;
-    }
-    const float real = (lane == 0) ? ph : add_rn(ph, mul_rn(jump, kPiF));
-    if (lane < nd) s_real_w[lane] = real;
-    __builtin_amdgcn_wave_barrier();
-    const float offset = np_sum_f32(s_real_w + (nd - 4), 4) / 4.0f;
-    const float pdev = np_sum_f32_wave(s_real_w, nd, lane) / (float)nd;
-    const float max_df = 20.0f / (float)P.df_no;
-    int locked = was_locked;
-    int new_len;
-    float df;
-    if (locked) {
-        const float mean_df = np_sum_f32_wave(s_df_w, df_len, lane) / (float)df_len;
-        df = add_rn(pdev, mean_df);                 // DF_GAIN2 = 1
-        if (fabsf(df) > max_df) df = (df > 0.f ? 1.f : -1.f) * max_df;
-        const int shift = df_len >= P.df_no ? 1 : 0;   // drop the oldest entry
-        new_len = df_len - shift + 1;
-        for (int i = lane; i < new_len - 1; i += 64) so.df[i] = s_df_w[i + shift];
-        if (lane == 0) so.df[new_len - 1] = df;
-    } else {
-        df = mul_rn(10.0f, pdev);                   // DF_GAIN1 = 10
-        new_len = 1;
-        if (lane == 0) so.df[0] = df;
-    }
-    if (fabsf(pdev) < 0.1f) locked = 1;
-
-    // ---- state update (gpslib.py:1178 via :1345-1346, then :1205-1208)
-    const float om = omega0 != 0.f ? omega0 : omega_of(freq0);
-    float phase = add_rn(phase0, mul_rn(om, P.t_last));
-    float mod = fmodf(phase, kTwoPiF);                 // np.remainder(phase, 2*pi)
-    if (mod != 0.f && mod < 0.f) mod = add_rn(mod, kTwoPiF);
-    phase = add_rn(mod, offset);
-    float freq = add_rn(freq0, df);
-    float om_new = 0.f;                                // FREQ is float32 from here on ...
-    if (freq > P.max_freq) { freq = P.max_freq; om_new = P.om_max; }   // ... unless clamped to
-    else if (freq < P.min_freq) { freq = P.min_freq; om_new = P.om_min; }  // a Python float
-
-    if (lane == 0) {
-        so.prn = si.prn;
-        so.delay = d;
-        so.freq = freq;
-        so.phase = phase;
-        so.phase_locked = locked;
-        so.nps = nps_new;
-        so.prev_sum_re = car_r;
-        so.prev_sum_im = car_i;
-        so.df_len = new_len;
-        so.omega0 = om_new;
-        so.edge_state = edge_state;
-        so.prev_signal = prev_signal;
-        so.std_dev = sdev;
-        so.reserved = 0;
-        o.n_dumps = nd;
-        o.first_len = (n1 == 0) ? cs : n1;
-        o.std_dev = sdev;
-        o.amplitude = mmean / sdev;
-        o.df = df;
-        o.phase_shift = offset;
-        o.freq = freq;
-        o.phase = phase;
-        o.phase_locked = locked;
-        o.nps = nps_new;
-        o.edge_mask = (uint32_t)edge_mask;
-        o.edge_mask_hi = (uint32_t)(edge_mask >> 32);
-        o.edge_sign0 = edge_sign0;
-        o.ms_count = ms_count;
-        o.reserved1 = 0;
-    }
-}
-
-// a closed channel: its state row is copied through, its record is all-zero (prn = 0); every
-// byte of an open channel's record is written by the correlation kernel and epilogue_job, so
-// the result buffer needs no memset per launch
-__device__ __forceinline__ void epilogue_closed(const gpsmi_trk_state& si, gpsmi_trk_state& so,
-                                                gpsmi_trk_out& out, bool copy, int lane, int nlanes = 64) {
-    if (copy) {
-        const int* a = reinterpret_cast<const int*>(&si);
-        int* b = reinterpret_cast<int*>(&so);
-        for (int i = lane; i < (int)(sizeof(gpsmi_trk_state) / 4); i += nlanes) b[i] = a[i];
-    }
-    int* z = reinterpret_cast<int*>(&out);
-    for (int i = lane; i < (int)(sizeof(gpsmi_trk_out) / 4); i += nlanes) z[i] = 0;
-}
-
-// One wave per job (four jobs per workgroup): the batch form.
-__global__ __launch_bounds__(256) void trk_epilogue_kernel(
-    const gpsmi_trk_state* __restrict__ st_in, gpsmi_trk_state* __restrict__ st_out,
-    const JobMid* __restrict__ mid, const float2* __restrict__ partial, TrkParams P,
-    int njobs, gpsmi_trk_out* __restrict__ out) {
-    __shared__ float s_mag[4][40], s_dev[4][40], s_real[4][40], s_df[4][GPSMI_MAX_DF];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int job = blockIdx.x * 4 + wave;
-    if (job >= njobs) return;
-    if (!mid[job].active) {
-        epilogue_closed(st_in[job], st_out[job], out[job], st_out != st_in, lane);
-        return;
-    }
-    epilogue_job(st_in[job], st_out[job], mid[job].delay_used, partial + (size_t)job * (P.n_cyc + 1), P,
-                 out[job], lane, s_mag[wave], s_dev[wave], s_real[wave], s_df[wave]);
-}
-
-// ---- The batch form with EIGHT LANES per job (round 4; option "epilogue_form" = 1, the default).
-// The wave-per-job kernel above spends a whole wave -- and, beside the code-phase correlation of the
-// next batch, a wave slot with its registers on every SIMD of a CU for the ~10 us of its dependent
-// chain -- on 33 dumps: 12288 jobs = 3072 workgroups that each keep one of that kernel's workgroups
-// off a CU while they wait for their own loads.  Here lane j of a job's eight carries the dumps
-// i = j, j + 8, j + 16, ... (slot k = i / 8; the (N_CYC + 1)-th dump is slot N_CYC / 8 of lane 0), a
-// wave is a workgroup and takes eight jobs: 1536 one-wave workgroups instead of 3072 four-wave ones,
-// an eighth of the wave slots.  The arithmetic is epilogue_job's, operation by operation:
-//   * numpy's pairwise sum IS this layout: its eight strided accumulators r[j] = a[j] + a[j + 8] + ...
-//     are the lanes' own slots added in slot order, the tree is the same three DPP steps (they stay
-//     inside a group of eight lanes), the tail element comes from lane 0's last slot;
-//   * the masks of the edge scan (dump positive / negative / step large) and the +-1 jumps of the phase
-//     unwrapping are bits i of per-job 64-bit words, OR-ed over the eight lanes by DPP; the scan is the
-//     same arithmetic on them in every lane of the group, the unwrap count of dump i is two popcounts
-//     (small integers: exact, like the float prefix sum of the wave form);
-//   * the neighbour dump (i - 1) is lane j - 1's slot k, or lane 7's slot k - 1 for j = 0: one
-//     rotation inside the group per slot.
-// Same bits as the wave form (tests/test_gpu_trk.py: both forms against each other and replay ==
-// closed loop, whose single-block epilogue is the wave form).
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_or(unsigned v) {
-    return v | (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
-}
-// OR over the eight lanes of a group, in every lane of it
-__device__ __forceinline__ unsigned long long or8(unsigned long long m) {
-    unsigned lo = (unsigned)m, hi = (unsigned)(m >> 32);
-    lo = dpp_or<0xB1>(lo); hi = dpp_or<0xB1>(hi);       // quad_perm [1,0,3,2]
-    lo = dpp_or<0x4E>(lo); hi = dpp_or<0x4E>(hi);       // quad_perm [2,3,0,1]
-    lo = dpp_or<0x141>(lo); hi = dpp_or<0x141>(hi);     // row_half_mirror
-    return ((unsigned long long)hi << 32) | lo;
-}
-// lane `l` of this lane's group of eight
-__device__ __forceinline__ float grp_get(float v, int lane, int l) { return __shfl(v, (lane & ~7) | l, 64); }
-// np.sum of a[0 .. n), element i in slot i / 8 of lane i % 8; n = 8 (K - 1) or 8 (K - 1) + 1
-template <int K>
-__device__ __forceinline__ float np_sum8(const float (&a)[K], int n, int lane) {
-    float r = a[0];
-#pragma unroll
-    for (int k = 1; k < K - 1; ++k) r = add_rn(r, a[k]);
-    r = dpp_add0<0xB1, 0xF>(r);
-    r = dpp_add0<0x4E, 0xF>(r);
-    r = dpp_add0<0x141, 0xF>(r);
-    const float t = grp_get(a[K - 1], lane, 0);
-    if (n > 8 * (K - 1)) r = add_rn(r, t);
-    return r;
-}
-// np_sum_f32_wave for a group of eight lanes (a: LDS, any n <= 128), every lane of the group returning it
-__device__ __forceinline__ float np_sum_f32_grp(const float* a, int n, int j) {
-    if (n < 8) return np_sum_f32(a, n);
-    const int body = n - (n % 8);
-    float r = a[j];
-    for (int i = 8; i < body; i += 8) r = add_rn(r, a[i + j]);
-    r = dpp_add0<0xB1, 0xF>(r);
-    r = dpp_add0<0x4E, 0xF>(r);
-    r = dpp_add0<0x141, 0xF>(r);
-    for (int i = body; i < n; ++i) r = add_rn(r, a[i]);
-    return r;
-}
-
-template <int NCV>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void trk_epilogue8_kernel(
-    const gpsmi_trk_state* __restrict__ st_in, gpsmi_trk_state* __restrict__ st_out,
-    const JobMid* __restrict__ mid, const float2* __restrict__ partial, TrkParams P,
-    int njobs, gpsmi_trk_out* __restrict__ out) {
-    constexpr int nc = NCV, K = NCV / 8 + 1, KD = (GPSMI_MAX_DUMPS + 7) / 8;
-    static_assert(NCV % 8 == 0 && NCV + 1 <= GPSMI_MAX_DUMPS, "slots of eight dumps");
-    __shared__ float s_real[8][NCV + 8], s_df[8][GPSMI_MAX_DF];
-    const int lane = threadIdx.x & 63, j = lane & 7, jw = lane >> 3;
-    const int job = blockIdx.x * 8 + jw;
-    if (job >= njobs) return;                       // (whole groups: nothing below leaves a group)
-    const gpsmi_trk_state& si = st_in[job];
-    gpsmi_trk_state& so = st_out[job];
-    gpsmi_trk_out& o = out[job];
-    const JobMid md = mid[job];
-    if (!md.active) {
-        epilogue_closed(si, so, o, st_out != st_in, j, 8);
-        return;
-    }
-    const float2* S = partial + (size_t)job * (nc + 1);
-    const int d = md.delay_used, cs = P.cs;
-    float* s_real_w = s_real[jw];
-    float* s_df_w = s_df[jw];
-    const int nps = si.nps, df_len = si.df_len, was_locked = si.phase_locked;
-    const float freq0 = si.freq, phase0 = si.phase, omega0 = si.omega0;
-    const float prev_r = si.prev_sum_re, prev_i = si.prev_sum_im;
-    const int edge_state0 = si.edge_state;
-    const float prev_signal0 = si.prev_signal, std_dev0 = si.std_dev;
-    for (int i = j; i < df_len; i += 8) s_df_w[i] = si.df[i];
-
-    // ---- prompt dumps (epilogue_job: gpslib.py:1403-1420, :1440)
-    const int n1 = nps + d;
-    int nd;
-    float gr[K], gi[K], car_r = 0.f, car_i = 0.f;
-    int nps_new = 0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) gr[k] = gi[k] = 0.f;
-    if (n1 == 0) {
-        nd = nc;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int i = j + 8 * k;
-            if (i < nd) { gr[k] = S[i + 1].x / (float)cs; gi[k] = S[i + 1].y / (float)cs; }
-        }
-    } else {
-        nd = (d == 0) ? nc + 1 : nc;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int i = j + 8 * k;
-            if (i == 0) {
-                gr[k] = (prev_r + S[0].x) / (float)n1;
-                gi[k] = (prev_i + S[0].y) / (float)n1;
-            } else if (i < nd) {
-                gr[k] = S[i].x / (float)cs;
-                gi[k] = S[i].y / (float)cs;
-            }
-        }
-        if (d != 0) { car_r = S[nc].x; car_i = S[nc].y; nps_new = cs - d; }
-    }
-#pragma unroll
-    for (int k = 0; k < KD; ++k) {
-        const int i = j + 8 * k;
-        if (i < GPSMI_MAX_DUMPS) {
-            o.dumps[2 * i] = (k < K && i < nd) ? gr[k < K ? k : 0] : 0.f;
-            o.dumps[2 * i + 1] = (k < K && i < nd) ? gi[k < K ? k : 0] : 0.f;
-        }
-    }
-    // the dump before dump i: slot k of lane j - 1, for j = 0 slot k - 1 of lane 7
-    const int rot = (lane & ~7) | ((j + 7) & 7);
-
-    // ---- edge scan (epilogue_job: gpslib.py:1394-1398, :1421-1436)
-    unsigned long long edge_mask = 0;
-    int edge_sign0 = 0, edge_state = edge_state0, ms_count = 0;
-    float prev_signal = prev_signal0;
-    if (was_locked) {
-        const unsigned long long V = (1ull << nd) - 1;
-        const float thr = mul_rn(3.0f, std_dev0);
-        unsigned long long Pm = 0, Nm = 0, Bm = 0;
-        float before = prev_signal0;                   // lane 0: slot k - 1 of lane 7
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int i = j + 8 * k;
-            const float up = __shfl(gr[k], rot, 64);
-            const float re_prev = j == 0 ? before : up;
-            before = up;
-            if (i < nd) {
-                if (gr[k] > 0.f) Pm |= 1ull << i;
-                if (gr[k] < 0.f) Nm |= 1ull << i;
-                if (fabsf(sub_rn(gr[k], re_prev)) > thr) Bm |= 1ull << i;
-            }
-        }
-        Pm = or8(Pm); Nm = or8(Nm); Bm = or8(Bm);
-        const unsigned long long Pp = (Pm << 1) | (prev_signal0 > 0.f ? 1ull : 0ull);
-        const unsigned long long Np = (Nm << 1) | (prev_signal0 < 0.f ? 1ull : 0ull);
-        unsigned long long todo = V;
-        int p = edge_state0 == 2 ? 0 : edge_state0;
-        if (edge_state0 == 0) {
-            const unsigned long long nz = Pm | Nm;
-            if (nz == 0) {
-                todo = 0;
-            } else {
-                const int q = __builtin_ctzll(nz);
-                p = ((Pm >> q) & 1) ? 1 : -1;
-                edge_sign0 = p;
-                todo = V & ~((2ull << q) - 1);
-            }
-        }
-        while (p != 0 && todo != 0) {
-            const unsigned long long cand = (p > 0 ? (Pp & ~Pm) : (Np & ~Nm)) & Bm & todo;
-            if (cand == 0) break;
-            const int i = __builtin_ctzll(cand);
-            edge_mask |= 1ull << i;
-            p = ((Pm >> i) & 1) ? 1 : (((Nm >> i) & 1) ? -1 : 0);
-            todo &= ~((2ull << i) - 1);
-        }
-        if (edge_state0 != 0 || edge_sign0 != 0) edge_state = p == 0 ? 2 : p;
-        const float last_full = grp_get(gr[K - 2], lane, 7), last_extra = grp_get(gr[K - 1], lane, 0);
-        prev_signal = nd == nc + 1 ? last_extra : last_full;       // the real part of dump nd - 1
-        ms_count = nd;
-    }
-
-    // ---- amplitude statistics (epilogue_job: gpslib.py:1186-1187)
-    float mag[K], dev[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) mag[k] = hypotf(gr[k], gi[k]);
-    const float mmean = np_sum8<K>(mag, nd, lane) / (float)nd;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const float e = sub_rn(mag[k], mmean);
-        dev[k] = mul_rn(e, e);
-    }
-    const float sdev = sqrtf(np_sum8<K>(dev, nd, lane) / (float)nd);
-
-    // ---- phaseLockedLoop (epilogue_job: gpslib.py:1215-1262)
-    float ph[K], real[K];
-    unsigned long long Jp = 0, Jn = 0;                 // dumps whose unwrap step is +1 / -1
-    {
-        float before = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int i = j + 8 * k;
-            ph[k] = atanf(gi[k] / gr[k]);
-            const float up = __shfl(ph[k], rot, 64);
-            const float ph_prev = j == 0 ? before : up;
-            before = up;
-            if (i >= 1 && i < nd) {
-                const float delta = sub_rn(ph[k], ph_prev);
-                if (fabsf(delta) > 2.0f) {
-                    if (delta > 0.f) Jn |= 1ull << i;
-                    else Jp |= 1ull << i;
-                }
-            }
-        }
-    }
-    Jp = or8(Jp); Jn = or8(Jn);
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int i = j + 8 * k;
-        const unsigned long long upto = (2ull << i) - 1;               // dumps 0 .. i
-        const float jump = (float)(__builtin_popcountll(Jp & upto) - __builtin_popcountll(Jn & upto));
-        real[k] = (i == 0) ? ph[k] : add_rn(ph[k], mul_rn(jump, kPiF));
-        if (i < nd) s_real_w[i] = real[k];
-    }
-    __builtin_amdgcn_wave_barrier();
-    const float offset = np_sum_f32(s_real_w + (nd - 4), 4) / 4.0f;
-    const float pdev = np_sum8<K>(real, nd, lane) / (float)nd;
-    const float max_df = 20.0f / (float)P.df_no;
-    int locked = was_locked;
-    int new_len;
-    float df;
-    if (locked) {
-        const float mean_df = np_sum_f32_grp(s_df_w, df_len, j) / (float)df_len;
-        df = add_rn(pdev, mean_df);
-        if (fabsf(df) > max_df) df = (df > 0.f ? 1.f : -1.f) * max_df;
-        const int shift = df_len >= P.df_no ? 1 : 0;
-        new_len = df_len - shift + 1;
-        for (int i = j; i < new_len - 1; i += 8) so.df[i] = s_df_w[i + shift];
-        if (j == 0) so.df[new_len - 1] = df;
-    } else {
-        df = mul_rn(10.0f, pdev);
-        new_len = 1;
-        if (j == 0) so.df[0] = df;
-    }
-    if (fabsf(pdev) < 0.1f) locked = 1;
-
-    // ---- state update (epilogue_job: gpslib.py:1178 via :1345-1346, then :1205-1208)
-    const float om = omega0 != 0.f ? omega0 : omega_of(freq0);
-    float phase = add_rn(phase0, mul_rn(om, P.t_last));
-    float mod = fmodf(phase, kTwoPiF);
-    if (mod != 0.f && mod < 0.f) mod = add_rn(mod, kTwoPiF);
-    phase = add_rn(mod, offset);
-    float freq = add_rn(freq0, df);
-    float om_new = 0.f;
-    if (freq > P.max_freq) { freq = P.max_freq; om_new = P.om_max; }
-    else if (freq < P.min_freq) { freq = P.min_freq; om_new = P.om_min; }
-
-    if (j == 0) {
-        so.prn = si.prn;
-        so.delay = d;
-        so.freq = freq;
-        so.phase = phase;
-        so.phase_locked = locked;
-        so.nps = nps_new;
-        so.prev_sum_re = car_r;
-        so.prev_sum_im = car_i;
-        so.df_len = new_len;
-        so.omega0 = om_new;
-        so.edge_state = edge_state;
-        so.prev_signal = prev_signal;
-        so.std_dev = sdev;
-        so.reserved = 0;
-        o.n_dumps = nd;
-        o.first_len = (n1 == 0) ? cs : n1;
-        o.std_dev = sdev;
-        o.amplitude = mmean / sdev;
-        o.df = df;
-        o.phase_shift = offset;
-        o.freq = freq;
-        o.phase = phase;
-        o.phase_locked = locked;
-        o.nps = nps_new;
-        o.edge_mask = (uint32_t)edge_mask;
-        o.edge_mask_hi = (uint32_t)(edge_mask >> 32);
-        o.edge_sign0 = edge_sign0;
-        o.ms_count = ms_count;
-        o.reserved1 = 0;
-    }
-}
-
-// One workgroup per job: behind the single-block form of the span correlator (the closed
-// loop).  The four waves add up the spans of one quarter each (independent loads, issued
-// together), wave 0 adds the quarters in their fixed order, forms the windows and runs the
-// per-job part.
-template <int NC>
-__global__ __launch_bounds__(256) void trk_epilogue_span_kernel(
-    const gpsmi_trk_state* __restrict__ st_in, gpsmi_trk_state* __restrict__ st_out,
-    const JobMid* __restrict__ mid, const float* __restrict__ rec, int ng_span, TrkParams P,
-    int njobs, gpsmi_trk_out* __restrict__ out) {
-    __shared__ float s_mag[40], s_dev[40], s_real[40], s_df[GPSMI_MAX_DF];
-    __shared__ float q_hi[4][64], q_lo[4][64], s_hi[64], s_lo[64];
-    __shared__ float2 s_S[GPSMI_MAX_DUMPS];
-    __shared__ gpsmi_trk_state s_si;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int job = blockIdx.x;
-    // the state row is requested with the job entry (one trip to memory for both) and waits in
-    // LDS for the per-job part
-    if (wave == 0) {
-        const int* a = reinterpret_cast<const int*>(&st_in[job]);
-        int* sa = reinterpret_cast<int*>(&s_si);
-        for (int i = lane; i < (int)(sizeof(gpsmi_trk_state) / 4); i += 64) sa[i] = a[i];
-    }
-    const JobMid md = mid[job];
-    if (!md.active) {
-        if (wave == 0) epilogue_closed(st_in[job], st_out[job], out[job], st_out != st_in, lane);
-        return;
-    }
-    span_collect_quarter<1, NC>(rec, ng_span, job / P.nch, job % P.nch, md.delay_used, lane, wave,
-                                q_hi[wave][lane], q_lo[wave][lane]);
-    __syncthreads();
-    if (wave != 0) return;
-    float h = 0.f, l = 0.f;
-#pragma unroll
-    for (int Q = 0; Q < 4; ++Q) { h += q_hi[Q][lane]; l += q_lo[Q][lane]; }
-    s_hi[lane] = h;
-    s_lo[lane] = l;
-    __builtin_amdgcn_wave_barrier();
-    span_windows<NC>(s_hi, s_lo, md.om, lane, s_S);
-    __builtin_amdgcn_wave_barrier();
-    epilogue_job(s_si, st_out[job], md.delay_used, s_S, P, out[job], lane, s_mag, s_dev, s_real, s_df);
-}
-
-// One wave per job (four jobs per workgroup) behind trk_span8_kernel: the wave adds up the 11 range
-// records of its job (span8_collect) and runs the per-job part on the windows: no separate collect
-// launch, no round trip of the window sums through memory.
-__global__ __launch_bounds__(256) void trk_epilogue_span8_kernel(
-    const gpsmi_trk_state* __restrict__ st_in, gpsmi_trk_state* __restrict__ st_out,
-    const JobMid* __restrict__ mid, const float* __restrict__ rec, int ngroups, TrkParams P, int njobs,
-    gpsmi_trk_out* __restrict__ out) {
-    __shared__ float s_mag[4][40], s_dev[4][40], s_real[4][40], s_df[4][GPSMI_MAX_DF];
-    __shared__ float s_hi[4][16], s_lo[4][16];
-    __shared__ float2 s_S[4][GPSMI_MAX_DUMPS];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int job = blockIdx.x * 4 + wave;
-    if (job >= njobs) return;
-    const JobMid md = mid[job];
-    if (!md.active) {
-        epilogue_closed(st_in[job], st_out[job], out[job], st_out != st_in, lane);
-        return;
-    }
-    span8_collect(rec, ngroups, job / P.nch, job % P.nch, md.delay_used, md.om, lane, s_hi[wave], s_lo[wave],
-                  s_S[wave]);
-    epilogue_job(st_in[job], st_out[job], md.delay_used, s_S[wave], P, out[job], lane, s_mag[wave], s_dev[wave],
-                 s_real[wave], s_df[wave]);
-}
-
-}  // namespace gpsmi
+#include "gpsmi_trk_epilogue.h"
 
 namespace gpsmi {
 // Upload of a streamed block by the GPU itself: the workgroups read the page-locked host block
@@ -925,6 +324,20 @@ static int trk_reserve(gpsmi_trk* h, size_t njobs) {
     return rc;
 }
 
+// The last kernel of a launch: with `tail_stop`, the event carries the dispatch's own completion
+// signal (and stop_used says so); else a plain launch.  The arguments are converted to the kernel's
+// parameter types here (hipExtLaunchKernelGGL takes no others).
+template <typename... KArgs, typename... Args>
+static void launch_tail(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t stream, hipEvent_t tail_stop,
+                        bool& stop_used, Args... args) {
+    if (tail_stop) {
+        hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, nullptr, tail_stop, 0, static_cast<KArgs>(args)...);
+        stop_used = true;
+    } else {
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, static_cast<KArgs>(args)...);
+    }
+}
+
 // the three kernels over njobs jobs on the handle's stream, events around them
 static int trk_launch(gpsmi_trk* h, gpsmi_trk::Slot& sl, const void* d_iq_v,
                       const gpsmi_trk_state* st_in, gpsmi_trk_state* st_out, const int* forced,
@@ -1051,19 +464,10 @@ static int trk_launch(gpsmi_trk* h, gpsmi_trk::Slot& sl, const void* d_iq_v,
     } else {                               // the vector correlator (other block / code lengths)
         const dim3 grid(sgrid.x, h->nchunks), block(kStreamThreads);
         float2* pdst = h->nchunks > 1 ? h->d_partial_g.p : sl.d_partial.p;
-#define GPSMI_LAUNCH_STREAM(NC, POW2, J)                                                        \
-    hipLaunchKernelGGL((trk_stream_kernel<NC, POW2, J>), grid, block, 0, rs, d_iq, st_in, \
-                       sl.d_mid.p, h->d_code.p, P, ngroups, nblocks, pdst)
-#define GPSMI_LAUNCH_STREAM_NC(POW2, J)                 \
-    do {                                                \
-        if (P.n_cyc == 32) GPSMI_LAUNCH_STREAM(32, POW2, J);      \
-        else if (P.n_cyc == 16) GPSMI_LAUNCH_STREAM(16, POW2, J); \
-        else GPSMI_LAUNCH_STREAM(8, POW2, J);           \
-    } while (0)
-        if (h->general) GPSMI_LAUNCH_STREAM_NC(false, 8);
-        else GPSMI_LAUNCH_STREAM_NC(true, 8);
-#undef GPSMI_LAUNCH_STREAM_NC
-#undef GPSMI_LAUNCH_STREAM
+        with_value<32, 16, 8>(P.n_cyc, [&](auto ncv) { with_value<1, 0>(h->general ? 0 : 1, [&](auto pow2) {
+            hipLaunchKernelGGL((trk_stream_kernel<decltype(ncv)::value, decltype(pow2)::value != 0, 8>), grid, block, 0,
+                               rs, d_iq, st_in, sl.d_mid.p, h->d_code.p, P, ngroups, nblocks, pdst);
+        }); });
         if (h->nchunks > 1) {
             const int per_job = P.n_cyc + 1;
             hipLaunchKernelGGL(trk_partial_reduce_kernel, dim3((njobs * per_job + 255) / 256),
@@ -1081,58 +485,23 @@ static int trk_launch(gpsmi_trk* h, gpsmi_trk::Slot& sl, const void* d_iq_v,
         h->main_tail = sl.corr_done;          // (gpsmi_acq_after_trk orders the search behind this one)
         GPSMI_HIP(hipStreamWaitEvent(es, sl.corr_done, 0));
     }
-    const gpsmi_trk_state* c_in = st_in;
-    const JobMid* c_mid = sl.d_mid.p;
-    const float* c_rec = sl.d_rec.p;
-    const float2* c_partial = sl.d_partial.p;
     bool stop_used = false;
-#define GPSMI_LAUNCH_EPI_SPAN(NCV)                                                                         \
-    do {                                                                                                  \
-        if (tail_stop) {                                                                                  \
-            hipExtLaunchKernelGGL(trk_epilogue_span_kernel<NCV>, dim3(njobs), dim3(256), 0, es, nullptr,  \
-                                  tail_stop, 0, c_in, st_out, c_mid, c_rec, ng_span, P, njobs, sl.d_out.p); \
-            stop_used = true;                                                                             \
-        } else {                                                                                          \
-            hipLaunchKernelGGL(trk_epilogue_span_kernel<NCV>, dim3(njobs), dim3(256), 0, es, c_in,        \
-                               st_out, c_mid, c_rec, ng_span, P, njobs, sl.d_out.p);                        \
-        }                                                                                                 \
-    } while (0)
-    if (h->span8)
+    if (h->span8)                            // (its epilogue does not take tail_stop)
         hipLaunchKernelGGL(trk_epilogue_span8_kernel, dim3((njobs + 3) / 4), dim3(256), 0, es, st_in,
                            st_out, sl.d_mid.p, sl.d_rec.p, ng_span, P, njobs, sl.d_out.p);
-    else if (span_single && P.n_cyc == 32)
-        GPSMI_LAUNCH_EPI_SPAN(32);
-    else if (span_single && P.n_cyc == 16)
-        GPSMI_LAUNCH_EPI_SPAN(16);
     else if (span_single)
-        GPSMI_LAUNCH_EPI_SPAN(8);
-    else if (h->epilogue_form == 0) {        // a wave per job
-        if (tail_stop) {
-            hipExtLaunchKernelGGL(trk_epilogue_kernel, dim3((njobs + 3) / 4), dim3(256), 0, es, nullptr,
-                                  tail_stop, 0, c_in, st_out, c_mid, c_partial, P, njobs, sl.d_out.p);
-            stop_used = true;
-        } else
-            hipLaunchKernelGGL(trk_epilogue_kernel, dim3((njobs + 3) / 4), dim3(256), 0, es, st_in,
-                               st_out, sl.d_mid.p, sl.d_partial.p, P, njobs, sl.d_out.p);
-    } else {                                 // eight lanes per job (the default)
-#define GPSMI_LAUNCH_EPI8(NCV)                                                                           \
-    do {                                                                                                \
-        if (tail_stop) {                                                                                \
-            hipExtLaunchKernelGGL(trk_epilogue8_kernel<NCV>, dim3((njobs + 7) / 8), dim3(64), 0, es,    \
-                                  nullptr, tail_stop, 0, c_in, st_out, c_mid, c_partial, P, njobs,      \
-                                  sl.d_out.p);                                                            \
-            stop_used = true;                                                                           \
-        } else {                                                                                        \
-            hipLaunchKernelGGL(trk_epilogue8_kernel<NCV>, dim3((njobs + 7) / 8), dim3(64), 0, es, c_in, \
-                               st_out, c_mid, c_partial, P, njobs, sl.d_out.p);                           \
-        }                                                                                               \
-    } while (0)
-        if (P.n_cyc == 32) GPSMI_LAUNCH_EPI8(32);
-        else if (P.n_cyc == 16) GPSMI_LAUNCH_EPI8(16);
-        else GPSMI_LAUNCH_EPI8(8);
-#undef GPSMI_LAUNCH_EPI8
-    }
-#undef GPSMI_LAUNCH_EPI_SPAN
+        with_value<32, 16, 8>(P.n_cyc, [&](auto ncv) {
+            launch_tail(trk_epilogue_span_kernel<decltype(ncv)::value>, dim3(njobs), dim3(256), es, tail_stop,
+                        stop_used, st_in, st_out, sl.d_mid.p, sl.d_rec.p, ng_span, P, njobs, sl.d_out.p);
+        });
+    else if (h->epilogue_form == 0)          // a wave per job
+        launch_tail(trk_epilogue_kernel, dim3((njobs + 3) / 4), dim3(256), es, tail_stop, stop_used, st_in,
+                    st_out, sl.d_mid.p, sl.d_partial.p, P, njobs, sl.d_out.p);
+    else                                     // eight lanes per job (the default)
+        with_value<32, 16, 8>(P.n_cyc, [&](auto ncv) {
+            launch_tail(trk_epilogue8_kernel<decltype(ncv)::value>, dim3((njobs + 7) / 8), dim3(64), es, tail_stop,
+                        stop_used, st_in, st_out, sl.d_mid.p, sl.d_partial.p, P, njobs, sl.d_out.p);
+        });
     if (tail_stop_used) *tail_stop_used = stop_used;
     GPSMI_HIP(hipGetLastError());
     if (timed) GPSMI_HIP(hipEventRecord(sl.ev[3], es));

@@ -480,8 +480,11 @@ typedef struct gpsmi_trk_state {
     float   df[GPSMI_MAX_DF];/* DF, oldest first                               */
     /* decodeData's edge scan (gpslib.py:1394-1398, :1421-1436), carried on the device   */
     int32_t edge_state;      /* 0: EDGES[0] not set yet; +1 / -1: prevSign; 2: prevSign */
-                             /*   is 0 (np.sign of an exact zero: no further edge until */
-                             /*   erasePrevData, as in the reference)                   */
+                             /*   is 0 (np.sign of an exact zero): no further edge until */
+                             /*   erasePrevData.  A deviation: the reference re-derives  */
+                             /*   prevSign at the start of every decodeData call, so it  */
+                             /*   finds edges again from the next block on.  Reachable   */
+                             /*   only when a dump's real part is exactly 0.             */
     float   prev_signal;     /* PREV_SIGNAL (:1434), the real part of the last dump      */
     float   std_dev;         /* STD_DEV before the block: MIN_EDGE_AMP = 3*STD_DEV       */
     int32_t reserved;        /* 0                                                        */

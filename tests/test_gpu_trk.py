@@ -272,15 +272,10 @@ def test_batch_epilogue_forms_reproduce_closed_loop(closed_loop, form):
             assert nxt[i, c]['df'][:n].tobytes() == states[i + 1, c]['df'][:n].tobytes()
 
 
-@pytest.mark.parametrize('n_cyc', [32, 16, 8])
-def test_batch_epilogue_forms_agree_on_random_states(closed_loop, n_cyc):
-    """Differential test of the two batch epilogues (option "epilogue_form") on state rows the closed
-    loop does not visit often: forced delay 0 with and without a carry (33 dumps / the rows are the
-    windows), every edge_state, locked and unlocked, drift lists of every length 1 .. 32, both signs
-    of PREV_SIGNAL, FREQ at and beyond the clamp.  Same IQ, same table: records bytewise, next states
-    field by field.  The other block lengths (five / three / two dumps per lane) take the first N_CYC
-    code periods of the same blocks."""
-    from gpsmi.engine import TrkEngine, DeviceBuffer, STATE_DTYPE, Config
+def random_state_runs(closed_loop, n_cyc):
+    """The inputs of test_batch_epilogue_forms_agree_on_random_states through both batch epilogues:
+    [(records, next states) of form 0, of form 1]."""
+    from gpsmi.engine import TrkEngine, DeviceBuffer, Config
     _, outs, states, blocks = closed_loop
     nb, nch = outs.shape
     blocks = [np.ascontiguousarray(b[:n_cyc * 2048]) for b in blocks]
@@ -327,17 +322,42 @@ def test_batch_epilogue_forms_agree_on_random_states(closed_loop, n_cyc):
         eng.close()
         got.append((rep, nxt))
     buf.free()
-    (r0, n0), (r1, n1) = got
+    return got
+
+
+def _assert_states_equal(a, b):
+    """Next-state rows field by field, the drift list up to its length."""
+    for k in a.dtype.names:
+        if k != 'df':
+            assert a[k].tobytes() == b[k].tobytes(), k
+    for idx in np.ndindex(a.shape):
+        n = int(a[idx]['df_len'])
+        assert a[idx]['df'][:n].tobytes() == b[idx]['df'][:n].tobytes(), idx
+
+
+@pytest.mark.parametrize('n_cyc', [32, 16, 8])
+def test_batch_epilogue_forms_agree_on_random_states(closed_loop, n_cyc):
+    """The two batch epilogues (option "epilogue_form") on state rows the closed loop does not visit
+    often: forced delay 0 with and without a carry (33 dumps / the rows are the windows), every
+    edge_state, locked and unlocked, drift lists of every length 1 .. 32, both signs of PREV_SIGNAL
+    and zero, FREQ at and beyond the clamp.  Same IQ, same table: records bytewise, next states field
+    by field -- against each other, and both against tests/golden/epilogue_pin.npz, what the wave
+    form computed on these inputs before the two forms came to share their per-job arithmetic
+    (tools/record_epilogue_pin.py; the first blocks of each run).  The other block lengths (five /
+    three / two dumps per lane) take the first N_CYC code periods of the same blocks."""
+    from gpsmi.engine import STATE_DTYPE
+    (r0, n0), (r1, n1) = random_state_runs(closed_loop, n_cyc)
     assert set(np.unique(r0['n_dumps'])) >= {n_cyc, n_cyc + 1}
     assert r0.tobytes() == r1.tobytes()
-    for k in STATE_DTYPE.names:
-        if k == 'df':
-            continue
-        assert n0[k].tobytes() == n1[k].tobytes(), k
-    for i in range(nb):
-        for c in range(nch):
-            n = int(n0[i, c]['df_len'])
-            assert n0[i, c]['df'][:n].tobytes() == n1[i, c]['df'][:n].tobytes(), (i, c)
+    assert n0.dtype == STATE_DTYPE
+    _assert_states_equal(n0, n1)
+    pin = load_golden('epilogue_pin.npz')
+    rec, st = pin[f'rec{n_cyc}'], pin[f'st{n_cyc}']
+    npin = len(rec)
+    assert npin >= 8 and rec.dtype == r0.dtype and st.dtype == n0.dtype
+    for r, n in ((r0, n0), (r1, n1)):
+        assert r[:npin].tobytes() == rec.tobytes()
+        _assert_states_equal(st, n[:npin])
 
 
 def test_replay_without_forced_delay(closed_loop):

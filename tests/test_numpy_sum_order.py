@@ -1,5 +1,5 @@
 """The order of numpy's float32 sums, which the device epilogues restate (np_sum_f32, np_sum_f32_wave,
-np_sum8 in gps-sdr-receiver_amd/csrc/gpsmi_trk.hip): for 8 <= n < 128 elements numpy adds eight strided
+np_sum8 in gps-sdr-receiver_amd/csrc/gpsmi_trk_epilogue.h): for 8 <= n < 128 elements numpy adds eight strided
 accumulators r[j] = a[j] + a[j + 8] + ..., combines them as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7))
 and adds the n % 8 tail elements in order; below eight elements it adds in order.  The reference takes
 np.mean / np.std of 32 or 33 float32 values per block and channel (gpslib.py:1186-1187, :1215-1262); the
