@@ -833,7 +833,8 @@ def test_other_block_lengths_match_the_oracle(n_cyc):
 def test_other_block_lengths_forced_delays_agree_with_the_vector_correlator(n_cyc):
     """Every residue mod 4 and every tile / quarter / period edge of the delay through the span
     correlator at N_CYC = 16 / 8 (batch form == single form bytewise), and against the vector
-    correlator (an independent kernel) within the reference tolerance."""
+    correlator (an independent kernel) within the reference tolerance.  (Each correlator against
+    a float64 reference on these edges: tests/test_gpu_trk_dumps.py.)"""
     from gpsmi import engine as E
     from gpsmi import synth
     from gpsmi.engine import Config, TrkEngine, DeviceBuffer, STATE_DTYPE
@@ -1050,7 +1051,8 @@ def test_forced_delays_at_every_edge_agree_across_correlators(closed_loop, monke
     through replay on the recorded states.  (a) The batch form of the kernel (160 blocks in one
     launch) and its single-block form (the same rows eight at a time) give the same bytes;
     (b) the vector correlator (GPSMI_STREAM_MFMA=0: an independent kernel, float32 sums in
-    another order) agrees within the reference tolerance, integer fields exactly."""
+    another order) agrees within the reference tolerance, integer fields exactly.  (Each correlator
+    against a float64 reference on these edges: tests/test_gpu_trk_dumps.py.)"""
     from gpsmi.engine import TrkEngine, DeviceBuffer
     eng, outs, states, blocks = closed_loop
     nb0, nch = outs.shape
