@@ -49,7 +49,7 @@ CARRIERS = ((3, -5000.0), (8, 5000.0), (11, 0.0))
 _CACHE = {}
 
 
-def _memo(key, make):
+def memo(key, make):
     if key not in _CACHE:
         _CACHE[key] = make()
     return _CACHE[key]
@@ -78,7 +78,7 @@ def boundary_blocks(cs, n_cyc):
         for x in c64:
             assert min(np.abs(x.real).min(), np.abs(x.imag).min()) >= 0.49
         return c64, raws
-    return _memo(('boundary', cs, n_cyc), make)
+    return memo(('boundary', cs, n_cyc), make)
 
 
 def signal_blocks(cs, n_cyc):
@@ -92,7 +92,7 @@ def signal_blocks(cs, n_cyc):
                          seed=5200 + n_cyc, code_samples=cs, n_cyc=n_cyc)
         raws = [sc.block_raw(b) for b in range(NB_SMALL)]
         return [cr.decode_u8(r) for r in raws], raws, sc
-    return _memo(('signal', cs, n_cyc), make)
+    return memo(('signal', cs, n_cyc), make)
 
 
 def template_row():
@@ -104,7 +104,7 @@ def template_row():
     return row
 
 
-def _empty_table(rows):
+def empty_table(rows):
     from gpsmi.engine import STATE_DTYPE
     table = np.empty((rows, NCH), STATE_DTYPE)
     table[...] = template_row()
@@ -141,7 +141,7 @@ def edge_table(cs, n_cyc):
     def make():
         edges = EDGES[cs]
         assert all(0 <= e < cs for e in edges) and len(set(edges)) == len(edges)
-        table, forced = _empty_table(len(edges))
+        table, forced = empty_table(len(edges))
         rng = np.random.default_rng([cs, n_cyc, 1])
         for i in range(len(edges)):
             for c in LIVE:
@@ -160,7 +160,7 @@ def edge_table(cs, n_cyc):
         for c in LIVE:
             assert set(forced[:, c]) == set(edges)
         return table, forced
-    return _memo(('edge', cs, n_cyc), make)
+    return memo(('edge', cs, n_cyc), make)
 
 
 CARRY_KINDS = 6
@@ -177,7 +177,7 @@ def carry_table(cs, n_cyc):
       5  nps and d anywhere
     with a drawn prev_sum of a few units wherever nps > 0."""
     def make():
-        table, forced = _empty_table(NB_SMALL)
+        table, forced = empty_table(NB_SMALL)
         rng = np.random.default_rng([cs, n_cyc, 2])
         for i in range(NB_SMALL):
             for c in LIVE:
@@ -203,7 +203,7 @@ def carry_table(cs, n_cyc):
                 forced[i, c] = d
                 table[i, c] = st
         return table, forced
-    return _memo(('carry', cs, n_cyc), make)
+    return memo(('carry', cs, n_cyc), make)
 
 
 def signal_table(cs, n_cyc):
@@ -213,7 +213,7 @@ def signal_table(cs, n_cyc):
     def make():
         from test_gpu_trk_corr import SATS
         _, _, sc = signal_blocks(cs, n_cyc)
-        table, forced = _empty_table(NB_SMALL)
+        table, forced = empty_table(NB_SMALL)
         rng = np.random.default_rng([cs, n_cyc, 3])
         offs = np.zeros((NB_SMALL, NCH), np.int32)
         for i in range(NB_SMALL):
@@ -233,7 +233,7 @@ def signal_table(cs, n_cyc):
                 table[i, c] = st
         table['prn'][:, list(CLOSED)] = 0
         return table, forced, offs
-    return _memo(('signal table', cs, n_cyc), make)
+    return memo(('signal table', cs, n_cyc), make)
 
 
 def references(blocks, table, forced, cs, n_cyc, key):
@@ -253,7 +253,35 @@ def references(blocks, table, forced, cs, n_cyc, key):
                     ref[i, c] = dr.dump_ref(*args, wiped=wiped[0])
                     orc[i, c] = dr.oracle_record(*args, wiped=wiped[1])
         return ref, orc
-    return _memo(('references', key, cs, n_cyc), make)
+    return memo(('references', key, cs, n_cyc), make)
+
+
+def engine(cs, n_cyc, family, prns):
+    """A TrkEngine whose prompt correlator is the family asked for ('vector', or the span / span8
+    correlator the handle chooses by default), asserted through get_option."""
+    from gpsmi import engine as E
+    cfg = E.Config(code_samples=cs, n_cyc=n_cyc)
+    if family != 'vector':
+        eng = E.TrkEngine(cfg, max_ch=NCH, prns=prns)
+        assert eng.get_option('correlator') == 1, (cs, n_cyc, family)
+        return eng
+    E.set_default('correlator', 0)
+    try:
+        eng = E.TrkEngine(cfg, max_ch=NCH, prns=prns)
+    finally:
+        E.clear_default('correlator')
+    assert eng.get_option('correlator') == 0, (cs, n_cyc)
+    return eng
+
+
+def replay(eng, buf, nbytes, table, forced):
+    """The table in launches of at most 16 rows (row i reads block i % 16 of the buffer)."""
+    outs, nxts = [], []
+    for r0 in range(0, table.shape[0], NB):
+        nb = min(NB, table.shape[0] - r0)
+        outs.append(eng.replay(buf.ptr, nb, table[r0:r0 + nb], forced[r0:r0 + nb]))
+        nxts.append(eng.replay_states(nb))
+    return np.concatenate(outs), np.concatenate(nxts)
 
 
 def live(a):

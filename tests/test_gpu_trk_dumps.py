@@ -33,32 +33,6 @@ FORMS = {2048: (('span', 'single', 'c64'), ('span', 'single', 'u8'), ('span', 'b
 _RUNS = {}
 
 
-def _engine(cs, n_cyc, family, prns):
-    from gpsmi import engine as E
-    cfg = E.Config(code_samples=cs, n_cyc=n_cyc)
-    if family != 'vector':
-        eng = E.TrkEngine(cfg, max_ch=ds.NCH, prns=prns)
-        assert eng.get_option('correlator') == 1, (cs, n_cyc, family)
-        return eng
-    E.set_default('correlator', 0)
-    try:
-        eng = E.TrkEngine(cfg, max_ch=ds.NCH, prns=prns)
-    finally:
-        E.clear_default('correlator')
-    assert eng.get_option('correlator') == 0, (cs, n_cyc)
-    return eng
-
-
-def _replay(eng, buf, nbytes, table, forced):
-    """The table in launches of at most 16 rows (row i reads block i % 16 of the buffer)."""
-    outs, nxts = [], []
-    for r0 in range(0, table.shape[0], ds.NB):
-        nb = min(ds.NB, table.shape[0] - r0)
-        outs.append(eng.replay(buf.ptr, nb, table[r0:r0 + nb], forced[r0:r0 + nb]))
-        nxts.append(eng.replay_states(nb))
-    return np.concatenate(outs), np.concatenate(nxts)
-
-
 def _run(kind, cs, n_cyc):
     """{(family, form, format): (records, next states)} of a table through every form, once."""
     key = (kind, cs, n_cyc)
@@ -76,7 +50,7 @@ def _run(kind, cs, n_cyc):
                 bufs[fmt].upload(np.stack(src))
         for family, form, fmt in FORMS[cs]:
             if family not in engines:
-                engines[family] = _engine(cs, n_cyc, family, prns)
+                engines[family] = ds.engine(cs, n_cyc, family, prns)
             eng = engines[family]
             if family == 'span':
                 if form == 'batch':                          # (the single-block form: the default threshold)
@@ -85,7 +59,7 @@ def _run(kind, cs, n_cyc):
                 assert single == (form == 'single'), (form, units)
                 eng.set_input_format(fmt == 'u8')
             src = c64 if fmt == 'c64' else raws
-            got[family, form, fmt] = _replay(eng, bufs[fmt], src[0].nbytes, table, forced)
+            got[family, form, fmt] = ds.replay(eng, bufs[fmt], src[0].nbytes, table, forced)
     finally:
         for b in bufs.values():
             b.free()
