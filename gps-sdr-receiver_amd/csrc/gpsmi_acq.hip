@@ -385,9 +385,6 @@ namespace gpsmi { HandleSync trk_sync(gpsmi_trk* h); }
 
 struct gpsmi_acq {
     gpsmi_cfg cfg;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t order = nullptr;        // orders other handles' streams behind this one
     // device memory: every buffer is a DevBuf (gpsmi_devmem.h) with a capacity of its own, in elements
     DevBuf<float2> d_tw;
     DevBuf<float> d_t32;
@@ -403,7 +400,6 @@ struct gpsmi_acq {
     // while the previous one still runs; no blocking copy, no use of the null stream)
     float* h_om[2] = {nullptr, nullptr};
     int32_t* h_slot[2] = {nullptr, nullptr};
-    hipEvent_t staged[2] = {nullptr, nullptr};
     bool staged_used[2] = {false, false};
     int stage = 0;
     // direct (time-domain) path for code_samples != 2048
@@ -437,6 +433,11 @@ struct gpsmi_acq {
     int iq_fmt = GPSMI_IQ_C64;              // what the iq pointers of the search calls point to
     float last_ms = 0.f;
     bool pending = false;
+    // released bottom up: the events, then the stream, then (above) the device buffers
+    DevStream stream;
+    DevEvent ev0, ev1;
+    DevEvent order;                         // orders other handles' streams behind this one
+    DevEvent staged[2];
 };
 
 extern "C" int gpsmi_acq_wait(gpsmi_acq* h);
@@ -501,14 +502,14 @@ int gpsmi_acq_create(const gpsmi_cfg* cfg, gpsmi_acq** out) {
 
 static int acq_build(const gpsmi_cfg* cfg, gpsmi_acq* h) {
     h->direct = cfg->code_samples != kFftN;
-    GPSMI_HIP(hipStreamCreate(&h->stream));
-    GPSMI_HIP(hipEventCreateWithFlags(&h->order, hipEventDisableTiming));
-    GPSMI_HIP(hipEventCreate(&h->ev0));
-    GPSMI_HIP(hipEventCreate(&h->ev1));
+    int rc = h->stream.create();
+    if (!rc) rc = h->order.create(hipEventDisableTiming);
+    if (!rc) rc = h->ev0.create();
+    if (!rc) rc = h->ev1.create();
+    if (rc) return rc;
     std::vector<float2> tw;
     make_twiddles(tw);
-    int rc = h->d_tw.upload(tw, "gpsmi_acq twiddles");
-    if (rc) return rc;
+    if ((rc = h->d_tw.upload(tw, "gpsmi_acq twiddles"))) return rc;
     // SEC_TIME (gpsrecv.py:32-33): float32(k+1) / SAMPLE_RATE in float32
     const int ngps = cfg->n_cyc * cfg->code_samples;
     const float fs = (float)(1000 * cfg->code_samples);
@@ -522,7 +523,7 @@ static int acq_build(const gpsmi_cfg* cfg, gpsmi_acq* h) {
         GPSMI_HIP(hipHostMalloc((void**)&h->h_om[k], 65536 * sizeof(float), hipHostMallocDefault));
         GPSMI_HIP(hipHostMalloc((void**)&h->h_slot[k], (GPSMI_MAX_PRN + 1) * sizeof(int32_t),
                                 hipHostMallocDefault));
-        GPSMI_HIP(hipEventCreateWithFlags(&h->staged[k], hipEventDisableTiming));
+        if ((rc = h->staged[k].create(hipEventDisableTiming))) return rc;
     }
     if (h->direct) {
         if ((rc = h->d_rep_time.reserve((size_t)(GPSMI_MAX_PRN + 1) * cfg->code_samples, "gpsmi_acq replicas")))
@@ -557,13 +558,8 @@ int gpsmi_acq_destroy(gpsmi_acq* h) {
     for (int k = 0; k < 2; ++k) {
         if (h->h_om[k]) (void)hipHostFree(h->h_om[k]);
         if (h->h_slot[k]) (void)hipHostFree(h->h_slot[k]);
-        if (h->staged[k]) (void)hipEventDestroy(h->staged[k]);
     }
-    if (h->order) (void)hipEventDestroy(h->order);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;                                // (releases the device buffers)
+    delete h;                                // (releases events, stream and device buffers, in this order)
     return GPSMI_OK;
 }
 

@@ -7,7 +7,7 @@
 
 #include <cstring>
 
-#include "gpsmi_common.h"
+#include "gpsmi_devmem.h"
 
 using namespace gpsmi;
 
@@ -15,7 +15,7 @@ static_assert(sizeof(ncclUniqueId) <= GPSMI_COMM_ID_BYTES, "unique id does not f
 
 struct gpsmi_comm {
     ncclComm_t comm = nullptr;
-    hipStream_t stream = nullptr;
+    DevStream stream;                // (released with the handle, after the communicator)
     int nranks = 0, rank = 0, device = 0;
 };
 
@@ -47,10 +47,10 @@ int gpsmi_comm_create(const void* id_bytes, int nranks, int rank, int device, gp
     *out = nullptr;
     ncclUniqueId id;
     memcpy(&id, id_bytes, sizeof(id));
-    hipError_t he = hipStreamCreate(&c->stream);
-    if (he != hipSuccess) {         // nothing half-built leaves this function
+    const int rc = c->stream.create();
+    if (rc) {                       // nothing half-built leaves this function
         (void)gpsmi_comm_destroy(c);
-        return fail(GPSMI_E_HIP, "hipStreamCreate: %s", hipGetErrorString(he));
+        return rc;
     }
     ncclResult_t nr = ncclCommInitRank(&c->comm, nranks, id, rank);
     if (nr != ncclSuccess) {
@@ -66,7 +66,6 @@ int gpsmi_comm_destroy(gpsmi_comm* c) {
     if (!c) return GPSMI_OK;
     (void)hipSetDevice(c->device);
     if (c->comm) (void)ncclCommDestroy(c->comm);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return GPSMI_OK;
 }

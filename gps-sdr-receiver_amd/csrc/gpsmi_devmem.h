@@ -64,6 +64,40 @@ struct DevBuf {
     }
 };
 
+// DevStream / DevEvent: the one owner of a stream / an event of a handle, empty until create().  They
+// convert to the runtime's handle, which is what HandleSync, the launch sites and every runtime call
+// take (borrowed, never destroyed there).
+template <typename H, hipError_t (*Destroy)(H)>
+struct DevHandle {
+    H h = nullptr;
+    DevHandle() = default;
+    DevHandle(DevHandle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    DevHandle& operator=(DevHandle&& o) noexcept {
+        if (this != &o) { release(); h = o.h; o.h = nullptr; }
+        return *this;
+    }
+    DevHandle(const DevHandle&) = delete;
+    DevHandle& operator=(const DevHandle&) = delete;
+    ~DevHandle() { release(); }
+    operator H() const { return h; }
+    void release() {
+        if (h) (void)Destroy(h);
+        h = nullptr;
+    }
+};
+struct DevStream : DevHandle<hipStream_t, hipStreamDestroy> {
+    int create() {
+        GPSMI_HIP(hipStreamCreate(&h));
+        return GPSMI_OK;
+    }
+};
+struct DevEvent : DevHandle<hipEvent_t, hipEventDestroy> {
+    int create(unsigned flags = hipEventDefault) {       // (hipEventDefault: what hipEventCreate passes)
+        GPSMI_HIP(hipEventCreateWithFlags(&h, flags));
+        return GPSMI_OK;
+    }
+};
+
 // Device copies of the input and the output of a host entry point that works block by block
 // (gpsmi_pb_apply, gpsmi_ifx_apply): room for both, then the input on its way up on `stream`.
 struct StagedIO {

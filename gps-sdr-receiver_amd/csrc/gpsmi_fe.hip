@@ -265,8 +265,6 @@ using namespace gpsmi;
 struct gpsmi_fe {
     gpsmi_fe_cfg cfg;
     FePlan plan;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     DevBuf<float> d_table;
     DevBuf<float2> d_carry;                                 // [kc]
     DevBuf<float2> d_vbuf;                                  // [kc + n_in]
@@ -276,6 +274,9 @@ struct gpsmi_fe {
     long long emitted = 0;                                  // outputs since create / reset
     bool flushed = false;
     float last_ms = 0.f;
+    // released bottom up: the events, then the stream, then (above) the device buffers
+    DevStream stream;
+    DevEvent ev0, ev1;
 };
 
 static size_t fe_sample_bytes(int fmt) {
@@ -379,13 +380,14 @@ int gpsmi_fe_create(const gpsmi_fe_cfg* cfg, gpsmi_fe** out) {
     h->plan = std::move(pl);
     rc = [&]() -> int {
         const FePlan& p = h->plan;
-        GPSMI_HIP(hipStreamCreate(&h->stream));
-        GPSMI_HIP(hipEventCreate(&h->ev0));
-        GPSMI_HIP(hipEventCreate(&h->ev1));
+        int rc = h->stream.create();
+        if (!rc) rc = h->ev0.create();
+        if (!rc) rc = h->ev1.create();
+        if (rc) return rc;
         if (p.lds > kFeLdsBudget)
             GPSMI_HIP(hipFuncSetAttribute((const void*)fe_filter_kernel,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-        int rc = h->d_table.upload(p.table, "front-end filter table");
+        rc = h->d_table.upload(p.table, "front-end filter table");
         if (!rc) rc = h->d_carry.reserve_zeroed(p.kc, "front-end carry");
         if (!rc) rc = h->d_out.reserve(h->cfg.max_out, "front-end output block");
         return rc;
@@ -402,10 +404,7 @@ int gpsmi_fe_destroy(gpsmi_fe* h) {
     if (!h) return GPSMI_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;                                // (releases the device buffers)
+    delete h;                                // (releases events, stream and device buffers, in this order)
     return GPSMI_OK;
 }
 

@@ -225,8 +225,6 @@ using namespace gpsmi;
 
 struct gpsmi_ifx {
     gpsmi_ifx_cfg cfg;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     DevBuf<float2> d_tw;
     DevBuf<float> d_win;                     // periodic Hann, float32 of the double value
     DevBuf<float2> d_carry;                  // [H] complex64
@@ -237,18 +235,21 @@ struct gpsmi_ifx {
     int fmt = GPSMI_IQ_C64;
     float scale = 0.f;                       // 10^(thresh_db / 10) as float32
     float last_ms = 0.f;
+    // released bottom up: the events, then the stream, then (above) the device buffers
+    DevStream stream;
+    DevEvent ev0, ev1;
 };
 
 static bool ifx_block_ok(int32_t n) { return n >= 4 * kIfxH && n <= (1 << 24) && n % kIfxH == 0; }
 
 static int ifx_build(gpsmi_ifx* h) {
-    GPSMI_HIP(hipStreamCreate(&h->stream));
-    GPSMI_HIP(hipEventCreate(&h->ev0));
-    GPSMI_HIP(hipEventCreate(&h->ev1));
+    int rc = h->stream.create();
+    if (!rc) rc = h->ev0.create();
+    if (!rc) rc = h->ev1.create();
+    if (rc) return rc;
     std::vector<float2> tw;
     make_twiddles(tw);
-    int rc = h->d_tw.upload(tw, "excision twiddles");
-    if (rc) return rc;
+    if ((rc = h->d_tw.upload(tw, "excision twiddles"))) return rc;
     std::vector<float> win(kIfxL);
     for (int i = 0; i < kIfxL; ++i) {
         const double s = sin(M_PI * (double)i / (double)kIfxL);
@@ -338,10 +339,7 @@ int gpsmi_ifx_destroy(gpsmi_ifx* h) {
     if (!h) return GPSMI_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;                                // (releases the device buffers)
+    delete h;                                // (releases events, stream and device buffers, in this order)
     return GPSMI_OK;
 }
 

@@ -310,8 +310,6 @@ using namespace gpsmi;
 
 struct gpsmi_pb {
     gpsmi_pb_cfg cfg;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     DevBuf<int> d_state;                                  // the carry into the next call's block 0
     DevBuf<uint32_t> d_hist;                              // [chunk blocks][slices][2048]
     DevBuf<uint2> d_sel; DevBuf<float> d_floors, d_thr;   // [blocks]
@@ -324,6 +322,9 @@ struct gpsmi_pb {
     int limit = 0;                                        // floor(max_frac * n)
     size_t chunk_bytes = 0;                               // input bytes per chunk (0: one chunk)
     float last_ms = 0.f;
+    // released bottom up: the events, then the stream, then (above) the device buffers
+    DevStream stream;
+    DevEvent ev0, ev1;
 };
 
 static size_t pb_in_bytes(const gpsmi_pb* h, int nb) {
@@ -331,10 +332,10 @@ static size_t pb_in_bytes(const gpsmi_pb* h, int nb) {
 }
 
 static int pb_build(gpsmi_pb* h) {
-    GPSMI_HIP(hipStreamCreate(&h->stream));
-    GPSMI_HIP(hipEventCreate(&h->ev0));
-    GPSMI_HIP(hipEventCreate(&h->ev1));
-    const int rc = h->d_state.reserve_zeroed(1, "pulse blanking carry");
+    int rc = h->stream.create();
+    if (!rc) rc = h->ev0.create();
+    if (!rc) rc = h->ev1.create();
+    if (!rc) rc = h->d_state.reserve_zeroed(1, "pulse blanking carry");
     if (rc) return rc;
     h->f = (float)pow(10.0, (double)h->cfg.thresh_db / 10.0);
     h->limit = (int)floor((double)h->cfg.max_frac * (double)h->cfg.block_samples);
@@ -460,10 +461,7 @@ int gpsmi_pb_destroy(gpsmi_pb* h) {
     if (!h) return GPSMI_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;                                // (releases the device buffers)
+    delete h;                                // (releases events, stream and device buffers, in this order)
     return GPSMI_OK;
 }
 

@@ -26,15 +26,10 @@
 //
 // Loop-carried state lives in device memory; the closed loop needs no host
 // round trip between blocks.
-#include <atomic>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
-#include <mutex>
-#include <thread>
 #include <utility>
 #include <vector>
 
@@ -43,6 +38,7 @@
 #include "gpsmi_common.h"
 #include "gpsmi_devmem.h"
 #include "gpsmi_fft.h"
+#include "gpsmi_submit.h"
 
 // Code that restates the reference's float32 arithmetic step by step (the phase
 // argument of the carrier, the PLL, numpy's summation order) must not be fused into
@@ -165,18 +161,9 @@ struct gpsmi_trk {
                                          // its single-block form (GPSMI_SPAN_SINGLE_MAX; measured per step with
                                          // the round's final kernels: 50 against 56 us at 64 units, 69 against 63
                                          // at 96, 81 against 66 at 128)
-    hipStream_t stream = nullptr;
-    hipStream_t copy_stream = nullptr;   // result read-back, overlaps the next replay run (the epilogue's
-    bool own_copy_stream = false;        // stream unless option "copy_stream" = 1)
-    hipStream_t alt_stream = nullptr;    // "corr_overlap": the runs of result slot 1 (slot 0 keeps `stream`)
-    hipStream_t epi_stream = nullptr;    // replay: the epilogue of run k beside the code-phase
-                                         // correlation of run k + 1 (the other slot's buffers)
     // streaming from host memory (gpsmi_trk_process_stream): two staging blocks filled on a stream
-    // of their own, so that the upload of block k + 1 runs under the kernels of block k
-    hipStream_t up_stream = nullptr;
+    // of their own (up_stream), so that the upload of block k + 1 runs under the kernels of block k
     DevBuf<char> d_stage[2];
-    hipEvent_t up_done[2] = {nullptr, nullptr}, stage_free[2] = {nullptr, nullptr};
-    hipEvent_t in_done[2] = {nullptr, nullptr};   // end of a streamed step (its iq read, its out written)
     bool in_pending[2] = {false, false};
     bool stage_used[2] = {false, false};
     int stage_idx = 0;
@@ -184,24 +171,7 @@ struct gpsmi_trk {
     size_t stream_direct_max = 0;            // bytes up to which the kernels of a streamed step read a page-locked
                                              // block where it lies (no staging copy): option "stream_direct_max"
                                              // (GPSMI_STREAM_INLINE_MAX)
-    hipEvent_t order = nullptr;          // orders other handles' streams behind this one
-    hipEvent_t main_tail = nullptr;      // the event recorded behind the last work on `stream`, if any
-    // two result slots: a replay run writes one while the other is still being copied out
-    struct Slot {
-        DevBuf<gpsmi_trk_out> d_out;
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // start, corr done, correlator done, end
-        hipEvent_t ready = nullptr, copied = nullptr;
-        hipEvent_t corr_stop = nullptr;      // the event that carries the end stamp of the slot's timed correlator
-        hipEvent_t corr_done = nullptr, epi_done = nullptr;   // correlator / epilogue of the slot's run
-        bool copy_pending = false, epi_pending = false;
-        int timing_pending = 0;              // the timing mode of the slot's run, until its times are taken
-        DevBuf<JobMid> d_mid;                // per-job descriptors and window sums of the slot's run
-        DevBuf<float2> d_partial;
-        hipStream_t run_stream = nullptr;    // "corr_overlap": the stream the slot's runs are enqueued on (null: h->stream)
-        DevBuf<float> d_rec;                 // raw sums of the single-block span correlator (gpsmi_trk_span.h):
-                                             // per slot, the epilogue of run k reads them on its own stream
-                                             // while run k + 1 writes the other slot's
-    } slot[2];
+    hipEvent_t main_tail = nullptr;      // the event recorded behind the last work on `stream`, if any (borrowed)
     int cur = 0;                         // slot of the latest launch
     int timing = 1;                      // 1: record the four kernel-timing events per launch; 2: only the
                                          // begin / end stamps of the batch correlator's own dispatch (no
@@ -253,35 +223,60 @@ struct gpsmi_trk {
     DevBuf<float2> d_RSp;
     bool span8 = false;              // the matrix-pipe correlator for CS = 16368, N_CYC = 8 (gpsmi_trk_span8.h)
     TrkParams P;
-    // gpsmi_trk_process_stream's submission thread (option "stream_thread", default on): the four
-    // launches and the event record of a streamed step cost ~25 us of runtime calls on the host --
-    // as long as the step runs on the GPU -- so they are made by a thread of the handle's own while
-    // the caller prepares its next block.  Every other entry point first waits for this thread to
-    // have nothing queued (trk_quiesce), so at any time only one thread works on the handle.
-    struct StreamJob { const void* iq; size_t n; gpsmi_trk_out* out; };
-    struct StreamWorker {
-        std::thread th;
-        std::mutex m;
-        std::condition_variable cv_job, cv_done;
-        std::deque<StreamJob> q;
-        bool stop = false;
-        long long submitted = 0;     // jobs handed over
-        long long cleared = 0;       // jobs whose step before last has been seen complete (the caller may go on)
-        long long finished = 0;      // jobs fully enqueued on the device
-        // the same three counters for the other thread to POLL before it goes to sleep on a condition
-        // variable: being woken from a futex measured 50-100 us on these hosts, three hand-overs per
-        // report block made gpsmi_trk_wait 290 us where the work outstanding was 60 us
-        std::atomic<long long> a_submitted{0}, a_cleared{0}, a_finished{0};
-        int err = 0;
-        char errmsg[512] = "";
-    };
-    StreamWorker* worker = nullptr;
     int stream_thread = 1;
     int stream_depth = 2;            // calls a streamed step's buffers stay in use: 2 (gpsmi.h) or 3
     long long stat_backlog = 0;
     long long stat_quiesce_ns = 0, stat_evwait_ns = 0, stat_waits = 0;   // gpsmi_trk_wait behind streamed steps
     long long stat_wait_ns = 0, stat_launch_ns = 0, stat_steps = 0;   // streamed steps: host time waiting for the
                                                                       // step before last / making the runtime calls
+    // What the runtime hands out comes last, in the order the members are released in, bottom up: the
+    // submission thread is joined, then events go, then streams, then (above) the device buffers.  A
+    // result slot goes as a whole, its buffers between its events and the streams.
+    DevStream stream;
+    DevStream epi_stream;                // replay: the epilogue of run k beside the code-phase
+                                         // correlation of run k + 1 (the other slot's buffers)
+    DevStream own_copy_stream;           // option "copy_stream" = 1 only
+    hipStream_t copy_stream = nullptr;   // result read-back, overlaps the next replay run: own_copy_stream, else
+                                         // the epilogue's stream (borrowed either way)
+    DevStream alt_stream;                // "corr_overlap": the runs of result slot 1 (slot 0 keeps `stream`)
+    DevStream up_stream;                 // uploads of streamed blocks beyond stream_inline_max
+    // two result slots: a replay run writes one while the other is still being copied out
+    struct Slot {
+        DevBuf<gpsmi_trk_out> d_out;
+        DevBuf<JobMid> d_mid;                // per-job descriptors and window sums of the slot's run
+        DevBuf<float2> d_partial;
+        DevBuf<float> d_rec;                 // raw sums of the single-block span correlator (gpsmi_trk_span.h):
+                                             // per slot, the epilogue of run k reads them on its own stream
+                                             // while run k + 1 writes the other slot's
+        DevEvent ev[4];                      // start, corr done, correlator done, end
+        DevEvent ready, copied;
+        DevEvent corr_done, epi_done;        // correlator / epilogue of the slot's run
+        hipEvent_t corr_stop = nullptr;      // the event that carries the end stamp of the slot's timed correlator (borrowed)
+        bool copy_pending = false, epi_pending = false;
+        int timing_pending = 0;              // the timing mode of the slot's run, until its times are taken
+        hipStream_t run_stream = nullptr;    // "corr_overlap": the stream the slot's runs are enqueued on (null: h->stream)
+        // a replay run of this slot, or its read-back, is still outstanding
+        bool in_flight() const { return copy_pending || epi_pending; }
+    } slot[2];
+    DevEvent order;                      // orders other handles' streams behind this one
+    DevEvent up_done[2], stage_free[2];
+    DevEvent in_done[2];                 // end of a streamed step (its iq read, its out written)
+    // gpsmi_trk_process_stream's submission thread (option "stream_thread", default on; gpsmi_submit.h):
+    // the four launches and the event record of a streamed step cost ~25 us of runtime calls on the
+    // host -- as long as the step runs on the GPU -- so they are made by a thread of the handle's own
+    // while the caller prepares its next block.  Every other entry point first waits for this thread
+    // to have nothing queued (trk_quiesce), so at any time only one thread works on the handle.
+    static int submit_step(void* h, const SubmitQueue::Job& job, SubmitQueue& q, char* errtext);
+    SubmitQueue submit{submit_step, this};
+
+    // A replay run, its read-back or its timing is still outstanding: the slots are not the closed
+    // loop's to use.  (gpsmi_trk_replay_load asks the slots' in_flight() alone: times not yet taken
+    // keep no kernel running, so they do not hold up a new table.)
+    bool replay_busy() const {
+        return slot[0].in_flight() || slot[1].in_flight() || slot[0].timing_pending || slot[1].timing_pending;
+    }
+    // bytes of `n` samples in the handle's input format
+    size_t iq_bytes(size_t n) const { return n * (iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)); }
 };
 
 constexpr int kSpanUnitsMax = 256;   // (block, channel group) units the single-block span form can serve (records)
@@ -566,21 +561,10 @@ static int trk_pull_state(gpsmi_trk* h) {
     return GPSMI_OK;
 }
 
-// Is [p, p + bytes) page-locked host memory a kernel may address?  -> its device pointer.
 // Wait for an event the GPU is about to signal by POLLING it: hipEventSynchronize may put the thread
 // to sleep, and being woken by the driver measured ~250 us where the GPU had ~100 us of work left (the
 // drop-in path waits like this once a second of signal: 353 -> ~110 us per report block).  After 2 ms
 // the thread gives in and sleeps.
-// Poll `done()` for up to `us` microseconds (then the caller sleeps on its condition variable).
-template <class F>
-static void trk_spin_until(F&& done, int us) {
-    const auto t0 = std::chrono::steady_clock::now();
-    while (!done()) {
-        if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(us)) return;
-        __builtin_ia32_pause();
-    }
-}
-
 static hipError_t trk_spin_wait(hipEvent_t ev) {
     const auto t0 = std::chrono::steady_clock::now();
     for (;;) {
@@ -593,10 +577,10 @@ static hipError_t trk_spin_wait(hipEvent_t ev) {
     return hipEventSynchronize(ev);
 }
 
+// Is [p, p + bytes) page-locked host memory a kernel may address?  -> its device pointer.
 // (memory from gpsmi_host_alloc is known without asking the runtime: hipPointerGetAttributes costs
 // ~2 us a call, twice per step)
-static bool trk_pinned_dev(gpsmi_trk* h, const void* p, size_t bytes, void** dev) {
-    (void)h;
+static bool trk_pinned_dev(const void* p, size_t bytes, void** dev) {
     if (bytes % 16 != 0 || ((uintptr_t)p & 15) != 0) return false;
     if (host_alloc_lookup(p, bytes, dev)) return true;
     hipPointerAttribute_t at{};
@@ -615,62 +599,23 @@ static bool trk_pinned_dev(gpsmi_trk* h, const void* p, size_t bytes, void** dev
     return true;
 }
 
+// `cleared`: the submission queue whose thread runs the step (null: the caller's own thread does)
 static int trk_stream_step(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out* out,
-                           void (*cleared)(gpsmi_trk*) = nullptr);
+                           SubmitQueue* cleared = nullptr);
 
-static void trk_worker_cleared(gpsmi_trk* h) {
-    gpsmi_trk::StreamWorker& w = *h->worker;
-    {
-        std::lock_guard<std::mutex> lock(w.m);
-        w.cleared = w.finished + 1;             // (the job in hand)
-        w.a_cleared.store(w.cleared, std::memory_order_release);
-    }
-    w.cv_done.notify_all();
-}
-
-static void trk_worker_main(gpsmi_trk* h) {
-    gpsmi_trk::StreamWorker& w = *h->worker;
-    (void)hipSetDevice(h->cfg.device);
-    for (;;) {
-        gpsmi_trk::StreamJob job;
-        trk_spin_until([&] { return w.a_submitted.load(std::memory_order_acquire) > w.a_finished.load(std::memory_order_relaxed); }, 300);
-        {
-            std::unique_lock<std::mutex> lock(w.m);
-            w.cv_job.wait(lock, [&] { return w.stop || !w.q.empty(); });
-            if (w.q.empty()) return;            // (stop, and nothing left to enqueue)
-            job = w.q.front();
-        }
-        int rc = w.err ? w.err : trk_stream_step(h, job.iq, job.n, job.out, trk_worker_cleared);
-        {
-            std::lock_guard<std::mutex> lock(w.m);
-            if (rc && !w.err) {                 // the first failure is kept for the caller
-                w.err = rc;
-                snprintf(w.errmsg, sizeof(w.errmsg), "%s", last_error_buf());
-            }
-            w.q.pop_front();
-            w.finished += 1;
-            if (w.cleared < w.finished) w.cleared = w.finished;
-            w.a_cleared.store(w.cleared, std::memory_order_release);
-            w.a_finished.store(w.finished, std::memory_order_release);
-        }
-        w.cv_done.notify_all();
-    }
+int gpsmi_trk::submit_step(void* h, const SubmitQueue::Job& job, SubmitQueue& q, char* errtext) {
+    const int rc = trk_stream_step(static_cast<gpsmi_trk*>(h), job.iq, job.n, static_cast<gpsmi_trk_out*>(job.out), &q);
+    if (rc) snprintf(errtext, SubmitQueue::kErrText, "%s", last_error_buf());
+    return rc;
 }
 
 // Nothing is queued on the submission thread and it is idle: from here on the calling thread is the
 // only one working on the handle.  A failure of a streamed step surfaces here (once).
 static int trk_quiesce(gpsmi_trk* h) {
-    if (!h || !h->worker) return GPSMI_OK;
-    gpsmi_trk::StreamWorker& w = *h->worker;
-    trk_spin_until([&] { return w.a_finished.load(std::memory_order_acquire) == w.a_submitted.load(std::memory_order_relaxed); }, 1000);
-    std::unique_lock<std::mutex> lock(w.m);
-    w.cv_done.wait(lock, [&] { return w.finished == w.submitted; });
-    if (w.err) {
-        const int rc = w.err;
-        w.err = 0;
-        return fail(rc, "a streamed step failed: %s", w.errmsg);
-    }
-    return GPSMI_OK;
+    if (!h) return GPSMI_OK;
+    char report[SubmitQueue::kReport];
+    const int rc = h->submit.quiesce(report);
+    return rc ? fail(rc, "%s", report) : GPSMI_OK;
 }
 
 #define GPSMI_QUIESCE(h)                 \
@@ -722,8 +667,9 @@ int gpsmi_trk_create(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk** out) {
 
 static int trk_build(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk* h) {
     GPSMI_HIP(hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device));
-    GPSMI_HIP(hipStreamCreate(&h->stream));
-    GPSMI_HIP(hipStreamCreate(&h->epi_stream));
+    int rc = h->stream.create();
+    if (!rc) rc = h->epi_stream.create();
+    if (rc) return rc;
     // The read-back of a replay run follows the run's epilogue anyway and is over long before the next
     // epilogue is due, so by default it shares the epilogue's stream: the HIP runtime maps streams onto
     // four hardware queues (one per pipe of the command processor), and a process with this handle's
@@ -734,21 +680,21 @@ static int trk_build(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk* h) {
     // Option "copy_stream" = 1 (create time) gives the read-back a stream of its own again.
     long long own_copy = 0;
     default_opt("copy_stream", &own_copy, 0);
-    h->own_copy_stream = own_copy != 0;
-    if (h->own_copy_stream) GPSMI_HIP(hipStreamCreate(&h->copy_stream));
-    else h->copy_stream = h->epi_stream;
-    GPSMI_HIP(hipEventCreateWithFlags(&h->order, hipEventDisableTiming));
+    if (own_copy != 0 && (rc = h->own_copy_stream.create())) return rc;
+    h->copy_stream = own_copy != 0 ? h->own_copy_stream : h->epi_stream;
+    rc = h->order.create(hipEventDisableTiming);
     for (auto& sl : h->slot) {
-        for (auto& e : sl.ev) GPSMI_HIP(hipEventCreate(&e));
-        GPSMI_HIP(hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming));
-        GPSMI_HIP(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
-        GPSMI_HIP(hipEventCreate(&sl.corr_done));   // (also used as a dispatch's stop event)
-        GPSMI_HIP(hipEventCreateWithFlags(&sl.epi_done, hipEventDisableTiming));
+        for (auto& e : sl.ev)
+            if (!rc) rc = e.create();
+        if (!rc) rc = sl.ready.create(hipEventDisableTiming);
+        if (!rc) rc = sl.copied.create(hipEventDisableTiming);
+        if (!rc) rc = sl.corr_done.create();        // (with timing: also used as a dispatch's stop event)
+        if (!rc) rc = sl.epi_done.create(hipEventDisableTiming);
     }
+    if (rc) return rc;
     std::vector<float2> tw;
     make_twiddles(tw);
-    int rc = h->d_tw.upload(tw, "gpsmi_trk twiddles");
-    if (rc) return rc;
+    if ((rc = h->d_tw.upload(tw, "gpsmi_trk twiddles"))) return rc;
     const int ngps = cfg->n_cyc * cfg->code_samples;
     const float fs = (float)(1000 * cfg->code_samples);
     std::vector<float> t32(ngps);
@@ -835,42 +781,15 @@ extern "C" {
 
 int gpsmi_trk_destroy(gpsmi_trk* h) {
     if (!h) return GPSMI_OK;
-    if (h->worker) {
-        (void)trk_quiesce(h);
-        {
-            std::lock_guard<std::mutex> lock(h->worker->m);
-            h->worker->stop = true;
-        }
-        h->worker->cv_job.notify_all();
-        h->worker->th.join();
-        delete h->worker;
-        h->worker = nullptr;
-    }
+    (void)trk_quiesce(h);
+    h->submit.stop();
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->copy_stream && h->own_copy_stream) (void)hipStreamSynchronize(h->copy_stream);
+    if (h->own_copy_stream) (void)hipStreamSynchronize(h->own_copy_stream);
     if (h->epi_stream) (void)hipStreamSynchronize(h->epi_stream);
-    for (auto& sl : h->slot) {
-        for (auto e : sl.ev)
-            if (e) (void)hipEventDestroy(e);
-        if (sl.ready) (void)hipEventDestroy(sl.ready);
-        if (sl.copied) (void)hipEventDestroy(sl.copied);
-        if (sl.corr_done) (void)hipEventDestroy(sl.corr_done);
-        if (sl.epi_done) (void)hipEventDestroy(sl.epi_done);
-    }
-    if (h->order) (void)hipEventDestroy(h->order);
     if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
-    for (int k = 0; k < 2; ++k) {
-        if (h->up_done[k]) (void)hipEventDestroy(h->up_done[k]);
-        if (h->stage_free[k]) (void)hipEventDestroy(h->stage_free[k]);
-        if (h->in_done[k]) (void)hipEventDestroy(h->in_done[k]);
-    }
-    if (h->up_stream) (void)hipStreamDestroy(h->up_stream);
-    if (h->copy_stream && h->own_copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    if (h->alt_stream) { (void)hipStreamSynchronize(h->alt_stream); (void)hipStreamDestroy(h->alt_stream); }
-    if (h->epi_stream) (void)hipStreamDestroy(h->epi_stream);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;                                // (releases the device buffers)
+    if (h->alt_stream) (void)hipStreamSynchronize(h->alt_stream);
+    delete h;                                // (releases events, streams and device buffers, in this order)
     return GPSMI_OK;
 }
 
@@ -994,12 +913,7 @@ int gpsmi_trk_process_dev(gpsmi_trk* h, const void* d_iq, size_t n, gpsmi_trk_ou
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     int rc = trk_push_state(h);
     if (rc) return rc;
-    if (h->slot[0].copy_pending || h->slot[1].copy_pending || h->slot[0].timing_pending ||
-        h->slot[1].timing_pending || h->slot[0].epi_pending ||
-        h->slot[1].epi_pending) {          // a replay still in flight owns the slots
-        rc = trk_settle(h);
-        if (rc) return rc;
-    }
+    if (h->replay_busy() && (rc = trk_settle(h))) return rc;
     gpsmi_trk::Slot& sl = h->slot[0];      // the closed loop needs one slot only
     h->cur = 0;
     sl.run_stream = nullptr;
@@ -1014,12 +928,8 @@ int gpsmi_trk_process_dev(gpsmi_trk* h, const void* d_iq, size_t n, gpsmi_trk_ou
     // next call queues behind it (get_state / wait / a call with `out` synchronise)
     if (!out && h->timing != 1) return GPSMI_OK;
     GPSMI_HIP(hipStreamSynchronize(h->stream));
-    if (h->timing == 1) {
-        GPSMI_HIP(hipEventElapsedTime(&h->last_total_ms, sl.ev[0], sl.ev[3]));
-        GPSMI_HIP(hipEventElapsedTime(&h->last_corr_ms, sl.ev[1], sl.ev[2]));
-        GPSMI_HIP(hipEventElapsedTime(&h->last_cp_ms, sl.ev[0], sl.ev[1]));
-    }
-    return GPSMI_OK;
+    sl.timing_pending = h->timing == 1;    // (mode 2 is read out for replay runs only)
+    return trk_take_timing(h, sl);
 }
 
 int gpsmi_trk_process(gpsmi_trk* h, const float* iq, size_t n, gpsmi_trk_out* out) {
@@ -1029,41 +939,35 @@ int gpsmi_trk_process(gpsmi_trk* h, const float* iq, size_t n, gpsmi_trk_out* ou
                   "input must hold one block of NGPS samples per stream");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     h->main_tail = nullptr;
-    GPSMI_HIP(hipMemcpyAsync(h->d_block.p, iq, n * (h->iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)),
-                             hipMemcpyHostToDevice, h->stream));
+    GPSMI_HIP(hipMemcpyAsync(h->d_block.p, iq, h->iq_bytes(n), hipMemcpyHostToDevice, h->stream));
     return gpsmi_trk_process_dev(h, h->d_block.p, n, out);
 }
 
 // One streamed step: everything gpsmi_trk_process_stream promises, made by whichever thread works
 // on the handle (the caller, or the handle's submission thread).  `cleared`, if given, is told as soon
 // as the step before last is known to be complete.
-static int trk_stream_step(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out* out,
-                           void (*cleared)(gpsmi_trk*)) {
+static int trk_stream_step(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out* out, SubmitQueue* cleared) {
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    const size_t bytes = n * (h->iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2));
+    const size_t bytes = h->iq_bytes(n);
+    int rc = GPSMI_OK;
     if (!h->up_stream) {
-        GPSMI_HIP(hipStreamCreate(&h->up_stream));
+        rc = h->up_stream.create();
         for (int k = 0; k < 2; ++k) {
-            GPSMI_HIP(hipEventCreateWithFlags(&h->up_done[k], hipEventDisableTiming));
-            GPSMI_HIP(hipEventCreateWithFlags(&h->stage_free[k], hipEventDisableTiming));
-            GPSMI_HIP(hipEventCreate(&h->in_done[k]));       // (also a dispatch's stop event)
+            if (!rc) rc = h->up_done[k].create(hipEventDisableTiming);
+            if (!rc) rc = h->stage_free[k].create(hipEventDisableTiming);
+            if (!rc) rc = h->in_done[k].create();            // (with timing: also a dispatch's stop event)
         }
+        if (rc) return rc;
     }
     if (bytes > h->d_stage[0].n || bytes > h->d_stage[1].n) {
-        int rc = trk_settle(h);
-        if (rc) return rc;
+        if ((rc = trk_settle(h))) return rc;
         for (int k = 0; k < 2; ++k) {
             h->stage_used[k] = false;
             if ((rc = h->d_stage[k].reserve(bytes, "gpsmi_trk staging block"))) return rc;
         }
     }
-    int rc = trk_push_state(h);
-    if (rc) return rc;
-    if (h->slot[0].copy_pending || h->slot[1].copy_pending || h->slot[0].timing_pending ||
-        h->slot[1].timing_pending || h->slot[0].epi_pending || h->slot[1].epi_pending) {
-        rc = trk_settle(h);                 // a replay still in flight owns the slots
-        if (rc) return rc;
-    }
+    if ((rc = trk_push_state(h))) return rc;
+    if (h->replay_busy() && (rc = trk_settle(h))) return rc;
     const int s = h->stage_idx;
     h->stage_idx ^= 1;
     // back-pressure: the step of the call before last has finished when this call returns (its iq may
@@ -1076,15 +980,15 @@ static int trk_stream_step(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out
     }
     const auto t_w1 = std::chrono::steady_clock::now();
     h->stat_wait_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(t_w1 - t_w0).count();
-    if (cleared) cleared(h);
+    if (cleared) cleared->step_cleared();
     // page-locked memory is read by a kernel (see stage_copy_kernel); anything else -- pageable
     // memory would fault under a kernel -- goes through the runtime's copy
     void* iq_dev = nullptr;
-    const bool pinned = trk_pinned_dev(h, iq, bytes, &iq_dev);
+    const bool pinned = trk_pinned_dev(iq, bytes, &iq_dev);
     // the records of a step go straight into a page-locked `out` (the two kernels that fill a record
     // store over PCIe: 376 bytes per channel) instead of through d_out and a copy command behind them
     void* out_dev = nullptr;
-    const bool out_direct = out && trk_pinned_dev(h, out, (size_t)h->rows() * sizeof(gpsmi_trk_out), &out_dev);
+    const bool out_direct = out && trk_pinned_dev(out, (size_t)h->rows() * sizeof(gpsmi_trk_out), &out_dev);
     // Up to 8 MiB per step (measured: one receiver's 128 KiB to 64 receivers' 8 MiB of raw samples)
     // the block goes up IN FRONT of its own kernels on the main stream: the two event packets that
     // order an upload stream against the main one cost ~7 us per step, and a copy kernel beside the
@@ -1126,7 +1030,7 @@ static int trk_stream_step(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out
     const bool want_tail = in_line && (!out || out_direct);
     bool tail_used = false;
     rc = trk_launch(h, sl, direct_in ? iq_dev : h->d_stage[s].p, h->d_state.p, h->d_state.p, nullptr, h->rows(), h->max_ch,
-                    /*side_epilogue=*/false, want_tail ? h->in_done[s] : nullptr, &tail_used);
+                    /*side_epilogue=*/false, want_tail ? h->in_done[s].h : nullptr, &tail_used);
     sl.d_out.p = d_out_keep;
     h->timing = timing;
     if (rc) return rc;
@@ -1146,7 +1050,6 @@ static int trk_stream_step(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out
     return GPSMI_OK;
 }
 
-
 int gpsmi_trk_process_stream(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out* out) {
     GPSMI_REQUIRE(h && iq, "null argument");
     GPSMI_REQUIRE(n == (size_t)h->n_streams * h->cfg.n_cyc * h->cfg.code_samples,
@@ -1155,42 +1058,17 @@ int gpsmi_trk_process_stream(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_o
         GPSMI_QUIESCE(h);
         return trk_stream_step(h, iq, n, out);
     }
-    if (!h->worker) {
-        h->worker = new (std::nothrow) gpsmi_trk::StreamWorker();
-        if (!h->worker) return fail(GPSMI_E_NOMEM, "out of host memory");
-        try {
-            h->worker->th = std::thread(trk_worker_main, h);
-        } catch (...) {                     // (no thread to be had: nothing may be thrown across the ABI;
-            delete h->worker;               // the caller's thread makes the runtime calls itself)
-            h->worker = nullptr;
-            h->stream_thread = 0;
-            return trk_stream_step(h, iq, n, out);
-        }
+    if (!h->submit.running() && !h->submit.start()) {   // (no thread to be had: the caller's thread makes
+        h->stream_thread = 0;                           // the runtime calls itself)
+        return trk_stream_step(h, iq, n, out);
     }
-    gpsmi_trk::StreamWorker& w = *h->worker;
-    std::unique_lock<std::mutex> lock(w.m);
-    if (w.err) {                                // an earlier step failed: report it instead of queueing more
-        w.cv_done.wait(lock, [&] { return w.finished == w.submitted; });
-        const int rc = w.err;
-        w.err = 0;
-        return fail(rc, "a streamed step failed: %s", w.errmsg);
-    }
-    w.q.push_back({iq, n, out});
-    const long long k = ++w.submitted;          // this job's ordinal, from 1
-    w.a_submitted.store(k, std::memory_order_release);
-    w.cv_job.notify_one();
     // the contract of gpsmi.h: return once the step of the call before last is complete -- the
     // submission thread says so when it has waited for that step on its way into this one
     // ("stream_depth" = 3: one step more -- the call returns when the step three calls back is
     // complete, so the caller can hand over its next block while this one is still being enqueued)
-    const long long need = k - (h->stream_depth - 2);
-    if (w.cleared < need) {
-        lock.unlock();
-        trk_spin_until([&] { return w.a_cleared.load(std::memory_order_acquire) >= need; }, 300);
-        lock.lock();
-    }
-    w.cv_done.wait(lock, [&] { return w.cleared >= need; });
-    return GPSMI_OK;
+    char report[SubmitQueue::kReport];
+    const int rc = h->submit.submit({iq, n, out}, h->stream_depth, report);
+    return rc ? fail(rc, "%s", report) : GPSMI_OK;
 }
 
 int gpsmi_trk_replay_load(gpsmi_trk* h, int nb, const gpsmi_trk_state* table,
@@ -1216,11 +1094,7 @@ int gpsmi_trk_replay_load(gpsmi_trk* h, int nb, const gpsmi_trk_state* table,
     // the epilogue of a run in flight reads d_tab_in and writes d_tab_out on its own stream: a new
     // table may only land once every outstanding run has finished (gpsmi.h states the rule)
     int rc = GPSMI_OK;
-    if (h->slot[0].epi_pending || h->slot[1].epi_pending || h->slot[0].copy_pending ||
-        h->slot[1].copy_pending) {
-        rc = trk_settle(h);
-        if (rc) return rc;
-    }
+    if ((h->slot[0].in_flight() || h->slot[1].in_flight()) && (rc = trk_settle(h))) return rc;
     rc = trk_reserve(h, njobs);
     if (rc) return rc;
     h->main_tail = nullptr;
@@ -1250,7 +1124,10 @@ int gpsmi_trk_replay_run_async(gpsmi_trk* h, const void* d_iq, int nb) {
     // run k still runs, and the chip is never left to one kernel's tail.  Every kernel then shares
     // CUs with another one: throughput mode; the default keeps each kernel alone (its duration is
     // what the roofline is quoted on).
-    if (h->corr_overlap && h->cur == 1 && !h->alt_stream) GPSMI_HIP(hipStreamCreate(&h->alt_stream));
+    if (h->corr_overlap && h->cur == 1 && !h->alt_stream) {
+        const int rc = h->alt_stream.create();
+        if (rc) return rc;
+    }
     sl.run_stream = (h->corr_overlap && h->cur == 1) ? h->alt_stream : nullptr;
     hipStream_t rs = sl.run_stream ? sl.run_stream : h->stream;
     if (sl.copy_pending) {                 // its previous results must have left first
@@ -1275,7 +1152,7 @@ int gpsmi_trk_replay_run_async(gpsmi_trk* h, const void* d_iq, int nb) {
 int gpsmi_trk_wait(gpsmi_trk* h) {
     GPSMI_REQUIRE(h, "null handle");
     const auto t_q0 = std::chrono::steady_clock::now();
-    if (h->worker) h->stat_backlog += h->worker->a_submitted.load() - h->worker->a_finished.load();
+    h->stat_backlog += h->submit.submitted() - h->submit.finished();
     GPSMI_QUIESCE(h);
     const auto t_q1 = std::chrono::steady_clock::now();
     h->stat_quiesce_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(t_q1 - t_q0).count();
@@ -1283,9 +1160,7 @@ int gpsmi_trk_wait(gpsmi_trk* h) {
     // only streamed steps outstanding (in line on the main stream): the event behind the latest one
     // covers everything, and waiting for an event returns ~100 us sooner than the three stream
     // synchronisations of the general case
-    const bool replay_busy = h->slot[0].copy_pending || h->slot[1].copy_pending || h->slot[0].timing_pending ||
-                             h->slot[1].timing_pending || h->slot[0].epi_pending || h->slot[1].epi_pending;
-    if (!replay_busy && !h->stage_used[0] && !h->stage_used[1] && (h->in_pending[0] || h->in_pending[1])) {
+    if (!h->replay_busy() && !h->stage_used[0] && !h->stage_used[1] && (h->in_pending[0] || h->in_pending[1])) {
         const int latest = h->stage_idx ^ 1;               // (the slot of the step enqueued last)
         if (h->in_pending[latest]) {
             GPSMI_HIP(trk_spin_wait(h->in_done[latest]));
@@ -1508,7 +1383,7 @@ int gpsmi_trk_get_option(gpsmi_trk* h, const char* key, long long* value) {
     else if (!strcmp(key, "correlator")) *value = (h->mfma == 4 || h->span8) ? 1 : 0;     // what runs, not what was asked
     else if (!strcmp(key, "codephase")) *value = h->general ? (h->pfa ? 0 : (h->big ? 2 : 1)) : 0;
     else if (!strcmp(key, "debug_flags")) *value = h->P.flags;
-    else if (!strcmp(key, "copy_stream")) *value = h->own_copy_stream ? 1 : 0;
+    else if (!strcmp(key, "copy_stream")) *value = h->own_copy_stream.h ? 1 : 0;
     else return fail(GPSMI_E_ARG, "gpsmi_trk_get_option: unknown option '%s'", key);
     return GPSMI_OK;
 }
