@@ -1,30 +1,14 @@
-// Acquisition: batched per-SV x Doppler parallel code-phase search on gfx950.
+// Acquisition: batched per-SV x Doppler parallel code-phase search on gfx950: the handle and the
+// entry points.  The kernels live beside it, one header per feature:
 //
-// Replaces the array arithmetic of reference src/gpsrecv.py:241-274.
-//
-//   acq_spectrum_kernel   one workgroup per Doppler bin: carrier wipe-off with
-//                         the reference's float32 phase argument
-//                         (gpsrecv.py:232-235), fold of the n_avg code periods
-//                         (sum of FFTs = FFT of the sum, :250-254), 2048-point
-//                         FFT in LDS, spectrum to a small L2-resident scratch.
-//   acq_corr_kernel       one workgroup per (SV, bin): conj(X) * R from
-//                         coalesced reads of the replica spectra, the same FFT
-//                         as the inverse (|ifft(Y)| = |fft(conj Y)| / N, :258),
-//                         |.|, then mean / population std / first-index argmax
-//                         (findCodePhase, :217-223) by wave64 shuffles.  The
-//                         nbins x nsv x 2048 correlation surface never reaches
-//                         HBM; 16 bytes per cell do.
-//   acq_spectrum_nc_kernel, acq_nc_corr_kernel, acq_fold_nc_kernel + pfa_corr_kernel<2>
-//                         the non-coherent search (gpsmi_acq_search_nc): the
-//                         mean of |corr| over n_seg segments, summed in registers per cell.
-//   acq_deep_corr_kernel + pfa_corr_kernel<3>
-//                         the deep search (gpsmi_acq_search_deep): the same mean
-//                         with every segment's magnitudes rotated by the code-Doppler slide.
-//   refine_prompt_kernel, refine_grid_kernel, refine_final_kernel (gpsmi_refine.h)
-//                         refinement of weak / deep hits (gpsmi_acq_refine): fine
-//                         Doppler, bit edge, sub-sample code phase, C/N0.
-//   wtrk_kernel (gpsmi_wtrk.h)
-//                         bit-synchronous tracking of refined hits (gpsmi_acq_track)
+//   gpsmi_acq_search.h    the coherent, the non-coherent and the deep search (gpsmi_acq_search*,
+//                         DESIGN.md 4.2, 4.2a, 4.2e): one wipe-off fold per code length, one
+//                         correlation kernel in three modes
+//   gpsmi_pfa.h, gpsmi_bigfft.h, gpsmi_direct.h
+//                         the correlations of the other code lengths
+//   gpsmi_refine.h        refinement of weak / deep hits (gpsmi_acq_refine): fine
+//                         Doppler, bit edge, sub-sample code phase, C/N0
+//   gpsmi_wtrk.h          bit-synchronous tracking of refined hits (gpsmi_acq_track)
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -39,344 +23,7 @@
 #include "gpsmi_stats.h"
 #include "gpsmi_refine.h"
 #include "gpsmi_wtrk.h"
-
-namespace gpsmi {
-
-// ---- kernels ---------------------------------------------------------------
-// G = 1: 256 threads, the code periods folded one after the other.  G = 4 (long coherent
-// searches): 1024 threads, the periods dealt round-robin to four groups of 256 whose partial
-// folds meet in LDS (the sine / cosine per sample is what this kernel spends its time on);
-// group 0 then adds them in group order and transforms.
-// (FMT 1: iq holds the recorder's raw uint16 samples, decoded on load: gpsmi_acq_set_input_format)
-template <int G, int FMT = 0>
-__global__ __launch_bounds__(256 * G) void acq_spectrum_kernel(
-    const void* __restrict__ iq, const float* __restrict__ t32,
-    const float* __restrict__ omega, int n_avg, float2* __restrict__ spectra,
-    const float2* __restrict__ tw) {
-    __shared__ __attribute__((aligned(16))) float lds[kFftLdsFloats];
-    __shared__ __attribute__((aligned(16))) float lds_tw[kFftTwFloats];
-    __shared__ float2 part[G > 1 ? G - 1 : 1][G > 1 ? kFftN : 1];
-    const int t = threadIdx.x & 255, grp = threadIdx.x >> 8, bin = blockIdx.x;
-    const FftTw ftw = fft_setup(lds_tw, tw, t);           // (every group writes the same tables)
-    const float om = omega[bin];
-    float2 v[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] = make_float2(0.f, 0.f);
-    for (int i = grp; i < n_avg; i += G) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            int k = i * kFftN + t + 256 * r;
-            float2 x = load_iq<FMT>(iq, k);
-            float p = mul_rn(om, t32[k]);      // float32 phase argument, phase0 = 0
-            float s, c;
-            sincosf(p, &s, &c);
-            // factor = (c, -s); factor * x as numpy multiplies complex64
-            v[r].x += c * x.x + s * x.y;
-            v[r].y += c * x.y - s * x.x;
-        }
-    }
-    if (G > 1) {
-        if (grp > 0) {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) part[grp - 1][t + 256 * r] = v[r];
-        }
-        __syncthreads();
-        if (grp > 0) return;                   // (a wave that has ended no longer counts at a barrier)
-#pragma unroll
-        for (int g = 1; g < G; ++g)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const float2 o = part[g - 1][t + 256 * r];
-                v[r].x += o.x; v[r].y += o.y;
-            }
-    }
-    __syncthreads();
-    fft2048(v, lds, ftw, t);
-    const float sc = 1.0f / (float)n_avg;
-    float2* out = spectra + (size_t)bin * kFftN;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) out[t + 256 * q] = make_float2(v[q].x * sc, v[q].y * sc);
-}
-
-__global__ __launch_bounds__(256) void acq_corr_kernel(
-    const float2* __restrict__ spectra, const float2* __restrict__ rep,
-    const int* __restrict__ slot, gpsmi_peak* __restrict__ out, int nsv,
-    const float2* __restrict__ tw, float2* __restrict__ nbr) {
-    __shared__ __attribute__((aligned(16))) float lds[kFftLdsFloats];
-    __shared__ float red[kStatsRedFloats];
-    __shared__ __attribute__((aligned(16))) float lds_tw[kFftTwFloats];
-    // the statistics' copy of the magnitudes lives in the second FFT buffer, which the transform
-    // leaves free when it returns: 40.4 KiB of LDS, four workgroups per CU instead of three
-    float* magbuf = lds + 2 * kFftPlane;
-    static_assert(kFftN <= 2 * kFftPlane1, "the alias must fit buffer 1");
-    const int t = threadIdx.x, sv = blockIdx.x, bin = blockIdx.y;
-    const FftTw ftw = fft_setup(lds_tw, tw, t);
-    const float2* X = spectra + (size_t)bin * kFftN;
-    const float2* R = rep + (size_t)slot[sv] * kFftN;
-    float2 v[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        float2 x = X[t + 256 * q], r = R[t + 256 * q];
-        v[q] = make_float2(x.x * r.x + x.y * r.y, x.x * r.y - x.y * r.x);   // conj(x) * r
-    }
-    __syncthreads();
-    fft2048(v, lds, ftw, t);
-    float mag[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) mag[q] = __builtin_amdgcn_sqrtf(v[q].x * v[q].x + v[q].y * v[q].y) * (1.0f / kFftN);   // v_sqrt_f32, 1 ulp
-    int amax; float peak, mean, sd, lo, hi;
-    corr_stats8(mag, t, magbuf, red, amax, peak, mean, sd, lo, hi);
-    if (t == 0) {
-        // fft(conj Y)[n] = conj(N ifft(Y)[n]): same lag index, no reversal
-        gpsmi_peak p; p.argmax = amax; p.peak = peak; p.mean = mean; p.std = sd;
-        out[(size_t)bin * nsv + sv] = p;
-        if (nbr) nbr[(size_t)bin * nsv + sv] = make_float2(lo, hi);   // circular neighbours
-    }
-}
-
-// ---- general code length: wipe-off + fold in the time domain ----------------
-// x[bin][m] = (1/n_avg) sum_i iq[i L + m] exp(-j fl32(om t32[i L + m]))
-template <int FMT = 0>
-__global__ __launch_bounds__(256) void acq_fold_kernel(
-    const void* __restrict__ iq, const float* __restrict__ t32,
-    const float* __restrict__ omega, int n_avg, int L, float2* __restrict__ xout) {
-    const int m = blockIdx.x * 256 + threadIdx.x, bin = blockIdx.y;
-    if (m >= L) return;
-    const float om = omega[bin];
-    float ar = 0.f, ai = 0.f;
-    for (int i = 0; i < n_avg; ++i) {
-        const int k = i * L + m;
-        const float2 v = load_iq<FMT>(iq, k);
-        float sn, co;
-        sincosf(mul_rn(om, t32[k]), &sn, &co);
-        ar += co * v.x + sn * v.y;
-        ai += co * v.y - sn * v.x;
-    }
-    const float sc = 1.0f / (float)n_avg;
-    xout[(size_t)bin * L + m] = make_float2(ar * sc, ai * sc);
-}
-
-__global__ void acq_cells_kernel(int* __restrict__ xsel, int* __restrict__ rsel,
-                                 const int* __restrict__ slot, int nsv, int ncell) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ncell) return;
-    xsel[c] = c / nsv;                       // the bin's folded block
-    rsel[c] = slot[c % nsv];                 // the SV's replica
-}
-
-__global__ void acq_peaks_kernel(const DirStats* __restrict__ st, gpsmi_peak* __restrict__ out,
-                                 float2* __restrict__ nbr, int ncell) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ncell) return;
-    gpsmi_peak p;
-    p.argmax = st[c].argmax; p.peak = st[c].peak; p.mean = st[c].mean; p.std = st[c].std;
-    out[c] = p;
-    if (nbr) nbr[c] = make_float2(st[c].lo, st[c].hi);
-}
-
-// ---- non-coherent search (gpsmi_acq_search_nc) ------------------------------
-// Segment s of a bin is acq_spectrum_kernel's fold on iq advanced by s * n_coh * 2048 samples (the
-// wipe-off restarts at phase 0 and SEC_TIME[0] in every segment).  Grid (bins, segments); the
-// spectrum of (bin b, segment s) goes to spectra[(b * nseg + s) * 2048].  The arithmetic per
-// workgroup is acq_spectrum_kernel's, operation for operation.
-template <int G, int FMT>
-__global__ __launch_bounds__(256 * G) void acq_spectrum_nc_kernel(
-    const void* __restrict__ iq, const float* __restrict__ t32,
-    const float* __restrict__ omega, int n_coh, int nseg, float2* __restrict__ spectra,
-    const float2* __restrict__ tw) {
-    __shared__ __attribute__((aligned(16))) float lds[kFftLdsFloats];
-    __shared__ __attribute__((aligned(16))) float lds_tw[kFftTwFloats];
-    __shared__ float2 part[G > 1 ? G - 1 : 1][G > 1 ? kFftN : 1];
-    const int t = threadIdx.x & 255, grp = threadIdx.x >> 8, bin = blockIdx.x, seg = blockIdx.y;
-    const FftTw ftw = fft_setup(lds_tw, tw, t);
-    const float om = omega[bin];
-    const size_t base = (size_t)seg * n_coh * kFftN;
-    float2 v[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] = make_float2(0.f, 0.f);
-    for (int i = grp; i < n_coh; i += G) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            int k = i * kFftN + t + 256 * r;
-            float2 x = load_iq<FMT>(iq, base + k);
-            float p = mul_rn(om, t32[k]);
-            float s, c;
-            sincosf(p, &s, &c);
-            v[r].x += c * x.x + s * x.y;
-            v[r].y += c * x.y - s * x.x;
-        }
-    }
-    if (G > 1) {
-        if (grp > 0) {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) part[grp - 1][t + 256 * r] = v[r];
-        }
-        __syncthreads();
-        if (grp > 0) return;
-#pragma unroll
-        for (int g = 1; g < G; ++g)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const float2 o = part[g - 1][t + 256 * r];
-                v[r].x += o.x; v[r].y += o.y;
-            }
-    }
-    __syncthreads();
-    fft2048(v, lds, ftw, t);
-    const float sc = 1.0f / (float)n_coh;
-    float2* out = spectra + ((size_t)bin * nseg + seg) * kFftN;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) out[t + 256 * q] = make_float2(v[q].x * sc, v[q].y * sc);
-}
-
-// One workgroup per (SV, bin): acq_corr_kernel's product, inverse transform and |.| for every
-// segment, the magnitudes summed in registers in ascending segment order, scaled by 1 / nseg, then
-// the statistics once.  The next segment's spectrum is requested before the current one is
-// transformed (the cells are latency-bound chains).  With nseg = 1 every operation
-// is acq_corr_kernel's (0 + m = m, m * 1 = m).  spectra: this launch's bins, [bin][nseg][2048];
-// out / nbr: [bin0 + bin][sv].
-__global__ __launch_bounds__(256) void acq_nc_corr_kernel(
-    const float2* __restrict__ spectra, const float2* __restrict__ rep,
-    const int* __restrict__ slot, gpsmi_peak* __restrict__ out, int nsv, int nseg, int bin0,
-    const float2* __restrict__ tw, float2* __restrict__ nbr) {
-    __shared__ __attribute__((aligned(16))) float lds[kFftLdsFloats];
-    __shared__ float red[kStatsRedFloats];
-    __shared__ __attribute__((aligned(16))) float lds_tw[kFftTwFloats];
-    float* magbuf = lds + 2 * kFftPlane;
-    const int t = threadIdx.x, sv = blockIdx.x, bin = blockIdx.y;
-    const FftTw ftw = fft_setup(lds_tw, tw, t);
-    const float2* X = spectra + (size_t)bin * nseg * kFftN;
-    const float2* R = rep + (size_t)slot[sv] * kFftN;
-    float2 r[8], x[8];
-    float acc[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        r[q] = R[t + 256 * q];
-        x[q] = X[t + 256 * q];
-        acc[q] = 0.f;
-    }
-#pragma unroll 1
-    for (int s = 0; s < nseg; ++s) {
-        float2 v[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            v[q] = make_float2(x[q].x * r[q].x + x[q].y * r[q].y, x[q].x * r[q].y - x[q].y * r[q].x);
-        // the next segment (past the last one the last again, never used: no branch around the loads)
-        const float2* Xn = X + (size_t)(s + 1 < nseg ? s + 1 : s) * kFftN;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) x[q] = Xn[t + 256 * q];
-        __syncthreads();                       // (the previous transform's last LDS reads are done)
-        fft2048(v, lds, ftw, t);
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            acc[q] += __builtin_amdgcn_sqrtf(v[q].x * v[q].x + v[q].y * v[q].y) * (1.0f / kFftN);
-    }
-    const float sc = 1.0f / (float)nseg;
-    float mag[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) mag[q] = acc[q] * sc;
-    int amax; float peak, mean, sd, lo, hi;
-    corr_stats8(mag, t, magbuf, red, amax, peak, mean, sd, lo, hi);
-    if (t == 0) {
-        const size_t c = (size_t)(bin0 + bin) * nsv + sv;
-        gpsmi_peak p; p.argmax = amax; p.peak = peak; p.mean = mean; p.std = sd;
-        out[c] = p;
-        if (nbr) nbr[c] = make_float2(lo, hi);
-    }
-}
-
-// Deep search (gpsmi_acq_search_deep): acq_nc_corr_kernel with the magnitudes of
-// segment s added at the lag they had at the start of the data, S[i] += |corr_s[(i + m) mod 2048]|,
-// m = shift[bin][s] in 0 .. 2047 (the code-Doppler slide, one integer per bin and segment from the
-// host).  The magnitude a sum needs now comes from another thread: a segment's 2048 magnitudes go
-// through LDS once, unscaled, in the plane the statistics use as their copy (the transform's buffer
-// 1, free once its last exchange barrier is passed), and thread t picks up its eight lags at
-// (t + 256 q + m) mod 2048 -- consecutive lanes read consecutive floats, rotated as a whole: no bank
-// conflicts.  The scale 1 / 2048 is applied where acq_nc_corr_kernel applies it, in the addition,
-// so with m = 0 every sum sees that kernel's operations on the same bits.  m is uniform per
-// workgroup and segment (a scalar load, issued ahead of the transform like the next spectrum).
-// Barriers per segment: the loop's own (the reads of the previous segment's magnitudes are done
-// before the next transform's second pass overwrites the plane) and one between writing and reading.
-__global__ __launch_bounds__(256) void acq_deep_corr_kernel(
-    const float2* __restrict__ spectra, const float2* __restrict__ rep,
-    const int* __restrict__ slot, gpsmi_peak* __restrict__ out, int nsv, int nseg, int bin0,
-    const float2* __restrict__ tw, float2* __restrict__ nbr, const int* __restrict__ shift) {
-    __shared__ __attribute__((aligned(16))) float lds[kFftLdsFloats];
-    __shared__ float red[kStatsRedFloats];
-    __shared__ __attribute__((aligned(16))) float lds_tw[kFftTwFloats];
-    float* magbuf = lds + 2 * kFftPlane;
-    const int t = threadIdx.x, sv = blockIdx.x, bin = blockIdx.y;
-    const FftTw ftw = fft_setup(lds_tw, tw, t);
-    const float2* X = spectra + (size_t)bin * nseg * kFftN;
-    const float2* R = rep + (size_t)slot[sv] * kFftN;
-    const int* M = shift + (size_t)bin * nseg;
-    float2 r[8], x[8];
-    float acc[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        r[q] = R[t + 256 * q];
-        x[q] = X[t + 256 * q];
-        acc[q] = 0.f;
-    }
-#pragma unroll 1
-    for (int s = 0; s < nseg; ++s) {
-        float2 v[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            v[q] = make_float2(x[q].x * r[q].x + x[q].y * r[q].y, x[q].x * r[q].y - x[q].y * r[q].x);
-        const float2* Xn = X + (size_t)(s + 1 < nseg ? s + 1 : s) * kFftN;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) x[q] = Xn[t + 256 * q];
-        const int m = __builtin_amdgcn_readfirstlane(M[s]);
-        lds_barrier();                         // (the previous segment's LDS reads are done)
-        fft2048(v, lds, ftw, t);
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            magbuf[t + 256 * q] = __builtin_amdgcn_sqrtf(v[q].x * v[q].x + v[q].y * v[q].y);
-        lds_barrier();
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            acc[q] += magbuf[(t + 256 * q + m) & (kFftN - 1)] * (1.0f / kFftN);
-    }
-    lds_barrier();                             // (the statistics write the plane the sums just read)
-    const float sc = 1.0f / (float)nseg;
-    float mag[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) mag[q] = acc[q] * sc;
-    int amax; float peak, mean, sd, lo, hi;
-    corr_stats8(mag, t, magbuf, red, amax, peak, mean, sd, lo, hi);
-    if (t == 0) {
-        const size_t c = (size_t)(bin0 + bin) * nsv + sv;
-        gpsmi_peak p; p.argmax = amax; p.peak = peak; p.mean = mean; p.std = sd;
-        out[c] = p;
-        if (nbr) nbr[c] = make_float2(lo, hi);
-    }
-}
-
-// Native 16368 path: the fold of segment s of a bin, acq_fold_kernel's arithmetic on iq advanced by
-// s * n_coh * L samples.  Grid (lag blocks, bins of this launch, segments); xout [bin][nseg][L].
-template <int FMT>
-__global__ __launch_bounds__(256) void acq_fold_nc_kernel(
-    const void* __restrict__ iq, const float* __restrict__ t32,
-    const float* __restrict__ omega, int n_coh, int nseg, int L, float2* __restrict__ xout) {
-    const int m = blockIdx.x * 256 + threadIdx.x, bin = blockIdx.y, seg = blockIdx.z;
-    if (m >= L) return;
-    const float om = omega[bin];
-    const size_t base = (size_t)seg * n_coh * L;
-    float ar = 0.f, ai = 0.f;
-    for (int i = 0; i < n_coh; ++i) {
-        const int k = i * L + m;
-        const float2 v = load_iq<FMT>(iq, base + k);
-        float sn, co;
-        sincosf(mul_rn(om, t32[k]), &sn, &co);
-        ar += co * v.x + sn * v.y;
-        ai += co * v.y - sn * v.x;
-    }
-    const float sc = 1.0f / (float)n_coh;
-    xout[((size_t)bin * nseg + seg) * L + m] = make_float2(ar * sc, ai * sc);
-}
-
-}  // namespace gpsmi
+#include "gpsmi_acq_search.h"
 
 using namespace gpsmi;
 
@@ -431,6 +78,8 @@ struct gpsmi_acq {
     DevBuf<gpsmi_wtrk_state> d_ws;          // [kWtrkMaxHits]
     DevBuf<gpsmi_wtrk_bit> d_wb;
     int iq_fmt = GPSMI_IQ_C64;              // what the iq pointers of the search calls point to
+    // bytes of `n` samples in the handle's input format
+    size_t iq_bytes(size_t n) const { return n * (iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)); }
     float last_ms = 0.f;
     bool pending = false;
     // released bottom up: the events, then the stream, then (above) the device buffers
@@ -469,8 +118,7 @@ static int acq_reserve_cells(gpsmi_acq* h, size_t cells) {
 static int acq_upload(gpsmi_acq* h, const void* iq, size_t count) {
     const int rc = h->d_iq.reserve(count, "gpsmi_acq input block");
     if (rc) return rc;
-    GPSMI_HIP(hipMemcpyAsync(h->d_iq.p, iq, count * (h->iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)),
-                             hipMemcpyHostToDevice, h->stream));
+    GPSMI_HIP(hipMemcpyAsync(h->d_iq.p, iq, h->iq_bytes(count), hipMemcpyHostToDevice, h->stream));
     return GPSMI_OK;
 }
 
@@ -630,78 +278,7 @@ static int acq_copy_out(gpsmi_acq* h, int nbins, int nsv, gpsmi_peak* out, void*
     return GPSMI_OK;
 }
 
-static int acq_search_impl(gpsmi_acq* h, const void* d_iq, size_t n, const int32_t* prn, int nsv,
-                           const double* freqs, int nbins, int n_avg, gpsmi_peak* out,
-                           void* out_dev, float* nbr, bool wait = true) {
-    GPSMI_REQUIRE(h && d_iq && prn && freqs, "null argument");
-    GPSMI_REQUIRE(out || out_dev, "no output requested");
-    GPSMI_REQUIRE(nsv >= 0 && nsv <= GPSMI_MAX_PRN, "nsv out of range");
-    GPSMI_REQUIRE(nbins >= 0 && nbins <= 65535, "nbins out of range");
-    GPSMI_REQUIRE(n_avg >= 1 && n_avg <= h->cfg.n_cyc, "n_avg out of range 1..n_cyc");
-    const int cs = h->cfg.code_samples;
-    GPSMI_REQUIRE(n >= (size_t)n_avg * cs, "iq shorter than n_avg code periods");
-    for (int i = 0; i < nsv; ++i) {
-        GPSMI_REQUIRE(prn[i] >= 1 && prn[i] <= GPSMI_MAX_PRN, "prn out of range 1..37");
-        if (!(h->direct ? h->have_time[prn[i]] : h->have_rep[prn[i]]))
-            return fail(GPSMI_E_STATE, "no replica set for PRN %d", (int)prn[i]);
-    }
-    h->last_ms = 0.f;
-    if (nsv == 0 || nbins == 0) return GPSMI_OK;            // empty search: nothing to do
-    GPSMI_HIP(hipSetDevice(h->cfg.device));
-    int rc = acq_reserve(h, nbins, nsv);
-    if (rc) return rc;
-    rc = acq_stage(h, prn, nsv, freqs, nbins);
-    if (rc) return rc;
-    if (h->direct) {
-        const size_t cells = (size_t)nbins * nsv;
-        if ((rc = h->d_fold.reserve((size_t)nbins * cs, "gpsmi_acq folded samples")) ||
-            (!h->pfa && (rc = h->d_mag.reserve(cells * cs, "gpsmi_acq magnitudes"))) ||
-            (rc = acq_reserve_cells(h, cells)))
-            return rc;
-    }
-    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
-    if (h->direct) {
-        const int ncell = nbins * nsv;
-        with_fmt(h->iq_fmt, [&](auto fmt) {
-            hipLaunchKernelGGL(acq_fold_kernel<decltype(fmt)::value>, dim3((cs + 255) / 256, nbins), dim3(256), 0,
-                               h->stream, d_iq, h->d_t32.p, h->d_omega.p, n_avg, cs, h->d_fold.p);
-        });
-        hipLaunchKernelGGL(acq_cells_kernel, dim3((ncell + 255) / 256), dim3(256), 0, h->stream,
-                           h->d_xsel.p, h->d_rsel.p, h->d_slot.p, nsv, ncell);
-        if (h->pfa)              // transform, product, transform and statistics in one launch
-            pfa_corr_launch(h->stream, h->d_fold.p, h->d_xsel.p, h->d_rsel.p, ncell, h->d_RSp.p, h->d_stats.p);
-        else if (h->big)
-            big_corr_launch(h->stream, h->d_fold.p, h->d_xsel.p, h->d_rsel.p, ncell, cs, h->d_RS.p, h->d_S.p,
-                            h->d_tw.p, h->d_twN.p, h->d_mag.p);
-        else
-            hipLaunchKernelGGL(circ_corr_direct_kernel,
-                               dim3((cs + kDirLagsPerWg - 1) / kDirLagsPerWg, ncell), dim3(256), 0,
-                               h->stream, h->d_fold.p, h->d_rep_time.p, h->d_xsel.p, h->d_rsel.p, cs,
-                               h->d_mag.p);
-        if (!h->pfa)
-            hipLaunchKernelGGL(corr_stats_kernel, dim3(ncell), dim3(256), 0, h->stream, h->d_mag.p, cs,
-                               h->d_stats.p);
-        hipLaunchKernelGGL(acq_peaks_kernel, dim3((ncell + 255) / 256), dim3(256), 0, h->stream,
-                           h->d_stats.p, h->d_peaks.p, nbr ? h->d_nbr.p : nullptr, ncell);
-    } else {
-        // four groups of 256 threads for the long coherent searches (acq_spectrum_kernel)
-        with_value<4, 1>(n_avg >= 4 ? 4 : 1, [&](auto g) { with_fmt(h->iq_fmt, [&](auto fmt) {
-            constexpr int G = decltype(g)::value;
-            hipLaunchKernelGGL((acq_spectrum_kernel<G, decltype(fmt)::value>), dim3(nbins), dim3(256 * G), 0,
-                               h->stream, d_iq, h->d_t32.p, h->d_omega.p, n_avg, h->d_spec.p, h->d_tw.p);
-        }); });
-        hipLaunchKernelGGL(acq_corr_kernel, dim3(nsv, nbins), dim3(256), 0, h->stream, h->d_spec.p,
-                           h->d_rep.p, h->d_slot.p, h->d_peaks.p, nsv, h->d_tw.p,
-                           nbr ? h->d_nbr.p : nullptr);
-    }
-    GPSMI_HIP(hipGetLastError());
-    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
-    rc = acq_copy_out(h, nbins, nsv, out, out_dev, nbr);
-    if (rc || !wait) return rc;
-    return gpsmi_acq_wait(h);
-}
-
-// Scratch of one chunk of bins of a non-coherent search: the spectra / folded samples of all its
+// Scratch of one chunk of bins of a segmented search: the spectra / folded samples of all its
 // segments.  Longer searches take the bins in chunks; the magnitude sums stay in registers.
 constexpr size_t kNcScratchMax = size_t(512) << 20;
 
@@ -717,119 +294,175 @@ static int deep_shift(double f_hz, const DeepShift& d, int s, int n_coh, int cs)
     return (int)(r < 0.0 ? r + (double)cs : r);
 }
 
-// a bin's rotated sums need all its segments in one launch: no chunking over segments
-static int deep_span_check(int n_seg, int cs) {
-    if ((size_t)n_seg * cs * sizeof(float2) > kNcScratchMax)
-        return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_search_deep: the %d segments of one bin exceed the "
-                                         "%zu MiB of scratch", n_seg, kNcScratchMax >> 20);
-    return GPSMI_OK;
-}
+// What tells the searches apart.  segmented = false: gpsmi_acq_search* (n_coh is its n_avg, n_seg 1,
+// no rotation); true: gpsmi_acq_search_nc* and, with `deep`, gpsmi_acq_search_deep*.
+struct AcqSearch {
+    int n_coh, n_seg;
+    const DeepShift* deep;
+    bool wait;                               // false: the caller collects the table with gpsmi_acq_wait
+    bool segmented;
+};
 
-static int acq_search_nc_impl(gpsmi_acq* h, const void* d_iq, size_t n, const int32_t* prn, int nsv,
-                              const double* freqs, int nbins, int n_coh, int n_seg, gpsmi_peak* out,
-                              void* out_dev, float* nbr, const DeepShift* deep = nullptr) {
-    GPSMI_REQUIRE(h && d_iq && prn && freqs, "null argument");
-    if (deep) {
-        GPSMI_REQUIRE(std::isfinite(deep->carrier_hz) && deep->carrier_hz > 0.0, "carrier_hz must be positive");
-        GPSMI_REQUIRE(std::isfinite(deep->f_offset_hz), "f_offset_hz must be finite");
+// The arguments of every search entry point, before anything is uploaded or enqueued.  on_host: iq
+// and out are the caller's host arrays (the host-input entry points have no out_dev).
+static int acq_check_search(const gpsmi_acq* h, const void* iq, bool on_host, size_t n, const int32_t* prn,
+                            int nsv, const double* freqs, int nbins, const AcqSearch& s,
+                            const gpsmi_peak* out, const void* out_dev) {
+    GPSMI_REQUIRE(h && iq && prn && freqs && (out || !on_host), "null argument");
+    if (s.deep) {
+        GPSMI_REQUIRE(std::isfinite(s.deep->carrier_hz) && s.deep->carrier_hz > 0.0, "carrier_hz must be positive");
+        GPSMI_REQUIRE(std::isfinite(s.deep->f_offset_hz), "f_offset_hz must be finite");
     }
     GPSMI_REQUIRE(out || out_dev, "no output requested");
     GPSMI_REQUIRE(nsv >= 0 && nsv <= GPSMI_MAX_PRN, "nsv out of range");
     GPSMI_REQUIRE(nbins >= 0 && nbins <= 65535, "nbins out of range");
-    GPSMI_REQUIRE(n_coh >= 1 && n_coh <= h->cfg.n_cyc, "n_coh out of range 1..n_cyc");
-    GPSMI_REQUIRE(n_seg >= 1 && n_seg <= 65535, "n_seg out of range 1..65535");
     const int cs = h->cfg.code_samples;
-    GPSMI_REQUIRE(n / ((size_t)n_coh * cs) >= (size_t)n_seg, "iq shorter than n_seg * n_coh code periods");
+    if (!s.segmented) {
+        GPSMI_REQUIRE(s.n_coh >= 1 && s.n_coh <= h->cfg.n_cyc, "n_avg out of range 1..n_cyc");
+        GPSMI_REQUIRE(n >= (size_t)s.n_coh * cs, "iq shorter than n_avg code periods");
+    } else {
+        GPSMI_REQUIRE(s.n_coh >= 1 && s.n_coh <= h->cfg.n_cyc, "n_coh out of range 1..n_cyc");
+        GPSMI_REQUIRE(s.n_seg >= 1 && s.n_seg <= 65535, "n_seg out of range 1..65535");
+        GPSMI_REQUIRE(n / ((size_t)s.n_coh * cs) >= (size_t)s.n_seg, "iq shorter than n_seg * n_coh code periods");
+    }
     for (int i = 0; i < nsv; ++i) {
         GPSMI_REQUIRE(prn[i] >= 1 && prn[i] <= GPSMI_MAX_PRN, "prn out of range 1..37");
         if (!(h->direct ? h->have_time[prn[i]] : h->have_rep[prn[i]]))
             return fail(GPSMI_E_STATE, "no replica set for PRN %d", (int)prn[i]);
     }
-    if (h->direct && !h->pfa)
+    if (s.segmented && h->direct && !h->pfa)
         return fail(GPSMI_E_UNSUPPORTED, "%s: code_samples 2048 or the native 16368 "
                                          "correlation only (not the \"codephase\" time-domain paths)",
-                    deep ? "gpsmi_acq_search_deep" : "gpsmi_acq_search_nc");
-    const size_t per_bin = (size_t)n_seg * cs * sizeof(float2);
-    if (deep) {
+                    s.deep ? "gpsmi_acq_search_deep" : "gpsmi_acq_search_nc");
+    if (s.deep) {
         for (int b = 0; b < nbins; ++b)
             GPSMI_REQUIRE(std::isfinite(freqs[b]), "freqs_hz must be finite");
-        if (deep_span_check(n_seg, cs)) return GPSMI_E_UNSUPPORTED;
+        // a bin's rotated sums need all its segments in one launch: no chunking over segments
+        if ((size_t)s.n_seg * cs * sizeof(float2) > kNcScratchMax)
+            return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_search_deep: the %d segments of one bin exceed the "
+                                             "%zu MiB of scratch", s.n_seg, kNcScratchMax >> 20);
     }
+    return GPSMI_OK;
+}
+
+// Code lengths other than 2048, bins b0 .. b0 + nb - 1: fold into x [bin][n_seg][cs], the cell tables,
+// the correlation with its statistics into d_stats.  The coherent search is b0 = 0, nb = nbins,
+// n_seg = 1, and the only one with the time-domain correlations.
+static void acq_direct_chunk(gpsmi_acq* h, const void* d_iq, const AcqSearch& s, float2* x, int b0, int nb,
+                             int nsv) {
+    const int cs = h->cfg.code_samples, c0 = b0 * nsv, ncell = nb * nsv;
+    int *xsel = h->d_xsel.p + c0, *rsel = h->d_rsel.p + c0;
+    DirStats* stats = h->d_stats.p + c0;
+    with_fmt(h->iq_fmt, [&](auto fmt) {
+        hipLaunchKernelGGL(acq_fold_kernel<decltype(fmt)::value>, dim3((cs + 255) / 256, nb, s.n_seg), dim3(256),
+                           0, h->stream, d_iq, h->d_t32.p, h->d_omega.p + b0, s.n_coh, s.n_seg, cs, x);
+    });
+    hipLaunchKernelGGL(acq_cells_kernel, dim3((ncell + 255) / 256), dim3(256), 0, h->stream, xsel, rsel,
+                       h->d_slot.p, nsv, ncell);
+    if (h->pfa) {                // transform, product, transform and statistics in one launch
+        if (!s.segmented) pfa_corr_launch<0>(h->stream, x, xsel, rsel, ncell, h->d_RSp.p, stats);
+        else if (!s.deep) pfa_corr_launch<2>(h->stream, x, xsel, rsel, ncell, h->d_RSp.p, stats, s.n_seg);
+        else pfa_corr_launch<3>(h->stream, x, xsel, rsel, ncell, h->d_RSp.p, stats, s.n_seg,
+                                h->d_shift.p + (size_t)b0 * s.n_seg);
+        return;
+    }
+    if (h->big)
+        big_corr_launch(h->stream, x, xsel, rsel, ncell, cs, h->d_RS.p, h->d_S.p, h->d_tw.p, h->d_twN.p,
+                        h->d_mag.p);
+    else
+        hipLaunchKernelGGL(circ_corr_direct_kernel, dim3((cs + kDirLagsPerWg - 1) / kDirLagsPerWg, ncell),
+                           dim3(256), 0, h->stream, x, h->d_rep_time.p, xsel, rsel, cs, h->d_mag.p);
+    hipLaunchKernelGGL(corr_stats_kernel, dim3(ncell), dim3(256), 0, h->stream, h->d_mag.p, cs, stats);
+}
+
+// Every search, on device-resident iq whose arguments acq_check_search has passed.
+static int acq_search_run(gpsmi_acq* h, const void* d_iq, const int32_t* prn, int nsv, const double* freqs,
+                          int nbins, AcqSearch s, gpsmi_peak* out, void* out_dev, float* nbr) {
     // one segment of the 16368 path: the coherent search itself (MODE 0 forms its statistics from the
     // unscaled squares; MODE 2's would differ in the last bits of std)
-    if (h->pfa && n_seg == 1)
-        return acq_search_impl(h, d_iq, n, prn, nsv, freqs, nbins, n_coh, out, out_dev, nbr);
+    if (h->pfa && s.segmented && s.n_seg == 1) s = AcqSearch{s.n_coh, 1, nullptr, s.wait, false};
     h->last_ms = 0.f;
-    if (nsv == 0 || nbins == 0) return GPSMI_OK;
+    if (nsv == 0 || nbins == 0) return GPSMI_OK;            // empty search: nothing to do
     GPSMI_HIP(hipSetDevice(h->cfg.device));
+    const int cs = h->cfg.code_samples, n_seg = s.n_seg;
+    const size_t cells = (size_t)nbins * nsv;
     int rc = acq_reserve(h, nbins, nsv);
     if (rc) return rc;
-    size_t nbc = kNcScratchMax / per_bin;
-    nbc = nbc < 1 ? 1 : nbc > (size_t)nbins ? (size_t)nbins : nbc;
-    rc = h->d_nc.reserve(nbc * n_seg * cs, "gpsmi_acq segment scratch");
-    if (rc) return rc;
-    const size_t cells = (size_t)nbins * nsv;
-    if (h->pfa && (rc = acq_reserve_cells(h, cells))) return rc;
+    // where the folds go, and how many bins of them at a time: a coherent search is one chunk
+    size_t nbc = (size_t)nbins;
+    float2* x = nullptr;
+    if (s.segmented) {
+        nbc = kNcScratchMax / ((size_t)n_seg * cs * sizeof(float2));
+        nbc = nbc < 1 ? 1 : nbc > (size_t)nbins ? (size_t)nbins : nbc;
+        if ((rc = h->d_nc.reserve(nbc * n_seg * cs, "gpsmi_acq segment scratch"))) return rc;
+        x = h->d_nc.p;
+    } else if (h->direct) {
+        if ((rc = h->d_fold.reserve((size_t)nbins * cs, "gpsmi_acq folded samples")) ||
+            (!h->pfa && (rc = h->d_mag.reserve(cells * cs, "gpsmi_acq magnitudes"))))
+            return rc;
+        x = h->d_fold.p;
+    } else {
+        x = h->d_spec.p;
+    }
+    if (h->direct && (rc = acq_reserve_cells(h, cells))) return rc;
     rc = acq_stage(h, prn, nsv, freqs, nbins);
     if (rc) return rc;
-    if (deep) {
+    if (s.deep) {
         std::vector<int> shift;
         const size_t ns = (size_t)nbins * n_seg;
         try { shift.resize(ns); } catch (const std::bad_alloc&) {
             return fail(GPSMI_E_NOMEM, "gpsmi_acq_search_deep: out of host memory");
         }
         for (int b = 0; b < nbins; ++b)
-            for (int s = 0; s < n_seg; ++s)
-                shift[(size_t)b * n_seg + s] = deep_shift(freqs[b], *deep, s, n_coh, cs);
+            for (int sg = 0; sg < n_seg; ++sg)
+                shift[(size_t)b * n_seg + sg] = deep_shift(freqs[b], *s.deep, sg, s.n_coh, cs);
         if ((rc = h->d_shift.reserve(ns, "gpsmi_acq lag rotations"))) return rc;
         GPSMI_HIP(hipMemcpyAsync(h->d_shift.p, shift.data(), ns * sizeof(int), hipMemcpyHostToDevice,
                                  h->stream));
         GPSMI_HIP(hipStreamSynchronize(h->stream));      // (the table is pageable and leaves scope here)
     }
+    float2* d_nbr = nbr ? h->d_nbr.p : nullptr;
     GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
     for (int b0 = 0; b0 < nbins; b0 += (int)nbc) {
         const int nb = nbins - b0 < (int)nbc ? nbins - b0 : (int)nbc;
-        const float* om = h->d_omega.p + b0;
-        if (h->pfa) {
-            const dim3 grid((cs + 255) / 256, nb, n_seg);
-            with_fmt(h->iq_fmt, [&](auto fmt) {
-                hipLaunchKernelGGL(acq_fold_nc_kernel<decltype(fmt)::value>, grid, dim3(256), 0, h->stream, d_iq,
-                                   h->d_t32.p, om, n_coh, n_seg, cs, h->d_nc.p);
-            });
-            const int c0 = b0 * nsv, ncc = nb * nsv;
-            hipLaunchKernelGGL(acq_cells_kernel, dim3((ncc + 255) / 256), dim3(256), 0, h->stream,
-                               h->d_xsel.p + c0, h->d_rsel.p + c0, h->d_slot.p, nsv, ncc);
-            if (deep)
-                pfa_deep_corr_launch(h->stream, h->d_nc.p, h->d_xsel.p + c0, h->d_rsel.p + c0, ncc, n_seg,
-                                     h->d_RSp.p, h->d_stats.p + c0, h->d_shift.p + (size_t)b0 * n_seg);
-            else
-                pfa_nc_corr_launch(h->stream, h->d_nc.p, h->d_xsel.p + c0, h->d_rsel.p + c0, ncc, n_seg, h->d_RSp.p,
-                                   h->d_stats.p + c0);
-        } else {
-            const dim3 grid(nb, n_seg);
-            with_value<4, 1>(n_coh >= 4 ? 4 : 1, [&](auto g) { with_fmt(h->iq_fmt, [&](auto fmt) {
-                constexpr int G = decltype(g)::value;
-                hipLaunchKernelGGL((acq_spectrum_nc_kernel<G, decltype(fmt)::value>), grid, dim3(256 * G), 0,
-                                   h->stream, d_iq, h->d_t32.p, om, n_coh, n_seg, h->d_nc.p, h->d_tw.p);
-            }); });
-            if (deep)
-                hipLaunchKernelGGL(acq_deep_corr_kernel, dim3(nsv, nb), dim3(256), 0, h->stream, h->d_nc.p,
-                                   h->d_rep.p, h->d_slot.p, h->d_peaks.p, nsv, n_seg, b0, h->d_tw.p,
-                                   nbr ? h->d_nbr.p : nullptr, h->d_shift.p + (size_t)b0 * n_seg);
-            else
-                hipLaunchKernelGGL(acq_nc_corr_kernel, dim3(nsv, nb), dim3(256), 0, h->stream, h->d_nc.p,
-                                   h->d_rep.p, h->d_slot.p, h->d_peaks.p, nsv, n_seg, b0, h->d_tw.p,
-                                   nbr ? h->d_nbr.p : nullptr);
+        if (h->direct) {
+            acq_direct_chunk(h, d_iq, s, x, b0, nb, nsv);
+            continue;
         }
+        // four groups of 256 threads for the long coherent integrations (acq_spectrum_kernel)
+        with_value<4, 1>(s.n_coh >= 4 ? 4 : 1, [&](auto g) { with_fmt(h->iq_fmt, [&](auto fmt) {
+            constexpr int G = decltype(g)::value;
+            hipLaunchKernelGGL((acq_spectrum_kernel<G, decltype(fmt)::value>), dim3(nb, n_seg), dim3(256 * G), 0,
+                               h->stream, d_iq, h->d_t32.p, h->d_omega.p + b0, s.n_coh, n_seg, x, h->d_tw.p);
+        }); });
+        with_value<0, 2, 1>(!s.segmented ? 0 : s.deep ? 2 : 1, [&](auto mode) {
+            hipLaunchKernelGGL(acq_corr_kernel<decltype(mode)::value>, dim3(nsv, nb), dim3(256), 0, h->stream, x,
+                               h->d_rep.p, h->d_slot.p, h->d_peaks.p, nsv, n_seg, b0, h->d_tw.p, d_nbr,
+                               s.deep ? h->d_shift.p + (size_t)b0 * n_seg : nullptr);
+        });
     }
-    if (h->pfa)
+    if (h->direct)
         hipLaunchKernelGGL(acq_peaks_kernel, dim3(((int)cells + 255) / 256), dim3(256), 0, h->stream,
-                           h->d_stats.p, h->d_peaks.p, nbr ? h->d_nbr.p : nullptr, (int)cells);
+                           h->d_stats.p, h->d_peaks.p, d_nbr, (int)cells);
     GPSMI_HIP(hipGetLastError());
     GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
     rc = acq_copy_out(h, nbins, nsv, out, out_dev, nbr);
-    if (rc) return rc;
+    if (rc || !s.wait) return rc;
     return gpsmi_acq_wait(h);
+}
+
+// An entry point: the checks, host input uploaded (as much of it as the search reads), the search.
+static int acq_search(gpsmi_acq* h, const void* iq, bool on_host, size_t n, const int32_t* prn, int nsv,
+                      const double* freqs, int nbins, const AcqSearch& s, gpsmi_peak* out, void* out_dev,
+                      float* nbr) {
+    int rc = acq_check_search(h, iq, on_host, n, prn, nsv, freqs, nbins, s, out, out_dev);
+    if (rc) return rc;
+    if (on_host) {
+        GPSMI_HIP(hipSetDevice(h->cfg.device));
+        if ((rc = acq_upload(h, iq, (size_t)s.n_seg * s.n_coh * h->cfg.code_samples))) return rc;
+        iq = h->d_iq.p;
+    }
+    return acq_search_run(h, iq, prn, nsv, freqs, nbins, s, out, out_dev, nbr);
 }
 
 int gpsmi_acq_wait(gpsmi_acq* h) {
@@ -845,13 +478,15 @@ int gpsmi_acq_wait(gpsmi_acq* h) {
 int gpsmi_acq_search_dev_async(gpsmi_acq* h, const void* d_iq, size_t n, const int32_t* prn,
                                int nsv, const double* freqs, int nbins, int n_avg,
                                gpsmi_peak* out, void* out_dev) {
-    return acq_search_impl(h, d_iq, n, prn, nsv, freqs, nbins, n_avg, out, out_dev, nullptr, false);
+    return acq_search(h, d_iq, false, n, prn, nsv, freqs, nbins, {n_avg, 1, nullptr, false, false}, out, out_dev,
+                      nullptr);
 }
 
 int gpsmi_acq_search_dev(gpsmi_acq* h, const void* d_iq, size_t n, const int32_t* prn, int nsv,
                          const double* freqs, int nbins, int n_avg, gpsmi_peak* out,
                          void* out_dev) {
-    return acq_search_impl(h, d_iq, n, prn, nsv, freqs, nbins, n_avg, out, out_dev, nullptr);
+    return acq_search(h, d_iq, false, n, prn, nsv, freqs, nbins, {n_avg, 1, nullptr, true, false}, out, out_dev,
+                      nullptr);
 }
 
 int gpsmi_acq_search(gpsmi_acq* h, const float* iq, size_t n, const int32_t* prn, int nsv,
@@ -861,58 +496,36 @@ int gpsmi_acq_search(gpsmi_acq* h, const float* iq, size_t n, const int32_t* prn
 
 int gpsmi_acq_search_ex(gpsmi_acq* h, const float* iq, size_t n, const int32_t* prn, int nsv,
                         const double* freqs, int nbins, int n_avg, gpsmi_peak* out, float* nbr) {
-    GPSMI_REQUIRE(h && iq && out, "null argument");
-    GPSMI_REQUIRE(n_avg >= 1 && n_avg <= h->cfg.n_cyc, "n_avg out of range 1..n_cyc");
-    GPSMI_REQUIRE(n >= (size_t)n_avg * h->cfg.code_samples, "iq shorter than n_avg code periods");
-    GPSMI_HIP(hipSetDevice(h->cfg.device));
-    const size_t need = (size_t)n_avg * h->cfg.code_samples;
-    const int rc = acq_upload(h, iq, need);
-    if (rc) return rc;
-    return acq_search_impl(h, h->d_iq.p, need, prn, nsv, freqs, nbins, n_avg, out, nullptr, nbr);
+    return acq_search(h, iq, true, n, prn, nsv, freqs, nbins, {n_avg, 1, nullptr, true, false}, out, nullptr, nbr);
 }
 
 int gpsmi_acq_search_nc_dev(gpsmi_acq* h, const void* d_iq, size_t n, const int32_t* prn, int nsv,
                             const double* freqs_hz, int nbins, int n_coh, int n_seg, gpsmi_peak* out,
                             void* out_dev) {
-    return acq_search_nc_impl(h, d_iq, n, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, out_dev, nullptr);
-}
-
-// host input of the non-coherent and the deep search: upload, then the search on the copy
-static int acq_search_nc_host(gpsmi_acq* h, const void* iq, size_t n, const int32_t* prn, int nsv,
-                              const double* freqs_hz, int nbins, int n_coh, int n_seg, gpsmi_peak* out,
-                              float* nbr, const DeepShift* deep) {
-    GPSMI_REQUIRE(h && iq && out, "null argument");
-    GPSMI_REQUIRE(n_coh >= 1 && n_coh <= h->cfg.n_cyc, "n_coh out of range 1..n_cyc");
-    GPSMI_REQUIRE(n_seg >= 1 && n_seg <= 65535, "n_seg out of range 1..65535");
-    GPSMI_REQUIRE(n / ((size_t)n_coh * h->cfg.code_samples) >= (size_t)n_seg,
-                  "iq shorter than n_seg * n_coh code periods");
-    if (deep && deep_span_check(n_seg, h->cfg.code_samples)) return GPSMI_E_UNSUPPORTED;   // (before the upload)
-    GPSMI_HIP(hipSetDevice(h->cfg.device));
-    const size_t need = (size_t)n_seg * n_coh * h->cfg.code_samples;
-    const int rc = acq_upload(h, iq, need);
-    if (rc) return rc;
-    return acq_search_nc_impl(h, h->d_iq.p, need, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, nullptr, nbr,
-                              deep);
+    return acq_search(h, d_iq, false, n, prn, nsv, freqs_hz, nbins, {n_coh, n_seg, nullptr, true, true}, out,
+                      out_dev, nullptr);
 }
 
 int gpsmi_acq_search_nc(gpsmi_acq* h, const void* iq, size_t n, const int32_t* prn, int nsv,
                         const double* freqs_hz, int nbins, int n_coh, int n_seg, gpsmi_peak* out,
                         float* nbr) {
-    return acq_search_nc_host(h, iq, n, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, nbr, nullptr);
+    return acq_search(h, iq, true, n, prn, nsv, freqs_hz, nbins, {n_coh, n_seg, nullptr, true, true}, out, nullptr,
+                      nbr);
 }
 
 int gpsmi_acq_search_deep(gpsmi_acq* h, const void* iq, size_t n, const int32_t* prn, int nsv,
                           const double* freqs_hz, int nbins, int n_coh, int n_seg, double carrier_hz,
                           double f_offset_hz, gpsmi_peak* out, float* nbr) {
     const DeepShift d{carrier_hz, f_offset_hz};
-    return acq_search_nc_host(h, iq, n, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, nbr, &d);
+    return acq_search(h, iq, true, n, prn, nsv, freqs_hz, nbins, {n_coh, n_seg, &d, true, true}, out, nullptr, nbr);
 }
 
 int gpsmi_acq_search_deep_dev(gpsmi_acq* h, const void* d_iq, size_t n, const int32_t* prn, int nsv,
                               const double* freqs_hz, int nbins, int n_coh, int n_seg, double carrier_hz,
                               double f_offset_hz, gpsmi_peak* out, void* out_dev) {
     const DeepShift d{carrier_hz, f_offset_hz};
-    return acq_search_nc_impl(h, d_iq, n, prn, nsv, freqs_hz, nbins, n_coh, n_seg, out, out_dev, nullptr, &d);
+    return acq_search(h, d_iq, false, n, prn, nsv, freqs_hz, nbins, {n_coh, n_seg, &d, true, true}, out, out_dev,
+                      nullptr);
 }
 
 // ---- refinement of weak / deep hits (kernels and plan: gpsmi_refine.h) ------------------------

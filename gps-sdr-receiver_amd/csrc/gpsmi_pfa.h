@@ -558,42 +558,23 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
     }
 }
 
-// all correlations of `ncell` cells on `stream`, statistics included
+// all correlations of `ncell` cells on `stream`, statistics included.  MODE 0: cells cell0 ..
+// cell0 + ncell - 1 of xsel, rsel and stats.  MODE 2 (non-coherent) and 3 (deep): `cell0` carries the
+// segment count as the kernel's does, x is [xsel][nseg][L], and xsel, rsel and stats point at the
+// launch's first cell; MODE 3 adds shift [xsel][nseg], the lag rotation of every (bin, segment) of the
+// launch, each in 0 .. L - 1.
+template <int MODE = 0>
 inline void pfa_corr_launch(hipStream_t stream, const float2* x, const int* xsel, const int* rsel,
-                            int ncell, float2* RS, DirStats* stats, int cell0 = 0) {
+                            int ncell, float2* RS, DirStats* stats, int cell0 = 0, const int* shift = nullptr) {
+    static_assert(MODE == 0 || MODE == 2 || MODE == 3, "the replica's MODE 1 is pfa_replica_launch");
     if (ncell <= 0) return;
     int dev = 0, n_cu = 256;
     if (hipGetDevice(&dev) == hipSuccess)
         (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
     const int grid = ncell < n_cu ? ncell : n_cu;
-    hipLaunchKernelGGL(pfa_corr_kernel<0>, dim3(grid), dim3(kPfaThreads), 0, stream, x,
-                       (const float*)nullptr, xsel, rsel, RS, cell0, ncell, stats);
-}
-
-// the non-coherent form (MODE 2): ncell cells of nseg segments each, x [xsel][nseg][L]; xsel, rsel and
-// stats point at the launch's first cell
-inline void pfa_nc_corr_launch(hipStream_t stream, const float2* x, const int* xsel, const int* rsel,
-                               int ncell, int nseg, float2* RS, DirStats* stats) {
-    if (ncell <= 0) return;
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    const int grid = ncell < n_cu ? ncell : n_cu;
-    hipLaunchKernelGGL(pfa_corr_kernel<2>, dim3(grid), dim3(kPfaThreads), 0, stream, x,
-                       (const float*)nullptr, xsel, rsel, RS, nseg, ncell, stats);
-}
-
-// the deep form (MODE 3): pfa_nc_corr_launch plus shift [xsel][nseg], the lag rotation of every
-// (bin, segment) of the launch, each in 0 .. L - 1
-inline void pfa_deep_corr_launch(hipStream_t stream, const float2* x, const int* xsel, const int* rsel,
-                                 int ncell, int nseg, float2* RS, DirStats* stats, const int* shift) {
-    if (ncell <= 0) return;
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    const int grid = ncell < n_cu ? ncell : n_cu;
-    hipLaunchKernelGGL(pfa_corr_kernel<3>, dim3(grid), dim3(kPfaThreads), 0, stream, x,
-                       reinterpret_cast<const float*>(shift), xsel, rsel, RS, nseg, ncell, stats);
+    hipLaunchKernelGGL(pfa_corr_kernel<MODE>, dim3(grid), dim3(kPfaThreads), 0, stream, x,
+                       reinterpret_cast<const float*>(MODE == 3 ? shift : nullptr), xsel, rsel, RS, cell0, ncell,
+                       stats);
 }
 
 // spectrum of the replica in slot `slot` (rep_slot0 = table of real replicas [slots][L])

@@ -60,8 +60,8 @@ def run_point(pt, reps):
                 deep_ms_min_max=[float(np.min(deep)), float(np.max(deep))], reps=reps)
 
 
-STAT_KERNELS = ['acq_spectrum_nc_kernel', 'acq_nc_corr_kernel', 'acq_deep_corr_kernel',
-                'acq_fold_nc_kernel', 'pfa_corr_kernel<2>', 'pfa_corr_kernel<3>']
+STAT_KERNELS = ['acq_spectrum_kernel<', 'acq_corr_kernel<1>', 'acq_corr_kernel<2>',
+                'acq_fold_kernel<', 'pfa_corr_kernel<2>', 'pfa_corr_kernel<3>']
 
 
 def from_stats(path):

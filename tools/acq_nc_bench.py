@@ -86,10 +86,12 @@ def cpu_time(pt):
     return (time.perf_counter() - t0) * 1e3
 
 
-# kernels of the non-coherent search -> (point, transforms per call they carry)
-STAT_KERNELS = {'acq_spectrum_nc_kernel': (0, lambda p: p['n_seg'] * p['nbins']),
-                'acq_nc_corr_kernel': (0, lambda p: p['n_seg'] * p['nsv'] * p['nbins']),
-                'acq_fold_nc_kernel': (1, lambda p: 0),
+# kernels of the non-coherent search -> (point, transforms per call they carry).  The wipe-off folds
+# also serve the coherent search this tool alternates with (one segment a launch): their rows of a
+# trace hold both searches' launches, the FLOP/s of that row is an upper bound
+STAT_KERNELS = {'acq_spectrum_kernel<': (0, lambda p: p['n_seg'] * p['nbins']),
+                'acq_corr_kernel<1>': (0, lambda p: p['n_seg'] * p['nsv'] * p['nbins']),
+                'acq_fold_kernel<': (1, lambda p: 0),
                 'pfa_corr_kernel<2>': (1, lambda p: 2 * p['n_seg'] * p['nsv'] * p['nbins'])}
 
 

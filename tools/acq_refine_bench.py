@@ -55,7 +55,7 @@ def run_point(pt, reps):
 
 
 STAT_KERNELS = ['refine_prompt_kernel', 'refine_grid_kernel', 'refine_final_kernel',
-                'acq_spectrum_nc_kernel', 'acq_deep_corr_kernel']
+                'acq_spectrum_kernel<', 'acq_corr_kernel<2>']
 
 
 def from_stats(path):

@@ -62,7 +62,7 @@ def from_stats(path):
     import csv
     for r in csv.DictReader(open(path)):
         for k in ('wtrk_kernel', 'refine_prompt_kernel', 'refine_grid_kernel', 'refine_final_kernel',
-                  'acq_spectrum_nc_kernel', 'acq_deep_corr_kernel'):
+                  'acq_spectrum_kernel<', 'acq_corr_kernel<2>'):
             if k in r['Name'].replace(' ', ''):
                 print(f"{k:24s} calls {int(r['Calls']):4d}  mean {float(r['AverageNs']) / 1e3:9.1f} us"
                       f"  total {float(r['TotalDurationNs']) / 1e6:9.3f} ms")
