@@ -127,6 +127,18 @@ struct FftTw {
 // tw[k] = exp(-2 pi i k / 2048) in global memory; lds_tw: kFftTwFloats floats.
 // Call once per kernel by all 256 threads, then __syncthreads() before the
 // first transform.
+// (W4 = false leaves the six pass-4 values to a later fft_setup_w4: a kernel whose registers peak
+// before its first transform requests them behind that peak)
+__device__ __forceinline__ void fft_setup_w4(FftTw& f, const float2* __restrict__ tw, int t) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int r = 1; r <= 3; ++r) {
+            const float2 w = tw[r * (t + 256 * b)];
+            f.w4[b][r - 1] = fft_c{w.x, w.y};
+        }
+}
+template <bool W4 = true>
 __device__ __forceinline__ FftTw fft_setup(float* lds_tw, const float2* __restrict__ tw, int t) {
     float2* t64 = reinterpret_cast<float2*>(lds_tw);
     float2* t512 = t64 + 64;
@@ -136,13 +148,7 @@ __device__ __forceinline__ FftTw fft_setup(float* lds_tw, const float2* __restri
     FftTw f;
     f.t64 = reinterpret_cast<const fft_c*>(t64);
     f.t512 = reinterpret_cast<const fft_c*>(t512);
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 1; r <= 3; ++r) {
-            const float2 w = tw[r * (t + 256 * b)];
-            f.w4[b][r - 1] = fft_c{w.x, w.y};
-        }
+    if constexpr (W4) fft_setup_w4(f, tw, t);
     return f;
 }
 
@@ -153,39 +159,47 @@ __device__ __forceinline__ void fft2048(float2* vio, float* lds, const FftTw& tw
 #pragma unroll
     for (int r = 0; r < 8; ++r) v[r] = fft_c{vio[r].x, vio[r].y};
 
+    // Every padded index below is one per-thread base plus a compile-time multiple of r (the
+    // same elements as fft_pad / fft_pad1 of the unpadded index, t < 256, r < 8: no carry from
+    // r reaches the pad term's shift), so that an exchange keeps one address register and the
+    // rest goes into the instructions' offset fields instead of eight registers per exchange.
+    const int g0 = fft_pad(t), g1 = fft_pad1(t);     // gathers: t + 256 r -> g0 + 264 r, g1 + 288 r
     // pass 1: Ns = 1, no twiddles; out index 8 t + r
     dft8p(v);
+    {
+        const int base = fft_pad(8 * t);
 #pragma unroll
-    for (int r = 0; r < 8; ++r) buf0[fft_pad(8 * t + r)] = v[r];
+        for (int r = 0; r < 8; ++r) buf0[base + r] = v[r];
+    }
     lds_barrier();
 #pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] = buf0[fft_pad(t + 256 * r)];
+    for (int r = 0; r < 8; ++r) v[r] = buf0[g0 + 264 * r];
     // pass 2: Ns = 8, twiddle exp(-2 pi i r k / 64), out (t/8)*64 + k + 8 r
     {
         const int k = t & 7;
 #pragma unroll
         for (int r = 1; r < 8; ++r) v[r] = cmulp(v[r], tw.t64[r * k]);
         dft8p(v);
-        const int base = (t >> 3) * 64 + k;
+        const int base = fft_pad1((t >> 3) * 64 + k);
 #pragma unroll
-        for (int r = 0; r < 8; ++r) buf1[fft_pad1(base + 8 * r)] = v[r];
+        for (int r = 0; r < 8; ++r) buf1[base + 8 * r] = v[r];
     }
     lds_barrier();
 #pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] = buf1[fft_pad1(t + 256 * r)];
+    for (int r = 0; r < 8; ++r) v[r] = buf1[g1 + 288 * r];
     // pass 3: Ns = 64, twiddle exp(-2 pi i r k / 512), out (t/64)*512 + k + 64 r
     {
         const int k = t & 63;
 #pragma unroll
         for (int r = 1; r < 8; ++r) v[r] = cmulp(v[r], tw.t512[r * k]);
         dft8p(v);
-        const int base = (t >> 6) * 512 + k;
+        const int base = fft_pad((t >> 6) * 512 + k);
 #pragma unroll
-        for (int r = 0; r < 8; ++r) buf0[fft_pad(base + 64 * r)] = v[r];
+        for (int r = 0; r < 8; ++r) buf0[base + 66 * r] = v[r];
     }
     lds_barrier();
 #pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] = buf0[fft_pad(t + 256 * r)];
+    for (int r = 0; r < 8; ++r) v[r] = buf0[g0 + 264 * r];
     // pass 4: Ns = 512, radix 4, two butterflies per thread (j = t, t + 256);
     // inputs z[j + 512 r] = v[b + 2 r], outputs X[j + 512 r] -> same slots.
 #pragma unroll

@@ -24,9 +24,12 @@
 
 namespace gpsmi {
 
-// rows of the fold in flight per workgroup: three beside four channels' accumulators; all eight
-// when a workgroup serves one channel of one block (the closed loop: latency is all that counts)
-template <int CG> constexpr int kFoldDepthOf = CG == 1 ? 8 : 3;
+// rows of the fold in flight per workgroup: two beside four channels' accumulators (the batch
+// form: three make the fold the kernel's register peak, and three workgroups then leave a CU's
+// other kernels no room: DESIGN.md section 4.4, the CU budget), three at CG = 2 and 6; all
+// eight when a workgroup serves one channel of one block (the closed loop: latency is all that
+// counts)
+template <int CG> constexpr int kFoldDepthOf = CG == 1 ? 8 : CG == 4 ? 2 : 3;
 constexpr int kFoldChunk = 8;      // the row count the pipelined fold is written for (CORR_AVG of the reference)
 
 // One channel's correlation result (thread 0 parks it in LDS), and its way into the output
@@ -65,8 +68,12 @@ __device__ __forceinline__ void corr_finish(const StreamChan& s, const CorrFin& 
 
 // (FMT 1: iq holds raw uint16 (Q << 8 | I) samples, decoded on load exactly as
 // gpsmi_dev_unpack_u8iq does)
+// (waves per SIMD: at least two or three as before; the batch form at most three as well, so
+// that a build of it that needs 128 registers or fewer is still given the 136 of three waves
+// and a fourth workgroup does not take a CU's last registers from the kernels beside it)
 template <int CG, int FMT = 0>
-__global__ __launch_bounds__(256, (CG > 4 || CG == 1) ? 2 : 3) void trk_corr_kernel(
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu((CG > 4 || CG == 1) ? 2 : 3, CG == 4 ? 3 : 8))) void trk_corr_kernel(
     const void* __restrict__ iq, const gpsmi_trk_state* __restrict__ st_in,
     const int* __restrict__ delay_forced, const float2* __restrict__ rep,
     const float2* __restrict__ tw, TrkParams P, int ngroups, int nblocks,
@@ -77,9 +84,10 @@ __global__ __launch_bounds__(256, (CG > 4 || CG == 1) ? 2 : 3) void trk_corr_ker
     // Two small arrays live inside the second FFT buffer, which a transform leaves free when it
     // returns and does not write before its first barrier: the magnitudes of the statistics
     // (8 KiB) and the row factors of the fold (1 KiB, used before any transform).  39.3 KiB of
-    // LDS per workgroup, three workgroups per CU at CG = 4 by the registers (160 VGPRs, capped
-    // at 168 by the launch bounds); CG = 2 (four workgroups per CU, the fold's rows read six
-    // times per block instead of three) measured 10 % slower per batch; CG = 4 compiled for four
+    // LDS per workgroup, three workgroups per CU at CG = 4 by the registers (130 VGPRs, 136
+    // allocated: 104 of a SIMD's 512 stay free for one wave of the kernels that run beside this
+    // one in a replay step; tests/test_cu_budget.py holds the sum); CG = 2 (four workgroups per
+    // CU, the fold's rows read six times per block instead of three) measured 10 % slower per batch; CG = 4 compiled for four
     // workgroups per CU (128 registers: 68-128 bytes of scratch, the per-thread twiddles of the
     // transforms reloaded in front of every pass) 25 % slower (round 4: 0.162-0.165 against 0.131 ms).
     float* magbuf = lds + 2 * kFftPlane;
@@ -100,6 +108,13 @@ __global__ __launch_bounds__(256, (CG > 4 || CG == 1) ? 2 : 3) void trk_corr_ker
     const int t = threadIdx.x;
     const int cs = kFftN;
     constexpr int kFoldDepth = kFoldDepthOf<CG>;
+    // The batch form keeps to the CU budget: at most 136 registers, so
+    // that three workgroups leave every SIMD 104, one wave of any kernel a replay step runs
+    // beside this one.  Three moves of loads, no arithmetic: the fold two rows deep; the
+    // transforms' per-thread twiddles requested behind the fold, where the registers peak,
+    // instead of in the prologue; a channel's replica spectrum requested behind its first
+    // transform instead of in front of it (the CU's other workgroups cover that trip).
+    constexpr bool kLean = CG == 4;
     const float2* blk = static_cast<const float2*>(iq) + (size_t)b * ((size_t)cs * P.n_cyc);
     const uint16_t* rblk = static_cast<const uint16_t*>(iq) + (size_t)b * ((size_t)cs * P.n_cyc);
     const double inv_2pi = 0.15915494309189533576888376337251;
@@ -142,7 +157,7 @@ __global__ __launch_bounds__(256, (CG > 4 || CG == 1) ? 2 : 3) void trk_corr_ker
 #pragma unroll
             for (int r = 0; r < 8; ++r) x[k][r] = fetch(first + k, r);
     }
-    const FftTw ftw = fft_setup(lds_tw, tw, t);
+    FftTw ftw = fft_setup<!kLean>(lds_tw, tw, t);
     asm volatile("" : "+v"(st_prn), "+v"(st_delay), "+v"(st_om0), "+v"(st_freq), "+v"(st_phase));   // (pins the loads above this line)
 
     // ---- per-channel constants (one thread each), then one barrier
@@ -234,12 +249,14 @@ __global__ __launch_bounds__(256, (CG > 4 || CG == 1) ? 2 : 3) void trk_corr_ker
         }
     }
 
+    if constexpr (kLean) fft_setup_w4(ftw, tw, t);       // (needed in the fourth pass of the first transform)
     // ---- per channel: apply V, FFT, x conj(R), FFT, statistics
     // (1 / N of the inverse transform rides on the same factor: a power of two, so the
     // magnitudes carry the same bits as when they are scaled at the end)
     const float sc = (1.0f / (float)P.corr_avg) * (1.0f / kFftN);
     // V(m) for m = t + 256 r (base phasor and seven steps of 256 positions) applied to the fold;
-    // the replica spectrum is fetched at the same time so that its latency hides behind the FFT
+    // (CG = 1, 2, 6: the replica spectrum is fetched at the same time so that its latency hides
+    // behind the FFT)
 #pragma unroll
     for (int c = 0; c < CG; ++c) {
         const float2 e1 = vtab[c][t & 15], e2 = vtab[c][16 + (t >> 4)], s2 = step[c];
@@ -251,9 +268,11 @@ __global__ __launch_bounds__(256, (CG > 4 || CG == 1) ? 2 : 3) void trk_corr_ker
             vm = cmulp(vm, st256);
         }
     }
-    auto prepare = [&](int c, const StreamChan& s, float2 (&v)[8], float2 (&rs)[8]) {
+    auto prepare = [&](int c, float2 (&v)[8]) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) v[r] = make_float2(acc[c][r].x, acc[c][r].y);
+    };
+    auto replica = [&](const StreamChan& s, float2 (&rs)[8]) {
         const float2* R = rep + (size_t)s.prn * kFftN;
 #pragma unroll
         for (int q = 0; q < 8; ++q) rs[q] = R[t + 256 * q];
@@ -275,8 +294,10 @@ __global__ __launch_bounds__(256, (CG > 4 || CG == 1) ? 2 : 3) void trk_corr_ker
     auto single = [&](int c) {
         const StreamChan s = schan[c];
         float2 v[8], rs[8];
-        prepare(c, s, v, rs);
+        prepare(c, v);
+        if constexpr (!kLean) replica(s, rs);
         fft2048(v, lds, ftw, t);
+        if constexpr (kLean) replica(s, rs);
         times_conj(v, rs);
         lds_barrier();
         fft2048(v, lds, ftw, t);
