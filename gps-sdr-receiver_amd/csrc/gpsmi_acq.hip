@@ -706,3 +706,35 @@ int gpsmi_acq_after_trk(gpsmi_acq* later, gpsmi_trk* earlier) {
 }
 
 }  // extern "C"
+
+// ---- diagnostics: the statistics alone -----------------------------------------------------
+namespace gpsmi {
+// one workgroup per set of 2048 magnitudes, held and reduced as the correlation kernels do
+__global__ __launch_bounds__(256) void corr_stats_kernel(const float* __restrict__ mags,
+                                                         gpsmi_corr_stats* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float red[kStatsRedFloats];
+    __shared__ float magbuf[kFftN];
+    const int t = threadIdx.x;
+    const float* m = mags + (size_t)blockIdx.x * kFftN;
+    float mag[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) mag[q] = m[t + 256 * q];
+    int amax; float peak, mean, sd, lo, hi;
+    corr_stats8(mag, stats_sum8(mag), t, magbuf, red, amax, peak, mean, sd, lo, hi);
+    if (t == 0) {
+        gpsmi_corr_stats r;
+        r.argmax = amax; r.peak = peak; r.mean = mean; r.std = sd; r.lo = lo; r.hi = hi;
+        out[blockIdx.x] = r;
+    }
+}
+}  // namespace gpsmi
+
+extern "C" int gpsmi_dev_corr_stats(int device, const void* d_mags, int nsets, void* d_out) {
+    GPSMI_REQUIRE(d_mags && d_out && nsets > 0, "null pointer or no sets");
+    GPSMI_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(gpsmi::corr_stats_kernel, dim3((unsigned)nsets), dim3(256), 0, 0,
+                       static_cast<const float*>(d_mags), static_cast<gpsmi_corr_stats*>(d_out));
+    GPSMI_HIP(hipGetLastError());
+    GPSMI_HIP(hipDeviceSynchronize());
+    return GPSMI_OK;
+}

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void acq_corr_kernel(
     const int* __restrict__ slot, gpsmi_peak* __restrict__ out, int nsv, int nseg, int bin0,
     const float2* __restrict__ tw, float2* __restrict__ nbr, const int* __restrict__ shift) {
     __shared__ __attribute__((aligned(16))) float lds[kFftLdsFloats];
-    __shared__ float red[kStatsRedFloats];
+    __shared__ __attribute__((aligned(16))) float red[kStatsRedFloats];
     __shared__ __attribute__((aligned(16))) float lds_tw[kFftTwFloats];
     // the statistics' copy of the magnitudes lives in the second FFT buffer, which the transform
     // leaves free when it returns: 40.4 KiB of LDS, four workgroups per CU instead of three
@@ -193,8 +193,10 @@ __global__ __launch_bounds__(256) void acq_corr_kernel(
             else mag[q] += a[q] * (1.0f / kFftN);
         }
     };
+    float sm;                                  // the thread's share of the statistics' sum
     if constexpr (MODE == 0) {
         segment(0);
+        sm = stats_sum8(mag);
     } else {
 #pragma unroll
         for (int q = 0; q < 8; ++q) mag[q] = 0.f;
@@ -202,11 +204,20 @@ __global__ __launch_bounds__(256) void acq_corr_kernel(
         for (int s = 0; s < nseg; ++s) segment(s);
         if constexpr (MODE == 2) lds_barrier();   // (the statistics write the plane the sums just read)
         const float sc = 1.0f / (float)nseg;
+        // The means of these searches are pinned bytewise (tests/golden/acq_parent_tables.npz) to a
+        // build in which the compiler had taken the scale into the sum from the third row on: the
+        // first two rows add their rounded magnitudes, the others add the unrounded product in one
+        // fused step.  Written out, so that it no longer depends on what the compiler fuses; every
+        // other use of a magnitude takes the rounded value.
+        float raw[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) mag[q] *= sc;
+        for (int q = 0; q < 8; ++q) { raw[q] = mag[q]; mag[q] = mul_rn(raw[q], sc); }
+        sm = add_rn(add_rn(0.f, mag[0]), mag[1]);
+#pragma unroll
+        for (int q = 2; q < 8; ++q) sm = __builtin_fmaf(raw[q], sc, sm);
     }
     int amax; float peak, mean, sd, lo, hi;
-    corr_stats8(mag, t, magbuf, red, amax, peak, mean, sd, lo, hi);
+    corr_stats8(mag, sm, t, magbuf, red, amax, peak, mean, sd, lo, hi);
     if (t == 0)
         acq_store_peak(out, nbr, (size_t)(MODE == 0 ? bin : bin0 + bin) * nsv + sv, amax, peak, mean, sd, lo, hi);
 }

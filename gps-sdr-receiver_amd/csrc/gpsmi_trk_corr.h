@@ -80,7 +80,7 @@ __attribute__((amdgpu_waves_per_eu((CG > 4 || CG == 1) ? 2 : 3, CG == 4 ? 3 : 8)
     gpsmi_trk_out* __restrict__ out, JobMid* __restrict__ mid) {
     __shared__ __attribute__((aligned(16))) float lds[kFftLdsFloats];
     __shared__ __attribute__((aligned(16))) float lds_tw[kFftTwFloats];
-    __shared__ float red[kStatsRedFloats];
+    __shared__ __attribute__((aligned(16))) float red[kStatsRedFloats];
     // Two small arrays live inside the second FFT buffer, which a transform leaves free when it
     // returns and does not write before its first barrier: the magnitudes of the statistics
     // (8 KiB) and the row factors of the fold (1 KiB, used before any transform).  39.3 KiB of
@@ -305,7 +305,7 @@ __attribute__((amdgpu_waves_per_eu((CG > 4 || CG == 1) ? 2 : 3, CG == 4 ? 3 : 8)
         magnitudes(v, mag);
         // mean / std / first-index argmax over the 2048 lags, neighbours of the peak
         int bi; float bv, mean, sd, elo, ehi;
-        corr_stats8(mag, t, magbuf, red, bi, bv, mean, sd, elo, ehi);
+        corr_stats8(mag, stats_sum8(mag), t, magbuf, red, bi, bv, mean, sd, elo, ehi);
         if (t == 0) fin[c] = CorrFin{bi, bv, mean, sd, elo, ehi};
     };
     if (diag_flag(P, 64)) {                          // diagnostics: no transforms

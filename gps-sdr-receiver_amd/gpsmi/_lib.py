@@ -118,7 +118,7 @@ EXPORTS = [
     'gpsmi_device_name', 'gpsmi_dev_alloc', 'gpsmi_dev_free',
     'gpsmi_dev_upload', 'gpsmi_dev_download', 'gpsmi_dev_sync',
     'gpsmi_host_alloc', 'gpsmi_host_free',
-    'gpsmi_dev_unpack_u8iq',
+    'gpsmi_dev_unpack_u8iq', 'gpsmi_dev_corr_stats',
     'gpsmi_acq_create', 'gpsmi_acq_destroy', 'gpsmi_acq_set_replica',
     'gpsmi_acq_set_replica_time',
     'gpsmi_acq_search', 'gpsmi_acq_search_dev', 'gpsmi_acq_search_ex',
@@ -181,6 +181,7 @@ def load():
         'gpsmi_dev_download': [C.c_int, vp, vp, sz],
         'gpsmi_dev_sync': [C.c_int],
         'gpsmi_dev_unpack_u8iq': [C.c_int, vp, vp, sz],
+        'gpsmi_dev_corr_stats': [C.c_int, vp, C.c_int, vp],
         'gpsmi_acq_create': [P(Cfg), P(vp)],
         'gpsmi_acq_destroy': [vp],
         'gpsmi_acq_set_replica': [vp, C.c_int, vp],

@@ -139,6 +139,16 @@ int gpsmi_host_free(void* hptr);
  * -> complex64 (I + jQ)/127.5 - (1+1j); both pointers are device pointers.  */
 int gpsmi_dev_unpack_u8iq(int device, void* d_iq_c64, const void* d_raw_u16,
                           size_t n_samples);
+/* Diagnostics: the statistics that end every 2048-lag correlation (mean, population standard
+ * deviation, first-index argmax, the peak's two circular neighbours) on magnitudes of the
+ * caller's choosing, run exactly as the correlation kernels run them: nsets x 2048 floats, none
+ * negative, one 256-thread workgroup per set.  Both pointers are device pointers; returns when
+ * the records are written.                                                                  */
+typedef struct gpsmi_corr_stats {
+    int32_t argmax;
+    float   peak, mean, std, lo, hi;
+} gpsmi_corr_stats;
+int gpsmi_dev_corr_stats(int device, const void* d_mags_f32, int nsets, void* d_out);
 
 /* ========================================================================
  * Acquisition -- replaces the array arithmetic of gpsrecv.sweepAllSats
