@@ -12,7 +12,8 @@
 //   ifx_mask_kernel   one workgroup per block: P = (sum of the partials in group order) / (n/H - 1),
 //                     floor = median(P) (bitonic sort of the 2048 values in LDS, the mean of the two
 //                     middle ones), flag P > floor * 10^(thresh_db / 10), widen by +-dilate bins
-//                     circularly, count; more than max_bins: count -1 and an empty mask.
+//                     circularly, count; more than max_bins: count -1 and an empty mask.  The P it
+//                     thresholded is kept per block for gpsmi_ifx_last_psd (a diagnostic).
 //   ifx_apply_kernel  one workgroup per (block, run of consecutive output segments [s H, s H + H)):
 //                     transforms the frames s0 .. s0 + S in order, zeroes the masked bins, transforms
 //                     back (ifft(Y) = conj(fft(conj Y)) / L) and writes segment s = frame s's second
@@ -24,6 +25,12 @@
 //
 // No atomics: every sum has a fixed order, so the output bits do not depend on the grid, on the
 // number of blocks per call or on the run.
+//
+// The first block after create / reset stands behind a zero carry: a strong tone then starts with a
+// step at sample 0, which leaks across frame 0's spectrum.  A short block (4096 or 5120 samples:
+// 3 or 4 frames in P) is classed wideband by it and passes through jammed (count -1); a longer one
+// is excised with a wider mask than its successors (35 dB tone: some 170 bins at 20480, some 95
+// at 65536).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -88,7 +95,8 @@ __global__ __launch_bounds__(256) void ifx_psd_kernel(const void* __restrict__ i
 __global__ __launch_bounds__(256) void ifx_mask_kernel(const float* __restrict__ partial, int groups,
                                                        int nframes, float scale, int dilate,
                                                        int max_bins, int32_t* __restrict__ counts,
-                                                       uint32_t* __restrict__ masks) {
+                                                       uint32_t* __restrict__ masks,
+                                                       float* __restrict__ psd) {
     __shared__ float P[kIfxL];
     __shared__ float srt[kIfxL];
     __shared__ int flag[kIfxL];
@@ -104,6 +112,7 @@ __global__ __launch_bounds__(256) void ifx_mask_kernel(const float* __restrict__
         s = s / inv;
         P[k] = s;
         srt[k] = s;
+        psd[(size_t)b * kIfxL + k] = s;
     }
     __syncthreads();
     // bitonic sort, ascending: 1024 compare-exchanges per stage, four per thread
@@ -231,6 +240,8 @@ struct gpsmi_ifx {
     DevBuf<float> d_partial;                 // [nb][groups][2048]
     DevBuf<int32_t> d_counts;                // [nb]
     DevBuf<uint32_t> d_masks;                // [nb][kMaskWords]
+    DevBuf<float> d_psd;                     // [nb][2048]: the P the mask pass thresholded
+    int last_nb = 0;                         // blocks of the last call (0: none yet)
     StagedIO io;                             // host entry: staged input and output
     int fmt = GPSMI_IQ_C64;
     float scale = 0.f;                       // 10^(thresh_db / 10) as float32
@@ -268,6 +279,7 @@ static int ifx_run(gpsmi_ifx* h, const void* d_iq, void* d_out, int nb) {
     int rc = h->d_partial.reserve((size_t)nb * groups * kIfxL, "excision spectra");
     if (!rc) rc = h->d_counts.reserve(nb, "excision results");
     if (!rc) rc = h->d_masks.reserve((size_t)nb * kMaskWords, "excision results");
+    if (!rc) rc = h->d_psd.reserve((size_t)nb * kIfxL, "excision results");
     if (rc) return rc;
     // segments per apply workgroup: one frame transform pair per segment plus one per workgroup;
     // runs of up to 8 segments once the grid has some 2048 workgroups anyway (same bits either way)
@@ -281,7 +293,8 @@ static int ifx_run(gpsmi_ifx* h, const void* d_iq, void* d_out, int nb) {
         hipLaunchKernelGGL(ifx_psd_kernel<FMT>, dim3((unsigned)(nb * groups)), dim3(256), 0, h->stream, d_iq,
                            h->d_carry.p, h->d_win.p, n, groups, h->d_partial.p, h->d_tw.p);
         hipLaunchKernelGGL(ifx_mask_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, h->d_partial.p, groups,
-                           nf - 1, h->scale, h->cfg.dilate, h->cfg.max_bins, h->d_counts.p, h->d_masks.p);
+                           nf - 1, h->scale, h->cfg.dilate, h->cfg.max_bins, h->d_counts.p, h->d_masks.p,
+                           h->d_psd.p);
         hipLaunchKernelGGL(ifx_apply_kernel<FMT>, dim3((unsigned)(nb * runs)), dim3(256), 0, h->stream, d_iq,
                            h->d_carry.p, h->d_win.p, n, runs, S, h->d_counts.p, h->d_masks.p, (float2*)d_out,
                            h->d_tw.p);
@@ -289,6 +302,7 @@ static int ifx_run(gpsmi_ifx* h, const void* d_iq, void* d_out, int nb) {
     });
     GPSMI_HIP(hipGetLastError());
     GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
+    h->last_nb = nb;
     return GPSMI_OK;
 }
 
@@ -394,6 +408,16 @@ int gpsmi_ifx_apply(gpsmi_ifx* h, const void* iq, float* out, int nb, int32_t* c
 int gpsmi_ifx_last_ms(gpsmi_ifx* h, float* ms) {
     GPSMI_REQUIRE(h && ms, "null argument");
     *ms = h->last_ms;
+    return GPSMI_OK;
+}
+
+int gpsmi_ifx_last_psd(gpsmi_ifx* h, float* psd) {
+    GPSMI_REQUIRE(h && psd, "null argument");
+    if (h->last_nb <= 0) return fail(GPSMI_E_STATE, "gpsmi_ifx_last_psd: no call yet");
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    GPSMI_HIP(hipMemcpyAsync(psd, h->d_psd.p, (size_t)h->last_nb * kIfxL * sizeof(float), hipMemcpyDeviceToHost,
+                             h->stream));
+    GPSMI_HIP(hipStreamSynchronize(h->stream));
     return GPSMI_OK;
 }
 

@@ -143,7 +143,7 @@ EXPORTS = [
     'gpsmi_set_default', 'gpsmi_clear_default', 'gpsmi_trk_set_option', 'gpsmi_trk_get_option',
     'gpsmi_trk_corr_grid', 'gpsmi_trk_corr_wg_map',
     'gpsmi_ifx_create', 'gpsmi_ifx_destroy', 'gpsmi_ifx_set_input_format', 'gpsmi_ifx_reset',
-    'gpsmi_ifx_apply', 'gpsmi_ifx_apply_dev', 'gpsmi_ifx_last_ms',
+    'gpsmi_ifx_apply', 'gpsmi_ifx_apply_dev', 'gpsmi_ifx_last_ms', 'gpsmi_ifx_last_psd',
     'gpsmi_fe_design', 'gpsmi_fe_create', 'gpsmi_fe_destroy', 'gpsmi_fe_reset', 'gpsmi_fe_push',
     'gpsmi_fe_push_dev', 'gpsmi_fe_flush', 'gpsmi_fe_last_ms',
     'gpsmi_pb_create', 'gpsmi_pb_destroy', 'gpsmi_pb_set_input_format', 'gpsmi_pb_reset',
@@ -258,6 +258,7 @@ def load():
         'gpsmi_ifx_apply': [vp, vp, vp, C.c_int, vp, vp],
         'gpsmi_ifx_apply_dev': [vp, vp, vp, C.c_int, vp, vp],
         'gpsmi_ifx_last_ms': [vp, P(f32)],
+        'gpsmi_ifx_last_psd': [vp, vp],
         'gpsmi_fe_design': [P(FeCfg), P(C.c_int), P(C.c_int), vp],
         'gpsmi_fe_create': [P(FeCfg), P(vp)],
         'gpsmi_fe_destroy': [vp],

@@ -36,6 +36,7 @@ class Excision:
             check(self.lib.gpsmi_ifx_set_input_format(self.h, 1), 'gpsmi_ifx_set_input_format')
         self.last_counts = None         # int32 [nb] of the last call: bins removed, -1 wideband
         self.last_masks = None          # uint32 [nb, 64] of the last call: the bins removed
+        self._psd_nb = 0                # blocks of the last call that ran (rows of last_psd)
 
     def _results(self, nb):
         self.last_counts = np.zeros(nb, dtype=np.int32)
@@ -61,6 +62,7 @@ class Excision:
         counts, masks = self._results(nb)
         check(self.lib.gpsmi_ifx_apply(self.h, ptr(x), ptr(out), nb, ptr(counts), ptr(masks)),
               'gpsmi_ifx_apply')
+        self._psd_nb = nb
         return out
 
     def apply_dev(self, d_in, d_out, nb):
@@ -68,6 +70,7 @@ class Excision:
         counts, masks = self._results(int(nb))
         check(self.lib.gpsmi_ifx_apply_dev(self.h, d_in, d_out, int(nb), ptr(counts), ptr(masks)),
               'gpsmi_ifx_apply_dev')
+        self._psd_nb = int(nb)
 
     def reset(self):
         """Carry := 0, as after creation (the block before the next one is taken as silence)."""
@@ -77,6 +80,13 @@ class Excision:
         ms = C.c_float(0.0)
         check(self.lib.gpsmi_ifx_last_ms(self.h, C.byref(ms)), 'gpsmi_ifx_last_ms')
         return ms.value
+
+    def last_psd(self):
+        """float32 [nb, 2048]: the P[k] that the mask pass of the last call thresholded, bit for bit
+        (a diagnostic; EngineError with GPSMI_E_STATE before the first call)."""
+        psd = np.zeros((max(self._psd_nb, 1), 2048), dtype=np.float32)
+        check(self.lib.gpsmi_ifx_last_psd(self.h, ptr(psd)), 'gpsmi_ifx_last_psd')
+        return psd
 
     def close(self):
         if getattr(self, 'h', None):

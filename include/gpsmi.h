@@ -678,6 +678,14 @@ int gpsmi_trk_last_codephase_ms(gpsmi_trk* h, float* ms);
  * b = 0), and the handle's carry is the last block's tail afterwards.  Input and output must not
  * overlap (GPSMI_E_ARG: no in-place excision).  Both calls return when the work is done;
  * gpsmi_ifx_last_ms reports its device time.  thresh_db = +inf flags nothing.
+ * The first block after create / reset stands behind a zero carry: a strong tone then starts with a
+ * step at sample 0, which leaks across frame 0's spectrum.  A short block (4096 or 5120 samples:
+ * 3 or 4 frames in P) is classed wideband by it and passes through jammed (count -1); a longer one
+ * is excised with a wider mask than its successors (35 dB tone: some 170 bins at 20480, some 95
+ * at 65536).
+ * gpsmi_ifx_last_psd (a diagnostic) copies out the float32 P[k] that the last call thresholded,
+ * bit for bit: psd is a host array of nb * 2048 floats, nb that call's; GPSMI_E_STATE before the
+ * first call.
  * ======================================================================== */
 typedef struct gpsmi_ifx gpsmi_ifx;
 typedef struct gpsmi_ifx_cfg {
@@ -699,6 +707,7 @@ int gpsmi_ifx_apply(gpsmi_ifx* h, const void* iq, float* out, int nb,
 int gpsmi_ifx_apply_dev(gpsmi_ifx* h, const void* d_iq, void* d_out, int nb,
                         int32_t* counts, uint32_t* masks);
 int gpsmi_ifx_last_ms(gpsmi_ifx* h, float* ms);
+int gpsmi_ifx_last_psd(gpsmi_ifx* h, float* psd);
 
 /* ========================================================================
  * Front end: recordings of other SDR front ends -> complex64 at the engine's rate.

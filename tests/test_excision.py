@@ -103,6 +103,7 @@ def test_abi_argument_errors_do_not_need_a_gpu():
     assert lib.gpsmi_ifx_set_input_format(None, 0) == -1
     assert lib.gpsmi_ifx_reset(None) == -1
     assert lib.gpsmi_ifx_last_ms(None, None) == -1
+    assert lib.gpsmi_ifx_last_psd(None, None) == -1
     assert lib.gpsmi_ifx_destroy(None) == 0
 
 

@@ -10,6 +10,7 @@ import ifx_ref as R
 pytestmark = pytest.mark.gpu
 
 JN_DB, TONE_HZ = 35.0, -2717.3
+FACTOR = 4
 _CACHE = {}
 
 
@@ -44,6 +45,7 @@ def test_kernel_matches_restatement():
     xs = _blocks(0, 4)
     ex = Excision()
     ref = R.ExcisionRef(_scene().ngps)
+    orc = R.Oracle32(_scene().ngps)              # float32 of the same arithmetic: what the format costs
     borderline = []
     for b, x in enumerate(xs):
         y = ex.apply(x)
@@ -61,7 +63,13 @@ def test_kernel_matches_restatement():
             ref.carry = nxt
         assert ex.last_counts[0] == (count if not len(diff) else gm.sum())
         assert 0 < ex.last_counts[0] <= 256
-        assert np.abs(y - y_ref).max() <= 1e-4 * _rms(x), (b, np.abs(y - y_ref).max() / _rms(x))
+        # FACTOR x the float32 oracle's own distance from float64 (tests/test_gpu_excision_ref.py),
+        # and never more than the 1e-4 this test used to allow
+        dev = float(np.abs(orc.overlap_add(orc.spectra(x), gm) - y_ref).max()) / _rms(x)
+        orc.carry = x[-R.H:].copy()
+        err = float(np.abs(y - y_ref).max()) / _rms(x)
+        print(f'block {b}: output error {err:.3e}, bound {FACTOR * dev:.3e}')
+        assert 0 < dev and err <= min(1e-4, FACTOR * dev), (b, err, FACTOR * dev)
     if borderline:
         print(f'bins within 1e-4 of the threshold that differ (allowed): {borderline}')
     ex.close()
