@@ -216,3 +216,295 @@ def save_results(path, result_list):
 
 def make_udp_socket():
     return socket.socket(socket.AF_INET, socket.SOCK_DGRAM)
+
+
+def largest_peak_hits(acq, data, prns, freqs, n_coh=4, n_seg=250, f_offset=0.0):
+    """Deep-search hits ``(normMaxCorr, satNo, freq, delay)`` of satellites known to be there, one
+    per PRN at the bin of its largest peak.  (sweepDeepSats' first bin over the threshold is a
+    sidelobe for a strong satellite, and its own sidelobes raise the std normMaxCorr divides by.)"""
+    tab = acq.engine.search_deep(data, list(prns), list(freqs), n_coh, n_seg, f_offset=f_offset)
+    best = tab['peak'].argmax(axis=0)
+    nmc = (tab['peak'].astype(np.float64) - tab['mean']) / tab['std']
+    return [(float(nmc[b, j]), s, freqs[b], int(tab[b, j]['argmax'])) for j, (s, b) in enumerate(zip(prns, best))]
+
+
+def refine_centred(acq, data, found, f_offset=0.0):
+    """Acquisition.refineHits, and again for every confirmed hit that came back without a code
+    phase because its early or late tap was larger than its prompt: the search's integer delay
+    was one off (the peak of a second's search lies where the sliding code spent most of it), so
+    the hit is refined one tap spacing towards the larger tap, twice at the most.
+    -> (found with the delays used, records, device ms)."""
+    cs = acq.cfg.code_samples
+    tap = 1 if cs == 2048 else 8
+    found = list(found)
+    rec = acq.refineHits(data, found, f_offset=f_offset)
+    ms = acq.engine.last_ms()
+    for _ in range(2):
+        bad = [i for i, r in enumerate(rec) if r['confirmed'] == 1 and r['code_phase'] < 0]
+        if not bad:
+            break
+        for i in bad:
+            nmc, s, f, d = found[i]
+            e, _, l = rec[i]['tap_metric']
+            found[i] = (nmc, s, f, int(d + (-tap if e > l else tap)) % cs)
+        rec[bad] = acq.refineHits(data, [found[i] for i in bad], f_offset=f_offset)
+        ms += acq.engine.last_ms()
+    return found, rec, ms
+
+
+class WeakTracker:
+    """Weak channels (states of acquisition.open_weak_channels) followed through a stream in
+    chunks: push() the samples that follow those pushed so far and get every channel's new bit
+    records (AcqEngine.track_weak).  Between chunks the samples before the
+    earliest channel's next bit are dropped and first_sample moves up; the records are the same
+    bytes for any chunking.  `first_sample`: the stream index of the first sample pushed, on the
+    clock the states were opened on.  `track_cfg`: track_weak's keyword arguments."""
+
+    def __init__(self, engine, states, first_sample=0, **track_cfg):
+        self.engine, self.states, self.cfg = engine, states, track_cfg
+        self.first = int(first_sample)
+        cs = engine.cfg.code_samples
+        self.tap = track_cfg.get('tap_samples') or (1 if cs == 2048 else 8)
+        self.pending = None
+        self.device_ms, self.chunks = 0.0, 0
+
+    def push(self, data):
+        """-> [records of channel h that this chunk added] in the order of `states`."""
+        self.pending = data if self.pending is None else np.concatenate([self.pending, data])
+        if not len(self.states):
+            return []
+        n_bits = len(self.pending) // (20 * self.engine.cfg.code_samples) + 1
+        bits, new = self.engine.track_weak(self.pending, self.states, n_bits, first_sample=self.first,
+                                           **self.cfg)
+        self.device_ms += self.engine.last_ms()
+        self.chunks += 1
+        out = [bits[h, :int(new['bit_no'][h] - self.states['bit_no'][h])] for h in range(len(new))]
+        self.states = new
+        self._trim()
+        return out
+
+    def _trim(self):
+        lo = int(np.floor(self.states['tau']).min()) - self.tap if len(self.states) else self.first + len(self.pending)
+        if lo > self.first:
+            self.pending = self.pending[lo - self.first:]
+            self.first = lo
+
+    def drop(self, h):
+        self.states = np.delete(self.states, h)
+        if self.pending is not None:
+            self._trim()
+
+
+class WeakAssist:
+    """A Receiver with the satellites its 4-ms sweep cannot acquire added to its datagrams
+    (DESIGN.md 4.2h).  feed() forwards every block to the receiver.  The first `seconds` of blocks
+    after the receiver's cold sweep has finished are kept; on them the receiver's own Acquisition
+    runs the deep search (sweepDeepSats, `n_coh`-ms segments) for the PRNs the receiver does not
+    track, refines the hits (refineHits) and opens a bit-synchronous channel on every confirmed one
+    (`min_snr`: and of at least that C/N0 in dB-Hz), on the receiver's sample clock.  From then on
+    the channels are tracked every `chunk_blocks` blocks (WeakTracker; `track_cfg` goes to
+    track_weak), their bits decoded and their code phases reported block by block
+    (weaknav.WeakHandoff), and each datagram of the receiver leaves merged with the weak channels'
+    of the same report block (weaknav.merge_datagrams) -- which the weak side has only once it has
+    tracked past that block, so a merged datagram trails the receiver's by up to `chunk_blocks`
+    blocks.  Without a weak channel every datagram is returned as the receiver made it, bytes
+    and block.  A PRN the receiver acquires itself is closed here; a lost stretch of the stream
+    (`skip`) closes all of them and the search starts over."""
+
+    def __init__(self, receiver, seconds=1.0, n_coh=4, min_snr=None, chunk_blocks=16, **track_cfg):
+        from .weaknav import WeakHandoff
+        self.rx, self.cfg = receiver, receiver.cfg
+        self.n_coh, self.min_snr, self.chunk_blocks = int(n_coh), min_snr, int(chunk_blocks)
+        self.n_seg = int(round(seconds * 1000)) // self.n_coh
+        if not 1 <= self.n_seg <= 32768 or self.chunk_blocks < 1:
+            raise ValueError('seconds / n_coh / chunk_blocks out of range')
+        self.track_cfg = track_cfg
+        self.handoff = WeakHandoff(self.cfg, track_cfg.get('f_offset', 0.0),
+                                   track_cfg.get('carrier_hz', 1575.42e6))
+        self.result_list = []                        # every datagram handed out, in order
+        self.found, self.refined = [], None          # what the deep search and refinement returned
+        self.own_refined = None                      # ... and the receiver's own satellites, refined alike
+        self.search_ms = 0.0
+        self._n_rx = len(receiver.result_list)
+        self._out, self._last_s = [], -1
+        self._rearm()
+
+    def _rearm(self):
+        for prn in list(self.handoff.chan):
+            self.handoff.close(prn)
+        self.tracker = None
+        self.searched = False
+        self._kept, self._kept_start, self._n_kept = [], None, 0
+        self._blocks = []                            # fed since the tracker's last chunk
+        self._strong, self._weak = [], {}
+
+    @property
+    def weak_prns(self):
+        return list(self.handoff.chan)
+
+    def feed(self, block, skip=0):
+        """Receiver.feed's arguments; returns a pickled hand-off (the receiver's, the weak
+        channels', or both merged) or None."""
+        rx = self.rx
+        sweeping = rx.sweep_all_freq
+        rx.feed(block, skip)
+        if skip:
+            self._flush()
+            self._rearm()
+        self._strong += rx.result_list[self._n_rx:]
+        self._n_rx = len(rx.result_list)
+        if rx._clean is not None:                    # (the engines saw the filters' output)
+            block = rx._clean.array
+        if self.tracker is None:
+            if not self.searched and not sweeping and not rx.sweep_all_freq:
+                self._keep(block)
+        else:
+            self._close_taken()
+            self._blocks.append(np.array(block))
+            if len(self._blocks) >= self.chunk_blocks:
+                self._track([np.concatenate(self._blocks)])
+        self._release()
+        return self._hand_out()
+
+    def _hand_out(self):
+        if not self._out:
+            return None
+        res = self._out.pop(0)
+        self.result_list.append(res)
+        return res
+
+    def _keep(self, block):
+        if self._kept_start is None:
+            self._kept_start = int(self.rx.smp_time)     # the receiver's clock at block[0]
+        self._kept.append(np.array(block))
+        self._n_kept += len(block)
+        if self._n_kept >= max(self.n_seg * self.n_coh, 43) * self.cfg.code_samples:
+            self._search()
+
+    def _search(self):
+        from .acquisition import open_weak_channels
+        c, acq = self.cfg, self.rx.acq
+        whole = np.concatenate(self._kept)
+        self._kept, self.searched = [], True
+        freqs = [c.min_freq + c.step_freq * i for i in range(int(round((c.max_freq - c.min_freq) / c.step_freq)))]
+        sat_lst = [s for s in self.rx.sat_all if s not in self.rx.act_sat_set]
+        f_off = self.track_cfg.get('f_offset', 0.0)
+        self.found = acq.sweepDeepSats(whole[:self.n_seg * self.n_coh * c.code_samples], freqs, sat_lst, [],
+                                       n_coh=self.n_coh, n_seg=self.n_seg, f_offset=f_off)
+        self.search_ms = acq.engine.last_ms()
+        if not self.found:
+            return
+        self.found, self.refined, ms = refine_centred(acq, whole, self.found, f_offset=f_off)
+        self.search_ms += ms
+        good = (self.refined['confirmed'] == 1) & (self.refined['code_phase'] >= 0)
+        good &= ~self._ghosts(whole, freqs, f_off)
+        if self.min_snr is not None:
+            good &= self.refined['cn0_dbhz'] >= self.min_snr     # (NaN: no)
+        rec = self.refined[good]
+        if not len(rec):
+            return
+        states = open_weak_channels(rec, c, data_start=self._kept_start, f_offset=f_off)
+        for prn in states['prn']:
+            self.handoff.open(prn)
+        self.tracker = WeakTracker(acq.engine, states, self._kept_start, **self.track_cfg)
+        step = self.chunk_blocks * c.ngps
+        self._track([whole[i:i + step] for i in range(0, len(whole), step)])
+
+    GHOST_HZ, GHOST_DB = 5.0, 10.0
+
+    def _ghosts(self, whole, freqs, f_off):
+        """Which refined hits are the receiver's own satellites seen through another PRN's code:
+        the C/A codes' cross-correlation (-24 dB, -21 dB at the worst Doppler offset) turns a
+        satellite 20 dB above the search's sensitivity into a peak the search finds, at the strong
+        satellite's Doppler plus a multiple of the code's 1-kHz line spacing, and such a channel
+        would track it and decode the STRONG satellite's subframes under the wrong PRN.  The
+        receiver's satellites go through the same search (largest_peak_hits) and the same
+        refinement; a hit within GHOST_HZ of one of them modulo 1 kHz that reads GHOST_DB or more
+        below it is dropped.  -> bool per refined record."""
+        c, acq = self.cfg, self.rx.acq
+        own = sorted(self.rx.act_sat_set)
+        self.own_refined = None
+        out = np.zeros(len(self.refined), bool)
+        if not own:
+            return out
+        hits = largest_peak_hits(acq, whole[:self.n_seg * self.n_coh * c.code_samples], own, freqs, self.n_coh,
+                                 self.n_seg, f_offset=f_off)
+        self.search_ms += acq.engine.last_ms()
+        _, self.own_refined, ms = refine_centred(acq, whole, hits, f_offset=f_off)
+        self.search_ms += ms
+        for o in self.own_refined:
+            if o['confirmed'] != 1 or np.isnan(o['cn0_dbhz']):
+                continue
+            d = np.abs((self.refined['f_hz'] - o['f_hz'] + 500.0) % 1000.0 - 500.0)
+            out |= (d <= self.GHOST_HZ) & ~(self.refined['cn0_dbhz'] > o['cn0_dbhz'] - self.GHOST_DB)
+        return out
+
+    def _track(self, chunks):
+        self._blocks = []
+        for data in chunks:
+            before = self.tracker.states['bit_no'].copy()
+            new = self.tracker.push(data)
+            st = self.tracker.states
+            for h in range(len(st) - 1, -1, -1):
+                self.handoff.absorb(st['prn'][h], new[h])
+                if st['bit_no'][h] == before[h] and not st['flags'][h] & _lib.WTRK_DATA_END:
+                    self._close(h)               # (a state that is no longer finite stops for good)
+        for s, dg in self.handoff.datagrams():
+            if s > self._last_s:                 # (the receiver's of that block has left already)
+                self._weak[s] = dg
+
+    def _close(self, h):
+        self.handoff.close(self.tracker.states['prn'][h])
+        self.tracker.drop(h)
+
+    def _close_taken(self):
+        st = self.tracker.states
+        for h in range(len(st) - 1, -1, -1):
+            if int(st['prn'][h]) in self.rx.act_sat_set:
+                self._close(h)
+
+    def _release(self, everything=False):
+        """Moves to _out what can leave: the receiver's datagrams as they are while no weak channel
+        is open; else those of report blocks the weak side has finished (all, with `everything`),
+        merged with its datagram of that block."""
+        from .weaknav import merge_datagrams, report_stream
+        live = self.tracker is not None and len(self.tracker.states) > 0 and not everything
+        if not live and not self._weak:
+            if self._strong:
+                self._last_s = report_stream(pickle.loads(self._strong[-1]), self._last_s)
+            self._out += self._strong
+            self._strong = []
+            return
+        done = self.handoff.next_report          # the weak side is complete below this block
+        while self._strong:
+            tup = pickle.loads(self._strong[0])
+            s = report_stream(tup, int(self.rx.smp_time) // self.cfg.ngps)
+            if live and (done is None or s >= done):
+                break
+            dg = self._strong.pop(0)
+            for w in sorted(k for k in self._weak if k < s):       # (the receiver had none there)
+                self._out.append(pickle.dumps(self._weak.pop(w)))
+            self._last_s = s
+            weak = self._weak.pop(s, None)
+            self._out.append(dg if weak is None else pickle.dumps(merge_datagrams(tup, weak)))
+        if not self._strong and (not live or not self.rx.act_sat_set):
+            for w in sorted(self._weak):
+                self._out.append(pickle.dumps(self._weak.pop(w)))
+
+    def _flush(self):
+        self.rx.drain()
+        self._strong += self.rx.result_list[self._n_rx:]
+        self._n_rx = len(self.rx.result_list)
+        if self.tracker is not None and self._blocks:
+            self._track([np.concatenate(self._blocks)])
+        self._release(everything=True)
+
+    def drain(self):
+        """Everything still on its way, on either side; the datagrams go to result_list."""
+        self._flush()
+        while self._out:
+            self._hand_out()
+
+    def close(self):
+        self.drain()
+        self.rx.close()

@@ -5,7 +5,7 @@ gpseval) as one command on the GPU path.
 
     python tools/run_file.py <recording.bin> [--seconds S] [--start-stream K] [--save-pickle P]
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--blank] [--json]
-                             [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track]]]
+                             [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track [--weak-fix]]]]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -40,8 +40,12 @@ channel of the reference's kind would be opened with (acquisition.hit_at).
 (Acquisition.trackHits / AcqEngine.track_weak) and follows it through the recording in
 chunks: 20-ms coherent sums between the bit edges refinement found, carrier and code loops closed at
 50 Hz.  It prints, per PRN, the bits tracked, the Doppler (mean of the last 20 bits), the code phase,
-C/N0 and the phase-lock indicator at the end, and the device time.  The bits are not fed into the
-position fix.
+C/N0 and the phase-lock indicator at the end, and the device time.
+--weak-fix (with --track) runs the receiver inside pipeline.WeakAssist: the same
+search, refinement and tracking, online, on the first SECONDS behind the cold sweep; the weak
+channels' subframes and code phases are merged into the datagrams the position fix is made of (and
+--save-pickle writes).  The report gains, per weak PRN, the subframes decoded and the fixes it took
+part in.  Without the flag every output is as before.
 
 There is no recording in this repository (data/test.bin is absent from the reference
 checkout, SURVEY F2, and too short for a fix even upstream): tests/test_run_file.py writes a
@@ -87,42 +91,30 @@ TRACK_CHUNK_BLOCKS = 16
 def track_refined(acq, rec, whole, source, cfg):
     """--track: channels on the confirmed records of refineHits, followed through `whole` (the data
     they were refined on, stream index 0) and the blocks `source` still yields, in chunks of
-    TRACK_CHUNK_BLOCKS blocks; between chunks the samples before the earliest channel's next bit are
-    dropped and first_sample moves up."""
+    TRACK_CHUNK_BLOCKS blocks (pipeline.WeakTracker)."""
     from gpsmi.acquisition import open_weak_channels
+    from gpsmi.pipeline import WeakTracker
     cs = cfg.code_samples
-    tap = 1 if cs == 2048 else 8
     good = rec[(rec['confirmed'] == 1) & (rec['code_phase'] >= 0)]
     if not len(good):
         return {'device_ms': 0.0, 'chunks': 0, 'channels': []}
-    states = open_weak_channels(good, cfg)
+    trk = WeakTracker(acq.engine, open_weak_channels(good, cfg))
     hist = [[] for _ in good]                       # (f_hz, cn0, lock) of every bit
-    buf, first, ms, chunks = whole, 0, 0.0, 0
     step = TRACK_CHUNK_BLOCKS * cfg.ngps
-    pos = 0                                          # samples of `whole` handed on so far
-    pending = whole[:0]
-    done = False
-    while not done:
-        if pos < len(whole):
-            pending = np.concatenate([pending, whole[pos:pos + step]])
-            pos += step
-        else:
+
+    def chunks():
+        for pos in range(0, len(whole), step):
+            yield whole[pos:pos + step]
+        while True:
             got = [b for _, b in zip(range(TRACK_CHUNK_BLOCKS), source)]
-            done = len(got) < TRACK_CHUNK_BLOCKS
-            if got:
-                pending = np.concatenate([pending] + got)
-        n_bits = len(pending) // (20 * cs) + 1
-        bits, new = acq.engine.track_weak(pending, states, n_bits, first_sample=first)
-        ms += acq.engine.last_ms()
-        chunks += 1
-        for h in range(len(good)):
-            k = int(new['bit_no'][h] - states['bit_no'][h])
-            hist[h] += [(float(r['f_hz']), float(r['cn0_dbhz']), float(r['lock'])) for r in bits[h, :k]]
-        states = new
-        lo = int(np.floor(states['tau']).min()) - tap
-        if lo > first:
-            pending = pending[lo - first:]
-            first = lo
+            yield np.concatenate(got) if got else whole[:0]
+            if len(got) < TRACK_CHUNK_BLOCKS:
+                return
+
+    for data in chunks():
+        for h, bits in enumerate(trk.push(data)):
+            hist[h] += [(float(r['f_hz']), float(r['cn0_dbhz']), float(r['lock'])) for r in bits]
+    states, ms, chunks = trk.states, trk.device_ms, trk.chunks
     chans = []
     for h, st in enumerate(states):
         f = [x[0] for x in hist[h][-20:]]
@@ -201,12 +193,36 @@ def deep_acquisition(path, seconds, start_stream, skip_prns, frontend=None, n_co
     return out
 
 
+def weak_fix_report(assist, solver, fixes, cfg):
+    """--weak-fix: per weak PRN the subframes decoded and the fixes it took part in (a fix is one
+    (TOW, block) group of the solver's measurements; its time names it)."""
+    import datetime
+    from gpsmi import position as P
+    stamps = {f[0] for f in fixes}
+    groups = {}
+    for r in solver.sat_results:
+        groups.setdefault((r[1], r[7], r[6]), set()).add(r[0])
+    took = {}
+    for (tow, cyc, week), sats in groups.items():
+        t = P.gps_datetime(tow, week) + datetime.timedelta(seconds=cyc * cfg.n_cyc / 1000)
+        if len(sats) >= solver.min_sat and t.timestamp() in stamps:
+            for s in sats:
+                took[s] = took.get(s, 0) + 1
+    return {'search_device_ms': round(assist.search_ms, 3),
+            'channels': [{'prn': prn, 'bits': ch.n_bits, 'subframes': len(ch.frames), 'fixes': took.get(prn, 0)}
+                         for prn, ch in assist.handoff.chan.items()]}
+
+
 def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, cpu_acq=False, report_lag=16,
-        excise=False, frontend=None, blank=False, deep_acq=None, refine=False, track=False):
+        excise=False, frontend=None, blank=False, deep_acq=None, refine=False, track=False, weak_fix=False):
     """frontend: None (the recorder's u8 format at 2.048 Msps) or a dict of frontend.FrontEnd's
     keyword arguments (fs_in, fmt, if_hz, conjugate).  deep_acq: None, or the seconds of the
     recording's start that deep_acquisition searches for the PRNs the sweep did not acquire; refine:
-    its hits are refined as well; track: the confirmed ones are tracked bit-synchronously."""
+    its hits are refined as well; track: the confirmed ones are tracked bit-synchronously.
+    weak_fix (with deep_acq, refine and track): the receiver runs inside pipeline.WeakAssist, which
+    searches the first deep_acq seconds behind the cold sweep, tracks what it confirms and merges
+    those channels' subframes and code phases into the datagrams the solver is fed (DESIGN.md 4.2h);
+    the report gains 'weak_fix'."""
     from gpsmi import ingest, position as P
     from gpsmi.engine import Config
     from gpsmi.pipeline import Receiver, save_results
@@ -224,28 +240,34 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
         rx = Receiver(cfg, raw_u8=False, report_lag=report_lag, excise=True if excise else None,
                       blank=True if blank else None)
         source = (b for k, b in enumerate(ingest.read_frontend_blocks(path, fe)) if k >= start_stream)
+    if weak_fix:
+        from gpsmi.pipeline import WeakAssist
+        top = WeakAssist(rx, seconds=deep_acq)
+    else:
+        top = rx
     solver = P.PositionSolver(cfg.code_samples, cfg.n_cyc, ephemerides=ephemerides)
     max_blocks = None if seconds is None else int(seconds * 1000 // cfg.n_cyc)
     fixes, n_dg, n_blocks, found = [], 0, 0, None
     t0 = time.perf_counter()
     for raw in source:
-        rx.feed(raw)
+        top.feed(raw)
         n_blocks += 1
         if found is None and not rx.sweep_all_freq:
             found = list(rx.found_sats)
-        for dg in rx.result_list[n_dg:]:           # (every datagram, in order: RESULT_LIST)
+        for dg in top.result_list[n_dg:]:          # (every datagram, in order: RESULT_LIST)
             n_dg += 1
             fixes += solver.feed(pickle.loads(dg))
         if max_blocks is not None and n_blocks >= max_blocks:
             break
-    rx.drain()
-    for dg in rx.result_list[n_dg:]:
+    top.drain()
+    for dg in top.result_list[n_dg:]:
         n_dg += 1
         fixes += solver.feed(pickle.loads(dg))
     wall = time.perf_counter() - t0
     if save_pickle:
-        save_results(save_pickle, rx.result_list)
+        save_results(save_pickle, top.result_list)
     sats = sorted(rx.act_sat_set)
+    weak = weak_fix_report(top, solver, fixes, cfg) if weak_fix else None
     rx.close()
     if fe is not None:
         fe.close()
@@ -263,6 +285,8 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
                            'height_m': round(float(alt), 1), 'ecef_m': [round(float(v), 2) for v in mean],
                            'from': f'mean of the last {len(late)} fixes',
                            'sd_of_mean_m': round(float(np.linalg.norm(late.std(axis=0)) / np.sqrt(len(late))), 2)}
+    if weak is not None:
+        out['weak_fix'] = weak
     if cpu_acq:
         out['cpu_cold_acquisition'] = cpu_cold_acquisition(path)
     if deep_acq:
@@ -299,12 +323,16 @@ def main():
                     help='with --deep-acq: refine its hits (fine Doppler, bit edge, code phase, C/N0; DESIGN.md 4.2f)')
     ap.add_argument('--track', action='store_true',
                     help='with --refine: track the confirmed hits bit-synchronously through the recording (DESIGN.md 4.2g)')
+    ap.add_argument('--weak-fix', action='store_true',
+                    help='with --track: merge the weak channels into the datagrams the position fix is made of (DESIGN.md 4.2h)')
     ap.add_argument('--json', action='store_true', help='one JSON line instead of text')
     a = ap.parse_args()
     if a.refine and not a.deep_acq:
         ap.error('--refine needs --deep-acq SECONDS')
     if a.track and not a.refine:
         ap.error('--track needs --refine')
+    if a.weak_fix and not a.track:
+        ap.error('--weak-fix needs --track')
     frontend = None
     if a.format is not None or a.fs is not None or a.if_hz is not None or a.conjugate:
         frontend = {'fmt': a.format or 'u8iq', 'fs_in': a.fs or 2048000, 'if_hz': a.if_hz or 0.0,
@@ -314,7 +342,7 @@ def main():
         with open(a.ephemeris) as f:
             eph = {int(k): v for k, v in json.load(f).items()}
     out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise,
-              frontend, a.blank, a.deep_acq, a.refine, a.track)
+              frontend, a.blank, a.deep_acq, a.refine, a.track, a.weak_fix)
     if a.json:
         print(json.dumps(out))
         return
@@ -328,6 +356,11 @@ def main():
               f"(SD of mean {p['sd_of_mean_m']} m)")
     else:
         print('no position fix (too little signal for subframes 1-3 of four satellites, or no ephemerides)')
+    if 'weak_fix' in out:
+        w = out['weak_fix']
+        print(f"weak channels merged into the fix ({w['search_device_ms']} ms of search on the device): {len(w['channels'])}")
+        for q in w['channels']:
+            print(f"  PRN {q['prn']:2d}  bits {q['bits']:5d}  subframes decoded {q['subframes']}  fixes it took part in {q['fixes']}")
     if 'cpu_cold_acquisition' in out:
         c = out['cpu_cold_acquisition']
         print(f"CPU cold acquisition (configs[0], numpy path, {c['cores']} core): {c['wall_ms']} ms, {len(c['found'])} satellites")
