@@ -4,8 +4,8 @@
 //   gpsmi_acq_search.h    the coherent, the non-coherent and the deep search (gpsmi_acq_search*,
 //                         DESIGN.md 4.2, 4.2a, 4.2e): one wipe-off fold per code length, one
 //                         correlation kernel in three modes
-//   gpsmi_pfa.h, gpsmi_bigfft.h, gpsmi_direct.h
-//                         the correlations of the other code lengths
+//   gpsmi_longcorr.h      the correlations of the other code lengths (gpsmi_pfa.h, gpsmi_bigfft.h,
+//                         gpsmi_direct.h), shared with the tracking handle
 //   gpsmi_refine.h        refinement of weak / deep hits (gpsmi_acq_refine): fine
 //                         Doppler, bit edge, sub-sample code phase, C/N0
 //   gpsmi_wtrk.h          bit-synchronous tracking of refined hits (gpsmi_acq_track)
@@ -16,9 +16,7 @@
 
 #include "gpsmi_common.h"
 #include "gpsmi_devmem.h"
-#include "gpsmi_bigfft.h"
-#include "gpsmi_pfa.h"
-#include "gpsmi_direct.h"
+#include "gpsmi_longcorr.h"
 #include "gpsmi_fft.h"
 #include "gpsmi_stats.h"
 #include "gpsmi_refine.h"
@@ -49,20 +47,12 @@ struct gpsmi_acq {
     int32_t* h_slot[2] = {nullptr, nullptr};
     bool staged_used[2] = {false, false};
     int stage = 0;
-    // direct (time-domain) path for code_samples != 2048
+    // code_samples != 2048: the bins folded in the time domain, then the long-code correlation
     bool direct = false;
     DevBuf<float> d_rep_time;               // [GPSMI_MAX_PRN + 1][cs]
     bool have_time[GPSMI_MAX_PRN + 1] = {};
     DevBuf<float2> d_fold;                  // [bins][cs]
-    DevBuf<float> d_mag;                    // [cells][cs], the paths without the native correlation
-    DevBuf<DirStats> d_stats;               // [cells], as d_xsel and d_rsel
-    DevBuf<int> d_xsel, d_rsel;
-    // ... through one 32768-point FFT pair when the code period fits (gpsmi_bigfft.h)
-    bool big = false;
-    DevBuf<float2> d_twN, d_RS, d_S;
-    // ... or natively in LDS when the code period is 16368 = 16 * 3 * 11 * 31 samples (gpsmi_pfa.h)
-    bool pfa = false;
-    DevBuf<float2> d_RSp;                   // [GPSMI_MAX_PRN + 1][16368] replica spectra, P3's order
+    LongCorr lc;                            // its method, replica spectra, cell tables and statistics
     // non-coherent search: the per-(bin, segment) spectra (CS = 2048) or folded samples (16368) of
     // one chunk of bins, sized per call (gpsmi_acq_search_nc)
     DevBuf<float2> d_nc;
@@ -105,14 +95,6 @@ static int acq_reserve(gpsmi_acq* h, int nbins, int nsv) {
     return rc;
 }
 
-// the cells of the time-domain and native-length paths (d_mag: not with the native correlation)
-static int acq_reserve_cells(gpsmi_acq* h, size_t cells) {
-    int rc = h->d_stats.reserve(cells, "gpsmi_acq cell statistics");
-    if (!rc) rc = h->d_xsel.reserve(cells, "gpsmi_acq cell table");
-    if (!rc) rc = h->d_rsel.reserve(cells, "gpsmi_acq cell table");
-    return rc;
-}
-
 // host input of a search, a refinement or a tracking call: `count` samples in the handle's input
 // format into d_iq on the handle's stream (d_iq is sized for complex64; raw input fills a quarter)
 static int acq_upload(gpsmi_acq* h, const void* iq, size_t count) {
@@ -121,32 +103,6 @@ static int acq_upload(gpsmi_acq* h, const void* iq, size_t count) {
     GPSMI_HIP(hipMemcpyAsync(h->d_iq.p, iq, h->iq_bytes(count), hipMemcpyHostToDevice, h->stream));
     return GPSMI_OK;
 }
-
-extern "C" {
-
-static int acq_build(const gpsmi_cfg* cfg, gpsmi_acq* h);
-
-int gpsmi_acq_create(const gpsmi_cfg* cfg, gpsmi_acq** out) {
-    GPSMI_REQUIRE(cfg && out, "null argument");
-    *out = nullptr;
-    GPSMI_REQUIRE(cfg->code_samples >= 1024 && cfg->code_samples <= 65536 &&
-                      cfg->code_samples % 16 == 0,
-                  "code_samples must be a multiple of 16 in 1024..65536");
-    GPSMI_REQUIRE(cfg->n_cyc >= 1 && cfg->n_cyc <= 64, "n_cyc out of range");
-    GPSMI_HIP(hipSetDevice(cfg->device));
-    gpsmi_acq* h = new (std::nothrow) gpsmi_acq();
-    if (!h) return fail(GPSMI_E_NOMEM, "out of host memory");
-    h->cfg = *cfg;
-    const int rc = acq_build(cfg, h);
-    if (rc) {                       // nothing half-built leaves this function
-        (void)gpsmi_acq_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return GPSMI_OK;
-}
-
-}  // extern "C"
 
 static int acq_build(const gpsmi_cfg* cfg, gpsmi_acq* h) {
     h->direct = cfg->code_samples != kFftN;
@@ -176,28 +132,32 @@ static int acq_build(const gpsmi_cfg* cfg, gpsmi_acq* h) {
     if (h->direct) {
         if ((rc = h->d_rep_time.reserve((size_t)(GPSMI_MAX_PRN + 1) * cfg->code_samples, "gpsmi_acq replicas")))
             return rc;
-        long long forced = 0;                    // option "codephase": 1 keeps the time-domain kernel,
-        default_opt("codephase", &forced, 0);    // 2 the zero-padded 32768-point pair
-        h->pfa = cfg->code_samples == kPfaL && forced == 0;
-        h->big = !h->pfa && 2 * cfg->code_samples - 1 <= kBigN && forced != 1;
-        if (h->pfa && (rc = h->d_RSp.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * kPfaL, "gpsmi_acq replica spectra")))
-            return rc;
-        if (h->big) {
-            std::vector<float2> twn(kBigN);
-            for (int k = 0; k < kBigN; ++k) {
-                const double a = -2.0 * M_PI * (double)k / (double)kBigN;
-                twn[k] = make_float2((float)cos(a), (float)sin(a));
-            }
-            if ((rc = h->d_twN.upload(twn, "gpsmi_acq twiddles")) ||
-                (rc = h->d_RS.reserve((size_t)(GPSMI_MAX_PRN + 1) * kBigN, "gpsmi_acq replica spectra")) ||
-                (rc = h->d_S.reserve((size_t)kBigChunkCells * kBigN, "gpsmi_acq correlation scratch")))
-                return rc;
-        }
+        return h->lc.build(cfg->code_samples, "gpsmi_acq");
     }
     return GPSMI_OK;
 }
 
 extern "C" {
+
+int gpsmi_acq_create(const gpsmi_cfg* cfg, gpsmi_acq** out) {
+    GPSMI_REQUIRE(cfg && out, "null argument");
+    *out = nullptr;
+    GPSMI_REQUIRE(cfg->code_samples >= 1024 && cfg->code_samples <= 65536 &&
+                      cfg->code_samples % 16 == 0,
+                  "code_samples must be a multiple of 16 in 1024..65536");
+    GPSMI_REQUIRE(cfg->n_cyc >= 1 && cfg->n_cyc <= 64, "n_cyc out of range");
+    GPSMI_HIP(hipSetDevice(cfg->device));
+    gpsmi_acq* h = new (std::nothrow) gpsmi_acq();
+    if (!h) return fail(GPSMI_E_NOMEM, "out of host memory");
+    h->cfg = *cfg;
+    const int rc = acq_build(cfg, h);
+    if (rc) {                       // nothing half-built leaves this function
+        (void)gpsmi_acq_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return GPSMI_OK;
+}
 
 int gpsmi_acq_destroy(gpsmi_acq* h) {
     if (!h) return GPSMI_OK;
@@ -215,24 +175,12 @@ int gpsmi_acq_set_replica_time(gpsmi_acq* h, int prn, const float* replica) {
     GPSMI_REQUIRE(h && replica, "null argument");
     GPSMI_REQUIRE(prn >= 1 && prn <= GPSMI_MAX_PRN, "prn out of range 1..37");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    if (!h->direct) {                        // the FFT path has no use for it: kept for gpsmi_acq_refine
-        const int rc = h->d_rep_time.reserve((size_t)(GPSMI_MAX_PRN + 1) * h->cfg.code_samples, "gpsmi_acq replicas");
-        if (rc) return rc;
-        GPSMI_HIP(hipMemcpy(h->d_rep_time.p + (size_t)prn * h->cfg.code_samples, replica,
-                            (size_t)h->cfg.code_samples * sizeof(float), hipMemcpyHostToDevice));
-        h->have_time[prn] = true;
-        return GPSMI_OK;
-    }
+    int rc = GPSMI_OK;                       // (the FFT path has no use for it: kept for gpsmi_acq_refine)
+    if (!h->direct && (rc = h->d_rep_time.reserve((size_t)(GPSMI_MAX_PRN + 1) * h->cfg.code_samples, "gpsmi_acq replicas")))
+        return rc;
     GPSMI_HIP(hipMemcpy(h->d_rep_time.p + (size_t)prn * h->cfg.code_samples, replica,
                         (size_t)h->cfg.code_samples * sizeof(float), hipMemcpyHostToDevice));
-    if (h->big)
-        big_replica_launch(h->stream, h->d_rep_time.p, prn, h->cfg.code_samples, h->d_RS.p, h->d_tw.p,
-                           h->d_twN.p);
-    if (h->pfa) pfa_replica_launch(h->stream, h->d_rep_time.p, prn, h->d_RSp.p);
-    if (h->big || h->pfa) {
-        GPSMI_HIP(hipGetLastError());
-        GPSMI_HIP(hipStreamSynchronize(h->stream));
-    }
+    if (h->direct && (rc = h->lc.set_replica(h->stream, h->d_rep_time.p, prn, h->d_tw.p))) return rc;
     h->have_time[prn] = true;
     return GPSMI_OK;
 }
@@ -330,7 +278,7 @@ static int acq_check_search(const gpsmi_acq* h, const void* iq, bool on_host, si
         if (!(h->direct ? h->have_time[prn[i]] : h->have_rep[prn[i]]))
             return fail(GPSMI_E_STATE, "no replica set for PRN %d", (int)prn[i]);
     }
-    if (s.segmented && h->direct && !h->pfa)
+    if (s.segmented && h->direct && !h->lc.pfa())
         return fail(GPSMI_E_UNSUPPORTED, "%s: code_samples 2048 or the native 16368 "
                                          "correlation only (not the \"codephase\" time-domain paths)",
                     s.deep ? "gpsmi_acq_search_deep" : "gpsmi_acq_search_nc");
@@ -346,33 +294,22 @@ static int acq_check_search(const gpsmi_acq* h, const void* iq, bool on_host, si
 }
 
 // Code lengths other than 2048, bins b0 .. b0 + nb - 1: fold into x [bin][n_seg][cs], the cell tables,
-// the correlation with its statistics into d_stats.  The coherent search is b0 = 0, nb = nbins,
+// the correlation with its statistics into lc.d_stats.  The coherent search is b0 = 0, nb = nbins,
 // n_seg = 1, and the only one with the time-domain correlations.
 static void acq_direct_chunk(gpsmi_acq* h, const void* d_iq, const AcqSearch& s, float2* x, int b0, int nb,
                              int nsv) {
     const int cs = h->cfg.code_samples, c0 = b0 * nsv, ncell = nb * nsv;
-    int *xsel = h->d_xsel.p + c0, *rsel = h->d_rsel.p + c0;
-    DirStats* stats = h->d_stats.p + c0;
+    LongCorr& lc = h->lc;
     with_fmt(h->iq_fmt, [&](auto fmt) {
         hipLaunchKernelGGL(acq_fold_kernel<decltype(fmt)::value>, dim3((cs + 255) / 256, nb, s.n_seg), dim3(256),
                            0, h->stream, d_iq, h->d_t32.p, h->d_omega.p + b0, s.n_coh, s.n_seg, cs, x);
     });
-    hipLaunchKernelGGL(acq_cells_kernel, dim3((ncell + 255) / 256), dim3(256), 0, h->stream, xsel, rsel,
-                       h->d_slot.p, nsv, ncell);
-    if (h->pfa) {                // transform, product, transform and statistics in one launch
-        if (!s.segmented) pfa_corr_launch<0>(h->stream, x, xsel, rsel, ncell, h->d_RSp.p, stats);
-        else if (!s.deep) pfa_corr_launch<2>(h->stream, x, xsel, rsel, ncell, h->d_RSp.p, stats, s.n_seg);
-        else pfa_corr_launch<3>(h->stream, x, xsel, rsel, ncell, h->d_RSp.p, stats, s.n_seg,
-                                h->d_shift.p + (size_t)b0 * s.n_seg);
-        return;
-    }
-    if (h->big)
-        big_corr_launch(h->stream, x, xsel, rsel, ncell, cs, h->d_RS.p, h->d_S.p, h->d_tw.p, h->d_twN.p,
-                        h->d_mag.p);
-    else
-        hipLaunchKernelGGL(circ_corr_direct_kernel, dim3((cs + kDirLagsPerWg - 1) / kDirLagsPerWg, ncell),
-                           dim3(256), 0, h->stream, x, h->d_rep_time.p, xsel, rsel, cs, h->d_mag.p);
-    hipLaunchKernelGGL(corr_stats_kernel, dim3(ncell), dim3(256), 0, h->stream, h->d_mag.p, cs, stats);
+    hipLaunchKernelGGL(acq_cells_kernel, dim3((ncell + 255) / 256), dim3(256), 0, h->stream,
+                       lc.d_xsel.p + c0, lc.d_rsel.p + c0, h->d_slot.p, nsv, ncell);
+    if (!s.segmented) lc.correlate<0>(h->stream, x, c0, ncell, h->d_rep_time.p, h->d_tw.p);
+    else if (!s.deep) lc.correlate<2>(h->stream, x, c0, ncell, h->d_rep_time.p, h->d_tw.p, s.n_seg);
+    else lc.correlate<3>(h->stream, x, c0, ncell, h->d_rep_time.p, h->d_tw.p, s.n_seg,
+                         h->d_shift.p + (size_t)b0 * s.n_seg);
 }
 
 // Every search, on device-resident iq whose arguments acq_check_search has passed.
@@ -380,7 +317,7 @@ static int acq_search_run(gpsmi_acq* h, const void* d_iq, const int32_t* prn, in
                           int nbins, AcqSearch s, gpsmi_peak* out, void* out_dev, float* nbr) {
     // one segment of the 16368 path: the coherent search itself (MODE 0 forms its statistics from the
     // unscaled squares; MODE 2's would differ in the last bits of std)
-    if (h->pfa && s.segmented && s.n_seg == 1) s = AcqSearch{s.n_coh, 1, nullptr, s.wait, false};
+    if (h->lc.pfa() && s.segmented && s.n_seg == 1) s = AcqSearch{s.n_coh, 1, nullptr, s.wait, false};
     h->last_ms = 0.f;
     if (nsv == 0 || nbins == 0) return GPSMI_OK;            // empty search: nothing to do
     GPSMI_HIP(hipSetDevice(h->cfg.device));
@@ -397,14 +334,12 @@ static int acq_search_run(gpsmi_acq* h, const void* d_iq, const int32_t* prn, in
         if ((rc = h->d_nc.reserve(nbc * n_seg * cs, "gpsmi_acq segment scratch"))) return rc;
         x = h->d_nc.p;
     } else if (h->direct) {
-        if ((rc = h->d_fold.reserve((size_t)nbins * cs, "gpsmi_acq folded samples")) ||
-            (!h->pfa && (rc = h->d_mag.reserve(cells * cs, "gpsmi_acq magnitudes"))))
-            return rc;
+        if ((rc = h->d_fold.reserve((size_t)nbins * cs, "gpsmi_acq folded samples"))) return rc;
         x = h->d_fold.p;
     } else {
         x = h->d_spec.p;
     }
-    if (h->direct && (rc = acq_reserve_cells(h, cells))) return rc;
+    if (h->direct && (rc = h->lc.reserve(cells))) return rc;
     rc = acq_stage(h, prn, nsv, freqs, nbins);
     if (rc) return rc;
     if (s.deep) {
@@ -443,7 +378,7 @@ static int acq_search_run(gpsmi_acq* h, const void* d_iq, const int32_t* prn, in
     }
     if (h->direct)
         hipLaunchKernelGGL(acq_peaks_kernel, dim3(((int)cells + 255) / 256), dim3(256), 0, h->stream,
-                           h->d_stats.p, h->d_peaks.p, d_nbr, (int)cells);
+                           h->lc.d_stats.p, h->d_peaks.p, d_nbr, (int)cells);
     GPSMI_HIP(hipGetLastError());
     GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
     rc = acq_copy_out(h, nbins, nsv, out, out_dev, nbr);

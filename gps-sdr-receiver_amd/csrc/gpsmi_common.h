@@ -32,6 +32,7 @@ int fail(int code, const char* fmt, ...);
 // the value set through the ABI, else the environment variable of the same meaning, else `fallback`.
 // Keys: see the table in gpsmi_core.hip.  -> false for an unknown key.
 bool default_opt(const char* key, long long* value, long long fallback);
+int default_opt_count();                 // how many keys there are
 
 // Is [p, p + bytes) inside a block handed out by gpsmi_host_alloc (and not freed since)?  -> the
 // address a kernel reaches it at.

@@ -27,7 +27,8 @@ int fail(int code, const char* fmt, ...) {
 }
 
 // The options of gpsmi_set_default / gpsmi_trk_set_option (include/gpsmi.h) and the environment
-// variable that sets each one's default when the ABI has not.
+// variable that sets each one's default when the ABI has not.  What a tracking handle does with each
+// is the table of gpsmi_trk.hip; gpsmi_trk_create refuses to build when the two key lists differ.
 struct OptDef { const char* key; const char* env; bool set; long long value; };
 static OptDef g_opts[] = {
     {"correlator", "GPSMI_STREAM_MFMA", false, 0},
@@ -37,14 +38,12 @@ static OptDef g_opts[] = {
     {"corr_small2", nullptr, false, 0},
     {"span_single_max", "GPSMI_SPAN_SINGLE_MAX", false, 0},
     {"stream_inline_max", "GPSMI_STREAM_INLINE_MAX", false, 0},
-    {"stream_direct_max", "GPSMI_STREAM_DIRECT_MAX", false, 0},
     {"done_by_dispatch", "GPSMI_DONE_BY_DISPATCH", false, 0},
     {"corr_overlap", "GPSMI_CORR_OVERLAP", false, 0},
     {"stream_thread", "GPSMI_STREAM_THREAD", false, 0},
     {"stream_depth", "GPSMI_STREAM_DEPTH", false, 0},
     {"fold_chunk", "GPSMI_FOLD_CHUNK", false, 0},
     {"epilogue_form", "GPSMI_EPILOGUE_FORM", false, 0},
-    {"copy_stream", "GPSMI_COPY_STREAM", false, 0},
     {"debug_flags", "GPSMI_DEBUG_FLAGS", false, 0},
 };
 static std::mutex g_opts_mutex;
@@ -72,6 +71,8 @@ bool default_opt(const char* key, long long* value, long long fallback) {
     }
     return true;
 }
+
+int default_opt_count() { return (int)(sizeof(g_opts) / sizeof(g_opts[0])); }
 
 // the page-locked blocks gpsmi_host_alloc has handed out
 struct HostAlloc { char* base; size_t bytes; char* dev; };

@@ -3,26 +3,27 @@
 // Replaces the numeric part of gpslib.SatStream.process (reference
 // src/gpslib.py:1141-1210).  A "job" is one (channel, block) pair; the closed
 // loop runs the open channels of one block, replay runs nb x nch jobs at once
-// from a recorded state table.  Three kernels per call, in stream order:
+// from a recorded state table.  A call is three stages in stream order (trk_launch), each with the
+// paths a handle fixes at create time (CodePhase, Correlator):
 //
-//   trk_corr_kernel   (gpsmi_trk_corr.h) one workgroup per (block, six
-//                     channels): carrier wipe-off and fold of the centre
-//                     corr_avg code periods (demodDoppler :1343-1346),
-//                     2048-point FFT in LDS, x conj(replica spectrum), FFT
-//                     again as the inverse, |.|, mean / std / first argmax and
-//                     the neighbours of the peak (cacodeCorr :1315-1327,
-//                     findCodePhase :1293-1304); CORR_MIN threshold,
-//                     fitCodePhase (:1268-1290) and the DELAY the block is
-//                     decoded with (:1181-1182).
-//   trk_stream_kernel (gpsmi_trk_stream.h) the correlator: carrier-NCO mix of
-//                     the whole block times the replica rolled by DELAY
-//                     (decodeData :1400-1401), summed per code-period window
-//                     (:1408-1420) including the partial first window and the
-//                     carry into the next block (:1403-1405, :1440).
-//   trk_epilogue_kernel  (gpsmi_trk_epilogue.h) one wave per job, lane = prompt
-//                     dump: window means,
-//                     amplitude statistics (:1186-1188), phaseLockedLoop
-//                     (:1215-1262) and the state update (:1178, :1205-1208).
+//   code phase   carrier wipe-off and fold of the centre corr_avg code periods (demodDoppler
+//                :1343-1346), circular correlation with the replica, |.|, mean / std / first argmax and
+//                the neighbours of the peak (cacodeCorr :1315-1327, findCodePhase :1293-1304); CORR_MIN
+//                threshold, fitCodePhase (:1268-1290) and the DELAY the block is decoded with (:1181-1182).
+//                Fft2048: trk_corr_kernel (gpsmi_trk_corr.h), all of it in one workgroup per (block, up to
+//                six channels), the 2048-point FFTs in LDS.  Long, any other code length:
+//                trk_fold_general_kernel, the correlation of gpsmi_longcorr.h (native 16368-point,
+//                32768-point pair or time domain), trk_decide_kernel (gpsmi_trk_general.h).
+//   correlator   carrier-NCO mix of the whole block times the replica rolled by DELAY (decodeData
+//                :1400-1401), summed per code-period window (:1408-1420) including the partial first
+//                window and the carry into the next block (:1403-1405, :1440).  Span: trk_span_kernel on
+//                the matrix pipe (gpsmi_trk_span.h), CS = 2048, a single-block form for small launches
+//                and a batch form of persistent workgroups.  Span8: trk_span8_kernel (gpsmi_trk_span8.h),
+//                CS = 16368 with N_CYC = 8.  Vector: trk_stream_kernel (gpsmi_trk_stream.h), everything
+//                else; in chunks plus trk_partial_reduce_kernel where a code period exceeds one span.
+//   epilogue     (gpsmi_trk_epilogue.h) window means, amplitude statistics (:1186-1188), phaseLockedLoop
+//                (:1215-1262) and the state update (:1178, :1205-1208): from the records of Span8 or of
+//                Span's single-block form, else from the window sums, eight lanes or a wave per job.
 //
 // Loop-carried state lives in device memory; the closed loop needs no host
 // round trip between blocks.
@@ -126,8 +127,7 @@ __device__ inline double fit_code_phase(double lo, double pk, double hi, int mx)
 #pragma clang fp contract(fast)
 #include "gpsmi_trk_stream.h"
 #include "gpsmi_trk_corr.h"
-#include "gpsmi_bigfft.h"
-#include "gpsmi_pfa.h"
+#include "gpsmi_longcorr.h"
 #include "gpsmi_trk_general.h"
 #pragma clang fp contract(off)
 #include "gpsmi_trk_span.h"
@@ -168,8 +168,6 @@ struct gpsmi_trk {
     bool stage_used[2] = {false, false};
     int stage_idx = 0;
     size_t stream_inline_max = 8u << 20;     // bytes up to which a streamed block is copied on the main stream
-    size_t stream_direct_max = 0;            // bytes up to which the kernels of a streamed step read a page-locked
-                                             // block where it lies (no staging copy): option "stream_direct_max"
                                              // (GPSMI_STREAM_INLINE_MAX)
     hipEvent_t main_tail = nullptr;      // the event recorded behind the last work on `stream`, if any (borrowed)
     int cur = 0;                         // slot of the latest launch
@@ -197,17 +195,31 @@ struct gpsmi_trk {
     bool replay_forced = false;
     int corr_cg = 4;
     int corr_small1 = 384, corr_small2 = 1536;   // jobs per launch up to which 1 / 2 channels per correlation workgroup
-    int done_by_dispatch = 1;          // option "done_by_dispatch" = 0: an event record behind the correlator instead
-    // code_samples != 2048: time-domain correlation + chunked correlator
-    bool general = false;
+    int done_by_dispatch = 1;          // 0: an event record behind the correlator instead
+    bool want_matrix = true;           // the matrix-pipe correlators where they exist, as asked at create time
+    // The path plan, fixed at create time: which kernels the code-phase stage and the correlator are.
+    // One form per handle: the closed loop and the replay of a handle sum in the same order (bytewise
+    // equal results).
+    enum class CodePhase { Fft2048, Long };            // Long: code_samples != 2048, the method is lc's
+    enum class Correlator { Span, Span8, Vector };     // Span: CS = 2048 (N_CYC 32 / 16 / 8 as template parameter
+                                                       // NC); Span8: CS = 16368 with N_CYC = 8; both by default
+                                                       // where they apply, Vector everywhere else
+    CodePhase codephase = CodePhase::Fft2048;
+    Correlator correlator = Correlator::Vector;
+    LongCorr lc;                     // CodePhase::Long: method, replica spectra, job tables and statistics
+    bool long_code() const { return codephase == CodePhase::Long; }
+    // raw u8 input is read by trk_corr_kernel and trk_span_kernel alone
+    bool takes_raw_u8() const { return correlator == Correlator::Span; }
+    // the fold / correlation / statistics scratch of the long-code path exists once per handle, not per
+    // result slot: two batches in flight on two streams would overwrite each other's intermediates
+    bool scratch_per_handle() const { return long_code(); }
+    // the vector correlator in more than one span per code period: partial sums, then a reduction
+    bool chunked() const { return correlator == Correlator::Vector && nchunks > 1; }
     static constexpr int stream_j = 8;   // code positions per lane of the vector correlator
-    int mfma = 0;                    // 4: the span form of the matrix-pipe correlator (gpsmi_trk_span.h),
-                                     // the default where it applies; 0: another correlator
-    int codephase = 0;               // option "codephase" as taken at create time
-    int corr_overlap = 0;            // option "corr_overlap": see gpsmi_trk_replay_run_async
-    int fold_chunk = 0;              // option "fold_chunk": blocks per fold -> correlation piece at CS = 16368
-    int epilogue_form = 1;           // option "epilogue_form": 1 = eight lanes per job in the batch epilogue
-                                     // (trk_epilogue8_kernel), 0 = a wave per job (trk_epilogue_kernel); same bits
+    int corr_overlap = 0;            // see gpsmi_trk_replay_run_async
+    int fold_chunk = 0;              // blocks per fold -> correlation piece at CS = 16368
+    int epilogue_form = 1;           // 1 = eight lanes per job in the batch epilogue (trk_epilogue8_kernel),
+                                     // 0 = a wave per job (trk_epilogue_kernel); same bits
     DevBuf<float> d_code_eo;         // [GPSMI_MAX_PRN + 1][...]: the replica re-cut for the matrix correlators.  Span form
                                      // (2048): four planes by index mod 4, entry h of plane e = replica[(4 h + e) mod 2048],
                                      // 1024 entries each (a lane's run never wraps); span8 form: two planes by index
@@ -215,13 +227,8 @@ struct gpsmi_trk {
     int n_cu = 256;                  // compute units of the device
     int iq_fmt = GPSMI_IQ_C64;       // what the iq pointers of process / replay point to
     int nchunks = 1;                 // spans of 256 * stream_j positions per code period
-    DevBuf<float2> d_fold; DevBuf<float> d_mag; DevBuf<DirStats> d_stats;
-    DevBuf<int> d_xsel, d_rsel; DevBuf<float2> d_partial_g;
-    bool big = false;                // correlation through the 32768-point FFT pair
-    DevBuf<float2> d_twN, d_RS, d_S;
-    bool pfa = false;                // ... or natively in LDS at 16368 samples (gpsmi_pfa.h)
-    DevBuf<float2> d_RSp;
-    bool span8 = false;              // the matrix-pipe correlator for CS = 16368, N_CYC = 8 (gpsmi_trk_span8.h)
+    DevBuf<float2> d_fold;           // CodePhase::Long: the folded samples of one piece of a launch
+    DevBuf<float2> d_partial_g;      // chunked(): [jobs][nchunks][n_cyc + 1] partial sums
     TrkParams P;
     int stream_thread = 1;
     int stream_depth = 2;            // calls a streamed step's buffers stay in use: 2 (gpsmi.h) or 3
@@ -234,11 +241,9 @@ struct gpsmi_trk {
     // result slot goes as a whole, its buffers between its events and the streams.
     DevStream stream;
     DevStream epi_stream;                // replay: the epilogue of run k beside the code-phase
-                                         // correlation of run k + 1 (the other slot's buffers)
-    DevStream own_copy_stream;           // option "copy_stream" = 1 only
-    hipStream_t copy_stream = nullptr;   // result read-back, overlaps the next replay run: own_copy_stream, else
-                                         // the epilogue's stream (borrowed either way)
-    DevStream alt_stream;                // "corr_overlap": the runs of result slot 1 (slot 0 keeps `stream`)
+                                         // correlation of run k + 1 (the other slot's buffers), and the
+                                         // result read-back behind it (trk_build says why not on a stream of its own)
+    DevStream alt_stream;                // corr_overlap: the runs of result slot 1 (slot 0 keeps `stream`)
     DevStream up_stream;                 // uploads of streamed blocks beyond stream_inline_max
     // two result slots: a replay run writes one while the other is still being copied out
     struct Slot {
@@ -254,14 +259,14 @@ struct gpsmi_trk {
         hipEvent_t corr_stop = nullptr;      // the event that carries the end stamp of the slot's timed correlator (borrowed)
         bool copy_pending = false, epi_pending = false;
         int timing_pending = 0;              // the timing mode of the slot's run, until its times are taken
-        hipStream_t run_stream = nullptr;    // "corr_overlap": the stream the slot's runs are enqueued on (null: h->stream)
+        hipStream_t run_stream = nullptr;    // corr_overlap: the stream the slot's runs are enqueued on (null: h->stream)
         // a replay run of this slot, or its read-back, is still outstanding
         bool in_flight() const { return copy_pending || epi_pending; }
     } slot[2];
     DevEvent order;                      // orders other handles' streams behind this one
     DevEvent up_done[2], stage_free[2];
     DevEvent in_done[2];                 // end of a streamed step (its iq read, its out written)
-    // gpsmi_trk_process_stream's submission thread (option "stream_thread", default on; gpsmi_submit.h):
+    // gpsmi_trk_process_stream's submission thread (default on; gpsmi_submit.h):
     // the four launches and the event record of a streamed step cost ~25 us of runtime calls on the
     // host -- as long as the step runs on the GPU -- so they are made by a thread of the handle's own
     // while the caller prepares its next block.  Every other entry point first waits for this thread
@@ -279,34 +284,37 @@ struct gpsmi_trk {
     size_t iq_bytes(size_t n) const { return n * (iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)); }
 };
 
+using CodePhase = gpsmi_trk::CodePhase;
+using Correlator = gpsmi_trk::Correlator;
+
 constexpr int kSpanUnitsMax = 256;   // (block, channel group) units the single-block span form can serve (records)
 
-// Everything sized by the job count, for njobs jobs.  A larger count reallocates all of it (a
-// DevBuf whose size grows; the records of the single-block span form, of one fixed size, by hand).
+// Everything sized by the job count, for njobs jobs, path by path.  A larger count reallocates all of
+// it (a DevBuf whose size grows; the records of the single-block span form, of one fixed size, by hand).
 static int trk_reserve(gpsmi_trk* h, size_t njobs) {
     if (njobs <= h->njobs_cap) return GPSMI_OK;
     h->njobs_cap = 0;
     const size_t cs = h->cfg.code_samples, per_job = h->cfg.n_cyc + 1;
     int rc = GPSMI_OK;
-    if (h->mfma == 4)       // 32 records per (block, channel group) of the single-block span form
+    // code phase, Long: the folded samples and LongCorr's tables (Fft2048 keeps everything in LDS)
+    if (h->long_code()) {
+        rc = h->d_fold.reserve(njobs * cs, "gpsmi_trk folded samples");
+        if (!rc) rc = h->lc.reserve(njobs);
+    }
+    // correlator.  Span: 32 records per (block, channel group) of the single-block form; Span8: one
+    // 2 KiB record per range of every (block, channel group); Vector in chunks: the partial sums
+    if (h->correlator == Correlator::Span)
         for (auto& sl : h->slot) {
             sl.d_rec.release();
             if (!rc) rc = sl.d_rec.reserve((size_t)kSpanUnitsMax * 32 * kSpRecFloats, "gpsmi_trk span records");
         }
-    if (h->general) {
-        if (!rc) rc = h->d_fold.reserve(njobs * cs, "gpsmi_trk folded samples");
-        if (!rc && !h->pfa) rc = h->d_mag.reserve(njobs * cs, "gpsmi_trk magnitudes");
-        if (!rc) rc = h->d_stats.reserve(njobs, "gpsmi_trk job statistics");
-        if (!rc) rc = h->d_xsel.reserve(njobs, "gpsmi_trk job table");
-        if (!rc) rc = h->d_rsel.reserve(njobs, "gpsmi_trk job table");
-    }
-    if (h->span8) {         // one 2 KiB record per range of every (block, channel group)
+    if (h->correlator == Correlator::Span8) {
         const size_t units = ((njobs + h->max_ch - 1) / h->max_ch) * ((h->max_ch + kSpCh - 1) / kSpCh);
         for (auto& sl : h->slot)
             if (!rc) rc = sl.d_rec.reserve(units * kS8Ranges * kS8RecFloats, "gpsmi_trk span records");
     }
-    if (!rc && h->nchunks > 1 && !h->span8)
-        rc = h->d_partial_g.reserve(njobs * h->nchunks * per_job, "gpsmi_trk partial sums");
+    if (!rc && h->chunked()) rc = h->d_partial_g.reserve(njobs * h->nchunks * per_job, "gpsmi_trk partial sums");
+    // every path: the replay tables and, per result slot, descriptors, window sums and records
     if (!rc) rc = h->d_tab_in.reserve(njobs, "gpsmi_trk job table");
     if (!rc) rc = h->d_tab_out.reserve(njobs, "gpsmi_trk job table");
     if (!rc) rc = h->d_forced.reserve(njobs, "gpsmi_trk job table");
@@ -319,184 +327,178 @@ static int trk_reserve(gpsmi_trk* h, size_t njobs) {
     return rc;
 }
 
-// The last kernel of a launch: with `tail_stop`, the event carries the dispatch's own completion
-// signal (and stop_used says so); else a plain launch.  The arguments are converted to the kernel's
-// parameter types here (hipExtLaunchKernelGGL takes no others).
+// One kernel with an optional start and an optional stop event that carry the dispatch's own begin /
+// end stamps and completion signal (hipExtLaunchKernelGGL) instead of event records around it; with
+// neither, a plain launch.  The arguments are converted to the kernel's parameter types here
+// (hipExtLaunchKernelGGL takes no others).
 template <typename... KArgs, typename... Args>
-static void launch_tail(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t stream, hipEvent_t tail_stop,
-                        bool& stop_used, Args... args) {
-    if (tail_stop) {
-        hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, nullptr, tail_stop, 0, static_cast<KArgs>(args)...);
-        stop_used = true;
-    } else {
+static void launch_ev(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t stream, hipEvent_t start,
+                      hipEvent_t stop, Args... args) {
+    if (start || stop)
+        hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, start, stop, 0, static_cast<KArgs>(args)...);
+    else
         hipLaunchKernelGGL(kernel, grid, block, 0, stream, static_cast<KArgs>(args)...);
-    }
 }
 
-// the three kernels over njobs jobs on the handle's stream, events around them
-static int trk_launch(gpsmi_trk* h, gpsmi_trk::Slot& sl, const void* d_iq_v,
-                      const gpsmi_trk_state* st_in, gpsmi_trk_state* st_out, const int* forced,
-                      int njobs, int nch, bool side_epilogue = false, hipEvent_t tail_stop = nullptr,
-                      bool* tail_stop_used = nullptr) {
-    // tail_stop: an event to carry the completion signal of the launch's LAST kernel (the epilogue),
-    // instead of an event record behind it -- a record is a barrier packet, ~5 us of idle queue
-    // between this step and the next (the streamed closed loop: 32.5 -> 27 us per block);
-    // *tail_stop_used says whether the epilogue form at hand could take it
-    TrkParams P = h->P;
-    P.nch = nch;
-    // the stream this launch goes to: the handle's, or ("corr_overlap") the slot's own, so that the
-    // code-phase correlation of this batch may run beside the correlator of the batch before
-    hipStream_t rs = sl.run_stream ? sl.run_stream : h->stream;
-    h->main_tail = nullptr;
-    const float2* d_iq = static_cast<const float2*>(d_iq_v);       // (raw uint16 when iq_fmt says so)
-    sl.corr_stop = sl.ev[2];
-    const bool timed = h->timing == 1;   // each event record is a barrier packet (~5 us of bubble)
-    const bool corr_stamps = h->timing == 2;
-    if (timed) GPSMI_HIP(hipEventRecord(sl.ev[0], rs));
-    const int nblocks = njobs / nch;
-    const int ngroups = (nch + kGroupCh - 1) / kGroupCh;
-    const dim3 sgrid(((nblocks + 7) / 8) * 8 * ngroups);
-    // a launch too small to fill the CUs with whole blocks (the closed loop): every span of
-    // a block is a wave of its own; same bits as the batch form (gpsmi_trk_span.h)
-    const int ng_span = (nch + kSpCh - 1) / kSpCh;
-    const bool span_single = h->mfma == 4 && nblocks * ng_span <= h->span_single_max;
-    // ---- code-phase correlation
-    if (h->general) {
-        const int cs = P.cs;
-        // The folded samples (nch x cs complex64 per block: 805 MB for a 512-block batch at 16368) are an
-        // intermediate between two kernels: with the native-length correlation they go through in
-        // pieces of `fold_chunk` blocks that reuse one scratch area, so that what the fold writes is
-        // still in the memory-side cache when the correlation reads it (option "fold_chunk"; 0: the
-        // whole launch at once)
-        const int chunk = (h->pfa && h->fold_chunk > 0 && h->fold_chunk < nblocks) ? h->fold_chunk : nblocks;
-        for (int b0 = 0; b0 < nblocks; b0 += chunk) {
-            const int nbc = nblocks - b0 < chunk ? nblocks - b0 : chunk;
-            hipLaunchKernelGGL(trk_fold_general_kernel, dim3((cs + 255) / 256, nbc), dim3(256), 0,
-                               rs, d_iq, h->d_t32.p, st_in, P, h->d_fold.p, h->d_xsel.p, h->d_rsel.p,
-                               sl.d_mid.p, b0);
-            if (h->pfa)              // transform, product, transform and statistics in one launch
-                pfa_corr_launch(rs, h->d_fold.p, h->d_xsel.p, h->d_rsel.p, nbc * nch, h->d_RSp.p, h->d_stats.p, b0 * nch);
+// The geometry of one launch of njobs = nblocks x nch jobs.
+struct TrkGeom {
+    int nblocks;
+    int ngroups, ng_span;    // channel groups of the vector correlator / of the span forms and their epilogues
+    // Span, a launch too small to fill the CUs with whole blocks (the closed loop): the single-block
+    // form, every span of a block a wave of its own; same bits as the batch form (gpsmi_trk_span.h)
+    bool span_single;
+    bool span_batch;         // Span's other form: persistent workgroups, the one whose dispatch can carry events
+    dim3 span_grid, vec_grid;
+};
+static TrkGeom trk_geometry(const gpsmi_trk* h, int njobs, int nch) {
+    TrkGeom g{njobs / nch, (nch + kGroupCh - 1) / kGroupCh, (nch + kSpCh - 1) / kSpCh};
+    const int span_units = g.nblocks * g.ng_span;
+    g.span_single = h->correlator == Correlator::Span && span_units <= h->span_single_max;
+    g.span_batch = h->correlator == Correlator::Span && !g.span_single;
+    // batch form: two workgroups per CU, an equal number of (block, channel group) units each
+    const int span_slots = sp_wg_per_cu(h->P.n_cyc) * h->n_cu;
+    const int span_per = (span_units + span_slots - 1) / span_slots;
+    g.span_grid = dim3(g.span_single ? span_units * 32 : (span_units + span_per - 1) / (span_per > 0 ? span_per : 1));
+    g.vec_grid = dim3(((g.nblocks + 7) / 8) * 8 * g.ngroups, h->nchunks);
+    return g;
+}
+
+// One launch: what its three stages share, and the stages.
+struct TrkLaunch {
+    gpsmi_trk* h; gpsmi_trk::Slot& sl; TrkParams P; TrkGeom g;
+    const void* d_iq;                    // (raw uint16 when iq_fmt says so)
+    const gpsmi_trk_state* st_in; gpsmi_trk_state* st_out; const int* forced;
+    int njobs, nch;
+    const float2* iq_c64() const { return static_cast<const float2*>(d_iq); }
+
+    void launch_codephase(hipStream_t rs) const {
+        const int nblocks = g.nblocks;
+        if (h->long_code()) {
+            // The folded samples (nch x cs complex64 per block: 805 MB for a 512-block batch at 16368) are an
+            // intermediate between two kernels: with the native-length correlation they go through in
+            // pieces of `fold_chunk` blocks that reuse one scratch area, so that what the fold writes is
+            // still in the memory-side cache when the correlation reads it (0: the whole launch at once)
+            const int chunk = (h->lc.pfa() && h->fold_chunk > 0 && h->fold_chunk < nblocks) ? h->fold_chunk : nblocks;
+            for (int b0 = 0; b0 < nblocks; b0 += chunk) {
+                const int nbc = nblocks - b0 < chunk ? nblocks - b0 : chunk;
+                hipLaunchKernelGGL(trk_fold_general_kernel, dim3((P.cs + 255) / 256, nbc), dim3(256), 0, rs, iq_c64(),
+                                   h->d_t32.p, st_in, P, h->d_fold.p, h->lc.d_xsel.p, h->lc.d_rsel.p, sl.d_mid.p, b0);
+                h->lc.correlate(rs, h->d_fold.p, b0 * nch, nbc * nch, h->d_code.p, h->d_tw.p);
+            }
+            hipLaunchKernelGGL(trk_decide_kernel, dim3((njobs + 255) / 256), dim3(256), 0, rs, h->lc.d_stats.p,
+                               forced, P, njobs, sl.d_out.p, sl.d_mid.p);
+            return;
         }
-        if (h->pfa) {
-        } else if (h->big)
-            big_corr_launch(rs, h->d_fold.p, h->d_xsel.p, h->d_rsel.p, njobs, cs, h->d_RS.p, h->d_S.p,
-                            h->d_tw.p, h->d_twN.p, h->d_mag.p);
-        else
-            hipLaunchKernelGGL(circ_corr_direct_kernel,
-                               dim3((cs + kDirLagsPerWg - 1) / kDirLagsPerWg, njobs), dim3(256), 0,
-                               rs, h->d_fold.p, h->d_code.p, h->d_xsel.p, h->d_rsel.p, cs,
-                               h->d_mag.p);
-        if (!h->pfa)
-            hipLaunchKernelGGL(corr_stats_kernel, dim3(njobs), dim3(256), 0, rs, h->d_mag.p, cs,
-                               h->d_stats.p);
-        hipLaunchKernelGGL(trk_decide_kernel, dim3((njobs + 255) / 256), dim3(256), 0, rs,
-                           h->d_stats.p, forced, P, njobs, sl.d_out.p, sl.d_mid.p);
-    } else {
         // channels per correlation workgroup: fewer channels = fewer live accumulators
         // = more workgroups per CU for the barrier-heavy FFT phase (GPSMI_CORR_CG to tune)
         // (a single block, the closed loop, is latency-bound: spread it over more CUs)
         // (GPSMI_CORR_SMALL: job counts up to which one / two channels per workgroup are taken; measured
         // with R batched receivers of 12 channels, tools/batched_bench.py)
-        const int jobs_all = nblocks * nch;
-        const int cg = jobs_all <= h->corr_small1 ? 1 : (jobs_all <= h->corr_small2 ? 2 : h->corr_cg);
+        const int cg = njobs <= h->corr_small1 ? 1 : (njobs <= h->corr_small2 ? 2 : h->corr_cg);
         const int ng = (nch + cg - 1) / cg;
-        const dim3 cgrid(corr_grid(nblocks, ng));
         with_value<6, 4, 2, 1>(cg, [&](auto cgv) { with_fmt(h->iq_fmt, [&](auto fmt) {
-            hipLaunchKernelGGL((trk_corr_kernel<decltype(cgv)::value, decltype(fmt)::value>), cgrid, dim3(256), 0,
-                               rs, d_iq_v, st_in, forced, h->d_rep.p, h->d_tw.p, P, ng, nblocks, sl.d_out.p, sl.d_mid.p);
+            hipLaunchKernelGGL((trk_corr_kernel<decltype(cgv)::value, decltype(fmt)::value>), dim3(corr_grid(nblocks, ng)),
+                               dim3(256), 0, rs, d_iq, st_in, forced, h->d_rep.p, h->d_tw.p, P, ng, nblocks,
+                               sl.d_out.p, sl.d_mid.p);
         }); });
     }
-    // ---- the correlator.  When a launch is timed, the two events of the batch form of the span
-    // correlator are the dispatch's own begin / end stamps (hipExtLaunchKernel: what a kernel
-    // trace reports), not event records around it: no barrier packets next to the kernel and
-    // no launch gap inside the pair.
-    const bool ext_timed = (timed || corr_stamps) && h->mfma == 4 && !span_single;
-    bool corr_done_recorded = false;
-    // batch form of the span correlator: persistent workgroups, two per CU, an equal number of
-    // (block, channel group) units each
-    const int span_units = nblocks * ng_span, span_slots = sp_wg_per_cu(P.n_cyc) * h->n_cu;
-    const int span_per = (span_units + span_slots - 1) / span_slots;
-    const dim3 span_grid((span_units + span_per - 1) / (span_per > 0 ? span_per : 1));
-    if (timed && !ext_timed) GPSMI_HIP(hipEventRecord(sl.ev[1], rs));
-    if (h->mfma) {                         // the correlator on the matrix pipe (span form, N_CYC = 32 / 16 / 8)
-        const int ng12 = (nch + kSpCh - 1) / kSpCh;
-        const JobMid* cmid = sl.d_mid.p;
-        const float* ceo = h->d_code_eo.p;
-        // replay: the event the epilogue stream (and a search) waits for is the completion signal of
-        // this very dispatch, not a record behind it - a record is one more barrier packet between
-        // this kernel and the next batch's first one
-        const bool by_dispatch = !span_single && side_epilogue && h->done_by_dispatch;
-        // (a timed launch that is also the one the epilogue stream waits for: ONE stop event serves
-        // both -- the dispatch's completion signal -- instead of a record packet behind the kernel)
-        sl.corr_stop = (ext_timed && by_dispatch) ? sl.corr_done : sl.ev[2];
-        // One launch of trk_span_kernel<NSPANS, WAVES, FMT, 0, NC>.  The single-block form goes out plainly.
-        // The batch form goes out with the dispatch's own begin / end stamps when it is timed (both events),
-        // with its completion signal as the stop event alone when the epilogue stream waits for this very
-        // dispatch, and plainly otherwise.
-        with_value<32, 16, 8>(P.n_cyc, [&](auto ncv) { with_fmt(h->iq_fmt, [&](auto fmt) {
-            constexpr int NC = decltype(ncv)::value, FMT = decltype(fmt)::value;
-            if (span_single)
-                hipLaunchKernelGGL((trk_span_kernel<1, 1, FMT, 0, NC>), dim3(nblocks * ng12 * 32), dim3(64), 0, rs,
-                                   d_iq_v, cmid, ceo, P, ng12, nblocks, sl.d_rec.p, sl.d_partial.p);
-            else if (ext_timed)
-                hipExtLaunchKernelGGL((trk_span_kernel<8, 4, FMT, 0, NC>), span_grid, dim3(256), 0, rs, sl.ev[1],
-                                      sl.corr_stop, 0, d_iq_v, cmid, ceo, P, ng12, nblocks, sl.d_rec.p,
-                                      sl.d_partial.p);
-            else if (by_dispatch)
-                hipExtLaunchKernelGGL((trk_span_kernel<8, 4, FMT, 0, NC>), span_grid, dim3(256), 0, rs, nullptr,
-                                      sl.corr_done, 0, d_iq_v, cmid, ceo, P, ng12, nblocks, sl.d_rec.p,
-                                      sl.d_partial.p);
-            else
-                hipLaunchKernelGGL((trk_span_kernel<8, 4, FMT, 0, NC>), span_grid, dim3(256), 0, rs, d_iq_v, cmid,
-                                   ceo, P, ng12, nblocks, sl.d_rec.p, sl.d_partial.p);
-        }); });
-        corr_done_recorded = by_dispatch;
-    } else if (h->span8) {                 // CS = 16368, N_CYC = 8 on the matrix pipe
-        const int ng12 = (nch + kSpCh - 1) / kSpCh;
-        const int nwaves = nblocks * ng12 * kS8Ranges;
-        hipLaunchKernelGGL(trk_span8_kernel, dim3((nwaves + 3) / 4), dim3(256), 0, rs, d_iq,
-                           sl.d_mid.p, h->d_code_eo.p, P, ng12, nblocks, sl.d_rec.p);
-    } else {                               // the vector correlator (other block / code lengths)
-        const dim3 grid(sgrid.x, h->nchunks), block(kStreamThreads);
-        float2* pdst = h->nchunks > 1 ? h->d_partial_g.p : sl.d_partial.p;
-        with_value<32, 16, 8>(P.n_cyc, [&](auto ncv) { with_value<1, 0>(h->general ? 0 : 1, [&](auto pow2) {
-            hipLaunchKernelGGL((trk_stream_kernel<decltype(ncv)::value, decltype(pow2)::value != 0, 8>), grid, block, 0,
-                               rs, d_iq, st_in, sl.d_mid.p, h->d_code.p, P, ngroups, nblocks, pdst);
-        }); });
-        if (h->nchunks > 1) {
-            const int per_job = P.n_cyc + 1;
-            hipLaunchKernelGGL(trk_partial_reduce_kernel, dim3((njobs * per_job + 255) / 256),
-                               dim3(256), 0, rs, h->d_partial_g.p, h->nchunks, per_job, njobs,
-                               sl.d_mid.p, sl.d_partial.p);
+
+    // `start` / `stop` (either may be null) go to the span form's dispatch
+    void launch_correlator(hipStream_t rs, hipEvent_t start, hipEvent_t stop) const {
+        if (h->correlator == Correlator::Span) {
+            // trk_span_kernel<NSPANS, WAVES, FMT, 0, NC>: <1, 1> the single-block form, <8, 4> the batch form
+            with_value<32, 16, 8>(P.n_cyc, [&](auto ncv) { with_fmt(h->iq_fmt, [&](auto fmt) {
+                with_value<1, 8>(g.span_single ? 1 : 8, [&](auto nsp) {
+                    constexpr int NS = decltype(nsp)::value, W = NS == 1 ? 1 : 4;
+                    launch_ev(trk_span_kernel<NS, W, decltype(fmt)::value, 0, decltype(ncv)::value>, g.span_grid,
+                              dim3(64 * W), rs, start, stop, d_iq, sl.d_mid.p, h->d_code_eo.p, P, g.ng_span, g.nblocks,
+                              sl.d_rec.p, sl.d_partial.p);
+                });
+            }); });
+        } else if (h->correlator == Correlator::Span8) {
+            const int nwaves = g.nblocks * g.ng_span * kS8Ranges;
+            hipLaunchKernelGGL(trk_span8_kernel, dim3((nwaves + 3) / 4), dim3(256), 0, rs, iq_c64(), sl.d_mid.p,
+                               h->d_code_eo.p, P, g.ng_span, g.nblocks, sl.d_rec.p);
+        } else {                               // other block / code lengths
+            float2* pdst = h->chunked() ? h->d_partial_g.p : sl.d_partial.p;
+            with_value<32, 16, 8>(P.n_cyc, [&](auto ncv) { with_value<1, 0>(h->long_code() ? 0 : 1, [&](auto pow2) {
+                hipLaunchKernelGGL((trk_stream_kernel<decltype(ncv)::value, decltype(pow2)::value != 0, 8>), g.vec_grid,
+                                   dim3(kStreamThreads), 0, rs, iq_c64(), st_in, sl.d_mid.p, h->d_code.p, P, g.ngroups,
+                                   g.nblocks, pdst);
+            }); });
+            if (h->chunked())
+                hipLaunchKernelGGL(trk_partial_reduce_kernel, dim3((njobs * (P.n_cyc + 1) + 255) / 256), dim3(256), 0, rs,
+                                   h->d_partial_g.p, h->nchunks, P.n_cyc + 1, njobs, sl.d_mid.p, sl.d_partial.p);
         }
     }
+
+    // on `es`, with `tail_stop` (may be null) as its dispatch's stop event where the form at hand can
+    // take it.  -> whether it did
+    bool launch_epilogue(hipStream_t es, hipEvent_t tail_stop) const {
+        if (h->correlator == Correlator::Span8) {      // (its epilogue does not take tail_stop)
+            hipLaunchKernelGGL(trk_epilogue_span8_kernel, dim3((njobs + 3) / 4), dim3(256), 0, es, st_in, st_out,
+                               sl.d_mid.p, sl.d_rec.p, g.ng_span, P, njobs, sl.d_out.p);
+            return false;
+        }
+        if (g.span_single)
+            with_value<32, 16, 8>(P.n_cyc, [&](auto ncv) {
+                launch_ev(trk_epilogue_span_kernel<decltype(ncv)::value>, dim3(njobs), dim3(256), es, nullptr, tail_stop,
+                          st_in, st_out, sl.d_mid.p, sl.d_rec.p, g.ng_span, P, njobs, sl.d_out.p);
+            });
+        else if (h->epilogue_form == 0)          // a wave per job
+            launch_ev(trk_epilogue_kernel, dim3((njobs + 3) / 4), dim3(256), es, nullptr, tail_stop, st_in, st_out,
+                      sl.d_mid.p, sl.d_partial.p, P, njobs, sl.d_out.p);
+        else                                     // eight lanes per job (the default)
+            with_value<32, 16, 8>(P.n_cyc, [&](auto ncv) {
+                launch_ev(trk_epilogue8_kernel<decltype(ncv)::value>, dim3((njobs + 7) / 8), dim3(64), es, nullptr,
+                          tail_stop, st_in, st_out, sl.d_mid.p, sl.d_partial.p, P, njobs, sl.d_out.p);
+            });
+        return tail_stop != nullptr;
+    }
+};
+
+// the three stages over njobs jobs on the handle's stream, events around them
+static int trk_launch(gpsmi_trk* h, gpsmi_trk::Slot& sl, const void* d_iq, const gpsmi_trk_state* st_in,
+                      gpsmi_trk_state* st_out, const int* forced, int njobs, int nch, bool side_epilogue = false,
+                      hipEvent_t tail_stop = nullptr, bool* tail_stop_used = nullptr) {
+    // tail_stop: an event to carry the completion signal of the launch's LAST kernel (the epilogue),
+    // instead of an event record behind it -- a record is a barrier packet, ~5 us of idle queue
+    // between this step and the next (the streamed closed loop: 32.5 -> 27 us per block);
+    // *tail_stop_used says whether the epilogue form at hand could take it
+    TrkLaunch L{h, sl, h->P, trk_geometry(h, njobs, nch), d_iq, st_in, st_out, forced, njobs, nch};
+    L.P.nch = nch;
+    // the stream this launch goes to: the handle's, or (corr_overlap) the slot's own, so that the
+    // code-phase correlation of this batch may run beside the correlator of the batch before
+    hipStream_t rs = sl.run_stream ? sl.run_stream : h->stream;
+    h->main_tail = nullptr;
+    const bool timed = h->timing == 1;   // each event record is a barrier packet (~5 us of bubble)
+    if (timed) GPSMI_HIP(hipEventRecord(sl.ev[0], rs));
+    L.launch_codephase(rs);
+    // When a launch is timed, the two events of the batch form of the span correlator are the
+    // dispatch's own begin / end stamps (what a kernel trace reports), not event records around it:
+    // no barrier packets next to the kernel and no launch gap inside the pair.
+    const bool ext_timed = (timed || h->timing == 2) && L.g.span_batch;
+    // replay: the event the epilogue stream (and a search) waits for is the completion signal of
+    // the batch form's very dispatch, not a record behind it - a record is one more barrier packet
+    // between this kernel and the next batch's first one
+    const bool by_dispatch = L.g.span_batch && side_epilogue && h->done_by_dispatch;
+    // (a timed launch that is also the one the epilogue stream waits for: ONE stop event serves
+    // both -- the dispatch's completion signal -- instead of a record packet behind the kernel)
+    sl.corr_stop = (ext_timed && by_dispatch) ? sl.corr_done : sl.ev[2];
+    if (timed && !ext_timed) GPSMI_HIP(hipEventRecord(sl.ev[1], rs));
+    L.launch_correlator(rs, ext_timed ? sl.ev[1].h : nullptr,
+                        ext_timed ? sl.corr_stop : by_dispatch ? sl.corr_done.h : nullptr);
     if (timed && !ext_timed) GPSMI_HIP(hipEventRecord(sl.ev[2], rs));
     // replay: the epilogue goes to a stream of its own behind the correlator, so that the
     // code-phase correlation of the next run (other slot, main stream) starts at once
     hipStream_t es = rs;
     if (side_epilogue) {
         es = h->epi_stream;
-        if (!corr_done_recorded) GPSMI_HIP(hipEventRecord(sl.corr_done, rs));
+        if (!by_dispatch) GPSMI_HIP(hipEventRecord(sl.corr_done, rs));     // (else the dispatch signals it)
         h->main_tail = sl.corr_done;          // (gpsmi_acq_after_trk orders the search behind this one)
         GPSMI_HIP(hipStreamWaitEvent(es, sl.corr_done, 0));
     }
-    bool stop_used = false;
-    if (h->span8)                            // (its epilogue does not take tail_stop)
-        hipLaunchKernelGGL(trk_epilogue_span8_kernel, dim3((njobs + 3) / 4), dim3(256), 0, es, st_in,
-                           st_out, sl.d_mid.p, sl.d_rec.p, ng_span, P, njobs, sl.d_out.p);
-    else if (span_single)
-        with_value<32, 16, 8>(P.n_cyc, [&](auto ncv) {
-            launch_tail(trk_epilogue_span_kernel<decltype(ncv)::value>, dim3(njobs), dim3(256), es, tail_stop,
-                        stop_used, st_in, st_out, sl.d_mid.p, sl.d_rec.p, ng_span, P, njobs, sl.d_out.p);
-        });
-    else if (h->epilogue_form == 0)          // a wave per job
-        launch_tail(trk_epilogue_kernel, dim3((njobs + 3) / 4), dim3(256), es, tail_stop, stop_used, st_in,
-                    st_out, sl.d_mid.p, sl.d_partial.p, P, njobs, sl.d_out.p);
-    else                                     // eight lanes per job (the default)
-        with_value<32, 16, 8>(P.n_cyc, [&](auto ncv) {
-            launch_tail(trk_epilogue8_kernel<decltype(ncv)::value>, dim3((njobs + 7) / 8), dim3(64), es, tail_stop,
-                        stop_used, st_in, st_out, sl.d_mid.p, sl.d_partial.p, P, njobs, sl.d_out.p);
-        });
+    const bool stop_used = L.launch_epilogue(es, tail_stop);
     if (tail_stop_used) *tail_stop_used = stop_used;
     GPSMI_HIP(hipGetLastError());
     if (timed) GPSMI_HIP(hipEventRecord(sl.ev[3], es));
@@ -533,7 +535,7 @@ static int trk_settle(gpsmi_trk* h) {
     h->slot[0].epi_pending = h->slot[1].epi_pending = false;
     h->in_pending[0] = h->in_pending[1] = false;
     if (h->slot[0].copy_pending || h->slot[1].copy_pending)
-        GPSMI_HIP(hipStreamSynchronize(h->copy_stream));
+        GPSMI_HIP(hipStreamSynchronize(h->epi_stream));
     for (int k = 0; k < 2; ++k) {          // older slot first: last_*_ms end up with the latest run
         gpsmi_trk::Slot& sl = h->slot[k == 0 ? (h->cur ^ 1) : h->cur];
         sl.copy_pending = false;
@@ -632,56 +634,101 @@ HandleSync trk_sync(gpsmi_trk* h) {
 }
 }  // namespace gpsmi
 
-extern "C" {
+// ---- the options of a tracking handle (gpsmi.h documents them), one row each, read-only counters last.
+// trk_defaults, gpsmi_trk_set_option and gpsmi_trk_get_option walk this table; the process-wide defaults
+// and the environment names are gpsmi_core.hip's, whose keys trk_defaults holds against these.
+// Live: gpsmi_trk_set_option changes it on a live handle; LiveLower: ... and the next row bounds it from
+// above, as it bounds that one from below; Create: taken at create time from its default, `set` is
+// trk_defaults' alone; Stat: a counter, read only
+enum class OptKind { Live, LiveLower, Create, Stat };
+struct TrkOpt {
+    const char* key; OptKind kind;
+    long long builtin;                          // Create: the default of last resort (Live: the member's initialiser)
+    long long (*get)(const gpsmi_trk*);
+    // GPSMI_OK: stored; GPSMI_E_ARG: out of range (the caller words it); else the setter's own refusal
+    int (*set)(gpsmi_trk*, long long);
+};
+#define OPT_GET(expr) [](const gpsmi_trk* h) -> long long { return (expr); }
+#define OPT_SET(in_range, store) \
+    [](gpsmi_trk* h, long long v) -> int { if (!(in_range)) return GPSMI_E_ARG; store; return GPSMI_OK; }
+#define OPT_LIVE(key, field, in_range) {key, OptKind::Live, 0, OPT_GET(h->field), OPT_SET(in_range, h->field = (int)v)}
+#define OPT_FLAG(key, field) {key, OptKind::Live, 0, OPT_GET(h->field), OPT_SET(true, h->field = v != 0)}
+#define OPT_STAT(key, field) {key, OptKind::Stat, 0, OPT_GET(h->field), nullptr}
+static const TrkOpt kTrkOpts[] = {
+    // (reads as what runs, not what was asked)
+    {"correlator", OptKind::Create, 1, OPT_GET(h->correlator != Correlator::Vector), OPT_SET(true, h->want_matrix = v != 0)},
+    {"codephase", OptKind::Create, 0, OPT_GET(h->long_code() ? h->lc.option() : 0), nullptr},   // (LongCorr::build takes it)
+    {"debug_flags", OptKind::Create, 0, OPT_GET(h->P.flags), OPT_SET(true, h->P.flags = (int)v)},
+    OPT_LIVE("corr_cg", corr_cg, v == 2 || v == 4 || v == 6),
+    // 0 <= corr_small1 <= corr_small2 <= 2^24 at every moment; trk_defaults takes the two together
+    {"corr_small1", OptKind::LiveLower, 0, OPT_GET(h->corr_small1), OPT_SET(v >= 0 && v <= h->corr_small2, h->corr_small1 = (int)v)},
+    OPT_LIVE("corr_small2", corr_small2, v >= h->corr_small1 && v <= (1 << 24)),
+    OPT_LIVE("span_single_max", span_single_max, v >= 1 && v <= kSpanUnitsMax),
+    {"stream_inline_max", OptKind::Live, 0, OPT_GET((long long)h->stream_inline_max), OPT_SET(v >= 0, h->stream_inline_max = (size_t)v)},
+    OPT_FLAG("done_by_dispatch", done_by_dispatch), OPT_FLAG("stream_thread", stream_thread),
+    {"corr_overlap", OptKind::Live, 0, OPT_GET(h->corr_overlap),
+     [](gpsmi_trk* h, long long v) -> int {
+         if (v != 0 && h->scratch_per_handle())
+             return fail(GPSMI_E_STATE, "gpsmi_trk_set_option: corr_overlap needs CODE_SAMPLES = %d "
+                         "(the general path's scratch is per handle)", kFftN);
+         h->corr_overlap = v != 0;
+         return GPSMI_OK;
+     }},
+    OPT_LIVE("fold_chunk", fold_chunk, v >= 0 && v <= (1 << 20)), OPT_LIVE("epilogue_form", epilogue_form, v == 0 || v == 1),
+    OPT_LIVE("stream_depth", stream_depth, v >= 2 && v <= 64),
+    OPT_STAT("stat_stream_steps", stat_steps), OPT_STAT("stat_waits", stat_waits), OPT_STAT("stat_backlog", stat_backlog),
+    OPT_STAT("stat_quiesce_ns", stat_quiesce_ns), OPT_STAT("stat_evwait_ns", stat_evwait_ns),
+    OPT_STAT("stat_stream_wait_ns", stat_wait_ns), OPT_STAT("stat_stream_launch_ns", stat_launch_ns),
+};
 
-static int trk_build(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk* h);
+static const TrkOpt* trk_find_opt(const char* key) {
+    for (const TrkOpt& o : kTrkOpts)
+        if (!strcmp(o.key, key)) return &o;
+    return nullptr;
+}
 
-int gpsmi_trk_create(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk** out) {
-    GPSMI_REQUIRE(cfg && out, "null argument");
-    *out = nullptr;
-    GPSMI_REQUIRE(max_ch >= 1 && max_ch <= 4096, "max_ch out of range");
-    GPSMI_REQUIRE(cfg->code_samples >= 1024 && cfg->code_samples <= 65536 &&
-                      cfg->code_samples % 16 == 0,
-                  "code_samples must be a multiple of 16 in 1024..65536");
-    GPSMI_REQUIRE(cfg->n_cyc == 8 || cfg->n_cyc == 16 || cfg->n_cyc == 32,
-                  "n_cyc must be 8, 16 or 32 (gpsglob.py:122)");
-    GPSMI_REQUIRE(cfg->corr_avg >= 1, "corr_avg must be >= 1");
-    GPSMI_REQUIRE(1024 / cfg->n_cyc <= GPSMI_MAX_DF, "n_cyc too small for the DF list");
-    GPSMI_HIP(hipSetDevice(cfg->device));
-    gpsmi_trk* h = new (std::nothrow) gpsmi_trk();
-    if (!h) return fail(GPSMI_E_NOMEM, "out of host memory");
-    h->cfg = *cfg;
-    h->max_ch = max_ch;
-    h->general = cfg->code_samples != kFftN;
-    h->nchunks = (cfg->code_samples + 256 * h->stream_j - 1) / (256 * h->stream_j);
-    const int rc = trk_build(cfg, max_ch, h);
-    if (rc) {                       // nothing half-built leaves this function
-        (void)gpsmi_trk_destroy(h);
-        return rc;
+// The options of a new handle: their defaults come from gpsmi_set_default, else from the environment,
+// else from the measurements quoted at the fields.  A default the handle refuses (out of range, or
+// corr_overlap where the scratch is per handle) is ignored, and so is the error text of that refusal:
+// the caller's last error stays what it was.
+static int trk_defaults(gpsmi_trk* h) {
+    char prev_err[512];
+    snprintf(prev_err, sizeof(prev_err), "%s", last_error_buf());
+    int known = 0;
+    long long v = 0, v_up = 0;
+    for (const TrkOpt* o = kTrkOpts; o->kind != OptKind::Stat; ++o, ++known) {
+        const long long cur = o->kind == OptKind::Create ? o->builtin : o->get(h);
+        if (!default_opt(o->key, &v, cur)) return fail(GPSMI_E_STATE, "gpsmi_trk_create: no process-wide option '%s'", o->key);
+        if (o->kind == OptKind::LiveLower) {
+            // with the row behind it, a pair that bounds each other: both or neither.  With the lower one
+            // at 0 first, neither setter meets the other's old value
+            const TrkOpt* up = ++o;
+            const long long cur_up = up->get(h);
+            known += default_opt(up->key, &v_up, cur_up);
+            (up - 1)->set(h, 0);
+            if (up->set(h, v_up) || (up - 1)->set(h, v)) { up->set(h, cur_up); (up - 1)->set(h, cur); }
+        } else if (o->set && (o->kind == OptKind::Create || v != cur))
+            o->set(h, v);
     }
-    *out = h;
+    if (known != default_opt_count())
+        return fail(GPSMI_E_STATE, "gpsmi_trk_create: the handle's option table and the process-wide one differ");
+    snprintf(last_error_buf(), 512, "%s", prev_err);
     return GPSMI_OK;
 }
 
-}  // extern "C"
-
 static int trk_build(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk* h) {
     GPSMI_HIP(hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device));
-    int rc = h->stream.create();
+    int rc = trk_defaults(h);
+    if (!rc) rc = h->stream.create();
     if (!rc) rc = h->epi_stream.create();
     if (rc) return rc;
     // The read-back of a replay run follows the run's epilogue anyway and is over long before the next
-    // epilogue is due, so by default it shares the epilogue's stream: the HIP runtime maps streams onto
+    // epilogue is due, so it shares the epilogue's stream: the HIP runtime maps streams onto
     // four hardware queues (one per pipe of the command processor), and a process with this handle's
     // compute and epilogue streams, an acquisition handle's stream and the null stream has four.  A
     // fifth stream shares a queue with one of them -- which one differs from run to run -- and a step
     // whose epilogue or search queues behind the compute stream's kernels takes 0.33 ms instead of
     // 0.23 (GPU_MAX_HW_QUEUES=3 forces it; more queues than pipes cost as much: DESIGN.md 4.6).
-    // Option "copy_stream" = 1 (create time) gives the read-back a stream of its own again.
-    long long own_copy = 0;
-    default_opt("copy_stream", &own_copy, 0);
-    if (own_copy != 0 && (rc = h->own_copy_stream.create())) return rc;
-    h->copy_stream = own_copy != 0 ? h->own_copy_stream : h->epi_stream;
     rc = h->order.create(hipEventDisableTiming);
     for (auto& sl : h->slot) {
         for (auto& e : sl.ev)
@@ -704,41 +751,16 @@ static int trk_build(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk* h) {
         // (zeroed for slot 0: closed channels)
         (rc = h->d_code.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * cfg->code_samples, "gpsmi_trk replicas")))
         return rc;
-    long long want_matrix = 1;           // option "correlator": 0 keeps the vector kernel (gpsmi_trk_stream.h)
-    default_opt("correlator", &want_matrix, 1);
-    {
-        // default for CS = 2048, N_CYC = 32: the span form of the MFMA correlator.  One form per handle:
-        // the closed loop and the replay of a handle sum in the same order (bytewise equal results).
-        h->mfma = (!h->general && want_matrix != 0) ? 4 : 0;          // (N_CYC = 32, 16 and 8: template parameter NC)
-        if (h->mfma && (rc = h->d_code_eo.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * 2 * kFftN, "gpsmi_trk replica planes")))
-            return rc;
+    // the rest of the path plan (gpsmi_trk_create set the code phase)
+    if (h->want_matrix && !h->long_code()) {
+        h->correlator = Correlator::Span;
+        rc = h->d_code_eo.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * 2 * kFftN, "gpsmi_trk replica planes");
+    } else if (h->want_matrix && cfg->code_samples == kS8Cs && cfg->n_cyc == kS8Rows) {
+        h->correlator = Correlator::Span8;
+        rc = h->d_code_eo.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * 2 * kS8Cs, "gpsmi_trk replica planes");
     }
-    if (h->general) {
-        long long forced = 0;                    // option "codephase": 1 keeps the time-domain kernel,
-        default_opt("codephase", &forced, 0);    // 2 the zero-padded 32768-point pair
-        h->codephase = (int)forced;
-        h->pfa = cfg->code_samples == kPfaL && forced == 0;
-        h->big = !h->pfa && 2 * cfg->code_samples - 1 <= kBigN && forced != 1;
-    }
-    if (h->pfa && (rc = h->d_RSp.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * kPfaL, "gpsmi_trk replica spectra")))
-        return rc;                                           // (zeroed for slot 0: closed channels)
-    {
-        h->span8 = h->general && cfg->code_samples == kS8Cs && cfg->n_cyc == kS8Rows && want_matrix != 0;
-        if (h->span8 && (rc = h->d_code_eo.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * 2 * kS8Cs, "gpsmi_trk replica planes")))
-            return rc;
-    }
-    if (h->big) {
-        std::vector<float2> twn(kBigN);
-        for (int k = 0; k < kBigN; ++k) {
-            const double a = -2.0 * M_PI * (double)k / (double)kBigN;
-            twn[k] = make_float2((float)cos(a), (float)sin(a));
-        }
-        if ((rc = h->d_twN.upload(twn, "gpsmi_trk twiddles")) ||
-            // (zeroed for slot 0: closed channels)
-            (rc = h->d_RS.reserve_zeroed((size_t)(GPSMI_MAX_PRN + 1) * kBigN, "gpsmi_trk replica spectra")) ||
-            (rc = h->d_S.reserve((size_t)kBigChunkCells * kBigN, "gpsmi_trk correlation scratch")))
-            return rc;
-    }
+    if (!rc && h->long_code()) rc = h->lc.build(cfg->code_samples, "gpsmi_trk");
+    if (rc) return rc;
     if ((rc = h->d_block.reserve(ngps, "gpsmi_trk input block")) ||
         (rc = h->d_state.reserve_zeroed(max_ch, "gpsmi_trk states")))
         return rc;
@@ -750,34 +772,37 @@ static int trk_build(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk* h) {
     P.nch = max_ch; P.df_no = 1024 / cfg->n_cyc; P.t_last = t32[ngps - 1];
     P.om_min = (float)(2.0 * M_PI * (double)cfg->min_freq);
     P.om_max = (float)(2.0 * M_PI * (double)cfg->max_freq);
-    // the tuning options (gpsmi_trk_set_option changes them on a live handle); their defaults come
-    // from gpsmi_set_default, else from the environment, else from the measurements quoted at the fields
-    long long v = 0;
-    default_opt("debug_flags", &v, 0);
-    P.flags = (int)v;
-    const struct { const char* key; long long fallback; } tun[] = {
-        {"corr_cg", h->corr_cg}, {"span_single_max", h->span_single_max}, {"stream_inline_max", (long long)h->stream_inline_max},
-        {"stream_direct_max", (long long)h->stream_direct_max},
-        {"done_by_dispatch", h->done_by_dispatch}, {"corr_overlap", h->corr_overlap},
-        {"stream_thread", h->stream_thread}, {"stream_depth", h->stream_depth}, {"fold_chunk", h->fold_chunk},
-        {"epilogue_form", h->epilogue_form}};
-    // A default the handle refuses (out of range, or "corr_overlap" on the general path) is ignored,
-    // and so is the error text of that refusal: the caller's last error stays what it was.
-    char prev_err[512];
-    snprintf(prev_err, sizeof(prev_err), "%s", last_error_buf());
-    for (const auto& t : tun) {
-        default_opt(t.key, &v, t.fallback);
-        if (v != t.fallback && gpsmi_trk_set_option(h, t.key, v) != GPSMI_OK)
-            snprintf(last_error_buf(), 512, "%s", prev_err);
-    }
-    long long s1 = h->corr_small1, s2 = h->corr_small2;                 // (a pair: taken together)
-    default_opt("corr_small1", &s1, s1);
-    default_opt("corr_small2", &s2, s2);
-    if (s1 >= 0 && s2 >= s1 && s2 <= (1 << 24)) { h->corr_small1 = (int)s1; h->corr_small2 = (int)s2; }
     return trk_reserve(h, max_ch);
 }
 
 extern "C" {
+
+int gpsmi_trk_create(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk** out) {
+    GPSMI_REQUIRE(cfg && out, "null argument");
+    *out = nullptr;
+    GPSMI_REQUIRE(max_ch >= 1 && max_ch <= 4096, "max_ch out of range");
+    GPSMI_REQUIRE(cfg->code_samples >= 1024 && cfg->code_samples <= 65536 &&
+                      cfg->code_samples % 16 == 0,
+                  "code_samples must be a multiple of 16 in 1024..65536");
+    GPSMI_REQUIRE(cfg->n_cyc == 8 || cfg->n_cyc == 16 || cfg->n_cyc == 32,
+                  "n_cyc must be 8, 16 or 32 (gpsglob.py:122)");
+    GPSMI_REQUIRE(cfg->corr_avg >= 1, "corr_avg must be >= 1");
+    GPSMI_REQUIRE(1024 / cfg->n_cyc <= GPSMI_MAX_DF, "n_cyc too small for the DF list");
+    GPSMI_HIP(hipSetDevice(cfg->device));
+    gpsmi_trk* h = new (std::nothrow) gpsmi_trk();
+    if (!h) return fail(GPSMI_E_NOMEM, "out of host memory");
+    h->cfg = *cfg;
+    h->max_ch = max_ch;
+    h->codephase = cfg->code_samples != kFftN ? CodePhase::Long : CodePhase::Fft2048;
+    h->nchunks = (cfg->code_samples + 256 * h->stream_j - 1) / (256 * h->stream_j);
+    const int rc = trk_build(cfg, max_ch, h);
+    if (rc) {                       // nothing half-built leaves this function
+        (void)gpsmi_trk_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return GPSMI_OK;
+}
 
 int gpsmi_trk_destroy(gpsmi_trk* h) {
     if (!h) return GPSMI_OK;
@@ -785,7 +810,6 @@ int gpsmi_trk_destroy(gpsmi_trk* h) {
     h->submit.stop();
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->own_copy_stream) (void)hipStreamSynchronize(h->own_copy_stream);
     if (h->epi_stream) (void)hipStreamSynchronize(h->epi_stream);
     if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
     if (h->alt_stream) (void)hipStreamSynchronize(h->alt_stream);
@@ -794,35 +818,33 @@ int gpsmi_trk_destroy(gpsmi_trk* h) {
 }
 
 int gpsmi_trk_set_replica(gpsmi_trk* h, int prn, const float* replica, const float* spectrum) {
-    GPSMI_REQUIRE(h && replica && (spectrum || h->general), "null argument");
+    GPSMI_REQUIRE(h && replica && (spectrum || h->long_code()), "null argument");
     GPSMI_REQUIRE(prn >= 1 && prn <= GPSMI_MAX_PRN, "prn out of range 1..37");
     GPSMI_QUIESCE(h);
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     const size_t cs = h->cfg.code_samples;
     GPSMI_HIP(hipMemcpy(h->d_code.p + (size_t)prn * cs, replica, cs * sizeof(float),
                         hipMemcpyHostToDevice));
-    if (h->mfma) {
+    if (h->correlator == Correlator::Span) {
         std::vector<float> eo(2 * kFftN);          // plane e of four, entry h = replica[(4 h + e) mod 2048], 1024 entries
         for (int e = 0; e < 4; ++e)
             for (int i = 0; i < kFftN / 2; ++i) eo[e * (kFftN / 2) + i] = replica[(4 * i + e) % kFftN];
         GPSMI_HIP(hipMemcpy(h->d_code_eo.p + (size_t)prn * 2 * kFftN, eo.data(), eo.size() * sizeof(float),
                             hipMemcpyHostToDevice));
     }
-    if (h->span8) {                        // plane e, entry s = replica[2 (s mod cs / 2) + e], each plane twice
+    if (h->correlator == Correlator::Span8) {   // plane e, entry s = replica[2 (s mod cs / 2) + e], each plane twice
         std::vector<float> eo(2 * cs);
         for (int e = 0; e < 2; ++e)
             for (size_t i = 0; i < cs; ++i) eo[e * cs + i] = replica[2 * (i % (cs / 2)) + e];
         GPSMI_HIP(hipMemcpy(h->d_code_eo.p + (size_t)prn * 2 * cs, eo.data(), eo.size() * sizeof(float),
                             hipMemcpyHostToDevice));
     }
-    if (!h->general)                       // the other path needs no 2048-point spectrum
+    if (h->long_code()) {                  // (this path needs no 2048-point spectrum)
+        const int rc = h->lc.set_replica(h->stream, h->d_code.p, prn, h->d_tw.p);
+        if (rc) return rc;
+    } else {
         GPSMI_HIP(hipMemcpy(h->d_rep.p + (size_t)prn * kFftN, spectrum, kFftN * sizeof(float2),
                             hipMemcpyHostToDevice));
-    if (h->big) big_replica_launch(h->stream, h->d_code.p, prn, (int)cs, h->d_RS.p, h->d_tw.p, h->d_twN.p);
-    if (h->pfa) pfa_replica_launch(h->stream, h->d_code.p, prn, h->d_RSp.p);
-    if (h->big || h->pfa) {
-        GPSMI_HIP(hipGetLastError());
-        GPSMI_HIP(hipStreamSynchronize(h->stream));
     }
     h->have_rep[prn] = true;
     return GPSMI_OK;
@@ -996,17 +1018,12 @@ static int trk_stream_step(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out
     // 50 against 58 us for eight; equal at 64).  Beyond that it goes up on the upload stream under the
     // previous step's kernels, as soon as the kernels that read this staging block two calls ago have
     // finished.  Either way the host never waits.
-    // Small steps need no staging at all: the tracking kernels read the page-locked block over PCIe where it
-    // lies (each sample is read once by the correlator and one row of it by the code-phase correlation), which
-    // takes the copy kernel, its launch and the kernel boundary behind it out of the step.  The block
-    // stays the caller's until the step is complete, as the contract of gpsmi.h says anyway.
-    const bool direct_in = pinned && bytes <= h->stream_direct_max;
-    const bool in_line = pinned && (direct_in || bytes <= h->stream_inline_max);
+    // (Letting the tracking kernels read the page-locked block where it lies, with no staging at all,
+    // measured slower: DESIGN.md 8.)
+    const bool in_line = pinned && bytes <= h->stream_inline_max;
     hipStream_t us = in_line ? h->stream : h->up_stream;
     if (!in_line && h->stage_used[s]) GPSMI_HIP(hipStreamWaitEvent(h->up_stream, h->stage_free[s], 0));
-    if (direct_in) {
-        // (nothing to move)
-    } else if (pinned) {
+    if (pinned) {
         const size_t n16 = bytes / 16;
         const unsigned grid = (unsigned)((n16 + 255) / 256 < 512 ? (n16 + 255) / 256 : 512);
         hipLaunchKernelGGL(stage_copy_kernel, dim3(grid), dim3(256), 0, us,
@@ -1029,7 +1046,7 @@ static int trk_stream_step(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out
     // queued behind that kernel (no record copy, no upload-stream bookkeeping)
     const bool want_tail = in_line && (!out || out_direct);
     bool tail_used = false;
-    rc = trk_launch(h, sl, direct_in ? iq_dev : h->d_stage[s].p, h->d_state.p, h->d_state.p, nullptr, h->rows(), h->max_ch,
+    rc = trk_launch(h, sl, h->d_stage[s].p, h->d_state.p, h->d_state.p, nullptr, h->rows(), h->max_ch,
                     /*side_epilogue=*/false, want_tail ? h->in_done[s].h : nullptr, &tail_used);
     sl.d_out.p = d_out_keep;
     h->timing = timing;
@@ -1064,7 +1081,7 @@ int gpsmi_trk_process_stream(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_o
     }
     // the contract of gpsmi.h: return once the step of the call before last is complete -- the
     // submission thread says so when it has waited for that step on its way into this one
-    // ("stream_depth" = 3: one step more -- the call returns when the step three calls back is
+    // (stream_depth = 3: one step more -- the call returns when the step three calls back is
     // complete, so the caller can hand over its next block while this one is still being enqueued)
     char report[SubmitQueue::kReport];
     const int rc = h->submit.submit({iq, n, out}, h->stream_depth, report);
@@ -1119,7 +1136,7 @@ int gpsmi_trk_replay_run_async(gpsmi_trk* h, const void* d_iq, int nb) {
     const int nch = h->max_ch;
     h->cur ^= 1;                           // the other slot may still be on its way to the host
     gpsmi_trk::Slot& sl = h->slot[h->cur];
-    // "corr_overlap": consecutive runs are independent (two result slots), so they alternate between
+    // corr_overlap: consecutive runs are independent (two result slots), so they alternate between
     // two streams: the code-phase correlation of run k + 1 is then eligible while the correlator of
     // run k still runs, and the chip is never left to one kernel's tail.  Every kernel then shares
     // CUs with another one: throughput mode; the default keeps each kernel alone (its duration is
@@ -1143,8 +1160,7 @@ int gpsmi_trk_replay_run_async(gpsmi_trk* h, const void* d_iq, int nb) {
         sl.epi_pending = false;
     }
     // (mode 2 needs the batch form of the span correlator: its dispatch carries the stamps)
-    sl.timing_pending = (h->timing == 2 && !(h->mfma == 4 && nb * ((nch + kSpCh - 1) / kSpCh) > h->span_single_max))
-                            ? 0 : h->timing;
+    sl.timing_pending = (h->timing == 2 && !trk_geometry(h, nb * nch, nch).span_batch) ? 0 : h->timing;
     return trk_launch(h, sl, d_iq, h->d_tab_in.p, h->d_tab_out.p,
                       h->replay_forced ? h->d_forced.p : nullptr, nb * nch, nch, /*side_epilogue=*/true);
 }
@@ -1203,14 +1219,14 @@ int gpsmi_trk_replay_fetch_async(gpsmi_trk* h, gpsmi_trk_out* out, size_t n) {
     // the copy runs on its own stream behind the run that produced the records, so the
     // next run (other slot) overlaps it
     if (sl.epi_pending) {                  // the records are complete when the slot's epilogue is
-        GPSMI_HIP(hipStreamWaitEvent(h->copy_stream, sl.epi_done, 0));
+        GPSMI_HIP(hipStreamWaitEvent(h->epi_stream, sl.epi_done, 0));
     } else {
         GPSMI_HIP(hipEventRecord(sl.ready, sl.run_stream ? sl.run_stream : h->stream));
-        GPSMI_HIP(hipStreamWaitEvent(h->copy_stream, sl.ready, 0));
+        GPSMI_HIP(hipStreamWaitEvent(h->epi_stream, sl.ready, 0));
     }
     GPSMI_HIP(hipMemcpyAsync(out, sl.d_out.p, n * sizeof(gpsmi_trk_out), hipMemcpyDeviceToHost,
-                             h->copy_stream));
-    GPSMI_HIP(hipEventRecord(sl.copied, h->copy_stream));
+                             h->epi_stream));
+    GPSMI_HIP(hipEventRecord(sl.copied, h->epi_stream));
     sl.copy_pending = true;
     return GPSMI_OK;
 }
@@ -1271,7 +1287,7 @@ int gpsmi_trk_set_input_format(gpsmi_trk* h, int fmt) {
     GPSMI_REQUIRE(h, "null handle");
     GPSMI_QUIESCE(h);
     GPSMI_REQUIRE(fmt == GPSMI_IQ_C64 || fmt == GPSMI_IQ_U8, "unknown input format");
-    if (fmt == GPSMI_IQ_U8 && h->mfma != 4)
+    if (fmt == GPSMI_IQ_U8 && !h->takes_raw_u8())
         return fail(GPSMI_E_UNSUPPORTED, "raw u8 IQ input needs CODE_SAMPLES = 2048 and the span "
                                          "correlator (option \"correlator\" = 1)");
     h->iq_fmt = fmt;
@@ -1308,83 +1324,20 @@ int gpsmi_trk_set_streams(gpsmi_trk* h, int n_streams) {
 int gpsmi_trk_set_option(gpsmi_trk* h, const char* key, long long value) {
     GPSMI_REQUIRE(h && key, "null argument");
     GPSMI_QUIESCE(h);
-    const auto bad = [&]() { return fail(GPSMI_E_ARG, "gpsmi_trk_set_option: %s = %lld out of range", key, value); };
-    if (!strcmp(key, "corr_cg")) {
-        if (value != 2 && value != 4 && value != 6) return bad();
-        h->corr_cg = (int)value;
-    } else if (!strcmp(key, "corr_small1")) {
-        if (value < 0 || value > h->corr_small2) return bad();
-        h->corr_small1 = (int)value;
-    } else if (!strcmp(key, "corr_small2")) {
-        if (value < h->corr_small1 || value > (1 << 24)) return bad();
-        h->corr_small2 = (int)value;
-    } else if (!strcmp(key, "span_single_max")) {
-        if (value < 1 || value > kSpanUnitsMax) return bad();
-        h->span_single_max = (int)value;
-    } else if (!strcmp(key, "stream_inline_max")) {
-        if (value < 0) return bad();
-        h->stream_inline_max = (size_t)value;
-    } else if (!strcmp(key, "stream_direct_max")) {
-        if (value < 0) return bad();
-        h->stream_direct_max = (size_t)value;
-    } else if (!strcmp(key, "done_by_dispatch")) {
-        h->done_by_dispatch = value != 0;
-    } else if (!strcmp(key, "corr_overlap")) {
-        // The general path (CODE_SAMPLES != 2048) keeps its fold / pfa_corr / stats scratch once per
-        // handle, not per result slot: two batches in flight on two streams would overwrite each
-        // other's intermediates.
-        if (value != 0 && h->general)
-            return fail(GPSMI_E_STATE, "gpsmi_trk_set_option: corr_overlap needs CODE_SAMPLES = %d "
-                        "(the general path's scratch is per handle)", kFftN);
-        h->corr_overlap = value != 0;
-    } else if (!strcmp(key, "fold_chunk")) {
-        if (value < 0 || value > (1 << 20)) return bad();
-        h->fold_chunk = (int)value;
-    } else if (!strcmp(key, "epilogue_form")) {
-        if (value != 0 && value != 1) return bad();
-        h->epilogue_form = (int)value;
-    } else if (!strcmp(key, "stream_thread")) {
-        h->stream_thread = value != 0;
-    } else if (!strcmp(key, "stream_depth")) {
-        if (value < 2 || value > 64) return bad();
-        h->stream_depth = (int)value;
-    } else if (!strcmp(key, "correlator") || !strcmp(key, "codephase") || !strcmp(key, "debug_flags") ||
-               !strcmp(key, "copy_stream")) {
+    const TrkOpt* o = trk_find_opt(key);
+    if (!o || o->kind == OptKind::Stat) return fail(GPSMI_E_ARG, "gpsmi_trk_set_option: unknown option '%s'", key);
+    if (o->kind == OptKind::Create)
         return fail(GPSMI_E_STATE, "gpsmi_trk_set_option: '%s' is taken at create time (gpsmi_set_default)", key);
-    } else {
-        return fail(GPSMI_E_ARG, "gpsmi_trk_set_option: unknown option '%s'", key);
-    }
-    return GPSMI_OK;
+    const int rc = o->set(h, value);
+    return rc == GPSMI_E_ARG ? fail(rc, "gpsmi_trk_set_option: %s = %lld out of range", key, value) : rc;
 }
 
 int gpsmi_trk_get_option(gpsmi_trk* h, const char* key, long long* value) {
     GPSMI_REQUIRE(h && key && value, "null argument");
     GPSMI_QUIESCE(h);
-    if (!strcmp(key, "corr_cg")) *value = h->corr_cg;
-    else if (!strcmp(key, "corr_small1")) *value = h->corr_small1;
-    else if (!strcmp(key, "corr_small2")) *value = h->corr_small2;
-    else if (!strcmp(key, "span_single_max")) *value = h->span_single_max;
-    else if (!strcmp(key, "stream_inline_max")) *value = (long long)h->stream_inline_max;
-    else if (!strcmp(key, "stream_direct_max")) *value = (long long)h->stream_direct_max;
-    else if (!strcmp(key, "done_by_dispatch")) *value = h->done_by_dispatch;
-    else if (!strcmp(key, "corr_overlap")) *value = h->corr_overlap;
-    else if (!strcmp(key, "fold_chunk")) *value = h->fold_chunk;
-    else if (!strcmp(key, "epilogue_form")) *value = h->epilogue_form;
-    else if (!strcmp(key, "stream_thread")) *value = h->stream_thread;
-    else if (!strcmp(key, "stream_depth")) *value = h->stream_depth;
-    else if (!strcmp(key, "stat_stream_steps")) *value = h->stat_steps;
-    else if (!strcmp(key, "stat_waits")) *value = h->stat_waits;
-    else if (!strcmp(key, "stat_backlog")) *value = h->stat_backlog;
-
-    else if (!strcmp(key, "stat_quiesce_ns")) *value = h->stat_quiesce_ns;
-    else if (!strcmp(key, "stat_evwait_ns")) *value = h->stat_evwait_ns;
-    else if (!strcmp(key, "stat_stream_wait_ns")) *value = h->stat_wait_ns;
-    else if (!strcmp(key, "stat_stream_launch_ns")) *value = h->stat_launch_ns;
-    else if (!strcmp(key, "correlator")) *value = (h->mfma == 4 || h->span8) ? 1 : 0;     // what runs, not what was asked
-    else if (!strcmp(key, "codephase")) *value = h->general ? (h->pfa ? 0 : (h->big ? 2 : 1)) : 0;
-    else if (!strcmp(key, "debug_flags")) *value = h->P.flags;
-    else if (!strcmp(key, "copy_stream")) *value = h->own_copy_stream.h ? 1 : 0;
-    else return fail(GPSMI_E_ARG, "gpsmi_trk_get_option: unknown option '%s'", key);
+    const TrkOpt* o = trk_find_opt(key);
+    if (!o) return fail(GPSMI_E_ARG, "gpsmi_trk_get_option: unknown option '%s'", key);
+    *value = o->get(h);
     return GPSMI_OK;
 }
 

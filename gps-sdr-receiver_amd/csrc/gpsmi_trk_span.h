@@ -1,7 +1,7 @@
 // The tracking correlator, span form (default for CS = 2048; N_CYC = 32, and -- round 4 -- 16 and 8:
 // template parameter NC, one M tile of 16 rows instead of two, see "Other block lengths" below).
 //
-// Same mathematics as gpsmi_trk_stream_mfma.h -- prompt correlate-and-dump of a 32-ms
+// Same mathematics as the retired tools/probe/round1_stream_mfma.h -- prompt correlate-and-dump of a 32-ms
 // block, y = roll(replica, delay) * (data * exp(-j(phase + 2 pi f t))) summed per
 // code-period window (reference src/gpslib.py:1400-1420) -- re-cut so that
 //   (1) every load instruction reads 512 consecutive bytes of a row (tiles of 32 rows x 64

@@ -80,11 +80,8 @@ int gpsmi_abi_sizeof(int which);
  *   "codephase"         code_samples != 2048 only: 0 (default) native 16368-point LDS correlation
  *                       / zero-padded 32768-point pair, 1 the exact time-domain kernel, 2 the
  *                       32768-point pair at 16368 too (env GPSMI_DIRECT_CORR)
- *   "copy_stream"       0 (default): the read-back of a replay run (gpsmi_trk_replay_fetch_async) goes to
- *                       the stream of the run's epilogue, which it follows anyway; 1: to a stream of
- *                       its own.  The HIP runtime maps streams onto four hardware queues; with the
- *                       compute and epilogue streams of this handle, an acquisition handle's stream
- *                       and the null stream a process has four (env GPSMI_COPY_STREAM)
+ *   "debug_flags"       diagnostics builds only (make diag): the ablation switches of the tuning tools
+ *                       (env GPSMI_DEBUG_FLAGS); the shipped library stores and ignores them
  * keys a live tracking handle accepts as well (see DESIGN.md for the measurements behind them):
  *   "corr_cg"           channels per code-phase-correlation workgroup in batches: 2, 4 (default), 6
  *   "corr_small1/2"     jobs per launch up to which 1 / 2 channels per workgroup are taken (384, 1536;
@@ -96,8 +93,6 @@ int gpsmi_abi_sizeof(int which);
  *                       per span (80)
  *   "stream_inline_max" bytes up to which gpsmi_trk_process_stream uploads in front of the step's
  *                       own kernels (8 MiB)
- *   "stream_direct_max" bytes up to which the kernels of a streamed step read a page-locked block
- *                       where it lies instead of a staged copy (0: never -- measured slower)
  *   "done_by_dispatch"  1 (default): a replay's epilogue waits on the correlator dispatch's own
  *                       completion signal; 0: on an event record behind it
  *   "epilogue_form"     1 (default): the batch epilogue takes eight lanes per (block, channel) job
@@ -109,6 +104,9 @@ int gpsmi_abi_sizeof(int which);
  *                       CODE_SAMPLES = 2048 only: a handle of the general path keeps its
  *                       correlation scratch once per handle, refuses 1 with GPSMI_E_STATE and
  *                       ignores a default of 1 (the option reads 0)
+ *   "fold_chunk"        CODE_SAMPLES = 16368: blocks per fold -> correlation piece of a batch, so that the
+ *                       folded samples stay in the memory-side cache (0, the default: the whole launch
+ *                       at once; 0 .. 2^20)
  *   "stream_thread"     1 (default): the launches of a gpsmi_trk_process_stream step are made by a
  *                       submission thread of the handle while the caller prepares its next block
  *                       (they cost as much host time as the step takes on the GPU); 0: by the caller

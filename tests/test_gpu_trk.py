@@ -5,6 +5,8 @@ Bars (SURVEY.md 8c): argmax / DELAY / dump count / carry length bit-exact;
 prompt dumps rtol 1e-3 + atol 1e-5; the three correlator taps around the peak
 rtol 1e-3; codePhase atol 2e-3 samples; FREQ atol 0.05 Hz; lock flag equal
 after the same number of blocks."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -713,6 +715,124 @@ def test_corr_overlap_is_refused_where_scratch_is_per_handle():
     assert ok.get_option('corr_overlap') == 1
     hr.close()
     ok.close()
+
+
+# The options gpsmi.h documents.  Live keys: (built-in default, a valid other value, values outside the
+# documented range).  The flags take any non-zero value as 1 and have no range.
+LIVE_OPTIONS = {
+    'corr_cg': (4, 6, [3, 0, 8, -2]),
+    'corr_small1': (384, 100, [-1, 1537]),                       # (1537: above corr_small2)
+    'corr_small2': (1536, 4000, [383, (1 << 24) + 1]),           # (383: below corr_small1)
+    'span_single_max': (80, 17, [0, 257]),
+    'stream_inline_max': (8 << 20, 4096, [-1]),
+    'epilogue_form': (1, 0, [2, -1]),
+    'fold_chunk': (0, 3, [-1, (1 << 20) + 1]),
+    'stream_depth': (2, 3, [1, 65]),
+}
+FLAG_OPTIONS = {'done_by_dispatch': 1, 'corr_overlap': 0, 'stream_thread': 1}
+CREATE_OPTIONS = ('correlator', 'codephase', 'debug_flags')
+STAT_OPTIONS = ('stat_stream_steps', 'stat_waits', 'stat_backlog', 'stat_quiesce_ns', 'stat_evwait_ns',
+                'stat_stream_wait_ns', 'stat_stream_launch_ns')
+REMOVED_OPTIONS = ('stream_direct_max', 'copy_stream')
+E_ARG, E_STATE = -1, -3
+
+
+def test_every_documented_option_through_the_abi():
+    """Every option of gpsmi.h on a live handle and as a process-wide default, no kernel launched:
+    round trips, refusals that leave the stored value alone and name the key, the corr_small
+    ordering rule both ways, create-time and stat_* keys, the two removed keys, and defaults --
+    a valid one reaches the next handle, an invalid one leaves the built-in value and the
+    caller's last error text."""
+    from gpsmi import _lib
+    from gpsmi import engine as E
+    from gpsmi.engine import Config, TrkEngine
+    lib = _lib.load()
+
+    def fresh(**cfg):
+        return TrkEngine(Config(**cfg), max_ch=1, prns=())
+
+    def set_rc(eng, key, v):
+        return lib.gpsmi_trk_set_option(eng.h, key.encode(), v)
+
+    def refused(eng, key, v, code):
+        before = eng.get_option(key) if key not in REMOVED_OPTIONS else None
+        assert set_rc(eng, key, v) == code, (key, v)
+        assert key.encode() in lib.gpsmi_last_error(), (key, v)
+        if before is not None:
+            assert eng.get_option(key) == before, (key, v)
+
+    eng = fresh(n_cyc=32)
+    for key, (builtin, other, bad) in LIVE_OPTIONS.items():
+        assert eng.get_option(key) == builtin, key
+        for v in bad:
+            refused(eng, key, v, E_ARG)
+    for key, (builtin, other, bad) in LIVE_OPTIONS.items():          # (corr_small2 up before corr_small1 ...)
+        if key != 'corr_small1':
+            eng.set_option(key, other)
+            assert eng.get_option(key) == other, key
+    eng.set_option('corr_small1', 100)
+    assert (eng.get_option('corr_small1'), eng.get_option('corr_small2')) == (100, 4000)
+    refused(eng, 'corr_small1', 4001, E_ARG)                         # the ordering rule, both directions
+    refused(eng, 'corr_small2', 99, E_ARG)
+    eng.set_option('corr_small2', 100)
+    eng.set_option('corr_small1', 0)
+    eng.set_option('corr_small2', 0)
+    assert (eng.get_option('corr_small1'), eng.get_option('corr_small2')) == (0, 0)
+    for key, builtin in FLAG_OPTIONS.items():
+        assert eng.get_option(key) == builtin, key
+        eng.set_option(key, 1 - builtin)
+        assert eng.get_option(key) == 1 - builtin, key
+        eng.set_option(key, 0)
+        eng.set_option(key, 7)                                       # any non-zero value turns it on
+        assert eng.get_option(key) == 1, key
+    for key in CREATE_OPTIONS:
+        assert eng.get_option(key) == (1 if key == 'correlator' else 0), key
+        refused(eng, key, 0, E_STATE)
+    for key in STAT_OPTIONS:
+        assert eng.get_option(key) == 0, key                         # (a handle that has run nothing)
+        refused(eng, key, 1, E_ARG)
+    v = C.c_longlong(0)
+    for key in REMOVED_OPTIONS:
+        refused(eng, key, 0, E_ARG)
+        assert lib.gpsmi_trk_get_option(eng.h, key.encode(), C.byref(v)) == E_ARG
+        assert lib.gpsmi_set_default(key.encode(), 0) == E_ARG
+        assert lib.gpsmi_clear_default(key.encode()) == E_ARG
+    eng.close()
+
+    hr = fresh(code_samples=16368, n_cyc=8)                          # scratch per handle: no corr_overlap
+    assert (hr.get_option('correlator'), hr.get_option('codephase')) == (1, 0)
+    refused(hr, 'corr_overlap', 1, E_STATE)
+    hr.set_option('corr_overlap', 0)
+    hr.close()
+
+    # defaults: valid ones reach the next handle (the corr_small pair together, whatever the order) ...
+    want = {k: other for k, (_, other, _) in LIVE_OPTIONS.items()}
+    want.update({k: 1 - b for k, b in FLAG_OPTIONS.items()})
+    try:
+        for key, val in want.items():
+            E.set_default(key, val)
+        eng = fresh(n_cyc=32)
+    finally:
+        for key in want:
+            E.clear_default(key)
+    assert {k: eng.get_option(k) for k in want} == want
+    eng.close()
+    # ... invalid ones leave the built-in value and the caller's last error text
+    bad_defaults = {k: bad[0] for k, (_, _, bad) in LIVE_OPTIONS.items()}
+    bad_defaults.update(corr_small1=500, corr_small2=100)            # each in range, the pair out of order
+    try:
+        for key, val in bad_defaults.items():
+            E.set_default(key, val)
+        assert lib.gpsmi_set_default(b'no_such_option', 1) == E_ARG  # a known last error first
+        before = lib.gpsmi_last_error()
+        assert b'no_such_option' in before
+        eng = fresh(n_cyc=32)
+        assert lib.gpsmi_last_error() == before
+    finally:
+        for key in bad_defaults:
+            E.clear_default(key)
+    assert {k: eng.get_option(k) for k in LIVE_OPTIONS} == {k: b for k, (b, _, _) in LIVE_OPTIONS.items()}
+    eng.close()
 
 
 def test_search_ordered_behind_replay_batches(closed_loop):
