@@ -218,14 +218,23 @@ def make_udp_socket():
     return socket.socket(socket.AF_INET, socket.SOCK_DGRAM)
 
 
-def largest_peak_hits(acq, data, prns, freqs, n_coh=4, n_seg=250, f_offset=0.0):
+def largest_peak_hits(acq, data, prns, freqs, n_coh=4, n_seg=250, f_offset=0.0, corr_min=None):
     """Deep-search hits ``(normMaxCorr, satNo, freq, delay)`` of satellites known to be there, one
     per PRN at the bin of its largest peak.  (sweepDeepSats' first bin over the threshold is a
-    sidelobe for a strong satellite, and its own sidelobes raise the std normMaxCorr divides by.)"""
+    sidelobe for a strong satellite, and its own sidelobes raise the std normMaxCorr divides by.)
+    `corr_min`: for satellites that may be absent or weak -- only the bins whose normMaxCorr
+    exceeds it compete, and a PRN without such a bin has no hit.  (Beside strong satellites the
+    largest peak of a weak PRN is a strong one's cross-correlation in another bin, on a surface
+    those raise as a whole: a peak normMaxCorr does not take for a detection.)"""
     tab = acq.engine.search_deep(data, list(prns), list(freqs), n_coh, n_seg, f_offset=f_offset)
-    best = tab['peak'].argmax(axis=0)
     nmc = (tab['peak'].astype(np.float64) - tab['mean']) / tab['std']
-    return [(float(nmc[b, j]), s, freqs[b], int(tab[b, j]['argmax'])) for j, (s, b) in enumerate(zip(prns, best))]
+    if corr_min is None:
+        best = tab['peak'].argmax(axis=0)
+        return [(float(nmc[b, j]), s, freqs[b], int(tab[b, j]['argmax'])) for j, (s, b) in enumerate(zip(prns, best))]
+    over = nmc > corr_min
+    best = np.where(over, tab['peak'], -np.inf).argmax(axis=0)
+    return [(float(nmc[b, j]), s, freqs[b], int(tab[b, j]['argmax']))
+            for j, (s, b) in enumerate(zip(prns, best)) if over[b, j]]
 
 
 def refine_centred(acq, data, found, f_offset=0.0):
@@ -250,6 +259,20 @@ def refine_centred(acq, data, found, f_offset=0.0):
         rec[bad] = acq.refineHits(data, [found[i] for i in bad], f_offset=f_offset)
         ms += acq.engine.last_ms()
     return found, rec, ms
+
+
+GHOST_HZ, GHOST_DB = 5.0, 10.0
+
+
+def ghosts_of(strong, refined, hz=GHOST_HZ, db=GHOST_DB):
+    """Which records of `refined` are the satellite of the refinement record `strong` seen through
+    another PRN's code: within `hz` of it modulo the code's 1-kHz line spacing
+    and not reading within `db` of it (a record without a C/N0 does not).  A `strong` that is not
+    confirmed or has no C/N0 has no ghosts.  -> bool per record."""
+    if strong['confirmed'] != 1 or np.isnan(strong['cn0_dbhz']):
+        return np.zeros(len(refined), bool)
+    d = np.abs((refined['f_hz'] - strong['f_hz'] + 500.0) % 1000.0 - 500.0)
+    return (d <= hz) & ~(refined['cn0_dbhz'] > strong['cn0_dbhz'] - db)
 
 
 class WeakTracker:
@@ -410,7 +433,7 @@ class WeakAssist:
         step = self.chunk_blocks * c.ngps
         self._track([whole[i:i + step] for i in range(0, len(whole), step)])
 
-    GHOST_HZ, GHOST_DB = 5.0, 10.0
+    GHOST_HZ, GHOST_DB = GHOST_HZ, GHOST_DB
 
     def _ghosts(self, whole, freqs, f_off):
         """Which refined hits are the receiver's own satellites seen through another PRN's code:
@@ -433,10 +456,7 @@ class WeakAssist:
         _, self.own_refined, ms = refine_centred(acq, whole, hits, f_offset=f_off)
         self.search_ms += ms
         for o in self.own_refined:
-            if o['confirmed'] != 1 or np.isnan(o['cn0_dbhz']):
-                continue
-            d = np.abs((self.refined['f_hz'] - o['f_hz'] + 500.0) % 1000.0 - 500.0)
-            out |= (d <= self.GHOST_HZ) & ~(self.refined['cn0_dbhz'] > o['cn0_dbhz'] - self.GHOST_DB)
+            out |= ghosts_of(o, self.refined, self.GHOST_HZ, self.GHOST_DB)
         return out
 
     def _track(self, chunks):

@@ -1,0 +1,421 @@
+"""Snapshot fix: a position from a fraction of a second of signal, stored ephemerides and a rough
+idea of time and place -- no decoded subframe.
+
+``measure`` runs the stages the weak path already has on one uploaded snapshot (deep search ->
+refinement -> optionally bit-synchronous tracking, all on the GPU) and returns per satellite a
+code phase that is ambiguous by one code period, a Doppler and C/N0.  ``coarse_time_fix`` is the
+navigation step that works without decoded time: Gauss-Newton over ECEF position, a
+sub-millisecond clock bias and the coarse time, with the whole milliseconds of every satellite
+derived from the a-priori position and time relative to the strongest satellite.
+``doppler_fix`` makes an a-priori position from the Dopplers alone when the caller has none, and
+``snapshot_fix`` chains the three.  Everything in this module but the three engine calls inside
+``measure`` is host float64 numpy.
+
+Contract of ``coarse_time_fix``: the a-priori position within 50 km and the time within 30 s, or
+the position within 75 km at the right time, or the time within 90 s at the right position (the
+a-priori range errors of any two satellites must differ by less than half of c * 1 ms =
+149.9 km: 2 |position error| + 1.6 km/s |time error| < 150 km).  No atmosphere model, as in
+position.least_squares_pos4; the ephemerides must be the set valid at that time.  Five satellites
+leave no redundancy: the fix is then only as good as the a-priori, and is refused when it ends
+outside the region around it.  Six leave one degree of freedom: a solution that fails the
+residual test is refused; one bad satellite is dropped only from seven on.  Every fix carries
+`protect_m`, the position error one bad measurement could cause without failing the test.
+"""
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import position as P
+
+L1_HZ = 1575.42e6
+C_MS = P.GPS_C * 1.0e-3                  # metres of one code period
+MIN_SAT = 5
+FREEZE_AFTER = 3                         # iterations that re-derive the millisecond integers
+MAX_IT = 12
+STEP_TOL = 1.0e-4                        # metres: the Gauss-Newton step that ends the iteration
+RMS_MAX_SAMPLES = 1.0                    # post-fit residual rms a fix may have, in samples
+REGION_M, REGION_M_PER_S = 150.0e3, 1.6e3
+TRACK_MIN_SECONDS, TRACK_MIN_BITS = 0.5, 4
+EDGE_MIN_BITS = 10                       # bits refinement must span for `edge` (no transition in them: 2^-9)
+DEFAULT_SOURCE = 'track'                 # where it applies; the comparison is in DESIGN.md 4.2i
+
+# prn; sample: the stream index the code phase refers to; code_phase: samples in [0, cs), a code
+# start lies at sample + code_phase modulo cs; f_hz: as of the middle of the data; cn0_dbhz:
+# refinement's; edge: the stream position of a bit edge ('track': the code start itself; NaN when
+# refinement spanned fewer than EDGE_MIN_BITS bits), recorded and not used yet; source: b'refine' or b'track'
+MEAS_DTYPE = np.dtype([('prn', np.int32), ('sample', np.int64), ('code_phase', np.float64),
+                       ('f_hz', np.float64), ('cn0_dbhz', np.float64), ('edge', np.float64),
+                       ('source', 'S6')])
+
+
+# ---------------------------------------------------------------- the range model
+def modelled_range(eph, t_rx, pos, rounds=3):
+    """c * (reception time - satellite clock reading at transmission) of a signal received at GPS
+    time `t_rx` at ECEF `pos`: the geometric range with the receiver displaced by the Earth's
+    rotation during the flight (position.sagnac_shift) minus c * the satellite clock correction.
+    The transmit time is a fixed point: the first round leaves 12 m of range at the most, the
+    second 0.2 mm, the third nothing a float64 holds.
+    -> (range in m, unit vector from the satellite to the receiver)."""
+    pos = np.asarray(pos, dtype=np.float64)
+    v = np.array([-pos[1], pos[0], 0.0]) * P.OMEGA_EARTH
+    tau, dt_sv = 0.072, 0.0
+    for _ in range(rounds):
+        x, y, z, dt_sv = P.sat_ecef(1, eph, DT=t_rx - tau + dt_sv)
+        d = np.array([x, y, z]) - pos - v * tau
+        tau = np.sqrt(d.dot(d)) / P.GPS_C
+    rho = tau * P.GPS_C
+    return rho - P.GPS_C * dt_sv, -d / rho
+
+
+def _rates(ephs, prns, t_rx, pos, rate_dt=0.5):
+    """Range rates: the central difference of the modelled range over +-rate_dt (two rounds of
+    the fixed point: 0.2 mm over a second is far below what a rate is used for here)."""
+    return np.array([(modelled_range(ephs[int(prn)], t + rate_dt, pos, 2)[0]
+                      - modelled_range(ephs[int(prn)], t - rate_dt, pos, 2)[0]) / (2.0 * rate_dt)
+                     for prn, t in zip(prns, t_rx)])
+
+
+def _model(ephs, prns, t_rx, pos):
+    """Modelled ranges, unit vectors and range rates of `prns` at the reception times `t_rx`."""
+    n = len(prns)
+    f, e = np.empty(n), np.empty((n, 3))
+    for i, prn in enumerate(prns):
+        f[i], e[i] = modelled_range(ephs[int(prn)], t_rx[i], pos)
+    return f, e, _rates(ephs, prns, t_rx, pos)
+
+
+def cn0_weights(cn0_dbhz):
+    """Weights of the code phases: proportional to C/N0 (the variance of a code-phase estimate
+    falls with it), the strongest 1; a satellite without a reading counts as the weakest."""
+    cn0 = np.asarray(cn0_dbhz, dtype=np.float64)
+    if not np.isfinite(cn0).any():
+        return np.ones(len(cn0))
+    cn0 = np.where(np.isfinite(cn0), cn0, np.nanmin(cn0))
+    return 10.0 ** ((cn0 - cn0.max()) / 10.0)
+
+
+@dataclass
+class Fix:
+    ok: bool = False
+    reason: str = ''
+    ecef: object = None                  # ECEF metres, None unless ok
+    t_gps: float = None                  # GPS seconds of week of stream index `sample`
+    sample: int = 0
+    bias_m: float = 0.0                  # the clock bias, within half a code period
+    prns: list = field(default_factory=list)        # the satellites of the solution
+    residuals: object = None             # metres, per satellite of `prns`
+    integers: object = None              # whole milliseconds relative to `ref_prn`
+    ref_prn: int = 0
+    dropped: list = field(default_factory=list)     # what the residual test took out
+    g: float = float('nan')              # sqrt tr of the position block of inv(H' H)
+    rms_m: float = float('nan')           # weighted rms of the residuals
+    test_m: float = float('nan')          # ... per degree of freedom: rms * sqrt(n / (n - 5)), what is tested
+    protect_m: float = float('inf')       # the position error one bad measurement can cause and pass the test
+    moved_m: float = float('nan')   # 2 |position change| + 1.6 km/s |time change| from the a-priori
+    iterations: int = 0
+    tau: object = None                    # tested figure per metre of bias on each satellite
+    slope: object = None                  # position error per unit of the tested figure, per satellite
+
+
+def _solve(prns, samples, phases, w, ephs, clock, pos0, fs):
+    """Gauss-Newton over (position, bias, coarse time) for one set of satellites.  clock =
+    (stream index, a-priori GPS time of it); the solution's time is that of the strongest
+    satellite's `sample`."""
+    ref = int(np.argmax(w))
+    sample = int(samples[ref])
+    t0 = clock[1] + (sample - clock[0]) / fs
+    d = ((samples - sample) + phases) / fs           # seconds from `sample` to each code start
+    # the code phases as fractional pseudoranges: where the millisecond grid lies is the a-priori
+    # time's choice, which the bias absorbs (the fraction is taken first: t0 + d would round)
+    z = P.GPS_C * np.mod(np.mod(t0, 1.0e-3) + d, 1.0e-3)
+    pos, bias, dt = np.array(pos0, dtype=np.float64), 0.0, 0.0
+    N = np.zeros(len(prns))
+    fix = Fix(sample=sample, prns=[int(p) for p in prns], ref_prn=int(prns[ref]))
+    sw = np.sqrt(w)
+    for it in range(MAX_IT):
+        f, e, fd = _model(ephs, prns, t0 + dt + d, pos)
+        r = z - f
+        if it < FREEZE_AFTER:
+            N = np.rint((r - r[ref]) / C_MS)
+            if it == 0:
+                bias = r[ref]
+        y = r - N * C_MS - bias
+        H = np.column_stack([e, np.ones(len(prns)), fd])
+        step = np.linalg.lstsq(H * sw[:, None], y * sw, rcond=None)[0]
+        pos, bias, dt = pos + step[:3], bias + step[3], dt + step[4]
+        fix.iterations = it + 1
+        if not np.all(np.isfinite(step)) or np.linalg.norm(pos) > 1.0e8 or abs(dt) > 1.0e5:
+            fix.reason = 'diverged'
+            return fix
+        if it >= FREEZE_AFTER and np.linalg.norm(step[:4]) < STEP_TOL:
+            break
+    else:
+        fix.reason = 'no convergence'
+        return fix
+    f, e, fd = _model(ephs, prns, t0 + dt + d, pos)
+    r = z - f
+    y = r - N * C_MS - bias
+    H = np.column_stack([e, np.ones(len(prns)), fd])
+    cov = np.linalg.pinv(H.T @ H)
+    fix.g = float(np.sqrt(np.trace(cov[:3, :3])))
+    fix.residuals, fix.integers = y, N.astype(np.int64)
+    fix.rms_m = float(np.sqrt(np.sum(w * y * y) / np.sum(w)))
+    dof = len(prns) - 5
+    fix.test_m = fix.rms_m * np.sqrt(len(prns) / dof) if dof > 0 else 0.0
+    # what one bad measurement can do unseen: a bias b on satellite i moves the position by
+    # b |A[:3, i]| and the tested figure by b tau_i (A the solution map, S = I - H A the residual map)
+    A = np.linalg.pinv(H.T @ (H * w[:, None])) @ (H * w[:, None]).T
+    Sm = np.eye(len(prns)) - H @ A
+    fix.tau = np.sqrt(np.sum(w[:, None] * Sm * Sm, axis=0) / np.sum(w) * len(prns) / max(dof, 1)) if dof > 0 \
+        else np.zeros(len(prns))
+    fix.slope = np.linalg.norm(A[:3], axis=0) / np.maximum(fix.tau, 1.0e-12)
+    fix.bias_m = float(bias - np.rint(bias / C_MS) * C_MS)
+    fix.t_gps = float(t0 + dt)
+    fix.ecef = pos
+    fix.moved_m = float(2.0 * np.linalg.norm(pos - pos0) + REGION_M_PER_S * abs(dt))
+    if np.any(np.rint((r - r[ref]) / C_MS) != N):
+        fix.reason = 'the millisecond integers do not hold at the solution'
+    return fix
+
+
+def coarse_time_fix(meas, ephs, t_gps, pos, weights=None, code_samples=2048):
+    """Coarse-time navigation: `meas` (records with prn, sample, code_phase in samples and
+    cn0_dbhz; MEAS_DTYPE), `ephs` {prn: ephemeris}, `t_gps` the GPS seconds of week of the
+    strongest satellite's `sample` as far as known, `pos` the a-priori ECEF position -- within the
+    region of the module docstring.  `weights`: per record, default cn0_weights.  -> Fix; a Fix
+    that is not ok carries the reason and no position.
+
+    With six satellites or more the post-fit residual rms per degree of freedom (rms * sqrt(n /
+    (n - 5))) is tested against RMS_MAX_SAMPLES.  From seven on, a solution above it is solved
+    again with each satellite left out in turn, the best of those that pass replaces it (one
+    satellite dropped, once), and a solution that stays above is not ok.  Six satellites that fail
+    are refused: five of them would fit anything.  With five there is nothing to test, so the fix
+    must end inside the region around the a-priori that
+    guarantees its integers."""
+    meas = np.asarray(meas)
+    keep = [i for i, p in enumerate(meas['prn']) if int(p) in ephs]
+    meas = meas[keep]
+    if len(meas) < MIN_SAT:
+        return Fix(reason=f'{len(meas)} satellites with an ephemeris, {MIN_SAT} needed')
+    if len(set(meas['prn'].tolist())) < len(meas):
+        return Fix(reason='a satellite is measured twice')
+    fs = 1000.0 * code_samples
+    w = cn0_weights(meas['cn0_dbhz']) if weights is None else np.asarray(weights, np.float64)[keep]
+    prns = meas['prn'].astype(np.int64)
+    samples, phases = meas['sample'].astype(np.int64), meas['code_phase'].astype(np.float64)
+    clock = (int(samples[int(np.argmax(w))]), float(t_gps))
+    pos0 = np.asarray(pos, dtype=np.float64)
+    rms_max = RMS_MAX_SAMPLES * P.GPS_C / fs
+
+    def good(fx):
+        return not fx.reason and fx.test_m <= rms_max
+
+    fix = _solve(prns, samples, phases, w, ephs, clock, pos0, fs)
+    # (a set left with five satellites fits anything: one is dropped only from seven or more)
+    if len(prns) > MIN_SAT + 1 and not good(fix):
+        for k in range(len(prns)):
+            m = np.arange(len(prns)) != k
+            fx = _solve(prns[m], samples[m], phases[m], w[m], ephs, clock, pos0, fs)
+            fx.dropped = [int(prns[k])]
+            if good(fx) and (not good(fix) or fx.test_m < fix.test_m):
+                fix = fx
+    if not fix.reason and len(fix.prns) > MIN_SAT and fix.test_m > rms_max:
+        fix.reason = f'residual rms per degree of freedom {fix.test_m:.1f} m above {rms_max:.1f} m'
+    if not fix.reason and len(fix.prns) == MIN_SAT and fix.moved_m >= REGION_M:
+        fix.reason = 'five satellites and a solution outside the region around the a-priori'
+    if fix.residuals is not None:
+        fix.protect_m = float(np.max(fix.slope) * rms_max) if len(fix.prns) > MIN_SAT else float('inf')
+    fix.ok = not fix.reason
+    if not fix.ok:
+        fix.ecef = None
+    return fix
+
+
+# ---------------------------------------------------------------- a-priori from the Dopplers
+def doppler_fix(meas, ephs, t_gps, f_offset=0.0, max_it=30):
+    """Position and a common frequency offset from the Dopplers alone (`meas`: prn, f_hz), at
+    least four satellites: f_hz = -L1 / c * (range rate) + offset, Gauss-Newton from the point on
+    the Earth's surface under the mean satellite direction.  Kilometres at best (1 Hz is about
+    1.3 km): it is the a-priori position for coarse_time_fix when the caller has none, nothing more.
+    -> (ecef, clock_drift_hz)."""
+    meas = np.asarray(meas)
+    meas = meas[[i for i, p in enumerate(meas['prn']) if int(p) in ephs]]
+    if len(meas) < 4:
+        raise ValueError(f'{len(meas)} Dopplers with an ephemeris, 4 needed')
+    prns = meas['prn'].astype(np.int64)
+    t = np.full(len(prns), float(t_gps))
+    obs = (meas['f_hz'] - f_offset) * (-P.GPS_C / L1_HZ)          # range rates, m/s
+    up = np.zeros(3)
+    for prn in prns:
+        x = np.array(P.sat_ecef(1, ephs[int(prn)], DT=float(t_gps))[:3])
+        up += x / np.linalg.norm(x)
+    pos, drift = 6371.0e3 * up / np.linalg.norm(up), 0.0
+    h = 1.0e3
+    for _ in range(max_it):
+        fd = _rates(ephs, prns, t, pos)
+        J = np.ones((len(prns), 4))
+        for a in range(3):
+            dp = np.zeros(3)
+            dp[a] = h
+            J[:, a] = (_rates(ephs, prns, t, pos + dp) - _rates(ephs, prns, t, pos - dp)) / (2 * h)
+        step = np.linalg.lstsq(J, obs - fd - drift, rcond=None)[0]
+        n = np.linalg.norm(step[:3])
+        if n > 1.0e6:                                # (a long way off the model is not linear)
+            step *= 1.0e6 / n
+        pos, drift = pos + step[:3], drift + step[3]
+        if n < 10.0:                                 # (1 Hz of Doppler noise is a kilometre)
+            break
+    return pos, float(-drift * L1_HZ / P.GPS_C)
+
+
+# ---------------------------------------------------------------- measurements on the GPU
+def drop_ghosts(rec):
+    """DESIGN.md 4.2h's rule (pipeline.ghosts_of) among the records of one refinement call: a
+    record that is another one's satellite seen through the wrong code.  -> bool per record,
+    True = ghost."""
+    from .pipeline import ghosts_of
+    out = np.zeros(len(rec), bool)
+    for k, o in enumerate(rec):
+        hit = ghosts_of(o, rec)
+        hit[k] = False
+        out |= hit
+    return out
+
+
+def _bit_line(bits, n_bits, pull_in, cs, mid_sample):
+    """The straight line through the code starts of the bits behind pull-in against their nominal
+    positions, read at the middle one, and the Doppler line read at `mid_sample`.
+    -> (tau, f_hz) or None when too few bits are left."""
+    b = bits[pull_in:n_bits]
+    if len(b) < TRACK_MIN_BITS:
+        return None
+    x = (b['bit_no'] - b['bit_no'][len(b) // 2]).astype(np.float64)
+    nominal = x * 20.0 * cs
+    tau_mid = np.polyfit(x, b['tau'] - b['tau'][len(b) // 2] - nominal, 1)[1] + b['tau'][len(b) // 2]
+    pf = np.polyfit(b['tau'] - mid_sample, b['f_hz'], 1)
+    return float(tau_mid), float(pf[1])
+
+
+def refined_records(rec, found, cs, f_offset=0.0):
+    """The records of refinement (and the hits they were refined from) that count -- confirmed,
+    with a code phase, no ghost -- and their MEAS_DTYPE records as of the first sample.
+    -> (rec, found, records)."""
+    good = (rec['confirmed'] == 1) & (rec['code_phase'] >= 0) & ~drop_ghosts(rec)
+    rec, found = rec[good], [h for h, g in zip(found, good) if g]
+    out = np.zeros(len(rec), MEAS_DTYPE)
+    tap = 1 if cs == 2048 else 8
+    Tc = cs / (1.0 + (rec['f_hz'] - f_offset) / L1_HZ)
+    out['prn'], out['f_hz'], out['cn0_dbhz'] = rec['prn'], rec['f_hz'], rec['cn0_dbhz']
+    out['code_phase'] = np.mod(rec['code_phase'], cs)
+    # (refinement counts edge_ms from one period later when the delay is below the tap spacing)
+    late = np.array([1.0 if h[3] < tap else 0.0 for h in found])
+    out['edge'] = rec['code_phase'] + (rec['edge_ms'] + late) * Tc
+    # (without a transition in the data no edge shows: fewer than EDGE_MIN_BITS bits leave a chance)
+    out['edge'][rec['n_bits'] < EDGE_MIN_BITS] = np.nan
+    out['source'] = b'refine'
+    return rec, found, out
+
+
+def tracked_records(out, bits, n_done, n, cs, pull_in_bits=0):
+    """Replaces, in place, the records of refined_records by what the tracked bits say: bits
+    [nhits, n_bits] and n_done (bits each channel got through) of trackHits on the `n` samples."""
+    pull_in = 10 if pull_in_bits == 0 else max(int(pull_in_bits), 0)         # (track_weak's default)
+    for i in range(len(out)):
+        line = _bit_line(bits[i], int(n_done[i]), pull_in, cs, 0.5 * n)
+        if line is not None:
+            tau, f = line
+            k = int(np.floor(tau))
+            out[i] = (out['prn'][i], k, tau - k, f, out['cn0_dbhz'][i], tau, b'track')
+
+
+def min_samples(cs):
+    """The shortest snapshot: what Acquisition.refineHits needs for n_ms = 40 (two code periods and
+    the tap spacing in hand for the code slide), 86017 samples at 2048."""
+    return 42 * cs + (1 if cs == 2048 else 8)
+
+
+def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, **cfg):
+    """The satellites of one snapshot: MEAS_DTYPE records, one per satellite found, sorted by PRN.
+
+    `acq`: an acquisition.Acquisition; `data`: the samples in its input format (complex64, or the
+    recorder's uint16 with raw_u8) or a (device pointer, n) pair -- host data is uploaded once and
+    every stage reads that copy.  `prns`: what to search for (default acquisition.SAT_ALL; pass
+    the PRNs there are ephemerides for).  Stages: pipeline.largest_peak_hits over `prns` x the
+    bins (`freqs`, default the configured ones) in `n_coh`-ms segments, per PRN the largest peak
+    among the bins with normMaxCorr > `corr_min`; pipeline.refine_centred; confirmed records with
+    a code phase, ghosts dropped (drop_ghosts).  source 'refine': code phase and Doppler of the
+    refinement record, `sample` 0.
+    source 'track' (data of TRACK_MIN_SECONDS or more): Acquisition.trackHits through the same
+    data, the code starts of the bits behind pull-in fitted by a line and read at the middle bit,
+    `sample` there; a channel that leaves fewer than TRACK_MIN_BITS such bits keeps its refinement
+    values.  source None: DEFAULT_SOURCE where it applies.  `track_cfg`: trackHits' keywords.
+    `stats`: a dict that receives device_ms (the sum of the engine's last_ms), found and refined."""
+    from .acquisition import SAT_ALL
+    from .engine import DeviceBuffer
+    from .pipeline import largest_peak_hits, refine_centred
+    c = acq.cfg
+    cs = c.code_samples
+    n_coh = int(cfg.pop('n_coh', 4))
+    corr_min = float(cfg.pop('corr_min', c.corr_min))
+    freqs = cfg.pop('freqs', None)
+    track_cfg = dict(cfg.pop('track_cfg', None) or {})
+    if cfg:
+        raise TypeError(f'unknown options {sorted(cfg)}')
+    if freqs is None:
+        freqs = [c.min_freq + c.step_freq * i for i in range(int(round((c.max_freq - c.min_freq) / c.step_freq)))]
+    prns = list(SAT_ALL if prns is None else prns)
+    host = None if isinstance(data, tuple) else acq.engine._host_iq(data)
+    n = int(data[1]) if host is None else host.size
+    n_seg = n // cs // n_coh
+    if n < min_samples(cs) or n_seg < 1:
+        raise ValueError(f'{n} samples are too few: {min_samples(cs)} (40 ms and the code slide) are needed')
+    can_track = n >= int(TRACK_MIN_SECONDS * 1000) * cs
+    source = source or (DEFAULT_SOURCE if can_track else 'refine')
+    if source not in ('refine', 'track') or (source == 'track' and not can_track):
+        raise ValueError(f"source {source!r}: 'refine' or 'track', the latter from {TRACK_MIN_SECONDS} s on")
+    buf, dev = None, data
+    if host is not None:
+        buf = DeviceBuffer(host.nbytes, c.device)
+    try:
+        if buf is not None:
+            buf.upload(host)
+            dev = (buf.ptr, n)
+        out = np.zeros(0, MEAS_DTYPE)
+        st = {'device_ms': 0.0, 'found': [], 'refined': None}
+        found = largest_peak_hits(acq, (dev[0], n_seg * n_coh * cs), prns, freqs, n_coh, n_seg, f_offset=f_offset,
+                                  corr_min=corr_min)
+        st['device_ms'] += acq.engine.last_ms()
+        if found:
+            found, rec, ms = refine_centred(acq, dev, found, f_offset=f_offset)
+            st['device_ms'] += ms
+            st['found'], st['refined'] = found, rec
+            rec, found, out = refined_records(rec, found, cs, f_offset)
+            if source == 'track' and len(rec):
+                bits, states = acq.trackHits(dev, rec, f_offset=f_offset, **track_cfg)
+                st['device_ms'] += acq.engine.last_ms()
+                tracked_records(out, bits, states['bit_no'], n, cs, track_cfg.get('pull_in_bits', 0))
+            out = out[np.argsort(out['prn'], kind='stable')]
+        if stats is not None:
+            stats.update(st)
+        return out
+    finally:
+        if buf is not None:
+            buf.free()
+
+
+def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, **cfg):
+    """measure -> (doppler_fix when `pos` is None) -> coarse_time_fix.  `t_gps`: the GPS seconds
+    of week of the first sample as far as known.  -> (Fix, measurements, device ms).  The Fix's
+    t_gps is that of its `sample`."""
+    stats = {}
+    meas = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats, **cfg)
+    ms = stats.get('device_ms', 0.0)
+    if len(meas) < MIN_SAT:
+        return Fix(reason=f'{len(meas)} satellites measured, {MIN_SAT} needed'), meas, ms
+    fs = 1000.0 * acq.cfg.code_samples
+    if pos is None:
+        pos, _ = doppler_fix(meas, ephs, t_gps, f_offset=f_offset)
+    ref = int(np.argmax(cn0_weights(meas['cn0_dbhz'])))
+    fix = coarse_time_fix(meas, ephs, float(t_gps) + int(meas['sample'][ref]) / fs, pos,
+                          code_samples=acq.cfg.code_samples)
+    return fix, meas, ms

@@ -6,6 +6,7 @@ gpseval) as one command on the GPU path.
     python tools/run_file.py <recording.bin> [--seconds S] [--start-stream K] [--save-pickle P]
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--blank] [--json]
                              [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track [--weak-fix]]]]
+                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]]]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -46,6 +47,15 @@ search, refinement and tracking, online, on the first SECONDS behind the cold sw
 channels' subframes and code phases are merged into the datagrams the position fix is made of (and
 --save-pickle writes).  The report gains, per weak PRN, the subframes decoded and the fixes it took
 part in.  Without the flag every output is as before.
+--save-ephemeris PATH writes the ephemerides the run decoded in the format --ephemeris reads.
+--snapshot SECONDS replaces the run above by a snapshot fix (gpsmi.snapshot): the first
+SECONDS behind --start-stream (from 0.043 s on), read through --format / --fs / --if, --excise and --blank as
+above, searched, refined and -- from 0.5 s on -- tracked on the GPU for the PRNs of --ephemeris, and a
+position solved from the code phases without a decoded subframe.  It needs --time, the time of the first
+sample read, within 30 s: GPS seconds of week, or a UTC timestamp (2024-05-01T12:00:00) converted with the
+leap seconds of position.LEAPSEC and the ephemerides' week; --near LAT,LON[,H] is the position as far as
+known (within 50 km), without it the Dopplers give one.  It prints the measurements, the fix and the
+device time; with --json one line with a 'snapshot' key.
 
 There is no recording in this repository (data/test.bin is absent from the reference
 checkout, SURVEY F2, and too short for a fix even upstream): tests/test_run_file.py writes a
@@ -213,8 +223,136 @@ def weak_fix_report(assist, solver, fixes, cfg):
                          for prn, ch in assist.handoff.chan.items()]}
 
 
+def load_ephemerides(path):
+    """--ephemeris: {PRN: ephemeris} of a saved EPHEM_FILE (a JSON object keyed by the PRN)."""
+    with open(path) as f:
+        return {int(k): v for k, v in json.load(f).items()}
+
+
+def save_ephemerides(path, ephs):
+    """--save-ephemeris: {PRN: ephemeris} (position.EphemerisTable.ephem) as load_ephemerides reads
+    it back: the subframe 1-3 parameters, numpy scalars as plain numbers."""
+    from gpsmi import position as P
+    keys = P.EPHEM_SF1 + P.EPHEM_SF2 + P.EPHEM_SF3
+    out = {str(int(prn)): {k: getattr(e[k], 'tolist', lambda v=e[k]: v)() for k in keys}
+           for prn, e in sorted(ephs.items())}
+    with open(path, 'w') as f:
+        json.dump(out, f)
+
+
+def decoded_ephemerides(solver):
+    """{PRN: ephemeris} of the satellites whose subframes 1-3 a PositionSolver has read."""
+    return {s: o.data.ephem for s, o in solver.orbits.items() if o.data.ephem_ok}
+
+
+def parse_time(text, ephs):
+    """--time: GPS seconds of week, or a UTC timestamp turned into them with position.LEAPSEC and
+    the week number of the ephemerides."""
+    import datetime
+    from gpsmi import position as P
+    try:
+        return float(text)
+    except ValueError:
+        pass
+    t = datetime.datetime.fromisoformat(text.replace('Z', '+00:00'))
+    if t.tzinfo is not None:
+        t = t.astimezone(datetime.timezone.utc).replace(tzinfo=None)
+    week = next(iter(ephs.values()))['weekNum'] + P.ROLLOVER * 1024
+    start = datetime.datetime(1980, 1, 6) + datetime.timedelta(days=7 * week)
+    return (t - start).total_seconds() + P.LEAPSEC
+
+
+def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, frontend=None, excise=False,
+             blank=False):
+    """--snapshot: gpsmi.snapshot.snapshot_fix on the first `seconds` behind `start_stream`, read
+    and filtered block by block as run() feeds its receiver."""
+    from gpsmi import ingest, position as P, snapshot as S
+    from gpsmi.acquisition import Acquisition
+    from gpsmi.engine import Config
+    cfg = Config()
+    need = int(round(seconds * 1000)) * cfg.code_samples
+    fe = None
+    if frontend is None:
+        source = ingest.read_raw_blocks(path, cfg.ngps, start_stream)
+    else:
+        from gpsmi.frontend import FrontEnd
+        fe = FrontEnd(cfg, **frontend)
+        source = (b for k, b in enumerate(ingest.read_frontend_blocks(path, fe)) if k >= start_stream)
+    raw_u8 = frontend is None
+    filters, acq = [], None
+    try:
+        if excise:
+            from gpsmi.excision import Excision
+            filters.append(Excision(cfg, raw_u8=raw_u8))
+            raw_u8 = False
+        if blank:
+            from gpsmi.blanking import PulseBlanker
+            filters.append(PulseBlanker(cfg, raw_u8=raw_u8))
+            raw_u8 = False
+        blocks, have = [], 0
+        for blk in source:
+            for flt in filters:
+                blk = flt.apply(blk)
+            blocks.append(np.array(blk))
+            have += len(blk)
+            if have >= need:
+                break
+        if have < need:
+            sys.exit(f'--snapshot: the recording holds {have} samples after stream {start_stream}, {seconds} s need {need}')
+        acq = Acquisition(cfg, raw_u8=raw_u8)
+        t0 = time.perf_counter()
+        fix, meas, ms = S.snapshot_fix(acq, np.concatenate(blocks)[:need], ephemerides, t_gps,
+                                       pos=None if near is None else np.array(P.geo_to_ecef(*near)))
+        wall = time.perf_counter() - t0
+    finally:
+        for flt in filters:
+            flt.close()
+        if fe is not None:
+            fe.close()
+        if acq is not None:
+            acq.engine.close()
+    out = {'seconds': need / cfg.sample_rate, 'device_ms': round(ms, 3), 'wall_s': round(wall, 3),
+           'measurements': [{'prn': int(m['prn']), 'sample': int(m['sample']), 'code_phase': round(float(m['code_phase']), 4),
+                             'f_hz': round(float(m['f_hz']), 2),
+                             'cn0_dbhz': None if np.isnan(m['cn0_dbhz']) else round(float(m['cn0_dbhz']), 2),
+                             'source': m['source'].decode()} for m in meas],
+           'ok': bool(fix.ok), 'reason': fix.reason, 'satellites': fix.prns, 'dropped': fix.dropped}
+    if fix.ok:
+        geo = P.ecef_to_geo(fix.ecef)                # (None next to the Earth's centre)
+        out['position'] = {'lat_deg': None if geo is None else round(float(geo[0]), 6),
+                           'lon_deg': None if geo is None else round(float(geo[1]), 6),
+                           'height_m': None if geo is None else round(float(geo[2]), 1),
+                           'ecef_m': [round(float(v), 2) for v in fix.ecef]}
+        out.update({'t_gps': round(fix.t_gps, 6), 'sample': fix.sample, 'g': round(fix.g, 3),
+                    'residual_rms_m': round(fix.rms_m, 2),
+                    'protect_m': None if not np.isfinite(fix.protect_m) else round(fix.protect_m, 1)})
+    return {'file': os.path.basename(path), 'snapshot': out}
+
+
+def print_snapshot(out):
+    s = out['snapshot']
+    print(f"{out['file']}: snapshot of {s['seconds']} s, {len(s['measurements'])} satellites measured "
+          f"({s['device_ms']} ms on the device)")
+    for m in s['measurements']:
+        cn0 = 'n/a' if m['cn0_dbhz'] is None else f"{m['cn0_dbhz']:.1f}"
+        print(f"  PRN {m['prn']:2d}  sample {m['sample']:8d}  code_phase {m['code_phase']:9.4f}  f_hz {m['f_hz']:+9.2f}  "
+              f"cn0_dbhz {cn0}  ({m['source']})")
+    if s['ok']:
+        p = s['position']
+        where = f"ECEF {p['ecef_m']}" if p['lat_deg'] is None else \
+            f"{p['lat_deg']:.6f} N {p['lon_deg']:.6f} E, height {p['height_m']:.1f} m"
+        unseen = 'nothing bounds a bad measurement' if s['protect_m'] is None else \
+            f"one bad measurement could move it {s['protect_m']} m unseen"
+        print(f"fix from {len(s['satellites'])} satellites{' (dropped ' + str(s['dropped']) + ')' if s['dropped'] else ''}: "
+              f"{where}; GPS time {s['t_gps']} s at sample {s['sample']}; geometry factor {s['g']}, "
+              f"residual rms {s['residual_rms_m']} m; {unseen}")
+    else:
+        print(f"no snapshot fix: {s['reason']}")
+
+
 def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, cpu_acq=False, report_lag=16,
-        excise=False, frontend=None, blank=False, deep_acq=None, refine=False, track=False, weak_fix=False):
+        excise=False, frontend=None, blank=False, deep_acq=None, refine=False, track=False, weak_fix=False,
+        save_ephemeris=None):
     """frontend: None (the recorder's u8 format at 2.048 Msps) or a dict of frontend.FrontEnd's
     keyword arguments (fs_in, fmt, if_hz, conjugate).  deep_acq: None, or the seconds of the
     recording's start that deep_acquisition searches for the PRNs the sweep did not acquire; refine:
@@ -222,7 +360,7 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
     weak_fix (with deep_acq, refine and track): the receiver runs inside pipeline.WeakAssist, which
     searches the first deep_acq seconds behind the cold sweep, tracks what it confirms and merges
     those channels' subframes and code phases into the datagrams the solver is fed (DESIGN.md 4.2h);
-    the report gains 'weak_fix'."""
+    the report gains 'weak_fix'.  save_ephemeris: a path for the ephemerides the run decoded."""
     from gpsmi import ingest, position as P
     from gpsmi.engine import Config
     from gpsmi.pipeline import Receiver, save_results
@@ -266,6 +404,8 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
     wall = time.perf_counter() - t0
     if save_pickle:
         save_results(save_pickle, top.result_list)
+    if save_ephemeris:
+        save_ephemerides(save_ephemeris, decoded_ephemerides(solver))
     sats = sorted(rx.act_sat_set)
     weak = weak_fix_report(top, solver, fixes, cfg) if weak_fix else None
     rx.close()
@@ -325,6 +465,14 @@ def main():
                     help='with --refine: track the confirmed hits bit-synchronously through the recording (DESIGN.md 4.2g)')
     ap.add_argument('--weak-fix', action='store_true',
                     help='with --track: merge the weak channels into the datagrams the position fix is made of (DESIGN.md 4.2h)')
+    ap.add_argument('--save-ephemeris', default=None, metavar='PATH',
+                    help='write the ephemerides the run decoded, in the format --ephemeris reads')
+    ap.add_argument('--snapshot', type=float, default=None, metavar='SECONDS',
+                    help='a fix from the first SECONDS alone, no decoded subframe (DESIGN.md 4.2i); needs --ephemeris and --time')
+    ap.add_argument('--time', default=None,
+                    help='with --snapshot: time of the first sample read, GPS seconds of week or a UTC timestamp, within 30 s')
+    ap.add_argument('--near', default=None, metavar='LAT,LON[,H]',
+                    help='with --snapshot: the position as far as known (degrees, metres), within 50 km')
     ap.add_argument('--json', action='store_true', help='one JSON line instead of text')
     a = ap.parse_args()
     if a.refine and not a.deep_acq:
@@ -337,12 +485,29 @@ def main():
     if a.format is not None or a.fs is not None or a.if_hz is not None or a.conjugate:
         frontend = {'fmt': a.format or 'u8iq', 'fs_in': a.fs or 2048000, 'if_hz': a.if_hz or 0.0,
                     'conjugate': a.conjugate}
-    eph = None
-    if a.ephemeris:
-        with open(a.ephemeris) as f:
-            eph = {int(k): v for k, v in json.load(f).items()}
+    eph = load_ephemerides(a.ephemeris) if a.ephemeris else None
+    if a.snapshot is not None:
+        if not eph or a.time is None:
+            ap.error('--snapshot needs --ephemeris and --time')
+        if not 0.043 <= a.snapshot <= 8.0:            # (snapshot.min_samples: 86017 samples)
+            ap.error('--snapshot SECONDS: 0.043 .. 8')
+        near = None
+        if a.near:
+            near = [float(v) for v in a.near.split(',')]
+            if len(near) not in (2, 3):
+                ap.error('--near LAT,LON[,H]')
+            near = (near + [0.0])[:3]
+        out = snapshot(a.recording, a.snapshot, eph, parse_time(a.time, eph), near, a.start_stream, frontend,
+                       a.excise, a.blank)
+        if a.json:
+            print(json.dumps(out))
+        else:
+            print_snapshot(out)
+        return
+    if a.time is not None or a.near is not None:
+        ap.error('--time / --near need --snapshot SECONDS')
     out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise,
-              frontend, a.blank, a.deep_acq, a.refine, a.track, a.weak_fix)
+              frontend, a.blank, a.deep_acq, a.refine, a.track, a.weak_fix, a.save_ephemeris)
     if a.json:
         print(json.dumps(out))
         return
