@@ -98,17 +98,4 @@ struct DevEvent : DevHandle<hipEvent_t, hipEventDestroy> {
     }
 };
 
-// Device copies of the input and the output of a host entry point that works block by block
-// (gpsmi_pb_apply, gpsmi_ifx_apply): room for both, then the input on its way up on `stream`.
-struct StagedIO {
-    DevBuf<char> in, out;
-    int upload(const void* src, size_t in_bytes, size_t out_bytes, hipStream_t stream, const char* what) {
-        int rc = in.reserve(in_bytes, what);
-        if (!rc) rc = out.reserve(out_bytes, what);
-        if (rc) return rc;
-        GPSMI_HIP(hipMemcpyAsync(in.p, src, in_bytes, hipMemcpyHostToDevice, stream));
-        return GPSMI_OK;
-    }
-};
-
 }  // namespace gpsmi

@@ -27,11 +27,10 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "gpsmi_common.h"
-#include "gpsmi_devmem.h"
+#include "gpsmi_stage.h"
 
 namespace gpsmi {
 
@@ -273,10 +272,7 @@ struct gpsmi_fe {
     long long taken = 0;                                    // input samples since create / reset
     long long emitted = 0;                                  // outputs since create / reset
     bool flushed = false;
-    float last_ms = 0.f;
-    // released bottom up: the events, then the stream, then (above) the device buffers
-    DevStream stream;
-    DevEvent ev0, ev1;
+    StageSync sync;                                         // last: see gpsmi_stage.h
 };
 
 static size_t fe_sample_bytes(int fmt) {
@@ -297,47 +293,45 @@ static long long fe_complete(const FePlan& pl, long long total) {
     return (long long)((num + pl.P - 1) / pl.P);
 }
 
-template <int FMT>
-static void fe_launch_stage(gpsmi_fe* h, const void* in, long long n_in) {
-    const long long n = h->plan.kc + n_in;
-    hipLaunchKernelGGL(fe_stage_kernel<FMT>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, in,
-                       h->d_carry.p, h->plan.kc, n_in, h->taken, h->plan.inc,
-                       (h->cfg.flags & GPSMI_FE_CONJUGATE) ? 1 : 0, h->d_vbuf.p);
-}
-
 // One call: n_in samples at d_in (device, the handle's format; null: zeros) -> n_out outputs at d_out.
 static int fe_run(gpsmi_fe* h, const void* d_in, long long n_in, float2* d_out, long long n_out) {
     const FePlan& pl = h->plan;
+    const hipStream_t st = h->sync.stream;
     int rc = h->d_vbuf.reserve((size_t)(pl.kc + n_in), "front-end sample scratch");
+    if (!rc) rc = h->sync.begin();
     if (rc) return rc;
-    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
-    if (!d_in) fe_launch_stage<kFeZero>(h, nullptr, n_in);
-    else switch (h->cfg.format) {
-        case GPSMI_FE_C64: fe_launch_stage<GPSMI_FE_C64>(h, d_in, n_in); break;
-        case GPSMI_FE_U8IQ: fe_launch_stage<GPSMI_FE_U8IQ>(h, d_in, n_in); break;
-        case GPSMI_FE_SC8: fe_launch_stage<GPSMI_FE_SC8>(h, d_in, n_in); break;
-        case GPSMI_FE_SC16: fe_launch_stage<GPSMI_FE_SC16>(h, d_in, n_in); break;
-        default: fe_launch_stage<GPSMI_FE_R8>(h, d_in, n_in); break;
-    }
+    with_value<kFeZero, GPSMI_FE_C64, GPSMI_FE_U8IQ, GPSMI_FE_SC8, GPSMI_FE_SC16, GPSMI_FE_R8>(
+        d_in ? h->cfg.format : kFeZero, [&](auto fmt) {
+            const long long n = pl.kc + n_in;
+            hipLaunchKernelGGL(fe_stage_kernel<decltype(fmt)::value>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                               st, d_in, h->d_carry.p, pl.kc, n_in, h->taken, pl.inc,
+                               (h->cfg.flags & GPSMI_FE_CONJUGATE) ? 1 : 0, h->d_vbuf.p);
+        });
     if (n_out > 0) {
         const __int128 t0 = (__int128)h->emitted * pl.P;
         const long long I0 = (long long)(t0 / pl.Q), r0 = (long long)(t0 % pl.Q);
         const long long vbase = h->taken - pl.kc;
         const unsigned groups = (unsigned)((n_out + pl.R - 1) / pl.R);
-        hipLaunchKernelGGL(fe_filter_kernel, dim3(groups), dim3((unsigned)pl.R), pl.lds, h->stream, h->d_vbuf.p,
-                           vbase, I0, r0, pl.P, pl.Q, pl.K, pl.L, h->d_table.p, pl.tab_floats, pl.R, n_out, d_out);
+        hipLaunchKernelGGL(fe_filter_kernel, dim3(groups), dim3((unsigned)pl.R), pl.lds, st, h->d_vbuf.p, vbase, I0,
+                           r0, pl.P, pl.Q, pl.K, pl.L, h->d_table.p, pl.tab_floats, pl.R, n_out, d_out);
     }
-    hipLaunchKernelGGL(fe_carry_kernel, dim3(1), dim3(256), 0, h->stream, h->d_vbuf.p, n_in, pl.kc, h->d_carry.p);
-    GPSMI_HIP(hipGetLastError());
-    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
-    return GPSMI_OK;
+    hipLaunchKernelGGL(fe_carry_kernel, dim3(1), dim3(256), 0, st, h->d_vbuf.p, n_in, pl.kc, h->d_carry.p);
+    return h->sync.end();
 }
 
-static int fe_finish(gpsmi_fe* h, long long n_in, long long n_out) {
-    GPSMI_HIP(hipStreamSynchronize(h->stream));
-    GPSMI_HIP(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+// The tail of every entry point: run, the n outputs on their way to `host_out` (null: they stay at
+// d_out), finish, bookkeeping.
+static int fe_call(gpsmi_fe* h, const void* d_in, long long n_in, float2* d_out, long long n, float* host_out,
+                   size_t* n_out) {
+    int rc = fe_run(h, d_in, n_in, d_out, n);
+    if (rc) return rc;
+    if (host_out && n > 0)
+        GPSMI_HIP(hipMemcpyAsync(host_out, d_out, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost,
+                                 h->sync.stream));
+    if ((rc = h->sync.finish())) return rc;
     h->taken += n_in;
-    h->emitted += n_out;
+    h->emitted += n;
+    *n_out = (size_t)n;
     return GPSMI_OK;
 }
 
@@ -352,8 +346,6 @@ static int fe_check_call(gpsmi_fe* h, size_t n_in, size_t max_out, long long* n_
 }
 
 extern "C" {
-
-int gpsmi_fe_destroy(gpsmi_fe* h);
 
 int gpsmi_fe_design(const gpsmi_fe_cfg* cfg, int* n_taps, int* n_phases, float* table) {
     GPSMI_REQUIRE(cfg && n_taps && n_phases, "null argument");
@@ -373,46 +365,26 @@ int gpsmi_fe_create(const gpsmi_fe_cfg* cfg, gpsmi_fe** out) {
     FePlan pl;
     int rc = fe_plan(cfg, &pl);
     if (rc) return rc;
-    GPSMI_HIP(hipSetDevice(cfg->device));
-    gpsmi_fe* h = new (std::nothrow) gpsmi_fe();
-    if (!h) return fail(GPSMI_E_NOMEM, "out of host memory");
-    h->cfg = *cfg;
-    h->plan = std::move(pl);
-    rc = [&]() -> int {
+    return stage_create(cfg, out, [&](gpsmi_fe* h) {
+        h->plan = std::move(pl);
         const FePlan& p = h->plan;
-        int rc = h->stream.create();
-        if (!rc) rc = h->ev0.create();
-        if (!rc) rc = h->ev1.create();
-        if (rc) return rc;
         if (p.lds > kFeLdsBudget)
             GPSMI_HIP(hipFuncSetAttribute((const void*)fe_filter_kernel,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-        rc = h->d_table.upload(p.table, "front-end filter table");
+        int rc = h->d_table.upload(p.table, "front-end filter table");
         if (!rc) rc = h->d_carry.reserve_zeroed(p.kc, "front-end carry");
         if (!rc) rc = h->d_out.reserve(h->cfg.max_out, "front-end output block");
         return rc;
-    }();
-    if (rc) {
-        (void)gpsmi_fe_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return GPSMI_OK;
+    });
 }
 
-int gpsmi_fe_destroy(gpsmi_fe* h) {
-    if (!h) return GPSMI_OK;
-    (void)hipSetDevice(h->cfg.device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    delete h;                                // (releases events, stream and device buffers, in this order)
-    return GPSMI_OK;
-}
+int gpsmi_fe_destroy(gpsmi_fe* h) { return stage_destroy(h); }
 
 int gpsmi_fe_reset(gpsmi_fe* h) {
     GPSMI_REQUIRE(h, "null handle");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    GPSMI_HIP(hipMemsetAsync(h->d_carry.p, 0, (size_t)h->plan.kc * sizeof(float2), h->stream));
-    GPSMI_HIP(hipStreamSynchronize(h->stream));
+    GPSMI_HIP(hipMemsetAsync(h->d_carry.p, 0, (size_t)h->plan.kc * sizeof(float2), h->sync.stream));
+    GPSMI_HIP(hipStreamSynchronize(h->sync.stream));
     h->taken = 0;
     h->emitted = 0;
     h->flushed = false;
@@ -428,12 +400,7 @@ int gpsmi_fe_push_dev(gpsmi_fe* h, const void* d_in, size_t n_in, void* d_out, s
     *n_out = 0;
     if (n_in == 0) return GPSMI_OK;
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    rc = fe_run(h, d_in, (long long)n_in, static_cast<float2*>(d_out), n);
-    if (rc) return rc;
-    rc = fe_finish(h, (long long)n_in, n);
-    if (rc) return rc;
-    *n_out = (size_t)n;
-    return GPSMI_OK;
+    return fe_call(h, d_in, (long long)n_in, static_cast<float2*>(d_out), n, nullptr, n_out);
 }
 
 int gpsmi_fe_push(gpsmi_fe* h, const void* in, size_t n_in, float* out, size_t max_out, size_t* n_out) {
@@ -451,15 +418,8 @@ int gpsmi_fe_push(gpsmi_fe* h, const void* in, size_t n_in, float* out, size_t m
     const size_t ib = n_in * fe_sample_bytes(h->cfg.format);
     rc = h->d_in.reserve(ib, "front-end staging");
     if (rc) return rc;
-    GPSMI_HIP(hipMemcpyAsync(h->d_in.p, in, ib, hipMemcpyHostToDevice, h->stream));
-    rc = fe_run(h, h->d_in.p, (long long)n_in, h->d_out.p, n);
-    if (rc) return rc;
-    if (n > 0)
-        GPSMI_HIP(hipMemcpyAsync(out, h->d_out.p, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-    rc = fe_finish(h, (long long)n_in, n);
-    if (rc) return rc;
-    *n_out = (size_t)n;
-    return GPSMI_OK;
+    GPSMI_HIP(hipMemcpyAsync(h->d_in.p, in, ib, hipMemcpyHostToDevice, h->sync.stream));
+    return fe_call(h, h->d_in.p, (long long)n_in, h->d_out.p, n, out, n_out);
 }
 
 int gpsmi_fe_flush(gpsmi_fe* h, float* out, size_t max_out, size_t* n_out) {
@@ -473,21 +433,11 @@ int gpsmi_fe_flush(gpsmi_fe* h, float* out, size_t max_out, size_t* n_out) {
         return fail(GPSMI_E_ARG, "gpsmi_fe_flush: emits %lld samples, the handle's max_out is %d", n,
                     (int)h->cfg.max_out);
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    rc = fe_run(h, nullptr, pad, h->d_out.p, n);
-    if (rc) return rc;
-    if (n > 0)
-        GPSMI_HIP(hipMemcpyAsync(out, h->d_out.p, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-    rc = fe_finish(h, pad, n);
-    if (rc) return rc;
-    h->flushed = true;
-    *n_out = (size_t)n;
-    return GPSMI_OK;
+    rc = fe_call(h, nullptr, pad, h->d_out.p, n, out, n_out);
+    if (!rc) h->flushed = true;
+    return rc;
 }
 
-int gpsmi_fe_last_ms(gpsmi_fe* h, float* ms) {
-    GPSMI_REQUIRE(h && ms, "null argument");
-    *ms = h->last_ms;
-    return GPSMI_OK;
-}
+int gpsmi_fe_last_ms(gpsmi_fe* h, float* ms) { return stage_last_ms(h, ms, __func__); }
 
 }  // extern "C"

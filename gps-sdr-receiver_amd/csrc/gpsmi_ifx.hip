@@ -34,12 +34,11 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "gpsmi_common.h"
-#include "gpsmi_devmem.h"
 #include "gpsmi_fft.h"
+#include "gpsmi_stage.h"
 
 namespace gpsmi {
 
@@ -242,24 +241,18 @@ struct gpsmi_ifx {
     DevBuf<uint32_t> d_masks;                // [nb][kMaskWords]
     DevBuf<float> d_psd;                     // [nb][2048]: the P the mask pass thresholded
     int last_nb = 0;                         // blocks of the last call (0: none yet)
-    StagedIO io;                             // host entry: staged input and output
-    int fmt = GPSMI_IQ_C64;
     float scale = 0.f;                       // 10^(thresh_db / 10) as float32
-    float last_ms = 0.f;
-    // released bottom up: the events, then the stream, then (above) the device buffers
-    DevStream stream;
-    DevEvent ev0, ev1;
+    BlockStage blk;
+    StageSync sync;                          // last: see gpsmi_stage.h
 };
 
 static bool ifx_block_ok(int32_t n) { return n >= 4 * kIfxH && n <= (1 << 24) && n % kIfxH == 0; }
 
 static int ifx_build(gpsmi_ifx* h) {
-    int rc = h->stream.create();
-    if (!rc) rc = h->ev0.create();
-    if (!rc) rc = h->ev1.create();
-    if (rc) return rc;
+    h->blk.block_samples = h->cfg.block_samples;
     std::vector<float2> tw;
     make_twiddles(tw);
+    int rc;
     if ((rc = h->d_tw.upload(tw, "excision twiddles"))) return rc;
     std::vector<float> win(kIfxL);
     for (int i = 0; i < kIfxL; ++i) {
@@ -281,50 +274,41 @@ static int ifx_run(gpsmi_ifx* h, const void* d_iq, void* d_out, int nb) {
     if (!rc) rc = h->d_masks.reserve((size_t)nb * kMaskWords, "excision results");
     if (!rc) rc = h->d_psd.reserve((size_t)nb * kIfxL, "excision results");
     if (rc) return rc;
+    const hipStream_t st = h->sync.stream;
     // segments per apply workgroup: one frame transform pair per segment plus one per workgroup;
     // runs of up to 8 segments once the grid has some 2048 workgroups anyway (same bits either way)
     const long long segs = (long long)nb * nf;
     const int S = segs >= 16384 ? 8 : segs >= 8192 ? 4 : segs >= 4096 ? 2 : 1;
     const int runs = (nf + S - 1) / S;
     const size_t tail = (size_t)nb * n - kIfxH;
-    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
-    with_fmt(h->fmt, [&](auto fmt) {
+    if ((rc = h->sync.begin())) return rc;
+    with_fmt(h->blk.fmt, [&](auto fmt) {
         constexpr int FMT = decltype(fmt)::value;
-        hipLaunchKernelGGL(ifx_psd_kernel<FMT>, dim3((unsigned)(nb * groups)), dim3(256), 0, h->stream, d_iq,
+        hipLaunchKernelGGL(ifx_psd_kernel<FMT>, dim3((unsigned)(nb * groups)), dim3(256), 0, st, d_iq,
                            h->d_carry.p, h->d_win.p, n, groups, h->d_partial.p, h->d_tw.p);
-        hipLaunchKernelGGL(ifx_mask_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, h->d_partial.p, groups,
+        hipLaunchKernelGGL(ifx_mask_kernel, dim3((unsigned)nb), dim3(256), 0, st, h->d_partial.p, groups,
                            nf - 1, h->scale, h->cfg.dilate, h->cfg.max_bins, h->d_counts.p, h->d_masks.p,
                            h->d_psd.p);
-        hipLaunchKernelGGL(ifx_apply_kernel<FMT>, dim3((unsigned)(nb * runs)), dim3(256), 0, h->stream, d_iq,
+        hipLaunchKernelGGL(ifx_apply_kernel<FMT>, dim3((unsigned)(nb * runs)), dim3(256), 0, st, d_iq,
                            h->d_carry.p, h->d_win.p, n, runs, S, h->d_counts.p, h->d_masks.p, (float2*)d_out,
                            h->d_tw.p);
-        hipLaunchKernelGGL(ifx_carry_kernel<FMT>, dim3(1), dim3(256), 0, h->stream, d_iq, tail, h->d_carry.p);
+        hipLaunchKernelGGL(ifx_carry_kernel<FMT>, dim3(1), dim3(256), 0, st, d_iq, tail, h->d_carry.p);
     });
-    GPSMI_HIP(hipGetLastError());
-    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
-    h->last_nb = nb;
-    return GPSMI_OK;
+    if (!(rc = h->sync.end())) h->last_nb = nb;
+    return rc;
 }
 
 static int ifx_finish(gpsmi_ifx* h, int nb, int32_t* counts, uint32_t* masks) {
+    const hipStream_t st = h->sync.stream;
     if (counts)
-        GPSMI_HIP(hipMemcpyAsync(counts, h->d_counts.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                 h->stream));
+        GPSMI_HIP(hipMemcpyAsync(counts, h->d_counts.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (masks)
         GPSMI_HIP(hipMemcpyAsync(masks, h->d_masks.p, (size_t)nb * kMaskWords * sizeof(uint32_t),
-                                 hipMemcpyDeviceToHost, h->stream));
-    GPSMI_HIP(hipStreamSynchronize(h->stream));
-    GPSMI_HIP(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return GPSMI_OK;
-}
-
-static size_t ifx_in_bytes(const gpsmi_ifx* h, int nb) {
-    return (size_t)nb * h->cfg.block_samples * (h->fmt == GPSMI_IQ_U8 ? sizeof(uint16_t) : sizeof(float2));
+                                 hipMemcpyDeviceToHost, st));
+    return h->sync.finish();
 }
 
 extern "C" {
-
-int gpsmi_ifx_destroy(gpsmi_ifx* h);
 
 int gpsmi_ifx_create(const gpsmi_ifx_cfg* cfg, gpsmi_ifx** out) {
     GPSMI_REQUIRE(cfg && out, "null argument");
@@ -336,88 +320,50 @@ int gpsmi_ifx_create(const gpsmi_ifx_cfg* cfg, gpsmi_ifx** out) {
         return fail(GPSMI_E_UNSUPPORTED,
                     "gpsmi_ifx_create: block_samples %d is not a multiple of 1024 in 4096..2^24",
                     (int)cfg->block_samples);
-    GPSMI_HIP(hipSetDevice(cfg->device));
-    gpsmi_ifx* h = new (std::nothrow) gpsmi_ifx();
-    if (!h) return fail(GPSMI_E_NOMEM, "out of host memory");
-    h->cfg = *cfg;
-    const int rc = ifx_build(h);
-    if (rc) {
-        (void)gpsmi_ifx_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return GPSMI_OK;
+    return stage_create(cfg, out, ifx_build);
 }
 
-int gpsmi_ifx_destroy(gpsmi_ifx* h) {
-    if (!h) return GPSMI_OK;
-    (void)hipSetDevice(h->cfg.device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    delete h;                                // (releases events, stream and device buffers, in this order)
-    return GPSMI_OK;
-}
+int gpsmi_ifx_destroy(gpsmi_ifx* h) { return stage_destroy(h); }
 
-int gpsmi_ifx_set_input_format(gpsmi_ifx* h, int fmt) {
-    GPSMI_REQUIRE(h, "null handle");
-    GPSMI_REQUIRE(fmt == GPSMI_IQ_C64 || fmt == GPSMI_IQ_U8, "unknown input format");
-    GPSMI_HIP(hipSetDevice(h->cfg.device));
-    GPSMI_HIP(hipStreamSynchronize(h->stream));
-    h->fmt = fmt;
-    return GPSMI_OK;
-}
+int gpsmi_ifx_set_input_format(gpsmi_ifx* h, int fmt) { return stage_set_input_format(h, fmt, __func__); }
 
 int gpsmi_ifx_reset(gpsmi_ifx* h) {
     GPSMI_REQUIRE(h, "null handle");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    GPSMI_HIP(hipMemsetAsync(h->d_carry.p, 0, kIfxH * sizeof(float2), h->stream));
-    GPSMI_HIP(hipStreamSynchronize(h->stream));
+    GPSMI_HIP(hipMemsetAsync(h->d_carry.p, 0, kIfxH * sizeof(float2), h->sync.stream));
+    GPSMI_HIP(hipStreamSynchronize(h->sync.stream));
     return GPSMI_OK;
 }
 
 int gpsmi_ifx_apply_dev(gpsmi_ifx* h, const void* d_iq, void* d_out, int nb, int32_t* counts,
                         uint32_t* masks) {
-    GPSMI_REQUIRE(h && d_iq && d_out, "null argument");
-    GPSMI_REQUIRE(nb >= 1 && (size_t)nb * h->cfg.block_samples <= ((size_t)1 << 31),
-                  "nb out of range: 1 .. 2^31 samples per call");
-    {   // the output of one block is made of the input of the block before: no overlap at all
-        const char* i0 = static_cast<const char*>(d_iq);
-        const char* o0 = static_cast<const char*>(d_out);
-        const size_t ib = ifx_in_bytes(h, nb), ob = (size_t)nb * h->cfg.block_samples * sizeof(float2);
-        GPSMI_REQUIRE(o0 + ob <= i0 || i0 + ib <= o0, "input and output overlap (no in-place excision)");
-    }
+    int rc = stage_check_call(h, d_iq, d_out, nb, __func__, "excision", false);
+    if (rc) return rc;
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    int rc = ifx_run(h, d_iq, d_out, nb);
+    rc = ifx_run(h, d_iq, d_out, nb);
     if (rc) return rc;
     return ifx_finish(h, nb, counts, masks);
 }
 
 int gpsmi_ifx_apply(gpsmi_ifx* h, const void* iq, float* out, int nb, int32_t* counts, uint32_t* masks) {
-    GPSMI_REQUIRE(h && iq && out, "null argument");
-    GPSMI_REQUIRE(nb >= 1 && (size_t)nb * h->cfg.block_samples <= ((size_t)1 << 31),
-                  "nb out of range: 1 .. 2^31 samples per call");
+    int rc = stage_check_call(h, iq, out, nb, __func__, nullptr, false);   // (host buffers: overlap not checked)
+    if (rc) return rc;
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    const size_t ib = ifx_in_bytes(h, nb), ob = (size_t)nb * h->cfg.block_samples * sizeof(float2);
-    int rc = h->io.upload(iq, ib, ob, h->stream, "excision staging");
-    if (rc) return rc;
-    rc = ifx_run(h, h->io.in.p, h->io.out.p, nb);
-    if (rc) return rc;
-    GPSMI_HIP(hipMemcpyAsync(out, h->io.out.p, ob, hipMemcpyDeviceToHost, h->stream));
-    return ifx_finish(h, nb, counts, masks);
+    return h->blk.apply_host(
+        iq, out, nb, h->sync.stream, "excision staging",
+        [&](const void* d_iq, void* d_out) { return ifx_run(h, d_iq, d_out, nb); },
+        [&] { return ifx_finish(h, nb, counts, masks); });
 }
 
-int gpsmi_ifx_last_ms(gpsmi_ifx* h, float* ms) {
-    GPSMI_REQUIRE(h && ms, "null argument");
-    *ms = h->last_ms;
-    return GPSMI_OK;
-}
+int gpsmi_ifx_last_ms(gpsmi_ifx* h, float* ms) { return stage_last_ms(h, ms, __func__); }
 
 int gpsmi_ifx_last_psd(gpsmi_ifx* h, float* psd) {
     GPSMI_REQUIRE(h && psd, "null argument");
     if (h->last_nb <= 0) return fail(GPSMI_E_STATE, "gpsmi_ifx_last_psd: no call yet");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     GPSMI_HIP(hipMemcpyAsync(psd, h->d_psd.p, (size_t)h->last_nb * kIfxL * sizeof(float), hipMemcpyDeviceToHost,
-                             h->stream));
-    GPSMI_HIP(hipStreamSynchronize(h->stream));
+                             h->sync.stream));
+    GPSMI_HIP(hipStreamSynchronize(h->sync.stream));
     return GPSMI_OK;
 }
 

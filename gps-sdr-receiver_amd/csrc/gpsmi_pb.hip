@@ -36,10 +36,9 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 
 #include "gpsmi_common.h"
-#include "gpsmi_devmem.h"
+#include "gpsmi_stage.h"
 
 namespace gpsmi {
 
@@ -316,26 +315,16 @@ struct gpsmi_pb {
     DevBuf<int> d_carries; DevBuf<int32_t> d_counts;      // [blocks + 1], [blocks]
     DevBuf<int> d_scount;                                 // [blocks][slices]
     DevBuf<uint32_t> d_masks;                             // [blocks][n / 32]
-    StagedIO io;                                          // host entry: staged input and output
-    int fmt = GPSMI_IQ_C64;
     float f = 0.f;                                        // 10^(thresh_db / 10) as float32
     int limit = 0;                                        // floor(max_frac * n)
     size_t chunk_bytes = 0;                               // input bytes per chunk (0: one chunk)
-    float last_ms = 0.f;
-    // released bottom up: the events, then the stream, then (above) the device buffers
-    DevStream stream;
-    DevEvent ev0, ev1;
+    BlockStage blk;
+    StageSync sync;                                       // last: see gpsmi_stage.h
 };
 
-static size_t pb_in_bytes(const gpsmi_pb* h, int nb) {
-    return (size_t)nb * h->cfg.block_samples * (h->fmt == GPSMI_IQ_U8 ? sizeof(uint16_t) : sizeof(float2));
-}
-
 static int pb_build(gpsmi_pb* h) {
-    int rc = h->stream.create();
-    if (!rc) rc = h->ev0.create();
-    if (!rc) rc = h->ev1.create();
-    if (!rc) rc = h->d_state.reserve_zeroed(1, "pulse blanking carry");
+    h->blk.block_samples = h->cfg.block_samples;
+    const int rc = h->d_state.reserve_zeroed(1, "pulse blanking carry");
     if (rc) return rc;
     h->f = (float)pow(10.0, (double)h->cfg.thresh_db / 10.0);
     h->limit = (int)floor((double)h->cfg.max_frac * (double)h->cfg.block_samples);
@@ -357,7 +346,7 @@ static int pb_results(gpsmi_pb* h, int nb) {
 // the mask words into the handle's buffer.
 static int pb_run(gpsmi_pb* h, const void* d_iq, void* d_out, int nb, bool want_masks) {
     const int n = h->cfg.block_samples;
-    const size_t blk_bytes = pb_in_bytes(h, 1);
+    const size_t blk_bytes = h->blk.in_bytes(1);
     const int S = nb >= 16 ? kPbSliceBig : kPbSliceSmall;
     const int ns = (n + S - 1) / S;
     int cb = h->chunk_bytes ? (int)std::max<size_t>(1, h->chunk_bytes / blk_bytes) : nb;
@@ -370,69 +359,50 @@ static int pb_run(gpsmi_pb* h, const void* d_iq, void* d_out, int nb, bool want_
     uint32_t* masks = want_masks ? h->d_masks.p : nullptr;
     float2* out = static_cast<float2*>(d_out);
     const int pre = h->cfg.pre, post = h->cfg.post;
-    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
+    const hipStream_t st = h->sync.stream;
+    if ((rc = h->sync.begin())) return rc;
     for (int b0 = 0; b0 < nb; b0 += cb) {
         const int m = std::min(cb, nb - b0);
         const dim3 g((unsigned)(m * ns)), gb((unsigned)m), blk(256);
-        with_fmt(h->fmt, [&](auto fmt) {
+        with_fmt(h->blk.fmt, [&](auto fmt) {
             constexpr int FMT = decltype(fmt)::value;
-            hipLaunchKernelGGL((pb_hist_kernel<FMT, 0>), g, blk, 0, h->stream, d_iq, n, ns, S, b0, h->d_sel.p,
+            hipLaunchKernelGGL((pb_hist_kernel<FMT, 0>), g, blk, 0, st, d_iq, n, ns, S, b0, h->d_sel.p,
                                h->d_hist.p);
-            hipLaunchKernelGGL((pb_select_kernel<FMT, 0>), gb, blk, 0, h->stream, h->d_hist.p, ns, n, b0, h->d_sel.p,
+            hipLaunchKernelGGL((pb_select_kernel<FMT, 0>), gb, blk, 0, st, h->d_hist.p, ns, n, b0, h->d_sel.p,
                                h->f, d_iq, post, h->d_floors.p, h->d_thr.p, h->d_carries.p);
-            hipLaunchKernelGGL((pb_hist_kernel<FMT, 1>), g, blk, 0, h->stream, d_iq, n, ns, S, b0, h->d_sel.p,
+            hipLaunchKernelGGL((pb_hist_kernel<FMT, 1>), g, blk, 0, st, d_iq, n, ns, S, b0, h->d_sel.p,
                                h->d_hist.p);
-            hipLaunchKernelGGL((pb_select_kernel<FMT, 1>), gb, blk, 0, h->stream, h->d_hist.p, ns, n, b0, h->d_sel.p,
+            hipLaunchKernelGGL((pb_select_kernel<FMT, 1>), gb, blk, 0, st, h->d_hist.p, ns, n, b0, h->d_sel.p,
                                h->f, d_iq, post, h->d_floors.p, h->d_thr.p, h->d_carries.p);
-            hipLaunchKernelGGL((pb_hist_kernel<FMT, 2>), g, blk, 0, h->stream, d_iq, n, ns, S, b0, h->d_sel.p,
+            hipLaunchKernelGGL((pb_hist_kernel<FMT, 2>), g, blk, 0, st, d_iq, n, ns, S, b0, h->d_sel.p,
                                h->d_hist.p);
-            hipLaunchKernelGGL((pb_select_kernel<FMT, 2>), gb, blk, 0, h->stream, h->d_hist.p, ns, n, b0, h->d_sel.p,
+            hipLaunchKernelGGL((pb_select_kernel<FMT, 2>), gb, blk, 0, st, h->d_hist.p, ns, n, b0, h->d_sel.p,
                                h->f, d_iq, post, h->d_floors.p, h->d_thr.p, h->d_carries.p);
-            hipLaunchKernelGGL((pb_apply_kernel<FMT>), g, blk, 0, h->stream, d_iq, n, ns, S, b0, pre, post,
+            hipLaunchKernelGGL((pb_apply_kernel<FMT>), g, blk, 0, st, d_iq, n, ns, S, b0, pre, post,
                                h->d_thr.p, h->d_carries.p, h->d_state.p, out, masks, h->d_scount.p);
         });
     }
-    with_fmt(h->fmt, [&](auto fmt) {
-        hipLaunchKernelGGL(pb_fixup_kernel<decltype(fmt)::value>, dim3((unsigned)nb), dim3(256), 0, h->stream, d_iq,
+    with_fmt(h->blk.fmt, [&](auto fmt) {
+        hipLaunchKernelGGL(pb_fixup_kernel<decltype(fmt)::value>, dim3((unsigned)nb), dim3(256), 0, st, d_iq,
                            n, ns, nb, h->limit, h->d_scount.p, h->d_carries.p, h->d_state.p, h->d_counts.p, out, masks);
     });
-    GPSMI_HIP(hipGetLastError());
-    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
-    return GPSMI_OK;
+    return h->sync.end();
 }
 
 static int pb_finish(gpsmi_pb* h, int nb, int32_t* counts, float* floors, uint32_t* masks) {
     const int n = h->cfg.block_samples;
+    const hipStream_t st = h->sync.stream;
     if (counts)
-        GPSMI_HIP(hipMemcpyAsync(counts, h->d_counts.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                 h->stream));
+        GPSMI_HIP(hipMemcpyAsync(counts, h->d_counts.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (floors)
-        GPSMI_HIP(hipMemcpyAsync(floors, h->d_floors.p, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost,
-                                 h->stream));
+        GPSMI_HIP(hipMemcpyAsync(floors, h->d_floors.p, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost, st));
     if (masks)
         GPSMI_HIP(hipMemcpyAsync(masks, h->d_masks.p, (size_t)nb * (n / 32) * sizeof(uint32_t),
-                                 hipMemcpyDeviceToHost, h->stream));
-    GPSMI_HIP(hipStreamSynchronize(h->stream));
-    GPSMI_HIP(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    return GPSMI_OK;
-}
-
-// argument checks shared by both entry points (before any GPU work)
-static int pb_check_call(const gpsmi_pb* h, const void* iq, const void* out, int nb, const char* fn) {
-    if (!h || !iq || !out) return fail(GPSMI_E_ARG, "%s: null argument", fn);
-    if (nb < 1 || (size_t)nb * h->cfg.block_samples > ((size_t)1 << 31))
-        return fail(GPSMI_E_ARG, "%s: nb out of range: 1 .. 2^31 samples per call", fn);
-    const char* i0 = static_cast<const char*>(iq);
-    const char* o0 = static_cast<const char*>(out);
-    const size_t ib = pb_in_bytes(h, nb), ob = (size_t)nb * h->cfg.block_samples * sizeof(float2);
-    if (!(o0 + ob <= i0 || i0 + ib <= o0))
-        return fail(GPSMI_E_ARG, "%s: input and output overlap (no in-place blanking)", fn);
-    return GPSMI_OK;
+                                 hipMemcpyDeviceToHost, st));
+    return h->sync.finish();
 }
 
 extern "C" {
-
-int gpsmi_pb_destroy(gpsmi_pb* h);
 
 int gpsmi_pb_create(const gpsmi_pb_cfg* cfg, gpsmi_pb** out) {
     GPSMI_REQUIRE(cfg && out, "null argument");
@@ -444,50 +414,25 @@ int gpsmi_pb_create(const gpsmi_pb_cfg* cfg, gpsmi_pb** out) {
     GPSMI_REQUIRE(cfg->pre >= 0 && cfg->pre <= kPbMaxGuard, "pre out of range 0..1024");
     GPSMI_REQUIRE(cfg->post >= 0 && cfg->post <= kPbMaxGuard, "post out of range 0..1024");
     GPSMI_REQUIRE(cfg->max_frac >= 0.f && cfg->max_frac <= 1.f, "max_frac out of range 0..1");
-    GPSMI_HIP(hipSetDevice(cfg->device));
-    gpsmi_pb* h = new (std::nothrow) gpsmi_pb();
-    if (!h) return fail(GPSMI_E_NOMEM, "out of host memory");
-    h->cfg = *cfg;
-    const int rc = pb_build(h);
-    if (rc) {
-        (void)gpsmi_pb_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return GPSMI_OK;
+    return stage_create(cfg, out, pb_build);
 }
 
-int gpsmi_pb_destroy(gpsmi_pb* h) {
-    if (!h) return GPSMI_OK;
-    (void)hipSetDevice(h->cfg.device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    delete h;                                // (releases events, stream and device buffers, in this order)
-    return GPSMI_OK;
-}
+int gpsmi_pb_destroy(gpsmi_pb* h) { return stage_destroy(h); }
 
-int gpsmi_pb_set_input_format(gpsmi_pb* h, int fmt) {
-    GPSMI_REQUIRE(h, "null handle");
-    GPSMI_REQUIRE(fmt == GPSMI_IQ_C64 || fmt == GPSMI_IQ_U8, "unknown input format");
-    GPSMI_HIP(hipSetDevice(h->cfg.device));
-    GPSMI_HIP(hipStreamSynchronize(h->stream));
-    h->fmt = fmt;
-    return GPSMI_OK;
-}
+int gpsmi_pb_set_input_format(gpsmi_pb* h, int fmt) { return stage_set_input_format(h, fmt, __func__); }
 
 int gpsmi_pb_reset(gpsmi_pb* h) {
     GPSMI_REQUIRE(h, "null handle");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    GPSMI_HIP(hipMemsetAsync(h->d_state.p, 0, sizeof(int), h->stream));
-    GPSMI_HIP(hipStreamSynchronize(h->stream));
+    GPSMI_HIP(hipMemsetAsync(h->d_state.p, 0, sizeof(int), h->sync.stream));
+    GPSMI_HIP(hipStreamSynchronize(h->sync.stream));
     return GPSMI_OK;
 }
 
 int gpsmi_pb_apply_dev(gpsmi_pb* h, const void* d_iq, void* d_out, int nb, int32_t* counts, float* floors,
                        uint32_t* masks) {
-    int rc = pb_check_call(h, d_iq, d_out, nb, __func__);
+    int rc = stage_check_call(h, d_iq, d_out, nb, __func__, "blanking", true);
     if (rc) return rc;
-    GPSMI_REQUIRE(((uintptr_t)d_iq % (h->fmt == GPSMI_IQ_U8 ? 4 : 16)) == 0 && (uintptr_t)d_out % 16 == 0,
-                  "device input / output not aligned (4 bytes for u8, 16 for complex64)");
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     rc = pb_run(h, d_iq, d_out, nb, masks != nullptr);
     if (rc) return rc;
@@ -496,22 +441,15 @@ int gpsmi_pb_apply_dev(gpsmi_pb* h, const void* d_iq, void* d_out, int nb, int32
 
 int gpsmi_pb_apply(gpsmi_pb* h, const void* iq, float* out, int nb, int32_t* counts, float* floors,
                    uint32_t* masks) {
-    int rc = pb_check_call(h, iq, out, nb, __func__);
+    int rc = stage_check_call(h, iq, out, nb, __func__, "blanking", false);
     if (rc) return rc;
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    const size_t ib = pb_in_bytes(h, nb), ob = (size_t)nb * h->cfg.block_samples * sizeof(float2);
-    rc = h->io.upload(iq, ib, ob, h->stream, "pulse blanking staging");
-    if (rc) return rc;
-    rc = pb_run(h, h->io.in.p, h->io.out.p, nb, masks != nullptr);
-    if (rc) return rc;
-    GPSMI_HIP(hipMemcpyAsync(out, h->io.out.p, ob, hipMemcpyDeviceToHost, h->stream));
-    return pb_finish(h, nb, counts, floors, masks);
+    return h->blk.apply_host(
+        iq, out, nb, h->sync.stream, "pulse blanking staging",
+        [&](const void* d_iq, void* d_out) { return pb_run(h, d_iq, d_out, nb, masks != nullptr); },
+        [&] { return pb_finish(h, nb, counts, floors, masks); });
 }
 
-int gpsmi_pb_last_ms(gpsmi_pb* h, float* ms) {
-    GPSMI_REQUIRE(h && ms, "null argument");
-    *ms = h->last_ms;
-    return GPSMI_OK;
-}
+int gpsmi_pb_last_ms(gpsmi_pb* h, float* ms) { return stage_last_ms(h, ms, __func__); }
 
 }  // extern "C"

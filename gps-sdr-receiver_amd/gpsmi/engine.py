@@ -84,7 +84,10 @@ class DeviceBuffer:
               'gpsmi_dev_upload')
 
     def download(self, dtype, count, offset=0):
-        out = np.empty(count, dtype=dtype)
+        return self.download_into(np.empty(count, dtype=dtype), offset)
+
+    def download_into(self, out, offset=0):
+        """Fills `out` (C-contiguous, e.g. page-locked) from the buffer; -> out."""
         if offset + out.nbytes > self.nbytes:
             raise ValueError('download exceeds the buffer')
         src = C.c_void_p(self.ptr.value + offset)

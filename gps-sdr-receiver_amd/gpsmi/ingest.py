@@ -6,6 +6,8 @@ of that ring buffer on the GPU: blocks go from a small ring of page-locked buffe
 into the tracking engine without a host wait per block
 (``gpsmi_trk_process_stream``)."""
 from collections import deque
+from contextlib import contextmanager
+from itertools import islice
 
 import numpy as np
 
@@ -72,6 +74,36 @@ def read_frontend_blocks(path, fe, chunk_samples=1 << 20):
                 yield from fe.blocks(x)
             if x.size < per:
                 return
+
+
+@contextmanager
+def open_blocks(path, cfg, start_stream=0, frontend=None):
+    """The blocks of a recording behind its first `start_stream` ones, as ``(blocks, raw_u8)``:
+    read_raw_blocks and True for the recorder's own format (frontend None), else
+    read_frontend_blocks through a frontend.FrontEnd(cfg, **frontend) that lives as long as the
+    context, and False."""
+    if frontend is None:
+        yield read_raw_blocks(path, cfg.ngps, start_stream), True
+        return
+    from .frontend import FrontEnd
+    fe = FrontEnd(cfg, **frontend)
+    try:
+        yield islice(read_frontend_blocks(path, fe), start_stream, None), False
+    finally:
+        fe.close()
+
+
+def take(blocks, need, conditioner=None):
+    """The first blocks of `blocks` that hold `need` samples, each through `conditioner` (a
+    conditioning.Conditioner) and copied out of whatever page-locked buffer it came in
+    -> (list of blocks, samples in them: fewer than `need` when the stream ended first)."""
+    got, have = [], 0
+    for blk in blocks:
+        got.append(np.array(conditioner.apply(blk) if conditioner else blk))
+        have += len(blk)
+        if have >= need:
+            break
+    return got, have
 
 
 def decode_host(raw):

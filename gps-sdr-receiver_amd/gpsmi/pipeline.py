@@ -38,34 +38,13 @@ class Receiver:
         blanking).  With both, each block is excised, then blanked, on the device (one copy in, one
         out): a tone raises every sample's power and would hide the pulses from the blanker, while
         the pulses only add a flat level to the excision's spectrum.  The PulseBlanker then takes
-        complex64 (raw_u8=False).  None, the default: no blanking."""
+        complex64 (raw_u8=False).  None, the default: no blanking.  The chain is `conditioner`
+        (conditioning.Conditioner); its `last` is the block the engines saw."""
+        from .conditioning import Conditioner
         self.cfg = cfg or Config()
-        self.excision, self.blanker, self._clean = None, None, None
-        self._own_excision = self._own_blanker = False
-        self._d_in = self._d_mid = self._d_out = None
-        if excise is not None and excise is not False:
-            from .excision import Excision
-            self._own_excision = excise is True
-            self.excision = Excision(self.cfg, raw_u8=raw_u8) if excise is True else excise
-            if self.excision.raw_u8 != bool(raw_u8) or self.excision.n != self.cfg.ngps:
-                raise ValueError('the Excision does not match raw_u8 / the block length')
-        if blank is not None and blank is not False:
-            from .blanking import PulseBlanker
-            b_u8 = bool(raw_u8) and self.excision is None      # (behind the excision: its complex64)
-            self._own_blanker = blank is True
-            self.blanker = PulseBlanker(self.cfg, raw_u8=b_u8) if blank is True else blank
-            if self.blanker.raw_u8 != b_u8 or self.blanker.n != self.cfg.ngps:
-                raise ValueError('the PulseBlanker does not match raw_u8 / the block length')
-        if self.excision is not None or self.blanker is not None:
-            from .engine import DeviceBuffer, PinnedArray
-            self._clean = PinnedArray((self.cfg.ngps,), np.complex64)
-            if self.excision is not None and self.blanker is not None:
-                n = self.cfg.ngps
-                self._d_in = DeviceBuffer(n * (2 if raw_u8 else 8), self.cfg.device)
-                self._d_mid = DeviceBuffer(n * 8, self.cfg.device)
-                self._d_out = DeviceBuffer(n * 8, self.cfg.device)
-            raw_u8 = False                           # (the engines see the filters' complex64)
-        self.raw_u8 = bool(raw_u8)
+        self.conditioner = Conditioner(self.cfg, raw_u8, excise, blank)
+        self.excision, self.blanker = self.conditioner.excision, self.conditioner.blanker
+        self.raw_u8 = self.conditioner.out_raw_u8     # (the engines see the filters' complex64)
         self.sat_all = list(SAT_ALL if sat_all is None else sat_all)
         self.acq = Acquisition(self.cfg, raw_u8=self.raw_u8)
         self.pool, self.pool_no, self.pool_worker = R.initMultiProcPool(self.cfg.max_sat,
@@ -98,10 +77,9 @@ class Receiver:
         """One block (complex64[NGPS], or uint16[NGPS] when raw_u8); `skip` = streams lost before it
         (gpsrecv.py:469-471).  Returns the pickled hand-off or None."""
         c = self.cfg
-        if self._clean is not None:
-            # (one page-locked block serves every call: the acquisition reads it before it returns,
-            # the tracking pool copies it into its own input ring)
-            data = self._filter(data)
+        # (one page-locked block serves every call: the acquisition reads it before it returns,
+        # the tracking pool copies it into its own input ring)
+        data = self.conditioner.apply(data)
         self.skipped_data += skip * c.ngps
         self.smp_time += (1 + skip) * c.ngps
         if self.sweep_all_freq:
@@ -128,23 +106,6 @@ class Receiver:
                                    self.smp_time):
             res = self.hand_off(batch) or res
         return res
-
-    def _filter(self, data):
-        out = self._clean.array
-        if self.blanker is None:
-            return self.excision.apply(data, out=out)
-        if self.excision is None:
-            return self.blanker.apply(data, out=out)
-        want = np.uint16 if self.excision.raw_u8 else np.complex64
-        x = np.ascontiguousarray(data)
-        if x.dtype != want or x.size != self.cfg.ngps:
-            raise ValueError(f'one block of {self.cfg.ngps} {np.dtype(want).name} samples expected')
-        self._d_in.upload(x)
-        self.excision.apply_dev(self._d_in.ptr, self._d_mid.ptr, 1)
-        self.blanker.apply_dev(self._d_mid.ptr, self._d_out.ptr, 1)
-        _lib.check(_lib.load().gpsmi_dev_download(self.cfg.device, _lib.ptr(out), self._d_out.ptr, out.nbytes),
-                   'gpsmi_dev_download')
-        return out
 
     def drain(self):
         """Absorb the blocks that are still on their way (before anything that reads the
@@ -190,16 +151,7 @@ class Receiver:
         self.drain()
         R.closeMultiProcPool(self.pool)
         self.acq.engine.close()
-        if self._clean is not None:
-            self._clean.free()
-            self._clean = None
-            for d in (self._d_in, self._d_mid, self._d_out):
-                if d is not None:
-                    d.free()
-            if self._own_excision:
-                self.excision.close()
-            if self._own_blanker:
-                self.blanker.close()
+        self.conditioner.close()
 
 
 def send_udp(sock, res, ip=UDP_IP, port=UDP_PORT):
@@ -376,8 +328,7 @@ class WeakAssist:
             self._rearm()
         self._strong += rx.result_list[self._n_rx:]
         self._n_rx = len(rx.result_list)
-        if rx._clean is not None:                    # (the engines saw the filters' output)
-            block = rx._clean.array
+        block = rx.conditioner.last                  # (what the engines saw)
         if self.tracker is None:
             if not self.searched and not sweeping and not rx.sweep_all_freq:
                 self._keep(block)

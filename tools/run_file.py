@@ -12,7 +12,7 @@ gpseval) as one command on the GPU path.
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
                       (1 min = 245.76 MB).  `data/test.bin` of the reference when it is there.
 
-Flow: ingest.read_raw_blocks (the file loop of streamData, START_STREAM honoured) ->
+Flow: ingest.open_blocks (read_raw_blocks: the file loop of streamData, START_STREAM honoured) ->
 pipeline.Receiver(raw_u8=True).feed (cold sweep, channel selection, tracking, hand-off
 datagrams; the u8 decode happens inside the GPU kernels) -> position.PositionSolver.feed
 (prepCodePhase ... leastSquaresPos, the evaluation side's data path) -> fixes; the mean of
@@ -152,54 +152,39 @@ def deep_acquisition(path, seconds, start_stream, skip_prns, frontend=None, n_co
     if not 1 <= n_seg <= 32768:
         sys.exit(f'--deep-acq: {n_coh}-ms segments of {seconds} s: {n_seg}, must be 1..32768')
     need = n_seg * n_coh * cfg.code_samples
-    fe = None
-    if frontend is None:
-        source = ingest.read_raw_blocks(path, cfg.ngps, start_stream)
-    else:
-        from gpsmi.frontend import FrontEnd
-        fe = FrontEnd(cfg, **frontend)
-        source = (b for k, b in enumerate(ingest.read_frontend_blocks(path, fe)) if k >= start_stream)
-    blocks, have = [], 0
-    for blk in source:
-        blocks.append(blk)
-        have += len(blk)
-        if have >= need:
-            break
-    if have < need:
-        if fe is not None:
-            fe.close()
-        sys.exit(f'--deep-acq: the recording holds {have} samples after stream {start_stream}, '
-                 f'{seconds} s need {need}')
-    whole = np.concatenate(blocks)
-    data = whole[:need]
-    acq = Acquisition(cfg, raw_u8=frontend is None)
-    freqs = [cfg.min_freq + cfg.step_freq * i
-             for i in range(int(round((cfg.max_freq - cfg.min_freq) / cfg.step_freq)))]
-    sat_lst = [s for s in SAT_ALL if s not in skip_prns]
-    res = acq.sweepDeepSats(data, freqs, sat_lst, [], n_coh=n_coh, n_seg=n_seg)
-    ms = acq.engine.last_ms()
-    out = {'seconds': n_seg * n_coh / 1000.0, 'n_coh': n_coh, 'n_seg': n_seg, 'device_ms': round(ms, 3),
-           'searched': sat_lst,
-           'found': [(int(s), float(f), int(d), round(float(nmc), 2)) for nmc, s, f, d in res]}
-    if refine and res:
-        if len(whole) < 43 * cfg.code_samples:
-            sys.exit(f'--refine: {len(whole)} samples are too few for 40 ms and the code slide')
-        rec = acq.refineHits(whole, res)
-        out['refined'] = {'n_ms': int(20 * (rec['n_bits'][0] + 1)), 'device_ms': round(acq.engine.last_ms(), 3),
-                          'records': [{'prn': int(r['prn']), 'f_hz': round(float(r['f_hz']), 2),
-                                       'edge_ms': int(r['edge_ms']), 'code_phase': round(float(r['code_phase']), 3),
-                                       'cn0_dbhz': None if np.isnan(r['cn0_dbhz']) else round(float(r['cn0_dbhz']), 2),
-                                       'ratio': round(float(r['ratio']), 3), 'confirmed': bool(r['confirmed'])}
-                                      for r in rec]}
-        if track:
-            out['tracked'] = track_refined(acq, rec, whole, source, cfg)
-    elif refine:
-        out['refined'] = {'n_ms': 0, 'device_ms': 0.0, 'records': []}
-        if track:
-            out['tracked'] = {'device_ms': 0.0, 'chunks': 0, 'channels': []}
-    if fe is not None:
-        fe.close()
-    acq.engine.close()
+    with ingest.open_blocks(path, cfg, start_stream, frontend) as (source, raw_u8):
+        blocks, have = ingest.take(source, need)
+        if have < need:
+            sys.exit(f'--deep-acq: the recording holds {have} samples after stream {start_stream}, '
+                     f'{seconds} s need {need}')
+        whole = np.concatenate(blocks)
+        data = whole[:need]
+        acq = Acquisition(cfg, raw_u8=raw_u8)
+        freqs = [cfg.min_freq + cfg.step_freq * i
+                 for i in range(int(round((cfg.max_freq - cfg.min_freq) / cfg.step_freq)))]
+        sat_lst = [s for s in SAT_ALL if s not in skip_prns]
+        res = acq.sweepDeepSats(data, freqs, sat_lst, [], n_coh=n_coh, n_seg=n_seg)
+        ms = acq.engine.last_ms()
+        out = {'seconds': n_seg * n_coh / 1000.0, 'n_coh': n_coh, 'n_seg': n_seg, 'device_ms': round(ms, 3),
+               'searched': sat_lst,
+               'found': [(int(s), float(f), int(d), round(float(nmc), 2)) for nmc, s, f, d in res]}
+        if refine and res:
+            if len(whole) < 43 * cfg.code_samples:
+                sys.exit(f'--refine: {len(whole)} samples are too few for 40 ms and the code slide')
+            rec = acq.refineHits(whole, res)
+            out['refined'] = {'n_ms': int(20 * (rec['n_bits'][0] + 1)), 'device_ms': round(acq.engine.last_ms(), 3),
+                              'records': [{'prn': int(r['prn']), 'f_hz': round(float(r['f_hz']), 2),
+                                           'edge_ms': int(r['edge_ms']), 'code_phase': round(float(r['code_phase']), 3),
+                                           'cn0_dbhz': None if np.isnan(r['cn0_dbhz']) else round(float(r['cn0_dbhz']), 2),
+                                           'ratio': round(float(r['ratio']), 3), 'confirmed': bool(r['confirmed'])}
+                                          for r in rec]}
+            if track:
+                out['tracked'] = track_refined(acq, rec, whole, source, cfg)
+        elif refine:
+            out['refined'] = {'n_ms': 0, 'device_ms': 0.0, 'records': []}
+            if track:
+                out['tracked'] = {'device_ms': 0.0, 'chunks': 0, 'channels': []}
+        acq.engine.close()
     return out
 
 
@@ -268,49 +253,25 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
     and filtered block by block as run() feeds its receiver."""
     from gpsmi import ingest, position as P, snapshot as S
     from gpsmi.acquisition import Acquisition
+    from gpsmi.conditioning import Conditioner
     from gpsmi.engine import Config
     cfg = Config()
     need = int(round(seconds * 1000)) * cfg.code_samples
-    fe = None
-    if frontend is None:
-        source = ingest.read_raw_blocks(path, cfg.ngps, start_stream)
-    else:
-        from gpsmi.frontend import FrontEnd
-        fe = FrontEnd(cfg, **frontend)
-        source = (b for k, b in enumerate(ingest.read_frontend_blocks(path, fe)) if k >= start_stream)
-    raw_u8 = frontend is None
-    filters, acq = [], None
-    try:
-        if excise:
-            from gpsmi.excision import Excision
-            filters.append(Excision(cfg, raw_u8=raw_u8))
-            raw_u8 = False
-        if blank:
-            from gpsmi.blanking import PulseBlanker
-            filters.append(PulseBlanker(cfg, raw_u8=raw_u8))
-            raw_u8 = False
-        blocks, have = [], 0
-        for blk in source:
-            for flt in filters:
-                blk = flt.apply(blk)
-            blocks.append(np.array(blk))
-            have += len(blk)
-            if have >= need:
-                break
-        if have < need:
-            sys.exit(f'--snapshot: the recording holds {have} samples after stream {start_stream}, {seconds} s need {need}')
-        acq = Acquisition(cfg, raw_u8=raw_u8)
-        t0 = time.perf_counter()
-        fix, meas, ms = S.snapshot_fix(acq, np.concatenate(blocks)[:need], ephemerides, t_gps,
-                                       pos=None if near is None else np.array(P.geo_to_ecef(*near)))
-        wall = time.perf_counter() - t0
-    finally:
-        for flt in filters:
-            flt.close()
-        if fe is not None:
-            fe.close()
-        if acq is not None:
-            acq.engine.close()
+    with ingest.open_blocks(path, cfg, start_stream, frontend) as (source, raw_u8):
+        cond, acq = Conditioner(cfg, raw_u8, excise, blank), None
+        try:
+            blocks, have = ingest.take(source, need, cond)
+            if have < need:
+                sys.exit(f'--snapshot: the recording holds {have} samples after stream {start_stream}, {seconds} s need {need}')
+            acq = Acquisition(cfg, raw_u8=cond.out_raw_u8)
+            t0 = time.perf_counter()
+            fix, meas, ms = S.snapshot_fix(acq, np.concatenate(blocks)[:need], ephemerides, t_gps,
+                                           pos=None if near is None else np.array(P.geo_to_ecef(*near)))
+            wall = time.perf_counter() - t0
+        finally:
+            cond.close()
+            if acq is not None:
+                acq.engine.close()
     out = {'seconds': need / cfg.sample_rate, 'device_ms': round(ms, 3), 'wall_s': round(wall, 3),
            'measurements': [{'prn': int(m['prn']), 'sample': int(m['sample']), 'code_phase': round(float(m['code_phase']), 4),
                              'f_hz': round(float(m['f_hz']), 2),
@@ -367,50 +328,39 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
     cfg = Config()
     # (a recording: the datagrams may come out `report_lag` blocks behind the block they belong to, the
     # reader then runs ahead of the GPU instead of stalling it once a second -- pipeline.Receiver)
-    fe = None
-    if frontend is None:
-        rx = Receiver(cfg, raw_u8=True, report_lag=report_lag, excise=True if excise else None,
-                      blank=True if blank else None)
-        source = ingest.read_raw_blocks(path, cfg.ngps, start_stream)
-    else:
-        from gpsmi.frontend import FrontEnd
-        fe = FrontEnd(cfg, **frontend)
-        rx = Receiver(cfg, raw_u8=False, report_lag=report_lag, excise=True if excise else None,
-                      blank=True if blank else None)
-        source = (b for k, b in enumerate(ingest.read_frontend_blocks(path, fe)) if k >= start_stream)
-    if weak_fix:
-        from gpsmi.pipeline import WeakAssist
-        top = WeakAssist(rx, seconds=deep_acq)
-    else:
-        top = rx
-    solver = P.PositionSolver(cfg.code_samples, cfg.n_cyc, ephemerides=ephemerides)
-    max_blocks = None if seconds is None else int(seconds * 1000 // cfg.n_cyc)
-    fixes, n_dg, n_blocks, found = [], 0, 0, None
-    t0 = time.perf_counter()
-    for raw in source:
-        top.feed(raw)
-        n_blocks += 1
-        if found is None and not rx.sweep_all_freq:
-            found = list(rx.found_sats)
-        for dg in top.result_list[n_dg:]:          # (every datagram, in order: RESULT_LIST)
+    with ingest.open_blocks(path, cfg, start_stream, frontend) as (source, raw_u8):
+        rx = Receiver(cfg, raw_u8=raw_u8, report_lag=report_lag, excise=excise, blank=blank)
+        if weak_fix:
+            from gpsmi.pipeline import WeakAssist
+            top = WeakAssist(rx, seconds=deep_acq)
+        else:
+            top = rx
+        solver = P.PositionSolver(cfg.code_samples, cfg.n_cyc, ephemerides=ephemerides)
+        max_blocks = None if seconds is None else int(seconds * 1000 // cfg.n_cyc)
+        fixes, n_dg, n_blocks, found = [], 0, 0, None
+        t0 = time.perf_counter()
+        for raw in source:
+            top.feed(raw)
+            n_blocks += 1
+            if found is None and not rx.sweep_all_freq:
+                found = list(rx.found_sats)
+            for dg in top.result_list[n_dg:]:          # (every datagram, in order: RESULT_LIST)
+                n_dg += 1
+                fixes += solver.feed(pickle.loads(dg))
+            if max_blocks is not None and n_blocks >= max_blocks:
+                break
+        top.drain()
+        for dg in top.result_list[n_dg:]:
             n_dg += 1
             fixes += solver.feed(pickle.loads(dg))
-        if max_blocks is not None and n_blocks >= max_blocks:
-            break
-    top.drain()
-    for dg in top.result_list[n_dg:]:
-        n_dg += 1
-        fixes += solver.feed(pickle.loads(dg))
-    wall = time.perf_counter() - t0
-    if save_pickle:
-        save_results(save_pickle, top.result_list)
-    if save_ephemeris:
-        save_ephemerides(save_ephemeris, decoded_ephemerides(solver))
-    sats = sorted(rx.act_sat_set)
-    weak = weak_fix_report(top, solver, fixes, cfg) if weak_fix else None
-    rx.close()
-    if fe is not None:
-        fe.close()
+        wall = time.perf_counter() - t0
+        if save_pickle:
+            save_results(save_pickle, top.result_list)
+        if save_ephemeris:
+            save_ephemerides(save_ephemeris, decoded_ephemerides(solver))
+        sats = sorted(rx.act_sat_set)
+        weak = weak_fix_report(top, solver, fixes, cfg) if weak_fix else None
+        rx.close()
     out = {'file': os.path.basename(path), 'blocks': n_blocks, 'signal_s': round(n_blocks * cfg.n_cyc / 1000.0, 3),
            'wall_s': round(wall, 3), 'x_realtime': round(n_blocks * cfg.n_cyc / 1000.0 / wall, 1) if wall else None,
            'acquired': [(int(s), float(f), int(d)) for _, s, f, d in (found or [])],
