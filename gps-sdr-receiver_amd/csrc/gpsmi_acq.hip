@@ -9,6 +9,8 @@
 //   gpsmi_refine.h        refinement of weak / deep hits (gpsmi_acq_refine): fine
 //                         Doppler, bit edge, sub-sample code phase, C/N0
 //   gpsmi_wtrk.h          bit-synchronous tracking of refined hits (gpsmi_acq_track)
+//   gpsmi_cancel.h        cancellation of strong satellites ahead of the weak searches
+//                         (gpsmi_acq_cancel): per-period projection, in place
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -21,6 +23,7 @@
 #include "gpsmi_stats.h"
 #include "gpsmi_refine.h"
 #include "gpsmi_wtrk.h"
+#include "gpsmi_cancel.h"
 #include "gpsmi_acq_search.h"
 
 using namespace gpsmi;
@@ -67,6 +70,11 @@ struct gpsmi_acq {
     // bit-synchronous tracking (gpsmi_acq_track): the states of a call, its bit records
     DevBuf<gpsmi_wtrk_state> d_ws;          // [kWtrkMaxHits]
     DevBuf<gpsmi_wtrk_bit> d_wb;
+    // cancellation (gpsmi_acq_cancel): the complex64 output of a host call whose input is raw, the
+    // window tables of a call, the windows' results [nsat][max_windows]
+    DevBuf<float2> d_cx;
+    DevBuf<CancelWin> d_cw;
+    DevBuf<CancelRes> d_cr;
     int iq_fmt = GPSMI_IQ_C64;              // what the iq pointers of the search calls point to
     // bytes of `n` samples in the handle's input format
     size_t iq_bytes(size_t n) const { return n * (iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)); }
@@ -609,6 +617,117 @@ int gpsmi_acq_track_plan(int code_samples, size_t n, const gpsmi_wtrk_state* sta
 int gpsmi_wtrk_open(const gpsmi_refine_out* rec, int code_samples, int refine_tap_samples, int64_t data_start,
                     double carrier_hz, double f_offset_hz, gpsmi_wtrk_state* st) {
     return wtrk_open(rec, code_samples, refine_tap_samples, data_start, carrier_hz, f_offset_hz, st);
+}
+
+// ---- cancellation of strong satellites (kernels and plan: gpsmi_cancel.h) ---------------------
+static int acq_cancel_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n, const gpsmi_cancel_sat* sats,
+                           int nsat, const gpsmi_cancel_cfg* cfg, void* out_c64, gpsmi_cancel_out* out,
+                           float* coef) {
+    GPSMI_REQUIRE(h && iq && out_c64 && (out || nsat == 0), "null argument");
+    CancelPlan pl;
+    int rc = cancel_plan(h->cfg.code_samples, n, sats, nsat, cfg, &pl);
+    if (rc) return rc;
+    for (int i = 0; i < nsat; ++i)
+        if (!h->have_time[sats[i].prn])
+            return fail(GPSMI_E_STATE, "gpsmi_acq_cancel: no time-domain replica set for PRN %d "
+                                       "(gpsmi_acq_set_replica_time)", (int)sats[i].prn);
+    const bool u8 = h->iq_fmt == GPSMI_IQ_U8;
+    const size_t out_bytes = n * sizeof(float2);
+    bool in_place = false;
+    if (!on_host) {
+        const char *a = static_cast<const char*>(iq), *b = static_cast<const char*>(out_c64);
+        in_place = !u8 && a == b;
+        if (!in_place && a < b + out_bytes && b < a + h->iq_bytes(n))
+            return fail(GPSMI_E_ARG, "gpsmi_acq_cancel_dev: d_iq and d_out_c64 overlap (only one complex64 "
+                                     "buffer for both is cancelled in place)");
+    }
+    h->last_ms = 0.f;
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    // where the input lies and where the satellites are taken out
+    const void* d_in = iq;
+    float2* d_y = static_cast<float2*>(out_c64);
+    if (on_host) {
+        if ((rc = acq_upload(h, iq, n))) return rc;
+        d_in = h->d_iq.p;
+        if (u8) {
+            if ((rc = h->d_cx.reserve(n, "gpsmi_acq_cancel output"))) return rc;
+            d_y = h->d_cx.p;
+        } else {
+            d_y = h->d_iq.p;
+            in_place = true;
+        }
+    }
+    const int mw = pl.max_windows;
+    const size_t nres = (size_t)nsat * mw;
+    std::vector<CancelRes> res;
+    if (nres) {
+        try { res.resize(nres); } catch (const std::bad_alloc&) {
+            return fail(GPSMI_E_NOMEM, "gpsmi_acq_cancel: out of host memory");
+        }
+        if ((rc = h->d_cw.reserve(pl.wins.size(), "gpsmi_acq_cancel windows")) ||
+            (rc = h->d_cr.reserve(nres, "gpsmi_acq_cancel results")))
+            return rc;
+        GPSMI_HIP(hipMemcpyAsync(h->d_cw.p, pl.wins.data(), pl.wins.size() * sizeof(CancelWin),
+                                 hipMemcpyHostToDevice, h->stream));
+        GPSMI_HIP(hipMemsetAsync(h->d_cr.p, 0, nres * sizeof(CancelRes), h->stream));
+        GPSMI_HIP(hipStreamSynchronize(h->stream));      // (the table is pageable)
+    }
+    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
+    // step 0: the input decoded or copied to where it is worked on
+    if (u8) {
+        const size_t blocks = (n + 255) / 256;
+        hipLaunchKernelGGL(cancel_decode_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0,
+                           h->stream, static_cast<const uint16_t*>(d_in), n, d_y);
+    } else if (!in_place) {
+        GPSMI_HIP(hipMemcpyAsync(d_y, d_in, out_bytes, hipMemcpyDeviceToDevice, h->stream));
+    }
+    // one launch per satellite, in the order given, each on the output of the one before: a
+    // launch's workgroups own disjoint windows, the stream orders the launches
+    for (int s = 0; s < nsat; ++s) {
+        const int nw = pl.first[s + 1] - pl.first[s];
+        hipLaunchKernelGGL(cancel_kernel, dim3(nw), dim3(256), 0, h->stream, d_y,
+                           h->d_rep_time.p + (size_t)sats[s].prn * pl.cs, h->d_cw.p + pl.first[s], pl.inc[s], pl.cs,
+                           pl.min_window, h->d_cr.p + (size_t)s * mw);
+    }
+    GPSMI_HIP(hipGetLastError());
+    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
+    if (on_host)
+        GPSMI_HIP(hipMemcpyAsync(out_c64, d_y, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (nres)
+        GPSMI_HIP(hipMemcpyAsync(res.data(), h->d_cr.p, nres * sizeof(CancelRes), hipMemcpyDeviceToHost, h->stream));
+    h->pending = true;
+    if ((rc = gpsmi_acq_wait(h))) return rc;
+    // the windows' figures, added in window order
+    for (int s = 0; s < nsat; ++s) {
+        const int nw = pl.first[s + 1] - pl.first[s];
+        gpsmi_cancel_out o = {sats[s].prn, nw, 0, 0, 0.0, 0.0};
+        for (int w = 0; w < mw; ++w) {
+            const CancelRes& r = res[(size_t)s * mw + w];
+            if (w < nw && !r.done) ++o.n_skipped;
+            if (w < nw && r.done) { o.energy_in += r.e_in; o.energy_removed += r.e_rem; }
+            if (coef) std::memcpy(coef + ((size_t)s * mw + w) * 6, r.c, sizeof(r.c));
+        }
+        out[s] = o;
+    }
+    return GPSMI_OK;
+}
+
+int gpsmi_acq_cancel(gpsmi_acq* h, const void* iq, size_t n, const gpsmi_cancel_sat* sats, int nsat,
+                     const gpsmi_cancel_cfg* cfg, float* out_c64, gpsmi_cancel_out* out, float* coef) {
+    return acq_cancel_impl(h, iq, true, n, sats, nsat, cfg, out_c64, out, coef);
+}
+
+int gpsmi_acq_cancel_dev(gpsmi_acq* h, const void* d_iq, size_t n, const gpsmi_cancel_sat* sats, int nsat,
+                         const gpsmi_cancel_cfg* cfg, void* d_out_c64, gpsmi_cancel_out* out, float* coef) {
+    return acq_cancel_impl(h, d_iq, false, n, sats, nsat, cfg, d_out_c64, out, coef);
+}
+
+int gpsmi_acq_cancel_plan(int code_samples, size_t n, const gpsmi_cancel_sat* sats, int nsat,
+                          const gpsmi_cancel_cfg* cfg, int* max_windows) {
+    CancelPlan pl;
+    const int rc = cancel_plan(code_samples, n, sats, nsat, cfg, &pl);
+    if (rc == GPSMI_OK && max_windows) *max_windows = pl.max_windows;
+    return rc;
 }
 
 int gpsmi_acq_set_input_format(gpsmi_acq* h, int fmt) {

@@ -141,6 +141,9 @@ int gpsmi_abi_sizeof(int which) {
         case 10: return (int)sizeof(gpsmi_wtrk_cfg);
         case 11: return (int)sizeof(gpsmi_wtrk_state);
         case 12: return (int)sizeof(gpsmi_wtrk_bit);
+        case 13: return (int)sizeof(gpsmi_cancel_sat);
+        case 14: return (int)sizeof(gpsmi_cancel_cfg);
+        case 15: return (int)sizeof(gpsmi_cancel_out);
         default: return -1;
     }
 }

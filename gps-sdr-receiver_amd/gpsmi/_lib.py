@@ -56,6 +56,20 @@ class WtrkCfg(C.Structure):
                 ('reserved', C.c_int32)]
 
 
+class CancelSat(C.Structure):
+    _fields_ = [('prn', C.c_int32), ('reserved', C.c_int32), ('f_hz', C.c_double), ('tau', C.c_double)]
+
+
+class CancelOut(C.Structure):
+    _fields_ = [('prn', C.c_int32), ('n_windows', C.c_int32), ('n_skipped', C.c_int32),
+                ('reserved', C.c_int32), ('energy_in', C.c_double), ('energy_removed', C.c_double)]
+
+
+class CancelCfg(C.Structure):
+    _fields_ = [('carrier_hz', C.c_double), ('f_offset_hz', C.c_double), ('min_window', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
 class Cfg(C.Structure):
     _fields_ = [('code_samples', C.c_int32), ('n_cyc', C.c_int32),
                 ('corr_avg', C.c_int32), ('sweep_corr_avg', C.c_int32),
@@ -74,6 +88,13 @@ REFINE_OUT_DTYPE = np.dtype([
     ('f_hz', np.float64), ('code_phase', np.float64),
     ('peak', np.float32), ('median', np.float32), ('ratio', np.float32), ('mu', np.float32),
     ('cn0_dbhz', np.float32), ('tap_metric', np.float32, (3,))])
+
+CANCEL_SAT_DTYPE = np.dtype([('prn', np.int32), ('reserved', np.int32), ('f_hz', np.float64),
+                             ('tau', np.float64)])
+
+CANCEL_OUT_DTYPE = np.dtype([('prn', np.int32), ('n_windows', np.int32), ('n_skipped', np.int32),
+                             ('reserved', np.int32), ('energy_in', np.float64),
+                             ('energy_removed', np.float64)])
 
 WTRK_RING = 50                # GPSMI_WTRK_RING
 WTRK_DATA_END = 1             # GPSMI_WTRK_DATA_END
@@ -127,6 +148,7 @@ EXPORTS = [
     'gpsmi_acq_search_deep', 'gpsmi_acq_search_deep_dev',
     'gpsmi_acq_refine', 'gpsmi_acq_refine_dev', 'gpsmi_acq_refine_plan',
     'gpsmi_acq_track', 'gpsmi_acq_track_dev', 'gpsmi_acq_track_plan', 'gpsmi_wtrk_open',
+    'gpsmi_acq_cancel', 'gpsmi_acq_cancel_dev', 'gpsmi_acq_cancel_plan',
     'gpsmi_acq_last_ms',
     'gpsmi_trk_create', 'gpsmi_trk_destroy', 'gpsmi_trk_set_replica',
     'gpsmi_trk_open', 'gpsmi_trk_close', 'gpsmi_trk_get_state',
@@ -209,6 +231,9 @@ def load():
         'gpsmi_acq_track_dev': [vp, vp, sz, vp, C.c_int, P(WtrkCfg), vp],
         'gpsmi_acq_track_plan': [C.c_int, sz, vp, C.c_int, P(WtrkCfg)],
         'gpsmi_wtrk_open': [vp, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_double, vp],
+        'gpsmi_acq_cancel': [vp, vp, sz, vp, C.c_int, P(CancelCfg), vp, vp, vp],
+        'gpsmi_acq_cancel_dev': [vp, vp, sz, vp, C.c_int, P(CancelCfg), vp, vp, vp],
+        'gpsmi_acq_cancel_plan': [C.c_int, sz, vp, C.c_int, P(CancelCfg), P(C.c_int)],
         'gpsmi_acq_last_ms': [vp, P(f32)],
         'gpsmi_trk_create': [P(Cfg), C.c_int, P(vp)],
         'gpsmi_trk_destroy': [vp],
@@ -288,6 +313,8 @@ def load():
     got += [lib.gpsmi_abi_sizeof(i) for i in (7, 8, 9)]
     want += [C.sizeof(WtrkCfg), WTRK_STATE_DTYPE.itemsize, WTRK_BIT_DTYPE.itemsize]
     got += [lib.gpsmi_abi_sizeof(i) for i in (10, 11, 12)]
+    want += [CANCEL_SAT_DTYPE.itemsize, C.sizeof(CancelCfg), CANCEL_OUT_DTYPE.itemsize]
+    got += [lib.gpsmi_abi_sizeof(i) for i in (13, 14, 15)]
     if want != got:
         raise EngineError(f'ABI mismatch between gpsmi/_lib.py {want} and '
                           f'libgpsmi.so {got}')

@@ -154,6 +154,19 @@ class Acquisition:
         return self.engine.track_weak(data, states, n_bits, first_sample=first_sample,
                                       f_offset=f_offset, **cfg)
 
+    def cancelHits(self, data, rec, f_offset=0.0, out=None):
+        """Takes the satellites of `rec` out of `data` (AcqEngine.cancel): records
+        of refineHits (code_phase is the code start at the first sample) or snapshot.MEAS_DTYPE
+        records (a code start lies at sample + code_phase), the strongest (cn0_dbhz) first.
+        `data` and `out` as in AcqEngine.cancel.  Returns (out, records CANCEL_OUT_DTYPE in the
+        order cancelled)."""
+        rec = np.atleast_1d(np.asarray(rec))
+        order = np.argsort(-np.nan_to_num(rec['cn0_dbhz'].astype(np.float64), nan=-np.inf), kind='stable')
+        start = rec['sample'].astype(np.float64) if 'sample' in rec.dtype.names else 0.0
+        tau = start + rec['code_phase'].astype(np.float64)
+        sats = [(int(rec['prn'][i]), float(rec['f_hz'][i]), float(tau[i])) for i in order]
+        return self.engine.cancel(data, sats, out=out, f_offset=f_offset)
+
     def search_table(self, data, prns, freqs, n_avg):
         """The whole surface, no pruning (BASELINE configs 2 and 4)."""
         return self.engine.search(data, prns, freqs, n_avg)

@@ -7,8 +7,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib, codes
-from ._lib import (EngineError, OUT_DTYPE, PEAK_DTYPE, REFINE_HIT_DTYPE,  # noqa: F401
-                   REFINE_OUT_DTYPE, STATE_DTYPE, WTRK_BIT_DTYPE, WTRK_STATE_DTYPE, check, ptr)
+from ._lib import (CANCEL_OUT_DTYPE, CANCEL_SAT_DTYPE, EngineError, OUT_DTYPE, PEAK_DTYPE,  # noqa: F401
+                   REFINE_HIT_DTYPE, REFINE_OUT_DTYPE, STATE_DTYPE, WTRK_BIT_DTYPE, WTRK_STATE_DTYPE, check, ptr)
 
 
 @dataclass
@@ -334,6 +334,48 @@ class AcqEngine:
         check(fn(self.h, d_iq, n, ptr(st), len(st), C.byref(cfg), ptr(bits)),
               'gpsmi_acq_track' if host else 'gpsmi_acq_track_dev')
         return bits, st
+
+    def cancel(self, data, sats, out=None, f_offset=0.0, coef=False, carrier_hz=L1_HZ, min_window=0):
+        """Cancellation of strong satellites (gpsmi_acq_cancel): every satellite
+        of `sats` -- (prn, f_hz, tau) with the Doppler to a few Hz and tau any of its code starts in
+        samples from the first sample, to half a sample -- is projected out of the samples code
+        period by code period, in the order given (the strongest first).  data: a host array in
+        the input format, or a (device pointer, n) pair.  out: where the complex64 result goes --
+        host data: an optional complex64 array [n]; device data: a device pointer to complex64
+        [n], None = in place (complex64 input only).  Returns (out, records CANCEL_OUT_DTYPE
+        [nsat]), and with coef=True the windows' coefficients complex64 [nsat, max_windows, 3]
+        behind them."""
+        s_a = np.zeros(len(sats), dtype=CANCEL_SAT_DTYPE)
+        for i, (prn, f_hz, tau) in enumerate(sats):
+            s_a[i] = (int(prn), 0, float(f_hz), float(tau))
+        self._need_time_replicas(s_a['prn'])
+        cfg = _lib.CancelCfg(float(carrier_hz), float(f_offset), int(min_window), 0)
+        host = not isinstance(data, tuple)
+        if host:
+            data = self._host_iq(data)
+            d_iq, n = ptr(data), data.size
+        else:
+            d_iq, n = data
+        max_w = C.c_int(0)
+        check(self.lib.gpsmi_acq_cancel_plan(self.cfg.code_samples, n, ptr(s_a), len(s_a), C.byref(cfg),
+                                             C.byref(max_w)), 'gpsmi_acq_cancel_plan')
+        rec = np.zeros(len(s_a), dtype=CANCEL_OUT_DTYPE)
+        co = np.zeros((len(s_a), max_w.value, 3), np.complex64) if coef else None
+        if host:
+            if out is None:
+                out = np.empty(n, np.complex64)
+            if out.dtype != np.complex64 or out.size != n or not out.flags['C_CONTIGUOUS']:
+                raise TypeError('out must be a C-contiguous complex64 array of the length of data')
+            check(self.lib.gpsmi_acq_cancel(self.h, d_iq, n, ptr(s_a), len(s_a), C.byref(cfg), ptr(out), ptr(rec),
+                                            ptr(co)), 'gpsmi_acq_cancel')
+        else:
+            if out is None:
+                if self.raw_u8:
+                    raise ValueError('raw input cannot be cancelled in place: pass a complex64 device buffer')
+                out = d_iq
+            check(self.lib.gpsmi_acq_cancel_dev(self.h, d_iq, n, ptr(s_a), len(s_a), C.byref(cfg), out, ptr(rec),
+                                                ptr(co)), 'gpsmi_acq_cancel_dev')
+        return (out, rec, co) if coef else (out, rec)
 
     def search_async(self, d_iq, n, prns, freqs, n_avg, out, out_dev=None):
         """Enqueue a search on device-resident iq; `out` is a pinned PEAK_DTYPE

@@ -334,7 +334,33 @@ def min_samples(cs):
     return 42 * cs + (1 if cs == 2048 else 8)
 
 
-def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, **cfg):
+CANCEL_DBHZ = 40.0                       # measure(cancel=True): what counts as a strong satellite
+
+
+def _measure_pass(acq, dev, n, prns, freqs, n_coh, n_seg, corr_min, f_offset, st):
+    """Deep search, refinement and the records that count, on device-resident data.
+    -> (rec, found, records), all empty when nothing is found."""
+    from .pipeline import largest_peak_hits, refine_centred
+    cs = acq.cfg.code_samples
+    found = largest_peak_hits(acq, (dev[0], n_seg * n_coh * cs), prns, freqs, n_coh, n_seg, f_offset=f_offset,
+                              corr_min=corr_min)
+    st['device_ms'] += acq.engine.last_ms()
+    if not found:
+        return None, [], np.zeros(0, MEAS_DTYPE)
+    found, rec, ms = refine_centred(acq, dev, found, f_offset=f_offset)
+    st['device_ms'] += ms
+    st['found'], st['refined'] = st['found'] + found, rec if st['refined'] is None else np.concatenate([st['refined'], rec])
+    return refined_records(rec, found, cs, f_offset)
+
+
+def _track_records(acq, dev, rec, out, n, f_offset, track_cfg, st):
+    if len(rec):
+        bits, states = acq.trackHits(dev, rec, f_offset=f_offset, **track_cfg)
+        st['device_ms'] += acq.engine.last_ms()
+        tracked_records(out, bits, states['bit_no'], n, acq.cfg.code_samples, track_cfg.get('pull_in_bits', 0))
+
+
+def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=None, **cfg):
     """The satellites of one snapshot: MEAS_DTYPE records, one per satellite found, sorted by PRN.
 
     `acq`: an acquisition.Acquisition; `data`: the samples in its input format (complex64, or the
@@ -349,10 +375,16 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, **cfg):
     data, the code starts of the bits behind pull-in fitted by a line and read at the middle bit,
     `sample` there; a channel that leaves fewer than TRACK_MIN_BITS such bits keeps its refinement
     values.  source None: DEFAULT_SOURCE where it applies.  `track_cfg`: trackHits' keywords.
-    `stats`: a dict that receives device_ms (the sum of the engine's last_ms), found and refined."""
+    `cancel`: None or False -- the stages above, once.  A C/N0 in dB-Hz (True:
+    CANCEL_DBHZ) -- the records of that first pass at or above it are kept, their satellites are
+    cancelled into a complex64 device copy (Acquisition.cancelHits), and the stages run again on
+    the copy for every other PRN: the ghost rule of that second pass sees its own records only (the
+    cancelled satellites cast no ghosts any more), and with source 'track' the kept records are
+    tracked on the data as it came, the others on the copy.
+    `stats`: a dict that receives device_ms (the sum of the engine's last_ms over every stage),
+    found and refined (of both passes) and, with `cancel`, cancelled (the CANCEL_OUT_DTYPE records)."""
     from .acquisition import SAT_ALL
-    from .engine import DeviceBuffer
-    from .pipeline import largest_peak_hits, refine_centred
+    from .engine import CANCEL_OUT_DTYPE, DeviceBuffer
     c = acq.cfg
     cs = c.code_samples
     n_coh = int(cfg.pop('n_coh', 4))
@@ -373,42 +405,63 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, **cfg):
     source = source or (DEFAULT_SOURCE if can_track else 'refine')
     if source not in ('refine', 'track') or (source == 'track' and not can_track):
         raise ValueError(f"source {source!r}: 'refine' or 'track', the latter from {TRACK_MIN_SECONDS} s on")
-    buf, dev = None, data
+    cancel_dbhz = None if cancel is None or cancel is False else CANCEL_DBHZ if cancel is True else float(cancel)
+    buf, clean, dev = None, None, data
     if host is not None:
         buf = DeviceBuffer(host.nbytes, c.device)
     try:
         if buf is not None:
             buf.upload(host)
             dev = (buf.ptr, n)
-        out = np.zeros(0, MEAS_DTYPE)
         st = {'device_ms': 0.0, 'found': [], 'refined': None}
-        found = largest_peak_hits(acq, (dev[0], n_seg * n_coh * cs), prns, freqs, n_coh, n_seg, f_offset=f_offset,
-                                  corr_min=corr_min)
-        st['device_ms'] += acq.engine.last_ms()
-        if found:
-            found, rec, ms = refine_centred(acq, dev, found, f_offset=f_offset)
-            st['device_ms'] += ms
-            st['found'], st['refined'] = found, rec
-            rec, found, out = refined_records(rec, found, cs, f_offset)
-            if source == 'track' and len(rec):
-                bits, states = acq.trackHits(dev, rec, f_offset=f_offset, **track_cfg)
-                st['device_ms'] += acq.engine.last_ms()
-                tracked_records(out, bits, states['bit_no'], n, cs, track_cfg.get('pull_in_bits', 0))
-            out = out[np.argsort(out['prn'], kind='stable')]
+        rec, found, out = _measure_pass(acq, dev, n, prns, freqs, n_coh, n_seg, corr_min, f_offset, st)
+        if cancel_dbhz is not None:
+            st['cancelled'] = np.zeros(0, CANCEL_OUT_DTYPE)
+            strong = out['cn0_dbhz'] >= cancel_dbhz                   # (NaN: no)
+        if cancel_dbhz is None or not strong.any():
+            if source == 'track' and len(out):
+                _track_records(acq, dev, rec, out, n, f_offset, track_cfg, st)
+        else:
+            rec, out = rec[strong], out[strong]
+            if source == 'track':
+                _track_records(acq, dev, rec, out, n, f_offset, track_cfg, st)
+            clean = DeviceBuffer(8 * n, c.device)
+            _, st['cancelled'] = acq.cancelHits(dev, rec, f_offset=f_offset, out=clean.ptr)
+            st['device_ms'] += acq.engine.last_ms()
+            kept = set(out['prn'].tolist())
+            rest = [p for p in prns if p not in kept]
+            was_raw = acq.engine.raw_u8
+            rec2, out2 = None, np.zeros(0, MEAS_DTYPE)
+            try:                                     # the copy is complex64 whatever the data is
+                if was_raw:
+                    acq.engine.set_input_format(False)
+                dev2 = (clean.ptr, n)
+                if rest:
+                    rec2, _, out2 = _measure_pass(acq, dev2, n, rest, freqs, n_coh, n_seg, corr_min, f_offset, st)
+                if source == 'track' and len(out2):
+                    _track_records(acq, dev2, rec2, out2, n, f_offset, track_cfg, st)
+            finally:
+                if was_raw:
+                    acq.engine.set_input_format(True)
+            out = np.concatenate([out, out2])
+        out = out[np.argsort(out['prn'], kind='stable')]
         if stats is not None:
             stats.update(st)
         return out
     finally:
         if buf is not None:
             buf.free()
+        if clean is not None:
+            clean.free()
 
 
-def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, **cfg):
+def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, cancel=None, stats=None, **cfg):
     """measure -> (doppler_fix when `pos` is None) -> coarse_time_fix.  `t_gps`: the GPS seconds
-    of week of the first sample as far as known.  -> (Fix, measurements, device ms).  The Fix's
-    t_gps is that of its `sample`."""
-    stats = {}
-    meas = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats, **cfg)
+    of week of the first sample as far as known; `cancel`, `stats`: measure's.  -> (Fix,
+    measurements, device ms).  The Fix's t_gps is that of its `sample`."""
+    stats = {} if stats is None else stats
+    meas = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats, cancel=cancel,
+                   **cfg)
     ms = stats.get('device_ms', 0.0)
     if len(meas) < MIN_SAT:
         return Fix(reason=f'{len(meas)} satellites measured, {MIN_SAT} needed'), meas, ms

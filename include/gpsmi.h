@@ -449,6 +449,70 @@ int gpsmi_acq_track_plan(int code_samples, size_t n, const gpsmi_wtrk_state* sta
  * without a code phase (-1).                                                                    */
 int gpsmi_wtrk_open(const gpsmi_refine_out* rec, int code_samples, int refine_tap_samples,
                     int64_t data_start, double carrier_hz, double f_offset_hz, gpsmi_wtrk_state* st);
+/* Cancellation of strong satellites ahead of the weak searches (float64 restatement:
+ * tests/cancel_ref.py): what removes the near-far problem from the samples themselves.  Each satellite
+ * (prn, f_hz as gpsmi_refine_out.f_hz, tau = any of its code starts in samples from iq[0], float64) is
+ * projected out code period by code period; data bits, carrier phase and amplitude are absorbed per
+ * period, so there is no loop and nothing is remembered.  cs = code_samples, fs = 1000 cs.
+ * Windows.  Tc = cs / (1 + (f_hz - f_offset_hz) / carrier_hz) as in gpsmi_acq_track; window k holds the
+ * samples ceil(tau + k Tc) <= i < ceil(tau + (k + 1) Tc) cut to [0, n) (float64, unfused, on the host),
+ * for every k that leaves one: the first and the last are partial, the others have cs - 1 .. cs + 1.
+ * Basis.  With j = rint(tau + k Tc) (ties to even) and R = GPSCacode(prn) (gpsmi_acq_set_replica_time)
+ *     b_d[i] = R[(i - j - d) mod cs] exp(+j 2 pi f_hz (i + 1) / fs),    d = -1, 0, +1
+ * (the i + 1 is SEC_TIME's; the phase is the integer (i + 1) * (f_hz / fs in 0.64 fixed point) mod
+ * 2^64, exact at any index, its top 24 bits give sine and cosine as in gpsmi_acq_refine).  Three
+ * whole-sample shifts span every code phase within half a sample of the estimate (exactly for a
+ * linearly interpolated replica; a short channel estimate otherwise).
+ * Projection.  G = B^H B (real, symmetric: six float32 sums), p = B^H x (three complex float32 sums),
+ * each sum in one fixed order; G c = p is solved in float64 (L D L^T, no permutation) and the window
+ * becomes x - B c in float32.  A window of fewer than min_window samples, or one whose smallest pivot
+ * is below 1e-6 trace(G), passes through bit for bit and is counted in n_skipped.
+ * Satellites are cancelled one after another in the order given (pass the strongest first), each on
+ * the output of the one before.  nsat 0 .. 32; nsat = 0 only decodes or copies.
+ * iq: n samples in the handle's input format, host memory for gpsmi_acq_cancel, device memory for
+ * gpsmi_acq_cancel_dev.  The output is complex64 [n] (host / device alike); GPSMI_IQ_U8 input is first
+ * decoded with gpsmi_dev_unpack_u8iq's arithmetic, complex64 input is copied -- or, for
+ * gpsmi_acq_cancel_dev with d_out_c64 == d_iq, cancelled in place.  Input and output that overlap
+ * without being that one complex64 buffer are refused.  Samples outside the processed windows are
+ * the decoded / copied input, bit for bit.
+ * out [nsat]: energy_in = sum |x|^2 over the processed windows (as the satellite met them),
+ * energy_removed = sum c^H G c; the windows' float64 figures are added in window order on the host.
+ * coef: optional host array complex64 [nsat][max_windows][3] (taps d = -1, 0, +1; max_windows from
+ * gpsmi_acq_cancel_plan), zeros for skipped windows and past a satellite's last one.
+ * The same arguments give the same bytes, from either entry point.  Argument errors are GPSMI_E_ARG
+ * and need no GPU (gpsmi_acq_cancel_plan makes the same checks without a handle): nsat, a PRN outside
+ * 1 .. 37 or given twice, f_hz or tau not finite, |f_hz| >= fs / 2, (f_hz - f_offset_hz) beyond 1 % of
+ * carrier_hz, n outside 1 .. 2^40.  code_samples 2048 and 16368 only (GPSMI_E_UNSUPPORTED);
+ * GPSMI_E_STATE: no time-domain replica for a PRN; GPSMI_E_NOMEM leaves the handle usable.  cfg may be
+ * null (all defaults).  The call returns when the work is done; gpsmi_acq_last_ms reports it.     */
+typedef struct gpsmi_cancel_sat {   /* no implicit padding: 24 bytes */
+    int32_t prn;
+    int32_t reserved;               /* 0 */
+    double  f_hz;
+    double  tau;                    /* a code start, samples from iq[0]; any sign */
+} gpsmi_cancel_sat;
+typedef struct gpsmi_cancel_cfg {   /* no implicit padding: 24 bytes; 0 = the default */
+    double  carrier_hz;             /* 0: 1575.42e6 */
+    double  f_offset_hz;            /* as in gpsmi_acq_search_deep; finite */
+    int32_t min_window;             /* 0: 16 */
+    int32_t reserved;               /* 0 */
+} gpsmi_cancel_cfg;
+typedef struct gpsmi_cancel_out {   /* no implicit padding: 32 bytes */
+    int32_t prn;
+    int32_t n_windows;              /* windows that hold a sample of iq */
+    int32_t n_skipped;              /* ... of which passed through */
+    int32_t reserved;               /* 0 */
+    double  energy_in;
+    double  energy_removed;
+} gpsmi_cancel_out;
+int gpsmi_acq_cancel(gpsmi_acq* h, const void* iq, size_t n, const gpsmi_cancel_sat* sats, int nsat,
+                     const gpsmi_cancel_cfg* cfg, float* out_c64, gpsmi_cancel_out* out, float* coef);
+int gpsmi_acq_cancel_dev(gpsmi_acq* h, const void* d_iq, size_t n, const gpsmi_cancel_sat* sats, int nsat,
+                         const gpsmi_cancel_cfg* cfg, void* d_out_c64, gpsmi_cancel_out* out, float* coef);
+/* host only, no GPU: the argument checks of gpsmi_acq_cancel for a handle of code_samples, and the
+ * largest number of windows of any satellite (max_windows, optional) the coef array is sized by  */
+int gpsmi_acq_cancel_plan(int code_samples, size_t n, const gpsmi_cancel_sat* sats, int nsat,
+                          const gpsmi_cancel_cfg* cfg, int* max_windows);
 /* Input format of the iq pointers of the search calls that follow (host or device), as
  * gpsmi_trk_set_input_format below: GPSMI_IQ_U8 = the raw recording of streamData
  * (gpsrecv.py:162-173), decoded where the carrier wipe-off reads it; same bits out.   */

@@ -6,7 +6,7 @@ gpseval) as one command on the GPU path.
     python tools/run_file.py <recording.bin> [--seconds S] [--start-stream K] [--save-pickle P]
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--blank] [--json]
                              [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track [--weak-fix]]]]
-                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]]]
+                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]]]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -55,7 +55,10 @@ position solved from the code phases without a decoded subframe.  It needs --tim
 sample read, within 30 s: GPS seconds of week, or a UTC timestamp (2024-05-01T12:00:00) converted with the
 leap seconds of position.LEAPSEC and the ephemerides' week; --near LAT,LON[,H] is the position as far as
 known (within 50 km), without it the Dopplers give one.  It prints the measurements, the fix and the
-device time; with --json one line with a 'snapshot' key.
+device time; with --json one line with a 'snapshot' key.  --cancel [DBHZ] (with --snapshot only): the
+satellites measured at or above DBHZ (default 40 dB-Hz) are cancelled from the samples and the others
+measured on what is left; the report gains a 'cancelled' list.  Without the flag every
+output is as before.
 
 There is no recording in this repository (data/test.bin is absent from the reference
 checkout, SURVEY F2, and too short for a fix even upstream): tests/test_run_file.py writes a
@@ -248,9 +251,10 @@ def parse_time(text, ephs):
 
 
 def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, frontend=None, excise=False,
-             blank=False):
+             blank=False, cancel=None):
     """--snapshot: gpsmi.snapshot.snapshot_fix on the first `seconds` behind `start_stream`, read
-    and filtered block by block as run() feeds its receiver."""
+    and filtered block by block as run() feeds its receiver.  `cancel`: --cancel's C/N0 threshold
+    (snapshot.measure's `cancel`); None leaves everything as it is without the flag."""
     from gpsmi import ingest, position as P, snapshot as S
     from gpsmi.acquisition import Acquisition
     from gpsmi.conditioning import Conditioner
@@ -265,8 +269,10 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
                 sys.exit(f'--snapshot: the recording holds {have} samples after stream {start_stream}, {seconds} s need {need}')
             acq = Acquisition(cfg, raw_u8=cond.out_raw_u8)
             t0 = time.perf_counter()
+            stats = {}
             fix, meas, ms = S.snapshot_fix(acq, np.concatenate(blocks)[:need], ephemerides, t_gps,
-                                           pos=None if near is None else np.array(P.geo_to_ecef(*near)))
+                                           pos=None if near is None else np.array(P.geo_to_ecef(*near)),
+                                           cancel=cancel, stats=stats)
             wall = time.perf_counter() - t0
         finally:
             cond.close()
@@ -278,6 +284,10 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
                              'cn0_dbhz': None if np.isnan(m['cn0_dbhz']) else round(float(m['cn0_dbhz']), 2),
                              'source': m['source'].decode()} for m in meas],
            'ok': bool(fix.ok), 'reason': fix.reason, 'satellites': fix.prns, 'dropped': fix.dropped}
+    if cancel is not None:
+        out['cancelled'] = [{'prn': int(r['prn']), 'n_windows': int(r['n_windows']), 'n_skipped': int(r['n_skipped']),
+                             'removed': round(float(r['energy_removed'] / r['energy_in']), 5) if r['energy_in'] > 0 else 0.0}
+                            for r in stats.get('cancelled', [])]
     if fix.ok:
         geo = P.ecef_to_geo(fix.ecef)                # (None next to the Earth's centre)
         out['position'] = {'lat_deg': None if geo is None else round(float(geo[0]), 6),
@@ -294,6 +304,9 @@ def print_snapshot(out):
     s = out['snapshot']
     print(f"{out['file']}: snapshot of {s['seconds']} s, {len(s['measurements'])} satellites measured "
           f"({s['device_ms']} ms on the device)")
+    for r in s.get('cancelled', []):
+        print(f"  cancelled PRN {r['prn']:2d}: {r['removed']:.4f} of the power in {r['n_windows']} code periods "
+              f"({r['n_skipped']} skipped)")
     for m in s['measurements']:
         cn0 = 'n/a' if m['cn0_dbhz'] is None else f"{m['cn0_dbhz']:.1f}"
         print(f"  PRN {m['prn']:2d}  sample {m['sample']:8d}  code_phase {m['code_phase']:9.4f}  f_hz {m['f_hz']:+9.2f}  "
@@ -419,6 +432,9 @@ def main():
                     help='write the ephemerides the run decoded, in the format --ephemeris reads')
     ap.add_argument('--snapshot', type=float, default=None, metavar='SECONDS',
                     help='a fix from the first SECONDS alone, no decoded subframe (DESIGN.md 4.2i); needs --ephemeris and --time')
+    ap.add_argument('--cancel', type=float, nargs='?', const=40.0, default=None, metavar='DBHZ',
+                    help='with --snapshot: cancel the satellites measured at or above DBHZ (default 40) and measure '
+                         'the others on what is left (DESIGN.md 4.2j)')
     ap.add_argument('--time', default=None,
                     help='with --snapshot: time of the first sample read, GPS seconds of week or a UTC timestamp, within 30 s')
     ap.add_argument('--near', default=None, metavar='LAT,LON[,H]',
@@ -448,7 +464,7 @@ def main():
                 ap.error('--near LAT,LON[,H]')
             near = (near + [0.0])[:3]
         out = snapshot(a.recording, a.snapshot, eph, parse_time(a.time, eph), near, a.start_stream, frontend,
-                       a.excise, a.blank)
+                       a.excise, a.blank, a.cancel)
         if a.json:
             print(json.dumps(out))
         else:
@@ -456,6 +472,8 @@ def main():
         return
     if a.time is not None or a.near is not None:
         ap.error('--time / --near need --snapshot SECONDS')
+    if a.cancel is not None:
+        ap.error('--cancel needs --snapshot SECONDS')
     out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise,
               frontend, a.blank, a.deep_acq, a.refine, a.track, a.weak_fix, a.save_ephemeris)
     if a.json:
