@@ -11,6 +11,8 @@
 //   gpsmi_wtrk.h          bit-synchronous tracking of refined hits (gpsmi_acq_track)
 //   gpsmi_cancel.h        cancellation of strong satellites ahead of the weak searches
 //                         (gpsmi_acq_cancel): per-period projection, in place
+//   gpsmi_collective.h    collective detection over the surfaces of a deep search
+//                         (gpsmi_acq_collective)
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -24,6 +26,7 @@
 #include "gpsmi_refine.h"
 #include "gpsmi_wtrk.h"
 #include "gpsmi_cancel.h"
+#include "gpsmi_collective.h"
 #include "gpsmi_acq_search.h"
 
 using namespace gpsmi;
@@ -75,6 +78,11 @@ struct gpsmi_acq {
     DevBuf<float2> d_cx;
     DevBuf<CancelWin> d_cw;
     DevBuf<CancelRes> d_cr;
+    // collective detection (gpsmi_acq_collective): the normalised rows and the pooled ones, the
+    // satellites of a call, its cell map
+    DevBuf<float> d_cz;
+    DevBuf<gpsmi_collective_sat> d_csat;          // [kColMaxSats]
+    DevBuf<gpsmi_collective_cell> d_cc;
     int iq_fmt = GPSMI_IQ_C64;              // what the iq pointers of the search calls point to
     // bytes of `n` samples in the handle's input format
     size_t iq_bytes(size_t n) const { return n * (iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)); }
@@ -257,6 +265,7 @@ struct AcqSearch {
     const DeepShift* deep;
     bool wait;                               // false: the caller collects the table with gpsmi_acq_wait
     bool segmented;
+    float* rows = nullptr;                   // deep only: where the surfaces go, [nsv][nbins][cs] on the device
 };
 
 // The arguments of every search entry point, before anything is uploaded or enqueued.  on_host: iq
@@ -305,7 +314,7 @@ static int acq_check_search(const gpsmi_acq* h, const void* iq, bool on_host, si
 // the correlation with its statistics into lc.d_stats.  The coherent search is b0 = 0, nb = nbins,
 // n_seg = 1, and the only one with the time-domain correlations.
 static void acq_direct_chunk(gpsmi_acq* h, const void* d_iq, const AcqSearch& s, float2* x, int b0, int nb,
-                             int nsv) {
+                             int nsv, int nbins) {
     const int cs = h->cfg.code_samples, c0 = b0 * nsv, ncell = nb * nsv;
     LongCorr& lc = h->lc;
     with_fmt(h->iq_fmt, [&](auto fmt) {
@@ -316,8 +325,10 @@ static void acq_direct_chunk(gpsmi_acq* h, const void* d_iq, const AcqSearch& s,
                        lc.d_xsel.p + c0, lc.d_rsel.p + c0, h->d_slot.p, nsv, ncell);
     if (!s.segmented) lc.correlate<0>(h->stream, x, c0, ncell, h->d_rep_time.p, h->d_tw.p);
     else if (!s.deep) lc.correlate<2>(h->stream, x, c0, ncell, h->d_rep_time.p, h->d_tw.p, s.n_seg);
-    else lc.correlate<3>(h->stream, x, c0, ncell, h->d_rep_time.p, h->d_tw.p, s.n_seg,
-                         h->d_shift.p + (size_t)b0 * s.n_seg);
+    else if (!s.rows) lc.correlate<3>(h->stream, x, c0, ncell, h->d_rep_time.p, h->d_tw.p, s.n_seg,
+                                      h->d_shift.p + (size_t)b0 * s.n_seg);
+    else lc.correlate<4>(h->stream, x, c0, ncell, h->d_rep_time.p, h->d_tw.p, s.n_seg,
+                         h->d_shift.p + (size_t)b0 * s.n_seg, PfaRows{s.rows, nsv, nbins, b0});
 }
 
 // Every search, on device-resident iq whose arguments acq_check_search has passed.
@@ -325,7 +336,12 @@ static int acq_search_run(gpsmi_acq* h, const void* d_iq, const int32_t* prn, in
                           int nbins, AcqSearch s, gpsmi_peak* out, void* out_dev, float* nbr) {
     // one segment of the 16368 path: the coherent search itself (MODE 0 forms its statistics from the
     // unscaled squares; MODE 2's would differ in the last bits of std)
-    if (h->lc.pfa() && s.segmented && s.n_seg == 1) s = AcqSearch{s.n_coh, 1, nullptr, s.wait, false};
+    if (h->lc.pfa() && s.segmented && s.n_seg == 1) {
+        if (s.rows)
+            return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_search_deep_rows_dev: one segment at 16368 is the coherent "
+                                             "search, which keeps no surface (n_seg >= 2)");
+        s = AcqSearch{s.n_coh, 1, nullptr, s.wait, false};
+    }
     h->last_ms = 0.f;
     if (nsv == 0 || nbins == 0) return GPSMI_OK;            // empty search: nothing to do
     GPSMI_HIP(hipSetDevice(h->cfg.device));
@@ -369,7 +385,7 @@ static int acq_search_run(gpsmi_acq* h, const void* d_iq, const int32_t* prn, in
     for (int b0 = 0; b0 < nbins; b0 += (int)nbc) {
         const int nb = nbins - b0 < (int)nbc ? nbins - b0 : (int)nbc;
         if (h->direct) {
-            acq_direct_chunk(h, d_iq, s, x, b0, nb, nsv);
+            acq_direct_chunk(h, d_iq, s, x, b0, nb, nsv, nbins);
             continue;
         }
         // four groups of 256 threads for the long coherent integrations (acq_spectrum_kernel)
@@ -378,10 +394,10 @@ static int acq_search_run(gpsmi_acq* h, const void* d_iq, const int32_t* prn, in
             hipLaunchKernelGGL((acq_spectrum_kernel<G, decltype(fmt)::value>), dim3(nb, n_seg), dim3(256 * G), 0,
                                h->stream, d_iq, h->d_t32.p, h->d_omega.p + b0, s.n_coh, n_seg, x, h->d_tw.p);
         }); });
-        with_value<0, 2, 1>(!s.segmented ? 0 : s.deep ? 2 : 1, [&](auto mode) {
+        with_value<0, 2, 3, 1>(!s.segmented ? 0 : !s.deep ? 1 : s.rows ? 3 : 2, [&](auto mode) {
             hipLaunchKernelGGL(acq_corr_kernel<decltype(mode)::value>, dim3(nsv, nb), dim3(256), 0, h->stream, x,
                                h->d_rep.p, h->d_slot.p, h->d_peaks.p, nsv, n_seg, b0, h->d_tw.p, d_nbr,
-                               s.deep ? h->d_shift.p + (size_t)b0 * n_seg : nullptr);
+                               s.deep ? h->d_shift.p + (size_t)b0 * n_seg : nullptr, s.rows, nbins);
         });
     }
     if (h->direct)
@@ -469,6 +485,15 @@ int gpsmi_acq_search_deep_dev(gpsmi_acq* h, const void* d_iq, size_t n, const in
     const DeepShift d{carrier_hz, f_offset_hz};
     return acq_search(h, d_iq, false, n, prn, nsv, freqs_hz, nbins, {n_coh, n_seg, &d, true, true}, out, out_dev,
                       nullptr);
+}
+
+int gpsmi_acq_search_deep_rows_dev(gpsmi_acq* h, const void* d_iq, size_t n, const int32_t* prn, int nsv,
+                                   const double* freqs_hz, int nbins, int n_coh, int n_seg, double carrier_hz,
+                                   double f_offset_hz, gpsmi_peak* out, void* out_dev, void* d_rows) {
+    GPSMI_REQUIRE(d_rows, "null d_rows");
+    const DeepShift d{carrier_hz, f_offset_hz};
+    return acq_search(h, d_iq, false, n, prn, nsv, freqs_hz, nbins,
+                      {n_coh, n_seg, &d, true, true, static_cast<float*>(d_rows)}, out, out_dev, nullptr);
 }
 
 // ---- refinement of weak / deep hits (kernels and plan: gpsmi_refine.h) ------------------------
@@ -727,6 +752,55 @@ int gpsmi_acq_cancel_plan(int code_samples, size_t n, const gpsmi_cancel_sat* sa
     CancelPlan pl;
     const int rc = cancel_plan(code_samples, n, sats, nsat, cfg, &pl);
     if (rc == GPSMI_OK && max_windows) *max_windows = pl.max_windows;
+    return rc;
+}
+
+// ---- collective detection (kernels and plan: gpsmi_collective.h) ------------------------------
+int gpsmi_acq_collective_dev(gpsmi_acq* h, const void* d_rows, int nsv_rows, int nbins,
+                             const gpsmi_collective_sat* sats, int nsat, const gpsmi_collective_grid* grid,
+                             gpsmi_collective_cell* out_host, void* out_dev) {
+    GPSMI_REQUIRE(h && d_rows, "null argument");
+    GPSMI_REQUIRE(out_host || out_dev, "no output requested");
+    ColPlan pl;
+    int rc = collective_plan(h->cfg.code_samples, nsv_rows, nbins, sats, nsat, grid, &pl);
+    if (rc) return rc;
+    h->last_ms = 0.f;
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    const int cs = pl.cs;
+    const size_t nz = (size_t)nsat * cs;
+    if ((rc = h->d_cz.reserve(pl.scratch_bytes / sizeof(float), "gpsmi_acq_collective rows")) ||
+        (rc = h->d_csat.reserve(kColMaxSats, "gpsmi_acq_collective satellites")) ||
+        (rc = h->d_cc.reserve((size_t)pl.cells, "gpsmi_acq_collective cell map")))
+        return rc;
+    GPSMI_HIP(hipMemcpyAsync(h->d_csat.p, sats, (size_t)nsat * sizeof(gpsmi_collective_sat), hipMemcpyHostToDevice,
+                             h->stream));
+    GPSMI_HIP(hipStreamSynchronize(h->stream));          // (the caller's table is pageable)
+    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(collective_norm_kernel, dim3(nsat), dim3(256), 0, h->stream,
+                       static_cast<const float*>(d_rows), nbins, cs, h->d_csat.p, h->d_cz.p);
+    const float* z = h->d_cz.p;
+    if (pl.pool > 1) {
+        hipLaunchKernelGGL(collective_pool_kernel, dim3((cs + 255) / 256, nsat), dim3(256), 0, h->stream,
+                           h->d_cz.p, cs, pl.pool, h->d_cz.p + nz);
+        z = h->d_cz.p + nz;
+    }
+    hipLaunchKernelGGL(collective_kernel, dim3(pl.workgroups), dim3(256), 0, h->stream, z, h->d_csat.p, nsat, *grid,
+                       cs, (int)pl.cells, h->d_cc.p);
+    GPSMI_HIP(hipGetLastError());
+    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
+    const size_t bytes = (size_t)pl.cells * sizeof(gpsmi_collective_cell);
+    if (out_dev) GPSMI_HIP(hipMemcpyAsync(out_dev, h->d_cc.p, bytes, hipMemcpyDeviceToDevice, h->stream));
+    if (out_host) GPSMI_HIP(hipMemcpyAsync(out_host, h->d_cc.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    h->pending = true;
+    return gpsmi_acq_wait(h);
+}
+
+int gpsmi_acq_collective_plan(int code_samples, int nsv_rows, int nbins, const gpsmi_collective_sat* sats, int nsat,
+                              const gpsmi_collective_grid* grid, size_t* scratch_bytes, int* workgroups) {
+    ColPlan pl;
+    const int rc = collective_plan(code_samples, nsv_rows, nbins, sats, nsat, grid, &pl);
+    if (rc == GPSMI_OK && scratch_bytes) *scratch_bytes = pl.scratch_bytes;
+    if (rc == GPSMI_OK && workgroups) *workgroups = pl.workgroups;
     return rc;
 }
 

@@ -15,7 +15,8 @@
 //                         MODE 0: the coherent search, one segment.  MODE 1: the non-coherent search,
 //                         the mean of |corr| over the segments, summed in registers.  MODE 2: the deep
 //                         search, the same mean with every segment's magnitudes rotated by the
-//                         code-Doppler slide.
+//                         code-Doppler slide.  MODE 3: MODE 2 that also keeps the surface S of every
+//                         cell, rows [sv][nbins][2048] (gpsmi_acq_search_deep_rows_dev).
 //   acq_cells_kernel, acq_peaks_kernel
 //                         the cell tables of the time-domain and native-length correlations, and
 //                         their statistics as peak records.
@@ -125,7 +126,7 @@ __device__ __forceinline__ void acq_store_peak(gpsmi_peak* __restrict__ out, flo
 // summed in registers in ascending segment order and scaled by 1 / nseg, then the statistics once.
 // The next segment's spectrum is requested before the current one is transformed (the cells are
 // latency-bound chains).
-// MODE 2: segment s is added at the lag it had at the start of the data, S[i] += |corr_s[(i + m) mod
+// MODE 2, 3: segment s is added at the lag it had at the start of the data, S[i] += |corr_s[(i + m) mod
 // 2048]|, m = shift[bin][s] in 0 .. 2047 (the code-Doppler slide, one integer per bin and segment
 // from the host).  The magnitude a sum needs now comes from another thread: a segment's 2048
 // magnitudes go through LDS once, unscaled, in the plane the statistics use as their copy (the
@@ -139,7 +140,9 @@ template <int MODE>
 __global__ __launch_bounds__(256) void acq_corr_kernel(
     const float2* __restrict__ spectra, const float2* __restrict__ rep,
     const int* __restrict__ slot, gpsmi_peak* __restrict__ out, int nsv, int nseg, int bin0,
-    const float2* __restrict__ tw, float2* __restrict__ nbr, const int* __restrict__ shift) {
+    const float2* __restrict__ tw, float2* __restrict__ nbr, const int* __restrict__ shift,
+    float* __restrict__ rows, int nbins) {
+    constexpr bool DEEP = MODE >= 2;
     __shared__ __attribute__((aligned(16))) float lds[kFftLdsFloats];
     __shared__ __attribute__((aligned(16))) float red[kStatsRedFloats];
     __shared__ __attribute__((aligned(16))) float lds_tw[kFftTwFloats];
@@ -151,7 +154,7 @@ __global__ __launch_bounds__(256) void acq_corr_kernel(
     const FftTw ftw = fft_setup(lds_tw, tw, t);
     const float2* X = spectra + (size_t)bin * (MODE == 0 ? 1 : nseg) * kFftN;
     const float2* R = rep + (size_t)slot[sv] * kFftN;
-    const int* M = MODE == 2 ? shift + (size_t)bin * nseg : nullptr;
+    const int* M = DEEP ? shift + (size_t)bin * nseg : nullptr;
     float2 x[8], r[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
@@ -171,16 +174,16 @@ __global__ __launch_bounds__(256) void acq_corr_kernel(
             const float2* Xn = X + (size_t)(s + 1 < nseg ? s + 1 : s) * kFftN;
 #pragma unroll
             for (int q = 0; q < 8; ++q) x[q] = Xn[t + 256 * q];
-            if constexpr (MODE == 2) m = __builtin_amdgcn_readfirstlane(M[s]);
+            if constexpr (DEEP) m = __builtin_amdgcn_readfirstlane(M[s]);
         }
         // (the previous transform's last LDS reads, MODE 2 the previous segment's, are done)
-        if constexpr (MODE == 2) lds_barrier(); else __syncthreads();
+        if constexpr (DEEP) lds_barrier(); else __syncthreads();
         fft2048(v, lds, ftw, t);
         // fft(conj Y)[n] = conj(N ifft(Y)[n]): same lag index, no reversal
         float a[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) a[q] = __builtin_amdgcn_sqrtf(v[q].x * v[q].x + v[q].y * v[q].y);   // v_sqrt_f32, 1 ulp
-        if constexpr (MODE == 2) {
+        if constexpr (DEEP) {
 #pragma unroll
             for (int q = 0; q < 8; ++q) magbuf[t + 256 * q] = a[q];
             lds_barrier();
@@ -202,7 +205,7 @@ __global__ __launch_bounds__(256) void acq_corr_kernel(
         for (int q = 0; q < 8; ++q) mag[q] = 0.f;
 #pragma unroll 1
         for (int s = 0; s < nseg; ++s) segment(s);
-        if constexpr (MODE == 2) lds_barrier();   // (the statistics write the plane the sums just read)
+        if constexpr (DEEP) lds_barrier();   // (the statistics write the plane the sums just read)
         const float sc = 1.0f / (float)nseg;
         // The means of these searches are pinned bytewise (tests/golden/acq_parent_tables.npz) to a
         // build in which the compiler had taken the scale into the sum from the third row on: the
@@ -215,6 +218,11 @@ __global__ __launch_bounds__(256) void acq_corr_kernel(
         sm = add_rn(add_rn(0.f, mag[0]), mag[1]);
 #pragma unroll
         for (int q = 2; q < 8; ++q) sm = __builtin_fmaf(raw[q], sc, sm);
+        if constexpr (MODE == 3) {             // the surface the statistics below are formed of
+            float* row = rows + ((size_t)sv * nbins + bin0 + bin) * kFftN;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) row[t + 256 * q] = mag[q];
+        }
     }
     int amax; float peak, mean, sd, lo, hi;
     corr_stats8(mag, sm, t, magbuf, red, amax, peak, mean, sd, lo, hi);

@@ -144,6 +144,9 @@ int gpsmi_abi_sizeof(int which) {
         case 13: return (int)sizeof(gpsmi_cancel_sat);
         case 14: return (int)sizeof(gpsmi_cancel_cfg);
         case 15: return (int)sizeof(gpsmi_cancel_out);
+        case 17: return (int)sizeof(gpsmi_collective_sat);
+        case 18: return (int)sizeof(gpsmi_collective_grid);
+        case 19: return (int)sizeof(gpsmi_collective_cell);
         default: return -1;
     }
 }

@@ -85,17 +85,18 @@ struct LongCorr {
 
     // Cells cell0 .. cell0 + ncell - 1 of the tables on `stream`: folded rows x [d_xsel[cell]][cs] against
     // replica d_rsel[cell] (d_time and d_tw as in set_replica) into d_stats.  A piece of a launch is as
-    // good as the whole: tracking folds and correlates piece by piece.  MODE 2 (non-coherent) and 3
-    // (deep) are gpsmi_pfa.h's, with Pfa only (acq_check_search refuses the others): x is then
-    // [d_xsel[cell]][nseg][cs], and MODE 3 adds `shift`, the lag rotation of every (row, segment).
+    // good as the whole: tracking folds and correlates piece by piece.  MODE 2 (non-coherent), 3 (deep)
+    // and 4 (deep, the surfaces kept in `rows`) are gpsmi_pfa.h's, with Pfa only (acq_check_search
+    // refuses the others): x is then [d_xsel[cell]][nseg][cs], and MODE 3 / 4 add `shift`, the lag
+    // rotation of every (row, segment).
     template <int MODE = 0>
     void correlate(hipStream_t stream, const float2* x, int cell0, int ncell, const float* d_time, const float2* d_tw,
-                   int nseg = 1, const int* shift = nullptr) {
+                   int nseg = 1, const int* shift = nullptr, PfaRows rows = PfaRows{nullptr, 1, 0, 0}) {
         const int *xsel = d_xsel.p + cell0, *rsel = d_rsel.p + cell0;
         DirStats* stats = d_stats.p + cell0;
         if (pfa() && MODE == 0)          // (its kernel takes the first cell beside the tables)
             return pfa_corr_launch<0>(stream, x, d_xsel.p, d_rsel.p, ncell, d_RSp.p, d_stats.p, cell0);
-        if (pfa()) return pfa_corr_launch<MODE>(stream, x, xsel, rsel, ncell, d_RSp.p, stats, nseg, shift);
+        if (pfa()) return pfa_corr_launch<MODE>(stream, x, xsel, rsel, ncell, d_RSp.p, stats, nseg, shift, rows);
         float* mag = d_mag.p + (size_t)cell0 * cs;
         if (method == Method::BigFft)
             big_corr_launch(stream, x, xsel, rsel, ncell, cs, d_RS.p, d_S.p, d_tw, d_twN.p, mag);

@@ -215,10 +215,15 @@ __device__ __forceinline__ void pfa_slab33(fft_c* base) {
 //         the next P1 (or the final sums) from overwriting slots still being read.  With
 //         m = 1023 mj + mc the lag t + 1023 j + m lies at column c' = (t + mc) mod 1023 -- one sigma
 //         per thread and segment -- in row (j + mj + carry) mod 16.
+// MODE 4: MODE 3 that also keeps the surface S of every cell (gpsmi_acq_search_deep_rows_dev): cell c of
+//         the launch is (bin c / nsv, satellite c % nsv) and its 16368 values go to
+//         rows.p[(c % nsv) * nbins + bin0 + c / nsv].  The other modes do not read `rows`.
+struct PfaRows { float* p; int nsv, nbins, bin0; };
 template <int MODE>
 __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
     const float2* __restrict__ x, const float* __restrict__ rep, const int* __restrict__ xsel,
-    const int* __restrict__ rsel, float2* __restrict__ RS, int cell0, int ncell, DirStats* __restrict__ out) {
+    const int* __restrict__ rsel, float2* __restrict__ RS, int cell0, int ncell, DirStats* __restrict__ out,
+    PfaRows rows) {
     __shared__ __attribute__((aligned(16))) fft_c data[16 * kPfaPitch];
     __shared__ float red_s[16], red_v[16], red_d[16];
     __shared__ int red_i[16];
@@ -413,7 +418,7 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
     // per thread are requested right here and arrive under the reductions and barriers.
     float sm = 0.f, s2 = 0.f, bv = -1.f;
     int bi = 0x7fffffff;
-    if constexpr (MODE == 3) {
+    if constexpr (MODE >= 3) {
         const bool last = seg + 1 == nseg;
         const int m = __builtin_amdgcn_readfirstlane(
             reinterpret_cast<const int*>(rep)[xsel[cell] * nseg + seg]);
@@ -453,6 +458,9 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
                 s2 += m * m;
                 if (m > bv) { bv = m; bi = t + kPfaC * j; }
                 data[j * kPfaPitch + sig].x = m;
+                if constexpr (MODE == 4)
+                    rows.p[((size_t)(cell % rows.nsv) * rows.nbins + rows.bin0 + cell / rows.nsv) * kPfaL + t +
+                           kPfaC * j] = m;
             }
         }
     } else if constexpr (MODE == 2) {
@@ -565,23 +573,24 @@ __global__ __launch_bounds__(kPfaThreads) void pfa_corr_kernel(
 // launch, each in 0 .. L - 1.
 template <int MODE = 0>
 inline void pfa_corr_launch(hipStream_t stream, const float2* x, const int* xsel, const int* rsel,
-                            int ncell, float2* RS, DirStats* stats, int cell0 = 0, const int* shift = nullptr) {
-    static_assert(MODE == 0 || MODE == 2 || MODE == 3, "the replica's MODE 1 is pfa_replica_launch");
+                            int ncell, float2* RS, DirStats* stats, int cell0 = 0, const int* shift = nullptr,
+                            PfaRows rows = PfaRows{nullptr, 1, 0, 0}) {
+    static_assert(MODE == 0 || MODE >= 2, "the replica's MODE 1 is pfa_replica_launch");
     if (ncell <= 0) return;
     int dev = 0, n_cu = 256;
     if (hipGetDevice(&dev) == hipSuccess)
         (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
     const int grid = ncell < n_cu ? ncell : n_cu;
     hipLaunchKernelGGL(pfa_corr_kernel<MODE>, dim3(grid), dim3(kPfaThreads), 0, stream, x,
-                       reinterpret_cast<const float*>(MODE == 3 ? shift : nullptr), xsel, rsel, RS, cell0, ncell,
-                       stats);
+                       reinterpret_cast<const float*>(MODE >= 3 ? shift : nullptr), xsel, rsel, RS, cell0, ncell,
+                       stats, rows);
 }
 
 // spectrum of the replica in slot `slot` (rep_slot0 = table of real replicas [slots][L])
 inline void pfa_replica_launch(hipStream_t stream, const float* rep_slot0, int slot, float2* RS) {
     hipLaunchKernelGGL(pfa_corr_kernel<1>, dim3(1), dim3(kPfaThreads), 0, stream,
                        (const float2*)nullptr, rep_slot0, (const int*)nullptr, (const int*)nullptr, RS,
-                       slot, 1, (DirStats*)nullptr);
+                       slot, 1, (DirStats*)nullptr, PfaRows{nullptr, 1, 0, 0});
 }
 
 }  // namespace gpsmi

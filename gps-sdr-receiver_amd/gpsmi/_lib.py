@@ -70,6 +70,12 @@ class CancelCfg(C.Structure):
                 ('reserved', C.c_int32)]
 
 
+class CollectiveGrid(C.Structure):
+    _fields_ = [('n_e', C.c_int32), ('n_n', C.c_int32), ('n_t', C.c_int32), ('pool', C.c_int32),
+                ('e0', C.c_double), ('n0', C.c_double), ('t0', C.c_double),
+                ('d_e', C.c_double), ('d_n', C.c_double), ('d_t', C.c_double)]
+
+
 class Cfg(C.Structure):
     _fields_ = [('code_samples', C.c_int32), ('n_cyc', C.c_int32),
                 ('corr_avg', C.c_int32), ('sweep_corr_avg', C.c_int32),
@@ -95,6 +101,15 @@ CANCEL_SAT_DTYPE = np.dtype([('prn', np.int32), ('reserved', np.int32), ('f_hz',
 CANCEL_OUT_DTYPE = np.dtype([('prn', np.int32), ('n_windows', np.int32), ('n_skipped', np.int32),
                              ('reserved', np.int32), ('energy_in', np.float64),
                              ('energy_removed', np.float64)])
+
+COLLECTIVE_SAT_DTYPE = np.dtype([('row', np.int32), ('bin_lo', np.int32), ('bin_hi', np.int32),
+                                 ('reserved', np.int32), ('lag0', np.float64), ('g_e', np.float64),
+                                 ('g_n', np.float64), ('g_t', np.float64)])
+
+COLLECTIVE_CELL_DTYPE = np.dtype([('score', np.float32), ('lag', np.int32)])
+
+COLLECTIVE_MAX_SATS = 32      # kColMaxSats
+COLLECTIVE_MAX_CELLS = 1 << 22
 
 WTRK_RING = 50                # GPSMI_WTRK_RING
 WTRK_DATA_END = 1             # GPSMI_WTRK_DATA_END
@@ -145,7 +160,8 @@ EXPORTS = [
     'gpsmi_acq_search', 'gpsmi_acq_search_dev', 'gpsmi_acq_search_ex',
     'gpsmi_acq_search_dev_async', 'gpsmi_acq_wait',
     'gpsmi_acq_search_nc', 'gpsmi_acq_search_nc_dev',
-    'gpsmi_acq_search_deep', 'gpsmi_acq_search_deep_dev',
+    'gpsmi_acq_search_deep', 'gpsmi_acq_search_deep_dev', 'gpsmi_acq_search_deep_rows_dev',
+    'gpsmi_acq_collective_dev', 'gpsmi_acq_collective_plan',
     'gpsmi_acq_refine', 'gpsmi_acq_refine_dev', 'gpsmi_acq_refine_plan',
     'gpsmi_acq_track', 'gpsmi_acq_track_dev', 'gpsmi_acq_track_plan', 'gpsmi_wtrk_open',
     'gpsmi_acq_cancel', 'gpsmi_acq_cancel_dev', 'gpsmi_acq_cancel_plan',
@@ -224,6 +240,11 @@ def load():
                                   C.c_double, C.c_double, vp, vp],
         'gpsmi_acq_search_deep_dev': [vp, vp, sz, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                       C.c_double, C.c_double, vp, vp],
+        'gpsmi_acq_search_deep_rows_dev': [vp, vp, sz, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                           C.c_double, C.c_double, vp, vp, vp],
+        'gpsmi_acq_collective_dev': [vp, vp, C.c_int, C.c_int, vp, C.c_int, P(CollectiveGrid), vp, vp],
+        'gpsmi_acq_collective_plan': [C.c_int, C.c_int, C.c_int, vp, C.c_int, P(CollectiveGrid),
+                                      P(sz), P(C.c_int)],
         'gpsmi_acq_refine': [vp, vp, sz, vp, C.c_int, P(RefineCfg), vp, vp, vp],
         'gpsmi_acq_refine_dev': [vp, vp, sz, vp, C.c_int, P(RefineCfg), vp, vp, vp],
         'gpsmi_acq_refine_plan': [C.c_int, sz, vp, C.c_int, P(RefineCfg), P(C.c_int)],
@@ -315,6 +336,8 @@ def load():
     got += [lib.gpsmi_abi_sizeof(i) for i in (10, 11, 12)]
     want += [CANCEL_SAT_DTYPE.itemsize, C.sizeof(CancelCfg), CANCEL_OUT_DTYPE.itemsize]
     got += [lib.gpsmi_abi_sizeof(i) for i in (13, 14, 15)]
+    want += [COLLECTIVE_SAT_DTYPE.itemsize, C.sizeof(CollectiveGrid), COLLECTIVE_CELL_DTYPE.itemsize]
+    got += [lib.gpsmi_abi_sizeof(i) for i in (17, 18, 19)]
     if want != got:
         raise EngineError(f'ABI mismatch between gpsmi/_lib.py {want} and '
                           f'libgpsmi.so {got}')

@@ -167,6 +167,21 @@ class Acquisition:
         sats = [(int(rec['prn'][i]), float(rec['f_hz'][i]), float(tau[i])) for i in order]
         return self.engine.cancel(data, sats, out=out, f_offset=f_offset)
 
+    def deepRows(self, data, prns, freqs, n_coh=4, n_seg=250, f_offset=0.0):
+        """The deep surface kept whole (AcqEngine.search_deep with rows): the
+        table of sweepDeepSats' search and a DeviceBuffer of float32 [len(prns)][len(freqs)]
+        [code_samples] with the surface of every cell, for AcqEngine.collective.  The caller
+        frees the buffer.  -> (table, rows)."""
+        from .engine import DeviceBuffer
+        prns, freqs = list(prns), list(freqs)
+        rows = DeviceBuffer(len(prns) * len(freqs) * self.cfg.code_samples * 4, self.cfg.device)
+        try:
+            table = self.engine.search_deep(data, prns, freqs, n_coh, n_seg, f_offset=f_offset, rows=rows)
+        except Exception:
+            rows.free()
+            raise
+        return table, rows
+
     def search_table(self, data, prns, freqs, n_avg):
         """The whole surface, no pruning (BASELINE configs 2 and 4)."""
         return self.engine.search(data, prns, freqs, n_avg)

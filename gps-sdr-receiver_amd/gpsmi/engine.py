@@ -142,6 +142,25 @@ def sync(device=0):
     check(_lib.load().gpsmi_dev_sync(device), 'gpsmi_dev_sync')
 
 
+def collective_grid(n_e=1, n_n=1, n_t=1, pool=1, e0=0.0, n0=0.0, t0=0.0, d_e=0.0, d_n=0.0, d_t=0.0):
+    """The grid of a collective search (gpsmi_collective_grid): n_e x n_n x n_t points from
+    (e0, n0, t0) in steps (d_e, d_n, d_t), clock lags in steps of `pool` samples."""
+    return _lib.CollectiveGrid(int(n_e), int(n_n), int(n_t), int(pool), float(e0), float(n0),
+                               float(t0), float(d_e), float(d_n), float(d_t))
+
+
+def collective_plan(code_samples, nsv_rows, nbins, sats, grid):
+    """gpsmi_acq_collective_plan: the argument checks of AcqEngine.collective without a GPU.
+    -> (scratch_bytes, workgroups); EngineError where the call would refuse."""
+    sats = np.ascontiguousarray(sats, dtype=_lib.COLLECTIVE_SAT_DTYPE)
+    g = grid if isinstance(grid, _lib.CollectiveGrid) else collective_grid(**grid)
+    scratch, wgs = C.c_size_t(), C.c_int()
+    check(_lib.load().gpsmi_acq_collective_plan(
+        int(code_samples), int(nsv_rows), int(nbins), ptr(sats), len(sats), C.byref(g),
+        C.byref(scratch), C.byref(wgs)), 'gpsmi_acq_collective_plan')
+    return scratch.value, wgs.value
+
+
 def _spectrum_c64(prn, cs):
     return np.ascontiguousarray(codes.replica_spectrum(prn, cs)
                                 .astype(np.complex64))
@@ -235,17 +254,43 @@ class AcqEngine:
     L1_HZ = 1575.42e6
 
     def search_deep(self, iq, prns, freqs, n_coh, n_seg, f_offset=0.0, carrier_hz=L1_HZ,
-                    out_dev=None, nbr=False):
+                    out_dev=None, nbr=False, rows=None):
         """Deep search (gpsmi_acq_search_deep): search_noncoherent with the code Doppler
         compensated, for spans of seconds.  The magnitudes of segment s of bin f are added at the
         lag they had at the start of iq: rotated by rint(-(f - f_offset) / carrier_hz * s * n_coh *
         code_samples) samples.  f_offset: what the bin frequencies differ from the true Doppler
         by (a tuner's frequency error).  Arguments and returns otherwise as search_noncoherent;
-        the argmax is the code phase at the start of iq."""
+        the argmax is the code phase at the start of iq.
+        rows: a DeviceBuffer of at least nsv * nbins * code_samples * 4 bytes that receives the
+        surface of every cell, float32 [nsv][nbins][code_samples] (gpsmi_acq_search_deep_rows_dev;
+        host input is uploaded first; not together with nbr).  The table is the same bytes."""
         prn_a = np.ascontiguousarray(prns, dtype=np.int32)
         f_a = np.ascontiguousarray(freqs, dtype=np.float64)
         out = np.zeros((len(f_a), len(prn_a)), dtype=PEAK_DTYPE)
         nb = np.zeros((len(f_a), len(prn_a), 2), dtype=np.float32) if nbr else None
+        if rows is not None:
+            if nbr:
+                raise ValueError('nbr is not returned together with rows')
+            need = len(prn_a) * len(f_a) * self.cfg.code_samples * 4
+            if rows.nbytes < need:
+                raise ValueError(f'rows holds {rows.nbytes} bytes, the surfaces need {need}')
+            held = None
+            if isinstance(iq, tuple):
+                d_iq, n = iq
+            else:
+                iq = self._host_iq(iq)
+                held = DeviceBuffer(max(iq.nbytes, 1), self.cfg.device)
+                held.upload(iq)
+                d_iq, n = held.ptr, iq.size
+            try:
+                check(self.lib.gpsmi_acq_search_deep_rows_dev(
+                    self.h, d_iq, n, ptr(prn_a), len(prn_a), ptr(f_a), len(f_a),
+                    int(n_coh), int(n_seg), float(carrier_hz), float(f_offset), ptr(out), out_dev,
+                    rows.ptr), 'gpsmi_acq_search_deep_rows_dev')
+            finally:
+                if held is not None:
+                    held.free()
+            return out
         if isinstance(iq, tuple):
             if nbr:
                 raise ValueError('nbr is returned for host input only')
@@ -261,6 +306,32 @@ class AcqEngine:
                 int(n_coh), int(n_seg), float(carrier_hz), float(f_offset), ptr(out),
                 ptr(nb) if nbr else None), 'gpsmi_acq_search_deep')
         return (out, nb) if nbr else out
+
+    def collective(self, rows, sats, grid, nsv_rows=None, nbins=None):
+        """Collective detection (gpsmi_acq_collective_dev) over the surfaces `rows` that
+        search_deep(..., rows=) left: a DeviceBuffer of float32 [nsv_rows][nbins][code_samples].
+        sats: COLLECTIVE_SAT_DTYPE records (row, bin_lo, bin_hi, lag0, g_e, g_n, g_t); grid: a dict
+        or _lib.CollectiveGrid of n_e, n_n, n_t, pool, e0, n0, t0, d_e, d_n, d_t.  nsv_rows and
+        nbins describe the rows; by default the largest row and bin the satellites name, plus one.
+        Returns the cell map, COLLECTIVE_CELL_DTYPE [n_t, n_n, n_e]: per grid point the best
+        clock lag and its score."""
+        sats = np.ascontiguousarray(sats, dtype=_lib.COLLECTIVE_SAT_DTYPE)
+        g = grid if isinstance(grid, _lib.CollectiveGrid) else collective_grid(**grid)
+        if nsv_rows is None:
+            nsv_rows = int(sats['row'].max()) + 1 if len(sats) else 1
+        if nbins is None:
+            nbins = int(sats['bin_hi'].max()) + 1 if len(sats) else 1
+        need = int(nsv_rows) * int(nbins) * self.cfg.code_samples * 4
+        if rows.nbytes < need:
+            raise ValueError(f'rows holds {rows.nbytes} bytes, [{nsv_rows}][{nbins}] surfaces are {need}')
+        shape = (max(g.n_t, 0), max(g.n_n, 0), max(g.n_e, 0))
+        cells = shape[0] * shape[1] * shape[2]
+        out = np.zeros(shape if 0 < cells <= _lib.COLLECTIVE_MAX_CELLS else (1, 1, 1),
+                       dtype=_lib.COLLECTIVE_CELL_DTYPE)
+        check(self.lib.gpsmi_acq_collective_dev(
+            self.h, rows.ptr, int(nsv_rows), int(nbins), ptr(sats), len(sats), C.byref(g), ptr(out),
+            None), 'gpsmi_acq_collective_dev')
+        return out
 
     def refine(self, iq, hits, n_ms, df_step=2.0, df_half=120.0, tap_samples=0, f_offset=0.0,
                carrier_hz=L1_HZ, min_ratio=2.5, want_grid=False, want_prompts=False):

@@ -8,8 +8,10 @@ navigation step that works without decoded time: Gauss-Newton over ECEF position
 sub-millisecond clock bias and the coarse time, with the whole milliseconds of every satellite
 derived from the a-priori position and time relative to the strongest satellite.
 ``doppler_fix`` makes an a-priori position from the Dopplers alone when the caller has none, and
-``snapshot_fix`` chains the three.  Everything in this module but the three engine calls inside
-``measure`` is host float64 numpy.
+``snapshot_fix`` chains the three.  ``collective_search`` is the way in when every
+satellite is under measure's threshold: the deep surfaces of all visible satellites added over a grid
+of position, coarse time and clock.  Everything in this module but the engine calls inside
+``measure`` and ``collective_search`` is host float64 numpy.
 
 Contract of ``coarse_time_fix``: the a-priori position within 50 km and the time within 30 s, or
 the position within 75 km at the right time, or the time within 90 s at the right position (the
@@ -115,6 +117,7 @@ class Fix:
     iterations: int = 0
     tau: object = None                    # tested figure per metre of bias on each satellite
     slope: object = None                  # position error per unit of the tested figure, per satellite
+    path: str = 'measure'                 # what supplied the measurements: 'measure' or 'collective' (snapshot_fix)
 
 
 def _solve(prns, samples, phases, w, ephs, clock, pos0, fs):
@@ -455,14 +458,264 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
             clean.free()
 
 
-def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, cancel=None, stats=None, **cfg):
+# ---------------------------------------------------------------- collective detection
+COLLECTIVE_POOL = 8                      # lags pooled at the coarsest level of the pyramid
+COLLECTIVE_ELEVATION = 5.0               # degrees above the a-priori horizon a PRN must stand to be searched
+COLLECTIVE_WINDOW_MIN = 4.0              # (S - mean) / std a satellite's 3 x 3 window must reach
+COLLECTIVE_MARGIN_MIN = 6.0              # (best - median) / robust sigma of the coarsest map
+COLLECTIVE_FINE = 5                      # grid points per axis of the levels after the first
+
+
+def enu_axes(pos):
+    """Unit vectors east, north and up at ECEF `pos` (geodetic)."""
+    lat, lon, _ = P.ecef_to_geo(np.asarray(pos, dtype=np.float64))
+    la, lo = np.radians(lat), np.radians(lon)
+    east = np.array([-np.sin(lo), np.cos(lo), 0.0])
+    north = np.array([-np.sin(la) * np.cos(lo), -np.sin(la) * np.sin(lo), np.cos(la)])
+    return east, north, np.cross(east, north)
+
+
+def collective_model(ephs, prns, t_gps, pos, cs, f_offset=0.0):
+    """What a receiver at ECEF `pos` at GPS time `t_gps` (that of the first sample) expects of
+    `prns`, as collective detection needs it: the code start of satellite p lies at lag
+        lag0_p + g_e_p E + g_n_p N + g_t_p T + clock      (mod cs)
+    for a receiver E metres east and N metres north of `pos` at time t_gps + T.  lag0 = fs / c *
+    modelled_range mod cs; g_e, g_n = fs / c * the line of sight's east and north components;
+    g_t = fs / c * the range rate.  The part of the time that all satellites share (-fs T) and the
+    receiver's clock bias are the common term `clock`.
+    -> dict of arrays per PRN: lag0, g_e, g_n, g_t, f_hz (the predicted Doppler plus f_offset),
+    elevation (degrees)."""
+    fs = 1000.0 * cs
+    east, north, up = enu_axes(pos)
+    t = np.full(len(prns), float(t_gps))
+    f, e, fd = _model(ephs, prns, t, np.asarray(pos, dtype=np.float64))
+    k = fs / P.GPS_C
+    return {'lag0': np.mod(k * f, cs), 'g_e': k * (e @ east), 'g_n': k * (e @ north), 'g_t': k * fd,
+            'f_hz': -fd * L1_HZ / P.GPS_C + f_offset, 'elevation': np.degrees(np.arcsin(-(e @ up)))}
+
+
+def collective_levels(radius_m, time_s, cs, g_t_max, pool=COLLECTIVE_POOL):
+    """The pyramid: per level (pool w, step in metres, step in seconds, points per horizontal axis,
+    points in time).  w halves from `pool` to 1; the horizontal step is half of w samples of range
+    (w * c / fs / 2: neighbouring points then differ by at most 0.71 w lags in any satellite, less
+    than the w lags a pooled row covers), the time step a quarter of w lags of the fastest
+    satellite.  The first level covers +-radius_m and +-time_s, the others +-2 steps of their own
+    around the best cell of the level before (which is within one step of theirs)."""
+    fs = 1000.0 * cs
+    out, w = [], int(pool)
+    while w >= 1:
+        step_m, step_t = 0.5 * w * P.GPS_C / fs, 0.25 * w / max(g_t_max, 1.0e-3)
+        if not out:
+            n_h, n_t = 2 * int(np.ceil(radius_m / step_m)) + 1, 2 * int(np.ceil(time_s / step_t)) + 1
+        else:
+            n_h = n_t = COLLECTIVE_FINE
+        out.append((w, step_m, step_t, n_h, n_t))
+        w //= 2
+    return out
+
+
+def collective_level_args(model, bins, level):
+    """The satellites (engine.COLLECTIVE_SAT_DTYPE) and the grid (a dict) of one level, centred on
+    the point `model` was formed at.  `bins`: per satellite (row, bin_lo, bin_hi).  A pooled row
+    holds the maximum of lags l .. l + w - 1, so the prediction is moved back by (w - 1) / 2."""
+    from ._lib import COLLECTIVE_SAT_DTYPE
+    w, step_m, step_t, n_h, n_t = level
+    sats = np.zeros(len(bins), COLLECTIVE_SAT_DTYPE)
+    sats['row'], sats['bin_lo'], sats['bin_hi'] = np.array(bins, dtype=np.int64).T
+    sats['lag0'] = model['lag0'] - 0.5 * (w - 1)
+    sats['g_e'], sats['g_n'], sats['g_t'] = model['g_e'], model['g_n'], model['g_t']
+    grid = dict(n_e=n_h, n_n=n_h, n_t=n_t, pool=w, e0=-0.5 * (n_h - 1) * step_m, n0=-0.5 * (n_h - 1) * step_m,
+                t0=-0.5 * (n_t - 1) * step_t, d_e=step_m, d_n=step_m, d_t=step_t)
+    return sats, grid
+
+
+def collective_best(cells, grid):
+    """The best cell of a map.  Rounding the predicted lags to whole samples leaves a plateau of
+    equal scores around the optimum: of the cells that hold the largest score, the one nearest to
+    their centroid (in cells; the first of equally near ones in (i_t, i_n, i_e) order).
+    -> (E, N, T, clock lag, score, index)."""
+    top = np.argwhere(cells['score'] == cells['score'].max())
+    d = top - top.mean(axis=0)
+    it, i_n, ie = (int(v) for v in top[int(np.argmin(np.sum(d * d, axis=1)))])
+    return (grid['e0'] + ie * grid['d_e'], grid['n0'] + i_n * grid['d_n'], grid['t0'] + it * grid['d_t'],
+            int(cells['lag'][it, i_n, ie]), float(cells['score'][it, i_n, ie]), (it, i_n, ie))
+
+
+def collective_margin(cells):
+    """(best - median) / (1.4826 * median absolute deviation) of a map's scores."""
+    sc = cells['score'].astype(np.float64).ravel()
+    med = np.median(sc)
+    return float((sc.max() - med) / max(1.4826 * np.median(np.abs(sc - med)), 1.0e-30))
+
+
+def collective_pyramid(cell_map, ephs, prns, bins, t_gps, pos, cs, radius_m, time_s, f_offset=0.0,
+                       pool=COLLECTIVE_POOL):
+    """The coarse-to-fine search.  `cell_map(sats, grid)` -> the cell map of one level
+    (AcqEngine.collective on the GPU).  Every level is linearised anew at the best point of the one
+    before.  -> dict: ecef, t_gps, lag (clock, samples), score, margin (of the coarsest map), map
+    and grid (of the last level), model (collective_model at the optimum), levels (per level: pool,
+    grid shape, best index, score, grid, and the centre (ecef, t_gps) its offsets count from)."""
+    pos, t = np.array(pos, dtype=np.float64), float(t_gps)
+    model = collective_model(ephs, prns, t, pos, cs, f_offset)
+    levels = collective_levels(radius_m, time_s, cs, float(np.abs(model['g_t']).max()), pool)
+    res = {'levels': []}
+    for k, level in enumerate(levels):
+        if level[3] * level[3] * level[4] > (1 << 22):
+            raise ValueError(f'the first level has {level[3]} x {level[3]} x {level[4]} points, more than one '
+                             'collective call takes: a smaller radius_m or time_s')
+        sats, grid = collective_level_args(model, bins, level)
+        cells = cell_map(sats, grid)
+        E, N, T, lag, score, idx = collective_best(cells, grid)
+        if k == 0:
+            res['margin'] = collective_margin(cells)
+        res['levels'].append({'pool': level[0], 'shape': cells.shape, 'best': idx, 'score': score, 'grid': grid,
+                              'centre': (pos.copy(), t)})
+        east, north, _ = enu_axes(pos)
+        pos, t = pos + E * east + N * north, t + T
+        # the clock lag counts from the prediction this level was given; the next one (or the
+        # caller) gets it relative to the new linearisation
+        here = sats['lag0'] + sats['g_e'] * E + sats['g_n'] * N + sats['g_t'] * T + lag + 0.5 * (level[0] - 1)
+        model = collective_model(ephs, prns, t, pos, cs, f_offset)
+        clock = here - model['lag0']
+        clock = clock[0] + np.mod(clock - clock[0] + cs / 2.0, cs) - cs / 2.0      # (one turn of the code for all)
+        res.update(map=cells, grid=grid, score=score)
+    res.update(ecef=pos, t_gps=t, model=model, lag=float(np.mod(np.median(clock), cs)))
+    return res
+
+
+def collective_records(rows_of, prns, freqs, model, lag, cs, window_min=COLLECTIVE_WINDOW_MIN):
+    """Measurements at the optimum of a collective search.  rows_of(p) -> the surfaces of
+    satellite p in its bins, float [bins, cs]; freqs[p] their frequencies; the predicted lag of p
+    is model['lag0'][p] + lag.  Per satellite the largest of the 3 lags around the prediction, in
+    the bin where it is largest, counts as a measurement if its (S - mean) / std (mean and std of
+    its bin's whole row) reaches `window_min` -- lower than the threshold of a search over the
+    whole surface, because 3 lags x the satellite's bins are searched, not 2048 x 51 cells.  The
+    sub-sample phase is the vertex of the parabola through the peak and its two neighbours, within
+    half a sample.  -> MEAS_DTYPE records (sample 0, cn0_dbhz NaN: nothing here measures it,
+    source b'collec'), and the (S - mean) / std of every satellite."""
+    out, zs = [], np.zeros(len(prns))
+    for p, prn in enumerate(prns):
+        S_ = np.asarray(rows_of(p), dtype=np.float64)
+        z = (S_ - S_.mean(axis=1, keepdims=True)) / np.where(S_.std(axis=1, keepdims=True) > 0,
+                                                              S_.std(axis=1, keepdims=True), np.inf)
+        l0 = int(np.floor(model['lag0'][p] + lag + 0.5))
+        lags = np.array([l0 - 1, l0, l0 + 1]) % cs
+        b, j = np.unravel_index(int(np.argmax(z[:, lags])), (len(z), 3))
+        zs[p] = z[b, lags[j]]
+        if zs[p] < window_min:
+            continue
+        l = int(lags[j])
+        lo, mid, hi = S_[b, (l - 1) % cs], S_[b, l], S_[b, (l + 1) % cs]
+        den = lo - 2.0 * mid + hi
+        frac = float(np.clip(0.5 * (lo - hi) / den, -0.5, 0.5)) if den < 0 else 0.0
+        out.append((int(prn), 0, (l + frac) % cs, float(freqs[p][b]), np.nan, np.nan, b'collec'))
+    return np.array(out, dtype=MEAS_DTYPE), zs
+
+
+def collective_plan_bins(ephs, t_gps, pos, cfg, f_offset=0.0, elevation=COLLECTIVE_ELEVATION):
+    """Which PRNs a collective search takes and where: those of `ephs` standing `elevation`
+    degrees above the a-priori horizon, each with the window of its predicted Doppler bin +-1 on
+    the configured bin grid.  -> (prns, freqs searched (sorted, the union of the windows), per
+    satellite (row, bin_lo, bin_hi) into them)."""
+    prns = sorted(int(p) for p in ephs)
+    m = collective_model(ephs, prns, t_gps, pos, cfg.code_samples, f_offset)
+    nb = int(round((cfg.max_freq - cfg.min_freq) / cfg.step_freq))
+    seen = [(p, int(np.clip(round((f - cfg.min_freq) / cfg.step_freq), 0, nb - 1)))
+            for p, f, el in zip(prns, m['f_hz'], m['elevation']) if el >= elevation]
+    used = sorted({b for _, c in seen for b in range(max(c - 1, 0), min(c + 1, nb - 1) + 1)})
+    freqs = [cfg.min_freq + cfg.step_freq * b for b in used]
+    bins = [(r, used.index(max(c - 1, 0)), used.index(min(c + 1, nb - 1))) for r, (_, c) in enumerate(seen)]
+    return [p for p, _ in seen], freqs, bins
+
+
+def collective_search(acq, data, ephs, t_gps, pos, f_offset=0.0, radius_m=15.0e3, time_s=2.0, stats=None, **cfg):
+    """Collective detection: no decision per satellite -- the deep surfaces of
+    all visible satellites are added at the lags a candidate (position, coarse time, clock)
+    predicts, and the candidate where the sum peaks is taken; satellites that are each under the
+    search's threshold add up.
+
+    `pos`, `t_gps`: the a-priori ECEF position and the GPS time of the first sample, believed
+    within `radius_m` (horizontally) and `time_s`.  The height stays at the a-priori's: the search
+    moves east and north only.  1. collective_plan_bins picks the PRNs and their bin windows.  2. One
+    deep search with rows over them (`n_coh`-ms segments).  3. collective_pyramid: levels of pooled
+    rows from `pool` samples down to 1, each linearised at the best cell of the one before.  4. The
+    best (position, time, clock lag), the score map of the last level, the margin of the peak of
+    the coarsest map, and collective_records' measurements at the optimum (`window_min`).
+    -> dict of collective_pyramid's entries plus prns, meas, z (per PRN), device_ms (all calls) and
+    level_ms (per level)."""
+    c = acq.cfg
+    cs = c.code_samples
+    n_coh = int(cfg.pop('n_coh', 4))
+    pool = int(cfg.pop('pool', COLLECTIVE_POOL))
+    window_min = float(cfg.pop('window_min', COLLECTIVE_WINDOW_MIN))
+    elevation = float(cfg.pop('elevation', COLLECTIVE_ELEVATION))
+    if cfg:
+        raise TypeError(f'unknown options {sorted(cfg)}')
+    n = int(data[1]) if isinstance(data, tuple) else len(data)
+    n_seg = n // cs // n_coh
+    if n_seg < 1:
+        raise ValueError(f'{n} samples hold no segment of {n_coh} code periods')
+    prns, freqs, bins = collective_plan_bins(ephs, t_gps, pos, c, f_offset, elevation)
+    if not prns:
+        raise ValueError('no satellite of the ephemerides stands above the a-priori horizon')
+    _, rows = acq.deepRows(data if isinstance(data, tuple) else acq.engine._host_iq(data), prns, freqs, n_coh,
+                           n_seg, f_offset=f_offset)
+    try:
+        ms = {'device_ms': acq.engine.last_ms(), 'level_ms': []}
+
+        def cell_map(sats, grid):
+            cells = acq.engine.collective(rows, sats, grid, nsv_rows=len(prns), nbins=len(freqs))
+            ms['level_ms'].append(acq.engine.last_ms())
+            return cells
+        res = collective_pyramid(cell_map, ephs, prns, bins, t_gps, pos, cs, radius_m, time_s, f_offset, pool)
+        host = rows.download(np.float32, len(prns) * len(freqs) * cs).reshape(len(prns), len(freqs), cs)
+    finally:
+        rows.free()
+    res['meas'], res['z'] = collective_records(
+        lambda p: host[bins[p][0], bins[p][1]:bins[p][2] + 1], prns,
+        [freqs[b[1]:b[2] + 1] for b in bins], res['model'], res['lag'], cs, window_min)
+    res.update(prns=prns, level_ms=ms['level_ms'], device_ms=ms['device_ms'] + sum(ms['level_ms']))
+    if stats is not None:
+        stats['collective'] = res
+    return res
+
+
+def _collective_fix(acq, data, ephs, t_gps, pos, f_offset, cfg, stats):
+    """collective_search, then coarse_time_fix on its measurements from its optimum."""
+    res = collective_search(acq, data, ephs, t_gps, pos, f_offset=f_offset, stats=stats, **cfg)
+    meas = res['meas']
+    if res['margin'] < COLLECTIVE_MARGIN_MIN:
+        fix = Fix(reason=f"collective peak {res['margin']:.1f} robust sigma above the map, "
+                         f'{COLLECTIVE_MARGIN_MIN} needed')
+    elif len(meas) < MIN_SAT:
+        fix = Fix(reason=f'{len(meas)} satellites measured at the collective optimum, {MIN_SAT} needed')
+    else:
+        fix = coarse_time_fix(meas, ephs, res['t_gps'], res['ecef'], code_samples=acq.cfg.code_samples)
+    fix.path = 'collective'
+    return fix, meas, res['device_ms']
+
+
+def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, cancel=None, stats=None,
+                 collective=None, collective_cfg=None, **cfg):
     """measure -> (doppler_fix when `pos` is None) -> coarse_time_fix.  `t_gps`: the GPS seconds
     of week of the first sample as far as known; `cancel`, `stats`: measure's.  -> (Fix,
-    measurements, device ms).  The Fix's t_gps is that of its `sample`."""
+    measurements, device ms).  The Fix's t_gps is that of its `sample`.
+    `collective` (needs `pos`): True -- when measure yields fewer than MIN_SAT
+    satellites, collective_search (keywords: `collective_cfg`) supplies the a-priori and the
+    measurements instead, and coarse_time_fix solves from them; 'always' -- it does so whatever
+    measure yields.  Fix.path says which of the two made the fix.  None or False: nothing of this
+    runs."""
+    if collective not in (None, False, True, 'always'):
+        raise ValueError(f"collective {collective!r}: None, False, True or 'always'")
+    if collective and pos is None:
+        raise ValueError('collective detection needs an a-priori position')
     stats = {} if stats is None else stats
     meas = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats, cancel=cancel,
                    **cfg)
     ms = stats.get('device_ms', 0.0)
+    if collective and (collective == 'always' or len(meas) < MIN_SAT):
+        fix, meas, cms = _collective_fix(acq, data, ephs, t_gps, pos, f_offset, dict(collective_cfg or {}), stats)
+        return fix, meas, ms + cms
     if len(meas) < MIN_SAT:
         return Fix(reason=f'{len(meas)} satellites measured, {MIN_SAT} needed'), meas, ms
     fs = 1000.0 * acq.cfg.code_samples

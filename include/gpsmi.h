@@ -65,7 +65,8 @@ const char* gpsmi_last_error(void);
 const char* gpsmi_version(void);
 /* sizeof() of the ABI structs as compiled: 0 cfg, 1 peak, 2 trk_state, 3 trk_out,
  * 4 offsetof(trk_out, code_phase), 5 fe_cfg, 6 pb_cfg, 7 refine_hit, 8 refine_cfg, 9 refine_out,
- * 10 wtrk_cfg, 11 wtrk_state, 12 wtrk_bit; -1 otherwise.  Lets a binding verify its own struct declarations before the first real call.  */
+ * 10 wtrk_cfg, 11 wtrk_state, 12 wtrk_bit, 13 cancel_sat, 14 cancel_cfg, 15 cancel_out, 17 collective_sat,
+ * 18 collective_grid, 19 collective_cell (16 is not assigned); -1 otherwise.  Lets a binding verify its own struct declarations before the first real call.  */
 int gpsmi_abi_sizeof(int which);
 /* Kernel-variant selection and tuning thresholds, visible through the ABI (round 4: they used to
  * be environment variables read inside gpsmi_*_create, invisible to a C caller; the variables
@@ -271,6 +272,67 @@ int gpsmi_acq_search_deep_dev(gpsmi_acq* h, const void* d_iq, size_t n,
                               const double* freqs_hz, int nbins, int n_coh, int n_seg,
                               double carrier_hz, double f_offset_hz,
                               gpsmi_peak* out, void* out_dev);
+/* gpsmi_acq_search_deep_dev that also keeps the surfaces: d_rows receives S of every cell as float32
+ * [nsv][nbins][code_samples] on the device (note the order: satellite first).  The records are
+ * gpsmi_acq_search_deep_dev's byte for byte, and the rows are what they are statistics of: argmax is
+ * the first index of a row's maximum and peak its value, exactly; mean and std are the row's mean and
+ * population std, formed in the kernels' own summation orders (at 2048 the mean is the pinned sum of
+ * gpsmi_acq_search_nc, which adds unrounded products: it is not a function of the rounded row alone
+ * and differs from a sum over the row in the last bits).  code_samples 2048 and the native 16368, the
+ * same bin chunking, either input format.  At 16368 n_seg must be at least 2 (one segment is the
+ * coherent search, which keeps no surface: GPSMI_E_UNSUPPORTED).  d_rows == NULL is GPSMI_E_ARG.      */
+int gpsmi_acq_search_deep_rows_dev(gpsmi_acq* h, const void* d_iq, size_t n,
+                                   const int32_t* prn, int nsv,
+                                   const double* freqs_hz, int nbins, int n_coh, int n_seg,
+                                   double carrier_hz, double f_offset_hz,
+                                   gpsmi_peak* out, void* out_dev, void* d_rows);
+/* Collective detection (numpy restatement: tests/collective_ref.py): instead of a
+ * decision per satellite, the normalised surfaces of all satellites are added at the lags that a
+ * candidate receiver state (east, north, coarse time, clock) predicts, and the state where the sum
+ * peaks is taken.  d_rows: the rows of gpsmi_acq_search_deep_rows_dev, [nsv_rows][nbins][code_samples].
+ *
+ * Step a, once per call and satellite p, all float32, no fused operations:
+ *     mean[b] = sum(S[row][b]) / cs, std[b] = sqrt(sum((S - mean)^2) / cs)   (multiplications by
+ *               float32(1) / float32(cs); the sums: thread t of 256 adds lags t, t + 256, ... in
+ *               ascending order from 0, the 256 shares meet in an adjacent-pair tree -- at 2048
+ *               gpsmi_stats.h's order)
+ *     z[p][l] = max over b in [bin_lo, bin_hi] with std[b] > 0 of (S[row][b][l] - mean[b]) / std[b]
+ * A bin whose std is not positive is skipped (no NaN enters a comparison); a satellite all of whose
+ * bins are skipped has z = 0 everywhere.  With pool = w > 1, z is replaced by its circular running
+ * maximum zw[l] = max_{k<w} z[(l + k) mod cs].
+ * Step b, for grid point (i_t, i_n, i_e): E = e0 + i_e * d_e, N = n0 + i_n * d_n, T = t0 + i_t * d_t, and
+ * for every clock lag c in {0, w, 2w, ...} < cs
+ *     x_p = lag0_p + g_e_p * E + g_n_p * N + g_t_p * T + c     (float64, left to right, nothing fused)
+ *     i_p = floor(x_p + 0.5) mod cs                            (non-negative)
+ *     score = z_0[i_0] + z_1[i_1] + ...                        (float32, ascending p)
+ * The cell of the point holds the largest score and its c, between equal scores the smallest c.
+ * out_host / out_dev: gpsmi_collective_cell [n_t][n_n][n_e], at least one of them.  Limits: nsat
+ * 1..32, pool 1..64, every |x_p| below 2^30, at most 2^22 grid points per call (more:
+ * GPSMI_E_UNSUPPORTED, nothing is chunked silently), code_samples 2048 and 16368.  Argument errors are
+ * GPSMI_E_ARG and need no GPU (gpsmi_acq_collective_plan makes the same checks without a handle, and
+ * reports the scratch the call allocates and the workgroups of its grid launch, 64 grid points each).
+ * The call returns when the work is done; gpsmi_acq_last_ms reports its three kernels.              */
+typedef struct gpsmi_collective_sat {   /* no implicit padding: 48 bytes */
+    int32_t row;                    /* the satellite's index in d_rows */
+    int32_t bin_lo, bin_hi;         /* inclusive window of its bins */
+    int32_t reserved;               /* 0 */
+    double  lag0;                   /* predicted lag at E = N = T = 0, clock 0, samples */
+    double  g_e, g_n, g_t;          /* samples per metre east / north, per second of coarse time */
+} gpsmi_collective_sat;
+typedef struct gpsmi_collective_grid {  /* no implicit padding: 64 bytes */
+    int32_t n_e, n_n, n_t, pool;
+    double  e0, n0, t0, d_e, d_n, d_t;
+} gpsmi_collective_grid;
+typedef struct gpsmi_collective_cell {  /* 8 bytes */
+    float   score;
+    int32_t lag;
+} gpsmi_collective_cell;
+int gpsmi_acq_collective_dev(gpsmi_acq* h, const void* d_rows, int nsv_rows, int nbins,
+                             const gpsmi_collective_sat* sats, int nsat, const gpsmi_collective_grid* grid,
+                             gpsmi_collective_cell* out_host, void* out_dev);
+int gpsmi_acq_collective_plan(int code_samples, int nsv_rows, int nbins,
+                              const gpsmi_collective_sat* sats, int nsat, const gpsmi_collective_grid* grid,
+                              size_t* scratch_bytes, int* workgroups);
 /* Refinement of the hits of gpsmi_acq_search_nc / gpsmi_acq_search_deep: what a
  * high-sensitivity receiver runs between such a search and its loops.  Per hit (prn, delay = the
  * argmax the search returned, the code start at the start of iq; freq_hz = the bin) it integrates

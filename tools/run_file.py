@@ -6,7 +6,7 @@ gpseval) as one command on the GPU path.
     python tools/run_file.py <recording.bin> [--seconds S] [--start-stream K] [--save-pickle P]
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--blank] [--json]
                              [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track [--weak-fix]]]]
-                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]]]
+                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]]]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -58,7 +58,10 @@ known (within 50 km), without it the Dopplers give one.  It prints the measureme
 device time; with --json one line with a 'snapshot' key.  --cancel [DBHZ] (with --snapshot only): the
 satellites measured at or above DBHZ (default 40 dB-Hz) are cancelled from the samples and the others
 measured on what is left; the report gains a 'cancelled' list.  Without the flag every
-output is as before.
+output is as before.  --collective [RADIUS_KM] (with --snapshot and --near): when fewer than five satellites
+are measured, position, coarse time and clock are searched collectively within RADIUS_KM (default 15 km)
+and 2 s of --near and --time, and the fix is solved from the satellites measured at that optimum
+(DESIGN.md 4.2k); the report gains 'path' and, where the search ran, a 'collective' entry.
 
 There is no recording in this repository (data/test.bin is absent from the reference
 checkout, SURVEY F2, and too short for a fix even upstream): tests/test_run_file.py writes a
@@ -251,10 +254,11 @@ def parse_time(text, ephs):
 
 
 def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, frontend=None, excise=False,
-             blank=False, cancel=None):
+             blank=False, cancel=None, collective_km=None):
     """--snapshot: gpsmi.snapshot.snapshot_fix on the first `seconds` behind `start_stream`, read
     and filtered block by block as run() feeds its receiver.  `cancel`: --cancel's C/N0 threshold
-    (snapshot.measure's `cancel`); None leaves everything as it is without the flag."""
+    (snapshot.measure's `cancel`); None leaves everything as it is without the flag.
+    `collective_km`: --collective's radius (snapshot_fix's collective=True within it); None: not asked for."""
     from gpsmi import ingest, position as P, snapshot as S
     from gpsmi.acquisition import Acquisition
     from gpsmi.conditioning import Conditioner
@@ -272,7 +276,9 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
             stats = {}
             fix, meas, ms = S.snapshot_fix(acq, np.concatenate(blocks)[:need], ephemerides, t_gps,
                                            pos=None if near is None else np.array(P.geo_to_ecef(*near)),
-                                           cancel=cancel, stats=stats)
+                                           cancel=cancel, stats=stats,
+                                           **({} if collective_km is None else
+                                              {'collective': True, 'collective_cfg': {'radius_m': 1.0e3 * collective_km}}))
             wall = time.perf_counter() - t0
         finally:
             cond.close()
@@ -284,6 +290,16 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
                              'cn0_dbhz': None if np.isnan(m['cn0_dbhz']) else round(float(m['cn0_dbhz']), 2),
                              'source': m['source'].decode()} for m in meas],
            'ok': bool(fix.ok), 'reason': fix.reason, 'satellites': fix.prns, 'dropped': fix.dropped}
+    if collective_km is not None:
+        out['path'] = fix.path
+        c = stats.get('collective')
+        if c is not None:
+            geo = P.ecef_to_geo(c['ecef'])
+            out['collective'] = {'radius_km': collective_km, 'prns': c['prns'], 'margin': round(c['margin'], 2),
+                                 'score': round(c['score'], 3), 'clock_lag': round(c['lag'], 3),
+                                 'lat_deg': round(float(geo[0]), 6), 'lon_deg': round(float(geo[1]), 6),
+                                 't_gps': round(c['t_gps'], 4), 'z': [round(float(v), 2) for v in c['z']],
+                                 'level_ms': [round(float(v), 3) for v in c['level_ms']]}
     if cancel is not None:
         out['cancelled'] = [{'prn': int(r['prn']), 'n_windows': int(r['n_windows']), 'n_skipped': int(r['n_skipped']),
                              'removed': round(float(r['energy_removed'] / r['energy_in']), 5) if r['energy_in'] > 0 else 0.0}
@@ -307,6 +323,11 @@ def print_snapshot(out):
     for r in s.get('cancelled', []):
         print(f"  cancelled PRN {r['prn']:2d}: {r['removed']:.4f} of the power in {r['n_windows']} code periods "
               f"({r['n_skipped']} skipped)")
+    c = s.get('collective')
+    if c is not None:
+        print(f"  collective search within {c['radius_km']} km over PRNs {c['prns']}: peak {c['margin']} robust sigma above "
+              f"the map at {c['lat_deg']:.6f} N {c['lon_deg']:.6f} E, GPS time {c['t_gps']} s, clock lag {c['clock_lag']}; "
+              f"per satellite {c['z']}; levels {c['level_ms']} ms")
     for m in s['measurements']:
         cn0 = 'n/a' if m['cn0_dbhz'] is None else f"{m['cn0_dbhz']:.1f}"
         print(f"  PRN {m['prn']:2d}  sample {m['sample']:8d}  code_phase {m['code_phase']:9.4f}  f_hz {m['f_hz']:+9.2f}  "
@@ -435,6 +456,9 @@ def main():
     ap.add_argument('--cancel', type=float, nargs='?', const=40.0, default=None, metavar='DBHZ',
                     help='with --snapshot: cancel the satellites measured at or above DBHZ (default 40) and measure '
                          'the others on what is left (DESIGN.md 4.2j)')
+    ap.add_argument('--collective', type=float, nargs='?', const=15.0, default=None, metavar='RADIUS_KM',
+                    help='with --snapshot and --near: when fewer than five satellites are measured, search position, '
+                         'coarse time and clock collectively within RADIUS_KM (default 15) of --near (DESIGN.md 4.2k)')
     ap.add_argument('--time', default=None,
                     help='with --snapshot: time of the first sample read, GPS seconds of week or a UTC timestamp, within 30 s')
     ap.add_argument('--near', default=None, metavar='LAT,LON[,H]',
@@ -463,8 +487,10 @@ def main():
             if len(near) not in (2, 3):
                 ap.error('--near LAT,LON[,H]')
             near = (near + [0.0])[:3]
+        if a.collective is not None and (near is None or not 0.1 <= a.collective <= 100.0):
+            ap.error('--collective [RADIUS_KM]: needs --near, 0.1 .. 100 km')
         out = snapshot(a.recording, a.snapshot, eph, parse_time(a.time, eph), near, a.start_stream, frontend,
-                       a.excise, a.blank, a.cancel)
+                       a.excise, a.blank, a.cancel, a.collective)
         if a.json:
             print(json.dumps(out))
         else:
@@ -474,6 +500,8 @@ def main():
         ap.error('--time / --near need --snapshot SECONDS')
     if a.cancel is not None:
         ap.error('--cancel needs --snapshot SECONDS')
+    if a.collective is not None:
+        ap.error('--collective needs --snapshot SECONDS')
     out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise,
               frontend, a.blank, a.deep_acq, a.refine, a.track, a.weak_fix, a.save_ephemeris)
     if a.json:
