@@ -147,6 +147,7 @@ int gpsmi_abi_sizeof(int which) {
         case 17: return (int)sizeof(gpsmi_collective_sat);
         case 18: return (int)sizeof(gpsmi_collective_grid);
         case 19: return (int)sizeof(gpsmi_collective_cell);
+        case 21: return (int)sizeof(gpsmi_nul_cfg);
         default: return -1;
     }
 }

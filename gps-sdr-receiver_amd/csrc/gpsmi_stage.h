@@ -1,4 +1,4 @@
-// The host skeleton of a conditioning handle (gpsmi_fe, gpsmi_ifx, gpsmi_pb): the
+// The host skeleton of a conditioning handle (gpsmi_fe, gpsmi_ifx, gpsmi_pb, gpsmi_nul): the
 // stream and the timing events, create / destroy, and for the block filters the input format, the
 // staged host entry and the argument checks of a call.  The kernels and what a handle computes stay
 // in its own file.
@@ -89,15 +89,17 @@ struct StagedIO {
     }
 };
 
-// What the block filters (`blk` of gpsmi_ifx and gpsmi_pb) share: blocks of block_samples samples in
-// one of two input formats, complex64 out.
+// What the block filters (`blk` of gpsmi_ifx, gpsmi_pb and gpsmi_nul) share: blocks of block_samples
+// samples in one of two input formats, complex64 out.  fan_in: input blocks per output block (the
+// antennas of gpsmi_nul).
 struct BlockStage {
     int block_samples = 0;
     int fmt = GPSMI_IQ_C64;
+    int fan_in = 1;
     StagedIO io;                             // host entry: staged input and output
 
     size_t in_bytes(int nb) const {
-        return (size_t)nb * block_samples * (fmt == GPSMI_IQ_U8 ? sizeof(uint16_t) : sizeof(float2));
+        return (size_t)nb * block_samples * fan_in * (fmt == GPSMI_IQ_U8 ? sizeof(uint16_t) : sizeof(float2));
     }
     size_t out_bytes(int nb) const { return (size_t)nb * block_samples * sizeof(float2); }
 

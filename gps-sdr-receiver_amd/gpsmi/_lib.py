@@ -39,6 +39,11 @@ class PbCfg(C.Structure):
                 ('post', C.c_int32), ('max_frac', C.c_float), ('device', C.c_int32)]
 
 
+class NulCfg(C.Structure):
+    _fields_ = [('block_samples', C.c_int32), ('antennas', C.c_int32), ('load', C.c_float),
+                ('min_gain_db', C.c_float), ('device', C.c_int32), ('reserved', C.c_int32)]
+
+
 class RefineHit(C.Structure):
     _fields_ = [('prn', C.c_int32), ('delay', C.c_int32), ('freq_hz', C.c_double)]
 
@@ -186,6 +191,8 @@ EXPORTS = [
     'gpsmi_fe_push_dev', 'gpsmi_fe_flush', 'gpsmi_fe_last_ms',
     'gpsmi_pb_create', 'gpsmi_pb_destroy', 'gpsmi_pb_set_input_format', 'gpsmi_pb_reset',
     'gpsmi_pb_apply', 'gpsmi_pb_apply_dev', 'gpsmi_pb_last_ms',
+    'gpsmi_nul_create', 'gpsmi_nul_destroy', 'gpsmi_nul_set_input_format',
+    'gpsmi_nul_apply', 'gpsmi_nul_apply_dev', 'gpsmi_nul_last_ms',
 ]
 
 _lib = None
@@ -320,6 +327,12 @@ def load():
         'gpsmi_pb_apply': [vp, vp, vp, C.c_int, vp, vp, vp],
         'gpsmi_pb_apply_dev': [vp, vp, vp, C.c_int, vp, vp, vp],
         'gpsmi_pb_last_ms': [vp, P(f32)],
+        'gpsmi_nul_create': [P(NulCfg), P(vp)],
+        'gpsmi_nul_destroy': [vp],
+        'gpsmi_nul_set_input_format': [vp, C.c_int],
+        'gpsmi_nul_apply': [vp, vp, vp, C.c_int, vp, vp, vp],
+        'gpsmi_nul_apply_dev': [vp, vp, vp, C.c_int, vp, vp, vp],
+        'gpsmi_nul_last_ms': [vp, P(f32)],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -338,6 +351,8 @@ def load():
     got += [lib.gpsmi_abi_sizeof(i) for i in (13, 14, 15)]
     want += [COLLECTIVE_SAT_DTYPE.itemsize, C.sizeof(CollectiveGrid), COLLECTIVE_CELL_DTYPE.itemsize]
     got += [lib.gpsmi_abi_sizeof(i) for i in (17, 18, 19)]
+    want += [C.sizeof(NulCfg)]
+    got += [lib.gpsmi_abi_sizeof(21)]
     if want != got:
         raise EngineError(f'ABI mismatch between gpsmi/_lib.py {want} and '
                           f'libgpsmi.so {got}')

@@ -2,9 +2,10 @@
 
 ``BlockFilter`` is the wrapper of a handle that turns blocks of cfg.ngps samples (complex64, or the
 recorder's uint16) into complex64 blocks of the same length: ``excision.Excision`` (gpsmi_ifx_*) and
-``blanking.PulseBlanker`` (gpsmi_pb_*) are its two subclasses.  ``Conditioner`` is the chain
-recording -> (excision) -> (blanking) -> the complex64 block the engines see, one block per call
-(DESIGN.md section 3).
+``blanking.PulseBlanker`` (gpsmi_pb_*) are subclasses, and ``nulling.NullSteer`` (gpsmi_nul_*), whose
+input is the blocks of several antennas.  ``Conditioner`` is the chain recording -> (null steering)
+-> (excision) -> (blanking) -> the complex64 block the engines see, one block per call (DESIGN.md
+section 3).
 """
 import ctypes as C
 
@@ -93,36 +94,50 @@ def _wanted(arg):
 
 
 class Conditioner:
-    """excise / blank: True (a stage of default settings, made and closed here), an Excision / a
-    PulseBlanker of the caller's (used, not closed), or None / False (off).  raw_u8: apply() takes
-    the recorder's uint16 blocks; with any stage on it returns complex64 (out_raw_u8 False).  With
-    both, a block is excised, then blanked: a tone raises every sample's power and would hide the
-    pulses from the blanker, while the pulses only add a flat level to the excision's spectrum; the
-    PulseBlanker then takes complex64 (raw_u8=False).  A chain without a stage is falsy and passes
-    every block through."""
+    """excise / blank / null: True (a stage of default settings, made and closed here), an Excision /
+    a PulseBlanker / a NullSteer of the caller's (used, not closed), or None / False (off).  raw_u8:
+    apply() takes the recorder's uint16 blocks; with any stage on it returns complex64 (out_raw_u8
+    False).  The order is null steering, excision, blanking, and only the first stage takes the raw
+    format (the others: raw_u8=False).  Null steering goes first: it needs every antenna, and what it
+    leaves is one complex64 block like any other; with it apply() takes [antennas][n].  A tone raises
+    every sample's power and would hide the pulses from the blanker, while the pulses only add a
+    flat level to the excision's spectrum: excision before blanking.  A chain without a stage is falsy
+    and passes every block through."""
 
-    def __init__(self, cfg, raw_u8, excise=None, blank=None):
+    def __init__(self, cfg, raw_u8, excise=None, blank=None, null=None, antennas=1):
         self.cfg, self.raw_u8 = cfg, bool(raw_u8)
-        self.excision = self.blanker = self.last = None
+        self.antennas = int(antennas)
+        self.nuller = self.excision = self.blanker = self.last = None
         self._owned, self._pinned, self._dev = [], None, []
+        if _wanted(null):
+            from .nulling import NullSteer
+            if self.antennas < 2:
+                raise ValueError('null steering needs antennas >= 2')
+            self.nuller = self._stage(NullSteer, null, self.raw_u8, antennas=self.antennas)
+            if self.nuller.antennas != self.antennas:
+                raise ValueError('the NullSteer does not match the number of antennas')
+        elif self.antennas != 1:
+            raise ValueError('several antennas need null=...: nothing else combines them')
         if _wanted(excise):
             from .excision import Excision
-            self.excision = self._stage(Excision, excise, self.raw_u8)
+            self.excision = self._stage(Excision, excise, self.raw_u8 and self.nuller is None)
         if _wanted(blank):
-            from .blanking import PulseBlanker         # (behind the excision: its complex64)
-            self.blanker = self._stage(PulseBlanker, blank, self.raw_u8 and self.excision is None)
-        self.stages = [s for s in (self.excision, self.blanker) if s is not None]
+            from .blanking import PulseBlanker         # (behind the stages before it: their complex64)
+            self.blanker = self._stage(PulseBlanker, blank,
+                                       self.raw_u8 and self.nuller is None and self.excision is None)
+        self.stages = [s for s in (self.nuller, self.excision, self.blanker) if s is not None]
         self.out_raw_u8 = self.raw_u8 and not self.stages
         n = cfg.ngps
         if self.stages:
             self._pinned = PinnedArray((n,), np.complex64)
-        if len(self.stages) == 2:                       # input, excised, blanked
-            self._dev = [DeviceBuffer(n * b, cfg.device) for b in (2 if self.raw_u8 else 8, 8, 8)]
+        if len(self.stages) > 1:                        # the input, then one block behind every stage
+            sizes = [n * self.antennas * (2 if self.raw_u8 else 8)] + [n * 8] * len(self.stages)
+            self._dev = [DeviceBuffer(b, cfg.device) for b in sizes]
 
-    def _stage(self, cls, arg, raw_u8):
+    def _stage(self, cls, arg, raw_u8, **kw):
         stage = arg
         if arg is True:
-            stage = cls(self.cfg, raw_u8=raw_u8)
+            stage = cls(self.cfg, raw_u8=raw_u8, **kw)
             self._owned.append(stage)
         if stage.raw_u8 != raw_u8 or stage.n != self.cfg.ngps:
             raise ValueError(f'the {cls.__name__} does not match raw_u8 / the block length')
@@ -132,20 +147,21 @@ class Conditioner:
         return bool(self.stages)
 
     def apply(self, block):
-        """One block -> the block the engines see: `block` itself without a stage, else the chain's
-        one page-locked complex64 block (use it, or copy it, before the next call)."""
+        """One block ([antennas][n] with null steering) -> the block the engines see: `block` itself
+        without a stage, else the chain's one page-locked complex64 block (use it, or copy it, before
+        the next call)."""
         if len(self.stages) == 1:
             block = self.stages[0].apply(block, out=self._pinned.array)
-        elif self.stages:                               # one copy in, both stages on the device, one out
+        elif self.stages:                               # one copy in, every stage on the device, one out
             want = np.uint16 if self.raw_u8 else np.complex64
             x = np.ascontiguousarray(block)
-            if x.dtype != want or x.size != self.cfg.ngps:
-                raise ValueError(f'one block of {self.cfg.ngps} {np.dtype(want).name} samples expected')
-            d_in, d_mid, d_out = self._dev
-            d_in.upload(x)
-            self.excision.apply_dev(d_in.ptr, d_mid.ptr, 1)
-            self.blanker.apply_dev(d_mid.ptr, d_out.ptr, 1)
-            block = d_out.download_into(self._pinned.array)
+            if x.dtype != want or x.size != self.cfg.ngps * self.antennas:
+                raise ValueError(f'one block of {self.cfg.ngps} {np.dtype(want).name} samples '
+                                 f'(of each of {self.antennas} antennas) expected')
+            self._dev[0].upload(x)
+            for stage, d_in, d_out in zip(self.stages, self._dev, self._dev[1:]):
+                stage.apply_dev(d_in.ptr, d_out.ptr, 1)
+            block = self._dev[-1].download_into(self._pinned.array)
         self.last = block
         return block
 

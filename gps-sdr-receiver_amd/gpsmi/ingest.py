@@ -76,12 +76,25 @@ def read_frontend_blocks(path, fe, chunk_samples=1 << 20):
                 return
 
 
+def read_array_blocks(paths, ngps=65536, start_stream=0):
+    """One raw file per antenna of a coherent recorder, read in step: uint16 [antennas][NGPS] per
+    block; the shortest file ends the stream."""
+    for rows in zip(*(read_raw_blocks(p, ngps, start_stream) for p in paths)):
+        yield np.stack(rows)
+
+
 @contextmanager
-def open_blocks(path, cfg, start_stream=0, frontend=None):
+def open_blocks(path, cfg, start_stream=0, frontend=None, antennas=()):
     """The blocks of a recording behind its first `start_stream` ones, as ``(blocks, raw_u8)``:
     read_raw_blocks and True for the recorder's own format (frontend None), else
     read_frontend_blocks through a frontend.FrontEnd(cfg, **frontend) that lives as long as the
-    context, and False."""
+    context, and False.  antennas: the files of the further antennas of a coherent recorder (the
+    recorder's own format only); the blocks are then [1 + len(antennas)][NGPS], `path` first."""
+    if antennas:
+        if frontend is not None:
+            raise ValueError('several antennas are read in the recorder\'s own format only')
+        yield read_array_blocks([path, *antennas], cfg.ngps, start_stream), True
+        return
     if frontend is None:
         yield read_raw_blocks(path, cfg.ngps, start_stream), True
         return

@@ -23,7 +23,8 @@ UDP_PORT = 61431                # gpsglob.py:82
 
 
 class Receiver:
-    def __init__(self, cfg=None, sat_all=None, raw_u8=False, report_lag=0, excise=None, blank=None):
+    def __init__(self, cfg=None, sat_all=None, raw_u8=False, report_lag=0, excise=None, blank=None,
+                 antennas=1, null=None):
         """raw_u8: feed() takes the recorder's uint16 (Q << 8 | I) blocks exactly as streamData
         reads them from the file (gpsrecv.py:162-173); the decode to complex64 happens inside
         the GPU kernels, every datagram is byte-identical to the complex64 path's.
@@ -38,12 +39,17 @@ class Receiver:
         blanking).  With both, each block is excised, then blanked, on the device (one copy in, one
         out): a tone raises every sample's power and would hide the pulses from the blanker, while
         the pulses only add a flat level to the excision's spectrum.  The PulseBlanker then takes
-        complex64 (raw_u8=False).  None, the default: no blanking.  The chain is `conditioner`
-        (conditioning.Conditioner); its `last` is the block the engines saw."""
+        complex64 (raw_u8=False).  None, the default: no blanking.
+        antennas = A > 1 with null = True or a nulling.NullSteer: feed() takes [A][NGPS], the blocks
+        of A coherent antennas, and null steering (power inversion, antenna 0 the reference) combines
+        them into one complex64 block ahead of the other stages.  The defaults (1, None): one antenna,
+        everything as without the arguments.  The chain is `conditioner` (conditioning.Conditioner);
+        its `last` is the block the engines saw."""
         from .conditioning import Conditioner
         self.cfg = cfg or Config()
-        self.conditioner = Conditioner(self.cfg, raw_u8, excise, blank)
+        self.conditioner = Conditioner(self.cfg, raw_u8, excise, blank, null, antennas)
         self.excision, self.blanker = self.conditioner.excision, self.conditioner.blanker
+        self.nuller = self.conditioner.nuller
         self.raw_u8 = self.conditioner.out_raw_u8     # (the engines see the filters' complex64)
         self.sat_all = list(SAT_ALL if sat_all is None else sat_all)
         self.acq = Acquisition(self.cfg, raw_u8=self.raw_u8)
@@ -74,7 +80,8 @@ class Receiver:
             self.running = False
 
     def feed(self, data, skip=0):
-        """One block (complex64[NGPS], or uint16[NGPS] when raw_u8); `skip` = streams lost before it
+        """One block (complex64[NGPS], or uint16[NGPS] when raw_u8; [antennas][NGPS] with null
+        steering); `skip` = streams lost before it
         (gpsrecv.py:469-471).  Returns the pickled hand-off or None."""
         c = self.cfg
         # (one page-locked block serves every call: the acquisition reads it before it returns,

@@ -66,7 +66,7 @@ const char* gpsmi_version(void);
 /* sizeof() of the ABI structs as compiled: 0 cfg, 1 peak, 2 trk_state, 3 trk_out,
  * 4 offsetof(trk_out, code_phase), 5 fe_cfg, 6 pb_cfg, 7 refine_hit, 8 refine_cfg, 9 refine_out,
  * 10 wtrk_cfg, 11 wtrk_state, 12 wtrk_bit, 13 cancel_sat, 14 cancel_cfg, 15 cancel_out, 17 collective_sat,
- * 18 collective_grid, 19 collective_cell (16 is not assigned); -1 otherwise.  Lets a binding verify its own struct declarations before the first real call.  */
+ * 18 collective_grid, 19 collective_cell, 21 nul_cfg (16 and 20 are not assigned); -1 otherwise.  Lets a binding verify its own struct declarations before the first real call.  */
 int gpsmi_abi_sizeof(int which);
 /* Kernel-variant selection and tuning thresholds, visible through the ABI (round 4: they used to
  * be environment variables read inside gpsmi_*_create, invisible to a C caller; the variables
@@ -946,6 +946,73 @@ int gpsmi_pb_apply(gpsmi_pb* h, const void* iq, float* out, int nb, int32_t* cou
 int gpsmi_pb_apply_dev(gpsmi_pb* h, const void* d_iq, void* d_out, int nb, int32_t* counts,
                        float* floors, uint32_t* masks);
 int gpsmi_pb_last_ms(gpsmi_pb* h, float* ms);
+
+/* ========================================================================
+ * Null steering (power inversion): an opt-in input stage against interference that is wide in
+ * frequency and continuous in time, for recordings of A coherent, sample-aligned antennas, ahead of
+ * everything else (float64 restatement: tests/nul_ref.py).  It minimises the output
+ * power with the gain of antenna 0 (the reference element) held at one; no calibration, no antenna
+ * positions, no satellite directions.  A call takes A antennas x nb consecutive blocks of
+ * n = block_samples samples, antenna-major: [A][nb * n], complex64 or the recorder's uint16 decoded
+ * as gpsmi_dev_unpack_u8iq does.  Every block is worked on alone (no carry, no state):
+ *   covariance C[a][b] = sum_i x_a[i] conj(x_b[i]), a >= b, the float32 samples converted to float64
+ *              (every product is exact), the sums float64 in this order: the block is cut into
+ *              slices of 8192 samples (the last one may be shorter); in a slice, lane t of 256 takes
+ *              the samples 2048 r + 8 t .. 2048 r + 8 t + 7 for r = 0, 1, 2, 3 (those the slice
+ *              has) in ascending order, from zero, per sample
+ *                  re += ar * br;  re += ai * bi;  im += ai * br;  im -= ar * bi;
+ *              the 256 lane sums are added as a binary tree of neighbours (lanes 2k and 2k + 1, then
+ *              pairs of those, eight levels); the slice sums are added in ascending slice order,
+ *              starting from slice 0's.  The order depends on n alone;
+ *   loading    R = C / n + delta I, delta = load * (sum_a C[a][a] / n) / A (the trace summed in
+ *              ascending a, each term divided by n first);
+ *   weights    R = L L^H by Cholesky without pivoting, in float64, column by column j = 0 .. A - 1:
+ *              d = R[j][j] - sum_{k<j} |L[j][k]|^2, L[j][j] = sqrt(d), then for i > j
+ *              L[i][j] = (R[i][j] - sum_{k<j} L[i][k] conj(L[j][k])) / L[j][j]; every sum subtracts
+ *              its terms one at a time in ascending k, nothing is fused; complex products are
+ *              (ar br - ai bi) + j (ar bi + ai br) with conj() a sign flip; L y = e0 forward
+ *              (y[i] = -(sum_{k<i} L[i][k] y[k]) / L[i][i], y[0] = 1 / L[0][0]) and L^H u = y backward
+ *              (u[i] = (y[i] - sum_{k>i} conj(L[k][i]) u[k]) / L[i][i], i descending, k ascending);
+ *              w[0] = 1, w[a] = u[a] / Re u[0]; predicted gain g = (C[0][0] / n) * Re u[0], the
+ *              power of antenna 0 over the output power; gain_db = (float)(10 log10 g);
+ *   decision   a pivot d that is not positive and finite (an all-zero block: its first pivot is
+ *              0), or 10 log10 g < min_gain_db: the block passes through: the output is
+ *              antenna 0's block bit for bit (decoded for u8), flag 0, weights e0; gain_db is 0
+ *              when the solve did not finish.  Otherwise flag 1;
+ *   apply      w32 = complex64(w); y[i] = sum_a conj(w32[a]) x_a[i] in float32, ascending a from
+ *              antenna 0's term, each term (wr xr + wi xi) + j (wr xi - wi xr): two products and
+ *              one add / subtract each, then one add per component into y; nothing is fused.
+ * The covariance runs on several workgroups per block (one per slice), a second kernel adds the
+ * slice sums and solves with one thread per block on the device, a third applies; no atomics.  One
+ * thread writes each output word: the bits do not depend on the grid, on nb or on the cut of the
+ * input into calls.  flags int32 [nb], gain_db float32 [nb] and weights float64 [nb][A][2] (re, im
+ * of w) are host arrays, each may be null.  Input and output must not overlap (GPSMI_E_ARG); device
+ * complex64 input and the output must be 16-byte aligned, device u8 input 4-byte aligned.  Both
+ * calls return when the work is done; gpsmi_nul_last_ms reports its device time.  Argument errors (a
+ * null cfg or handle, a bad n, antennas outside 2..8, a NaN or negative load or min_gain_db,
+ * nb <= 0) are GPSMI_E_ARG and need no GPU; a failed allocation is GPSMI_E_NOMEM and leaves the
+ * handle usable.
+ * ======================================================================== */
+typedef struct gpsmi_nul gpsmi_nul;
+typedef struct gpsmi_nul_cfg {
+    int32_t block_samples;      /* n: multiple of 32, >= 2048 (65536, 130944, ...)      */
+    int32_t antennas;           /* A: 2 .. 8, antenna 0 is the reference element         */
+    float   load;               /* diagonal loading; 0 means 1e-6; not NaN, not negative */
+    float   min_gain_db;        /* 0 means 3.0; not NaN, not negative                    */
+    int32_t device;
+    int32_t reserved;           /* 0 */
+} gpsmi_nul_cfg;
+int gpsmi_nul_create(const gpsmi_nul_cfg* cfg, gpsmi_nul** out);
+int gpsmi_nul_destroy(gpsmi_nul* h);
+/* GPSMI_IQ_C64 (default) or GPSMI_IQ_U8 (the recorder's uint16, decoded on load) */
+int gpsmi_nul_set_input_format(gpsmi_nul* h, int fmt);
+/* host iq ([A][nb * n] samples in the input format) -> host out (complex64 [nb * n])           */
+int gpsmi_nul_apply(gpsmi_nul* h, const void* iq, float* out, int nb, int32_t* flags, float* gain_db,
+                    double* weights);
+/* the same from device memory to device memory (the result arrays are host memory)             */
+int gpsmi_nul_apply_dev(gpsmi_nul* h, const void* d_iq, void* d_out, int nb, int32_t* flags,
+                        float* gain_db, double* weights);
+int gpsmi_nul_last_ms(gpsmi_nul* h, float* ms);
 
 /* ========================================================================
  * Multi-GPU: one process per GPU; SVs / blocks are sharded by the host and

@@ -5,6 +5,7 @@ gpseval) as one command on the GPU path.
 
     python tools/run_file.py <recording.bin> [--seconds S] [--start-stream K] [--save-pickle P]
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--blank] [--json]
+                             [--antenna FILE ... --null]
                              [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track [--weak-fix]]]]
                              [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]]]
 
@@ -24,14 +25,19 @@ the first five blocks of the same file, on one host core.  --excise removes narr
 interference (continuous-wave tones) from every block on the GPU before the receiver sees it
 (pipeline.Receiver(excise=True)).  --blank zeroes pulsed and swept (chirp)
 interference sample by sample on the GPU (pipeline.Receiver(blank=True)); with
---excise the tones are removed first, then the pulses.  --format (c64, u8iq, sc8, sc16, r8), --fs (the
+--excise the tones are removed first, then the pulses.  --antenna FILE (repeatable) names the files
+of the further channels of a coherent multi-antenna recorder, sample-aligned with the recording
+(antenna 0, the reference element), and --null combines them by null steering on the GPU ahead of
+everything else (pipeline.Receiver(antennas=A, null=True)): a defence against
+jammers that are wide in frequency and continuous in time; the flag (1 nulled, 0 antenna 0 passed
+through) and the predicted gain of every block are printed, with --json under 'null'.  --format (c64, u8iq, sc8, sc16, r8), --fs (the
 input rate in Hz), --if (the IF of real input or the tuner offset of complex input, Hz) and
 --conjugate read a recording of another front end: frontend.FrontEnd decodes, mixes, filters and
 resamples it on the GPU to complex64 blocks at 2.048 Msps, which Receiver(raw_u8=False) takes
 (DESIGN.md 4.2c); --start-stream then skips output blocks.  Without them the path above is unchanged.
 --deep-acq SECONDS adds a second acquisition pass at the end, over the first SECONDS of the recording
 and for the PRNs the 4-ms sweep did not acquire: Acquisition.sweepDeepSats, the non-coherent search
-with the code Doppler compensated (DESIGN.md 4.2e).  It prints PRN, Doppler bin, code delay and
+with the code Doppler compensated (DESIGN.md 4.2l).  It prints PRN, Doppler bin, code delay and
 normMaxCorr of what it finds and changes nothing else: the satellites are not handed to tracking.
 --refine (with --deep-acq) refines what the second pass found on the same data: Acquisition.refineHits
  integrates coherently over each 20-ms data bit and prints the fine Doppler, the bit
@@ -347,7 +353,7 @@ def print_snapshot(out):
 
 def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, cpu_acq=False, report_lag=16,
         excise=False, frontend=None, blank=False, deep_acq=None, refine=False, track=False, weak_fix=False,
-        save_ephemeris=None):
+        save_ephemeris=None, antennas=(), null=False):
     """frontend: None (the recorder's u8 format at 2.048 Msps) or a dict of frontend.FrontEnd's
     keyword arguments (fs_in, fmt, if_hz, conjugate).  deep_acq: None, or the seconds of the
     recording's start that deep_acquisition searches for the PRNs the sweep did not acquire; refine:
@@ -355,15 +361,21 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
     weak_fix (with deep_acq, refine and track): the receiver runs inside pipeline.WeakAssist, which
     searches the first deep_acq seconds behind the cold sweep, tracks what it confirms and merges
     those channels' subframes and code phases into the datagrams the solver is fed (DESIGN.md 4.2h);
-    the report gains 'weak_fix'.  save_ephemeris: a path for the ephemerides the run decoded."""
+    the report gains 'weak_fix'.  save_ephemeris: a path for the ephemerides the run decoded.
+    antennas: the files of the further channels of a coherent multi-antenna recorder, read in step
+    with `path` (antenna 0, the reference element); null: null steering combines them ahead of
+    everything else (pipeline.Receiver(antennas=A, null=True)) and the report gains
+    'null': the flag (1 nulled, 0 passed through) and the predicted gain in dB of every block."""
     from gpsmi import ingest, position as P
     from gpsmi.engine import Config
     from gpsmi.pipeline import Receiver, save_results
     cfg = Config()
     # (a recording: the datagrams may come out `report_lag` blocks behind the block they belong to, the
     # reader then runs ahead of the GPU instead of stalling it once a second -- pipeline.Receiver)
-    with ingest.open_blocks(path, cfg, start_stream, frontend) as (source, raw_u8):
-        rx = Receiver(cfg, raw_u8=raw_u8, report_lag=report_lag, excise=excise, blank=blank)
+    with ingest.open_blocks(path, cfg, start_stream, frontend, antennas) as (source, raw_u8):
+        array = dict(antennas=1 + len(antennas), null=True) if null else {}
+        rx = Receiver(cfg, raw_u8=raw_u8, report_lag=report_lag, excise=excise, blank=blank, **array)
+        null_flags, null_gain = [], []
         if weak_fix:
             from gpsmi.pipeline import WeakAssist
             top = WeakAssist(rx, seconds=deep_acq)
@@ -376,6 +388,9 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
         for raw in source:
             top.feed(raw)
             n_blocks += 1
+            if null:
+                null_flags.append(int(rx.nuller.last_flags[0]))
+                null_gain.append(round(float(rx.nuller.last_gain_db[0]), 2))
             if found is None and not rx.sweep_all_freq:
                 found = list(rx.found_sats)
             for dg in top.result_list[n_dg:]:          # (every datagram, in order: RESULT_LIST)
@@ -409,6 +424,9 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
                            'height_m': round(float(alt), 1), 'ecef_m': [round(float(v), 2) for v in mean],
                            'from': f'mean of the last {len(late)} fixes',
                            'sd_of_mean_m': round(float(np.linalg.norm(late.std(axis=0)) / np.sqrt(len(late))), 2)}
+    if null:
+        out['null'] = {'antennas': 1 + len(antennas), 'flags': null_flags, 'gain_db': null_gain,
+                       'blocks_nulled': int(sum(null_flags))}
     if weak is not None:
         out['weak_fix'] = weak
     if cpu_acq:
@@ -442,7 +460,7 @@ def main():
     ap.add_argument('--conjugate', action='store_true', help='mirror the spectrum of complex input')
     ap.add_argument('--deep-acq', type=float, default=None, metavar='SECONDS',
                     help='afterwards search the first SECONDS for the PRNs the sweep missed, code Doppler '
-                         'compensated (DESIGN.md 4.2e); printed only')
+                         'compensated (DESIGN.md 4.2l); printed only')
     ap.add_argument('--refine', action='store_true',
                     help='with --deep-acq: refine its hits (fine Doppler, bit edge, code phase, C/N0; DESIGN.md 4.2f)')
     ap.add_argument('--track', action='store_true',
@@ -463,6 +481,12 @@ def main():
                     help='with --snapshot: time of the first sample read, GPS seconds of week or a UTC timestamp, within 30 s')
     ap.add_argument('--near', default=None, metavar='LAT,LON[,H]',
                     help='with --snapshot: the position as far as known (degrees, metres), within 50 km')
+    ap.add_argument('--antenna', action='append', default=[], metavar='FILE',
+                    help='the file of a further antenna of a coherent recorder, sample-aligned with the '
+                         'recording (repeatable; the recording is antenna 0, the reference element)')
+    ap.add_argument('--null', action='store_true',
+                    help='null steering over the antennas against wideband jamming, ahead of everything '
+                         'else (DESIGN.md 4.2l)')
     ap.add_argument('--json', action='store_true', help='one JSON line instead of text')
     a = ap.parse_args()
     if a.refine and not a.deep_acq:
@@ -498,12 +522,16 @@ def main():
         return
     if a.time is not None or a.near is not None:
         ap.error('--time / --near need --snapshot SECONDS')
+    if bool(a.antenna) != a.null:
+        ap.error('--antenna FILE (the further channels) and --null go together')
+    if a.antenna and (frontend is not None or a.deep_acq or a.cpu_acq):
+        ap.error('--antenna: the recorder\'s own format, without --deep-acq / --cpu-acq')
     if a.cancel is not None:
         ap.error('--cancel needs --snapshot SECONDS')
     if a.collective is not None:
         ap.error('--collective needs --snapshot SECONDS')
     out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise,
-              frontend, a.blank, a.deep_acq, a.refine, a.track, a.weak_fix, a.save_ephemeris)
+              frontend, a.blank, a.deep_acq, a.refine, a.track, a.weak_fix, a.save_ephemeris, a.antenna, a.null)
     if a.json:
         print(json.dumps(out))
         return
@@ -517,6 +545,11 @@ def main():
               f"(SD of mean {p['sd_of_mean_m']} m)")
     else:
         print('no position fix (too little signal for subframes 1-3 of four satellites, or no ephemerides)')
+    if 'null' in out:
+        u = out['null']
+        print(f"null steering over {u['antennas']} antennas: {u['blocks_nulled']} of {len(u['flags'])} blocks nulled")
+        for b, (f, g) in enumerate(zip(u['flags'], u['gain_db'])):
+            print(f"  block {b:4d}  flag {f}  gain {g:6.2f} dB")
     if 'weak_fix' in out:
         w = out['weak_fix']
         print(f"weak channels merged into the fix ({w['search_device_ms']} ms of search on the device): {len(w['channels'])}")
