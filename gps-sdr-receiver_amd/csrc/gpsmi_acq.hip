@@ -123,9 +123,11 @@ static int acq_upload(gpsmi_acq* h, const void* iq, size_t count) {
 static int acq_build(const gpsmi_cfg* cfg, gpsmi_acq* h) {
     h->direct = cfg->code_samples != kFftN;
     int rc = h->stream.create();
-    if (!rc) rc = h->order.create(hipEventDisableTiming);
-    if (!rc) rc = h->ev0.create();
-    if (!rc) rc = h->ev1.create();
+    // (order feeds hipStreamWaitEvent alone; ev0 / ev1 are stamps read behind gpsmi_acq_wait's stream
+    // synchronisation, and the result table comes down by a copy command of its own)
+    if (!rc) rc = h->order.create<Ev::AcqOrder, EventScope::DeviceOnly>();
+    if (!rc) rc = h->ev0.create<Ev::AcqStamp, EventScope::DeviceOnly>();
+    if (!rc) rc = h->ev1.create<Ev::AcqStamp, EventScope::DeviceOnly>();
     if (rc) return rc;
     std::vector<float2> tw;
     make_twiddles(tw);
@@ -143,7 +145,8 @@ static int acq_build(const gpsmi_cfg* cfg, gpsmi_acq* h) {
         GPSMI_HIP(hipHostMalloc((void**)&h->h_om[k], 65536 * sizeof(float), hipHostMallocDefault));
         GPSMI_HIP(hipHostMalloc((void**)&h->h_slot[k], (GPSMI_MAX_PRN + 1) * sizeof(int32_t),
                                 hipHostMallocDefault));
-        if ((rc = h->staged[k].create(hipEventDisableTiming))) return rc;
+        // (acq_stage waits on it before the HOST rewrites h_om / h_slot, which the device only read)
+        if ((rc = h->staged[k].create<Ev::AcqStaged, EventScope::DeviceOnly>())) return rc;
     }
     if (h->direct) {
         if ((rc = h->d_rep_time.reserve((size_t)(GPSMI_MAX_PRN + 1) * cfg->code_samples, "gpsmi_acq replicas")))

@@ -3,6 +3,7 @@
 // deleted, and its capacity travels with it, in elements of T.
 #pragma once
 #include "gpsmi_common.h"
+#include "gpsmi_event_scope.h"
 
 namespace gpsmi {
 
@@ -91,9 +92,16 @@ struct DevStream : DevHandle<hipStream_t, hipStreamDestroy> {
         return GPSMI_OK;
     }
 };
+// An event is created as the row W of the classification (gpsmi_event_scope.h) and names its scope S at
+// the call: create<Ev::TrkCopied, EventScope::HostVisible>().  A call that disagrees with the table
+// does not compile.  Whether the event records time is the row's.
 struct DevEvent : DevHandle<hipEvent_t, hipEventDestroy> {
-    int create(unsigned flags = hipEventDefault) {       // (hipEventDefault: what hipEventCreate passes)
-        GPSMI_HIP(hipEventCreateWithFlags(&h, flags));
+    template <Ev W, EventScope S>
+    int create() {
+        constexpr EventClass c = event_class(W);
+        static_assert(c.scope == S, "the scope named here is not the one of the event's row in gpsmi_event_scope.h");
+        GPSMI_HIP(hipEventCreateWithFlags(&h, (c.stamps ? hipEventDefault : hipEventDisableTiming) |
+                                                  (S == EventScope::DeviceOnly ? hipEventDisableSystemFence : 0u)));
         return GPSMI_OK;
     }
 };

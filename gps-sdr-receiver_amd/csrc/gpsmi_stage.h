@@ -21,8 +21,9 @@ struct StageSync {
 
     int create() {
         int rc = stream.create();
-        if (!rc) rc = ev0.create();
-        if (!rc) rc = ev1.create();
+        // (stamps alone, read behind finish()'s stream synchronisation)
+        if (!rc) rc = ev0.create<Ev::StageStamp, EventScope::DeviceOnly>();
+        if (!rc) rc = ev1.create<Ev::StageStamp, EventScope::DeviceOnly>();
         return rc;
     }
     int begin() {                            // ahead of a call's first launch

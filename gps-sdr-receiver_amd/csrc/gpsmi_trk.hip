@@ -729,14 +729,21 @@ static int trk_build(const gpsmi_cfg* cfg, int max_ch, gpsmi_trk* h) {
     // fifth stream shares a queue with one of them -- which one differs from run to run -- and a step
     // whose epilogue or search queues behind the compute stream's kernels takes 0.33 ms instead of
     // 0.23 (GPU_MAX_HW_QUEUES=3 forces it; more queues than pipes cost as much: DESIGN.md 4.6).
-    rc = h->order.create(hipEventDisableTiming);
+    // The scope of each event is its row of gpsmi_event_scope.h (DESIGN.md 4.6 says who waits on what):
+    // only `copied` stands in front of a host read of device-written memory.  The others order one
+    // queue behind another or carry a stamp; made host-visible they would each write back and
+    // invalidate the caches at completion, two of them under the next batch's code-phase correlation.
+    rc = h->order.create<Ev::TrkOrder, EventScope::DeviceOnly>();
     for (auto& sl : h->slot) {
-        for (auto& e : sl.ev)
-            if (!rc) rc = e.create();
-        if (!rc) rc = sl.ready.create(hipEventDisableTiming);
-        if (!rc) rc = sl.copied.create(hipEventDisableTiming);
-        if (!rc) rc = sl.corr_done.create();        // (with timing: also used as a dispatch's stop event)
-        if (!rc) rc = sl.epi_done.create(hipEventDisableTiming);
+        for (auto& e : sl.ev)      // (stamps; gpsmi_trk_wait_prev synchronises on ev[3] / ev[2] to read stamps alone)
+            if (!rc) rc = e.create<Ev::TrkStamp, EventScope::DeviceOnly>();
+        if (!rc) rc = sl.ready.create<Ev::TrkReady, EventScope::DeviceOnly>();
+        if (!rc) rc = sl.copied.create<Ev::TrkCopied, EventScope::HostVisible>();
+        // corr_done (with timing: also a dispatch's stop event) is corr_stop as well, the stamp
+        // gpsmi_trk_wait_prev synchronises on when no copy is pending: only stamps are read behind it,
+        // never device-written memory, so it is device-only
+        if (!rc) rc = sl.corr_done.create<Ev::TrkCorrDone, EventScope::DeviceOnly>();
+        if (!rc) rc = sl.epi_done.create<Ev::TrkEpiDone, EventScope::DeviceOnly>();
     }
     if (rc) return rc;
     std::vector<float2> tw;
@@ -975,9 +982,11 @@ static int trk_stream_step(gpsmi_trk* h, const void* iq, size_t n, gpsmi_trk_out
     if (!h->up_stream) {
         rc = h->up_stream.create();
         for (int k = 0; k < 2; ++k) {
-            if (!rc) rc = h->up_done[k].create(hipEventDisableTiming);
-            if (!rc) rc = h->stage_free[k].create(hipEventDisableTiming);
-            if (!rc) rc = h->in_done[k].create();            // (with timing: also a dispatch's stop event)
+            if (!rc) rc = h->up_done[k].create<Ev::TrkUpDone, EventScope::DeviceOnly>();
+            if (!rc) rc = h->stage_free[k].create<Ev::TrkStageFree, EventScope::DeviceOnly>();
+            // (with timing: also a dispatch's stop event, the step's tail_stop.  Host-visible: behind
+            // trk_spin_wait on it the caller reads a page-locked `out` that the kernels stored into)
+            if (!rc) rc = h->in_done[k].create<Ev::TrkInDone, EventScope::HostVisible>();
         }
         if (rc) return rc;
     }
