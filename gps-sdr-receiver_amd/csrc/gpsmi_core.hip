@@ -148,6 +148,7 @@ int gpsmi_abi_sizeof(int which) {
         case 18: return (int)sizeof(gpsmi_collective_grid);
         case 19: return (int)sizeof(gpsmi_collective_cell);
         case 21: return (int)sizeof(gpsmi_nul_cfg);
+        case 23: return (int)sizeof(gpsmi_tfx_cfg);   // (20 and 22 stay unused: tests hold them to -1)
         default: return -1;
     }
 }

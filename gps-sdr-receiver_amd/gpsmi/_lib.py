@@ -44,6 +44,12 @@ class NulCfg(C.Structure):
                 ('min_gain_db', C.c_float), ('device', C.c_int32), ('reserved', C.c_int32)]
 
 
+class TfxCfg(C.Structure):
+    _fields_ = [('block_samples', C.c_int32), ('frame', C.c_int32), ('thresh_db', C.c_float),
+                ('dilate', C.c_int32), ('max_frac', C.c_float), ('keep_power', C.c_int32),
+                ('device', C.c_int32), ('reserved', C.c_int32)]
+
+
 class RefineHit(C.Structure):
     _fields_ = [('prn', C.c_int32), ('delay', C.c_int32), ('freq_hz', C.c_double)]
 
@@ -193,6 +199,8 @@ EXPORTS = [
     'gpsmi_pb_apply', 'gpsmi_pb_apply_dev', 'gpsmi_pb_last_ms',
     'gpsmi_nul_create', 'gpsmi_nul_destroy', 'gpsmi_nul_set_input_format',
     'gpsmi_nul_apply', 'gpsmi_nul_apply_dev', 'gpsmi_nul_last_ms',
+    'gpsmi_tfx_create', 'gpsmi_tfx_destroy', 'gpsmi_tfx_set_input_format', 'gpsmi_tfx_reset',
+    'gpsmi_tfx_apply', 'gpsmi_tfx_apply_dev', 'gpsmi_tfx_last_ms', 'gpsmi_tfx_last_power',
 ]
 
 _lib = None
@@ -333,6 +341,14 @@ def load():
         'gpsmi_nul_apply': [vp, vp, vp, C.c_int, vp, vp, vp],
         'gpsmi_nul_apply_dev': [vp, vp, vp, C.c_int, vp, vp, vp],
         'gpsmi_nul_last_ms': [vp, P(f32)],
+        'gpsmi_tfx_create': [P(TfxCfg), P(vp)],
+        'gpsmi_tfx_destroy': [vp],
+        'gpsmi_tfx_set_input_format': [vp, C.c_int],
+        'gpsmi_tfx_reset': [vp],
+        'gpsmi_tfx_apply': [vp, vp, vp, C.c_int, vp, vp, vp],
+        'gpsmi_tfx_apply_dev': [vp, vp, vp, C.c_int, vp, vp, vp],
+        'gpsmi_tfx_last_ms': [vp, P(f32)],
+        'gpsmi_tfx_last_power': [vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -351,8 +367,8 @@ def load():
     got += [lib.gpsmi_abi_sizeof(i) for i in (13, 14, 15)]
     want += [COLLECTIVE_SAT_DTYPE.itemsize, C.sizeof(CollectiveGrid), COLLECTIVE_CELL_DTYPE.itemsize]
     got += [lib.gpsmi_abi_sizeof(i) for i in (17, 18, 19)]
-    want += [C.sizeof(NulCfg)]
-    got += [lib.gpsmi_abi_sizeof(21)]
+    want += [C.sizeof(NulCfg), C.sizeof(TfxCfg)]
+    got += [lib.gpsmi_abi_sizeof(21), lib.gpsmi_abi_sizeof(23)]
     if want != got:
         raise EngineError(f'ABI mismatch between gpsmi/_lib.py {want} and '
                           f'libgpsmi.so {got}')

@@ -1,11 +1,11 @@
 """What the block filters share, and the chain a receiver runs its blocks through.
 
 ``BlockFilter`` is the wrapper of a handle that turns blocks of cfg.ngps samples (complex64, or the
-recorder's uint16) into complex64 blocks of the same length: ``excision.Excision`` (gpsmi_ifx_*) and
-``blanking.PulseBlanker`` (gpsmi_pb_*) are subclasses, and ``nulling.NullSteer`` (gpsmi_nul_*), whose
-input is the blocks of several antennas.  ``Conditioner`` is the chain recording -> (null steering)
--> (excision) -> (blanking) -> the complex64 block the engines see, one block per call (DESIGN.md
-section 3).
+recorder's uint16) into complex64 blocks of the same length: ``excision.Excision`` (gpsmi_ifx_*),
+``tfexcision.SweepExcision`` (gpsmi_tfx_*) and ``blanking.PulseBlanker`` (gpsmi_pb_*) are subclasses,
+and ``nulling.NullSteer`` (gpsmi_nul_*), whose input is the blocks of several antennas.
+``Conditioner`` is the chain recording -> (null steering) -> (excision) -> (sweep excision) ->
+(blanking) -> the complex64 block the engines see, one block per call.
 """
 import ctypes as C
 
@@ -94,20 +94,23 @@ def _wanted(arg):
 
 
 class Conditioner:
-    """excise / blank / null: True (a stage of default settings, made and closed here), an Excision /
-    a PulseBlanker / a NullSteer of the caller's (used, not closed), or None / False (off).  raw_u8:
+    """excise / blank / null / sweep: True (a stage of default settings, made and closed here), an
+    Excision / a PulseBlanker / a NullSteer / a SweepExcision of the caller's (used, not closed), or
+    None / False (off); sweep may also be a frame length (32 .. 256) for a stage made here.  raw_u8:
     apply() takes the recorder's uint16 blocks; with any stage on it returns complex64 (out_raw_u8
-    False).  The order is null steering, excision, blanking, and only the first stage takes the raw
-    format (the others: raw_u8=False).  Null steering goes first: it needs every antenna, and what it
-    leaves is one complex64 block like any other; with it apply() takes [antennas][n].  A tone raises
-    every sample's power and would hide the pulses from the blanker, while the pulses only add a
-    flat level to the excision's spectrum: excision before blanking.  A chain without a stage is falsy
-    and passes every block through."""
+    False).  The order is null steering, excision, sweep excision, blanking, and only the first stage
+    takes the raw format (the others: raw_u8=False).  Null steering goes first: it needs every antenna,
+    and what it leaves is one complex64 block like any other; with it apply() takes [antennas][n].  A
+    tone raises every sample's power and would hide the pulses from the blanker, while the pulses only
+    add a flat level to the excision's spectrum: excision before blanking.  A constant-envelope sweep
+    does the same to the blanker's median and also only adds a flat level to the tone excision's
+    spectrum: the sweep excision stands between the two.  A chain without a stage is falsy and passes
+    every block through."""
 
-    def __init__(self, cfg, raw_u8, excise=None, blank=None, null=None, antennas=1):
+    def __init__(self, cfg, raw_u8, excise=None, blank=None, null=None, antennas=1, sweep=None):
         self.cfg, self.raw_u8 = cfg, bool(raw_u8)
         self.antennas = int(antennas)
-        self.nuller = self.excision = self.blanker = self.last = None
+        self.nuller = self.excision = self.sweeper = self.blanker = self.last = None
         self._owned, self._pinned, self._dev = [], None, []
         if _wanted(null):
             from .nulling import NullSteer
@@ -121,11 +124,18 @@ class Conditioner:
         if _wanted(excise):
             from .excision import Excision
             self.excision = self._stage(Excision, excise, self.raw_u8 and self.nuller is None)
+        if _wanted(sweep):
+            from .tfexcision import SweepExcision      # (behind the stages before it: their complex64)
+            kw = {}
+            if isinstance(sweep, int) and not isinstance(sweep, bool):      # (a frame length: made here)
+                kw, sweep = dict(frame=sweep), True
+            self.sweeper = self._stage(SweepExcision, sweep,
+                                       self.raw_u8 and self.nuller is None and self.excision is None, **kw)
         if _wanted(blank):
-            from .blanking import PulseBlanker         # (behind the stages before it: their complex64)
-            self.blanker = self._stage(PulseBlanker, blank,
-                                       self.raw_u8 and self.nuller is None and self.excision is None)
-        self.stages = [s for s in (self.nuller, self.excision, self.blanker) if s is not None]
+            from .blanking import PulseBlanker
+            self.blanker = self._stage(PulseBlanker, blank, self.raw_u8 and self.nuller is None and
+                                       self.excision is None and self.sweeper is None)
+        self.stages = [s for s in (self.nuller, self.excision, self.sweeper, self.blanker) if s is not None]
         self.out_raw_u8 = self.raw_u8 and not self.stages
         n = cfg.ngps
         if self.stages:

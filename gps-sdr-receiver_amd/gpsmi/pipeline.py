@@ -24,7 +24,7 @@ UDP_PORT = 61431                # gpsglob.py:82
 
 class Receiver:
     def __init__(self, cfg=None, sat_all=None, raw_u8=False, report_lag=0, excise=None, blank=None,
-                 antennas=1, null=None):
+                 antennas=1, null=None, sweep=None):
         """raw_u8: feed() takes the recorder's uint16 (Q << 8 | I) blocks exactly as streamData
         reads them from the file (gpsrecv.py:162-173); the decode to complex64 happens inside
         the GPU kernels, every datagram is byte-identical to the complex64 path's.
@@ -43,13 +43,16 @@ class Receiver:
         antennas = A > 1 with null = True or a nulling.NullSteer: feed() takes [A][NGPS], the blocks
         of A coherent antennas, and null steering (power inversion, antenna 0 the reference) combines
         them into one complex64 block ahead of the other stages.  The defaults (1, None): one antenna,
-        everything as without the arguments.  The chain is `conditioner` (conditioning.Conditioner);
+        everything as without the arguments.
+        sweep = True or a tfexcision.SweepExcision: time-frequency excision against swept and chirp
+        interference, between the excision and the blanking.  None, the default: off, everything as
+        without the argument.  The chain is `conditioner` (conditioning.Conditioner);
         its `last` is the block the engines saw."""
         from .conditioning import Conditioner
         self.cfg = cfg or Config()
-        self.conditioner = Conditioner(self.cfg, raw_u8, excise, blank, null, antennas)
+        self.conditioner = Conditioner(self.cfg, raw_u8, excise, blank, null, antennas, sweep)
         self.excision, self.blanker = self.conditioner.excision, self.conditioner.blanker
-        self.nuller = self.conditioner.nuller
+        self.nuller, self.sweeper = self.conditioner.nuller, self.conditioner.sweeper
         self.raw_u8 = self.conditioner.out_raw_u8     # (the engines see the filters' complex64)
         self.sat_all = list(SAT_ALL if sat_all is None else sat_all)
         self.acq = Acquisition(self.cfg, raw_u8=self.raw_u8)

@@ -66,7 +66,7 @@ const char* gpsmi_version(void);
 /* sizeof() of the ABI structs as compiled: 0 cfg, 1 peak, 2 trk_state, 3 trk_out,
  * 4 offsetof(trk_out, code_phase), 5 fe_cfg, 6 pb_cfg, 7 refine_hit, 8 refine_cfg, 9 refine_out,
  * 10 wtrk_cfg, 11 wtrk_state, 12 wtrk_bit, 13 cancel_sat, 14 cancel_cfg, 15 cancel_out, 17 collective_sat,
- * 18 collective_grid, 19 collective_cell, 21 nul_cfg (16 and 20 are not assigned); -1 otherwise.  Lets a binding verify its own struct declarations before the first real call.  */
+ * 18 collective_grid, 19 collective_cell, 21 nul_cfg, 23 tfx_cfg (16, 20 and 22 are not assigned); -1 otherwise.  Lets a binding verify its own struct declarations before the first real call.  */
 int gpsmi_abi_sizeof(int which);
 /* Kernel-variant selection and tuning thresholds, visible through the ABI (round 4: they used to
  * be environment variables read inside gpsmi_*_create, invisible to a C caller; the variables
@@ -1013,6 +1013,78 @@ int gpsmi_nul_apply(gpsmi_nul* h, const void* iq, float* out, int nb, int32_t* f
 int gpsmi_nul_apply_dev(gpsmi_nul* h, const void* d_iq, void* d_out, int nb, int32_t* flags,
                         float* gain_db, double* weights);
 int gpsmi_nul_last_ms(gpsmi_nul* h, float* ms);
+
+/* ========================================================================
+ * Time-frequency (sweep) excision: an opt-in input stage against swept and chirp interference, for
+ * one antenna, ahead of acquisition and tracking (float64 restatement:
+ * tests/tfx_ref.py).  A slow in-band sweep is continuous in time and wide in a block's mean spectrum,
+ * so neither the tone excision nor the blanker grips it, but it is narrow in every short time slice.
+ * Per block of n = block_samples samples x (complex64, or the recorder's uint16 decoded as
+ * gpsmi_dev_unpack_u8iq does), L = frame, H = L / 2, nf = n / H frames:
+ *   frames     frame f = 0 .. nf - 1 covers block samples f H - H .. f H + H - 1; frame 0 starts in the
+ *              carry, the previous block's last H input samples (zero after create / reset; a format
+ *              switch keeps it).  Window: periodic Hann w[i] = (float)(0.5 - 0.5 cos(2 pi i / L)), the
+ *              formula in double; the last frame's second half is weighted 1, so that the frames sum
+ *              to 1 everywhere and output block k needs input blocks k - 1 and k only;
+ *   power      P[f][k] = re*re + im*im (float32: two products and one add, never fused) of the L-point
+ *              transform of the windowed frame, computed in float32;
+ *   floor      m = the order statistic of rank (c - 1) / 2 (from 0, ascending; the lower median) of
+ *              the c = (nf - 1) L values P[f][k] of all frames but the last;
+ *   threshold  F = (float)10^(thresh_db / 10) in double on the host, T = m * F in float32; the last
+ *              frame's threshold is T * (float)(11.0 / 6.0) in float32 (its window carries 11/6 of
+ *              Hann's power); cell (f, k) is a detection when P[f][k] > T, strictly (thresh_db = +inf,
+ *              an all-zero block: none);
+ *   widening   cell (f, k) is flagged when a detection (f, k') has (k - k') mod L within -dilate ..
+ *              dilate: circular inside the frame, none in time;
+ *   too much   count = the flagged cells of the block; count > floor(max_frac * nf * L) (in double):
+ *              the block passes through bit for bit (decoded for u8), count -1, mask empty; its
+ *              floor is still reported.  The carry for the next block is the input's tail always;
+ *   output     the flagged cells of every frame's transform are set to zero, each frame is
+ *              transformed back with scale 1 / L and the frames are overlap-added; out is complex64.
+ * counts int32 [nb] (flagged cells, -1 passed through), floors float32 [nb] (m) and masks uint32
+ * [nb][nf L / 32] (cell (f, k) of block b in bit k % 32 of word f L / 32 + k / 32 of the block's
+ * words) are host arrays, each may be null.  nb consecutive blocks in order: block b's carry is
+ * block b - 1's tail (the handle's for b = 0), the handle keeps the last block's.  Input and output
+ * must not overlap (GPSMI_E_ARG); device complex64 input and the output must be 16-byte aligned,
+ * device u8 input 4-byte aligned.  Floors, masks and counts follow from the stored P by comparisons
+ * and integer operations alone; every output sample is written once by one thread, no float
+ * atomics: the bits do not depend on the grid, on nb or on the cut of the input into calls.  Both
+ * calls return when the work is done; gpsmi_tfx_last_ms reports its device time.
+ * gpsmi_tfx_last_power copies out the float32 P of the last call, [nb][nf][L], nb that call's;
+ * GPSMI_E_STATE unless the handle was made with keep_power and a call has run.
+ * A bad block_samples or frame is GPSMI_E_UNSUPPORTED with the field's name in the message; the
+ * other argument errors (a null cfg or handle, a NaN threshold, dilate, max_frac or keep_power out
+ * of range, nb <= 0) are GPSMI_E_ARG; none needs a GPU.  A failed allocation is GPSMI_E_NOMEM and
+ * leaves the handle usable.
+ * Limits: a sweep that crosses more than about one bin width (fs / L) per frame length (L / fs),
+ * i.e. a rate above some (fs / L)^2, is wide in every frame and is not gripped at that L; at most
+ * max_frac of the plane is removed; the first block after create / reset stands behind a zero
+ * carry (a step at sample 0 in its frame 0).
+ * ======================================================================== */
+typedef struct gpsmi_tfx gpsmi_tfx;
+typedef struct gpsmi_tfx_cfg {
+    int32_t block_samples;      /* n: multiple of 128 in 1024 .. 2^24 (65536, 130944, 523776, ...) */
+    int32_t frame;              /* L: 32, 64, 128 or 256; 0 means 64                             */
+    float   thresh_db;          /* 0 means 12.0; not NaN; +inf flags nothing                     */
+    int32_t dilate;             /* 0 .. 8 bins each way; -1 means the default, 1                 */
+    float   max_frac;           /* in [0, 1]; 0 means 0.5                                        */
+    int32_t keep_power;         /* 0, or 1: gpsmi_tfx_last_power may be called                   */
+    int32_t device;
+    int32_t reserved;           /* 0 */
+} gpsmi_tfx_cfg;
+int gpsmi_tfx_create(const gpsmi_tfx_cfg* cfg, gpsmi_tfx** out);
+int gpsmi_tfx_destroy(gpsmi_tfx* h);
+/* GPSMI_IQ_C64 (default) or GPSMI_IQ_U8 (the recorder's uint16, decoded on load) */
+int gpsmi_tfx_set_input_format(gpsmi_tfx* h, int fmt);
+int gpsmi_tfx_reset(gpsmi_tfx* h);                            /* carry := 0 */
+/* host iq (nb * n samples in the input format) -> host out (complex64 [nb * n])                */
+int gpsmi_tfx_apply(gpsmi_tfx* h, const void* iq, float* out, int nb, int32_t* counts, float* floors,
+                    uint32_t* masks);
+/* the same from device memory to device memory (the result arrays are host memory)             */
+int gpsmi_tfx_apply_dev(gpsmi_tfx* h, const void* d_iq, void* d_out, int nb, int32_t* counts,
+                        float* floors, uint32_t* masks);
+int gpsmi_tfx_last_ms(gpsmi_tfx* h, float* ms);
+int gpsmi_tfx_last_power(gpsmi_tfx* h, float* P);
 
 /* ========================================================================
  * Multi-GPU: one process per GPU; SVs / blocks are sharded by the host and

@@ -4,7 +4,7 @@ gpsglob.LIVE_MEAS = False / BIN_DATA; gpsrecv.streamData -> processData -> UDP /
 gpseval) as one command on the GPU path.
 
     python tools/run_file.py <recording.bin> [--seconds S] [--start-stream K] [--save-pickle P]
-                             [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--blank] [--json]
+                             [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--sweep [L]] [--blank] [--json]
                              [--antenna FILE ... --null]
                              [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track [--weak-fix]]]]
                              [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]]]
@@ -25,7 +25,11 @@ the first five blocks of the same file, on one host core.  --excise removes narr
 interference (continuous-wave tones) from every block on the GPU before the receiver sees it
 (pipeline.Receiver(excise=True)).  --blank zeroes pulsed and swept (chirp)
 interference sample by sample on the GPU (pipeline.Receiver(blank=True)); with
---excise the tones are removed first, then the pulses.  --antenna FILE (repeatable) names the files
+--excise the tones are removed first, then the pulses.  --sweep [L] removes swept and chirp
+interference in the time-frequency plane of frames of L samples (default: the library's, 64) on the GPU
+(pipeline.Receiver(sweep=True)), between --excise and --blank; the report gains
+'sweep': the blocks excised and passed through and the mean share of the plane removed.
+--antenna FILE (repeatable) names the files
 of the further channels of a coherent multi-antenna recorder, sample-aligned with the recording
 (antenna 0, the reference element), and --null combines them by null steering on the GPU ahead of
 everything else (pipeline.Receiver(antennas=A, null=True)): a defence against
@@ -353,7 +357,7 @@ def print_snapshot(out):
 
 def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, cpu_acq=False, report_lag=16,
         excise=False, frontend=None, blank=False, deep_acq=None, refine=False, track=False, weak_fix=False,
-        save_ephemeris=None, antennas=(), null=False):
+        save_ephemeris=None, antennas=(), null=False, sweep=None):
     """frontend: None (the recorder's u8 format at 2.048 Msps) or a dict of frontend.FrontEnd's
     keyword arguments (fs_in, fmt, if_hz, conjugate).  deep_acq: None, or the seconds of the
     recording's start that deep_acquisition searches for the PRNs the sweep did not acquire; refine:
@@ -365,7 +369,9 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
     antennas: the files of the further channels of a coherent multi-antenna recorder, read in step
     with `path` (antenna 0, the reference element); null: null steering combines them ahead of
     everything else (pipeline.Receiver(antennas=A, null=True)) and the report gains
-    'null': the flag (1 nulled, 0 passed through) and the predicted gain in dB of every block."""
+    'null': the flag (1 nulled, 0 passed through) and the predicted gain in dB of every block.
+    sweep: None, True or a frame length: time-frequency excision (pipeline.Receiver(sweep=...),
+    DESIGN.md 4.2m); the report gains 'sweep'."""
     from gpsmi import ingest, position as P
     from gpsmi.engine import Config
     from gpsmi.pipeline import Receiver, save_results
@@ -374,8 +380,8 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
     # reader then runs ahead of the GPU instead of stalling it once a second -- pipeline.Receiver)
     with ingest.open_blocks(path, cfg, start_stream, frontend, antennas) as (source, raw_u8):
         array = dict(antennas=1 + len(antennas), null=True) if null else {}
-        rx = Receiver(cfg, raw_u8=raw_u8, report_lag=report_lag, excise=excise, blank=blank, **array)
-        null_flags, null_gain = [], []
+        rx = Receiver(cfg, raw_u8=raw_u8, report_lag=report_lag, excise=excise, blank=blank, sweep=sweep, **array)
+        null_flags, null_gain, sweep_counts = [], [], []
         if weak_fix:
             from gpsmi.pipeline import WeakAssist
             top = WeakAssist(rx, seconds=deep_acq)
@@ -391,6 +397,8 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
             if null:
                 null_flags.append(int(rx.nuller.last_flags[0]))
                 null_gain.append(round(float(rx.nuller.last_gain_db[0]), 2))
+            if sweep:
+                sweep_counts.append(int(rx.sweeper.last_counts[0]))
             if found is None and not rx.sweep_all_freq:
                 found = list(rx.found_sats)
             for dg in top.result_list[n_dg:]:          # (every datagram, in order: RESULT_LIST)
@@ -408,6 +416,12 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
         if save_ephemeris:
             save_ephemerides(save_ephemeris, decoded_ephemerides(solver))
         sats = sorted(rx.act_sat_set)
+        if sweep:
+            cells = 2 * rx.sweeper.n
+            done = [c for c in sweep_counts if c >= 0]
+            sweep_out = {'frame': rx.sweeper.frame, 'blocks_excised': sum(1 for c in done if c > 0),
+                         'blocks_passed_through': len(sweep_counts) - len(done),
+                         'mean_share': round(float(np.mean(done)) / cells, 4) if done else 0.0}
         weak = weak_fix_report(top, solver, fixes, cfg) if weak_fix else None
         rx.close()
     out = {'file': os.path.basename(path), 'blocks': n_blocks, 'signal_s': round(n_blocks * cfg.n_cyc / 1000.0, 3),
@@ -427,6 +441,8 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
     if null:
         out['null'] = {'antennas': 1 + len(antennas), 'flags': null_flags, 'gain_db': null_gain,
                        'blocks_nulled': int(sum(null_flags))}
+    if sweep:
+        out['sweep'] = sweep_out
     if weak is not None:
         out['weak_fix'] = weak
     if cpu_acq:
@@ -452,6 +468,10 @@ def main():
                     help='remove narrowband interference (CW tones) from every block first (DESIGN.md 4.2b)')
     ap.add_argument('--blank', action='store_true',
                     help='zero pulsed / chirp interference in every block (after --excise, DESIGN.md 4.2d)')
+    ap.add_argument('--sweep', type=int, nargs='?', const=True, default=None, metavar='L', choices=[32, 64, 128, 256],
+                    help='remove swept / chirp interference in the time-frequency plane of frames of L samples '
+                         '(default: tfexcision.default_frame, 64 at 2.048 Msps; after --excise, before --blank; '
+                         'DESIGN.md 4.2m)')
     ap.add_argument('--format', default=None, choices=['c64', 'u8iq', 'sc8', 'sc16', 'r8'],
                     help='sample format of another front end (DESIGN.md 4.2c); default u8iq when --fs / --if is given')
     ap.add_argument('--fs', type=int, default=None, help='input sample rate in Hz (default 2048000)')
@@ -531,7 +551,8 @@ def main():
     if a.collective is not None:
         ap.error('--collective needs --snapshot SECONDS')
     out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise,
-              frontend, a.blank, a.deep_acq, a.refine, a.track, a.weak_fix, a.save_ephemeris, a.antenna, a.null)
+              frontend, a.blank, a.deep_acq, a.refine, a.track, a.weak_fix, a.save_ephemeris, a.antenna, a.null,
+              a.sweep)
     if a.json:
         print(json.dumps(out))
         return
@@ -545,6 +566,10 @@ def main():
               f"(SD of mean {p['sd_of_mean_m']} m)")
     else:
         print('no position fix (too little signal for subframes 1-3 of four satellites, or no ephemerides)')
+    if 'sweep' in out:
+        u = out['sweep']
+        print(f"sweep excision, frames of {u['frame']}: {u['blocks_excised']} blocks excised, "
+              f"{u['blocks_passed_through']} passed through, {100 * u['mean_share']:.1f} % of the plane removed")
     if 'null' in out:
         u = out['null']
         print(f"null steering over {u['antennas']} antennas: {u['blocks_nulled']} of {len(u['flags'])} blocks nulled")
