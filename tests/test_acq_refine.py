@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from deep_ref import DEEP_HIGH, DEEP_ZERO, L1_HZ, deep_scene
+import small_scene as S
 from refine_ref import ABSENT, check_truth, refine_ref, scene_cases
 
 N_MS = 1000
@@ -166,3 +167,64 @@ def test_header_states_the_cap():
     m = re.search(r'#define\s+GPSMI_REFINE_MAX_MS\s+(\d+)', src)
     assert m and int(m.group(1)) >= 4000
     assert ABSENT[0] not in [p for p, _, _ in DEEP_HIGH + [DEEP_ZERO]]
+
+
+# ---- the option and shape cases of small_scene.py: the restatement's decisions are not marginal ----
+
+def _case_runs(case):
+    return [False, True] if case.raw else [False]
+
+
+@pytest.mark.parametrize('case', [c for c in S.REFINE_CASES if not c.zeros], ids=repr)
+def test_small_scene_decisions_are_not_marginal(case):
+    """The GPU test compares prn, n_bits, edge_ms, confirmed and code_phase == -1 exactly.  That is
+    sound where the restatement's own decision is clear of its threshold: ratio outside 2.5 +- 0.25,
+    the top two grid cells more than 1e-3 of the peak apart (2e-4 where the grid step cannot give
+    more, see small_scene.py), tap_metric[0] and [2] more than 1e-3 of [1] away from it -- on the
+    complex64 rendering and, where the case also runs from raw u8, on the decoded samples."""
+    for decoded in _case_runs(case):
+        ref, grid, P = case.ref(decoded)
+        ok, text = S.refine_margins(ref, grid, case.gap)
+        print('%s%s\n%s' % (case.name, ' (decoded u8)' if decoded else '', text))
+        assert ok
+        assert np.all(ref['n_bits'] == case.n_ms // 20 - 1) and P.shape == (len(case.hits), 3, case.n_ms)
+
+
+def test_small_scene_cases_reach_what_they_are_for():
+    """The shapes and branches each case exists for, read off the restatement."""
+    by = {c.name: c for c in S.REFINE_CASES}
+    B = lambda name: by[name].n_ms // 20 - 1
+    assert [B('min-2048'), B('lanes-1300'), B('lanes-1320'), B('threads-5140'), B('threads-5160')] == [1, 64, 65, 256, 257]
+    assert by['tail-60'].n_ms % 8 == by['tail-100'].n_ms % 8 == 4 and by['max-8000'].n_ms == 8000
+    n_df = [by[n].ref()[1].shape[1] for n in ('n_df-1-0.4', 'n_df-1-1', 'n_df-2-2', 'n_df-0.5-255.75')]
+    assert n_df == [1, 3, 3, 1024]
+    ref, grid, _ = by['n_df-0.5-255.75'].ref()
+    for h in range(len(ref)):                             # an interior peak: the parabola runs
+        d = int(np.argmax(grid[h])) // 20
+        assert 0 < d < 1023
+    for name, row in (('rows-first', 0), ('rows-last', 8)):
+        ref, grid, _ = by[name].ref()
+        assert grid.shape[1] == 9
+        for h in range(len(ref)):
+            assert int(np.argmax(grid[h])) // 20 == row
+            assert ref['f_hz'][h] == by[name].hits[h][1] + (-20.0 + 5.0 * row)      # no parabola
+    assert [h[2] for h in by['tap-512'].hits] == [0, 511, 512, 2047] and by['tap-512'].n == 62 * 2048 + 512
+    assert len(by['many-64'].hits) == 64 and len({h[1:] for h in by['many-64'].hits}) == 64
+    ref, _, _ = by['misaligned'].ref()
+    assert np.all(ref['code_phase'] == -1.0)
+    ok = by['tail-100'].ref()[0]
+    assert np.all(ok['code_phase'] >= 0) and np.all(ok['edge_ms'] == by['tail-100'].edge)
+    for name in ('slide-minus-2048', 'slide-plus-2048', 'slide-minus-16368', 'slide-plus-16368'):
+        c = by[name]                                      # windows sliding several samples per ms
+        slide = -(c.hits[0][1] - c.opts['f_offset']) / L1_HZ * c.cs
+        assert abs(slide) > 3.0 and (slide > 0) == (c.opts['f_offset'] > 0)
+
+
+def test_small_scene_zeros_is_the_degenerate_record():
+    case = next(c for c in S.REFINE_CASES if c.zeros)
+    ref, grid, P = case.ref()
+    assert not grid.any() and not P.any()
+    for r, (prn, freq, delay) in zip(ref, case.hits):
+        assert (r['prn'], r['edge_ms'], r['n_bits'], r['confirmed']) == (prn, 0, 1, 0)
+        assert r['f_hz'] == freq - 120.0 and r['peak'] == r['median'] == 0.0 and np.isnan(r['ratio'])
+        assert r['code_phase'] == delay and r['mu'] == 0.0 and np.isnan(r['cn0_dbhz'])

@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import small_scene as S
 import wtrk_ref as W
 from deep_ref import L1_HZ
 
@@ -229,3 +230,39 @@ def test_open_from_a_refined_record():
     near['code_phase'] = -1.0
     with pytest.raises(_lib.EngineError, match=r'\(-1\)'):
         open_weak_channels(near, Config())
+
+
+# ---- the option and shape cases of small_scene.py ----------------------------------------------------
+
+@pytest.mark.parametrize('name', list(S.TRACK_CASES))
+def test_small_scene_windows_keep_clear_of_integers(name):
+    """As test_windows_keep_clear_of_integers, for every scene test_gpu_track_cases.py compares window
+    by window: the restatement's s_k stay more than INTEGER_GUARD from an integer, in the far case at
+    stream positions past 2^31 (where an ulp of tau is 4.8e-7)."""
+    case = S.TRACK_CASES[name]
+    rec, st, nk = case.ref(first_sample=S.FAR if name == 'far' else 0)
+    assert [s['bit_no'] for s in st] == [case.n_bits] * len(st) and not any(s['flags'] for s in st)
+    worst = S.closest_to_integer(rec, st, nk, case.cs, **case.scene_kw())
+    print('%s: closest s_k to an integer: %.3e' % (name, worst))
+    assert worst > INTEGER_GUARD
+    if name == 'far':
+        assert nk.min() > 2 ** 31
+
+
+def test_small_scene_cases_reach_what_they_are_for():
+    ring = S.TRACK_CASES['ring']
+    rec, st, _ = ring.ref()
+    assert ring.n_bits > W.RING and len(st) == 3 and st[2]['prn'] == 3
+    assert not np.isnan(rec[:2, W.RING:]['cn0_dbhz']).any()          # the wrapped ring gives a C/N0
+    many = S.TRACK_CASES['many']
+    assert len(many.states()) == 64
+    cut = S.many_cut(many)
+    _, sc, _ = many.ref(n=cut)
+    stopped = [s['bit_no'] for s in sc].count(2)
+    assert 16 <= stopped <= 48 and stopped + [s['bit_no'] for s in sc].count(3) == 64
+    assert all((s['flags'] == 1) == (s['bit_no'] == 2) for s in sc)
+    for name in ('slide-minus-2048', 'slide-plus-16368'):                # windows sliding samples per ms
+        c = S.TRACK_CASES[name]
+        _, _, nk = c.ref()
+        step = np.diff(nk[0, 0]) - c.cs
+        assert np.all(np.abs(step) >= 3) and np.all((step > 0) == (c.opts['f_offset'] > 0))
