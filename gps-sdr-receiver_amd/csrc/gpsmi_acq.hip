@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include "gpsmi_common.h"
@@ -41,7 +42,7 @@ struct gpsmi_acq {
     DevBuf<float> d_t32;
     DevBuf<float2> d_rep;             // [GPSMI_MAX_PRN + 1][cs]
     bool have_rep[GPSMI_MAX_PRN + 1] = {};
-    DevBuf<float2> d_iq;              // host input of any entry point, sized as complex64 (acq_upload)
+    DevBuf<float2> d_iq;              // host input of any entry point, sized as complex64 (acq_input)
     DevBuf<float2> d_spec;            // [bins][2048]
     DevBuf<float> d_omega;            // [bins]
     DevBuf<int> d_slot;
@@ -111,12 +112,68 @@ static int acq_reserve(gpsmi_acq* h, int nbins, int nsv) {
     return rc;
 }
 
-// host input of a search, a refinement or a tracking call: `count` samples in the handle's input
-// format into d_iq on the handle's stream (d_iq is sized for complex64; raw input fills a quarter)
-static int acq_upload(gpsmi_acq* h, const void* iq, size_t count) {
+// ---- one call on the handle: every entry point is its own checks and plan, then
+// acq_enter, acq_input, its reserves (and acq_tables / acq_lds_optin where it has tables or a large
+// LDS), acq_begin, its launches, acq_end, its read-backs, gpsmi_acq_wait ----------------------------
+
+// behind the argument checks: a refused call leaves last_ms and the device alone
+static int acq_enter(gpsmi_acq* h) {
+    h->last_ms = 0.f;
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    return GPSMI_OK;
+}
+
+// -> *d_iq, what the kernels read: the caller's device pointer, or d_iq with the `count` samples a host
+// call reads, in the handle's input format, on their way up on the handle's stream (d_iq is sized for
+// complex64; raw input fills a quarter)
+static int acq_input(gpsmi_acq* h, const void* iq, bool on_host, size_t count, const void** d_iq) {
+    *d_iq = iq;
+    if (!on_host) return GPSMI_OK;
     const int rc = h->d_iq.reserve(count, "gpsmi_acq input block");
     if (rc) return rc;
     GPSMI_HIP(hipMemcpyAsync(h->d_iq.p, iq, h->iq_bytes(count), hipMemcpyHostToDevice, h->stream));
+    *d_iq = h->d_iq.p;
+    return GPSMI_OK;
+}
+
+// the refinement, tracking and cancellation kernels read GPSCacode itself; prn_of(i): the PRN of item i
+template <typename PrnOf>
+static int acq_need_time(const gpsmi_acq* h, const char* fn, int n, PrnOf&& prn_of) {
+    for (int i = 0; i < n; ++i)
+        if (!h->have_time[prn_of(i)])
+            return fail(GPSMI_E_STATE, "%s: no time-domain replica set for PRN %d (gpsmi_acq_set_replica_time)", fn,
+                        (int)prn_of(i));
+    return GPSMI_OK;
+}
+
+// per-call tables from pageable host memory into reserved device memory: the copies, then the stream
+// synchronised, since the tables may leave scope (or be rewritten by the caller) once this returns
+struct HostTable { void* dst; const void* src; size_t bytes; };
+static int acq_tables(gpsmi_acq* h, std::initializer_list<HostTable> tables) {
+    for (const HostTable& t : tables)
+        GPSMI_HIP(hipMemcpyAsync(t.dst, t.src, t.bytes, hipMemcpyHostToDevice, h->stream));
+    GPSMI_HIP(hipStreamSynchronize(h->stream));
+    return GPSMI_OK;
+}
+
+// more than 64 KiB of dynamic LDS for the kernel of the handle's input format
+template <typename K>
+static int acq_lds_optin(const gpsmi_acq* h, K* u8, K* c64, size_t lds) {
+    if (lds > 64 * 1024)
+        GPSMI_HIP(hipFuncSetAttribute((const void*)(h->iq_fmt == GPSMI_IQ_U8 ? u8 : c64),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return GPSMI_OK;
+}
+
+static int acq_begin(gpsmi_acq* h) {         // ahead of a call's first launch
+    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
+    return GPSMI_OK;
+}
+
+static int acq_end(gpsmi_acq* h) {           // behind its last one; gpsmi_acq_wait completes the call
+    GPSMI_HIP(hipGetLastError());
+    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
+    h->pending = true;
     return GPSMI_OK;
 }
 
@@ -241,7 +298,6 @@ static int acq_copy_out(gpsmi_acq* h, int nbins, int nsv, gpsmi_peak* out, void*
     if (nbr)
         GPSMI_HIP(hipMemcpyAsync(nbr, h->d_nbr.p, (size_t)nbins * nsv * sizeof(float2),
                                  hipMemcpyDeviceToHost, h->stream));
-    h->pending = true;
     return GPSMI_OK;
 }
 
@@ -345,13 +401,11 @@ static int acq_search_run(gpsmi_acq* h, const void* d_iq, const int32_t* prn, in
                                              "search, which keeps no surface (n_seg >= 2)");
         s = AcqSearch{s.n_coh, 1, nullptr, s.wait, false};
     }
-    h->last_ms = 0.f;
-    if (nsv == 0 || nbins == 0) return GPSMI_OK;            // empty search: nothing to do
-    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    int rc = acq_enter(h);
+    if (rc || nsv == 0 || nbins == 0) return rc;            // empty search: nothing to do
+    if ((rc = acq_reserve(h, nbins, nsv))) return rc;
     const int cs = h->cfg.code_samples, n_seg = s.n_seg;
     const size_t cells = (size_t)nbins * nsv;
-    int rc = acq_reserve(h, nbins, nsv);
-    if (rc) return rc;
     // where the folds go, and how many bins of them at a time: a coherent search is one chunk
     size_t nbc = (size_t)nbins;
     float2* x = nullptr;
@@ -378,13 +432,12 @@ static int acq_search_run(gpsmi_acq* h, const void* d_iq, const int32_t* prn, in
         for (int b = 0; b < nbins; ++b)
             for (int sg = 0; sg < n_seg; ++sg)
                 shift[(size_t)b * n_seg + sg] = deep_shift(freqs[b], *s.deep, sg, s.n_coh, cs);
-        if ((rc = h->d_shift.reserve(ns, "gpsmi_acq lag rotations"))) return rc;
-        GPSMI_HIP(hipMemcpyAsync(h->d_shift.p, shift.data(), ns * sizeof(int), hipMemcpyHostToDevice,
-                                 h->stream));
-        GPSMI_HIP(hipStreamSynchronize(h->stream));      // (the table is pageable and leaves scope here)
+        if ((rc = h->d_shift.reserve(ns, "gpsmi_acq lag rotations")) ||
+            (rc = acq_tables(h, {{h->d_shift.p, shift.data(), ns * sizeof(int)}})))   // (it leaves scope here)
+            return rc;
     }
     float2* d_nbr = nbr ? h->d_nbr.p : nullptr;
-    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
+    if ((rc = acq_begin(h))) return rc;
     for (int b0 = 0; b0 < nbins; b0 += (int)nbc) {
         const int nb = nbins - b0 < (int)nbc ? nbins - b0 : (int)nbc;
         if (h->direct) {
@@ -406,10 +459,7 @@ static int acq_search_run(gpsmi_acq* h, const void* d_iq, const int32_t* prn, in
     if (h->direct)
         hipLaunchKernelGGL(acq_peaks_kernel, dim3(((int)cells + 255) / 256), dim3(256), 0, h->stream,
                            h->lc.d_stats.p, h->d_peaks.p, d_nbr, (int)cells);
-    GPSMI_HIP(hipGetLastError());
-    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
-    rc = acq_copy_out(h, nbins, nsv, out, out_dev, nbr);
-    if (rc || !s.wait) return rc;
+    if ((rc = acq_end(h)) || (rc = acq_copy_out(h, nbins, nsv, out, out_dev, nbr)) || !s.wait) return rc;
     return gpsmi_acq_wait(h);
 }
 
@@ -419,12 +469,10 @@ static int acq_search(gpsmi_acq* h, const void* iq, bool on_host, size_t n, cons
                       float* nbr) {
     int rc = acq_check_search(h, iq, on_host, n, prn, nsv, freqs, nbins, s, out, out_dev);
     if (rc) return rc;
-    if (on_host) {
-        GPSMI_HIP(hipSetDevice(h->cfg.device));
-        if ((rc = acq_upload(h, iq, (size_t)s.n_seg * s.n_coh * h->cfg.code_samples))) return rc;
-        iq = h->d_iq.p;
-    }
-    return acq_search_run(h, iq, prn, nsv, freqs, nbins, s, out, out_dev, nbr);
+    if (on_host) GPSMI_HIP(hipSetDevice(h->cfg.device));
+    const void* d_iq;
+    if ((rc = acq_input(h, iq, on_host, (size_t)s.n_seg * s.n_coh * h->cfg.code_samples, &d_iq))) return rc;
+    return acq_search_run(h, d_iq, prn, nsv, freqs, nbins, s, out, out_dev, nbr);
 }
 
 int gpsmi_acq_wait(gpsmi_acq* h) {
@@ -507,18 +555,11 @@ static int acq_refine_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n,
     RefPlan pl;
     int rc = ref_plan(h->cfg.code_samples, n, hits, nhits, cfg, &pl);
     if (rc) return rc;
-    for (int i = 0; i < nhits; ++i)
-        if (!h->have_time[hits[i].prn])
-            return fail(GPSMI_E_STATE, "gpsmi_acq_refine: no time-domain replica set for PRN %d "
-                                       "(gpsmi_acq_set_replica_time)", (int)hits[i].prn);
+    const void* d_iq;
+    if ((rc = acq_need_time(h, "gpsmi_acq_refine", nhits, [&](int i) { return hits[i].prn; })) ||
+        (rc = acq_enter(h)) || (rc = acq_input(h, iq, on_host, pl.hi, &d_iq)))   // (only what the windows read)
+        return rc;
     const int cs = pl.cs, n_ms = pl.n_ms, n_df = pl.n_df;
-    h->last_ms = 0.f;
-    GPSMI_HIP(hipSetDevice(h->cfg.device));
-    const void* d_iq = iq;
-    if (on_host) {                           // only what the windows read is uploaded
-        if ((rc = acq_upload(h, iq, pl.hi))) return rc;
-        d_iq = h->d_iq.p;
-    }
     // the tables of the call, 8-byte items first
     const size_t b_start = pl.start.size() * sizeof(long long), b_inc = (size_t)n_df * sizeof(unsigned long long),
                  b_df = (size_t)n_df * sizeof(double), b_hit = (size_t)nhits * sizeof(RefHit);
@@ -532,18 +573,12 @@ static int acq_refine_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n,
     unsigned long long* d_inc = reinterpret_cast<unsigned long long*>(h->d_rt.p + b_start);
     double* d_df = reinterpret_cast<double*>(h->d_rt.p + b_start + b_inc);
     RefHit* d_hit = reinterpret_cast<RefHit*>(h->d_rt.p + b_start + b_inc + b_df);
-    GPSMI_HIP(hipMemcpyAsync(d_start, pl.start.data(), b_start, hipMemcpyHostToDevice, h->stream));
-    GPSMI_HIP(hipMemcpyAsync(d_inc, pl.dfinc.data(), b_inc, hipMemcpyHostToDevice, h->stream));
-    GPSMI_HIP(hipMemcpyAsync(d_df, pl.dfs.data(), b_df, hipMemcpyHostToDevice, h->stream));
-    GPSMI_HIP(hipMemcpyAsync(d_hit, pl.hits.data(), b_hit, hipMemcpyHostToDevice, h->stream));
-    GPSMI_HIP(hipStreamSynchronize(h->stream));          // (the tables are pageable and leave scope here)
     const size_t lds_p = ((size_t)cs + kRefMsPerWg * 4 * 6) * sizeof(float);
     const size_t lds_g = (size_t)n_ms * sizeof(float2);
-    const bool u8 = h->iq_fmt == GPSMI_IQ_U8;
-    if (lds_p > 64 * 1024)
-        GPSMI_HIP(hipFuncSetAttribute(u8 ? (const void*)refine_prompt_kernel<1> : (const void*)refine_prompt_kernel<0>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
+    if ((rc = acq_tables(h, {{d_start, pl.start.data(), b_start}, {d_inc, pl.dfinc.data(), b_inc},
+                             {d_df, pl.dfs.data(), b_df}, {d_hit, pl.hits.data(), b_hit}})) ||
+        (rc = acq_lds_optin(h, refine_prompt_kernel<1>, refine_prompt_kernel<0>, lds_p)) || (rc = acq_begin(h)))
+        return rc;
     const dim3 gp((n_ms + kRefMsPerWg - 1) / kRefMsPerWg, nhits);
     with_fmt(h->iq_fmt, [&](auto fmt) {
         hipLaunchKernelGGL(refine_prompt_kernel<decltype(fmt)::value>, gp, dim3(256), lds_p, h->stream, d_iq,
@@ -553,15 +588,13 @@ static int acq_refine_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n,
                        d_inc, n_df, n_ms, h->d_rm.p);
     hipLaunchKernelGGL(refine_final_kernel, dim3(nhits), dim3(256), 0, h->stream, h->d_rp.p, h->d_rm.p, d_inc, d_df,
                        d_hit, n_df, n_ms, pl.tap, pl.step, pl.min_ratio, h->d_ro.p);
-    GPSMI_HIP(hipGetLastError());
-    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
+    if ((rc = acq_end(h))) return rc;
     GPSMI_HIP(hipMemcpyAsync(out, h->d_ro.p, (size_t)nhits * sizeof(gpsmi_refine_out), hipMemcpyDeviceToHost,
                              h->stream));
     if (grid)
         GPSMI_HIP(hipMemcpyAsync(grid, h->d_rm.p, nm * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (prompts)
         GPSMI_HIP(hipMemcpyAsync(prompts, h->d_rp.p, np * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-    h->pending = true;
     return gpsmi_acq_wait(h);
 }
 
@@ -590,18 +623,10 @@ static int acq_track_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n, 
     WtrkPar par;
     int rc = wtrk_plan(h->cfg.code_samples, n, states, nhits, cfg, &par);
     if (rc) return rc;
-    for (int i = 0; i < nhits; ++i)
-        if (!h->have_time[states[i].prn])
-            return fail(GPSMI_E_STATE, "gpsmi_acq_track: no time-domain replica set for PRN %d "
-                                       "(gpsmi_acq_set_replica_time)", (int)states[i].prn);
-    h->last_ms = 0.f;
-    GPSMI_HIP(hipSetDevice(h->cfg.device));
-    const bool u8 = h->iq_fmt == GPSMI_IQ_U8;
-    const void* d_iq = iq;
-    if (on_host) {
-        if ((rc = acq_upload(h, iq, n))) return rc;
-        d_iq = h->d_iq.p;
-    }
+    const void* d_iq;
+    if ((rc = acq_need_time(h, "gpsmi_acq_track", nhits, [&](int i) { return states[i].prn; })) ||
+        (rc = acq_enter(h)) || (rc = acq_input(h, iq, on_host, n, &d_iq)))
+        return rc;
     const size_t nb = (size_t)nhits * par.n_bits * sizeof(gpsmi_wtrk_bit);
     if ((rc = h->d_wb.reserve((size_t)nhits * par.n_bits, "gpsmi_acq_track bit records")) ||
         (rc = h->d_ws.reserve(kWtrkMaxHits, "gpsmi_acq_track states")))
@@ -610,20 +635,15 @@ static int acq_track_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n, 
                              h->stream));
     GPSMI_HIP(hipMemsetAsync(h->d_wb.p, 0, nb, h->stream));
     const size_t lds = wtrk_lds_bytes(par.cs);
-    if (lds > 64 * 1024)
-        GPSMI_HIP(hipFuncSetAttribute(u8 ? (const void*)wtrk_kernel<1> : (const void*)wtrk_kernel<0>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
+    if ((rc = acq_lds_optin(h, wtrk_kernel<1>, wtrk_kernel<0>, lds)) || (rc = acq_begin(h))) return rc;
     with_fmt(h->iq_fmt, [&](auto fmt) {
         hipLaunchKernelGGL(wtrk_kernel<decltype(fmt)::value>, dim3(nhits), dim3(256), lds, h->stream, d_iq,
                            h->d_rep_time.p, par, h->d_ws.p, h->d_wb.p);
     });
-    GPSMI_HIP(hipGetLastError());
-    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
+    if ((rc = acq_end(h))) return rc;
     GPSMI_HIP(hipMemcpyAsync(states, h->d_ws.p, (size_t)nhits * sizeof(gpsmi_wtrk_state), hipMemcpyDeviceToHost,
                              h->stream));
     GPSMI_HIP(hipMemcpyAsync(bits, h->d_wb.p, nb, hipMemcpyDeviceToHost, h->stream));
-    h->pending = true;
     return gpsmi_acq_wait(h);
 }
 
@@ -655,10 +675,7 @@ static int acq_cancel_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n,
     CancelPlan pl;
     int rc = cancel_plan(h->cfg.code_samples, n, sats, nsat, cfg, &pl);
     if (rc) return rc;
-    for (int i = 0; i < nsat; ++i)
-        if (!h->have_time[sats[i].prn])
-            return fail(GPSMI_E_STATE, "gpsmi_acq_cancel: no time-domain replica set for PRN %d "
-                                       "(gpsmi_acq_set_replica_time)", (int)sats[i].prn);
+    if ((rc = acq_need_time(h, "gpsmi_acq_cancel", nsat, [&](int i) { return sats[i].prn; }))) return rc;
     const bool u8 = h->iq_fmt == GPSMI_IQ_U8;
     const size_t out_bytes = n * sizeof(float2);
     bool in_place = false;
@@ -669,14 +686,11 @@ static int acq_cancel_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n,
             return fail(GPSMI_E_ARG, "gpsmi_acq_cancel_dev: d_iq and d_out_c64 overlap (only one complex64 "
                                      "buffer for both is cancelled in place)");
     }
-    h->last_ms = 0.f;
-    GPSMI_HIP(hipSetDevice(h->cfg.device));
     // where the input lies and where the satellites are taken out
-    const void* d_in = iq;
+    const void* d_in;
+    if ((rc = acq_enter(h)) || (rc = acq_input(h, iq, on_host, n, &d_in))) return rc;
     float2* d_y = static_cast<float2*>(out_c64);
     if (on_host) {
-        if ((rc = acq_upload(h, iq, n))) return rc;
-        d_in = h->d_iq.p;
         if (u8) {
             if ((rc = h->d_cx.reserve(n, "gpsmi_acq_cancel output"))) return rc;
             d_y = h->d_cx.p;
@@ -695,12 +709,10 @@ static int acq_cancel_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n,
         if ((rc = h->d_cw.reserve(pl.wins.size(), "gpsmi_acq_cancel windows")) ||
             (rc = h->d_cr.reserve(nres, "gpsmi_acq_cancel results")))
             return rc;
-        GPSMI_HIP(hipMemcpyAsync(h->d_cw.p, pl.wins.data(), pl.wins.size() * sizeof(CancelWin),
-                                 hipMemcpyHostToDevice, h->stream));
         GPSMI_HIP(hipMemsetAsync(h->d_cr.p, 0, nres * sizeof(CancelRes), h->stream));
-        GPSMI_HIP(hipStreamSynchronize(h->stream));      // (the table is pageable)
+        if ((rc = acq_tables(h, {{h->d_cw.p, pl.wins.data(), pl.wins.size() * sizeof(CancelWin)}}))) return rc;
     }
-    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
+    if ((rc = acq_begin(h))) return rc;
     // step 0: the input decoded or copied to where it is worked on
     if (u8) {
         const size_t blocks = (n + 255) / 256;
@@ -717,13 +729,11 @@ static int acq_cancel_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n,
                            h->d_rep_time.p + (size_t)sats[s].prn * pl.cs, h->d_cw.p + pl.first[s], pl.inc[s], pl.cs,
                            pl.min_window, h->d_cr.p + (size_t)s * mw);
     }
-    GPSMI_HIP(hipGetLastError());
-    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
+    if ((rc = acq_end(h))) return rc;
     if (on_host)
         GPSMI_HIP(hipMemcpyAsync(out_c64, d_y, out_bytes, hipMemcpyDeviceToHost, h->stream));
     if (nres)
         GPSMI_HIP(hipMemcpyAsync(res.data(), h->d_cr.p, nres * sizeof(CancelRes), hipMemcpyDeviceToHost, h->stream));
-    h->pending = true;
     if ((rc = gpsmi_acq_wait(h))) return rc;
     // the windows' figures, added in window order
     for (int s = 0; s < nsat; ++s) {
@@ -766,19 +776,15 @@ int gpsmi_acq_collective_dev(gpsmi_acq* h, const void* d_rows, int nsv_rows, int
     GPSMI_REQUIRE(out_host || out_dev, "no output requested");
     ColPlan pl;
     int rc = collective_plan(h->cfg.code_samples, nsv_rows, nbins, sats, nsat, grid, &pl);
-    if (rc) return rc;
-    h->last_ms = 0.f;
-    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    if (rc || (rc = acq_enter(h))) return rc;
     const int cs = pl.cs;
     const size_t nz = (size_t)nsat * cs;
     if ((rc = h->d_cz.reserve(pl.scratch_bytes / sizeof(float), "gpsmi_acq_collective rows")) ||
         (rc = h->d_csat.reserve(kColMaxSats, "gpsmi_acq_collective satellites")) ||
-        (rc = h->d_cc.reserve((size_t)pl.cells, "gpsmi_acq_collective cell map")))
+        (rc = h->d_cc.reserve((size_t)pl.cells, "gpsmi_acq_collective cell map")) ||
+        (rc = acq_tables(h, {{h->d_csat.p, sats, (size_t)nsat * sizeof(gpsmi_collective_sat)}})) ||
+        (rc = acq_begin(h)))
         return rc;
-    GPSMI_HIP(hipMemcpyAsync(h->d_csat.p, sats, (size_t)nsat * sizeof(gpsmi_collective_sat), hipMemcpyHostToDevice,
-                             h->stream));
-    GPSMI_HIP(hipStreamSynchronize(h->stream));          // (the caller's table is pageable)
-    GPSMI_HIP(hipEventRecord(h->ev0, h->stream));
     hipLaunchKernelGGL(collective_norm_kernel, dim3(nsat), dim3(256), 0, h->stream,
                        static_cast<const float*>(d_rows), nbins, cs, h->d_csat.p, h->d_cz.p);
     const float* z = h->d_cz.p;
@@ -789,12 +795,10 @@ int gpsmi_acq_collective_dev(gpsmi_acq* h, const void* d_rows, int nsv_rows, int
     }
     hipLaunchKernelGGL(collective_kernel, dim3(pl.workgroups), dim3(256), 0, h->stream, z, h->d_csat.p, nsat, *grid,
                        cs, (int)pl.cells, h->d_cc.p);
-    GPSMI_HIP(hipGetLastError());
-    GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
+    if ((rc = acq_end(h))) return rc;
     const size_t bytes = (size_t)pl.cells * sizeof(gpsmi_collective_cell);
     if (out_dev) GPSMI_HIP(hipMemcpyAsync(out_dev, h->d_cc.p, bytes, hipMemcpyDeviceToDevice, h->stream));
     if (out_host) GPSMI_HIP(hipMemcpyAsync(out_host, h->d_cc.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    h->pending = true;
     return gpsmi_acq_wait(h);
 }
 

@@ -354,21 +354,16 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
-    want = [C.sizeof(Cfg), PEAK_DTYPE.itemsize, STATE_DTYPE.itemsize,
-            OUT_DTYPE.itemsize, OUT_DTYPE.fields['code_phase'][1]]
-    got = [lib.gpsmi_abi_sizeof(i) for i in range(5)]
-    want += [C.sizeof(FeCfg), C.sizeof(PbCfg)]
-    got += [lib.gpsmi_abi_sizeof(5), lib.gpsmi_abi_sizeof(6)]
-    want += [REFINE_HIT_DTYPE.itemsize, C.sizeof(RefineCfg), REFINE_OUT_DTYPE.itemsize]
-    got += [lib.gpsmi_abi_sizeof(i) for i in (7, 8, 9)]
-    want += [C.sizeof(WtrkCfg), WTRK_STATE_DTYPE.itemsize, WTRK_BIT_DTYPE.itemsize]
-    got += [lib.gpsmi_abi_sizeof(i) for i in (10, 11, 12)]
-    want += [CANCEL_SAT_DTYPE.itemsize, C.sizeof(CancelCfg), CANCEL_OUT_DTYPE.itemsize]
-    got += [lib.gpsmi_abi_sizeof(i) for i in (13, 14, 15)]
-    want += [COLLECTIVE_SAT_DTYPE.itemsize, C.sizeof(CollectiveGrid), COLLECTIVE_CELL_DTYPE.itemsize]
-    got += [lib.gpsmi_abi_sizeof(i) for i in (17, 18, 19)]
-    want += [C.sizeof(NulCfg), C.sizeof(TfxCfg)]
-    got += [lib.gpsmi_abi_sizeof(21), lib.gpsmi_abi_sizeof(23)]
+    # (index of gpsmi_abi_sizeof, size here) of every struct both sides lay out
+    abi = [(0, C.sizeof(Cfg)), (1, PEAK_DTYPE.itemsize), (2, STATE_DTYPE.itemsize), (3, OUT_DTYPE.itemsize),
+           (4, OUT_DTYPE.fields['code_phase'][1]), (5, C.sizeof(FeCfg)), (6, C.sizeof(PbCfg)),
+           (7, REFINE_HIT_DTYPE.itemsize), (8, C.sizeof(RefineCfg)), (9, REFINE_OUT_DTYPE.itemsize),
+           (10, C.sizeof(WtrkCfg)), (11, WTRK_STATE_DTYPE.itemsize), (12, WTRK_BIT_DTYPE.itemsize),
+           (13, CANCEL_SAT_DTYPE.itemsize), (14, C.sizeof(CancelCfg)), (15, CANCEL_OUT_DTYPE.itemsize),
+           (17, COLLECTIVE_SAT_DTYPE.itemsize), (18, C.sizeof(CollectiveGrid)), (19, COLLECTIVE_CELL_DTYPE.itemsize),
+           (21, C.sizeof(NulCfg)), (23, C.sizeof(TfxCfg))]
+    want = [size for _, size in abi]
+    got = [lib.gpsmi_abi_sizeof(i) for i, _ in abi]
     if want != got:
         raise EngineError(f'ABI mismatch between gpsmi/_lib.py {want} and '
                           f'libgpsmi.so {got}')

@@ -161,6 +161,21 @@ def collective_plan(code_samples, nsv_rows, nbins, sats, grid):
     return scratch.value, wgs.value
 
 
+def _iq_dtype(raw_u8):
+    """What a handle's input format holds per sample: the recorder's uint16 (Q << 8 | I) or complex64."""
+    return np.uint16 if raw_u8 else np.complex64
+
+
+def _host_block(a, raw_u8, what):
+    """A host array handed to a handle, C-contiguous, in its input format (a silent cast would
+    turn one format into garbage of the other)."""
+    a = np.asarray(a)
+    if a.dtype != _iq_dtype(raw_u8):
+        raise TypeError(f'{what} dtype {a.dtype} does not match the input format '
+                        f'({np.dtype(_iq_dtype(raw_u8)).name}; see set_input_format)')
+    return np.ascontiguousarray(a)
+
+
 def _spectrum_c64(prn, cs):
     return np.ascontiguousarray(codes.replica_spectrum(prn, cs)
                                 .astype(np.complex64))
@@ -199,30 +214,41 @@ class AcqEngine:
         self.raw_u8 = bool(raw_u8)
 
     def _host_iq(self, iq):
-        want = np.uint16 if self.raw_u8 else np.complex64
-        iq = np.asarray(iq)
-        if iq.dtype != want:
-            raise TypeError(f'iq dtype {iq.dtype} does not match the input format '
-                            f'({np.dtype(want).name}; see set_input_format)')
-        return np.ascontiguousarray(iq)
+        return _host_block(iq, self.raw_u8, 'iq')
+
+    def _input(self, iq, nbr=False):
+        """iq of any entry point -> (pointer, n, host?): a host array in the input format, or a
+        (c_void_p, n) device pair as it is (the neighbours `nbr` come back for host input only)."""
+        if isinstance(iq, tuple):
+            if nbr:
+                raise ValueError('nbr is returned for host input only')
+            return iq[0], iq[1], False
+        iq = self._host_iq(iq)
+        return ptr(iq), iq.size, True              # (the pointer keeps the array alive)
+
+    @staticmethod
+    def _tables(prns, freqs, nbr=False):
+        """The tables of a search -> (the four arguments that name the PRNs and the bins, the
+        PEAK_DTYPE table [nbins, nsv] it fills, the neighbours float32 [nbins, nsv, 2] or None)."""
+        prn_a = np.ascontiguousarray(prns, dtype=np.int32)
+        f_a = np.ascontiguousarray(freqs, dtype=np.float64)
+        out = np.zeros((len(f_a), len(prn_a)), dtype=PEAK_DTYPE)
+        nb = np.zeros((len(f_a), len(prn_a), 2), dtype=np.float32) if nbr else None
+        return (ptr(prn_a), len(prn_a), ptr(f_a), len(f_a)), out, nb
+
+    def _export(self, name, host):
+        """The entry point `name` for host input, its `_dev` twin for device input -> (function, its name)."""
+        name = name if host else name + '_dev'
+        return getattr(self.lib, name), name
 
     def search(self, iq, prns, freqs, n_avg, out_dev=None):
         """iq: complex64 numpy array (host; uint16 after set_input_format(True)) or a
         (c_void_p, n) device pair.
         Returns a structured array [nbins, nsv] of (argmax, peak, mean, std)."""
-        prn_a = np.ascontiguousarray(prns, dtype=np.int32)
-        f_a = np.ascontiguousarray(freqs, dtype=np.float64)
-        out = np.zeros((len(f_a), len(prn_a)), dtype=PEAK_DTYPE)
-        if isinstance(iq, tuple):
-            d_iq, n = iq
-            check(self.lib.gpsmi_acq_search_dev(
-                self.h, d_iq, n, ptr(prn_a), len(prn_a), ptr(f_a), len(f_a),
-                n_avg, ptr(out), out_dev), 'gpsmi_acq_search_dev')
-        else:
-            iq = self._host_iq(iq)
-            check(self.lib.gpsmi_acq_search(
-                self.h, ptr(iq), iq.size, ptr(prn_a), len(prn_a), ptr(f_a),
-                len(f_a), n_avg, ptr(out)), 'gpsmi_acq_search')
+        tab, out, _ = self._tables(prns, freqs)
+        d_iq, n, host = self._input(iq)
+        fn, name = self._export('gpsmi_acq_search', host)
+        check(fn(self.h, d_iq, n, *tab, n_avg, ptr(out), *(() if host else (out_dev,))), name)
         return out
 
     def search_noncoherent(self, iq, prns, freqs, n_coh, n_seg, out_dev=None, nbr=False):
@@ -232,23 +258,10 @@ class AcqEngine:
         (c_void_p, n) device pair.  Returns the PEAK_DTYPE table [nbins, nsv] of that mean
         surface, and with nbr=True also its values left / right of every argmax
         (float32 [nbins, nsv, 2]; host input only)."""
-        prn_a = np.ascontiguousarray(prns, dtype=np.int32)
-        f_a = np.ascontiguousarray(freqs, dtype=np.float64)
-        out = np.zeros((len(f_a), len(prn_a)), dtype=PEAK_DTYPE)
-        nb = np.zeros((len(f_a), len(prn_a), 2), dtype=np.float32) if nbr else None
-        if isinstance(iq, tuple):
-            if nbr:
-                raise ValueError('nbr is returned for host input only')
-            d_iq, n = iq
-            check(self.lib.gpsmi_acq_search_nc_dev(
-                self.h, d_iq, n, ptr(prn_a), len(prn_a), ptr(f_a), len(f_a),
-                int(n_coh), int(n_seg), ptr(out), out_dev), 'gpsmi_acq_search_nc_dev')
-        else:
-            iq = self._host_iq(iq)
-            check(self.lib.gpsmi_acq_search_nc(
-                self.h, ptr(iq), iq.size, ptr(prn_a), len(prn_a), ptr(f_a), len(f_a),
-                int(n_coh), int(n_seg), ptr(out), ptr(nb) if nbr else None),
-                'gpsmi_acq_search_nc')
+        tab, out, nb = self._tables(prns, freqs, nbr)
+        d_iq, n, host = self._input(iq, nbr)
+        fn, name = self._export('gpsmi_acq_search_nc', host)
+        check(fn(self.h, d_iq, n, *tab, int(n_coh), int(n_seg), ptr(out), ptr(nb) if host else out_dev), name)
         return (out, nb) if nbr else out
 
     L1_HZ = 1575.42e6
@@ -264,47 +277,28 @@ class AcqEngine:
         rows: a DeviceBuffer of at least nsv * nbins * code_samples * 4 bytes that receives the
         surface of every cell, float32 [nsv][nbins][code_samples] (gpsmi_acq_search_deep_rows_dev;
         host input is uploaded first; not together with nbr).  The table is the same bytes."""
-        prn_a = np.ascontiguousarray(prns, dtype=np.int32)
-        f_a = np.ascontiguousarray(freqs, dtype=np.float64)
-        out = np.zeros((len(f_a), len(prn_a)), dtype=PEAK_DTYPE)
-        nb = np.zeros((len(f_a), len(prn_a), 2), dtype=np.float32) if nbr else None
+        tab, out, nb = self._tables(prns, freqs, nbr)
         if rows is not None:
             if nbr:
                 raise ValueError('nbr is not returned together with rows')
-            need = len(prn_a) * len(f_a) * self.cfg.code_samples * 4
+            need = out.size * self.cfg.code_samples * 4
             if rows.nbytes < need:
                 raise ValueError(f'rows holds {rows.nbytes} bytes, the surfaces need {need}')
-            held = None
-            if isinstance(iq, tuple):
-                d_iq, n = iq
-            else:
-                iq = self._host_iq(iq)
-                held = DeviceBuffer(max(iq.nbytes, 1), self.cfg.device)
-                held.upload(iq)
-                d_iq, n = held.ptr, iq.size
-            try:
-                check(self.lib.gpsmi_acq_search_deep_rows_dev(
-                    self.h, d_iq, n, ptr(prn_a), len(prn_a), ptr(f_a), len(f_a),
-                    int(n_coh), int(n_seg), float(carrier_hz), float(f_offset), ptr(out), out_dev,
-                    rows.ptr), 'gpsmi_acq_search_deep_rows_dev')
-            finally:
-                if held is not None:
-                    held.free()
-            return out
-        if isinstance(iq, tuple):
-            if nbr:
-                raise ValueError('nbr is returned for host input only')
-            d_iq, n = iq
-            check(self.lib.gpsmi_acq_search_deep_dev(
-                self.h, d_iq, n, ptr(prn_a), len(prn_a), ptr(f_a), len(f_a),
-                int(n_coh), int(n_seg), float(carrier_hz), float(f_offset), ptr(out), out_dev),
-                'gpsmi_acq_search_deep_dev')
-        else:
-            iq = self._host_iq(iq)
-            check(self.lib.gpsmi_acq_search_deep(
-                self.h, ptr(iq), iq.size, ptr(prn_a), len(prn_a), ptr(f_a), len(f_a),
-                int(n_coh), int(n_seg), float(carrier_hz), float(f_offset), ptr(out),
-                ptr(nb) if nbr else None), 'gpsmi_acq_search_deep')
+        d_iq, n, host = self._input(iq, nbr)
+        held = None
+        if rows is not None and host:              # the rows entry point reads device memory alone
+            nbytes = n * np.dtype(_iq_dtype(self.raw_u8)).itemsize
+            held = DeviceBuffer(max(nbytes, 1), self.cfg.device)
+            check(self.lib.gpsmi_dev_upload(held.device, held.ptr, d_iq, nbytes), 'gpsmi_dev_upload')
+            d_iq, host = held.ptr, False
+        name = 'gpsmi_acq_search_deep' + ('' if host else '_dev' if rows is None else '_rows_dev')
+        last = (ptr(nb),) if host else (out_dev,) if rows is None else (out_dev, rows.ptr)
+        try:
+            check(getattr(self.lib, name)(self.h, d_iq, n, *tab, int(n_coh), int(n_seg), float(carrier_hz),
+                                          float(f_offset), ptr(out), *last), name)
+        finally:
+            if held is not None:
+                held.free()
         return (out, nb) if nbr else out
 
     def collective(self, rows, sats, grid, nsv_rows=None, nbins=None):
@@ -349,21 +343,15 @@ class AcqEngine:
         self._need_time_replicas(h_a['prn'])   # the FFT searches never needed GPSCacode itself
         cfg = _lib.RefineCfg(int(n_ms), int(tap_samples), float(df_step), float(df_half),
                              float(carrier_hz), float(f_offset), float(min_ratio), 0)
-        host = not isinstance(iq, tuple)
-        if host:
-            iq = self._host_iq(iq)
-            d_iq, n = ptr(iq), iq.size
-        else:
-            d_iq, n = iq
+        d_iq, n, host = self._input(iq)
         n_df = C.c_int(0)
         check(self.lib.gpsmi_acq_refine_plan(cs, n, ptr(h_a), len(h_a), C.byref(cfg),
                                              C.byref(n_df)), 'gpsmi_acq_refine_plan')
         out = np.zeros(len(h_a), dtype=REFINE_OUT_DTYPE)
         grid = np.zeros((len(h_a), n_df.value, 20), np.float32) if want_grid else None
         prompts = np.zeros((len(h_a), 3, int(n_ms)), np.complex64) if want_prompts else None
-        fn = self.lib.gpsmi_acq_refine if host else self.lib.gpsmi_acq_refine_dev
-        check(fn(self.h, d_iq, n, ptr(h_a), len(h_a), C.byref(cfg), ptr(out), ptr(grid),
-                 ptr(prompts)), 'gpsmi_acq_refine' if host else 'gpsmi_acq_refine_dev')
+        fn, name = self._export('gpsmi_acq_refine', host)
+        check(fn(self.h, d_iq, n, ptr(h_a), len(h_a), C.byref(cfg), ptr(out), ptr(grid), ptr(prompts)), name)
         extra = [a for a in (grid, prompts) if a is not None]
         return (out, *extra) if extra else out
 
@@ -392,18 +380,12 @@ class AcqEngine:
         self._need_time_replicas(st['prn'])
         cfg = _lib.WtrkCfg(int(n_bits), int(tap_samples), float(pll_bw), float(fll_bw), float(dll_bw),
                            float(carrier_hz), float(f_offset), int(first_sample), int(pull_in_bits), 0)
-        host = not isinstance(iq, tuple)
-        if host:
-            iq = self._host_iq(iq)
-            d_iq, n = ptr(iq), iq.size
-        else:
-            d_iq, n = iq
+        d_iq, n, host = self._input(iq)
         check(self.lib.gpsmi_acq_track_plan(self.cfg.code_samples, n, ptr(st), len(st), C.byref(cfg)),
               'gpsmi_acq_track_plan')
         bits = np.zeros((len(st), int(n_bits)), dtype=WTRK_BIT_DTYPE)
-        fn = self.lib.gpsmi_acq_track if host else self.lib.gpsmi_acq_track_dev
-        check(fn(self.h, d_iq, n, ptr(st), len(st), C.byref(cfg), ptr(bits)),
-              'gpsmi_acq_track' if host else 'gpsmi_acq_track_dev')
+        fn, name = self._export('gpsmi_acq_track', host)
+        check(fn(self.h, d_iq, n, ptr(st), len(st), C.byref(cfg), ptr(bits)), name)
         return bits, st
 
     def cancel(self, data, sats, out=None, f_offset=0.0, coef=False, carrier_hz=L1_HZ, min_window=0):
@@ -421,12 +403,7 @@ class AcqEngine:
             s_a[i] = (int(prn), 0, float(f_hz), float(tau))
         self._need_time_replicas(s_a['prn'])
         cfg = _lib.CancelCfg(float(carrier_hz), float(f_offset), int(min_window), 0)
-        host = not isinstance(data, tuple)
-        if host:
-            data = self._host_iq(data)
-            d_iq, n = ptr(data), data.size
-        else:
-            d_iq, n = data
+        d_iq, n, host = self._input(data)
         max_w = C.c_int(0)
         check(self.lib.gpsmi_acq_cancel_plan(self.cfg.code_samples, n, ptr(s_a), len(s_a), C.byref(cfg),
                                              C.byref(max_w)), 'gpsmi_acq_cancel_plan')
@@ -437,15 +414,13 @@ class AcqEngine:
                 out = np.empty(n, np.complex64)
             if out.dtype != np.complex64 or out.size != n or not out.flags['C_CONTIGUOUS']:
                 raise TypeError('out must be a C-contiguous complex64 array of the length of data')
-            check(self.lib.gpsmi_acq_cancel(self.h, d_iq, n, ptr(s_a), len(s_a), C.byref(cfg), ptr(out), ptr(rec),
-                                            ptr(co)), 'gpsmi_acq_cancel')
-        else:
-            if out is None:
-                if self.raw_u8:
-                    raise ValueError('raw input cannot be cancelled in place: pass a complex64 device buffer')
-                out = d_iq
-            check(self.lib.gpsmi_acq_cancel_dev(self.h, d_iq, n, ptr(s_a), len(s_a), C.byref(cfg), out, ptr(rec),
-                                                ptr(co)), 'gpsmi_acq_cancel_dev')
+        elif out is None:
+            if self.raw_u8:
+                raise ValueError('raw input cannot be cancelled in place: pass a complex64 device buffer')
+            out = d_iq
+        fn, name = self._export('gpsmi_acq_cancel', host)
+        check(fn(self.h, d_iq, n, ptr(s_a), len(s_a), C.byref(cfg), ptr(out) if host else out, ptr(rec), ptr(co)),
+              name)
         return (out, rec, co) if coef else (out, rec)
 
     def search_async(self, d_iq, n, prns, freqs, n_avg, out, out_dev=None):
@@ -466,14 +441,9 @@ class AcqEngine:
 
     def search_ex(self, iq, prns, freqs, n_avg):
         """search() plus corr[argmax-1], corr[argmax+1] per cell: (table, nbr)."""
-        prn_a = np.ascontiguousarray(prns, dtype=np.int32)
-        f_a = np.ascontiguousarray(freqs, dtype=np.float64)
-        out = np.zeros((len(f_a), len(prn_a)), dtype=PEAK_DTYPE)
-        nbr = np.zeros((len(f_a), len(prn_a), 2), dtype=np.float32)
-        iq = self._host_iq(iq)
-        check(self.lib.gpsmi_acq_search_ex(
-            self.h, ptr(iq), iq.size, ptr(prn_a), len(prn_a), ptr(f_a), len(f_a),
-            n_avg, ptr(out), ptr(nbr)), 'gpsmi_acq_search_ex')
+        tab, out, nbr = self._tables(prns, freqs, True)
+        d_iq, n, _ = self._input(self._host_iq(iq))      # (host input only)
+        check(self.lib.gpsmi_acq_search_ex(self.h, d_iq, n, *tab, n_avg, ptr(out), ptr(nbr)), 'gpsmi_acq_search_ex')
         return out, nbr
 
     def last_ms(self):
@@ -519,6 +489,8 @@ class TrkEngine:
             check(self.lib.gpsmi_trk_set_replica(self.h, p, ptr(rep), ptr(spec)),
                   'gpsmi_trk_set_replica')
 
+    raw_u8 = False
+
     def _row(self, ch, stream):
         if self.streams == 1 and stream == 0:
             return ch                         # (the library checks the range itself)
@@ -559,12 +531,7 @@ class TrkEngine:
                                                  ptr(out)),
                   'gpsmi_trk_process_dev')
         else:
-            want = np.uint16 if getattr(self, 'raw_u8', False) else np.complex64
-            iq = np.asarray(iq)
-            if iq.dtype != want:       # a silent cast would turn one format into garbage of the other
-                raise TypeError(f'block dtype {iq.dtype} does not match the input format '
-                                f'({np.dtype(want).name}; see set_input_format)')
-            iq = np.ascontiguousarray(iq)
+            iq = _host_block(iq, self.raw_u8, 'block')
             if out is None:
                 out = np.zeros(shape, dtype=OUT_DTYPE)
             check(self.lib.gpsmi_trk_process(self.h, ptr(iq), iq.size, ptr(out)),
@@ -578,7 +545,7 @@ class TrkEngine:
         handle's input format, ideally a PinnedArray's, untouched until two later calls (or
         wait()) have returned; out: optional pinned OUT_DTYPE array, valid from the same moment."""
         n = self.streams * self.cfg.ngps
-        if iq.size != n or iq.dtype != (np.uint16 if getattr(self, 'raw_u8', False) else np.complex64):
+        if iq.size != n or iq.dtype != _iq_dtype(self.raw_u8):
             raise TypeError('block size or dtype does not match the handle')
         if not iq.flags.c_contiguous:
             raise ValueError('the block must be C-contiguous (its address is handed to the device)')

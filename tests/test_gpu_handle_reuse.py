@@ -14,6 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 P1, P2, P3 = 3, 11, 22
+SATS = [(P1, 0.0, 300.0), (P2, 0.0, 1200.0)]       # _scene's satellites as cancel takes them: (prn, f_hz, tau)
 
 
 def _same(a, b):
@@ -74,8 +75,10 @@ def _run_reused_and_fresh(make, steps):
 @pytest.mark.parametrize('raw_u8', [False, True], ids=['c64', 'u8'])
 def test_acq_2048(raw_u8):
     """search (3, 1), (9, 3), (3, 1); search_nc and search_deep with n_seg 2; refine of 1 and of 2
-    hits; acq_track of 1 hit; search (3, 1) again -- all from host memory, so each grows the one
-    input buffer they share."""
+    hits; acq_track of 1 hit; cancel of 1, of 2 and of 1 satellite (the last with the coefficients);
+    search (3, 1) again -- all from host memory, so each grows the one input buffer they share.  A
+    complex64 cancel works in place in that buffer, a raw one beside it, and the search that follows
+    reads the buffer again."""
     from gpsmi.acquisition import open_weak_channels
     from gpsmi.engine import Config
     cs = 2048
@@ -97,9 +100,86 @@ def test_acq_2048(raw_u8):
         lambda h: h.refine(iq, hits[:1], 40, want_grid=True, want_prompts=True),
         lambda h: h.refine(iq, hits, 40, want_grid=True, want_prompts=True),
         lambda h: h.track_weak(iq, state, 1),
+        lambda h: h.cancel(iq, SATS[:1]),
+        lambda h: h.cancel(iq, SATS),
+        lambda h: h.cancel(iq, SATS[:1], coef=True),
         lambda h: h.search(iq, (P1,), f3, 1),
     ]
     _run_reused_and_fresh(lambda: _acq(cs, raw_u8), steps)
+
+
+def test_acq_rows_and_collective():
+    """search_deep with rows (2 PRNs, 3 bins, n_seg 2) from host memory; collective over those rows
+    (2 satellites, a 2 x 2 x 1 grid) without and then with pooling, so the pooled half of the scratch
+    appears after the handle sized it without; the deep search again with 1 PRN."""
+    from gpsmi._lib import COLLECTIVE_SAT_DTYPE
+    from gpsmi.engine import DeviceBuffer
+    cs = 2048
+    iq = _scene(cs, 70, 1)[0]
+    f3 = np.array([-1000.0, 0.0, 1000.0])
+    sats = np.zeros(2, dtype=COLLECTIVE_SAT_DTYPE)      # (row, bin_lo, bin_hi, -, lag0, g_e, g_n, g_t)
+    sats[0] = (0, 0, 2, 0, 300.0, 0.75, -0.5, 0.0)
+    sats[1] = (1, 0, 2, 0, 1200.0, -1.25, 0.5, 0.0)
+    grid = dict(n_e=2, n_n=2, n_t=1, e0=-1.0, n0=-1.0, d_e=2.0, d_n=2.0)
+    rows = DeviceBuffer(2 * len(f3) * cs * 4)
+
+    def deep(prns):
+        def run(h):
+            tab = h.search_deep(iq, prns, f3, 2, 2, rows=rows)
+            return tab, rows.download(np.float32, len(prns) * len(f3) * cs)
+        return run
+
+    try:
+        # (the rows of the first step stay in the buffer for the two that follow: the fresh handle of
+        # a step writes what the reused one wrote)
+        _run_reused_and_fresh(lambda: _acq(cs, False), [
+            deep((P1, P2)),
+            lambda h: h.collective(rows, sats, dict(grid, pool=1), nsv_rows=2, nbins=3),
+            lambda h: h.collective(rows, sats, dict(grid, pool=2), nsv_rows=2, nbins=3),
+            deep((P1,)),
+        ])
+    finally:
+        rows.free()
+
+
+@pytest.mark.parametrize('raw_u8', [False, True], ids=['c64', 'u8'])
+def test_acq_host_and_device_input_agree(raw_u8):
+    """Every entry point that takes iq from host memory or as a (device pointer, n) pair gives the
+    same bytes for both: search, search_noncoherent, search_deep, refine (40 ms, one hit), track_weak
+    (one bit) and cancel (one satellite, into a device buffer of its own)."""
+    from gpsmi.acquisition import open_weak_channels
+    from gpsmi.engine import Config, DeviceBuffer
+    cs = 2048
+    iq = _scene(cs, 70, 1)[1 if raw_u8 else 0]
+    f3 = np.array([-1000.0, 0.0, 1000.0])
+    d_iq, d_out = DeviceBuffer(iq.nbytes), DeviceBuffer(iq.size * 8)
+    d_iq.upload(iq)
+    dev = (d_iq.ptr, iq.size)
+    e_host, e_dev = _acq(cs, raw_u8), _acq(cs, raw_u8)
+    try:
+        tab = e_host.search(iq, (P1,), [0.0], 1)
+        hit = [(P1, 0.0, int(tab[0, 0]['argmax']))]
+        state = open_weak_channels(e_host.refine(iq, hit, 40), Config(code_samples=cs, n_cyc=8))
+        calls = [
+            lambda h, x: h.search(x, (P1, P2), f3, 1),
+            lambda h, x: h.search_noncoherent(x, (P1, P2), f3, 1, 2),
+            lambda h, x: h.search_deep(x, (P1, P2), f3, 2, 2),
+            lambda h, x: h.refine(x, hit, 40, want_grid=True, want_prompts=True),
+            lambda h, x: h.track_weak(x, state, 1),
+        ]
+        for k, call in enumerate(calls):
+            try:
+                _same_all(call(e_host, iq), call(e_dev, dev))
+            except AssertionError as err:
+                raise AssertionError('call %d differs between host and device input' % k) from err
+        out, rec = e_host.cancel(iq, SATS[:1])
+        _, rec_dev = e_dev.cancel(dev, SATS[:1], out=d_out.ptr)
+        _same_all((out, rec), (d_out.download(np.complex64, iq.size), rec_dev))
+    finally:
+        e_host.close()
+        e_dev.close()
+        d_iq.free()
+        d_out.free()
 
 
 def test_acq_16368():
