@@ -13,6 +13,8 @@
 //                         (gpsmi_acq_cancel): per-period projection, in place
 //   gpsmi_collective.h    collective detection over the surfaces of a deep search
 //                         (gpsmi_acq_collective)
+//   gpsmi_peaks.h         the k largest peaks of every satellite over those surfaces, for the
+//                         spoofing check (gpsmi_acq_peaks)
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -28,6 +30,7 @@
 #include "gpsmi_wtrk.h"
 #include "gpsmi_cancel.h"
 #include "gpsmi_collective.h"
+#include "gpsmi_peaks.h"
 #include "gpsmi_acq_search.h"
 
 using namespace gpsmi;
@@ -84,6 +87,13 @@ struct gpsmi_acq {
     DevBuf<float> d_cz;
     DevBuf<gpsmi_collective_sat> d_csat;          // [kColMaxSats]
     DevBuf<gpsmi_collective_cell> d_cc;
+    // auxiliary peaks (gpsmi_acq_peaks): the statistics [nsv][nbins], zmax and its bins [nsv][cs], the
+    // picks [nsv][k] and their columns [nsv][k][2][nbins]
+    DevBuf<float2> d_pst;
+    DevBuf<float> d_pz;
+    DevBuf<int> d_pb;
+    DevBuf<gpsmi_peaks_pick> d_pk;
+    DevBuf<float> d_pcol;
     int iq_fmt = GPSMI_IQ_C64;              // what the iq pointers of the search calls point to
     // bytes of `n` samples in the handle's input format
     size_t iq_bytes(size_t n) const { return n * (iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)); }
@@ -806,6 +816,51 @@ int gpsmi_acq_collective_plan(int code_samples, int nsv_rows, int nbins, const g
                               const gpsmi_collective_grid* grid, size_t* scratch_bytes, int* workgroups) {
     ColPlan pl;
     const int rc = collective_plan(code_samples, nsv_rows, nbins, sats, nsat, grid, &pl);
+    if (rc == GPSMI_OK && scratch_bytes) *scratch_bytes = pl.scratch_bytes;
+    if (rc == GPSMI_OK && workgroups) *workgroups = pl.workgroups;
+    return rc;
+}
+
+// ---- auxiliary peaks per satellite (kernels and plan: gpsmi_peaks.h) ---------------------------
+int gpsmi_acq_peaks_dev(gpsmi_acq* h, const void* d_rows, int nsv_rows, int nbins, const gpsmi_peaks_cfg* cfg,
+                        gpsmi_peaks_pick* out_host, void* out_dev, float* cols_host, void* cols_dev) {
+    GPSMI_REQUIRE(h && d_rows, "null argument");
+    GPSMI_REQUIRE(out_host || out_dev, "no output requested");
+    PeaksPlan pl;
+    int rc = peaks_plan(h->cfg.code_samples, nsv_rows, nbins, cfg, &pl);
+    if (rc || (rc = acq_enter(h))) return rc;
+    const int cs = pl.cs;
+    const bool want_cols = cols_host || cols_dev;
+    const size_t npick = (size_t)nsv_rows * pl.k, ncol = npick * 2 * nbins;
+    if ((rc = h->d_pst.reserve((size_t)nsv_rows * nbins, "gpsmi_acq_peaks statistics")) ||
+        (rc = h->d_pz.reserve((size_t)nsv_rows * cs, "gpsmi_acq_peaks zmax")) ||
+        (rc = h->d_pb.reserve((size_t)nsv_rows * cs, "gpsmi_acq_peaks bins")) ||
+        (rc = h->d_pk.reserve(npick, "gpsmi_acq_peaks picks")) ||
+        (want_cols && (rc = h->d_pcol.reserve(ncol, "gpsmi_acq_peaks columns"))) ||
+        (rc = acq_begin(h)))
+        return rc;
+    const float* rows = static_cast<const float*>(d_rows);
+    hipLaunchKernelGGL(peaks_stats_kernel, dim3(pl.hi - pl.lo + 1, nsv_rows), dim3(256), 0, h->stream, rows, nbins, cs,
+                       pl.lo, h->d_pst.p);
+    hipLaunchKernelGGL(peaks_zmax_kernel, dim3((cs + kPeaksLagTile - 1) / kPeaksLagTile, nsv_rows),
+                       dim3(kPeaksLagTile), 0, h->stream, rows, nbins, cs, pl.lo, pl.hi, h->d_pst.p, h->d_pz.p,
+                       h->d_pb.p);
+    hipLaunchKernelGGL(peaks_pick_kernel, dim3(nsv_rows), dim3(256), 0, h->stream, rows, nbins, cs, pl.k, pl.guard,
+                       pl.lo, pl.hi, h->d_pst.p, h->d_pz.p, h->d_pb.p, h->d_pk.p,
+                       want_cols ? h->d_pcol.p : (float*)nullptr);
+    if ((rc = acq_end(h))) return rc;
+    const size_t bp = npick * sizeof(gpsmi_peaks_pick), bc = ncol * sizeof(float);
+    if (out_dev) GPSMI_HIP(hipMemcpyAsync(out_dev, h->d_pk.p, bp, hipMemcpyDeviceToDevice, h->stream));
+    if (out_host) GPSMI_HIP(hipMemcpyAsync(out_host, h->d_pk.p, bp, hipMemcpyDeviceToHost, h->stream));
+    if (cols_dev) GPSMI_HIP(hipMemcpyAsync(cols_dev, h->d_pcol.p, bc, hipMemcpyDeviceToDevice, h->stream));
+    if (cols_host) GPSMI_HIP(hipMemcpyAsync(cols_host, h->d_pcol.p, bc, hipMemcpyDeviceToHost, h->stream));
+    return gpsmi_acq_wait(h);
+}
+
+int gpsmi_acq_peaks_plan(int code_samples, int nsv_rows, int nbins, const gpsmi_peaks_cfg* cfg, size_t* scratch_bytes,
+                         int* workgroups) {
+    PeaksPlan pl;
+    const int rc = peaks_plan(code_samples, nsv_rows, nbins, cfg, &pl);
     if (rc == GPSMI_OK && scratch_bytes) *scratch_bytes = pl.scratch_bytes;
     if (rc == GPSMI_OK && workgroups) *workgroups = pl.workgroups;
     return rc;

@@ -104,6 +104,18 @@ __device__ __forceinline__ float col_tree_sum(float v, float* red, int t) {
     return red[0];
 }
 
+// mean and population std of one surface S[cs] as step a forms them, in every thread of a 256-thread
+// workgroup (inv = 1 / cs): the one copy, shared with gpsmi_peaks.h
+__device__ __forceinline__ void col_row_stats(const float* __restrict__ S, int cs, float inv, float* red, int t,
+                                              float& mean, float& sd) {
+    float a = 0.f;
+    for (int l = t; l < cs; l += 256) a = a + S[l];
+    mean = col_tree_sum(a, red, t) * inv;
+    a = 0.f;
+    for (int l = t; l < cs; l += 256) { const float d = S[l] - mean; a = a + d * d; }
+    sd = sqrtf(col_tree_sum(a, red, t) * inv);    // (correctly rounded, as the divisions by it)
+}
+
 __global__ __launch_bounds__(256) void collective_norm_kernel(const float* __restrict__ rows, int nbins, int cs,
                                                               const gpsmi_collective_sat* __restrict__ sats,
                                                               float* __restrict__ z) {
@@ -115,12 +127,8 @@ __global__ __launch_bounds__(256) void collective_norm_kernel(const float* __res
     bool any = false;
     for (int b = sat.bin_lo; b <= sat.bin_hi; ++b) {
         const float* S = rows + ((size_t)sat.row * nbins + b) * cs;
-        float a = 0.f;
-        for (int l = t; l < cs; l += 256) a = a + S[l];
-        const float mean = col_tree_sum(a, red, t) * inv;
-        a = 0.f;
-        for (int l = t; l < cs; l += 256) { const float d = S[l] - mean; a = a + d * d; }
-        const float sd = sqrtf(col_tree_sum(a, red, t) * inv);        // (correctly rounded, as the division below)
+        float mean, sd;
+        col_row_stats(S, cs, inv, red, t, mean, sd);
         if (!(sd > 0.f)) continue;                // (the same in every thread)
         for (int l = t; l < cs; l += 256) {
             const float v = (S[l] - mean) / sd;

@@ -149,6 +149,8 @@ int gpsmi_abi_sizeof(int which) {
         case 19: return (int)sizeof(gpsmi_collective_cell);
         case 21: return (int)sizeof(gpsmi_nul_cfg);
         case 23: return (int)sizeof(gpsmi_tfx_cfg);   // (20 and 22 stay unused: tests hold them to -1)
+        case 24: return (int)sizeof(gpsmi_peaks_cfg);
+        case 25: return (int)sizeof(gpsmi_peaks_pick);
         default: return -1;
     }
 }

@@ -87,6 +87,10 @@ class CollectiveGrid(C.Structure):
                 ('d_e', C.c_double), ('d_n', C.c_double), ('d_t', C.c_double)]
 
 
+class PeaksCfg(C.Structure):
+    _fields_ = [('k', C.c_int32), ('guard_lags', C.c_int32), ('bin_lo', C.c_int32), ('bin_hi', C.c_int32)]
+
+
 class Cfg(C.Structure):
     _fields_ = [('code_samples', C.c_int32), ('n_cyc', C.c_int32),
                 ('corr_avg', C.c_int32), ('sweep_corr_avg', C.c_int32),
@@ -118,6 +122,9 @@ COLLECTIVE_SAT_DTYPE = np.dtype([('row', np.int32), ('bin_lo', np.int32), ('bin_
                                  ('g_n', np.float64), ('g_t', np.float64)])
 
 COLLECTIVE_CELL_DTYPE = np.dtype([('score', np.float32), ('lag', np.int32)])
+
+PEAKS_PICK_DTYPE = np.dtype([('lag', np.int32), ('bin', np.int32), ('z', np.float32), ('s', np.float32)])
+PEAKS_MAX_K = 8               # kPeaksMaxK
 
 COLLECTIVE_MAX_SATS = 32      # kColMaxSats
 COLLECTIVE_MAX_CELLS = 1 << 22
@@ -173,6 +180,7 @@ EXPORTS = [
     'gpsmi_acq_search_nc', 'gpsmi_acq_search_nc_dev',
     'gpsmi_acq_search_deep', 'gpsmi_acq_search_deep_dev', 'gpsmi_acq_search_deep_rows_dev',
     'gpsmi_acq_collective_dev', 'gpsmi_acq_collective_plan',
+    'gpsmi_acq_peaks_dev', 'gpsmi_acq_peaks_plan',
     'gpsmi_acq_refine', 'gpsmi_acq_refine_dev', 'gpsmi_acq_refine_plan',
     'gpsmi_acq_track', 'gpsmi_acq_track_dev', 'gpsmi_acq_track_plan', 'gpsmi_wtrk_open',
     'gpsmi_acq_cancel', 'gpsmi_acq_cancel_dev', 'gpsmi_acq_cancel_plan',
@@ -260,6 +268,8 @@ def load():
         'gpsmi_acq_collective_dev': [vp, vp, C.c_int, C.c_int, vp, C.c_int, P(CollectiveGrid), vp, vp],
         'gpsmi_acq_collective_plan': [C.c_int, C.c_int, C.c_int, vp, C.c_int, P(CollectiveGrid),
                                       P(sz), P(C.c_int)],
+        'gpsmi_acq_peaks_dev': [vp, vp, C.c_int, C.c_int, P(PeaksCfg), vp, vp, vp, vp],
+        'gpsmi_acq_peaks_plan': [C.c_int, C.c_int, C.c_int, P(PeaksCfg), P(sz), P(C.c_int)],
         'gpsmi_acq_refine': [vp, vp, sz, vp, C.c_int, P(RefineCfg), vp, vp, vp],
         'gpsmi_acq_refine_dev': [vp, vp, sz, vp, C.c_int, P(RefineCfg), vp, vp, vp],
         'gpsmi_acq_refine_plan': [C.c_int, sz, vp, C.c_int, P(RefineCfg), P(C.c_int)],
@@ -361,7 +371,7 @@ def load():
            (10, C.sizeof(WtrkCfg)), (11, WTRK_STATE_DTYPE.itemsize), (12, WTRK_BIT_DTYPE.itemsize),
            (13, CANCEL_SAT_DTYPE.itemsize), (14, C.sizeof(CancelCfg)), (15, CANCEL_OUT_DTYPE.itemsize),
            (17, COLLECTIVE_SAT_DTYPE.itemsize), (18, C.sizeof(CollectiveGrid)), (19, COLLECTIVE_CELL_DTYPE.itemsize),
-           (21, C.sizeof(NulCfg)), (23, C.sizeof(TfxCfg))]
+           (21, C.sizeof(NulCfg)), (23, C.sizeof(TfxCfg)), (24, C.sizeof(PeaksCfg)), (25, PEAKS_PICK_DTYPE.itemsize)]
     want = [size for _, size in abi]
     got = [lib.gpsmi_abi_sizeof(i) for i, _ in abi]
     if want != got:

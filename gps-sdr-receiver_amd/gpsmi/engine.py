@@ -161,6 +161,27 @@ def collective_plan(code_samples, nsv_rows, nbins, sats, grid):
     return scratch.value, wgs.value
 
 
+PEAKS_PICK_DTYPE = _lib.PEAKS_PICK_DTYPE
+MAX_PEAK_ROWS = _lib.MAX_PRN + 1          # kPeaksMaxRows
+
+
+def peaks_cfg(nbins, k=4, guard_lags=-1, bins=None):
+    """The options of AcqEngine.peaks (gpsmi_peaks_cfg).  bins: the inclusive window (lo, hi), by
+    default the whole row."""
+    lo, hi = (0, int(nbins) - 1) if bins is None else bins
+    return _lib.PeaksCfg(int(k), int(guard_lags), int(lo), int(hi))
+
+
+def peaks_plan(code_samples, nsv_rows, nbins, k=4, guard_lags=-1, bins=None):
+    """gpsmi_acq_peaks_plan: the argument checks of AcqEngine.peaks without a GPU.
+    -> (scratch_bytes, workgroups); EngineError where the call would refuse."""
+    c = peaks_cfg(nbins, k, guard_lags, bins)
+    scratch, wgs = C.c_size_t(), C.c_int()
+    check(_lib.load().gpsmi_acq_peaks_plan(int(code_samples), int(nsv_rows), int(nbins), C.byref(c),
+                                           C.byref(scratch), C.byref(wgs)), 'gpsmi_acq_peaks_plan')
+    return scratch.value, wgs.value
+
+
 def _iq_dtype(raw_u8):
     """What a handle's input format holds per sample: the recorder's uint16 (Q << 8 | I) or complex64."""
     return np.uint16 if raw_u8 else np.complex64
@@ -326,6 +347,32 @@ class AcqEngine:
             self.h, rows.ptr, int(nsv_rows), int(nbins), ptr(sats), len(sats), C.byref(g), ptr(out),
             None), 'gpsmi_acq_collective_dev')
         return out
+
+    def peaks_plan(self, nsv_rows, nbins, k=4, guard_lags=-1, bins=None):
+        """peaks_plan at the engine's code length."""
+        return peaks_plan(self.cfg.code_samples, nsv_rows, nbins, k, guard_lags, bins)
+
+    def peaks(self, d_rows, nsv_rows, nbins, k=4, guard_lags=-1, bins=None, cols=True, out_dev=None,
+              cols_dev=None):
+        """Auxiliary peaks (gpsmi_acq_peaks_dev) over the surfaces `d_rows` that
+        search_deep(..., rows=) left: a DeviceBuffer of float32 [nsv_rows][nbins][code_samples].
+        Per satellite the k largest values of z = (S - mean) / std over the bins of the window
+        `bins` (inclusive (lo, hi), by default all), more than guard_lags apart (circular; -1: two
+        chips).  Returns (picks, cols): PEAKS_PICK_DTYPE [nsv_rows, k] (lag, bin, z, s; -1, -1, 0, 0
+        where there is no pick) and, with cols=True, float32 [nsv_rows, k, 2, nbins]: S and z down
+        the bins at every picked lag (else None).  out_dev / cols_dev: device pointers that receive
+        the same bytes."""
+        c = peaks_cfg(nbins, k, guard_lags, bins)
+        need = int(nsv_rows) * int(nbins) * self.cfg.code_samples * 4
+        if need > 0 and d_rows.nbytes < need:
+            raise ValueError(f'rows holds {d_rows.nbytes} bytes, [{nsv_rows}][{nbins}] surfaces are {need}')
+        ok = 0 < int(nsv_rows) <= MAX_PEAK_ROWS and 0 < int(nbins) <= 4096 and 0 < c.k <= _lib.PEAKS_MAX_K
+        shape = (int(nsv_rows), c.k) if ok else (1, 1)        # (a refused call writes nothing)
+        picks = np.zeros(shape, dtype=PEAKS_PICK_DTYPE)
+        col = np.zeros(shape + (2, int(nbins) if ok else 1), np.float32) if cols else None
+        check(self.lib.gpsmi_acq_peaks_dev(self.h, d_rows.ptr, int(nsv_rows), int(nbins), C.byref(c), ptr(picks),
+                                           out_dev, ptr(col), cols_dev), 'gpsmi_acq_peaks_dev')
+        return picks, col
 
     def refine(self, iq, hits, n_ms, df_step=2.0, df_half=120.0, tap_samples=0, f_offset=0.0,
                carrier_hz=L1_HZ, min_ratio=2.5, want_grid=False, want_prompts=False):

@@ -199,16 +199,53 @@ def largest_peak_hits(acq, data, prns, freqs, n_coh=4, n_seg=250, f_offset=0.0, 
             for j, (s, b) in enumerate(zip(prns, best)) if over[b, j]]
 
 
-def refine_centred(acq, data, found, f_offset=0.0):
+def hits_of_picks(picks, cols, prns, freqs, corr_min):
+    """The hits ``(z, satNo, freq, lag)`` of AcqEngine.peaks' picks [nsv][k] and columns
+    [nsv][k][2][nbins]: one per pick with z > corr_min, in pick order.  The bin is
+    not the pick's own (the bin of largest z lies beside a strong or doubled satellite, whose own
+    peaks raise the std of its bin) but largest_peak_hits' choice on the pick's column: among the
+    bins with z > corr_min at that lag the one of largest S, the first of equal ones."""
+    hits = []
+    for j, s in enumerate(prns):
+        for pk, col in zip(picks[j], cols[j]):
+            if pk['lag'] < 0 or not pk['z'] > corr_min:
+                continue
+            over = col[1] > corr_min
+            b = int(np.where(over, col[0], -np.inf).argmax())
+            hits.append((float(pk['z']), s, freqs[b], int(pk['lag'])))
+    return hits
+
+
+def peak_candidates(acq, data, prns, freqs, n_coh, n_seg, f_offset=0.0, corr_min=None, k=4, stats=None):
+    """Up to `k` deep-search hits ``(z, satNo, freq, lag)`` per PRN, more than two chips apart in
+    code phase: one deep search that keeps its surfaces (Acquisition.deepRows), then
+    AcqEngine.peaks over them and hits_of_picks (`corr_min` defaults to the configuration's).  A
+    PRN that is in the air twice yields two hits where largest_peak_hits keeps the stronger.
+    `stats`: a dict that receives picks, cols and the device ms of the two calls."""
+    prns, freqs = list(prns), list(freqs)
+    corr_min = acq.cfg.corr_min if corr_min is None else corr_min
+    _, rows = acq.deepRows(data, prns, freqs, n_coh, n_seg, f_offset=f_offset)
+    try:
+        search_ms = acq.engine.last_ms()
+        picks, cols = acq.engine.peaks(rows, len(prns), len(freqs), k=k)
+        peaks_ms = acq.engine.last_ms()
+    finally:
+        rows.free()
+    if stats is not None:
+        stats.update(picks=picks, cols=cols, search_ms=search_ms, peaks_ms=peaks_ms)
+    return hits_of_picks(picks, cols, prns, freqs, corr_min)
+
+
+def refine_centred(acq, data, found, f_offset=0.0, **cfg):
     """Acquisition.refineHits, and again for every confirmed hit that came back without a code
     phase because its early or late tap was larger than its prompt: the search's integer delay
     was one off (the peak of a second's search lies where the sliding code spent most of it), so
-    the hit is refined one tap spacing towards the larger tap, twice at the most.
-    -> (found with the delays used, records, device ms)."""
+    the hit is refined one tap spacing towards the larger tap, twice at the most.  `cfg`:
+    refineHits' keywords (df_half, ...).  -> (found with the delays used, records, device ms)."""
     cs = acq.cfg.code_samples
     tap = 1 if cs == 2048 else 8
     found = list(found)
-    rec = acq.refineHits(data, found, f_offset=f_offset)
+    rec = acq.refineHits(data, found, f_offset=f_offset, **cfg)
     ms = acq.engine.last_ms()
     for _ in range(2):
         bad = [i for i, r in enumerate(rec) if r['confirmed'] == 1 and r['code_phase'] < 0]
@@ -218,7 +255,7 @@ def refine_centred(acq, data, found, f_offset=0.0):
             nmc, s, f, d = found[i]
             e, _, l = rec[i]['tap_metric']
             found[i] = (nmc, s, f, int(d + (-tap if e > l else tap)) % cs)
-        rec[bad] = acq.refineHits(data, [found[i] for i in bad], f_offset=f_offset)
+        rec[bad] = acq.refineHits(data, [found[i] for i in bad], f_offset=f_offset, **cfg)
         ms += acq.engine.last_ms()
     return found, rec, ms
 

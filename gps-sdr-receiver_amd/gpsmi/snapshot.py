@@ -118,6 +118,7 @@ class Fix:
     tau: object = None                    # tested figure per metre of bias on each satellite
     slope: object = None                  # position error per unit of the tested figure, per satellite
     path: str = 'measure'                 # what supplied the measurements: 'measure' or 'collective' (snapshot_fix)
+    spoof: object = field(default=None, compare=False, repr=False)   # snapshot_fix(..., spoof=True): the SpoofReport
 
 
 def _solve(prns, samples, phases, w, ephs, clock, pos0, fs):
@@ -356,6 +357,157 @@ def _measure_pass(acq, dev, n, prns, freqs, n_coh, n_seg, corr_min, f_offset, st
     return refined_records(rec, found, cs, f_offset)
 
 
+# ---------------------------------------------------------------- the spoofing check
+SPOOF_REL_DB = 12.0                      # a PRN's second record must read within this of its strongest
+SPOOF_MIN_DOUBLED = 2                    # doubled PRNs that raise the alarm
+SPOOF_MAX_DOUBLED = 8                    # doubled PRNs the twin fixes enumerate: 2^7 assignments
+SPOOF_PICKS = 4                          # peaks taken per PRN
+SPOOF_REFINE_HITS = 64                   # hits of one refinement call (kRefMaxHits)
+
+
+@dataclass
+class SpoofReport:
+    """What measure(..., spoof=True) and snapshot_fix(..., spoof=True) say about a snapshot.  It
+    names PRNs that are in the air twice and, where both sets solve, two positions; it makes no
+    claim about which of them is authentic."""
+    doubled: list = field(default_factory=list)     # PRNs with two records
+    alarm: bool = False                             # len(doubled) >= min_doubled
+    crowded: bool = False                           # a PRN had more than two records that count: the two strongest stayed
+    prns: list = field(default_factory=list)        # the PRN of every row of `picks`
+    picks: object = None                            # PEAKS_PICK_DTYPE [len(prns)][k] (None off the GPU path)
+    fixes: tuple = None                             # snapshot_fix: (fix_a, fix_b), or (the single fix, None)
+    separation_m: float = None                      # |fix_a - fix_b|, None without two fixes
+    assignments: int = 0                            # pairs of sets that were solved
+
+
+def spoof_keep(rec, found, cs, f_offset=0.0, min_doubled=SPOOF_MIN_DOUBLED):
+    """The keep rule of the spoofing check on the refinement records `rec` of the hits `found`
+    (several per PRN): refined_records' rule (confirmed, a code phase, no ghost), then per PRN the
+    records reading within SPOOF_REL_DB of its strongest by refinement's C/N0 -- the code's
+    autocorrelation sidelobes lie 24 dB down, a spoofer that means to capture a loop within a few
+    dB -- and of those the two strongest.  -> (rec, found, MEAS_DTYPE records sorted by PRN, a PRN
+    may appear twice; SpoofReport with doubled, alarm and crowded)."""
+    rec, found, out = refined_records(rec, found, cs, f_offset)
+    cn0 = np.where(np.isfinite(rec['cn0_dbhz']), rec['cn0_dbhz'], -np.inf).astype(np.float64)
+    keep, report = [], SpoofReport()
+    for prn in sorted(set(rec['prn'].tolist())):
+        idx = np.flatnonzero(rec['prn'] == prn)
+        idx = idx[np.argsort(-cn0[idx], kind='stable')]               # the strongest first
+        near = [i for i in idx if cn0[i] >= cn0[idx[0]] - SPOOF_REL_DB]
+        report.crowded = report.crowded or len(near) > 2
+        keep += sorted(near[:2])
+        if len(near) >= 2:
+            report.doubled.append(int(prn))
+    report.alarm = len(report.doubled) >= min_doubled
+    keep = np.array(keep, dtype=np.int64)
+    return rec[keep], [found[i] for i in keep], out[keep], report
+
+
+def twin_sets(meas):
+    """The complementary assignments of the records of doubled PRNs to two sets: records of
+    `meas` (sorted by PRN).  Single records go into both sets; of D doubled PRNs (beyond
+    SPOOF_MAX_DOUBLED the ones with the strongest weaker record) the first keeps its order and the
+    others take both: 2^(D-1) pairs.  A PRN doubled beyond the limit gives its stronger record to
+    both sets.  -> list of (indices of set a, indices of set b)."""
+    prns = meas['prn'].tolist()
+    pairs = {p: [i for i, q in enumerate(prns) if q == p] for p in sorted(set(prns))}
+    doubled = [p for p, ix in pairs.items() if len(ix) == 2]
+    weaker = {p: min(meas['cn0_dbhz'][i] for i in pairs[p]) for p in doubled}
+    used = sorted(sorted(doubled, key=lambda p: -np.nan_to_num(weaker[p], nan=-np.inf))[:SPOOF_MAX_DOUBLED])
+    base = []
+    for p, ix in pairs.items():
+        if p not in used:
+            base.append(ix[0] if len(ix) == 1 else max(ix, key=lambda i: np.nan_to_num(meas['cn0_dbhz'][i], nan=-np.inf)))
+    out = []
+    for code in range(1 << max(len(used) - 1, 0)):
+        a, b = list(base), list(base)
+        for j, p in enumerate(used):
+            flip = j > 0 and (code >> (j - 1)) & 1
+            a.append(pairs[p][1 if flip else 0])
+            b.append(pairs[p][0 if flip else 1])
+        out.append((sorted(a), sorted(b)))
+    return out
+
+
+def twin_fixes(meas, ephs, t_gps, pos, report, code_samples=2048, have_pos=True):
+    """Solves once per consistent assignment (twin_sets) with coarse_time_fix, `t_gps` the GPS time
+    of stream index 0 and `pos` the a-priori (the first solution that is ok serves as the a-priori
+    of the sets that follow), and takes the pair whose two fixes are both ok with the least sum of
+    rms_m.  With an a-priori position of the caller's (`have_pos`) the fix nearer to it goes first,
+    otherwise the one with the lower mean C/N0 on its doubled records.  Without such a pair: the
+    best single ok fix and None.  Fills report.fixes, separation_m and assignments.
+    -> fix_a (a Fix that is not ok when nothing solved)."""
+    fs = 1000.0 * code_samples
+    pos0 = np.asarray(pos, dtype=np.float64)
+    apriori, solved = pos0, {}
+
+    def solve(ix):
+        nonlocal apriori
+        key = tuple(ix)
+        if key not in solved:
+            m = meas[list(ix)]
+            ref = int(np.argmax(cn0_weights(m['cn0_dbhz'])))
+            solved[key] = coarse_time_fix(m, ephs, float(t_gps) + int(m['sample'][ref]) / fs, apriori,
+                                          code_samples=code_samples)
+            if solved[key].ok and apriori is pos0:
+                apriori = solved[key].ecef.copy()
+        return solved[key]
+
+    doubled = set(report.doubled)
+    best, single = None, None
+    for a, b in twin_sets(meas):
+        fa, fb = solve(a), solve(b)
+        report.assignments += 1
+        for f in (fa, fb):
+            if f.ok and (single is None or f.rms_m < single.rms_m):
+                single = f
+        if a != b and fa.ok and fb.ok and (best is None or fa.rms_m + fb.rms_m < best[0]):     # (a == b: no doubled PRN)
+            best = (fa.rms_m + fb.rms_m, (fa, a), (fb, b))
+    if best is None:
+        fix = single if single is not None else solve(twin_sets(meas)[0][0])
+        report.fixes, report.separation_m = (fix, None), None
+        return fix
+    (fa, a), (fb, b) = best[1], best[2]
+    if have_pos:
+        swap = np.linalg.norm(fb.ecef - pos0) < np.linalg.norm(fa.ecef - pos0)
+    else:
+        def level(ix):
+            c = [meas['cn0_dbhz'][i] for i in ix if int(meas['prn'][i]) in doubled]
+            return float(np.nanmean(c)) if c else 0.0
+        swap = level(b) < level(a)
+    if swap:
+        fa, fb = fb, fa
+    report.fixes, report.separation_m = (fa, fb), float(np.linalg.norm(fa.ecef - fb.ecef))
+    return fa
+
+
+def _spoof_pass(acq, dev, n, prns, freqs, n_coh, n_seg, corr_min, f_offset, st, min_doubled):
+    """_measure_pass with several candidates per PRN: pipeline.peak_candidates, refinement over
+    +- one bin step (a hit's bin lies up to half a step beside a doubled satellite's Doppler, which
+    the default +-120 Hz would leave at the edge of the grid), spoof_keep.
+    -> (rec, found, records, SpoofReport)."""
+    from .pipeline import peak_candidates, refine_centred
+    cs = acq.cfg.code_samples
+    pst = {}
+    found = peak_candidates(acq, (dev[0], n_seg * n_coh * cs), prns, freqs, n_coh, n_seg, f_offset=f_offset,
+                            corr_min=corr_min, k=SPOOF_PICKS, stats=pst)
+    st['device_ms'] += pst['search_ms'] + pst['peaks_ms']
+    st['peaks_ms'] = pst['peaks_ms']
+    if not found:
+        return None, [], np.zeros(0, MEAS_DTYPE), SpoofReport(prns=list(prns), picks=pst['picks'])
+    step = abs(freqs[1] - freqs[0]) if len(freqs) > 1 else acq.cfg.step_freq
+    recs, used = [], []
+    for i in range(0, len(found), SPOOF_REFINE_HITS):
+        f, r, ms = refine_centred(acq, dev, found[i:i + SPOOF_REFINE_HITS], f_offset=f_offset, df_half=float(step))
+        st['device_ms'] += ms
+        used, recs = used + f, recs + [r]
+    rec = np.concatenate(recs)
+    st['found'], st['refined'] = st['found'] + used, rec if st['refined'] is None else np.concatenate([st['refined'], rec])
+    rec, used, out, report = spoof_keep(rec, used, cs, f_offset, min_doubled)
+    report.prns, report.picks = list(prns), pst['picks']
+    return rec, used, out, report
+
+
 def _track_records(acq, dev, rec, out, n, f_offset, track_cfg, st):
     if len(rec):
         bits, states = acq.trackHits(dev, rec, f_offset=f_offset, **track_cfg)
@@ -363,7 +515,7 @@ def _track_records(acq, dev, rec, out, n, f_offset, track_cfg, st):
         tracked_records(out, bits, states['bit_no'], n, acq.cfg.code_samples, track_cfg.get('pull_in_bits', 0))
 
 
-def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=None, **cfg):
+def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=None, spoof=False, **cfg):
     """The satellites of one snapshot: MEAS_DTYPE records, one per satellite found, sorted by PRN.
 
     `acq`: an acquisition.Acquisition; `data`: the samples in its input format (complex64, or the
@@ -385,7 +537,12 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
     cancelled satellites cast no ghosts any more), and with source 'track' the kept records are
     tracked on the data as it came, the others on the copy.
     `stats`: a dict that receives device_ms (the sum of the engine's last_ms over every stage),
-    found and refined (of both passes) and, with `cancel`, cancelled (the CANCEL_OUT_DTYPE records)."""
+    found and refined (of both passes) and, with `cancel`, cancelled (the CANCEL_OUT_DTYPE records).
+    `spoof` (not together with `cancel`): True -- the candidates are up to
+    SPOOF_PICKS peaks per PRN (pipeline.peak_candidates), refined over +- one bin step and kept by
+    spoof_keep: a PRN that is in the air twice comes back with two records.  -> (records,
+    SpoofReport); `min_doubled`: the doubled PRNs that set its alarm; stats also receives spoof
+    (the report) and peaks_ms.  With the option off nothing of this runs."""
     from .acquisition import SAT_ALL
     from .engine import CANCEL_OUT_DTYPE, DeviceBuffer
     c = acq.cfg
@@ -394,8 +551,11 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
     corr_min = float(cfg.pop('corr_min', c.corr_min))
     freqs = cfg.pop('freqs', None)
     track_cfg = dict(cfg.pop('track_cfg', None) or {})
+    min_doubled = int(cfg.pop('min_doubled', SPOOF_MIN_DOUBLED))
     if cfg:
         raise TypeError(f'unknown options {sorted(cfg)}')
+    if spoof and cancel not in (None, False):
+        raise ValueError('spoof and cancel are not combined')
     if freqs is None:
         freqs = [c.min_freq + c.step_freq * i for i in range(int(round((c.max_freq - c.min_freq) / c.step_freq)))]
     prns = list(SAT_ALL if prns is None else prns)
@@ -417,6 +577,15 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
             buf.upload(host)
             dev = (buf.ptr, n)
         st = {'device_ms': 0.0, 'found': [], 'refined': None}
+        if spoof:
+            rec, found, out, report = _spoof_pass(acq, dev, n, prns, freqs, n_coh, n_seg, corr_min, f_offset, st,
+                                                  min_doubled)
+            if source == 'track' and len(out):
+                _track_records(acq, dev, rec, out, n, f_offset, track_cfg, st)     # (indexed by record)
+            st['spoof'] = report
+            if stats is not None:
+                stats.update(st)
+            return out, report
         rec, found, out = _measure_pass(acq, dev, n, prns, freqs, n_coh, n_seg, corr_min, f_offset, st)
         if cancel_dbhz is not None:
             st['cancelled'] = np.zeros(0, CANCEL_OUT_DTYPE)
@@ -696,7 +865,7 @@ def _collective_fix(acq, data, ephs, t_gps, pos, f_offset, cfg, stats):
 
 
 def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, cancel=None, stats=None,
-                 collective=None, collective_cfg=None, **cfg):
+                 collective=None, collective_cfg=None, spoof=False, **cfg):
     """measure -> (doppler_fix when `pos` is None) -> coarse_time_fix.  `t_gps`: the GPS seconds
     of week of the first sample as far as known; `cancel`, `stats`: measure's.  -> (Fix,
     measurements, device ms).  The Fix's t_gps is that of its `sample`.
@@ -704,15 +873,38 @@ def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, ca
     satellites, collective_search (keywords: `collective_cfg`) supplies the a-priori and the
     measurements instead, and coarse_time_fix solves from them; 'always' -- it does so whatever
     measure yields.  Fix.path says which of the two made the fix.  None or False: nothing of this
-    runs."""
+    runs.
+    `spoof` (not together with `cancel` or `collective`): True -- measure(...,
+    spoof=True); without a doubled PRN everything goes on as with the option off.  With doubled
+    PRNs twin_fixes solves once per consistent assignment of their records to two sets; the first
+    return value is fix_a, the SpoofReport (doubled, alarm, fixes = (fix_a, fix_b), separation_m)
+    rides on stats['spoof'] and on the Fix's attribute `spoof`.  Which fix is authentic is not
+    claimed."""
     if collective not in (None, False, True, 'always'):
         raise ValueError(f"collective {collective!r}: None, False, True or 'always'")
     if collective and pos is None:
         raise ValueError('collective detection needs an a-priori position')
+    if spoof and collective:
+        raise ValueError('spoof and collective are not combined')
     stats = {} if stats is None else stats
-    meas = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats, cancel=cancel,
-                   **cfg)
+    report = None
+    if spoof:
+        meas, report = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats,
+                               cancel=cancel, spoof=True, **cfg)
+    else:
+        meas = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats, cancel=cancel,
+                       **cfg)
     ms = stats.get('device_ms', 0.0)
+    if report is not None and report.doubled:
+        if len(set(meas['prn'].tolist())) < MIN_SAT:
+            fix = Fix(reason=f"{len(set(meas['prn'].tolist()))} satellites measured, {MIN_SAT} needed")
+        else:
+            have_pos = pos is not None
+            if not have_pos:                         # (one record per PRN, the stronger: a Doppler is a Doppler)
+                pos, _ = doppler_fix(meas[twin_sets(meas)[0][0]], ephs, t_gps, f_offset=f_offset)
+            fix = twin_fixes(meas, ephs, t_gps, pos, report, acq.cfg.code_samples, have_pos)
+        fix.spoof = report
+        return fix, meas, ms
     if collective and (collective == 'always' or len(meas) < MIN_SAT):
         fix, meas, cms = _collective_fix(acq, data, ephs, t_gps, pos, f_offset, dict(collective_cfg or {}), stats)
         return fix, meas, ms + cms
@@ -724,4 +916,7 @@ def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, ca
     ref = int(np.argmax(cn0_weights(meas['cn0_dbhz'])))
     fix = coarse_time_fix(meas, ephs, float(t_gps) + int(meas['sample'][ref]) / fs, pos,
                           code_samples=acq.cfg.code_samples)
+    if report is not None:
+        report.fixes = (fix, None)
+        fix.spoof = report
     return fix, meas, ms

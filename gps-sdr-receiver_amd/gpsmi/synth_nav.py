@@ -112,6 +112,34 @@ def geometric_scene(truth, seconds, tow0=50001, lead_s=0.25, n_sats=8, amp=0.11,
                    'fit_err_samples': fit_err}
 
 
+def add_spoofer(scene, info, pos, clock_s=0.0, gain_db=3.0, prns=None):
+    """Appends to a geometric_scene one more Sat per PRN (of `prns`, default all): the signals a
+    receiver at ECEF `pos` would see, as a spoofer replays them -- the same ephemerides evaluated
+    at `pos`, every arrival `clock_s` later, the same nav bits, the amplitude scaled by `gain_db`.
+    The receiver itself stays where the scene has it.  -> the Sats added."""
+    cs = scene.code_samples
+    fs = 1000.0 * cs
+    pos = np.asarray(pos, dtype=np.float64)
+    added = []
+    for s in list(scene.sats):
+        if prns is not None and s.prn not in prns:
+            continue
+        _, k0, ks = s.pos_poly
+        seconds = 2.0 * k0 / fs
+        ms_nodes = np.arange(-1500, int(seconds * 1000) + 1501, 250)
+        k_nodes = np.array([arrival_sample(info['ephs'][s.prn], pos, info['tow0'], info['t0_gps'], int(m), fs)
+                            for m in ms_nodes]) + clock_s * fs
+        coefs = np.polyfit((k_nodes - k0) / ks, ms_nodes * float(cs), 5)
+        d1 = np.polyder(coefs)
+        dop0 = (np.polyval(d1, (0 - k0) / ks) / ks - 1.0) * F_L1
+        dop1 = (np.polyval(d1, (seconds * fs - k0) / ks) / ks - 1.0) * F_L1
+        added.append(synth.Sat(prn=s.prn, doppler=float(dop0), delay=0.0, amp=s.amp * 10.0 ** (gain_db / 20.0),
+                               phase0=s.phase0 + 1.0, doppler_rate=float((dop1 - dop0) / seconds),
+                               nav_bits=s.nav_bits, pos_poly=(coefs, k0, ks)))
+    scene.sats.extend(added)
+    return added
+
+
 HANDOFF_SECONDS = 14.0
 
 

@@ -66,7 +66,7 @@ const char* gpsmi_version(void);
 /* sizeof() of the ABI structs as compiled: 0 cfg, 1 peak, 2 trk_state, 3 trk_out,
  * 4 offsetof(trk_out, code_phase), 5 fe_cfg, 6 pb_cfg, 7 refine_hit, 8 refine_cfg, 9 refine_out,
  * 10 wtrk_cfg, 11 wtrk_state, 12 wtrk_bit, 13 cancel_sat, 14 cancel_cfg, 15 cancel_out, 17 collective_sat,
- * 18 collective_grid, 19 collective_cell, 21 nul_cfg, 23 tfx_cfg (16, 20 and 22 are not assigned); -1 otherwise.  Lets a binding verify its own struct declarations before the first real call.  */
+ * 18 collective_grid, 19 collective_cell, 21 nul_cfg, 23 tfx_cfg, 24 peaks_cfg, 25 peaks_pick (16, 20 and 22 are not assigned); -1 otherwise.  Lets a binding verify its own struct declarations before the first real call.  */
 int gpsmi_abi_sizeof(int which);
 /* Kernel-variant selection and tuning thresholds, visible through the ABI (round 4: they used to
  * be environment variables read inside gpsmi_*_create, invisible to a C caller; the variables
@@ -333,6 +333,55 @@ int gpsmi_acq_collective_dev(gpsmi_acq* h, const void* d_rows, int nsv_rows, int
 int gpsmi_acq_collective_plan(int code_samples, int nsv_rows, int nbins,
                               const gpsmi_collective_sat* sats, int nsat, const gpsmi_collective_grid* grid,
                               size_t* scratch_bytes, int* workgroups);
+/* Auxiliary peaks per satellite (numpy restatement: tests/peaks_ref.py): the k largest
+ * normalised peaks of every satellite's surfaces, more than a guard apart, so that a PRN that is in the
+ * air twice (a spoofer beside the signal it replaces) yields two candidates where every search keeps
+ * one.  d_rows: the rows of gpsmi_acq_search_deep_rows_dev, float32 [nsv_rows][nbins][code_samples],
+ * finite (not checked).
+ *
+ * Step a, per satellite p and bin b of [bin_lo, bin_hi], all float32, no fused operations:
+ *     mean[b], std[b]   exactly as step a of gpsmi_acq_collective forms them (the same operations and
+ *                       summation order: 256 strided shares in ascending order, then the adjacent-pair
+ *                       tree; the kernels share one device function)
+ *     z[b][l] = (S[p][b][l] - mean[b]) / std[b]          (a subtraction and an IEEE division)
+ * A bin whose std is not positive is skipped (no NaN enters a comparison).
+ *     zmax[l] = max of z[b][l] over the bins of the window that are not skipped
+ *     bin[l]  = the smallest such bin that attains it
+ * Ranking by z and not by the excess over the mean keeps the cross-correlation ghosts of a strong
+ * satellite out of the picks; which bin a peak belongs to is left to the caller, who gets the column
+ * down the bins (a strong peak inflates its own bin's std, so the bin of largest z can lie beside it).
+ * Step b, for pick i = 0 .. k - 1 of satellite p:
+ *     lag    = the first index of the maximum of zmax among the lags still free
+ *     pick   = {lag, bin[lag], zmax[lag], S[p][bin[lag]][lag]}
+ *     cols[p][i][0][b] = S[p][b][lag] for every bin b of the row
+ *     cols[p][i][1][b] = z[b][lag], or 0 for a skipped bin and for a bin outside the window
+ * and every lag at circular distance <= guard_lags from `lag` stops being free.  When no lag is free,
+ * or every bin of the window was skipped, the pick is {-1, -1, 0, 0} and its columns are zeros.
+ * A satellite's picks depend on its own rows alone; two calls give the same bytes; there are no
+ * atomics and no order that depends on scheduling.
+ * out_host / out_dev: gpsmi_peaks_pick [nsv_rows][k], at least one of them; cols_host / cols_dev:
+ * float32 [nsv_rows][k][2][nbins], optional.  Limits: code_samples 2048 and 16368 (anything else:
+ * GPSMI_E_UNSUPPORTED), nsv_rows 1..38, nbins 1..4096, k 1..8, guard_lags -1 or 0..code_samples / 2.
+ * Argument errors are GPSMI_E_ARG and need no GPU (gpsmi_acq_peaks_plan makes the same checks without
+ * a handle, and reports the scratch the call allocates besides its outputs and the workgroups of its
+ * statistics launch, one per satellite and bin of the window).  GPSMI_E_NOMEM leaves the handle
+ * usable.  The call returns when the work is done; gpsmi_acq_last_ms reports its three kernels.     */
+typedef struct gpsmi_peaks_cfg {   /* no implicit padding: 16 bytes */
+    int32_t k;                      /* picks per satellite, 1..8 */
+    int32_t guard_lags;             /* lags excluded either side of a pick, circular; -1: two chips
+                                     * (4 at 2048, 32 at 16368); 0..code_samples / 2 */
+    int32_t bin_lo, bin_hi;         /* inclusive bin window, 0 <= bin_lo <= bin_hi < nbins */
+} gpsmi_peaks_cfg;
+typedef struct gpsmi_peaks_pick {  /* 16 bytes */
+    int32_t lag, bin;               /* -1, -1: no pick */
+    float   z, s;                   /* z[bin][lag], S[bin][lag] */
+} gpsmi_peaks_pick;
+int gpsmi_acq_peaks_dev(gpsmi_acq* h, const void* d_rows, int nsv_rows, int nbins,
+                        const gpsmi_peaks_cfg* cfg,
+                        gpsmi_peaks_pick* out_host, void* out_dev,
+                        float* cols_host, void* cols_dev);
+int gpsmi_acq_peaks_plan(int code_samples, int nsv_rows, int nbins, const gpsmi_peaks_cfg* cfg,
+                         size_t* scratch_bytes, int* workgroups);
 /* Refinement of the hits of gpsmi_acq_search_nc / gpsmi_acq_search_deep: what a
  * high-sensitivity receiver runs between such a search and its loops.  Per hit (prn, delay = the
  * argmax the search returned, the code start at the start of iq; freq_hz = the bin) it integrates

@@ -7,7 +7,7 @@ gpseval) as one command on the GPU path.
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--sweep [L]] [--blank] [--json]
                              [--antenna FILE ... --null]
                              [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track [--weak-fix]]]]
-                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]]]
+                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]] [--spoof-check [K]]]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -72,6 +72,10 @@ output is as before.  --collective [RADIUS_KM] (with --snapshot and --near): whe
 are measured, position, coarse time and clock are searched collectively within RADIUS_KM (default 15 km)
 and 2 s of --near and --time, and the fix is solved from the satellites measured at that optimum
 (DESIGN.md 4.2k); the report gains 'path' and, where the search ran, a 'collective' entry.
+--spoof-check [K] (with --snapshot only): up to four peaks per PRN are refined, PRNs that are in the air twice
+are listed, from K of them on (default 2) the alarm is raised, and both sets of records are solved: the
+report gains a 'spoof' entry with the doubled PRNs, both fixes and their separation.  Which
+fix is authentic is not decided, and the exit status is 0 either way.
 
 There is no recording in this repository (data/test.bin is absent from the reference
 checkout, SURVEY F2, and too short for a fix even upstream): tests/test_run_file.py writes a
@@ -264,11 +268,12 @@ def parse_time(text, ephs):
 
 
 def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, frontend=None, excise=False,
-             blank=False, cancel=None, collective_km=None):
+             blank=False, cancel=None, collective_km=None, spoof_k=None):
     """--snapshot: gpsmi.snapshot.snapshot_fix on the first `seconds` behind `start_stream`, read
     and filtered block by block as run() feeds its receiver.  `cancel`: --cancel's C/N0 threshold
     (snapshot.measure's `cancel`); None leaves everything as it is without the flag.
-    `collective_km`: --collective's radius (snapshot_fix's collective=True within it); None: not asked for."""
+    `collective_km`: --collective's radius (snapshot_fix's collective=True within it); None: not asked for.
+    `spoof_k`: --spoof-check's doubled PRNs that raise the alarm (snapshot_fix's spoof=True); None: not asked for."""
     from gpsmi import ingest, position as P, snapshot as S
     from gpsmi.acquisition import Acquisition
     from gpsmi.conditioning import Conditioner
@@ -287,6 +292,7 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
             fix, meas, ms = S.snapshot_fix(acq, np.concatenate(blocks)[:need], ephemerides, t_gps,
                                            pos=None if near is None else np.array(P.geo_to_ecef(*near)),
                                            cancel=cancel, stats=stats,
+                                           **({} if spoof_k is None else {'spoof': True, 'min_doubled': spoof_k}),
                                            **({} if collective_km is None else
                                               {'collective': True, 'collective_cfg': {'radius_m': 1.0e3 * collective_km}}))
             wall = time.perf_counter() - t0
@@ -310,6 +316,23 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
                                  'lat_deg': round(float(geo[0]), 6), 'lon_deg': round(float(geo[1]), 6),
                                  't_gps': round(c['t_gps'], 4), 'z': [round(float(v), 2) for v in c['z']],
                                  'level_ms': [round(float(v), 3) for v in c['level_ms']]}
+    if spoof_k is not None:
+        rep = fix.spoof if fix.spoof is not None else stats.get('spoof')
+        sp = {'min_doubled': spoof_k, 'doubled': [] if rep is None else rep.doubled,
+              'alarm': bool(rep is not None and rep.alarm), 'crowded': bool(rep is not None and rep.crowded),
+              'separation_m': None if rep is None or rep.separation_m is None else round(rep.separation_m, 1),
+              'fixes': []}
+        for fx in (rep.fixes if rep is not None and rep.fixes else ()):
+            if fx is None or not fx.ok:
+                sp['fixes'].append(None if fx is None else {'ok': False, 'reason': fx.reason})
+                continue
+            geo = P.ecef_to_geo(fx.ecef)
+            sp['fixes'].append({'ok': True, 'lat_deg': None if geo is None else round(float(geo[0]), 6),
+                                'lon_deg': None if geo is None else round(float(geo[1]), 6),
+                                'height_m': None if geo is None else round(float(geo[2]), 1),
+                                'ecef_m': [round(float(v), 2) for v in fx.ecef], 'satellites': fx.prns,
+                                'dropped': fx.dropped, 'residual_rms_m': round(fx.rms_m, 2)})
+        out['spoof'] = sp
     if cancel is not None:
         out['cancelled'] = [{'prn': int(r['prn']), 'n_windows': int(r['n_windows']), 'n_skipped': int(r['n_skipped']),
                              'removed': round(float(r['energy_removed'] / r['energy_in']), 5) if r['energy_in'] > 0 else 0.0}
@@ -338,6 +361,19 @@ def print_snapshot(out):
         print(f"  collective search within {c['radius_km']} km over PRNs {c['prns']}: peak {c['margin']} robust sigma above "
               f"the map at {c['lat_deg']:.6f} N {c['lon_deg']:.6f} E, GPS time {c['t_gps']} s, clock lag {c['clock_lag']}; "
               f"per satellite {c['z']}; levels {c['level_ms']} ms")
+    sp = s.get('spoof')
+    if sp is not None:
+        print(f"  spoofing check: PRNs in the air twice {sp['doubled']}"
+              f"{' (more than two copies of one: the two strongest kept)' if sp['crowded'] else ''}; "
+              f"{'ALARM' if sp['alarm'] else 'no alarm'} (from {sp['min_doubled']} doubled PRNs on)")
+        for name, fx in zip(('fix a', 'fix b'), sp['fixes']):
+            if fx is not None and fx['ok']:
+                print(f"  {name}: {fx['lat_deg']} N {fx['lon_deg']} E {fx['height_m']} m, {len(fx['satellites'])} satellites, "
+                      f"residual rms {fx['residual_rms_m']} m")
+            elif fx is not None:
+                print(f"  {name}: no fix ({fx['reason']})")
+        if sp['separation_m'] is not None:
+            print(f"  the two fixes are {sp['separation_m']} m apart; which of them is authentic is not decided here")
     for m in s['measurements']:
         cn0 = 'n/a' if m['cn0_dbhz'] is None else f"{m['cn0_dbhz']:.1f}"
         print(f"  PRN {m['prn']:2d}  sample {m['sample']:8d}  code_phase {m['code_phase']:9.4f}  f_hz {m['f_hz']:+9.2f}  "
@@ -497,6 +533,9 @@ def main():
     ap.add_argument('--collective', type=float, nargs='?', const=15.0, default=None, metavar='RADIUS_KM',
                     help='with --snapshot and --near: when fewer than five satellites are measured, search position, '
                          'coarse time and clock collectively within RADIUS_KM (default 15) of --near (DESIGN.md 4.2k)')
+    ap.add_argument('--spoof-check', type=int, nargs='?', const=2, default=None, metavar='K',
+                    help='with --snapshot: look for PRNs that are in the air twice, raise the alarm from K of them on '
+                         '(default 2) and solve both sets (DESIGN.md 4.2n); the exit status stays 0 either way')
     ap.add_argument('--time', default=None,
                     help='with --snapshot: time of the first sample read, GPS seconds of week or a UTC timestamp, within 30 s')
     ap.add_argument('--near', default=None, metavar='LAT,LON[,H]',
@@ -533,8 +572,10 @@ def main():
             near = (near + [0.0])[:3]
         if a.collective is not None and (near is None or not 0.1 <= a.collective <= 100.0):
             ap.error('--collective [RADIUS_KM]: needs --near, 0.1 .. 100 km')
+        if a.spoof_check is not None and (a.spoof_check < 1 or a.cancel is not None or a.collective is not None):
+            ap.error('--spoof-check [K]: K from 1 on, without --cancel / --collective')
         out = snapshot(a.recording, a.snapshot, eph, parse_time(a.time, eph), near, a.start_stream, frontend,
-                       a.excise, a.blank, a.cancel, a.collective)
+                       a.excise, a.blank, a.cancel, a.collective, a.spoof_check)
         if a.json:
             print(json.dumps(out))
         else:
@@ -550,6 +591,8 @@ def main():
         ap.error('--cancel needs --snapshot SECONDS')
     if a.collective is not None:
         ap.error('--collective needs --snapshot SECONDS')
+    if a.spoof_check is not None:
+        ap.error('--spoof-check needs --snapshot SECONDS')
     out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise,
               frontend, a.blank, a.deep_acq, a.refine, a.track, a.weak_fix, a.save_ephemeris, a.antenna, a.null,
               a.sweep)
