@@ -4,7 +4,8 @@
 // Per block of n samples, alone: the A x A covariance of the antennas in float64 (the products of
 // float32 samples are exact there), R = C / n + delta I, R u = e0 by Cholesky, w = u / u[0], and the
 // output y = sum_a conj(w32[a]) x_a in float32; a block whose predicted gain is below min_gain_db (or
-// whose R has no Cholesky factor) passes antenna 0 through.
+// whose R has no Cholesky factor) passes antenna 0 through.  With cfg.taps = 3, 5 or 7 every antenna has a
+// filter of that many taps instead: the kernels of gpsmi_nul_stap.h, dispatched from nul_run below.
 //
 //   nul_cov_kernel<FMT, A>    one workgroup per (block, slice of 8192 samples): lane t takes the samples
 //                             2048 r + 8 t .. + 7, r = 0 .. 3, as b128 loads (two complex64 or
@@ -288,15 +289,20 @@ __global__ __launch_bounds__(kNulThreads) void nul_apply_kernel(const void* __re
 
 }  // namespace gpsmi
 
+#include "gpsmi_nul_stap.h"
+
 using namespace gpsmi;
 
 struct gpsmi_nul {
     gpsmi_nul_cfg cfg;
-    DevBuf<double> d_part;                                // [blocks][slices][A (A + 1)]
-    DevBuf<float2> d_w32;                                 // [blocks][8]
-    DevBuf<double> d_w64;                                 // [blocks][A][2]
+    DevBuf<double> d_part;                                // [blocks][slices][A (A + 1)] (taps: stap_values)
+    DevBuf<float2> d_w32;                                 // [blocks][8] (taps: [blocks][56])
+    DevBuf<double> d_w64;                                 // [blocks][A][2] (taps: [blocks][A][T][2])
     DevBuf<int32_t> d_flags; DevBuf<float> d_gain;        // [blocks]
     double load = 0.0, min_db = 0.0;                      // the cfg's, defaults filled in
+    int taps = 1;                                         // 1: one weight per antenna, else 3, 5 or 7
+    DevEvent ev_cov, ev_solve;                            // stamps behind the first and the second kernel
+    float kernel_ms[3] = {0.f, 0.f, 0.f};                 // covariance, solve, apply of the last finished call
     BlockStage blk;
     StageSync sync;                                       // last: see gpsmi_stage.h
 };
@@ -306,17 +312,20 @@ static int nul_build(gpsmi_nul* h) {
     h->blk.fan_in = h->cfg.antennas;
     h->load = (double)(h->cfg.load == 0.f ? 1e-6f : h->cfg.load);
     h->min_db = (double)(h->cfg.min_gain_db == 0.f ? 3.0f : h->cfg.min_gain_db);
-    return GPSMI_OK;
+    h->taps = h->cfg.taps <= 1 ? 1 : h->cfg.taps;
+    int rc = h->ev_cov.create<Ev::StageStamp, EventScope::DeviceOnly>();
+    if (!rc) rc = h->ev_solve.create<Ev::StageStamp, EventScope::DeviceOnly>();
+    return rc;
 }
 
 // The three passes over nb blocks of every antenna at d_iq (device, the handle's input format) into d_out.
 static int nul_run(gpsmi_nul* h, const void* d_iq, void* d_out, int nb) {
-    const int n = h->cfg.block_samples, A = h->cfg.antennas;
+    const int n = h->cfg.block_samples, A = h->cfg.antennas, T = h->taps;
     const int ns = (n + kNulSlice - 1) / kNulSlice;
     const size_t astride = (size_t)nb * n;
-    int rc = h->d_part.reserve((size_t)nb * ns * nul_values(A), "null steering slice sums");
-    if (!rc) rc = h->d_w32.reserve((size_t)nb * kNulMaxA, "null steering results");
-    if (!rc) rc = h->d_w64.reserve((size_t)nb * A * 2, "null steering results");
+    int rc = h->d_part.reserve((size_t)nb * ns * stap_values(A, T), "null steering slice sums");   // (T = 1: nul_values)
+    if (!rc) rc = h->d_w32.reserve((size_t)nb * (T == 1 ? kNulMaxA : kStapMaxK), "null steering results");
+    if (!rc) rc = h->d_w64.reserve((size_t)nb * A * T * 2, "null steering results");
     if (!rc) rc = h->d_flags.reserve(nb, "null steering results");
     if (!rc) rc = h->d_gain.reserve(nb, "null steering results");
     if (rc) return rc;
@@ -327,12 +336,28 @@ static int nul_run(gpsmi_nul* h, const void* d_iq, void* d_out, int nb) {
         constexpr int FMT = decltype(fmt)::value;
         constexpr int V = FMT == 0 ? kNulApplyC64 : kNulApplyU8;
         const int nc = (n + kNulThreads * V - 1) / (kNulThreads * V);
+        if (T > 1) {
+            with_value<3, 5, 7>(T, [&](auto nt) {
+                constexpr int NT = decltype(nt)::value;
+                hipLaunchKernelGGL((stap_cov_kernel<FMT, NT>), dim3((unsigned)(nb * ns)), dim3(kNulThreads), 0, st,
+                                   d_iq, n, ns, A, astride, h->d_part.p);
+                (void)hipEventRecord(h->ev_cov, st);
+                hipLaunchKernelGGL(stap_solve_kernel, dim3((unsigned)nb), dim3(64), 0, st, h->d_part.p, n, ns, A,
+                                   NT, h->load, h->min_db, h->d_w32.p, h->d_w64.p, h->d_flags.p, h->d_gain.p);
+                (void)hipEventRecord(h->ev_solve, st);
+                hipLaunchKernelGGL((stap_apply_kernel<FMT, NT>), dim3((unsigned)(nb * nc)), dim3(kNulThreads), 0,
+                                   st, d_iq, n, nc, A, astride, h->d_w32.p, h->d_flags.p, out);
+            });
+            return;
+        }
         with_value<2, 3, 4, 5, 6, 7, 8>(A, [&](auto na) {
             constexpr int NA = decltype(na)::value;
             hipLaunchKernelGGL((nul_cov_kernel<FMT, NA>), dim3((unsigned)(nb * ns)), dim3(kNulThreads), 0, st,
                                d_iq, n, ns, astride, h->d_part.p);
+            (void)hipEventRecord(h->ev_cov, st);
             hipLaunchKernelGGL(nul_solve_kernel<NA>, dim3((unsigned)nb), dim3(128), 0, st, h->d_part.p, n, ns,
                                h->load, h->min_db, h->d_w32.p, h->d_w64.p, h->d_flags.p, h->d_gain.p);
+            (void)hipEventRecord(h->ev_solve, st);
             hipLaunchKernelGGL((nul_apply_kernel<FMT, NA>), dim3((unsigned)(nb * nc)), dim3(kNulThreads), 0, st,
                                d_iq, n, nc, astride, h->d_w32.p, h->d_flags.p, out);
         });
@@ -347,9 +372,14 @@ static int nul_finish(gpsmi_nul* h, int nb, int32_t* flags, float* gain_db, doub
     if (gain_db)
         GPSMI_HIP(hipMemcpyAsync(gain_db, h->d_gain.p, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost, st));
     if (weights)
-        GPSMI_HIP(hipMemcpyAsync(weights, h->d_w64.p, (size_t)nb * h->cfg.antennas * 2 * sizeof(double),
+        GPSMI_HIP(hipMemcpyAsync(weights, h->d_w64.p, (size_t)nb * h->cfg.antennas * h->taps * 2 * sizeof(double),
                                  hipMemcpyDeviceToHost, st));
-    return h->sync.finish();
+    const int rc = h->sync.finish();
+    if (rc) return rc;
+    GPSMI_HIP(hipEventElapsedTime(&h->kernel_ms[0], h->sync.ev0, h->ev_cov));
+    GPSMI_HIP(hipEventElapsedTime(&h->kernel_ms[1], h->ev_cov, h->ev_solve));
+    GPSMI_HIP(hipEventElapsedTime(&h->kernel_ms[2], h->ev_solve, h->sync.ev1));
+    return GPSMI_OK;
 }
 
 extern "C" {
@@ -364,6 +394,8 @@ int gpsmi_nul_create(const gpsmi_nul_cfg* cfg, gpsmi_nul** out) {
     GPSMI_REQUIRE(cfg->load >= 0.f && std::isfinite(cfg->load), "load is negative, NaN or infinite");
     GPSMI_REQUIRE(cfg->min_gain_db >= 0.f && std::isfinite(cfg->min_gain_db),
                   "min_gain_db is negative, NaN or infinite");
+    GPSMI_REQUIRE(cfg->taps == 0 || cfg->taps == 1 || cfg->taps == 3 || cfg->taps == 5 || cfg->taps == 7,
+                  "taps is not 0, 1, 3, 5 or 7");
     return stage_create(cfg, out, nul_build);
 }
 
@@ -393,5 +425,11 @@ int gpsmi_nul_apply(gpsmi_nul* h, const void* iq, float* out, int nb, int32_t* f
 }
 
 int gpsmi_nul_last_ms(gpsmi_nul* h, float* ms) { return stage_last_ms(h, ms, __func__); }
+
+int gpsmi_nul_last_kernel_ms(gpsmi_nul* h, float* ms) {
+    GPSMI_REQUIRE(h && ms, "null argument");
+    for (int k = 0; k < 3; ++k) ms[k] = h->kernel_ms[k];
+    return GPSMI_OK;
+}
 
 }  // extern "C"

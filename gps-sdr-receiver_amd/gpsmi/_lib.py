@@ -41,7 +41,7 @@ class PbCfg(C.Structure):
 
 class NulCfg(C.Structure):
     _fields_ = [('block_samples', C.c_int32), ('antennas', C.c_int32), ('load', C.c_float),
-                ('min_gain_db', C.c_float), ('device', C.c_int32), ('reserved', C.c_int32)]
+                ('min_gain_db', C.c_float), ('device', C.c_int32), ('taps', C.c_int32)]
 
 
 class TfxCfg(C.Structure):
@@ -206,7 +206,7 @@ EXPORTS = [
     'gpsmi_pb_create', 'gpsmi_pb_destroy', 'gpsmi_pb_set_input_format', 'gpsmi_pb_reset',
     'gpsmi_pb_apply', 'gpsmi_pb_apply_dev', 'gpsmi_pb_last_ms',
     'gpsmi_nul_create', 'gpsmi_nul_destroy', 'gpsmi_nul_set_input_format',
-    'gpsmi_nul_apply', 'gpsmi_nul_apply_dev', 'gpsmi_nul_last_ms',
+    'gpsmi_nul_apply', 'gpsmi_nul_apply_dev', 'gpsmi_nul_last_ms', 'gpsmi_nul_last_kernel_ms',
     'gpsmi_tfx_create', 'gpsmi_tfx_destroy', 'gpsmi_tfx_set_input_format', 'gpsmi_tfx_reset',
     'gpsmi_tfx_apply', 'gpsmi_tfx_apply_dev', 'gpsmi_tfx_last_ms', 'gpsmi_tfx_last_power',
 ]
@@ -351,6 +351,7 @@ def load():
         'gpsmi_nul_apply': [vp, vp, vp, C.c_int, vp, vp, vp],
         'gpsmi_nul_apply_dev': [vp, vp, vp, C.c_int, vp, vp, vp],
         'gpsmi_nul_last_ms': [vp, P(f32)],
+        'gpsmi_nul_last_kernel_ms': [vp, P(f32)],
         'gpsmi_tfx_create': [P(TfxCfg), P(vp)],
         'gpsmi_tfx_destroy': [vp],
         'gpsmi_tfx_set_input_format': [vp, C.c_int],

@@ -9,6 +9,8 @@ nulls land on whatever is far above the noise, without calibration, antenna posi
 directions.  A block in which that would gain less than ``min_gain_db`` passes antenna 0 through bit
 for bit.  Opt-in: nothing else changes when it is not used (``pipeline.Receiver(null=...)``).
 """
+import ctypes as C
+
 import numpy as np
 
 from . import _lib
@@ -21,21 +23,30 @@ class NullSteer(BlockFilter):
     load: diagonal loading relative to the mean antenna power (0: 1e-6); min_gain_db: a block whose
     predicted gain (antenna 0's power over the output power) is below it passes through (0: 3 dB).
     raw_u8: the input is the recorder's uint16 (Q << 8 | I), decoded on the GPU; the output is
-    complex64 either way.  Input of a call: [antennas][nb * n], every antenna's blocks contiguous."""
+    complex64 either way.  Input of a call: [antennas][nb * n], every antenna's blocks contiguous.
+    taps: 0 or 1: one complex weight per antenna.  3, 5 or 7: space-time, a filter of that many taps
+    per antenna, y[i] = sum_a sum_t conj(w[a][t]) x_a[i + c - t] with c = (taps - 1) / 2 and the
+    centre tap of antenna 0 held at one.  It absorbs delay and filter mismatch between the channels
+    and nulls more than antennas - 1 narrowband interferers; the output stays aligned with antenna 0,
+    and its first and last c samples of a block are zero (a tap would reach outside the block)."""
     PREFIX = 'nul'
 
-    def __init__(self, cfg=None, antennas=4, load=0.0, min_gain_db=0.0, raw_u8=False):
+    def __init__(self, cfg=None, antennas=4, load=0.0, min_gain_db=0.0, raw_u8=False, taps=1):
         super().__init__(cfg, raw_u8)
         self.antennas = int(antennas)
-        self._create(_lib.NulCfg(self.n, self.antennas, float(load), float(min_gain_db), self.cfg.device, 0))
+        self.taps = int(taps)
+        self._create(_lib.NulCfg(self.n, self.antennas, float(load), float(min_gain_db), self.cfg.device,
+                                 self.taps))
         self.last_flags = None          # int32 [nb] of the last call: 1 nulled, 0 passed through
         self.last_gain_db = None        # float32 [nb]: the predicted gain
-        self.last_weights = None        # complex128 [nb, antennas]: w (e0 for a pass-through block)
+        self.last_weights = None        # complex128 [nb, antennas] (taps <= 1) or [nb, antennas, taps]: w
+        #                                 (the unit vector of antenna 0's centre tap for a pass-through block)
 
     def _results(self, nb):
         self.last_flags = np.zeros(nb, dtype=np.int32)
         self.last_gain_db = np.zeros(nb, dtype=np.float32)
-        self.last_weights = np.zeros((nb, self.antennas), dtype=np.complex128)
+        shape = (nb, self.antennas) if self.taps <= 1 else (nb, self.antennas, self.taps)
+        self.last_weights = np.zeros(shape, dtype=np.complex128)
         return self.last_flags, self.last_gain_db, self.last_weights
 
     def apply(self, blocks, out=None):
@@ -61,3 +72,9 @@ class NullSteer(BlockFilter):
 
     def reset(self):
         """Nothing to reset: every block is worked on alone."""
+
+    def last_kernel_ms(self):
+        """Device time of the last call's three kernels: (covariance, solve, apply) in ms."""
+        ms = (C.c_float * 3)()
+        self._call('last_kernel_ms', self.h, ms)
+        return tuple(float(v) for v in ms)

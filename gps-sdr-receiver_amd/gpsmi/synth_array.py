@@ -7,6 +7,12 @@ synth.py the generator is counter-based: noise and jammer waveforms are hashes o
 index, so any block of any antenna can be rendered on its own with the same bits.  Antenna 0 of a
 scene with unit steering and no jammer is the synth.Scene itself.
 
+Optionally every antenna has a channel response of its own (``channel``): a short complex FIR, or a
+fractional delay rendered as a windowed sinc -- cables and filters that are not matched, which one
+complex weight per antenna cannot undo (gpsmi.nulling, taps).  It acts on what arrives through the
+antenna, satellites and jammers, not on the receiver noise behind it.  The filter reads the same
+counter-based waveforms at the neighbouring sample indices, so a block still renders alone.
+
 Everything is scaled by one factor (``scale``) before the 8-bit rendering, chosen so that the total
 power per antenna leaves the quantiser clipping fewer than 1e-3 of the samples
 (``clip_fraction`` counts them).
@@ -19,6 +25,15 @@ import numpy as np
 from . import synth
 
 _MAX_POWER = 0.16       # per complex sample: sigma 0.283 per component, P(|N| > 1) = 4e-4
+SINC_HALF = 8           # a fractional delay is a Hamming-windowed sinc of 2 * SINC_HALF + 1 taps
+
+
+def delay_fir(delay, half=SINC_HALF):
+    """The centred FIR [2 half + 1] of a delay of `delay` samples (|delay| < 1): a Hamming-windowed
+    sinc, unit gain at zero frequency."""
+    m = np.arange(-half, half + 1, dtype=np.float64)
+    h = np.sinc(m - delay) * (0.54 + 0.46 * np.cos(np.pi * (m - delay) / (half + 1.0)))
+    return (h / h.sum()).astype(np.complex128)
 
 
 def _gauss(seed, stream, idx):
@@ -52,6 +67,9 @@ class ArrayScene:
     steering: object                 # complex [antennas][satellites]
     jammers: List[Jammer] = field(default_factory=list)
     scale: float = None              # None: as large as the clipping limit allows, at most 1
+    channel: object = None           # None, or per antenna: None (none), a delay in samples (float) or
+    #                                  the taps of a centred complex FIR (odd length):
+    #                                  out[k] = sum_m h[m] in[k + (len(h) - 1) / 2 - m]
 
     def __post_init__(self):
         self.steering = np.asarray(self.steering, dtype=np.complex128)
@@ -62,6 +80,19 @@ class ArrayScene:
                 raise ValueError('a jammer needs one steering factor per antenna')
         self._sats = [replace(self.scene, sats=[s], noise_sigma=0.0, _rep=self.scene._rep)
                       for s in self.scene.sats]
+        self._fir = None
+        if self.channel is not None:
+            if len(self.channel) != self.antennas:
+                raise ValueError('channel needs one entry per antenna')
+            firs = [np.ones(1, dtype=np.complex128) if c is None else
+                    delay_fir(float(c)) if np.ndim(c) == 0 else np.asarray(c, dtype=np.complex128)
+                    for c in self.channel]
+            if any(h.ndim != 1 or len(h) % 2 == 0 for h in firs):
+                raise ValueError('a channel FIR needs an odd number of taps (it is centred)')
+            half = max(len(h) for h in firs) // 2
+            self._fir = np.zeros((self.antennas, 2 * half + 1), dtype=np.complex128)
+            for a, h in enumerate(firs):
+                self._fir[a, half - len(h) // 2:half + len(h) // 2 + 1] = h
         if self.scale is None:
             self.scale = min(1.0, float(np.sqrt(_MAX_POWER / self.power())))
 
@@ -101,7 +132,9 @@ class ArrayScene:
 
     def jammer_parts(self, block_no, n=None):
         """complex128 [jammers][n]: every jammer's waveform at unit steering."""
-        k = self._index(block_no, n)
+        return self._jammers_at(self._index(block_no, n))
+
+    def _jammers_at(self, k):
         out = []
         for j in self.jammers:
             amp = np.sqrt(self.jammer_power(j))
@@ -123,9 +156,40 @@ class ArrayScene:
         complex128 [antennas][n] each; their sum is block_float."""
         js = np.array([np.atleast_1d(j.steering) for j in self.jammers],
                       dtype=np.complex128).reshape(len(self.jammers), self.antennas)
-        sat = self.steering @ self.sat_parts(block_no, n)
-        jam = js.T @ self.jammer_parts(block_no, n)
+        if self._fir is None:
+            sat = self.steering @ self.sat_parts(block_no, n)
+            jam = js.T @ self.jammer_parts(block_no, n)
+        else:
+            sat = self._through(self.steering @ self._sats_around(block_no, n))
+            k = self._index(block_no, n)
+            half = self._fir.shape[1] // 2
+            jam = self._through(js.T @ self._jammers_at(np.arange(k[0] - half, k[-1] + half + 1, dtype=np.int64)))
         return self.scale * sat, self.scale * self.noise_parts(block_no, n), self.scale * jam
+
+    def sat_components(self, block_no, n=None):
+        """complex128 [satellites][antennas][n]: every satellite alone as every antenna receives it,
+        scaled; their sum over the satellites is parts()[0]."""
+        if self._fir is None:
+            sp = self.sat_parts(block_no, n)
+            return self.scale * self.steering.T[:, :, None] * sp[:, None, :]
+        sp = self._sats_around(block_no, n)
+        return self.scale * np.stack([self._through(self.steering[:, s][:, None] * sp[s][None, :])
+                                      for s in range(len(self._sats))])
+
+    def _sats_around(self, block_no, n):
+        """sat_parts of the block's samples and of the channel filters' reach either side of them
+        (the tail of the block before, the head of the one after)."""
+        n = self.ngps if n is None else n
+        half = self._fir.shape[1] // 2
+        here = min(n + half, self.ngps)
+        parts = [self.sat_parts(block_no - 1)[:, self.ngps - half:], self.sat_parts(block_no, here)]
+        if n + half > here:
+            parts.append(self.sat_parts(block_no + 1, n + half - here))
+        return np.concatenate(parts, axis=1)
+
+    def _through(self, x):
+        """[antennas][n + 2 half] -> [antennas][n]: every antenna's row through its channel FIR."""
+        return np.stack([np.convolve(x[a], self._fir[a], mode='valid') for a in range(self.antennas)])
 
     def block_float(self, block_no, n=None):
         """complex128 [antennas][n] before quantisation."""

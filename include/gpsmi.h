@@ -1041,6 +1041,43 @@ int gpsmi_pb_last_ms(gpsmi_pb* h, float* ms);
  * null cfg or handle, a bad n, antennas outside 2..8, a NaN or negative load or min_gain_db,
  * nb <= 0) are GPSMI_E_ARG and need no GPU; a failed allocation is GPSMI_E_NOMEM and leaves the
  * handle usable.
+ *
+ * Space-time taps (cfg.taps = T in {3, 5, 7}; restatement: tests/stap_ref.py).  taps 0
+ * or 1 is everything above, byte for byte; any other value is GPSMI_E_ARG and needs no GPU.  Every A in
+ * 2..8 goes with every T: K = A T <= 56 weights per block, w[a][t] at k(a, t) = a T + t, c = (T - 1) / 2.
+ * A filter of T taps per antenna compensates what one complex weight cannot: delay and filter mismatch
+ * between the channels, and more than A - 1 narrowband interferers.  Each block is worked on alone:
+ *   lag sums   r_ab(l) = sum_{i=l}^{n-1} x_a[i] conj(x_b[i - l]) for l = 0 .. T - 1 and all (a, b); at
+ *              l = 0 only a >= b is kept.  The block is zero outside 0 .. n - 1, no sample of a
+ *              neighbouring block is read.  Accumulators are float64 (every product of two float32
+ *              samples is exact there).  The four real sums of a pair, RR = sum Re Re, II, IR =
+ *              sum Im x_a Re x_b and RI, are accumulated apart and combined after the last sample:
+ *              re = RR + II, im = IR - RI; the imaginary part of r_aa(0) is exactly 0.  The order of
+ *              each sum is fixed by n alone -- it does not depend on the grid, on nb or on how the
+ *              input is cut into calls -- and is not otherwise specified (the kernel forms the sums
+ *              on the float64 matrix pipe, four samples per instruction, per wave and slice of 8192
+ *              samples; waves and slices are added in ascending order);
+ *   matrix     R[k(a,t)][k(b,s)] = r_ab(s - t) / n for s >= t and conj(r_ba(t - s)) / n for s < t: the
+ *              Gram matrix of the zero-extended, shifted rows Z[k(a,t)][i] = x_a[i - t],
+ *              i = 0 .. n + T - 2, over n: Hermitian, block-Toeplitz, positive semidefinite;
+ *   loading    delta = load * (sum_a r_aa(0) / n) / A on the diagonal, load as above;
+ *   weights    R = L L^H by Cholesky without pivoting in float64, column by column as above (K for
+ *              A); L y = e_{k(0,c)} forward, every row subtracting its terms in ascending column
+ *              order from its right-hand side, and L^H u = y backward as above; w = u / Re u_{k(0,c)}
+ *              with w[0][c] exactly 1; predicted gain g = (r_00(0) / n) * Re u_{k(0,c)},
+ *              gain_db = (float)(10 log10 g).  Nothing is fused;
+ *   decision   as above: a pivot that is not positive and finite, or 10 log10 g < min_gain_db: the
+ *              output is antenna 0's whole block bit for bit (decoded for u8), flag 0, weights
+ *              e_{k(0,c)};
+ *   apply      w32 = complex64(w).  For c <= i < n - c:
+ *                  y[i] = sum_a sum_t conj(w32[a][t]) x_a[i + c - t]
+ *              in float32, ascending a, ascending t within a, starting from (0, 0)'s term; each term
+ *              (wr xr + wi xi) + j (wr xi - wi xr) and one add per component into y as above.  For
+ *              i < c and i >= n - c the output is +0.0 + 0.0j: a tap there would reach outside the
+ *              block and the cancellation would be incomplete.  The output is aligned with antenna 0:
+ *              code phases do not move.
+ * weights is float64 [nb][A][T][2] ([nb][A][2] for taps <= 1).  Formats, alignment, the overlap
+ * refusal, last_ms and GPSMI_E_NOMEM are as above.
  * ======================================================================== */
 typedef struct gpsmi_nul gpsmi_nul;
 typedef struct gpsmi_nul_cfg {
@@ -1049,7 +1086,7 @@ typedef struct gpsmi_nul_cfg {
     float   load;               /* diagonal loading; 0 means 1e-6; not NaN, not negative */
     float   min_gain_db;        /* 0 means 3.0; not NaN, not negative                    */
     int32_t device;
-    int32_t reserved;           /* 0 */
+    int32_t taps;               /* 0 or 1: one weight per antenna; 3, 5 or 7: space-time */
 } gpsmi_nul_cfg;
 int gpsmi_nul_create(const gpsmi_nul_cfg* cfg, gpsmi_nul** out);
 int gpsmi_nul_destroy(gpsmi_nul* h);
@@ -1062,6 +1099,8 @@ int gpsmi_nul_apply(gpsmi_nul* h, const void* iq, float* out, int nb, int32_t* f
 int gpsmi_nul_apply_dev(gpsmi_nul* h, const void* d_iq, void* d_out, int nb, int32_t* flags,
                         float* gain_db, double* weights);
 int gpsmi_nul_last_ms(gpsmi_nul* h, float* ms);
+/* device time of the three kernels of the last finished call: ms[0] covariance, ms[1] solve, ms[2] apply */
+int gpsmi_nul_last_kernel_ms(gpsmi_nul* h, float* ms);
 
 /* ========================================================================
  * Time-frequency (sweep) excision: an opt-in input stage against swept and chirp interference, for

@@ -5,7 +5,7 @@ gpseval) as one command on the GPU path.
 
     python tools/run_file.py <recording.bin> [--seconds S] [--start-stream K] [--save-pickle P]
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--sweep [L]] [--blank] [--json]
-                             [--antenna FILE ... --null]
+                             [--antenna FILE ... --null [--null-taps T]]
                              [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track [--weak-fix]]]]
                              [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]] [--spoof-check [K]]]
 
@@ -34,7 +34,8 @@ of the further channels of a coherent multi-antenna recorder, sample-aligned wit
 (antenna 0, the reference element), and --null combines them by null steering on the GPU ahead of
 everything else (pipeline.Receiver(antennas=A, null=True)): a defence against
 jammers that are wide in frequency and continuous in time; the flag (1 nulled, 0 antenna 0 passed
-through) and the predicted gain of every block are printed, with --json under 'null'.  --format (c64, u8iq, sc8, sc16, r8), --fs (the
+through) and the predicted gain of every block are printed, with --json under 'null'; --null-taps T
+(3, 5 or 7) gives every antenna T space-time taps instead of one weight.  --format (c64, u8iq, sc8, sc16, r8), --fs (the
 input rate in Hz), --if (the IF of real input or the tuner offset of complex input, Hz) and
 --conjugate read a recording of another front end: frontend.FrontEnd decodes, mixes, filters and
 resamples it on the GPU to complex64 blocks at 2.048 Msps, which Receiver(raw_u8=False) takes
@@ -393,7 +394,7 @@ def print_snapshot(out):
 
 def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, cpu_acq=False, report_lag=16,
         excise=False, frontend=None, blank=False, deep_acq=None, refine=False, track=False, weak_fix=False,
-        save_ephemeris=None, antennas=(), null=False, sweep=None):
+        save_ephemeris=None, antennas=(), null=False, sweep=None, null_taps=1):
     """frontend: None (the recorder's u8 format at 2.048 Msps) or a dict of frontend.FrontEnd's
     keyword arguments (fs_in, fmt, if_hz, conjugate).  deep_acq: None, or the seconds of the
     recording's start that deep_acquisition searches for the PRNs the sweep did not acquire; refine:
@@ -405,7 +406,8 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
     antennas: the files of the further channels of a coherent multi-antenna recorder, read in step
     with `path` (antenna 0, the reference element); null: null steering combines them ahead of
     everything else (pipeline.Receiver(antennas=A, null=True)) and the report gains
-    'null': the flag (1 nulled, 0 passed through) and the predicted gain in dB of every block.
+    'null': the flag (1 nulled, 0 passed through) and the predicted gain in dB of every block;
+    null_taps: 1, or 3 / 5 / 7 space-time taps per antenna (nulling.NullSteer(taps=...)).
     sweep: None, True or a frame length: time-frequency excision (pipeline.Receiver(sweep=...),
     DESIGN.md 4.2m); the report gains 'sweep'."""
     from gpsmi import ingest, position as P
@@ -416,6 +418,11 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
     # reader then runs ahead of the GPU instead of stalling it once a second -- pipeline.Receiver)
     with ingest.open_blocks(path, cfg, start_stream, frontend, antennas) as (source, raw_u8):
         array = dict(antennas=1 + len(antennas), null=True) if null else {}
+        steer = None
+        if null and null_taps > 1:                      # (a stage of the caller's: used by the chain, closed here)
+            from gpsmi.nulling import NullSteer
+            steer = NullSteer(cfg, antennas=1 + len(antennas), raw_u8=raw_u8, taps=null_taps)
+            array['null'] = steer
         rx = Receiver(cfg, raw_u8=raw_u8, report_lag=report_lag, excise=excise, blank=blank, sweep=sweep, **array)
         null_flags, null_gain, sweep_counts = [], [], []
         if weak_fix:
@@ -460,6 +467,8 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
                          'mean_share': round(float(np.mean(done)) / cells, 4) if done else 0.0}
         weak = weak_fix_report(top, solver, fixes, cfg) if weak_fix else None
         rx.close()
+        if steer is not None:
+            steer.close()
     out = {'file': os.path.basename(path), 'blocks': n_blocks, 'signal_s': round(n_blocks * cfg.n_cyc / 1000.0, 3),
            'wall_s': round(wall, 3), 'x_realtime': round(n_blocks * cfg.n_cyc / 1000.0 / wall, 1) if wall else None,
            'acquired': [(int(s), float(f), int(d)) for _, s, f, d in (found or [])],
@@ -475,7 +484,8 @@ def run(path, seconds=None, start_stream=0, save_pickle=None, ephemerides=None, 
                            'from': f'mean of the last {len(late)} fixes',
                            'sd_of_mean_m': round(float(np.linalg.norm(late.std(axis=0)) / np.sqrt(len(late))), 2)}
     if null:
-        out['null'] = {'antennas': 1 + len(antennas), 'flags': null_flags, 'gain_db': null_gain,
+        out['null'] = {'antennas': 1 + len(antennas), 'taps': max(1, null_taps), 'flags': null_flags,
+                       'gain_db': null_gain,
                        'blocks_nulled': int(sum(null_flags))}
     if sweep:
         out['sweep'] = sweep_out
@@ -546,6 +556,9 @@ def main():
     ap.add_argument('--null', action='store_true',
                     help='null steering over the antennas against wideband jamming, ahead of everything '
                          'else (DESIGN.md 4.2l)')
+    ap.add_argument('--null-taps', type=int, default=1, choices=(1, 3, 5, 7), metavar='T',
+                    help='with --null: T = 3, 5 or 7 space-time taps per antenna instead of one weight, against '
+                         'delay and filter mismatch between the channels and dense tone fields')
     ap.add_argument('--json', action='store_true', help='one JSON line instead of text')
     a = ap.parse_args()
     if a.refine and not a.deep_acq:
@@ -585,6 +598,8 @@ def main():
         ap.error('--time / --near need --snapshot SECONDS')
     if bool(a.antenna) != a.null:
         ap.error('--antenna FILE (the further channels) and --null go together')
+    if a.null_taps != 1 and not a.null:
+        ap.error('--null-taps needs --null')
     if a.antenna and (frontend is not None or a.deep_acq or a.cpu_acq):
         ap.error('--antenna: the recorder\'s own format, without --deep-acq / --cpu-acq')
     if a.cancel is not None:
@@ -595,7 +610,7 @@ def main():
         ap.error('--spoof-check needs --snapshot SECONDS')
     out = run(a.recording, a.seconds, a.start_stream, a.save_pickle, eph, a.cpu_acq, a.report_lag, a.excise,
               frontend, a.blank, a.deep_acq, a.refine, a.track, a.weak_fix, a.save_ephemeris, a.antenna, a.null,
-              a.sweep)
+              a.sweep, a.null_taps)
     if a.json:
         print(json.dumps(out))
         return
