@@ -15,6 +15,8 @@
 //                         (gpsmi_acq_collective)
 //   gpsmi_peaks.h         the k largest peaks of every satellite over those surfaces, for the
 //                         spoofing check (gpsmi_acq_peaks)
+//   gpsmi_sig.h           spatial signatures of refined records over several antennas
+//                         (gpsmi_acq_signature): prompts per antenna, their covariance
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -31,6 +33,7 @@
 #include "gpsmi_cancel.h"
 #include "gpsmi_collective.h"
 #include "gpsmi_peaks.h"
+#include "gpsmi_sig.h"
 #include "gpsmi_acq_search.h"
 
 using namespace gpsmi;
@@ -94,6 +97,11 @@ struct gpsmi_acq {
     DevBuf<int> d_pb;
     DevBuf<gpsmi_peaks_pick> d_pk;
     DevBuf<float> d_pcol;
+    // signatures (gpsmi_acq_signature): the prompts [nsat][A][max_windows], the records and the window
+    // starts of a call in one block, the covariances [nsat][A][A][2]
+    DevBuf<float2> d_sp;
+    DevBuf<char> d_st;
+    DevBuf<double> d_sc;
     int iq_fmt = GPSMI_IQ_C64;              // what the iq pointers of the search calls point to
     // bytes of `n` samples in the handle's input format
     size_t iq_bytes(size_t n) const { return n * (iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)); }
@@ -776,6 +784,68 @@ int gpsmi_acq_cancel_plan(int code_samples, size_t n, const gpsmi_cancel_sat* sa
     const int rc = cancel_plan(code_samples, n, sats, nsat, cfg, &pl);
     if (rc == GPSMI_OK && max_windows) *max_windows = pl.max_windows;
     return rc;
+}
+
+// ---- spatial signatures over several antennas (kernels and plan: gpsmi_sig.h) -----------------
+static int acq_signature_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n, const gpsmi_sig_sat* sats,
+                              int nsat, const gpsmi_sig_cfg* cfg, double* cov, int32_t* n_win, float* prompts) {
+    GPSMI_REQUIRE(h && iq && sats && cov && n_win, "null argument");
+    SigPlan pl;
+    int rc = sig_plan(h->cfg.code_samples, n, sats, nsat, cfg, &pl);
+    if (rc) return rc;
+    const void* d_iq;
+    if ((rc = acq_need_time(h, "gpsmi_acq_signature", nsat, [&](int i) { return sats[i].prn; })) ||
+        (rc = acq_enter(h)) || (rc = acq_input(h, iq, on_host, (size_t)pl.A * n, &d_iq)))
+        return rc;
+    const int cs = pl.cs, A = pl.A, mw = pl.max_windows;
+    // the tables of the call, 8-byte items first
+    const size_t b_start = pl.start.size() * sizeof(long long), b_rec = (size_t)nsat * sizeof(SigRec);
+    const size_t np = (size_t)nsat * A * mw, nc = (size_t)nsat * A * A * 2;
+    if ((rc = h->d_st.reserve(b_start + b_rec, "gpsmi_acq_signature tables")) ||
+        (rc = h->d_sp.reserve(np, "gpsmi_acq_signature prompts")) ||
+        (rc = h->d_sc.reserve(nc, "gpsmi_acq_signature covariances")))
+        return rc;
+    long long* d_start = reinterpret_cast<long long*>(h->d_st.p);
+    SigRec* d_rec = reinterpret_cast<SigRec*>(h->d_st.p + b_start);
+    const size_t lds = sig_lds_bytes(cs);
+    GPSMI_HIP(hipMemsetAsync(h->d_sp.p, 0, np * sizeof(float2), h->stream));
+    if ((rc = acq_tables(h, {{d_start, pl.start.data(), b_start}, {d_rec, pl.recs.data(), b_rec}})) ||
+        (rc = acq_lds_optin(h, sig_prompt_kernel<1>, sig_prompt_kernel<0>, lds)) || (rc = acq_begin(h)))
+        return rc;
+    const dim3 gp((mw + kSigWinPerWg - 1) / kSigWinPerWg, nsat);
+    with_fmt(h->iq_fmt, [&](auto fmt) {
+        hipLaunchKernelGGL(sig_prompt_kernel<decltype(fmt)::value>, gp, dim3(256), lds, h->stream, d_iq, n, A,
+                           h->d_rep_time.p, d_rec, d_start, cs, mw, h->d_sp.p);
+    });
+    hipLaunchKernelGGL(sig_cov_kernel, dim3(nsat), dim3(256), 0, h->stream, h->d_sp.p, d_rec, A, mw, h->d_sc.p);
+    if ((rc = acq_end(h))) return rc;
+    GPSMI_HIP(hipMemcpyAsync(cov, h->d_sc.p, nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (prompts)
+        GPSMI_HIP(hipMemcpyAsync(prompts, h->d_sp.p, np * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = gpsmi_acq_wait(h))) return rc;
+    for (int s = 0; s < nsat; ++s) n_win[s] = pl.recs[s].n_win;
+    return GPSMI_OK;
+}
+
+int gpsmi_acq_signature(gpsmi_acq* h, const void* iq, size_t n, const gpsmi_sig_sat* sats, int nsat,
+                        const gpsmi_sig_cfg* cfg, double* cov, int32_t* n_win, float* prompts) {
+    return acq_signature_impl(h, iq, true, n, sats, nsat, cfg, cov, n_win, prompts);
+}
+
+int gpsmi_acq_signature_dev(gpsmi_acq* h, const void* d_iq, size_t n, const gpsmi_sig_sat* sats, int nsat,
+                            const gpsmi_sig_cfg* cfg, double* cov, int32_t* n_win, float* prompts) {
+    return acq_signature_impl(h, d_iq, false, n, sats, nsat, cfg, cov, n_win, prompts);
+}
+
+int gpsmi_acq_signature_plan(int code_samples, size_t n, const gpsmi_sig_sat* sats, int nsat,
+                             const gpsmi_sig_cfg* cfg, int32_t* n_win, int* max_windows) {
+    SigPlan pl;
+    const int rc = sig_plan(code_samples, n, sats, nsat, cfg, &pl);
+    if (rc != GPSMI_OK) return rc;
+    if (n_win)
+        for (int s = 0; s < nsat; ++s) n_win[s] = pl.recs[s].n_win;
+    if (max_windows) *max_windows = pl.max_windows;
+    return GPSMI_OK;
 }
 
 // ---- collective detection (kernels and plan: gpsmi_collective.h) ------------------------------

@@ -151,6 +151,8 @@ int gpsmi_abi_sizeof(int which) {
         case 23: return (int)sizeof(gpsmi_tfx_cfg);   // (20 and 22 stay unused: tests hold them to -1)
         case 24: return (int)sizeof(gpsmi_peaks_cfg);
         case 25: return (int)sizeof(gpsmi_peaks_pick);
+        case 27: return (int)sizeof(gpsmi_sig_sat);   // (26 stays unused as well)
+        case 28: return (int)sizeof(gpsmi_sig_cfg);
         default: return -1;
     }
 }

@@ -91,6 +91,11 @@ class PeaksCfg(C.Structure):
     _fields_ = [('k', C.c_int32), ('guard_lags', C.c_int32), ('bin_lo', C.c_int32), ('bin_hi', C.c_int32)]
 
 
+class SigCfg(C.Structure):
+    _fields_ = [('antennas', C.c_int32), ('n_ms', C.c_int32), ('carrier_hz', C.c_double),
+                ('f_offset_hz', C.c_double)]
+
+
 class Cfg(C.Structure):
     _fields_ = [('code_samples', C.c_int32), ('n_cyc', C.c_int32),
                 ('corr_avg', C.c_int32), ('sweep_corr_avg', C.c_int32),
@@ -116,6 +121,8 @@ CANCEL_SAT_DTYPE = np.dtype([('prn', np.int32), ('reserved', np.int32), ('f_hz',
 CANCEL_OUT_DTYPE = np.dtype([('prn', np.int32), ('n_windows', np.int32), ('n_skipped', np.int32),
                              ('reserved', np.int32), ('energy_in', np.float64),
                              ('energy_removed', np.float64)])
+
+SIG_SAT_DTYPE = np.dtype([('prn', np.int32), ('reserved', np.int32), ('f_hz', np.float64), ('tau', np.float64)])
 
 COLLECTIVE_SAT_DTYPE = np.dtype([('row', np.int32), ('bin_lo', np.int32), ('bin_hi', np.int32),
                                  ('reserved', np.int32), ('lag0', np.float64), ('g_e', np.float64),
@@ -184,6 +191,7 @@ EXPORTS = [
     'gpsmi_acq_refine', 'gpsmi_acq_refine_dev', 'gpsmi_acq_refine_plan',
     'gpsmi_acq_track', 'gpsmi_acq_track_dev', 'gpsmi_acq_track_plan', 'gpsmi_wtrk_open',
     'gpsmi_acq_cancel', 'gpsmi_acq_cancel_dev', 'gpsmi_acq_cancel_plan',
+    'gpsmi_acq_signature', 'gpsmi_acq_signature_dev', 'gpsmi_acq_signature_plan',
     'gpsmi_acq_last_ms',
     'gpsmi_trk_create', 'gpsmi_trk_destroy', 'gpsmi_trk_set_replica',
     'gpsmi_trk_open', 'gpsmi_trk_close', 'gpsmi_trk_get_state',
@@ -280,6 +288,9 @@ def load():
         'gpsmi_acq_cancel': [vp, vp, sz, vp, C.c_int, P(CancelCfg), vp, vp, vp],
         'gpsmi_acq_cancel_dev': [vp, vp, sz, vp, C.c_int, P(CancelCfg), vp, vp, vp],
         'gpsmi_acq_cancel_plan': [C.c_int, sz, vp, C.c_int, P(CancelCfg), P(C.c_int)],
+        'gpsmi_acq_signature': [vp, vp, sz, vp, C.c_int, P(SigCfg), vp, vp, vp],
+        'gpsmi_acq_signature_dev': [vp, vp, sz, vp, C.c_int, P(SigCfg), vp, vp, vp],
+        'gpsmi_acq_signature_plan': [C.c_int, sz, vp, C.c_int, P(SigCfg), vp, P(C.c_int)],
         'gpsmi_acq_last_ms': [vp, P(f32)],
         'gpsmi_trk_create': [P(Cfg), C.c_int, P(vp)],
         'gpsmi_trk_destroy': [vp],
@@ -372,7 +383,8 @@ def load():
            (10, C.sizeof(WtrkCfg)), (11, WTRK_STATE_DTYPE.itemsize), (12, WTRK_BIT_DTYPE.itemsize),
            (13, CANCEL_SAT_DTYPE.itemsize), (14, C.sizeof(CancelCfg)), (15, CANCEL_OUT_DTYPE.itemsize),
            (17, COLLECTIVE_SAT_DTYPE.itemsize), (18, C.sizeof(CollectiveGrid)), (19, COLLECTIVE_CELL_DTYPE.itemsize),
-           (21, C.sizeof(NulCfg)), (23, C.sizeof(TfxCfg)), (24, C.sizeof(PeaksCfg)), (25, PEAKS_PICK_DTYPE.itemsize)]
+           (21, C.sizeof(NulCfg)), (23, C.sizeof(TfxCfg)), (24, C.sizeof(PeaksCfg)), (25, PEAKS_PICK_DTYPE.itemsize),
+           (27, SIG_SAT_DTYPE.itemsize), (28, C.sizeof(SigCfg))]
     want = [size for _, size in abi]
     got = [lib.gpsmi_abi_sizeof(i) for i, _ in abi]
     if want != got:

@@ -167,6 +167,15 @@ class Acquisition:
         sats = [(int(rec['prn'][i]), float(rec['f_hz'][i]), float(tau[i])) for i in order]
         return self.engine.cancel(data, sats, out=out, f_offset=f_offset)
 
+    def signatureHits(self, data, rec, antennas, f_offset=0.0, **cfg):
+        """The spatial signatures of the records `rec` over `antennas` coherent channels
+        (AcqEngine.signatures): records of refineHits (code_phase is the code start
+        at the first sample) or snapshot.MEAS_DTYPE records (a code start lies at sample +
+        code_phase), in the order given; a PRN may appear more than once.  `data`: [antennas][n] on
+        the host or a (device pointer, n) pair with the rows n samples apart.
+        Returns (cov complex128 [R][A][A], n_win)."""
+        return self.engine.signatures(data, signature_sats(rec), antennas, f_offset=f_offset, **cfg)[:2]
+
     def deepRows(self, data, prns, freqs, n_coh=4, n_seg=250, f_offset=0.0):
         """The deep surface kept whole (AcqEngine.search_deep with rows): the
         table of sweepDeepSats' search and a DeviceBuffer of float32 [len(prns)][len(freqs)]
@@ -185,6 +194,15 @@ class Acquisition:
     def search_table(self, data, prns, freqs, n_avg):
         """The whole surface, no pruning (BASELINE configs 2 and 4)."""
         return self.engine.search(data, prns, freqs, n_avg)
+
+
+def signature_sats(rec):
+    """(prn, f_hz, tau) of records of refineHits or snapshot.MEAS_DTYPE, tau = sample + code_phase
+    as in cancelHits, in the order given.  Host only."""
+    rec = np.atleast_1d(np.asarray(rec))
+    start = rec['sample'].astype(np.float64) if 'sample' in rec.dtype.names else 0.0
+    tau = start + rec['code_phase'].astype(np.float64)
+    return [(int(rec['prn'][i]), float(rec['f_hz'][i]), float(tau[i])) for i in range(len(rec))]
 
 
 def hit_at(rec, sample, cfg, carrier_hz=L1_HZ):

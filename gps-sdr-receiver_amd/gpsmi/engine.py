@@ -182,6 +182,26 @@ def peaks_plan(code_samples, nsv_rows, nbins, k=4, guard_lags=-1, bins=None):
     return scratch.value, wgs.value
 
 
+def _sig_args(sats, antennas, n_ms, f_offset, carrier_hz):
+    """The records and the options of a signature call (gpsmi_sig_sat [R], gpsmi_sig_cfg)."""
+    s_a = np.zeros(len(sats), dtype=_lib.SIG_SAT_DTYPE)
+    for i, (prn, f_hz, tau) in enumerate(sats):
+        s_a[i] = (int(prn), 0, float(f_hz), float(tau))
+    return s_a, _lib.SigCfg(int(antennas), int(n_ms), float(carrier_hz), float(f_offset))
+
+
+def signature_plan(code_samples, n, sats, antennas, n_ms=0, f_offset=0.0, carrier_hz=1575.42e6):
+    """gpsmi_acq_signature_plan: the argument checks of AcqEngine.signatures without a GPU, for
+    rows of `n` samples.  -> (n_win int32 [R], max_windows); EngineError where the call would
+    refuse."""
+    s_a, cfg = _sig_args(sats, antennas, n_ms, f_offset, carrier_hz)
+    n_win = np.zeros(max(len(s_a), 1), np.int32)
+    max_w = C.c_int(0)
+    check(_lib.load().gpsmi_acq_signature_plan(int(code_samples), int(n), ptr(s_a), len(s_a), C.byref(cfg),
+                                               ptr(n_win), C.byref(max_w)), 'gpsmi_acq_signature_plan')
+    return n_win[:len(s_a)], max_w.value
+
+
 def _iq_dtype(raw_u8):
     """What a handle's input format holds per sample: the recorder's uint16 (Q << 8 | I) or complex64."""
     return np.uint16 if raw_u8 else np.complex64
@@ -469,6 +489,35 @@ class AcqEngine:
         check(fn(self.h, d_iq, n, ptr(s_a), len(s_a), C.byref(cfg), ptr(out) if host else out, ptr(rec), ptr(co)),
               name)
         return (out, rec, co) if coef else (out, rec)
+
+    def signatures(self, data, sats, antennas, n_ms=0, f_offset=0.0, carrier_hz=L1_HZ, prompts=False):
+        """Spatial signatures over several coherent antennas (gpsmi_acq_signature):
+        per record of `sats` -- (prn, f_hz, tau) as in cancel; a PRN may appear more than once --
+        the 1-ms prompts of every antenna at the record's code starts and their covariance over the
+        antennas.  data: a host array [antennas][n] in the input format, or a (device pointer, n)
+        pair with the rows n samples apart.  n_ms: the windows taken per record (0: all that fit).
+        Returns (cov complex128 [R][A][A], n_win int32 [R]) and with prompts=True the prompts
+        complex64 [R][A][max_windows] behind them (zero past a record's last window)."""
+        A = int(antennas)
+        s_a, cfg = _sig_args(sats, A, n_ms, f_offset, carrier_hz)
+        self._need_time_replicas(s_a['prn'])
+        if isinstance(data, tuple):
+            d_iq, n, host = data[0], int(data[1]), False
+        else:
+            rows = self._host_iq(data)
+            if rows.ndim != 2 or rows.shape[0] != A:
+                raise ValueError(f'data must be [{A}][n], one row per antenna')
+            d_iq, n, host = ptr(rows), rows.shape[1], True
+        n_win = np.zeros(max(len(s_a), 1), np.int32)
+        max_w = C.c_int(0)
+        check(self.lib.gpsmi_acq_signature_plan(self.cfg.code_samples, n, ptr(s_a), len(s_a), C.byref(cfg),
+                                                ptr(n_win), C.byref(max_w)), 'gpsmi_acq_signature_plan')
+        n_win = n_win[:len(s_a)]
+        cov = np.zeros((len(s_a), A, A), np.complex128)
+        pr = np.zeros((len(s_a), A, max_w.value), np.complex64) if prompts else None
+        fn, name = self._export('gpsmi_acq_signature', host)
+        check(fn(self.h, d_iq, n, ptr(s_a), len(s_a), C.byref(cfg), ptr(cov), ptr(n_win), ptr(pr)), name)
+        return (cov, n_win, pr) if prompts else (cov, n_win)
 
     def search_async(self, d_iq, n, prns, freqs, n_avg, out, out_dev=None):
         """Enqueue a search on device-resident iq; `out` is a pinned PEAK_DTYPE

@@ -363,13 +363,23 @@ SPOOF_MIN_DOUBLED = 2                    # doubled PRNs that raise the alarm
 SPOOF_MAX_DOUBLED = 8                    # doubled PRNs the twin fixes enumerate: 2^7 assignments
 SPOOF_PICKS = 4                          # peaks taken per PRN
 SPOOF_REFINE_HITS = 64                   # hits of one refinement call (kRefMaxHits)
+# the least |v_i^H v_j| at which two records count as one source.  Measured on the
+# four-antenna spoofed scene of tests/sig_ref.py: the restated chain over 64 ms
+# (tests/test_snapshot_signature.py) puts the least same-source pair at 0.9985 and the pairs of the
+# authentic set at 0.0093 .. 0.688; the GPU path over the whole second (MI355X,
+# tests/test_gpu_snapshot_signature.py) at 0.9999 and a least authentic pair of 0.0012.  0.95 leaves
+# more than thirty times the larger same-source deviation from 1
+SPOOF_RHO_MIN = 0.95
+SPOOF_DIRECTION_PRNS = 4                 # distinct PRNs from one direction that raise the alarm by themselves
 
 
 @dataclass
 class SpoofReport:
     """What measure(..., spoof=True) and snapshot_fix(..., spoof=True) say about a snapshot.  It
-    names PRNs that are in the air twice and, where both sets solve, two positions; it makes no
-    claim about which of them is authentic."""
+    names PRNs that are in the air twice and, where both sets solve, two positions; with one antenna
+    it makes no claim about which of them is authentic.  With `antennas` every
+    record has a spatial signature, and the set whose doubled records all arrive from one direction
+    is the spoofer's: `authentic` names the other fix."""
     doubled: list = field(default_factory=list)     # PRNs with two records
     alarm: bool = False                             # len(doubled) >= min_doubled
     crowded: bool = False                           # a PRN had more than two records that count: the two strongest stayed
@@ -378,6 +388,14 @@ class SpoofReport:
     fixes: tuple = None                             # snapshot_fix: (fix_a, fix_b), or (the single fix, None)
     separation_m: float = None                      # |fix_a - fix_b|, None without two fixes
     assignments: int = 0                            # pairs of sets that were solved
+    sets: tuple = None                              # the record indices behind `fixes` (None without two fixes)
+    antennas: int = 0                               # the coherent channels the signatures were taken over (0: none)
+    signature: object = None                        # complex128 [records][antennas]: signature_vectors, per record
+    quality: object = None                          # float64 [records]: largest eigenvalue over the mean of the others
+    rho: object = None                              # float64 [records][records]: signature_rho
+    one_source: tuple = (False, False)              # per set of `sets`: its doubled records arrive from one direction
+    one_direction: bool = False                     # SPOOF_DIRECTION_PRNS or more PRNs, every record from one direction
+    authentic: object = None                        # 0 or 1 into `fixes`; None without a verdict
 
 
 def spoof_keep(rec, found, cs, f_offset=0.0, min_doubled=SPOOF_MIN_DOUBLED):
@@ -401,6 +419,73 @@ def spoof_keep(rec, found, cs, f_offset=0.0, min_doubled=SPOOF_MIN_DOUBLED):
     report.alarm = len(report.doubled) >= min_doubled
     keep = np.array(keep, dtype=np.int64)
     return rec[keep], [found[i] for i in keep], out[keep], report
+
+
+def signature_vectors(cov):
+    """The signatures of AcqEngine.signatures' covariances complex128 [R][A][A]: per record the
+    unit principal eigenvector (numpy.linalg.eigh), turned so that its antenna-0 entry is real and
+    not negative, and the largest eigenvalue over the mean of the others (inf when those vanish).
+    -> (v complex128 [R][A], quality float64 [R])."""
+    cov = np.asarray(cov, dtype=np.complex128)
+    v = np.zeros(cov.shape[:2], np.complex128)
+    quality = np.zeros(len(cov), np.float64)
+    for r, c in enumerate(cov):
+        w, vec = np.linalg.eigh(c)
+        x = vec[:, -1]
+        if abs(x[0]) > 0.0:
+            x = x * (np.conj(x[0]) / abs(x[0]))
+        x = x / np.linalg.norm(x)
+        v[r] = x
+        v[r, 0] = abs(x[0])
+        rest = float(np.mean(w[:-1]))
+        quality[r] = w[-1] / rest if rest > 0.0 else np.inf
+    return v, quality
+
+
+def signature_rho(v):
+    """|v_i^H v_j| of unit signatures [R][A] -> float64 [R][R]."""
+    v = np.asarray(v, dtype=np.complex128)
+    return np.abs(v.conj() @ v.T)
+
+
+def _least_rho(rho, idx):
+    idx = list(idx)
+    return min((rho[i, j] for k, i in enumerate(idx) for j in idx[k + 1:]), default=np.inf)
+
+
+def spoof_resolve(report, meas, sets, v, rho_min=SPOOF_RHO_MIN):
+    """The decision on top of the signatures `v` (signature_vectors, one per record of `meas`).
+    `sets`: the pair of record-index sets behind report.fixes (None: no pair of fixes).  In each
+    set the records of the doubled PRNs count (single records are in both sets); a set is one
+    source when it holds at least two of them and their least pairwise rho is >= rho_min.  Exactly
+    one such set is the spoofer's and the other fix is authentic; both or neither: no verdict.
+    Independently one_direction: the records of SPOOF_DIRECTION_PRNS or more distinct PRNs (twins
+    included), all with a least pairwise rho >= rho_min -- a spoofer that has swamped the sky; it
+    raises the alarm without a doubled PRN.  Fills report.signature, rho, one_source,
+    one_direction, authentic (and alarm).  -> authentic."""
+    v = np.asarray(v, dtype=np.complex128)
+    rho = signature_rho(v)
+    doubled = set(report.doubled)
+    prns = [int(p) for p in meas['prn']]
+    one = [False, False]
+    if sets is not None:
+        for s, ix in enumerate(sets):
+            twins = [i for i in ix if prns[i] in doubled]
+            one[s] = len(twins) >= 2 and bool(_least_rho(rho, twins) >= rho_min)
+    report.signature, report.rho, report.one_source = v, rho, (one[0], one[1])
+    report.authentic = None if one[0] == one[1] else 1 if one[0] else 0
+    report.one_direction = len(set(prns)) >= SPOOF_DIRECTION_PRNS and bool(_least_rho(rho, range(len(prns))) >= rho_min)
+    report.alarm = report.alarm or report.one_direction
+    return report.authentic
+
+
+def authentic_first(report):
+    """With a verdict (spoof_resolve) the authentic fix goes first in report.fixes, whatever order
+    twin_fixes gave them; sets and one_source follow and authentic becomes 0.  -> fixes[0]."""
+    if report.authentic == 1:
+        report.fixes, report.sets = report.fixes[::-1], report.sets[::-1]
+        report.one_source, report.authentic = report.one_source[::-1], 0
+    return report.fixes[0]
 
 
 def twin_sets(meas):
@@ -435,7 +520,8 @@ def twin_fixes(meas, ephs, t_gps, pos, report, code_samples=2048, have_pos=True)
     of the sets that follow), and takes the pair whose two fixes are both ok with the least sum of
     rms_m.  With an a-priori position of the caller's (`have_pos`) the fix nearer to it goes first,
     otherwise the one with the lower mean C/N0 on its doubled records.  Without such a pair: the
-    best single ok fix and None.  Fills report.fixes, separation_m and assignments.
+    best single ok fix and None.  Fills report.fixes, separation_m, assignments and sets (per fix the
+    indices of the records it is made of: its set without what its residual test dropped).
     -> fix_a (a Fix that is not ok when nothing solved)."""
     fs = 1000.0 * code_samples
     pos0 = np.asarray(pos, dtype=np.float64)
@@ -476,8 +562,11 @@ def twin_fixes(meas, ephs, t_gps, pos, report, code_samples=2048, have_pos=True)
             return float(np.nanmean(c)) if c else 0.0
         swap = level(b) < level(a)
     if swap:
-        fa, fb = fb, fa
+        fa, fb, a, b = fb, fa, b, a
     report.fixes, report.separation_m = (fa, fb), float(np.linalg.norm(fa.ecef - fb.ecef))
+    # the records each fix is made of: what its residual test dropped is not behind it (the pair with
+    # the least rms may hold a PRN the wrong way round, which either fix then drops)
+    report.sets = tuple([i for i in ix if int(meas['prn'][i]) in f.prns] for f, ix in ((fa, a), (fb, b)))
     return fa
 
 
@@ -515,7 +604,8 @@ def _track_records(acq, dev, rec, out, n, f_offset, track_cfg, st):
         tracked_records(out, bits, states['bit_no'], n, acq.cfg.code_samples, track_cfg.get('pull_in_bits', 0))
 
 
-def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=None, spoof=False, **cfg):
+def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=None, spoof=False, antennas=None,
+            **cfg):
     """The satellites of one snapshot: MEAS_DTYPE records, one per satellite found, sorted by PRN.
 
     `acq`: an acquisition.Acquisition; `data`: the samples in its input format (complex64, or the
@@ -542,7 +632,12 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
     SPOOF_PICKS peaks per PRN (pipeline.peak_candidates), refined over +- one bin step and kept by
     spoof_keep: a PRN that is in the air twice comes back with two records.  -> (records,
     SpoofReport); `min_doubled`: the doubled PRNs that set its alarm; stats also receives spoof
-    (the report) and peaks_ms.  With the option off nothing of this runs."""
+    (the report) and peaks_ms.  With the option off nothing of this runs.
+    `antennas` (with `spoof` only): A = 2 .. 8 -- `data` is [A][n] on the host, or
+    (pointer, n) with A rows n samples apart behind the pointer.  Every stage above reads row 0, the
+    first n samples, exactly as without the option; after spoof_keep (and tracking) the kept records'
+    signatures are taken once over all rows (Acquisition.signatureHits) and spoof_resolve fills the
+    report's signature, quality, rho and one_direction; stats receives signature_ms."""
     from .acquisition import SAT_ALL
     from .engine import CANCEL_OUT_DTYPE, DeviceBuffer
     c = acq.cfg
@@ -556,11 +651,19 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
         raise TypeError(f'unknown options {sorted(cfg)}')
     if spoof and cancel not in (None, False):
         raise ValueError('spoof and cancel are not combined')
+    if antennas is not None:
+        if not spoof:
+            raise ValueError('antennas goes with spoof=True (the signatures serve the spoofing check)')
+        antennas = int(antennas)
+        if not 2 <= antennas <= 8:
+            raise ValueError('antennas must be 2 .. 8')
     if freqs is None:
         freqs = [c.min_freq + c.step_freq * i for i in range(int(round((c.max_freq - c.min_freq) / c.step_freq)))]
     prns = list(SAT_ALL if prns is None else prns)
     host = None if isinstance(data, tuple) else acq.engine._host_iq(data)
-    n = int(data[1]) if host is None else host.size
+    if antennas is not None and host is not None and (host.ndim != 2 or host.shape[0] != antennas):
+        raise ValueError(f'data must be [{antennas}][n], one row per antenna')
+    n = int(data[1]) if host is None else host.shape[-1] if antennas is not None else host.size
     n_seg = n // cs // n_coh
     if n < min_samples(cs) or n_seg < 1:
         raise ValueError(f'{n} samples are too few: {min_samples(cs)} (40 ms and the code slide) are needed')
@@ -582,6 +685,16 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
                                                   min_doubled)
             if source == 'track' and len(out):
                 _track_records(acq, dev, rec, out, n, f_offset, track_cfg, st)     # (indexed by record)
+            if antennas is not None:
+                report.antennas = antennas
+                if len(out):
+                    cov, _ = acq.signatureHits(dev, out, antennas, f_offset=f_offset)
+                    st['signature_ms'] = acq.engine.last_ms()
+                    st['device_ms'] += st['signature_ms']
+                    v, report.quality = signature_vectors(cov)
+                    spoof_resolve(report, out, None, v)
+                else:
+                    st['signature_ms'] = 0.0
             st['spoof'] = report
             if stats is not None:
                 stats.update(st)
@@ -865,7 +978,7 @@ def _collective_fix(acq, data, ephs, t_gps, pos, f_offset, cfg, stats):
 
 
 def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, cancel=None, stats=None,
-                 collective=None, collective_cfg=None, spoof=False, **cfg):
+                 collective=None, collective_cfg=None, spoof=False, antennas=None, **cfg):
     """measure -> (doppler_fix when `pos` is None) -> coarse_time_fix.  `t_gps`: the GPS seconds
     of week of the first sample as far as known; `cancel`, `stats`: measure's.  -> (Fix,
     measurements, device ms).  The Fix's t_gps is that of its `sample`.
@@ -878,19 +991,26 @@ def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, ca
     spoof=True); without a doubled PRN everything goes on as with the option off.  With doubled
     PRNs twin_fixes solves once per consistent assignment of their records to two sets; the first
     return value is fix_a, the SpoofReport (doubled, alarm, fixes = (fix_a, fix_b), separation_m)
-    rides on stats['spoof'] and on the Fix's attribute `spoof`.  Which fix is authentic is not
-    claimed."""
+    rides on stats['spoof'] and on the Fix's attribute `spoof`.  With one antenna which fix is
+    authentic is not claimed.
+    `antennas` (with `spoof` only, measure's): twin_fixes is followed by
+    spoof_resolve on the records' signatures; with a verdict the authentic fix goes first
+    (fixes[0], the returned Fix, report.authentic 0) whatever the a-priori or the C/N0 say, without
+    one the order of twin_fixes stands.  report.one_direction raises the alarm without a doubled
+    PRN."""
     if collective not in (None, False, True, 'always'):
         raise ValueError(f"collective {collective!r}: None, False, True or 'always'")
     if collective and pos is None:
         raise ValueError('collective detection needs an a-priori position')
     if spoof and collective:
         raise ValueError('spoof and collective are not combined')
+    if antennas is not None and not spoof:
+        raise ValueError('antennas goes with spoof=True (the signatures serve the spoofing check)')
     stats = {} if stats is None else stats
     report = None
     if spoof:
         meas, report = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats,
-                               cancel=cancel, spoof=True, **cfg)
+                               cancel=cancel, spoof=True, antennas=antennas, **cfg)
     else:
         meas = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats, cancel=cancel,
                        **cfg)
@@ -903,6 +1023,9 @@ def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, ca
             if not have_pos:                         # (one record per PRN, the stronger: a Doppler is a Doppler)
                 pos, _ = doppler_fix(meas[twin_sets(meas)[0][0]], ephs, t_gps, f_offset=f_offset)
             fix = twin_fixes(meas, ephs, t_gps, pos, report, acq.cfg.code_samples, have_pos)
+            if report.signature is not None:
+                spoof_resolve(report, meas, report.sets, report.signature)
+                fix = authentic_first(report)
         fix.spoof = report
         return fix, meas, ms
     if collective and (collective == 'always' or len(meas) < MIN_SAT):

@@ -66,7 +66,7 @@ const char* gpsmi_version(void);
 /* sizeof() of the ABI structs as compiled: 0 cfg, 1 peak, 2 trk_state, 3 trk_out,
  * 4 offsetof(trk_out, code_phase), 5 fe_cfg, 6 pb_cfg, 7 refine_hit, 8 refine_cfg, 9 refine_out,
  * 10 wtrk_cfg, 11 wtrk_state, 12 wtrk_bit, 13 cancel_sat, 14 cancel_cfg, 15 cancel_out, 17 collective_sat,
- * 18 collective_grid, 19 collective_cell, 21 nul_cfg, 23 tfx_cfg, 24 peaks_cfg, 25 peaks_pick (16, 20 and 22 are not assigned); -1 otherwise.  Lets a binding verify its own struct declarations before the first real call.  */
+ * 18 collective_grid, 19 collective_cell, 21 nul_cfg, 23 tfx_cfg, 24 peaks_cfg, 25 peaks_pick, 27 sig_sat, 28 sig_cfg (16, 20, 22 and 26 are not assigned); -1 otherwise.  Lets a binding verify its own struct declarations before the first real call.  */
 int gpsmi_abi_sizeof(int which);
 /* Kernel-variant selection and tuning thresholds, visible through the ABI (round 4: they used to
  * be environment variables read inside gpsmi_*_create, invisible to a C caller; the variables
@@ -624,6 +624,60 @@ int gpsmi_acq_cancel_dev(gpsmi_acq* h, const void* d_iq, size_t n, const gpsmi_c
  * largest number of windows of any satellite (max_windows, optional) the coef array is sized by  */
 int gpsmi_acq_cancel_plan(int code_samples, size_t n, const gpsmi_cancel_sat* sats, int nsat,
                           const gpsmi_cancel_cfg* cfg, int* max_windows);
+/* Spatial signatures of refined records over several coherent antennas (float64
+ * restatement: tests/sig_ref.py): what tells signals that arrive from one direction -- a spoofer sends
+ * every PRN from one antenna -- from satellites all over the sky.  Per record (prn, f_hz, tau, with the
+ * meaning of gpsmi_cancel_sat; the same PRN may appear more than once: twin records are the point) the
+ * 1-ms prompts of every antenna and their covariance over the antennas; the principal eigenvector of
+ * that matrix is the record's signature (host: gpsmi/snapshot.py).  cs = code_samples, fs = 1000 cs.
+ * iq: `antennas` rows of n samples each ([A][n], row a = antenna a, antenna 0 first: the layout of
+ * gpsmi_nul_apply) in the handle's input format, host memory for gpsmi_acq_signature, device memory for
+ * gpsmi_acq_signature_dev; GPSMI_IQ_U8 gives the same bytes as its complex64 decode.  A = 2 .. 8,
+ * nsat = 1 .. 64.
+ * Windows.  Tc = cs / (1 + (f_hz - f_offset_hz) / carrier_hz) and j_k = rint(tau + k Tc) (float64,
+ * unfused, ties to even, on the host) as in gpsmi_acq_cancel; a record's windows are all k with
+ * 0 <= j_k and j_k + cs <= n, in order, of which a positive n_ms keeps the first n_ms.  A record
+ * without a window is GPSMI_E_ARG.
+ * Prompts.  P[r][a][k] = sum_{i < cs} x_a[j_k + i] exp(-j 2 pi f_hz (j_k + i + 1) / fs) R[i] with
+ * R = GPSCacode(prn) (gpsmi_acq_set_replica_time) and the integer carrier phase of gpsmi_acq_cancel
+ * (0.64 fixed point, its top 24 bits give sine and cosine).  float32 sums in one fixed order that is the
+ * same for every antenna and depends neither on A nor on nsat nor on what else shares the call.
+ * Covariance.  C[r][a][b] = sum_k P[r][a][k] conj(P[r][b][k]): float64 sums of the widened float32
+ * prompts in one fixed order over k; the upper triangle is computed, the lower one is its exact
+ * conjugate, the diagonal's imaginary part is exactly 0.  A factor common to the antennas of a window
+ * drops out -- the data bit, the residual carrier phase, a Doppler error of a few Hz -- so there is no
+ * bit edge and no loop.
+ * Outputs (host arrays): cov double [nsat][A][A][2]; n_win int32 [nsat]; prompts: optional complex64
+ * [nsat][A][max_windows] (max_windows from gpsmi_acq_signature_plan), zero past a record's last window.
+ * A record's result depends on that record alone.  The same arguments give the same bytes, from
+ * either entry point.  Argument errors are GPSMI_E_ARG and need no GPU (gpsmi_acq_signature_plan makes
+ * the same checks without a handle): a null pointer, antennas outside 2 .. 8, nsat, a PRN outside
+ * 1 .. 37, f_hz or tau not finite, |f_hz| >= fs / 2, (f_hz - f_offset_hz) beyond 1 % of carrier_hz,
+ * n outside 1 .. 2^40 / A, a reserved field that is not 0.  code_samples 2048 and 16368 only
+ * (GPSMI_E_UNSUPPORTED); GPSMI_E_STATE: no time-domain replica for a PRN; GPSMI_E_NOMEM leaves the
+ * handle usable.  cfg may be null (all defaults).  The call returns when the work is done;
+ * gpsmi_acq_last_ms reports it.                                                                  */
+typedef struct gpsmi_sig_sat {      /* no implicit padding: 24 bytes */
+    int32_t prn;
+    int32_t reserved;               /* 0 */
+    double  f_hz;
+    double  tau;                    /* a code start, samples from iq[0] of every row; any sign */
+} gpsmi_sig_sat;
+typedef struct gpsmi_sig_cfg {      /* no implicit padding: 24 bytes; 0 = the default */
+    int32_t antennas;               /* 0: 2 */
+    int32_t n_ms;                   /* 0: every window that fits */
+    double  carrier_hz;             /* 0: 1575.42e6 */
+    double  f_offset_hz;            /* as in gpsmi_acq_search_deep; finite */
+} gpsmi_sig_cfg;
+int gpsmi_acq_signature(gpsmi_acq* h, const void* iq, size_t n, const gpsmi_sig_sat* sats, int nsat,
+                        const gpsmi_sig_cfg* cfg, double* cov, int32_t* n_win, float* prompts);
+int gpsmi_acq_signature_dev(gpsmi_acq* h, const void* d_iq, size_t n, const gpsmi_sig_sat* sats, int nsat,
+                            const gpsmi_sig_cfg* cfg, double* cov, int32_t* n_win, float* prompts);
+/* host only, no GPU: the argument checks of gpsmi_acq_signature for a handle of code_samples, the
+ * windows of every record (n_win [nsat], optional) and the largest of them (max_windows, optional)
+ * the prompts array is sized by  */
+int gpsmi_acq_signature_plan(int code_samples, size_t n, const gpsmi_sig_sat* sats, int nsat,
+                             const gpsmi_sig_cfg* cfg, int32_t* n_win, int* max_windows);
 /* Input format of the iq pointers of the search calls that follow (host or device), as
  * gpsmi_trk_set_input_format below: GPSMI_IQ_U8 = the raw recording of streamData
  * (gpsrecv.py:162-173), decoded where the carrier wipe-off reads it; same bits out.   */

@@ -7,7 +7,7 @@ gpseval) as one command on the GPU path.
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--sweep [L]] [--blank] [--json]
                              [--antenna FILE ... --null [--null-taps T]]
                              [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track [--weak-fix]]]]
-                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]] [--spoof-check [K]]]
+                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]] [--spoof-check [K]] [--antenna FILE ...]]]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -75,8 +75,12 @@ and 2 s of --near and --time, and the fix is solved from the satellites measured
 (DESIGN.md 4.2k); the report gains 'path' and, where the search ran, a 'collective' entry.
 --spoof-check [K] (with --snapshot only): up to four peaks per PRN are refined, PRNs that are in the air twice
 are listed, from K of them on (default 2) the alarm is raised, and both sets of records are solved: the
-report gains a 'spoof' entry with the doubled PRNs, both fixes and their separation.  Which
-fix is authentic is not decided, and the exit status is 0 either way.
+report gains a 'spoof' entry with the doubled PRNs, both fixes and their separation.  With one
+antenna which fix is authentic is not decided, and the exit status is 0 either way.  With --antenna FILE ...
+(without --null) every file gives one further row of the snapshot of a coherent multi-antenna recorder: every
+record gets a spatial signature over the antennas, the set of doubled records that all arrive from one direction
+is the spoofer's, and the report names the authentic fix (first) and says whether every signal arrives from one
+direction ('authentic', 'one_source', 'one_direction').
 
 There is no recording in this repository (data/test.bin is absent from the reference
 checkout, SURVEY F2, and too short for a fix even upstream): tests/test_run_file.py writes a
@@ -269,31 +273,44 @@ def parse_time(text, ephs):
 
 
 def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, frontend=None, excise=False,
-             blank=False, cancel=None, collective_km=None, spoof_k=None):
+             blank=False, cancel=None, collective_km=None, spoof_k=None, antennas=()):
     """--snapshot: gpsmi.snapshot.snapshot_fix on the first `seconds` behind `start_stream`, read
     and filtered block by block as run() feeds its receiver.  `cancel`: --cancel's C/N0 threshold
     (snapshot.measure's `cancel`); None leaves everything as it is without the flag.
     `collective_km`: --collective's radius (snapshot_fix's collective=True within it); None: not asked for.
-    `spoof_k`: --spoof-check's doubled PRNs that raise the alarm (snapshot_fix's spoof=True); None: not asked for."""
+    `spoof_k`: --spoof-check's doubled PRNs that raise the alarm (snapshot_fix's spoof=True); None: not asked for.
+    `antennas` (with `spoof_k`): the files of the further channels of a coherent recorder; every file gives one
+    row of the snapshot, `path` the first, and the spoofing check names the authentic fix from the records'
+    spatial signatures (snapshot_fix's antennas=A)."""
     from gpsmi import ingest, position as P, snapshot as S
     from gpsmi.acquisition import Acquisition
     from gpsmi.conditioning import Conditioner
     from gpsmi.engine import Config
     cfg = Config()
     need = int(round(seconds * 1000)) * cfg.code_samples
-    with ingest.open_blocks(path, cfg, start_stream, frontend) as (source, raw_u8):
+    with ingest.open_blocks(path, cfg, start_stream, frontend, antennas) as (source, raw_u8):
         cond, acq = Conditioner(cfg, raw_u8, excise, blank), None
         try:
-            blocks, have = ingest.take(source, need, cond)
+            if antennas:                             # [A][NGPS] blocks, as they come (no conditioning stage is asked for)
+                blocks, have = [], 0
+                for blk in source:
+                    blocks.append(np.array(blk))
+                    have += blk.shape[1]
+                    if have >= need:
+                        break
+            else:
+                blocks, have = ingest.take(source, need, cond)
             if have < need:
                 sys.exit(f'--snapshot: the recording holds {have} samples after stream {start_stream}, {seconds} s need {need}')
             acq = Acquisition(cfg, raw_u8=cond.out_raw_u8)
             t0 = time.perf_counter()
             stats = {}
-            fix, meas, ms = S.snapshot_fix(acq, np.concatenate(blocks)[:need], ephemerides, t_gps,
+            data = np.ascontiguousarray(np.concatenate(blocks, axis=1)[:, :need]) if antennas else np.concatenate(blocks)[:need]
+            fix, meas, ms = S.snapshot_fix(acq, data, ephemerides, t_gps,
                                            pos=None if near is None else np.array(P.geo_to_ecef(*near)),
                                            cancel=cancel, stats=stats,
                                            **({} if spoof_k is None else {'spoof': True, 'min_doubled': spoof_k}),
+                                           **({'antennas': 1 + len(antennas)} if antennas else {}),
                                            **({} if collective_km is None else
                                               {'collective': True, 'collective_cfg': {'radius_m': 1.0e3 * collective_km}}))
             wall = time.perf_counter() - t0
@@ -333,6 +350,11 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
                                 'height_m': None if geo is None else round(float(geo[2]), 1),
                                 'ecef_m': [round(float(v), 2) for v in fx.ecef], 'satellites': fx.prns,
                                 'dropped': fx.dropped, 'residual_rms_m': round(fx.rms_m, 2)})
+        if antennas:
+            sp.update({'antennas': 1 + len(antennas), 'authentic': None if rep is None else rep.authentic,
+                       'one_source': [False, False] if rep is None else [bool(v) for v in rep.one_source],
+                       'one_direction': bool(rep is not None and rep.one_direction),
+                       'signature_ms': round(float(stats.get('signature_ms', 0.0)), 3)})
         out['spoof'] = sp
     if cancel is not None:
         out['cancelled'] = [{'prn': int(r['prn']), 'n_windows': int(r['n_windows']), 'n_skipped': int(r['n_skipped']),
@@ -374,7 +396,19 @@ def print_snapshot(out):
             elif fx is not None:
                 print(f"  {name}: no fix ({fx['reason']})")
         if sp['separation_m'] is not None:
-            print(f"  the two fixes are {sp['separation_m']} m apart; which of them is authentic is not decided here")
+            if sp.get('authentic') is not None:
+                print(f"  the two fixes are {sp['separation_m']} m apart; the doubled signals of fix "
+                      f"{'ab'[1 - sp['authentic']]} arrive from one direction over {sp['antennas']} antennas: "
+                      f"fix {'ab'[sp['authentic']]} is authentic")
+            elif 'antennas' in sp:
+                print(f"  the two fixes are {sp['separation_m']} m apart; over {sp['antennas']} antennas "
+                      f"{'both sets' if all(sp['one_source']) else 'neither set'} of doubled signals arrive from one "
+                      f"direction: no verdict")
+            else:
+                print(f"  the two fixes are {sp['separation_m']} m apart; with one antenna which of them is authentic is "
+                      f"not decided here")
+        if 'antennas' in sp:
+            print(f"  one direction for every signal over {sp['antennas']} antennas: {'YES' if sp['one_direction'] else 'no'}")
     for m in s['measurements']:
         cn0 = 'n/a' if m['cn0_dbhz'] is None else f"{m['cn0_dbhz']:.1f}"
         print(f"  PRN {m['prn']:2d}  sample {m['sample']:8d}  code_phase {m['code_phase']:9.4f}  f_hz {m['f_hz']:+9.2f}  "
@@ -587,8 +621,12 @@ def main():
             ap.error('--collective [RADIUS_KM]: needs --near, 0.1 .. 100 km')
         if a.spoof_check is not None and (a.spoof_check < 1 or a.cancel is not None or a.collective is not None):
             ap.error('--spoof-check [K]: K from 1 on, without --cancel / --collective')
+        if a.antenna and (a.spoof_check is None or a.null or a.null_taps != 1 or frontend is not None or a.excise
+                          or a.blank or len(a.antenna) > 7):
+            ap.error('--antenna FILE with --snapshot: up to seven further channels, with --spoof-check, in the '
+                     'recorder\'s own format, without --null / --null-taps / --excise / --blank')
         out = snapshot(a.recording, a.snapshot, eph, parse_time(a.time, eph), near, a.start_stream, frontend,
-                       a.excise, a.blank, a.cancel, a.collective, a.spoof_check)
+                       a.excise, a.blank, a.cancel, a.collective, a.spoof_check, a.antenna)
         if a.json:
             print(json.dumps(out))
         else:
