@@ -6,6 +6,8 @@
 // output y = sum_a conj(w32[a]) x_a in float32; a block whose predicted gain is below min_gain_db (or
 // whose R has no Cholesky factor) passes antenna 0 through.  With cfg.taps = 3, 5 or 7 every antenna has a
 // filter of that many taps instead: the kernels of gpsmi_nul_stap.h, dispatched from nul_run below.
+// gpsmi_nul_beams forms per-satellite beams from the same covariance: the kernels of gpsmi_nul_beam.h,
+// dispatched from beam_run below; it shares nul_cov_kernel and leaves everything else here alone.
 //
 //   nul_cov_kernel<FMT, A>    one workgroup per (block, slice of 8192 samples): lane t takes the samples
 //                             2048 r + 8 t .. + 7, r = 0 .. 3, as b128 loads (two complex64 or
@@ -290,6 +292,7 @@ __global__ __launch_bounds__(kNulThreads) void nul_apply_kernel(const void* __re
 }  // namespace gpsmi
 
 #include "gpsmi_nul_stap.h"
+#include "gpsmi_nul_beam.h"
 
 using namespace gpsmi;
 
@@ -303,6 +306,14 @@ struct gpsmi_nul {
     int taps = 1;                                         // 1: one weight per antenna, else 3, 5 or 7
     DevEvent ev_cov, ev_solve;                            // stamps behind the first and the second kernel
     float kernel_ms[3] = {0.f, 0.f, 0.f};                 // covariance, solve, apply of the last finished call
+    // gpsmi_nul_beams: its own results, so that a call leaves gpsmi_nul_apply's alone
+    DevBuf<double> d_bvec;                                // [nbeam + nnull][A][2]: steer, then nulls
+    DevBuf<uint32_t> d_bmask;                             // [nbeam]
+    DevBuf<float2> d_bw32;                                // [blocks][nbeam][8]
+    DevBuf<double> d_bw64;                                // [blocks][nbeam][A][2]
+    DevBuf<int32_t> d_bflags; DevBuf<float> d_bgain;      // [blocks][nbeam]
+    DevBuf<char> d_bout;                                  // host entry: the staged beams
+    float beam_ms[3] = {0.f, 0.f, 0.f};                   // covariance, solve, apply of the last finished beams call
     BlockStage blk;
     StageSync sync;                                       // last: see gpsmi_stage.h
 };
@@ -382,6 +393,171 @@ static int nul_finish(gpsmi_nul* h, int nb, int32_t* flags, float* gain_db, doub
     return GPSMI_OK;
 }
 
+// ---- beams -------------------------------------------------------------------------------------
+
+struct BeamPlan {
+    int nbeam, nnull;
+    const double *steer, *nulls;
+    const uint32_t* mask;
+};
+
+// The checks of a beam description that need neither a handle nor a GPU (gpsmi_nul_beams_plan).
+static int beam_check_plan(const char* fn, int A, const BeamPlan& p) {
+    if (A < 2 || A > kNulMaxA) return fail(GPSMI_E_ARG, "%s: antennas out of range 2..8", fn);
+    if (p.nbeam < 1 || p.nbeam > kBeamMax) return fail(GPSMI_E_ARG, "%s: nbeam out of range 1..64", fn);
+    if (p.nnull < 0 || p.nnull > kBeamMaxNull) return fail(GPSMI_E_ARG, "%s: nnull out of range 0..4", fn);
+    if (!p.steer || (p.nnull > 0 && (!p.nulls || !p.mask))) return fail(GPSMI_E_ARG, "%s: null argument", fn);
+    // every vector finite and not zero; unit[j]: vector j over its length (steer, then nulls)
+    auto unit = [&](const double* g, double (*u)[2]) {
+        double s2 = 0.0;
+        for (int a = 0; a < A; ++a) {
+            if (!std::isfinite(g[2 * a]) || !std::isfinite(g[2 * a + 1])) return false;
+            s2 += g[2 * a] * g[2 * a] + g[2 * a + 1] * g[2 * a + 1];
+        }
+        const double len = std::sqrt(s2);
+        if (!(len > 0.0) || !std::isfinite(len)) return false;
+        for (int a = 0; a < A; ++a) {
+            u[a][0] = g[2 * a] / len;
+            u[a][1] = g[2 * a + 1] / len;
+        }
+        return true;
+    };
+    double un[kBeamMaxNull][kNulMaxA][2];
+    for (int q = 0; q < p.nnull; ++q)
+        if (!unit(p.nulls + (size_t)q * A * 2, un[q]))
+            return fail(GPSMI_E_ARG, "%s: null vector %d is zero or not finite", fn, q);
+    for (int b = 0; b < p.nbeam; ++b) {
+        double (*col[kBeamMaxM])[2];
+        double us[kNulMaxA][2];
+        if (!unit(p.steer + (size_t)b * A * 2, us))
+            return fail(GPSMI_E_ARG, "%s: steering vector %d is zero or not finite", fn, b);
+        const uint32_t mk = p.mask ? p.mask[b] : 0u;
+        if (p.nnull < 32 && (mk >> p.nnull) != 0u)
+            return fail(GPSMI_E_ARG, "%s: null_mask of beam %d names a null vector the call does not have", fn, b);
+        int m = 0;
+        col[m++] = us;
+        for (int q = 0; q < p.nnull; ++q)
+            if ((mk >> q) & 1u) col[m++] = un[q];
+        if (m > A) return fail(GPSMI_E_ARG, "%s: beam %d has more constraints than antennas", fn, b);
+        // the Gram matrix of the unit columns and its Cholesky: every pivot >= 1 / 64
+        double Lr[kBeamMaxM][kBeamMaxM], Li[kBeamMaxM][kBeamMaxM];
+        for (int j = 0; j < m; ++j) {
+            for (int i = j; i < m; ++i) {
+                double re = 0.0, im = 0.0;                // conj(col i) . col j
+                for (int a = 0; a < A; ++a) {
+                    re += col[i][a][0] * col[j][a][0] + col[i][a][1] * col[j][a][1];
+                    im += col[i][a][0] * col[j][a][1] - col[i][a][1] * col[j][a][0];
+                }
+                for (int k = 0; k < j; ++k) {             // - L[i][k] conj(L[j][k])
+                    re -= Lr[i][k] * Lr[j][k] + Li[i][k] * Li[j][k];
+                    im -= Li[i][k] * Lr[j][k] - Lr[i][k] * Li[j][k];
+                }
+                if (i == j) {
+                    if (!(re >= 1.0 / 64.0))
+                        return fail(GPSMI_E_ARG, "%s: the constraints of beam %d are dependent (pivot %.4g < 1/64)",
+                                    fn, b, re);
+                    Lr[j][j] = std::sqrt(re);
+                    Li[j][j] = 0.0;
+                } else {
+                    Lr[i][j] = re / Lr[j][j];
+                    Li[i][j] = im / Lr[j][j];
+                }
+            }
+        }
+    }
+    return GPSMI_OK;
+}
+
+// The checks of a beams call on a live handle, before any GPU work.  Strides in samples, 0 filled in.
+static int beam_check_call(const gpsmi_nul* h, const char* fn, const void* iq, size_t in_stride, const void* out,
+                           size_t out_stride, int nb, const BeamPlan& p, bool dev) {
+    if (!h || !iq || !out) return fail(GPSMI_E_ARG, "%s: null argument", fn);
+    if (h->taps != 1) return fail(GPSMI_E_STATE, "%s: the handle is a space-time one (taps %d)", fn, h->taps);
+    const int n = h->cfg.block_samples, A = h->cfg.antennas;
+    if (nb < 1 || (size_t)nb * n > ((size_t)1 << 31))
+        return fail(GPSMI_E_ARG, "%s: nb out of range: 1 .. 2^31 samples per call", fn);
+    const int rc = beam_check_plan(fn, A, p);
+    if (rc) return rc;
+    const size_t row = (size_t)nb * n, ss = h->blk.fmt == GPSMI_IQ_U8 ? sizeof(uint16_t) : sizeof(float2);
+    if (in_stride < row || out_stride < row || in_stride > ((size_t)1 << 40) || out_stride > ((size_t)1 << 40))
+        return fail(GPSMI_E_ARG, "%s: a row stride is shorter than the nb * n samples of a row", fn);
+    if (dev && ((uintptr_t)iq % (ss == 2 ? 4 : 16) != 0 || (uintptr_t)out % 16 != 0 || in_stride % 2 != 0 ||
+                out_stride % 2 != 0))
+        return fail(GPSMI_E_ARG,
+                    "%s: device input / output rows not aligned (4 bytes for u8, 16 for complex64: even strides)", fn);
+    const char* i0 = static_cast<const char*>(iq);
+    const char* o0 = static_cast<const char*>(out);
+    for (int a = 0; a < A; ++a) {
+        const char* ia = i0 + a * in_stride * ss;
+        for (int b = 0; b < p.nbeam; ++b) {
+            const char* ob = o0 + b * out_stride * sizeof(float2);
+            if (!(ob + row * sizeof(float2) <= ia || ia + row * ss <= ob))
+                return fail(GPSMI_E_ARG, "%s: input and output overlap (no in-place beams)", fn);
+        }
+    }
+    return GPSMI_OK;
+}
+
+// The three passes over nb blocks: nul_cov_kernel as gpsmi_nul_apply runs it, then the beams' own two.
+static int beam_run(gpsmi_nul* h, const void* d_iq, size_t in_stride, void* d_out, size_t out_stride, int nb,
+                    const BeamPlan& p) {
+    const int n = h->cfg.block_samples, A = h->cfg.antennas, B = p.nbeam, Q = p.nnull;
+    const int ns = (n + kNulSlice - 1) / kNulSlice;
+    const char* what = "beam results";
+    int rc = h->d_part.reserve((size_t)nb * ns * nul_values(A), "null steering slice sums");
+    if (!rc) rc = h->d_bvec.reserve((size_t)(kBeamMax + kBeamMaxNull) * kNulMaxA * 2, what);
+    if (!rc) rc = h->d_bmask.reserve(kBeamMax, what);
+    if (!rc) rc = h->d_bw32.reserve((size_t)nb * B * kNulMaxA, what);
+    if (!rc) rc = h->d_bw64.reserve((size_t)nb * B * A * 2, what);
+    if (!rc) rc = h->d_bflags.reserve((size_t)nb * B, what);
+    if (!rc) rc = h->d_bgain.reserve((size_t)nb * B, what);
+    if (rc) return rc;
+    const hipStream_t st = h->sync.stream;
+    uint32_t mask[kBeamMax];
+    for (int b = 0; b < B; ++b) mask[b] = p.mask ? p.mask[b] : 0u;
+    double* d_nulls = h->d_bvec.p + (size_t)B * A * 2;
+    GPSMI_HIP(hipMemcpyAsync(h->d_bvec.p, p.steer, (size_t)B * A * 2 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (Q > 0)
+        GPSMI_HIP(hipMemcpyAsync(d_nulls, p.nulls, (size_t)Q * A * 2 * sizeof(double), hipMemcpyHostToDevice, st));
+    GPSMI_HIP(hipMemcpyAsync(h->d_bmask.p, mask, (size_t)B * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    GPSMI_HIP(hipStreamSynchronize(st));                  // (mask is on this stack)
+    if ((rc = h->sync.begin())) return rc;
+    const int nc = (n + kNulThreads * kBeamApply - 1) / (kNulThreads * kBeamApply);
+    with_fmt(h->blk.fmt, [&](auto fmt) {
+        constexpr int FMT = decltype(fmt)::value;
+        with_value<2, 3, 4, 5, 6, 7, 8>(A, [&](auto na) {
+            constexpr int NA = decltype(na)::value;
+            hipLaunchKernelGGL((nul_cov_kernel<FMT, NA>), dim3((unsigned)(nb * ns)), dim3(kNulThreads), 0, st,
+                               d_iq, n, ns, in_stride, h->d_part.p);
+            (void)hipEventRecord(h->ev_cov, st);
+            hipLaunchKernelGGL(beam_solve_kernel<NA>, dim3((unsigned)nb), dim3(kBeamSolveThreads), 0, st,
+                               h->d_part.p, n, ns, h->load, B, Q, h->d_bvec.p, d_nulls, h->d_bmask.p, h->d_bw32.p,
+                               h->d_bw64.p, h->d_bflags.p, h->d_bgain.p);
+            (void)hipEventRecord(h->ev_solve, st);
+            hipLaunchKernelGGL((beam_apply_kernel<FMT, NA>), dim3((unsigned)(nb * nc)), dim3(kNulThreads), 0, st,
+                               d_iq, n, nc, in_stride, B, h->d_bw32.p, h->d_bflags.p, static_cast<float2*>(d_out),
+                               out_stride);
+        });
+    });
+    return h->sync.end();
+}
+
+static int beam_finish(gpsmi_nul* h, int nb, int B, int32_t* flags, float* gain_db, double* weights) {
+    const hipStream_t st = h->sync.stream;
+    const size_t r = (size_t)nb * B;
+    if (flags) GPSMI_HIP(hipMemcpyAsync(flags, h->d_bflags.p, r * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (gain_db) GPSMI_HIP(hipMemcpyAsync(gain_db, h->d_bgain.p, r * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (weights)
+        GPSMI_HIP(hipMemcpyAsync(weights, h->d_bw64.p, r * h->cfg.antennas * 2 * sizeof(double),
+                                 hipMemcpyDeviceToHost, st));
+    const int rc = h->sync.finish();
+    if (rc) return rc;
+    GPSMI_HIP(hipEventElapsedTime(&h->beam_ms[0], h->sync.ev0, h->ev_cov));
+    GPSMI_HIP(hipEventElapsedTime(&h->beam_ms[1], h->ev_cov, h->ev_solve));
+    GPSMI_HIP(hipEventElapsedTime(&h->beam_ms[2], h->ev_solve, h->sync.ev1));
+    return GPSMI_OK;
+}
+
 extern "C" {
 
 int gpsmi_nul_create(const gpsmi_nul_cfg* cfg, gpsmi_nul** out) {
@@ -429,6 +605,54 @@ int gpsmi_nul_last_ms(gpsmi_nul* h, float* ms) { return stage_last_ms(h, ms, __f
 int gpsmi_nul_last_kernel_ms(gpsmi_nul* h, float* ms) {
     GPSMI_REQUIRE(h && ms, "null argument");
     for (int k = 0; k < 3; ++k) ms[k] = h->kernel_ms[k];
+    return GPSMI_OK;
+}
+
+int gpsmi_nul_beams_plan(int antennas, int nbeam, const double* steer, int nnull, const double* nulls,
+                         const uint32_t* null_mask) {
+    return beam_check_plan(__func__, antennas, BeamPlan{nbeam, nnull, steer, nulls, null_mask});
+}
+
+int gpsmi_nul_beams_dev(gpsmi_nul* h, const void* d_iq, int64_t in_stride, void* d_out, int64_t out_stride, int nb,
+                        int nbeam, const double* steer, int nnull, const double* nulls, const uint32_t* null_mask,
+                        int32_t* flags, float* gain_db, double* weights) {
+    GPSMI_REQUIRE(h, "null argument");
+    GPSMI_REQUIRE(in_stride >= 0 && out_stride >= 0, "negative row stride");
+    const BeamPlan p{nbeam, nnull, steer, nulls, null_mask};
+    const size_t row = (size_t)(nb > 0 ? nb : 0) * h->cfg.block_samples;
+    const size_t is = in_stride ? (size_t)in_stride : row, os = out_stride ? (size_t)out_stride : row;
+    int rc = beam_check_call(h, __func__, d_iq, is, d_out, os, nb, p, true);
+    if (rc) return rc;
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    rc = beam_run(h, d_iq, is, d_out, os, nb, p);
+    if (rc) return rc;
+    return beam_finish(h, nb, nbeam, flags, gain_db, weights);
+}
+
+int gpsmi_nul_beams(gpsmi_nul* h, const void* iq, float* out, int nb, int nbeam, const double* steer, int nnull,
+                    const double* nulls, const uint32_t* null_mask, int32_t* flags, float* gain_db,
+                    double* weights) {
+    GPSMI_REQUIRE(h, "null argument");
+    const BeamPlan p{nbeam, nnull, steer, nulls, null_mask};
+    const size_t row = (size_t)(nb > 0 ? nb : 0) * h->cfg.block_samples;
+    int rc = beam_check_call(h, __func__, iq, row, out, row, nb, p, false);
+    if (rc) return rc;
+    GPSMI_HIP(hipSetDevice(h->cfg.device));
+    const hipStream_t st = h->sync.stream;
+    const size_t ib = h->blk.in_bytes(nb), ob = (size_t)nbeam * row * sizeof(float2);
+    rc = h->blk.io.in.reserve(ib, "beam staging");
+    if (!rc) rc = h->d_bout.reserve(ob, "beam staging");
+    if (rc) return rc;
+    GPSMI_HIP(hipMemcpyAsync(h->blk.io.in.p, iq, ib, hipMemcpyHostToDevice, st));
+    rc = beam_run(h, h->blk.io.in.p, row, h->d_bout.p, row, nb, p);
+    if (rc) return rc;
+    GPSMI_HIP(hipMemcpyAsync(out, h->d_bout.p, ob, hipMemcpyDeviceToHost, st));
+    return beam_finish(h, nb, nbeam, flags, gain_db, weights);
+}
+
+int gpsmi_nul_last_beam_kernel_ms(gpsmi_nul* h, float* ms) {
+    GPSMI_REQUIRE(h && ms, "null argument");
+    for (int k = 0; k < 3; ++k) ms[k] = h->beam_ms[k];
     return GPSMI_OK;
 }
 

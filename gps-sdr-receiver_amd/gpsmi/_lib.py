@@ -215,6 +215,7 @@ EXPORTS = [
     'gpsmi_pb_apply', 'gpsmi_pb_apply_dev', 'gpsmi_pb_last_ms',
     'gpsmi_nul_create', 'gpsmi_nul_destroy', 'gpsmi_nul_set_input_format',
     'gpsmi_nul_apply', 'gpsmi_nul_apply_dev', 'gpsmi_nul_last_ms', 'gpsmi_nul_last_kernel_ms',
+    'gpsmi_nul_beams_plan', 'gpsmi_nul_beams', 'gpsmi_nul_beams_dev', 'gpsmi_nul_last_beam_kernel_ms',
     'gpsmi_tfx_create', 'gpsmi_tfx_destroy', 'gpsmi_tfx_set_input_format', 'gpsmi_tfx_reset',
     'gpsmi_tfx_apply', 'gpsmi_tfx_apply_dev', 'gpsmi_tfx_last_ms', 'gpsmi_tfx_last_power',
 ]
@@ -363,6 +364,11 @@ def load():
         'gpsmi_nul_apply_dev': [vp, vp, vp, C.c_int, vp, vp, vp],
         'gpsmi_nul_last_ms': [vp, P(f32)],
         'gpsmi_nul_last_kernel_ms': [vp, P(f32)],
+        'gpsmi_nul_beams_plan': [C.c_int, C.c_int, vp, C.c_int, vp, vp],
+        'gpsmi_nul_beams': [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp],
+        'gpsmi_nul_beams_dev': [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, vp, vp,
+                                vp, vp, vp],
+        'gpsmi_nul_last_beam_kernel_ms': [vp, P(f32)],
         'gpsmi_tfx_create': [P(TfxCfg), P(vp)],
         'gpsmi_tfx_destroy': [vp],
         'gpsmi_tfx_set_input_format': [vp, C.c_int],

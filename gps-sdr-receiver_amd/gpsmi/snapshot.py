@@ -479,6 +479,121 @@ def spoof_resolve(report, meas, sets, v, rho_min=SPOOF_RHO_MIN):
     return report.authentic
 
 
+# ---------------------------------------------------------------- per-satellite beams
+# a record outside the spoofer's set carries the null when its signature's rho to the null vector is
+# at most this: the null costs 1 / (1 - rho^2) of noise gain, exactly 3 dB here
+BEAM_NULL_RHO_MAX = float(np.sqrt(0.5))
+BEAM_MAX = 64                            # beams of one gpsmi_nul_beams call
+
+
+def one_source(rho, prns, rho_min=SPOOF_RHO_MIN):
+    """What one transmitter sends: the largest set of records (indices into `prns`, ascending) of
+    SPOOF_DIRECTION_PRNS or more distinct PRNs whose pairwise rho is all >= rho_min.  A transmitter
+    sends a PRN once, so a set holds no PRN twice: of a spoofer's copy and the authentic satellite
+    that happens to stand in its direction only one belongs to it.  Of several sets of the largest
+    size the tightest, the one whose least pairwise rho is the greatest (then the smallest
+    indices).  None without one."""
+    rho = np.asarray(rho, dtype=np.float64)
+    prns = [int(p) for p in prns]
+    n = len(prns)
+    adj = [{j for j in range(n) if j != i and prns[j] != prns[i] and rho[i, j] >= rho_min} for i in range(n)]
+    best, best_key = None, None
+
+    def grow(clique, cand, done):                   # Bron-Kerbosch with a pivot: every maximal set
+        nonlocal best, best_key
+        if not cand and not done:
+            if len(clique) >= SPOOF_DIRECTION_PRNS:
+                ix = sorted(clique)
+                key = (-len(ix), -_least_rho(rho, ix), ix)
+                if best_key is None or key < best_key:
+                    best, best_key = ix, key
+            return
+        if best is not None and len(clique) + len(cand) < len(best):
+            return
+        pivot = max(cand | done, key=lambda u: (len(adj[u] & cand), -u))
+        for u in sorted(cand - adj[pivot]):
+            grow(clique + [u], cand & adj[u], done & adj[u])
+            cand, done = cand - {u}, done | {u}
+
+    grow([], set(range(n)), set())
+    return best
+
+
+def beam_plan(meas, cov, v, rho):
+    """What measure(..., beams=True) asks of NullSteer.beams for the records `meas`: cov
+    (AcqEngine.signatures' covariances [R][A][A]), v (signature_vectors) and rho (signature_rho).
+    Every record gets a beam at its own signature.  When one_source finds a set, its null vector is
+    the signature of the sum of that set's covariances, each over its trace; a record outside the
+    set carries the null iff its rho to that vector is <= BEAM_NULL_RHO_MAX, the set's own records
+    carry none.  -> (steer complex128 [R][A], nulls complex128 [1][A] or None, mask uint32 [R],
+    info: set (or None), null, rho_null float64 [R])."""
+    v = np.asarray(v, dtype=np.complex128)
+    cov = np.asarray(cov, dtype=np.complex128)
+    mask = np.zeros(len(v), dtype=np.uint32)
+    info = {'set': one_source(rho, meas['prn']), 'null': None, 'rho_null': np.zeros(len(v))}
+    if info['set'] is None:
+        return v.copy(), None, mask, info
+    pooled = sum(cov[i] / np.trace(cov[i]).real for i in info['set'])
+    u = signature_vectors(pooled[None])[0][0]
+    info['null'], info['rho_null'] = u, np.abs(v.conj() @ u)
+    outside = np.ones(len(v), dtype=bool)
+    outside[info['set']] = False
+    mask[outside & (info['rho_null'] <= BEAM_NULL_RHO_MAX)] = 1
+    return v.copy(), u[None].copy(), mask, info
+
+
+def _beam_pass(acq, dev, n, found, out, cov, v, rho, antennas, source, freqs, f_offset, track_cfg, st):
+    """measure's beams: one NullSteer of cfg.ngps forms the beams of all records over the whole blocks
+    of the snapshot into a complex64 device buffer, and every record is refined again (and, with
+    source 'track', tracked) on its own row from its own hit.  Replaces the confirmed records of
+    `out` in place; fills st['beams_ms'], st['before_beams'] and st['beams']."""
+    from .engine import DeviceBuffer
+    from .nulling import NullSteer
+    from .pipeline import refine_centred
+    c = acq.cfg
+    cs = c.code_samples
+    st['before_beams'], st['beams'], st['beams_ms'] = out.copy(), [], 0.0
+    nb = n // c.ngps
+    nn = nb * c.ngps
+    if not len(out) or nn < min_samples(cs):
+        return
+    steer, nulls, mask, info = beam_plan(out, cov, v, rho)
+    st['beam_plan'] = info
+    step = abs(freqs[1] - freqs[0]) if len(freqs) > 1 else c.step_freq
+    was_raw = acq.engine.raw_u8
+    ns = NullSteer(c, antennas=antennas, raw_u8=was_raw)
+    rows = DeviceBuffer(min(len(out), BEAM_MAX) * nn * 8, c.device)
+    try:                                            # the beams are complex64 whatever the data is
+        if was_raw:
+            acq.engine.set_input_format(False)
+        for k0 in range(0, len(out), BEAM_MAX):
+            sel = slice(k0, min(k0 + BEAM_MAX, len(out)))
+            ns.beams_dev(dev[0], rows.ptr, nb, steer[sel], nulls, mask[sel], in_stride=n, out_stride=nn)
+            st['beams_ms'] += ns.last_ms()
+            st['device_ms'] += ns.last_ms()
+            st['beam_kernel_ms'] = ns.last_beam_kernel_ms()
+            flags, gain, w = ns.last_beam_flags, ns.last_beam_gain_db, ns.last_beam_weights
+            for j, r in enumerate(range(sel.start, sel.stop)):
+                row = (rows.at(j * nn * 8), nn)
+                f1, rec1, ms = refine_centred(acq, row, [found[r]], f_offset=f_offset, df_half=float(step))
+                st['device_ms'] += ms
+                rec1, _, out1 = refined_records(rec1, f1, cs, f_offset)
+                entry = {'prn': int(out['prn'][r]), 'null': bool(mask[r]), 'confirmed': len(out1) == 1,
+                         'gain_db': float(np.mean(gain[:, j])), 'flags': sorted(set(flags[:, j].tolist())),
+                         'weights': w[:, j].copy()}
+                st['beams'].append(entry)
+                if len(out1) != 1:                  # not confirmed on its beam: the antenna-0 values stay
+                    continue
+                if source == 'track':
+                    _track_records(acq, row, rec1, out1, nn, f_offset, track_cfg, st)
+                out[r] = out1[0]
+    finally:
+        if was_raw:
+            acq.engine.set_input_format(True)
+        rows.free()
+        ns.close()
+
+
 def authentic_first(report):
     """With a verdict (spoof_resolve) the authentic fix goes first in report.fixes, whatever order
     twin_fixes gave them; sets and one_source follow and authentic becomes 0.  -> fixes[0]."""
@@ -605,7 +720,7 @@ def _track_records(acq, dev, rec, out, n, f_offset, track_cfg, st):
 
 
 def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=None, spoof=False, antennas=None,
-            **cfg):
+            beams=False, **cfg):
     """The satellites of one snapshot: MEAS_DTYPE records, one per satellite found, sorted by PRN.
 
     `acq`: an acquisition.Acquisition; `data`: the samples in its input format (complex64, or the
@@ -637,7 +752,15 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
     (pointer, n) with A rows n samples apart behind the pointer.  Every stage above reads row 0, the
     first n samples, exactly as without the option; after spoof_keep (and tracking) the kept records'
     signatures are taken once over all rows (Acquisition.signatureHits) and spoof_resolve fills the
-    report's signature, quality, rho and one_direction; stats receives signature_ms."""
+    report's signature, quality, rho and one_direction; stats receives signature_ms.
+    `beams` (with `antennas` only): after the signatures one nulling.NullSteer of
+    cfg.ngps forms a beam per kept record (beam_plan: steered at the record's signature, with a null
+    at the spoofer's pooled signature where one_source finds a set and the null costs at most 3 dB)
+    over the n // ngps whole blocks of the snapshot -- the tail is not beamed -- and every record is
+    refined again on its own row from its own hit and, with source 'track', tracked there; a record
+    whose re-refinement is not confirmed keeps its antenna-0 values.  stats receives beams_ms,
+    before_beams (the records as they were) and beams (per record: prn, null carried, confirmed,
+    mean gain_db, the flags seen, the weights [blocks][A]).  Without the option nothing of this runs."""
     from .acquisition import SAT_ALL
     from .engine import CANCEL_OUT_DTYPE, DeviceBuffer
     c = acq.cfg
@@ -657,6 +780,8 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
         antennas = int(antennas)
         if not 2 <= antennas <= 8:
             raise ValueError('antennas must be 2 .. 8')
+    elif beams:
+        raise ValueError('beams goes with antennas=A (the beams combine the antennas)')
     if freqs is None:
         freqs = [c.min_freq + c.step_freq * i for i in range(int(round((c.max_freq - c.min_freq) / c.step_freq)))]
     prns = list(SAT_ALL if prns is None else prns)
@@ -693,6 +818,9 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
                     st['device_ms'] += st['signature_ms']
                     v, report.quality = signature_vectors(cov)
                     spoof_resolve(report, out, None, v)
+                    if beams:
+                        _beam_pass(acq, dev, n, found, out, cov, v, report.rho, antennas, source, freqs, f_offset,
+                                   track_cfg, st)
                 else:
                     st['signature_ms'] = 0.0
             st['spoof'] = report
@@ -978,7 +1106,7 @@ def _collective_fix(acq, data, ephs, t_gps, pos, f_offset, cfg, stats):
 
 
 def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, cancel=None, stats=None,
-                 collective=None, collective_cfg=None, spoof=False, antennas=None, **cfg):
+                 collective=None, collective_cfg=None, spoof=False, antennas=None, beams=False, **cfg):
     """measure -> (doppler_fix when `pos` is None) -> coarse_time_fix.  `t_gps`: the GPS seconds
     of week of the first sample as far as known; `cancel`, `stats`: measure's.  -> (Fix,
     measurements, device ms).  The Fix's t_gps is that of its `sample`.
@@ -997,7 +1125,9 @@ def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, ca
     spoof_resolve on the records' signatures; with a verdict the authentic fix goes first
     (fixes[0], the returned Fix, report.authentic 0) whatever the a-priori or the C/N0 say, without
     one the order of twin_fixes stands.  report.one_direction raises the alarm without a doubled
-    PRN."""
+    PRN.
+    `beams` (with `antennas` only): measure's -- the records the fixes are made of
+    were measured on their own beams."""
     if collective not in (None, False, True, 'always'):
         raise ValueError(f"collective {collective!r}: None, False, True or 'always'")
     if collective and pos is None:
@@ -1006,11 +1136,14 @@ def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, ca
         raise ValueError('spoof and collective are not combined')
     if antennas is not None and not spoof:
         raise ValueError('antennas goes with spoof=True (the signatures serve the spoofing check)')
+    if beams and antennas is None:
+        raise ValueError('beams goes with antennas=A (the beams combine the antennas)')
     stats = {} if stats is None else stats
     report = None
     if spoof:
         meas, report = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats,
-                               cancel=cancel, spoof=True, antennas=antennas, **cfg)
+                               cancel=cancel, spoof=True, antennas=antennas, **({'beams': True} if beams else {}),
+                               **cfg)
     else:
         meas = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats, cancel=cancel,
                        **cfg)

@@ -1156,6 +1156,72 @@ int gpsmi_nul_last_ms(gpsmi_nul* h, float* ms);
 /* device time of the three kernels of the last finished call: ms[0] covariance, ms[1] solve, ms[2] apply */
 int gpsmi_nul_last_kernel_ms(gpsmi_nul* h, float* ms);
 
+/* ------------------------------------------------------------------------
+ * Per-satellite beams on the same handle (restatement: tests/beam_ref.py).  Where
+ * gpsmi_nul_apply holds antenna 0 at one and knows no direction, a beam holds a given steering vector
+ * s at one (w^H s = 1), holds up to four given null vectors u_q at zero (w^H u_q = 0) and minimises
+ * the output power under those constraints: w = R^-1 G (G^H R^-1 G)^-1 e0, G = [s, u_q ...].  One call
+ * forms nbeam beams from the same A rows: the samples are read once.  The handle must have been made
+ * with taps 0 or 1 (a space-time handle: GPSMI_E_STATE); nothing of gpsmi_nul_apply changes, and a
+ * beams call leaves the results of the last gpsmi_nul_apply call alone.
+ *   input      A rows of nb blocks of n = block_samples samples in the handle's input format; row a
+ *              starts a * in_stride samples behind row 0 (gpsmi_nul_beams_dev; 0 means nb * n, the
+ *              layout of gpsmi_nul_apply and of the host entry);
+ *   output     nbeam rows of nb * n complex64 samples, row b at b * out_stride samples (0: nb * n);
+ *   beams      nbeam 1 .. 64; steer float64 [nbeam][A][2] (re, im); nulls float64 [nnull][A][2],
+ *              nnull 0 .. 4, shared by the beams; null_mask uint32 [nbeam], bit q set: beam b carries
+ *              null q (null_mask may be a null pointer when nnull is 0).  A beam has
+ *              m = 1 + popcount(null_mask[b]) <= A constraints, G's columns: s_b, then its nulls in
+ *              ascending q.
+ * Every block is worked on alone, in float64, nothing fused, complex products and conj() as above:
+ *   covariance, loading, Cholesky   C, R = C / n + delta I and R = L L^H exactly as gpsmi_nul_apply
+ *              forms them, with the handle's load (min_gain_db plays no part).  A pivot that is not
+ *              positive and finite (an all-zero block): L = I in everything below, the beam is the
+ *              quiescent one, flag 0; else flag 1;
+ *   columns    z = L^-1 g for every column g of G, forward: z[i] = (g[i] - sum_{k<i} L[i][k] z[k]) /
+ *              L[i][i], the terms subtracted one at a time in ascending k;
+ *   M = Z^H Z  M[i][j] = sum_a conj(z_i[a]) z_j[a] for i > j, from 0 + 0j in ascending a, one complex
+ *              add per term; M[i][i] = sum_a (re^2 + im^2) of z_i[a], from 0 in ascending a;
+ *   M q = e0   M = K K^H by the Cholesky above (m for A), K y = e0 forward and K^H q = y backward as
+ *              above.  A pivot of M that is not positive and finite: flag -1, the beam's block of
+ *              output is +0.0 + 0.0j, its weights are 0 and gain_db is 0;
+ *   weights    t[a] = sum_j z_j[a] q[j], from 0 + 0j in ascending j; L^H w = t backward:
+ *              w[i] = (t[i] - sum_{k>i} conj(L[k][i]) w[k]) / L[i][i], i descending, k ascending.
+ *              Then w^H s = 1 and w^H u_q = 0 to rounding, and the output power w^H R w is p = Re q[0];
+ *   gain       gain_db = (float)(10 log10(tr / (|s|^2 p))), tr = sum_a C[a][a] / n as in the loading
+ *              (without delta), |s|^2 = sum_a (re^2 + im^2) from 0 in ascending a: the mean antenna
+ *              power over the output power referred to one antenna; 10 log10 A in white noise;
+ *   apply      w32 = complex64(w), y_b[i] = sum_a conj(w32_b[a]) x_a[i] in float32, exactly the apply
+ *              of gpsmi_nul_apply.
+ * flags int32 [nb][nbeam], gain_db float32 [nb][nbeam] and weights float64 [nb][nbeam][A][2] are host
+ * arrays, each may be null.  The bytes of a beam's block depend on that block and that beam (its
+ * steering vector, its null vectors, the load) alone: not on nbeam, the other beams, the bits of
+ * null_mask beyond its own, nb, the cut of the input into calls, the strides or the entry point; u8
+ * input gives the bytes of its complex64 decode.  One thread writes each output word, no atomics;
+ * samples between the rows of a strided output are not touched.
+ * Argument errors are GPSMI_E_ARG and need no GPU; gpsmi_nul_beams_plan makes those of the beam
+ * description without a handle: a null pointer; nbeam, nnull or antennas out of range; a mask bit
+ * >= nnull; m > A; a vector that is zero or not finite; dependent constraints -- the Gram matrix of a
+ * beam's columns, each divided by its length, must have a float64 Cholesky whose every pivot (the
+ * value under the square root) is >= 1 / 64: for one null, |s^H u| / (|s| |u|) <= 0.992, beyond which
+ * the null costs more than 18 dB of noise gain.  On a handle also: nb <= 0; a stride below nb * n or
+ * negative; device rows that break the alignment of gpsmi_nul_apply_dev (16 bytes for complex64 input
+ * and the output, 4 for u8 input: strides must be even); an input row that overlaps an output row.
+ * A failed allocation is GPSMI_E_NOMEM and leaves the handle usable.
+ * ------------------------------------------------------------------------ */
+int gpsmi_nul_beams_plan(int antennas, int nbeam, const double* steer, int nnull, const double* nulls,
+                         const uint32_t* null_mask);
+/* host iq ([A][nb * n] in the input format) -> host out (complex64 [nbeam][nb * n])             */
+int gpsmi_nul_beams(gpsmi_nul* h, const void* iq, float* out, int nb, int nbeam, const double* steer,
+                    int nnull, const double* nulls, const uint32_t* null_mask, int32_t* flags,
+                    float* gain_db, double* weights);
+/* the same from device memory to device memory, strides in samples (the other arrays are host memory) */
+int gpsmi_nul_beams_dev(gpsmi_nul* h, const void* d_iq, int64_t in_stride, void* d_out, int64_t out_stride,
+                        int nb, int nbeam, const double* steer, int nnull, const double* nulls,
+                        const uint32_t* null_mask, int32_t* flags, float* gain_db, double* weights);
+/* device time of the three kernels of the last finished beams call: covariance, solve, apply   */
+int gpsmi_nul_last_beam_kernel_ms(gpsmi_nul* h, float* ms);
+
 /* ========================================================================
  * Time-frequency (sweep) excision: an opt-in input stage against swept and chirp interference, for
  * one antenna, ahead of acquisition and tracking (float64 restatement:

@@ -7,7 +7,7 @@ gpseval) as one command on the GPU path.
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--sweep [L]] [--blank] [--json]
                              [--antenna FILE ... --null [--null-taps T]]
                              [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track [--weak-fix]]]]
-                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]] [--spoof-check [K]] [--antenna FILE ...]]]
+                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]] [--spoof-check [K]] [--antenna FILE ... [--beams]]]]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -80,7 +80,10 @@ antenna which fix is authentic is not decided, and the exit status is 0 either w
 (without --null) every file gives one further row of the snapshot of a coherent multi-antenna recorder: every
 record gets a spatial signature over the antennas, the set of doubled records that all arrive from one direction
 is the spoofer's, and the report names the authentic fix (first) and says whether every signal arrives from one
-direction ('authentic', 'one_source', 'one_direction').
+direction ('authentic', 'one_source', 'one_direction').  --beams on top of that measures every
+record again on a beam of its own over the antennas, steered at its signature and with a null at the spoofer
+where one is found and the null costs at most 3 dB; the report gains a 'beams' entry with one line per record
+(the null, the predicted gain, C/N0 on antenna 0).
 
 There is no recording in this repository (data/test.bin is absent from the reference
 checkout, SURVEY F2, and too short for a fix even upstream): tests/test_run_file.py writes a
@@ -273,7 +276,7 @@ def parse_time(text, ephs):
 
 
 def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, frontend=None, excise=False,
-             blank=False, cancel=None, collective_km=None, spoof_k=None, antennas=()):
+             blank=False, cancel=None, collective_km=None, spoof_k=None, antennas=(), beams=False):
     """--snapshot: gpsmi.snapshot.snapshot_fix on the first `seconds` behind `start_stream`, read
     and filtered block by block as run() feeds its receiver.  `cancel`: --cancel's C/N0 threshold
     (snapshot.measure's `cancel`); None leaves everything as it is without the flag.
@@ -281,7 +284,9 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
     `spoof_k`: --spoof-check's doubled PRNs that raise the alarm (snapshot_fix's spoof=True); None: not asked for.
     `antennas` (with `spoof_k`): the files of the further channels of a coherent recorder; every file gives one
     row of the snapshot, `path` the first, and the spoofing check names the authentic fix from the records'
-    spatial signatures (snapshot_fix's antennas=A)."""
+    spatial signatures (snapshot_fix's antennas=A).
+    `beams` (with `antennas`): --beams, every record is measured again on a beam of its own over the antennas, with
+    a null at the spoofer where one is found (snapshot_fix's beams=True)."""
     from gpsmi import ingest, position as P, snapshot as S
     from gpsmi.acquisition import Acquisition
     from gpsmi.conditioning import Conditioner
@@ -311,6 +316,7 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
                                            cancel=cancel, stats=stats,
                                            **({} if spoof_k is None else {'spoof': True, 'min_doubled': spoof_k}),
                                            **({'antennas': 1 + len(antennas)} if antennas else {}),
+                                           **({'beams': True} if beams else {}),
                                            **({} if collective_km is None else
                                               {'collective': True, 'collective_cfg': {'radius_m': 1.0e3 * collective_km}}))
             wall = time.perf_counter() - t0
@@ -356,6 +362,14 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
                        'one_direction': bool(rep is not None and rep.one_direction),
                        'signature_ms': round(float(stats.get('signature_ms', 0.0)), 3)})
         out['spoof'] = sp
+    if beams:
+        before = stats.get('before_beams')
+        out['beams'] = {'beams_ms': round(float(stats.get('beams_ms', 0.0)), 3),
+                        'records': [{'prn': b['prn'], 'null': b['null'], 'confirmed': b['confirmed'],
+                                     'gain_db': round(b['gain_db'], 2), 'flags': b['flags'],
+                                     'cn0_before_dbhz': None if np.isnan(before['cn0_dbhz'][i])
+                                     else round(float(before['cn0_dbhz'][i]), 2)}
+                                    for i, b in enumerate(stats.get('beams', []))]}
     if cancel is not None:
         out['cancelled'] = [{'prn': int(r['prn']), 'n_windows': int(r['n_windows']), 'n_skipped': int(r['n_skipped']),
                              'removed': round(float(r['energy_removed'] / r['energy_in']), 5) if r['energy_in'] > 0 else 0.0}
@@ -409,6 +423,14 @@ def print_snapshot(out):
                       f"not decided here")
         if 'antennas' in sp:
             print(f"  one direction for every signal over {sp['antennas']} antennas: {'YES' if sp['one_direction'] else 'no'}")
+    bm = s.get('beams')
+    if bm is not None:
+        print(f"  beams over the antennas ({bm['beams_ms']} ms on the device), one per record:")
+        for b in bm['records']:
+            was = 'n/a' if b['cn0_before_dbhz'] is None else f"{b['cn0_before_dbhz']:.1f}"
+            print(f"  beam PRN {b['prn']:2d}  {'null at the spoofer' if b['null'] else 'no null':19s}  gain {b['gain_db']:5.2f} dB  "
+                  f"flags {b['flags']}  cn0_dbhz on antenna 0 {was}  "
+                  f"{'measured on the beam' if b['confirmed'] else 'not confirmed on the beam: antenna-0 values kept'}")
     for m in s['measurements']:
         cn0 = 'n/a' if m['cn0_dbhz'] is None else f"{m['cn0_dbhz']:.1f}"
         print(f"  PRN {m['prn']:2d}  sample {m['sample']:8d}  code_phase {m['code_phase']:9.4f}  f_hz {m['f_hz']:+9.2f}  "
@@ -593,6 +615,9 @@ def main():
     ap.add_argument('--null-taps', type=int, default=1, choices=(1, 3, 5, 7), metavar='T',
                     help='with --null: T = 3, 5 or 7 space-time taps per antenna instead of one weight, against '
                          'delay and filter mismatch between the channels and dense tone fields')
+    ap.add_argument('--beams', action='store_true',
+                    help='with --snapshot --spoof-check --antenna FILE ...: measure every record again on a beam of '
+                         'its own over the antennas, with a null at the spoofer where one is found (DESIGN.md 4.2q)')
     ap.add_argument('--json', action='store_true', help='one JSON line instead of text')
     a = ap.parse_args()
     if a.refine and not a.deep_acq:
@@ -625,8 +650,10 @@ def main():
                           or a.blank or len(a.antenna) > 7):
             ap.error('--antenna FILE with --snapshot: up to seven further channels, with --spoof-check, in the '
                      'recorder\'s own format, without --null / --null-taps / --excise / --blank')
+        if a.beams and not a.antenna:
+            ap.error('--beams needs --antenna FILE ... (the beams combine the antennas)')
         out = snapshot(a.recording, a.snapshot, eph, parse_time(a.time, eph), near, a.start_stream, frontend,
-                       a.excise, a.blank, a.cancel, a.collective, a.spoof_check, a.antenna)
+                       a.excise, a.blank, a.cancel, a.collective, a.spoof_check, a.antenna, a.beams)
         if a.json:
             print(json.dumps(out))
         else:
@@ -634,6 +661,8 @@ def main():
         return
     if a.time is not None or a.near is not None:
         ap.error('--time / --near need --snapshot SECONDS')
+    if a.beams:
+        ap.error('--beams needs --snapshot SECONDS')
     if bool(a.antenna) != a.null:
         ap.error('--antenna FILE (the further channels) and --null go together')
     if a.null_taps != 1 and not a.null:
