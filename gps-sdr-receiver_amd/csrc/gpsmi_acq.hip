@@ -17,6 +17,8 @@
 //                         spoofing check (gpsmi_acq_peaks)
 //   gpsmi_sig.h           spatial signatures of refined records over several antennas
 //                         (gpsmi_acq_signature): prompts per antenna, their covariance
+//   gpsmi_profile.h       multi-tap correlation profiles of refined records on one antenna
+//                         (gpsmi_acq_profile): bit-coherent sums per tap, their covariance
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -34,6 +36,7 @@
 #include "gpsmi_collective.h"
 #include "gpsmi_peaks.h"
 #include "gpsmi_sig.h"
+#include "gpsmi_profile.h"
 #include "gpsmi_acq_search.h"
 
 using namespace gpsmi;
@@ -102,6 +105,11 @@ struct gpsmi_acq {
     DevBuf<float2> d_sp;
     DevBuf<char> d_st;
     DevBuf<double> d_sc;
+    // profiles (gpsmi_acq_profile): the sums [nsat][K][max_runs], the records and the window starts of
+    // a call in one block, the covariances [nsat][K][K][2]
+    DevBuf<float2> d_ps;
+    DevBuf<char> d_pt;
+    DevBuf<double> d_pc;
     int iq_fmt = GPSMI_IQ_C64;              // what the iq pointers of the search calls point to
     // bytes of `n` samples in the handle's input format
     size_t iq_bytes(size_t n) const { return n * (iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)); }
@@ -845,6 +853,70 @@ int gpsmi_acq_signature_plan(int code_samples, size_t n, const gpsmi_sig_sat* sa
     if (n_win)
         for (int s = 0; s < nsat; ++s) n_win[s] = pl.recs[s].n_win;
     if (max_windows) *max_windows = pl.max_windows;
+    return GPSMI_OK;
+}
+
+// ---- multi-tap correlation profiles (kernels and plan: gpsmi_profile.h) -----------------------
+static int acq_profile_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n, const gpsmi_prof_sat* sats,
+                            int nsat, const gpsmi_prof_cfg* cfg, double* cov, int32_t* n_runs, float* sums) {
+    GPSMI_REQUIRE(h && iq && sats && cov && n_runs, "null argument");
+    ProfPlan pl;
+    int rc = prof_plan(h->cfg.code_samples, n, sats, nsat, cfg, &pl);
+    if (rc) return rc;
+    const void* d_iq;
+    if ((rc = acq_need_time(h, "gpsmi_acq_profile", nsat, [&](int i) { return sats[i].prn; })) ||
+        (rc = acq_enter(h)) || (rc = acq_input(h, iq, on_host, n, &d_iq)))
+        return rc;
+    const int cs = pl.cs, Lh = pl.Lh, K = 2 * pl.Lh + 1, mr = pl.max_runs;
+    // the tables of the call, 8-byte items first
+    const size_t b_start = pl.start.size() * sizeof(long long), b_rec = (size_t)nsat * sizeof(ProfRec);
+    const size_t ns = (size_t)nsat * K * mr, nc = (size_t)nsat * K * K * 2;
+    if ((rc = h->d_pt.reserve(b_start + b_rec, "gpsmi_acq_profile tables")) ||
+        (rc = h->d_ps.reserve(ns, "gpsmi_acq_profile sums")) ||
+        (rc = h->d_pc.reserve(nc, "gpsmi_acq_profile covariances")))
+        return rc;
+    long long* d_start = reinterpret_cast<long long*>(h->d_pt.p);
+    ProfRec* d_rec = reinterpret_cast<ProfRec*>(h->d_pt.p + b_start);
+    GPSMI_HIP(hipMemsetAsync(h->d_ps.p, 0, ns * sizeof(float2), h->stream));
+    if ((rc = acq_tables(h, {{d_start, pl.start.data(), b_start}, {d_rec, pl.recs.data(), b_rec}})) ||
+        (rc = acq_begin(h)))
+        return rc;
+    const dim3 gp(mr, nsat);
+    with_fmt(h->iq_fmt, [&](auto fmt) {
+        with_value<8, kProfMaxHalf>(Lh <= 8 ? 8 : kProfMaxHalf, [&](auto lh) {
+            hipLaunchKernelGGL((prof_sum_kernel<decltype(fmt)::value, decltype(lh)::value>), gp, dim3(256), 0,
+                               h->stream, d_iq, h->d_rep_time.p, d_rec, d_start, cs, Lh, pl.coh, mr, h->d_ps.p);
+        });
+    });
+    hipLaunchKernelGGL(prof_cov_kernel, dim3(nsat), dim3(256), 0, h->stream, h->d_ps.p, d_rec, K, mr, h->d_pc.p);
+    if ((rc = acq_end(h))) return rc;
+    GPSMI_HIP(hipMemcpyAsync(cov, h->d_pc.p, nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (sums)
+        GPSMI_HIP(hipMemcpyAsync(sums, h->d_ps.p, ns * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = gpsmi_acq_wait(h))) return rc;
+    for (int s = 0; s < nsat; ++s) n_runs[s] = pl.recs[s].n_runs;
+    return GPSMI_OK;
+}
+
+int gpsmi_acq_profile(gpsmi_acq* h, const void* iq, size_t n, const gpsmi_prof_sat* sats, int nsat,
+                      const gpsmi_prof_cfg* cfg, double* cov, int32_t* n_runs, float* sums) {
+    return acq_profile_impl(h, iq, true, n, sats, nsat, cfg, cov, n_runs, sums);
+}
+
+int gpsmi_acq_profile_dev(gpsmi_acq* h, const void* d_iq, size_t n, const gpsmi_prof_sat* sats, int nsat,
+                          const gpsmi_prof_cfg* cfg, double* cov, int32_t* n_runs, float* sums) {
+    return acq_profile_impl(h, d_iq, false, n, sats, nsat, cfg, cov, n_runs, sums);
+}
+
+int gpsmi_acq_profile_plan(int code_samples, size_t n, const gpsmi_prof_sat* sats, int nsat,
+                           const gpsmi_prof_cfg* cfg, int32_t* n_runs, int* max_runs, int* taps) {
+    ProfPlan pl;
+    const int rc = prof_plan(code_samples, n, sats, nsat, cfg, &pl);
+    if (rc != GPSMI_OK) return rc;
+    if (n_runs)
+        for (int s = 0; s < nsat; ++s) n_runs[s] = pl.recs[s].n_runs;
+    if (max_runs) *max_runs = pl.max_runs;
+    if (taps) *taps = 2 * pl.Lh + 1;
     return GPSMI_OK;
 }
 

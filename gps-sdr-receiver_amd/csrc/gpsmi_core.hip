@@ -153,6 +153,8 @@ int gpsmi_abi_sizeof(int which) {
         case 25: return (int)sizeof(gpsmi_peaks_pick);
         case 27: return (int)sizeof(gpsmi_sig_sat);   // (26 stays unused as well)
         case 28: return (int)sizeof(gpsmi_sig_cfg);
+        case 29: return (int)sizeof(gpsmi_prof_sat);
+        case 30: return (int)sizeof(gpsmi_prof_cfg);
         default: return -1;
     }
 }

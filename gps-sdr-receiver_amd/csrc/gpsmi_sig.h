@@ -155,6 +155,15 @@ struct SigPlan {
     std::vector<long long> start;                 // [nsat][max_windows], 0 past a record's last window
 };
 
+// the first k with lo <= j_k = rint(tau + k Tc) (cancellation's edges: float64, unfused); shared with
+// the profiles (gpsmi_profile.h), whose windows keep lo = half_taps samples in hand
+inline long long sig_first_window(double tau, double Tc, int lo) {
+    long long k = (long long)std::floor(((double)lo - tau) / Tc);
+    while (std::nearbyint(cancel_edge(tau, Tc, k)) >= (double)lo) --k;
+    while (std::nearbyint(cancel_edge(tau, Tc, k)) < (double)lo) ++k;
+    return k;
+}
+
 #define SIG_REQUIRE(cond, msg)                                                             \
     do {                                                                                   \
         if (!(cond)) return ::gpsmi::fail(GPSMI_E_ARG, "gpsmi_acq_signature: %s", msg);    \
@@ -201,10 +210,7 @@ inline int sig_plan(int cs, size_t n, const gpsmi_sig_sat* sats, int nsat, const
         const double scale = 1.0 + (g.f_hz - f_offset) / carrier;
         SIG_REQUIRE(scale > 0.99 && scale < 1.01, "f_hz - f_offset_hz beyond 1 % of carrier_hz");
         const double Tc = (double)cs / scale;
-        // the first k with 0 <= j_k = rint(tau + k Tc) (cancellation's edges: float64, unfused)
-        long long k = (long long)std::floor(-g.tau / Tc);
-        while (std::nearbyint(cancel_edge(g.tau, Tc, k)) >= 0.0) --k;
-        while (std::nearbyint(cancel_edge(g.tau, Tc, k)) < 0.0) ++k;
+        long long k = sig_first_window(g.tau, Tc, 0);
         try {
             for (;; ++k) {
                 const long long j = (long long)std::nearbyint(cancel_edge(g.tau, Tc, k));

@@ -96,6 +96,11 @@ class SigCfg(C.Structure):
                 ('f_offset_hz', C.c_double)]
 
 
+class ProfCfg(C.Structure):
+    _fields_ = [('half_taps', C.c_int32), ('coh_ms', C.c_int32), ('n_runs', C.c_int32), ('reserved', C.c_int32),
+                ('carrier_hz', C.c_double), ('f_offset_hz', C.c_double)]
+
+
 class Cfg(C.Structure):
     _fields_ = [('code_samples', C.c_int32), ('n_cyc', C.c_int32),
                 ('corr_avg', C.c_int32), ('sweep_corr_avg', C.c_int32),
@@ -123,6 +128,9 @@ CANCEL_OUT_DTYPE = np.dtype([('prn', np.int32), ('n_windows', np.int32), ('n_ski
                              ('energy_removed', np.float64)])
 
 SIG_SAT_DTYPE = np.dtype([('prn', np.int32), ('reserved', np.int32), ('f_hz', np.float64), ('tau', np.float64)])
+
+PROF_SAT_DTYPE = np.dtype([('prn', np.int32), ('skip_ms', np.int32), ('f_hz', np.float64), ('tau', np.float64)])
+PROF_MAX_HALF = 32            # kProfMaxHalf
 
 COLLECTIVE_SAT_DTYPE = np.dtype([('row', np.int32), ('bin_lo', np.int32), ('bin_hi', np.int32),
                                  ('reserved', np.int32), ('lag0', np.float64), ('g_e', np.float64),
@@ -192,6 +200,7 @@ EXPORTS = [
     'gpsmi_acq_track', 'gpsmi_acq_track_dev', 'gpsmi_acq_track_plan', 'gpsmi_wtrk_open',
     'gpsmi_acq_cancel', 'gpsmi_acq_cancel_dev', 'gpsmi_acq_cancel_plan',
     'gpsmi_acq_signature', 'gpsmi_acq_signature_dev', 'gpsmi_acq_signature_plan',
+    'gpsmi_acq_profile', 'gpsmi_acq_profile_dev', 'gpsmi_acq_profile_plan',
     'gpsmi_acq_last_ms',
     'gpsmi_trk_create', 'gpsmi_trk_destroy', 'gpsmi_trk_set_replica',
     'gpsmi_trk_open', 'gpsmi_trk_close', 'gpsmi_trk_get_state',
@@ -292,6 +301,9 @@ def load():
         'gpsmi_acq_signature': [vp, vp, sz, vp, C.c_int, P(SigCfg), vp, vp, vp],
         'gpsmi_acq_signature_dev': [vp, vp, sz, vp, C.c_int, P(SigCfg), vp, vp, vp],
         'gpsmi_acq_signature_plan': [C.c_int, sz, vp, C.c_int, P(SigCfg), vp, P(C.c_int)],
+        'gpsmi_acq_profile': [vp, vp, sz, vp, C.c_int, P(ProfCfg), vp, vp, vp],
+        'gpsmi_acq_profile_dev': [vp, vp, sz, vp, C.c_int, P(ProfCfg), vp, vp, vp],
+        'gpsmi_acq_profile_plan': [C.c_int, sz, vp, C.c_int, P(ProfCfg), vp, P(C.c_int), P(C.c_int)],
         'gpsmi_acq_last_ms': [vp, P(f32)],
         'gpsmi_trk_create': [P(Cfg), C.c_int, P(vp)],
         'gpsmi_trk_destroy': [vp],
@@ -390,7 +402,8 @@ def load():
            (13, CANCEL_SAT_DTYPE.itemsize), (14, C.sizeof(CancelCfg)), (15, CANCEL_OUT_DTYPE.itemsize),
            (17, COLLECTIVE_SAT_DTYPE.itemsize), (18, C.sizeof(CollectiveGrid)), (19, COLLECTIVE_CELL_DTYPE.itemsize),
            (21, C.sizeof(NulCfg)), (23, C.sizeof(TfxCfg)), (24, C.sizeof(PeaksCfg)), (25, PEAKS_PICK_DTYPE.itemsize),
-           (27, SIG_SAT_DTYPE.itemsize), (28, C.sizeof(SigCfg))]
+           (27, SIG_SAT_DTYPE.itemsize), (28, C.sizeof(SigCfg)),
+           (29, PROF_SAT_DTYPE.itemsize), (30, C.sizeof(ProfCfg))]
     want = [size for _, size in abi]
     got = [lib.gpsmi_abi_sizeof(i) for i, _ in abi]
     if want != got:

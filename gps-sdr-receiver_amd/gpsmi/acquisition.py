@@ -176,6 +176,16 @@ class Acquisition:
         Returns (cov complex128 [R][A][A], n_win)."""
         return self.engine.signatures(data, signature_sats(rec), antennas, f_offset=f_offset, **cfg)[:2]
 
+    def profileHits(self, data, rec, f_offset=0.0, **cfg):
+        """The multi-tap correlation profiles of the records `rec` (AcqEngine.profiles; DESIGN.md
+        4.2r): snapshot.MEAS_DTYPE records or records of refineHits (profile_sats: the runs start
+        at the record's bit edge), in the order given; a PRN may appear more than once.  `data`: one
+        row of samples on the host or a (device pointer, n) pair; `cfg`: half_taps, coh_ms, n_runs, carrier_hz.
+        Returns (cov complex128 [R][K][K], n_runs)."""
+        sats = profile_sats(rec, self.cfg.code_samples, cfg.get('half_taps', 0), f_offset,
+                            cfg.get('carrier_hz', L1_HZ))
+        return self.engine.profiles(data, sats, f_offset=f_offset, **cfg)[:2]
+
     def deepRows(self, data, prns, freqs, n_coh=4, n_seg=250, f_offset=0.0):
         """The deep surface kept whole (AcqEngine.search_deep with rows): the
         table of sweepDeepSats' search and a DeviceBuffer of float32 [len(prns)][len(freqs)]
@@ -203,6 +213,31 @@ def signature_sats(rec):
     start = rec['sample'].astype(np.float64) if 'sample' in rec.dtype.names else 0.0
     tau = start + rec['code_phase'].astype(np.float64)
     return [(int(rec['prn'][i]), float(rec['f_hz'][i]), float(tau[i])) for i in range(len(rec))]
+
+
+def profile_sats(rec, cs, half_taps=0, f_offset=0.0, carrier_hz=L1_HZ):
+    """(prn, skip_ms, f_hz, tau) of snapshot.MEAS_DTYPE records (a code start lies at sample +
+    code_phase, a bit starts at `edge`) or of records of refineHits (code start code_phase, a bit
+    starts edge_ms periods on), in the order given.  skip_ms counts the windows of
+    gpsmi_acq_profile -- the first is the first code start with half_taps samples ahead of it --
+    up to the first one that starts a bit; 0 where the record names no edge.  Host only."""
+    rec = np.atleast_1d(np.asarray(rec))
+    Lh = int(half_taps) or (8 if cs == 2048 else 32)
+    meas = 'sample' in rec.dtype.names
+    out = []
+    for r in rec:
+        f = float(r['f_hz'])
+        Tc = cs / (1.0 + (f - f_offset) / carrier_hz)
+        tau = float(r['sample']) + float(r['code_phase']) if meas else float(r['code_phase'])
+        edge = float(r['edge']) if meas else tau + float(r['edge_ms']) * Tc if r['edge_ms'] >= 0 else np.nan
+        k = int(np.floor((Lh - tau) / Tc))
+        while np.rint(tau + float(k) * Tc) >= Lh:
+            k -= 1
+        while np.rint(tau + float(k) * Tc) < Lh:
+            k += 1
+        skip = (int(np.rint((edge - tau) / Tc)) - k) % 20 if np.isfinite(edge) else 0
+        out.append((int(r['prn']), skip, f, tau))
+    return out
 
 
 def hit_at(rec, sample, cfg, carrier_hz=L1_HZ):

@@ -202,6 +202,30 @@ def signature_plan(code_samples, n, sats, antennas, n_ms=0, f_offset=0.0, carrie
     return n_win[:len(s_a)], max_w.value
 
 
+def _prof_args(sats, half_taps, coh_ms, n_runs, f_offset, carrier_hz):
+    """The records and the options of a profile call (gpsmi_prof_sat [R], gpsmi_prof_cfg)."""
+    s_a = np.zeros(len(sats), dtype=_lib.PROF_SAT_DTYPE)
+    for i, (prn, skip_ms, f_hz, tau) in enumerate(sats):
+        s_a[i] = (int(prn), int(skip_ms), float(f_hz), float(tau))
+    return s_a, _lib.ProfCfg(int(half_taps), int(coh_ms), int(n_runs), 0, float(carrier_hz), float(f_offset))
+
+
+def _prof_plan(lib, code_samples, n, s_a, cfg):
+    n_runs = np.zeros(max(len(s_a), 1), np.int32)
+    max_r, taps = C.c_int(0), C.c_int(0)
+    check(lib.gpsmi_acq_profile_plan(int(code_samples), int(n), ptr(s_a), len(s_a), C.byref(cfg), ptr(n_runs),
+                                     C.byref(max_r), C.byref(taps)), 'gpsmi_acq_profile_plan')
+    return n_runs[:len(s_a)], max_r.value, taps.value
+
+
+def profiles_plan(code_samples, n, sats, half_taps=0, coh_ms=0, n_runs=0, f_offset=0.0, carrier_hz=1575.42e6):
+    """gpsmi_acq_profile_plan: the argument checks of AcqEngine.profiles without a GPU, for `n`
+    samples.  sats: [(prn, skip_ms, f_hz, tau)].  -> (n_runs int32 [R], max_runs, taps K);
+    EngineError where the call would refuse."""
+    s_a, cfg = _prof_args(sats, half_taps, coh_ms, n_runs, f_offset, carrier_hz)
+    return _prof_plan(_lib.load(), code_samples, n, s_a, cfg)
+
+
 def _iq_dtype(raw_u8):
     """What a handle's input format holds per sample: the recorder's uint16 (Q << 8 | I) or complex64."""
     return np.uint16 if raw_u8 else np.complex64
@@ -518,6 +542,32 @@ class AcqEngine:
         fn, name = self._export('gpsmi_acq_signature', host)
         check(fn(self.h, d_iq, n, ptr(s_a), len(s_a), C.byref(cfg), ptr(cov), ptr(n_win), ptr(pr)), name)
         return (cov, n_win, pr) if prompts else (cov, n_win)
+
+    def profiles(self, data, sats, half_taps=0, coh_ms=0, n_runs=0, f_offset=0.0, carrier_hz=L1_HZ, sums=False):
+        """Multi-tap correlation profiles on one antenna (gpsmi_acq_profile): per
+        record of `sats` -- (prn, skip_ms, f_hz, tau), f_hz and tau as in signatures, skip_ms the
+        windows dropped up to the bit edge; a PRN may appear more than once -- the correlation at
+        the whole-sample lags -half_taps .. +half_taps around the code start, summed coherently over
+        runs of coh_ms windows, and the covariance of those sums over the taps.  data: a host array
+        of n samples in the input format, or a (device pointer, n) pair.  0 for an option: its
+        default (8 taps either side at 2048, 32 at 16368; 20 ms; every run that fits).
+        Returns (cov complex128 [R][K][K], n_runs int32 [R]) and with sums=True the sums complex64
+        [R][K][max_runs] behind them (zero past a record's last run)."""
+        s_a, cfg = _prof_args(sats, half_taps, coh_ms, n_runs, f_offset, carrier_hz)
+        self._need_time_replicas(s_a['prn'])
+        if isinstance(data, tuple):
+            d_iq, n, host = data[0], int(data[1]), False
+        else:
+            row = self._host_iq(data)
+            if row.ndim != 1:
+                raise ValueError('data must be one row of samples')
+            d_iq, n, host = ptr(row), row.shape[0], True
+        runs, max_r, K = _prof_plan(self.lib, self.cfg.code_samples, n, s_a, cfg)
+        cov = np.zeros((len(s_a), K, K), np.complex128)
+        sm = np.zeros((len(s_a), K, max_r), np.complex64) if sums else None
+        fn, name = self._export('gpsmi_acq_profile', host)
+        check(fn(self.h, d_iq, n, ptr(s_a), len(s_a), C.byref(cfg), ptr(cov), ptr(runs), ptr(sm)), name)
+        return (cov, runs, sm) if sums else (cov, runs)
 
     def search_async(self, d_iq, n, prns, freqs, n_avg, out, out_dev=None):
         """Enqueue a search on device-resident iq; `out` is a pinned PEAK_DTYPE

@@ -23,6 +23,7 @@ outside the region around it.  Six leave one degree of freedom: a solution that 
 residual test is refused; one bad satellite is dropped only from seven on.  Every fix carries
 `protect_m`, the position error one bad measurement could cause without failing the test.
 """
+import functools
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -396,6 +397,9 @@ class SpoofReport:
     one_source: tuple = (False, False)              # per set of `sets`: its doubled records arrive from one direction
     one_direction: bool = False                     # SPOOF_DIRECTION_PRNS or more PRNs, every record from one direction
     authentic: object = None                        # 0 or 1 into `fixes`; None without a verdict
+    profile_t: object = None                        # float64 [records]: ProfileFit.T per record (None without profile=True)
+    distorted: list = field(default_factory=list)   # PRNs with a record whose profile needs a second path
+    profile: list = None                            # ProfileFit per record
 
 
 def spoof_keep(rec, found, cs, f_offset=0.0, min_doubled=SPOOF_MIN_DOUBLED):
@@ -419,6 +423,167 @@ def spoof_keep(rec, found, cs, f_offset=0.0, min_doubled=SPOOF_MIN_DOUBLED):
     report.alarm = len(report.doubled) >= min_doubled
     keep = np.array(keep, dtype=np.int64)
     return rec[keep], [found[i] for i in keep], out[keep], report
+
+
+# ---------------------------------------------------------------- correlation profiles
+# the least T (ProfileFit) at which a record's profile counts as distorted.  Measured on the CPU through
+# the restated chain (tests/test_profile.py: test_snapshot_spoof.py's chain, then tests/profile_ref.py on
+# its records): the eight records of the clean strong scene read T = 1.88 .. 5.59 (the strong satellites'
+# cross-correlations and what the one-path model leaves of the sub-sample sweep; white noise alone gives
+# about 1), the sixteen of the 30-us spoofed scene 1.42 .. 3.86 (the copies lie 52 .. 67 lags away, outside
+# the taps).  Twice the largest: 2 x 5.59.  The lift-off scene (tests/liftoff_truth.py: copies 0.16 .. 1.94
+# samples behind the authentic codes, +3 dB) reads 325.6, 80.2 and 76.9 on the three PRNs whose copies lie
+# 1.8 samples or more away -- 29, 7.2 and 6.9 times the threshold -- 14.4 at 1.40 samples, and 4.1 .. 9.5
+# on the four whose copies lie within a sample (not flagged: within half a chip the sweep of a single path
+# and a second path look alike to whole-sample windows).  The MI355X path reads the same T to 8.1e-7
+# relative (tests/test_gpu_snapshot_profile.py)
+PROFILE_T_MIN = 11.2
+# the least snr1 at which a record's T counts: E1 over the noise of one run and dimension.  A record of
+# 33 dB-Hz summed over a 20-ms run reads 10^((33 - 17) / 10) = 40; below that the two delays are fitted to
+# noise as much as to the signal and the record is left to the peaks' check
+PROFILE_SNR1_MIN = 40.0
+PROFILE_STEP = 1.0 / 16.0                # the template grid at 2048: samples
+PROFILE_SPAN = 3.0                       # ... over +- this many samples
+PROFILE_ORTH_MIN = 1.0e-6                # a second delay's part orthogonal to the first, of its norm
+PROFILE_SMEAR = 0.5                      # samples a single path's delay may lie off the best one: whole-sample windows
+PROFILE_RANK = 3                         # directions of the one-path model: the template, its slope, its curvature
+
+
+@dataclass
+class ProfileFit:
+    """profile_fit's result for one record.  T: the energy a second code replica picks up beyond the
+    best single one, over the noise per run and dimension (about 1 when one replica explains the
+    profile); snr1: the same for the best single replica.  d1, d2: the delays of the two replicas in
+    samples behind the window start (the record's own code start lies `frac` behind it); rel_power:
+    the second path's power over the first's in the two-column least squares."""
+    prn: int = 0
+    n_runs: int = 0
+    T: float = np.nan
+    snr1: float = np.nan
+    e1: float = np.nan
+    e2x: float = np.nan
+    sigma2: float = np.nan
+    d1: float = np.nan
+    d2: float = np.nan
+    frac: float = 0.0
+    rel_power: float = np.nan
+
+
+def _replica_f32(prn, cs):
+    from . import codes
+    return codes.code_replica(int(prn), cs).astype(np.float32).astype(np.float64)
+
+
+@functools.lru_cache(maxsize=64)
+def profile_noise(prn, cs, half_taps):
+    """N[l][l'] = r(l - l') / cs, r the autocorrelation of the sampled replica (the colour the taps of
+    white noise have), float64 [K][K], read-only."""
+    R = _replica_f32(prn, cs)
+    K = 2 * half_taps + 1
+    r = np.array([R[k:] @ R[:cs - k] for k in range(K)]) / cs
+    idx = np.abs(np.arange(K)[:, None] - np.arange(K)[None, :])
+    out = r[idx]
+    out.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=64)
+def profile_template(prn, cs, half_taps):
+    """The analytic template: g_d[l] = sum_i c(l + i - d) R[i], the continuous code c starting d
+    samples behind the window start against the sampled replica R.  c is the function R samples:
+    GPSCacode's own interpolant -- the chips doubled to 2046 knots, joined by straight lines, one
+    period over cs samples -- so that g_0 is the replica's own autocorrelation.  The grid is
+    d = -PROFILE_SPAN .. +PROFILE_SPAN in steps of PROFILE_STEP samples at 2048, both scaled by
+    cs / 2048 so that they cover the same chips at another rate.
+    -> (d float64 [nd], g float64 [nd][K]), read-only."""
+    from . import codes
+    R = _replica_f32(prn, cs)
+    y = np.repeat(codes.ca_chips(int(prn)).astype(np.float64), 2)     # 2046 knots, periodic
+    y = np.append(y, y[0])
+    knots_per_sample = (len(y) - 2.0) / (cs - 1.0)
+    scale = cs / 2048.0
+    nd_half = int(round(PROFILE_SPAN / PROFILE_STEP))
+    d = np.arange(-nd_half, nd_half + 1) * (PROFILE_STEP * scale)
+    K = 2 * half_taps + 1
+    u = np.arange(-half_taps, cs + half_taps, dtype=np.float64)
+    g = np.empty((len(d), K))
+    for q, dq in enumerate(d):
+        xk = np.mod((u - dq) * knots_per_sample, len(y) - 1.0)
+        j = np.minimum(np.floor(xk).astype(np.int64), len(y) - 2)
+        c = (y[j + 1] - y[j]) * (xk - j) + y[j]
+        g[q] = np.lib.stride_tricks.sliding_window_view(c, cs) @ R
+    d.setflags(write=False), g.setflags(write=False)
+    return d, g
+
+
+def profile_fit(cov, n_runs, prn, frac, cs, half_taps, template=None, smear=None):
+    """Does one code replica explain the profile covariance `cov` (complex [K][K] of one record of
+    AcqEngine.profiles over `n_runs` runs), or are two needed?  float64 numpy, DESIGN.md 4.2r:
+    Q is whitened by the Cholesky factor of profile_noise.  The best single template g_d over the
+    grid of delays gives d1.  One path: the windows start on whole samples, so under code Doppler a
+    single path's delay behind them sweeps +- half a sample within the second; the one-path model is
+    therefore the PROFILE_RANK leading directions of the templates within `smear` samples (default
+    PROFILE_SMEAR) of d1, and E1 the energy of Q in them (smear = 0: the one template, rank one).
+    Two paths: E2x, the largest energy the part of any g_d' orthogonal to that subspace picks up (a
+    d' whose orthogonal part is below PROFILE_ORTH_MIN of its norm is skipped).
+    sigma^2 = (tr Q - E1 - E2x) / ((K - rank - 1) n_runs); T = E2x / (n_runs sigma^2); snr1 =
+    E1 / (n_runs sigma^2).  `frac`: the record's code start behind its window start at sample 0
+    (tau - rint(tau)), carried into the result.  `template`: (d [nd], g [nd][K]) in place of
+    profile_template's -- the hook for a front end whose filter rounds the correlation peak.
+    -> ProfileFit."""
+    K = 2 * int(half_taps) + 1
+    Q = np.asarray(cov, dtype=np.complex128)
+    if Q.shape != (K, K):
+        raise ValueError(f'cov must be [{K}][{K}]')
+    d, g = profile_template(int(prn), int(cs), int(half_taps)) if template is None else template
+    d, g = np.asarray(d, dtype=np.float64), np.asarray(g, dtype=np.float64)
+    if g.shape != (len(d), K):
+        raise ValueError(f'template must be (d [nd], g [nd][{K}])')
+    smear = PROFILE_SMEAR if smear is None else float(smear)
+    Lc = np.linalg.cholesky(profile_noise(int(prn), int(cs), int(half_taps)))
+    Qw = np.linalg.solve(Lc, np.linalg.solve(Lc, Q).conj().T).conj().T          # L^-1 Q L^-H
+    Qw = 0.5 * (Qw + Qw.conj().T)
+    gw = np.linalg.solve(Lc, g.T).T                                              # [nd][K], real
+    nrm2 = np.einsum('dk,dk->d', gw, gw)
+    e = np.einsum('dk,kj,dj->d', gw, Qw, gw).real / nrm2
+    i1 = int(np.argmax(e))
+    near = gw[np.abs(d - d[i1]) <= smear + 1e-9]
+    rank = min(PROFILE_RANK, len(near)) if smear > 0 else 1
+    U = gw[i1][:, None] / np.sqrt(nrm2[i1]) if rank == 1 else np.linalg.svd(near.T, full_matrices=False)[0][:, :rank]
+    E1 = float(np.einsum('ka,kj,ja->', U, Qw, U).real)
+    orth = gw - (gw @ U) @ U.T
+    on2 = np.einsum('dk,dk->d', orth, orth)
+    ok = (on2 > PROFILE_ORTH_MIN ** 2 * nrm2) & (np.abs(d - d[i1]) > smear)      # (never d1 itself)
+    ok[i1] = False
+    e2 = np.full(len(d), -np.inf)
+    e2[ok] = np.einsum('dk,kj,dj->d', orth[ok], Qw, orth[ok]).real / on2[ok]
+    i2 = int(np.argmax(e2))
+    E2x = float(max(e2[i2], 0.0))
+    n_runs = int(n_runs)
+    sigma2 = (float(np.trace(Qw).real) - E1 - E2x) / ((K - rank - 1) * n_runs)
+    G = np.stack([gw[i1], gw[i2]], axis=1)                                       # two-column least squares
+    B = np.linalg.solve(G.T @ G, G.T)
+    P = np.einsum('ak,kj,aj->a', B, Qw, B).real
+    return ProfileFit(prn=int(prn), n_runs=n_runs, T=E2x / (n_runs * sigma2), snr1=E1 / (n_runs * sigma2), e1=E1,
+                      e2x=E2x, sigma2=sigma2, d1=float(d[i1]), d2=float(d[i2]), frac=float(frac),
+                      rel_power=float(P[1] / P[0]))
+
+
+def profile_verdict(report, meas, cov, n_runs, cs, half_taps, min_doubled=SPOOF_MIN_DOUBLED, template=None):
+    """profile_fit on every record of `meas` (cov [R][K][K], n_runs [R] of AcqEngine.profiles) into
+    report.profile and profile_t; report.distorted: the PRNs with a record whose T > PROFILE_T_MIN at an
+    snr1 of PROFILE_SNR1_MIN or more; the alarm is raised when the PRNs doubled or distorted count
+    `min_doubled`, and an alarm that stands already (doubled PRNs, one_direction) is never taken back."""
+    fits = []
+    for r in range(len(meas)):
+        tau = float(meas['sample'][r]) + float(meas['code_phase'][r])
+        fits.append(profile_fit(cov[r], n_runs[r], meas['prn'][r], tau - np.rint(tau), cs, half_taps, template))
+    report.profile = fits
+    report.profile_t = np.array([f.T for f in fits], dtype=np.float64)
+    report.distorted = sorted({f.prn for f in fits if f.T > PROFILE_T_MIN and f.snr1 >= PROFILE_SNR1_MIN})
+    # (on top of what is raised already: spoof_resolve's one_direction alarm stands)
+    report.alarm = report.alarm or len(set(report.doubled) | set(report.distorted)) >= min_doubled
+    return report
 
 
 def signature_vectors(cov):
@@ -720,7 +885,7 @@ def _track_records(acq, dev, rec, out, n, f_offset, track_cfg, st):
 
 
 def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=None, spoof=False, antennas=None,
-            beams=False, **cfg):
+            beams=False, profile=False, **cfg):
     """The satellites of one snapshot: MEAS_DTYPE records, one per satellite found, sorted by PRN.
 
     `acq`: an acquisition.Acquisition; `data`: the samples in its input format (complex64, or the
@@ -760,7 +925,13 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
     refined again on its own row from its own hit and, with source 'track', tracked there; a record
     whose re-refinement is not confirmed keeps its antenna-0 values.  stats receives beams_ms,
     before_beams (the records as they were) and beams (per record: prn, null carried, confirmed,
-    mean gain_db, the flags seen, the weights [blocks][A]).  Without the option nothing of this runs."""
+    mean gain_db, the flags seen, the weights [blocks][A]).  Without the option nothing of this runs.
+    `profile` (with `spoof` only): after spoof_keep (and tracking, signatures and
+    beams) every kept record's multi-tap correlation profile is taken on antenna 0
+    (Acquisition.profileHits: the default taps, 20-ms runs from the record's bit edge) and
+    profile_verdict fills the report's profile_t, distorted and profile; the alarm is then raised as
+    well when the PRNs doubled or distorted count `min_doubled` -- a copy within the guard of the peaks shows here.  stats receives
+    profile_ms.  Without the option nothing of this runs."""
     from .acquisition import SAT_ALL
     from .engine import CANCEL_OUT_DTYPE, DeviceBuffer
     c = acq.cfg
@@ -782,6 +953,8 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
             raise ValueError('antennas must be 2 .. 8')
     elif beams:
         raise ValueError('beams goes with antennas=A (the beams combine the antennas)')
+    if profile and not spoof:
+        raise ValueError('profile goes with spoof=True (the profiles serve the spoofing check)')
     if freqs is None:
         freqs = [c.min_freq + c.step_freq * i for i in range(int(round((c.max_freq - c.min_freq) / c.step_freq)))]
     prns = list(SAT_ALL if prns is None else prns)
@@ -823,6 +996,13 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
                                    track_cfg, st)
                 else:
                     st['signature_ms'] = 0.0
+            if profile:
+                st['profile_ms'] = 0.0
+                if len(out):
+                    pcov, runs = acq.profileHits((dev[0], n), out, f_offset=f_offset)
+                    st['profile_ms'] = acq.engine.last_ms()
+                    st['device_ms'] += st['profile_ms']
+                    profile_verdict(report, out, pcov, runs, cs, 8 if cs == 2048 else 32, min_doubled)
             st['spoof'] = report
             if stats is not None:
                 stats.update(st)
@@ -1106,7 +1286,8 @@ def _collective_fix(acq, data, ephs, t_gps, pos, f_offset, cfg, stats):
 
 
 def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, cancel=None, stats=None,
-                 collective=None, collective_cfg=None, spoof=False, antennas=None, beams=False, **cfg):
+                 collective=None, collective_cfg=None, spoof=False, antennas=None, beams=False, profile=False,
+                 **cfg):
     """measure -> (doppler_fix when `pos` is None) -> coarse_time_fix.  `t_gps`: the GPS seconds
     of week of the first sample as far as known; `cancel`, `stats`: measure's.  -> (Fix,
     measurements, device ms).  The Fix's t_gps is that of its `sample`.
@@ -1127,7 +1308,10 @@ def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, ca
     one the order of twin_fixes stands.  report.one_direction raises the alarm without a doubled
     PRN.
     `beams` (with `antennas` only): measure's -- the records the fixes are made of
-    were measured on their own beams."""
+    were measured on their own beams.
+    `profile` (with `spoof` only): measure's -- report.distorted and profile_t, and an
+    alarm that is raised as well when the PRNs doubled or distorted count `min_doubled`; the fixes are
+    made as without it."""
     if collective not in (None, False, True, 'always'):
         raise ValueError(f"collective {collective!r}: None, False, True or 'always'")
     if collective and pos is None:
@@ -1138,12 +1322,14 @@ def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, ca
         raise ValueError('antennas goes with spoof=True (the signatures serve the spoofing check)')
     if beams and antennas is None:
         raise ValueError('beams goes with antennas=A (the beams combine the antennas)')
+    if profile and not spoof:
+        raise ValueError('profile goes with spoof=True (the profiles serve the spoofing check)')
     stats = {} if stats is None else stats
     report = None
     if spoof:
         meas, report = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats,
                                cancel=cancel, spoof=True, antennas=antennas, **({'beams': True} if beams else {}),
-                               **cfg)
+                               **({'profile': True} if profile else {}), **cfg)
     else:
         meas = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats, cancel=cancel,
                        **cfg)

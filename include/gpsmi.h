@@ -678,6 +678,66 @@ int gpsmi_acq_signature_dev(gpsmi_acq* h, const void* d_iq, size_t n, const gpsm
  * the prompts array is sized by  */
 int gpsmi_acq_signature_plan(int code_samples, size_t n, const gpsmi_sig_sat* sats, int nsat,
                              const gpsmi_sig_cfg* cfg, int32_t* n_win, int* max_windows);
+/* Multi-tap correlation profiles of refined records on one antenna (float64
+ * restatement: tests/profile_ref.py): what shows a second copy of a code within two chips of the first
+ * -- a spoofer lifting off, or multipath -- where gpsmi_acq_peaks sees one peak.  Per record (prn, f_hz,
+ * tau as gpsmi_sig_sat; the same PRN may appear more than once) the complex correlation at every
+ * whole-sample lag l = -Lh .. +Lh around the code start, per 1-ms window, summed coherently over runs of
+ * coh_ms windows (a data bit from its edge: skip_ms), and the covariance of those sums over the taps;
+ * whether one code replica explains that matrix is decided on the host (gpsmi/snapshot.py,
+ * profile_fit).  cs = code_samples, fs = 1000 cs, K = 2 Lh + 1.
+ * iq: n samples in the handle's input format, host memory for gpsmi_acq_profile, device memory for
+ * gpsmi_acq_profile_dev; GPSMI_IQ_U8 gives the same bytes as its complex64 decode.  nsat = 1 .. 64.
+ * Windows.  Tc and j_k = rint(tau + k Tc) exactly as in gpsmi_acq_signature; a record's windows are all
+ * k with j_k - Lh >= 0 and j_k + Lh + cs <= n, in order; the first skip_ms of them are dropped, the rest
+ * are cut into runs of coh_ms consecutive windows, an incomplete last run is dropped, and a positive
+ * n_runs keeps the first n_runs.  A record without a run is GPSMI_E_ARG.
+ * Taps.  w[u] = x[u] exp(-j 2 pi f_hz (u + 1) / fs) with the integer carrier phase of gpsmi_acq_cancel
+ * at the absolute sample index u (0.64 fixed point, its top 24 bits give sine s and cosine c):
+ * Re w = fma(Re x, c, Im x * s), Im w = fma(Im x, c, -(Re x * s)) in float32 -- one value for all taps.
+ * D[r][l][k] = sum_{i < cs} w[j_k + l + i] R[i], R = GPSCacode(prn) (gpsmi_acq_set_replica_time), in
+ * float32 in this order: lane q = 0 .. 63 adds, by fused multiply-adds from 0, the points i with
+ * (i mod 256) div 4 = q in ascending i; the 64 lane sums are folded by a butterfly (lane q takes
+ * v[q] + v[q xor 32], then xor 16, 8, 4, 2, 1).  S[r][l][m] = the D[r][l][.] of run m's coh_ms windows
+ * added in float32 in ascending order from the first, stored as complex64.  None of it depends on nsat,
+ * on the record's place in the call, on half_taps or on what else shares the call.
+ * Covariance.  Q[r][l][l'] = sum_m S[r][l][m] conj(S[r][l'][m]): float64 sums of the widened complex64
+ * values in ascending m; the upper triangle is computed, the lower one is its exact conjugate, the
+ * diagonal's imaginary part is exactly 0.
+ * Outputs (host arrays): cov double [nsat][K][K][2]; n_runs int32 [nsat]; sums: optional complex64
+ * [nsat][K][max_runs] (max_runs from gpsmi_acq_profile_plan), zero past a record's last run.
+ * A record's result depends on that record alone.  The same arguments give the same bytes, from either
+ * entry point.  Argument errors are GPSMI_E_ARG and need no GPU (gpsmi_acq_profile_plan makes the same
+ * checks without a handle): a null pointer, nsat, a PRN outside 1 .. 37, skip_ms outside 0 .. 19, f_hz
+ * or tau not finite, |f_hz| >= fs / 2, (f_hz - f_offset_hz) beyond 1 % of carrier_hz, half_taps outside
+ * 0 .. 32, coh_ms outside 0 .. 20, n_runs < 0, a reserved field that is not 0, carrier_hz or f_offset_hz
+ * not finite, n outside 1 .. 2^40, a record without a run.  code_samples 2048 and 16368 only
+ * (GPSMI_E_UNSUPPORTED); GPSMI_E_STATE: no time-domain replica for a PRN; GPSMI_E_NOMEM leaves the
+ * handle usable.  cfg may be null (all defaults).  The call returns when the work is done;
+ * gpsmi_acq_last_ms reports it.                                                                  */
+typedef struct gpsmi_prof_sat {     /* no implicit padding: 24 bytes */
+    int32_t prn;
+    int32_t skip_ms;                /* windows dropped before the first run: the bit edge, 0 .. 19 */
+    double  f_hz;                   /* as gpsmi_sig_sat */
+    double  tau;                    /* a code start, samples from iq[0]; any sign */
+} gpsmi_prof_sat;
+typedef struct gpsmi_prof_cfg {     /* no implicit padding: 32 bytes; 0 = the default */
+    int32_t half_taps;              /* Lh, 1 .. 32; 0: 8 at 2048, 32 at 16368 (+-4 / +-2 chips) */
+    int32_t coh_ms;                 /* windows summed coherently per run, 1 .. 20; 0: 20 */
+    int32_t n_runs;                 /* 0: every run that fits */
+    int32_t reserved;               /* 0 */
+    double  carrier_hz;             /* 0: 1575.42e6 */
+    double  f_offset_hz;            /* as in gpsmi_acq_search_deep; finite */
+} gpsmi_prof_cfg;
+int gpsmi_acq_profile(gpsmi_acq* h, const void* iq, size_t n, const gpsmi_prof_sat* sats, int nsat,
+                      const gpsmi_prof_cfg* cfg, double* cov, int32_t* n_runs, float* sums);
+int gpsmi_acq_profile_dev(gpsmi_acq* h, const void* d_iq, size_t n, const gpsmi_prof_sat* sats, int nsat,
+                          const gpsmi_prof_cfg* cfg, double* cov, int32_t* n_runs, float* sums);
+/* host only, no GPU: the argument checks of gpsmi_acq_profile for a handle of code_samples, the runs
+ * of every record (n_runs [nsat], optional), the largest of them (max_runs, optional) the sums array
+ * is sized by, and the taps K = 2 Lh + 1 (taps, optional)  */
+int gpsmi_acq_profile_plan(int code_samples, size_t n, const gpsmi_prof_sat* sats, int nsat,
+                           const gpsmi_prof_cfg* cfg, int32_t* n_runs, int* max_runs, int* taps);
 /* Input format of the iq pointers of the search calls that follow (host or device), as
  * gpsmi_trk_set_input_format below: GPSMI_IQ_U8 = the raw recording of streamData
  * (gpsrecv.py:162-173), decoded where the carrier wipe-off reads it; same bits out.   */

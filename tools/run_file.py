@@ -7,7 +7,7 @@ gpseval) as one command on the GPU path.
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--sweep [L]] [--blank] [--json]
                              [--antenna FILE ... --null [--null-taps T]]
                              [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track [--weak-fix]]]]
-                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]] [--spoof-check [K]] [--antenna FILE ... [--beams]]]]
+                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]] [--spoof-check [K] [--profile-check]] [--antenna FILE ... [--beams]]]]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -83,7 +83,11 @@ is the spoofer's, and the report names the authentic fix (first) and says whethe
 direction ('authentic', 'one_source', 'one_direction').  --beams on top of that measures every
 record again on a beam of its own over the antennas, steered at its signature and with a null at the spoofer
 where one is found and the null costs at most 3 dB; the report gains a 'beams' entry with one line per record
-(the null, the predicted gain, C/N0 on antenna 0).
+(the null, the predicted gain, C/N0 on antenna 0).  --profile-check (with --spoof-check; one
+antenna is enough) takes every record's multi-tap correlation profile and tests whether one code replica
+explains it: a copy within two chips of the authentic code, which the peaks cannot separate, shows as a
+distorted profile; such PRNs are listed ('distorted') and count towards the alarm like doubled ones, and the
+report gains one 'profile' line per record.
 
 There is no recording in this repository (data/test.bin is absent from the reference
 checkout, SURVEY F2, and too short for a fix even upstream): tests/test_run_file.py writes a
@@ -276,7 +280,7 @@ def parse_time(text, ephs):
 
 
 def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, frontend=None, excise=False,
-             blank=False, cancel=None, collective_km=None, spoof_k=None, antennas=(), beams=False):
+             blank=False, cancel=None, collective_km=None, spoof_k=None, antennas=(), beams=False, profile=False):
     """--snapshot: gpsmi.snapshot.snapshot_fix on the first `seconds` behind `start_stream`, read
     and filtered block by block as run() feeds its receiver.  `cancel`: --cancel's C/N0 threshold
     (snapshot.measure's `cancel`); None leaves everything as it is without the flag.
@@ -286,7 +290,9 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
     row of the snapshot, `path` the first, and the spoofing check names the authentic fix from the records'
     spatial signatures (snapshot_fix's antennas=A).
     `beams` (with `antennas`): --beams, every record is measured again on a beam of its own over the antennas, with
-    a null at the spoofer where one is found (snapshot_fix's beams=True)."""
+    a null at the spoofer where one is found (snapshot_fix's beams=True).
+    `profile` (with `spoof_k`): --profile-check, every record's multi-tap correlation profile is tested for a second
+    copy of the code within the guard of the peaks (snapshot_fix's profile=True)."""
     from gpsmi import ingest, position as P, snapshot as S
     from gpsmi.acquisition import Acquisition
     from gpsmi.conditioning import Conditioner
@@ -317,6 +323,7 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
                                            **({} if spoof_k is None else {'spoof': True, 'min_doubled': spoof_k}),
                                            **({'antennas': 1 + len(antennas)} if antennas else {}),
                                            **({'beams': True} if beams else {}),
+                                           **({'profile': True} if profile else {}),
                                            **({} if collective_km is None else
                                               {'collective': True, 'collective_cfg': {'radius_m': 1.0e3 * collective_km}}))
             wall = time.perf_counter() - t0
@@ -361,6 +368,13 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
                        'one_source': [False, False] if rep is None else [bool(v) for v in rep.one_source],
                        'one_direction': bool(rep is not None and rep.one_direction),
                        'signature_ms': round(float(stats.get('signature_ms', 0.0)), 3)})
+        if profile:
+            fits = [] if rep is None or rep.profile is None else rep.profile
+            sp.update({'distorted': [] if rep is None else rep.distorted, 'profile_t_min': S.PROFILE_T_MIN,
+                       'profile_ms': round(float(stats.get('profile_ms', 0.0)), 3),
+                       'profile': [{'prn': f.prn, 'T': round(f.T, 2), 'snr1': round(f.snr1, 1), 'd1': round(f.d1, 3),
+                                    'd2': round(f.d2, 3), 'rel_power': round(f.rel_power, 3), 'n_runs': f.n_runs}
+                                   for f in fits]})
         out['spoof'] = sp
     if beams:
         before = stats.get('before_beams')
@@ -423,6 +437,14 @@ def print_snapshot(out):
                       f"not decided here")
         if 'antennas' in sp:
             print(f"  one direction for every signal over {sp['antennas']} antennas: {'YES' if sp['one_direction'] else 'no'}")
+        if 'profile' in sp:
+            print(f"  correlation profiles ({sp['profile_ms']} ms on the device), one per record; a second copy of the "
+                  f"code shows from T {sp['profile_t_min']} on:")
+            for f in sp['profile']:
+                print(f"  profile PRN {f['prn']:2d}  T {f['T']:8.2f}  snr1 {f['snr1']:8.1f}  delays {f['d1']:+.3f} {f['d2']:+.3f}  "
+                      f"second path {f['rel_power']:.3f} of the first  {'DISTORTED' if f['prn'] in sp['distorted'] else 'one path'}")
+            print(f"  PRNs with a distorted profile {sp['distorted']}; doubled or distorted: "
+                  f"{'ALARM' if sp['alarm'] else 'no alarm'}")
     bm = s.get('beams')
     if bm is not None:
         print(f"  beams over the antennas ({bm['beams_ms']} ms on the device), one per record:")
@@ -602,6 +624,10 @@ def main():
     ap.add_argument('--spoof-check', type=int, nargs='?', const=2, default=None, metavar='K',
                     help='with --snapshot: look for PRNs that are in the air twice, raise the alarm from K of them on '
                          '(default 2) and solve both sets (DESIGN.md 4.2n); the exit status stays 0 either way')
+    ap.add_argument('--profile-check', action='store_true',
+                    help='with --snapshot --spoof-check: test every record\'s multi-tap correlation profile for a second '
+                         'copy of the code within two chips, where the peaks see one; such PRNs count towards the alarm '
+                         '(DESIGN.md 4.2r)')
     ap.add_argument('--time', default=None,
                     help='with --snapshot: time of the first sample read, GPS seconds of week or a UTC timestamp, within 30 s')
     ap.add_argument('--near', default=None, metavar='LAT,LON[,H]',
@@ -652,8 +678,10 @@ def main():
                      'recorder\'s own format, without --null / --null-taps / --excise / --blank')
         if a.beams and not a.antenna:
             ap.error('--beams needs --antenna FILE ... (the beams combine the antennas)')
+        if a.profile_check and a.spoof_check is None:
+            ap.error('--profile-check needs --spoof-check (the profiles serve the spoofing check)')
         out = snapshot(a.recording, a.snapshot, eph, parse_time(a.time, eph), near, a.start_stream, frontend,
-                       a.excise, a.blank, a.cancel, a.collective, a.spoof_check, a.antenna, a.beams)
+                       a.excise, a.blank, a.cancel, a.collective, a.spoof_check, a.antenna, a.beams, a.profile_check)
         if a.json:
             print(json.dumps(out))
         else:
@@ -663,6 +691,8 @@ def main():
         ap.error('--time / --near need --snapshot SECONDS')
     if a.beams:
         ap.error('--beams needs --snapshot SECONDS')
+    if a.profile_check:
+        ap.error('--profile-check needs --snapshot SECONDS')
     if bool(a.antenna) != a.null:
         ap.error('--antenna FILE (the further channels) and --null go together')
     if a.null_taps != 1 and not a.null:
