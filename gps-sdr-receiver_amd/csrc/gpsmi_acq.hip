@@ -19,6 +19,8 @@
 //                         (gpsmi_acq_signature): prompts per antenna, their covariance
 //   gpsmi_profile.h       multi-tap correlation profiles of refined records on one antenna
 //                         (gpsmi_acq_profile): bit-coherent sums per tap, their covariance
+//   gpsmi_windows.h       host only: the window rule, the record checks and the tables that
+//                         cancellation, the signatures and the profiles share
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -100,16 +102,13 @@ struct gpsmi_acq {
     DevBuf<int> d_pb;
     DevBuf<gpsmi_peaks_pick> d_pk;
     DevBuf<float> d_pcol;
-    // signatures (gpsmi_acq_signature): the prompts [nsat][A][max_windows], the records and the window
-    // starts of a call in one block, the covariances [nsat][A][A][2]
-    DevBuf<float2> d_sp;
-    DevBuf<char> d_st;
-    DevBuf<double> d_sc;
-    // profiles (gpsmi_acq_profile): the sums [nsat][K][max_runs], the records and the window starts of
-    // a call in one block, the covariances [nsat][K][K][2]
-    DevBuf<float2> d_ps;
-    DevBuf<char> d_pt;
-    DevBuf<double> d_pc;
+    // signatures and profiles (gpsmi_acq_signature, gpsmi_acq_profile; either call has left the stream
+    // when it returns, so one set serves both): the sums -- prompts [nsat][A][max_windows] or tap sums
+    // [nsat][K][max_runs] --, the records and the window starts of a call in one block, the covariances
+    // [nsat][A][A][2] or [nsat][K][K][2]
+    DevBuf<float2> d_vs;
+    DevBuf<char> d_vt;
+    DevBuf<double> d_vc;
     int iq_fmt = GPSMI_IQ_C64;              // what the iq pointers of the search calls point to
     // bytes of `n` samples in the handle's input format
     size_t iq_bytes(size_t n) const { return n * (iq_fmt == GPSMI_IQ_U8 ? 2 : sizeof(float2)); }
@@ -200,6 +199,51 @@ static int acq_end(gpsmi_acq* h) {           // behind its last one; gpsmi_acq_w
     GPSMI_HIP(hipGetLastError());
     GPSMI_HIP(hipEventRecord(h->ev1, h->stream));
     h->pending = true;
+    return GPSMI_OK;
+}
+
+// ---- the call of the two covariance stages on refined records, signatures and profiles ---------
+struct CovCall {
+    const char* fn;                         // the entry point
+    const char* sums;                       // what its sums are called: "prompts", "sums"
+    size_t n_in, n_sums, n_cov;             // samples read; complex64 sums and float64 values made
+};
+
+static void acq_counts(const WinTable& t, int32_t* counts) {
+    if (counts)
+        for (size_t s = 0; s < t.recs.size(); ++s) counts[s] = t.recs[s].count;
+}
+
+// One call of either stage behind its plan: the tables of the call go up in one block, the sums are
+// zeroed, launch(d_iq, d_rec, d_start) -- acq_begin, the stage's kernels from d_vs into d_vc, acq_end --
+// runs, and the covariances, the sums where asked for and the records' counts come back.
+template <typename Launch>
+static int acq_cov_call(gpsmi_acq* h, const void* iq, bool on_host, const CovCall& c, const WinTable& t, double* cov,
+                        int32_t* counts, float* sums, Launch&& launch) {
+    int rc;
+    const void* d_iq;
+    if ((rc = acq_need_time(h, c.fn, (int)t.recs.size(), [&](int i) { return t.recs[i].prn; })) ||
+        (rc = acq_enter(h)) || (rc = acq_input(h, iq, on_host, c.n_in, &d_iq)))
+        return rc;
+    const char* part[3] = {"tables", c.sums, "covariances"};
+    char what[3][64];                       // the buffers' names, for a refused allocation
+    for (int i = 0; i < 3; ++i) snprintf(what[i], sizeof(what[i]), "%s %s", c.fn, part[i]);
+    // the tables of the call, 8-byte items first
+    const size_t b_start = t.start.size() * sizeof(long long), b_rec = t.recs.size() * sizeof(WinRec);
+    if ((rc = h->d_vt.reserve(b_start + b_rec, what[0])) || (rc = h->d_vs.reserve(c.n_sums, what[1])) ||
+        (rc = h->d_vc.reserve(c.n_cov, what[2])))
+        return rc;
+    long long* d_start = reinterpret_cast<long long*>(h->d_vt.p);
+    WinRec* d_rec = reinterpret_cast<WinRec*>(h->d_vt.p + b_start);
+    GPSMI_HIP(hipMemsetAsync(h->d_vs.p, 0, c.n_sums * sizeof(float2), h->stream));
+    if ((rc = acq_tables(h, {{d_start, t.start.data(), b_start}, {d_rec, t.recs.data(), b_rec}})) ||
+        (rc = launch(d_iq, d_rec, d_start)))
+        return rc;
+    GPSMI_HIP(hipMemcpyAsync(cov, h->d_vc.p, c.n_cov * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (sums)
+        GPSMI_HIP(hipMemcpyAsync(sums, h->d_vs.p, c.n_sums * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = gpsmi_acq_wait(h))) return rc;
+    acq_counts(t, counts);
     return GPSMI_OK;
 }
 
@@ -729,9 +773,7 @@ static int acq_cancel_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n,
     const size_t nres = (size_t)nsat * mw;
     std::vector<CancelRes> res;
     if (nres) {
-        try { res.resize(nres); } catch (const std::bad_alloc&) {
-            return fail(GPSMI_E_NOMEM, "gpsmi_acq_cancel: out of host memory");
-        }
+        if ((rc = win_guarded("gpsmi_acq_cancel", [&] { res.resize(nres); return (int)GPSMI_OK; }))) return rc;
         if ((rc = h->d_cw.reserve(pl.wins.size(), "gpsmi_acq_cancel windows")) ||
             (rc = h->d_cr.reserve(nres, "gpsmi_acq_cancel results")))
             return rc;
@@ -794,45 +836,28 @@ int gpsmi_acq_cancel_plan(int code_samples, size_t n, const gpsmi_cancel_sat* sa
     return rc;
 }
 
-// ---- spatial signatures over several antennas (kernels and plan: gpsmi_sig.h) -----------------
+// ---- the two covariance stages on refined records (their call: acq_cov_call above): spatial
+// signatures over several antennas (gpsmi_sig.h), multi-tap correlation profiles (gpsmi_profile.h) --
 static int acq_signature_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n, const gpsmi_sig_sat* sats,
                               int nsat, const gpsmi_sig_cfg* cfg, double* cov, int32_t* n_win, float* prompts) {
     GPSMI_REQUIRE(h && iq && sats && cov && n_win, "null argument");
     SigPlan pl;
     int rc = sig_plan(h->cfg.code_samples, n, sats, nsat, cfg, &pl);
     if (rc) return rc;
-    const void* d_iq;
-    if ((rc = acq_need_time(h, "gpsmi_acq_signature", nsat, [&](int i) { return sats[i].prn; })) ||
-        (rc = acq_enter(h)) || (rc = acq_input(h, iq, on_host, (size_t)pl.A * n, &d_iq)))
-        return rc;
     const int cs = pl.cs, A = pl.A, mw = pl.max_windows;
-    // the tables of the call, 8-byte items first
-    const size_t b_start = pl.start.size() * sizeof(long long), b_rec = (size_t)nsat * sizeof(SigRec);
-    const size_t np = (size_t)nsat * A * mw, nc = (size_t)nsat * A * A * 2;
-    if ((rc = h->d_st.reserve(b_start + b_rec, "gpsmi_acq_signature tables")) ||
-        (rc = h->d_sp.reserve(np, "gpsmi_acq_signature prompts")) ||
-        (rc = h->d_sc.reserve(nc, "gpsmi_acq_signature covariances")))
-        return rc;
-    long long* d_start = reinterpret_cast<long long*>(h->d_st.p);
-    SigRec* d_rec = reinterpret_cast<SigRec*>(h->d_st.p + b_start);
-    const size_t lds = sig_lds_bytes(cs);
-    GPSMI_HIP(hipMemsetAsync(h->d_sp.p, 0, np * sizeof(float2), h->stream));
-    if ((rc = acq_tables(h, {{d_start, pl.start.data(), b_start}, {d_rec, pl.recs.data(), b_rec}})) ||
-        (rc = acq_lds_optin(h, sig_prompt_kernel<1>, sig_prompt_kernel<0>, lds)) || (rc = acq_begin(h)))
-        return rc;
-    const dim3 gp((mw + kSigWinPerWg - 1) / kSigWinPerWg, nsat);
-    with_fmt(h->iq_fmt, [&](auto fmt) {
-        hipLaunchKernelGGL(sig_prompt_kernel<decltype(fmt)::value>, gp, dim3(256), lds, h->stream, d_iq, n, A,
-                           h->d_rep_time.p, d_rec, d_start, cs, mw, h->d_sp.p);
-    });
-    hipLaunchKernelGGL(sig_cov_kernel, dim3(nsat), dim3(256), 0, h->stream, h->d_sp.p, d_rec, A, mw, h->d_sc.p);
-    if ((rc = acq_end(h))) return rc;
-    GPSMI_HIP(hipMemcpyAsync(cov, h->d_sc.p, nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (prompts)
-        GPSMI_HIP(hipMemcpyAsync(prompts, h->d_sp.p, np * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-    if ((rc = gpsmi_acq_wait(h))) return rc;
-    for (int s = 0; s < nsat; ++s) n_win[s] = pl.recs[s].n_win;
-    return GPSMI_OK;
+    const CovCall c{"gpsmi_acq_signature", "prompts", (size_t)A * n, (size_t)nsat * A * mw, (size_t)nsat * A * A * 2};
+    auto launch = [&](const void* d_iq, const WinRec* d_rec, const long long* d_start) -> int {
+        const size_t lds = sig_lds_bytes(cs);
+        if ((rc = acq_lds_optin(h, sig_prompt_kernel<1>, sig_prompt_kernel<0>, lds)) || (rc = acq_begin(h))) return rc;
+        const dim3 gp((mw + kSigWinPerWg - 1) / kSigWinPerWg, nsat);
+        with_fmt(h->iq_fmt, [&](auto fmt) {
+            hipLaunchKernelGGL(sig_prompt_kernel<decltype(fmt)::value>, gp, dim3(256), lds, h->stream, d_iq, n, A,
+                               h->d_rep_time.p, d_rec, d_start, cs, mw, h->d_vs.p);
+        });
+        hipLaunchKernelGGL(sig_cov_kernel, dim3(nsat), dim3(256), 0, h->stream, h->d_vs.p, d_rec, A, mw, h->d_vc.p);
+        return acq_end(h);
+    };
+    return acq_cov_call(h, iq, on_host, c, pl, cov, n_win, prompts, launch);
 }
 
 int gpsmi_acq_signature(gpsmi_acq* h, const void* iq, size_t n, const gpsmi_sig_sat* sats, int nsat,
@@ -850,52 +875,32 @@ int gpsmi_acq_signature_plan(int code_samples, size_t n, const gpsmi_sig_sat* sa
     SigPlan pl;
     const int rc = sig_plan(code_samples, n, sats, nsat, cfg, &pl);
     if (rc != GPSMI_OK) return rc;
-    if (n_win)
-        for (int s = 0; s < nsat; ++s) n_win[s] = pl.recs[s].n_win;
+    acq_counts(pl, n_win);
     if (max_windows) *max_windows = pl.max_windows;
     return GPSMI_OK;
 }
 
-// ---- multi-tap correlation profiles (kernels and plan: gpsmi_profile.h) -----------------------
 static int acq_profile_impl(gpsmi_acq* h, const void* iq, bool on_host, size_t n, const gpsmi_prof_sat* sats,
                             int nsat, const gpsmi_prof_cfg* cfg, double* cov, int32_t* n_runs, float* sums) {
     GPSMI_REQUIRE(h && iq && sats && cov && n_runs, "null argument");
     ProfPlan pl;
     int rc = prof_plan(h->cfg.code_samples, n, sats, nsat, cfg, &pl);
     if (rc) return rc;
-    const void* d_iq;
-    if ((rc = acq_need_time(h, "gpsmi_acq_profile", nsat, [&](int i) { return sats[i].prn; })) ||
-        (rc = acq_enter(h)) || (rc = acq_input(h, iq, on_host, n, &d_iq)))
-        return rc;
     const int cs = pl.cs, Lh = pl.Lh, K = 2 * pl.Lh + 1, mr = pl.max_runs;
-    // the tables of the call, 8-byte items first
-    const size_t b_start = pl.start.size() * sizeof(long long), b_rec = (size_t)nsat * sizeof(ProfRec);
-    const size_t ns = (size_t)nsat * K * mr, nc = (size_t)nsat * K * K * 2;
-    if ((rc = h->d_pt.reserve(b_start + b_rec, "gpsmi_acq_profile tables")) ||
-        (rc = h->d_ps.reserve(ns, "gpsmi_acq_profile sums")) ||
-        (rc = h->d_pc.reserve(nc, "gpsmi_acq_profile covariances")))
-        return rc;
-    long long* d_start = reinterpret_cast<long long*>(h->d_pt.p);
-    ProfRec* d_rec = reinterpret_cast<ProfRec*>(h->d_pt.p + b_start);
-    GPSMI_HIP(hipMemsetAsync(h->d_ps.p, 0, ns * sizeof(float2), h->stream));
-    if ((rc = acq_tables(h, {{d_start, pl.start.data(), b_start}, {d_rec, pl.recs.data(), b_rec}})) ||
-        (rc = acq_begin(h)))
-        return rc;
-    const dim3 gp(mr, nsat);
-    with_fmt(h->iq_fmt, [&](auto fmt) {
-        with_value<8, kProfMaxHalf>(Lh <= 8 ? 8 : kProfMaxHalf, [&](auto lh) {
-            hipLaunchKernelGGL((prof_sum_kernel<decltype(fmt)::value, decltype(lh)::value>), gp, dim3(256), 0,
-                               h->stream, d_iq, h->d_rep_time.p, d_rec, d_start, cs, Lh, pl.coh, mr, h->d_ps.p);
+    const CovCall c{"gpsmi_acq_profile", "sums", n, (size_t)nsat * K * mr, (size_t)nsat * K * K * 2};
+    auto launch = [&](const void* d_iq, const WinRec* d_rec, const long long* d_start) -> int {
+        if ((rc = acq_begin(h))) return rc;
+        const dim3 gp(mr, nsat);
+        with_fmt(h->iq_fmt, [&](auto fmt) {
+            with_value<8, kProfMaxHalf>(Lh <= 8 ? 8 : kProfMaxHalf, [&](auto lh) {
+                hipLaunchKernelGGL((prof_sum_kernel<decltype(fmt)::value, decltype(lh)::value>), gp, dim3(256), 0,
+                                   h->stream, d_iq, h->d_rep_time.p, d_rec, d_start, cs, Lh, pl.coh, mr, h->d_vs.p);
+            });
         });
-    });
-    hipLaunchKernelGGL(prof_cov_kernel, dim3(nsat), dim3(256), 0, h->stream, h->d_ps.p, d_rec, K, mr, h->d_pc.p);
-    if ((rc = acq_end(h))) return rc;
-    GPSMI_HIP(hipMemcpyAsync(cov, h->d_pc.p, nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (sums)
-        GPSMI_HIP(hipMemcpyAsync(sums, h->d_ps.p, ns * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-    if ((rc = gpsmi_acq_wait(h))) return rc;
-    for (int s = 0; s < nsat; ++s) n_runs[s] = pl.recs[s].n_runs;
-    return GPSMI_OK;
+        hipLaunchKernelGGL(prof_cov_kernel, dim3(nsat), dim3(256), 0, h->stream, h->d_vs.p, d_rec, K, mr, h->d_vc.p);
+        return acq_end(h);
+    };
+    return acq_cov_call(h, iq, on_host, c, pl, cov, n_runs, sums, launch);
 }
 
 int gpsmi_acq_profile(gpsmi_acq* h, const void* iq, size_t n, const gpsmi_prof_sat* sats, int nsat,
@@ -913,8 +918,7 @@ int gpsmi_acq_profile_plan(int code_samples, size_t n, const gpsmi_prof_sat* sat
     ProfPlan pl;
     const int rc = prof_plan(code_samples, n, sats, nsat, cfg, &pl);
     if (rc != GPSMI_OK) return rc;
-    if (n_runs)
-        for (int s = 0; s < nsat; ++s) n_runs[s] = pl.recs[s].n_runs;
+    acq_counts(pl, n_runs);
     if (max_runs) *max_runs = pl.max_runs;
     if (taps) *taps = 2 * pl.Lh + 1;
     return GPSMI_OK;

@@ -24,6 +24,7 @@
 #include "gpsmi_common.h"
 #include "gpsmi_refine.h"
 #include "gpsmi_stats.h"
+#include "gpsmi_windows.h"
 
 namespace gpsmi {
 
@@ -176,60 +177,47 @@ struct CancelPlan {
     std::vector<unsigned long long> inc;          // [nsat]
 };
 
-#define CANCEL_REQUIRE(cond, msg)                                                       \
-    do {                                                                                \
-        if (!(cond)) return ::gpsmi::fail(GPSMI_E_ARG, "gpsmi_acq_cancel: %s", msg);    \
-    } while (0)
-
-#pragma clang fp contract(off)
-// edge k of a satellite's windows, float64, unfused: tau + k Tc
-inline double cancel_edge(double tau, double Tc, long long k) { return tau + (double)k * Tc; }
-#pragma clang fp contract(fast)
-
 // Validates the arguments of gpsmi_acq_cancel (the handle and the buffers aside) and fills the plan
-// (pl may be null).
+// (pl may be null).  The records and the common cfg fields are checked by the window rule
+// (gpsmi_windows.h); the windows themselves are cancellation's own: they tile iq without a gap, so
+// their edges are ceil(e_k), the first and the last are cut at iq's ends, and the replica is laid
+// from the rounded start j_k.
 inline int cancel_plan(int cs, size_t n, const gpsmi_cancel_sat* sats, int nsat, const gpsmi_cancel_cfg* c,
                        CancelPlan* pl) {
-    CANCEL_REQUIRE(nsat >= 0 && nsat <= kCancelMaxSats, "nsat out of range 0..32");
-    CANCEL_REQUIRE(sats || nsat == 0, "null argument");
-    CANCEL_REQUIRE(n >= 1 && n <= ((size_t)1 << 40), "n out of range 1..2^40");
-    double carrier = 1575.42e6, f_offset = 0.0;
-    int min_window = 16;
-    if (c) {
-        CANCEL_REQUIRE(std::isfinite(c->carrier_hz) && c->carrier_hz >= 0.0, "carrier_hz must be positive (0: L1)");
-        CANCEL_REQUIRE(std::isfinite(c->f_offset_hz), "f_offset_hz must be finite");
-        CANCEL_REQUIRE(c->min_window >= 0, "min_window must be >= 1 (0: 16)");
-        if (c->carrier_hz > 0.0) carrier = c->carrier_hz;
-        f_offset = c->f_offset_hz;
-        if (c->min_window > 0) min_window = c->min_window;
-    }
-    if (cs != 2048 && cs != 16368)
-        return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_cancel: code_samples 2048 and 16368 only (%d)", cs);
-    const double fs = 1000.0 * cs;
-    CancelPlan tmp;
-    CancelPlan& p = pl ? *pl : tmp;
-    p.cs = cs; p.min_window = min_window; p.max_windows = 0;
-    p.first.assign(1, 0);
-    p.wins.clear();
-    p.inc.clear();
-    for (int s = 0; s < nsat; ++s) {
-        const gpsmi_cancel_sat& g = sats[s];
-        CANCEL_REQUIRE(g.prn >= 1 && g.prn <= GPSMI_MAX_PRN, "prn out of range 1..37");
-        for (int q = 0; q < s; ++q) CANCEL_REQUIRE(sats[q].prn != g.prn, "a PRN appears twice");
-        CANCEL_REQUIRE(std::isfinite(g.f_hz) && std::fabs(g.f_hz) < 0.5 * fs, "f_hz out of range");
-        CANCEL_REQUIRE(std::isfinite(g.tau) && std::fabs(g.tau) < 1e15, "tau out of range");
-        const double scale = 1.0 + (g.f_hz - f_offset) / carrier;
-        CANCEL_REQUIRE(scale > 0.99 && scale < 1.01, "f_hz - f_offset_hz beyond 1 % of carrier_hz");
-        const double Tc = (double)cs / scale;
-        // the window that holds sample 0: ceil(edge k) <= 0 < ceil(edge k + 1)
-        long long k = (long long)std::floor(-g.tau / Tc);
-        while (std::ceil(cancel_edge(g.tau, Tc, k)) > 0.0) --k;
-        while (std::ceil(cancel_edge(g.tau, Tc, k + 1)) <= 0.0) ++k;
-        try {
-            p.inc.push_back(ref_phase_inc(g.f_hz, fs));
+    WinCall w{"gpsmi_acq_cancel"};
+    return win_guarded(w.fn, [&]() -> int {
+        GPSMI_REQUIRE_IN(w.fn, nsat >= 0 && nsat <= kCancelMaxSats, "nsat out of range 0..32");
+        GPSMI_REQUIRE_IN(w.fn, sats || nsat == 0, "null argument");
+        GPSMI_REQUIRE_IN(w.fn, n >= 1 && n <= ((size_t)1 << 40), "n out of range 1..2^40");
+        int rc, min_window = 16;
+        if (c) {
+            if ((rc = win_cfg(w, c->carrier_hz, c->f_offset_hz))) return rc;
+            GPSMI_REQUIRE_IN(w.fn, c->min_window >= 0, "min_window must be >= 1 (0: 16)");
+            if (c->min_window > 0) min_window = c->min_window;
+        }
+        if ((rc = win_code(w, cs))) return rc;
+        CancelPlan tmp;
+        CancelPlan& p = pl ? *pl : tmp;
+        p.cs = cs; p.min_window = min_window; p.max_windows = 0;
+        p.first.assign(1, 0);
+        p.wins.clear();
+        p.inc.clear();
+        for (int s = 0; s < nsat; ++s) {
+            const gpsmi_cancel_sat& g = sats[s];
+            bool twice = false;
+            for (int q = 0; q < s; ++q) twice |= sats[q].prn == g.prn;
+            double Tc;
+            unsigned long long inc;
+            if ((rc = win_record(w, g.prn, twice ? "a PRN appears twice" : nullptr, g.f_hz, g.tau, &Tc, &inc)))
+                return rc;
+            p.inc.push_back(inc);
+            // the window that holds sample 0: ceil(edge k) <= 0 < ceil(edge k + 1)
+            long long k = (long long)std::floor(-g.tau / Tc);
+            while (std::ceil(win_edge(g.tau, Tc, k)) > 0.0) --k;
+            while (std::ceil(win_edge(g.tau, Tc, k + 1)) <= 0.0) ++k;
             for (;; ++k) {
-                const double e0 = cancel_edge(g.tau, Tc, k);
-                long long lo = (long long)std::ceil(e0), hi = (long long)std::ceil(cancel_edge(g.tau, Tc, k + 1));
+                const double e0 = win_edge(g.tau, Tc, k);
+                long long lo = (long long)std::ceil(e0), hi = (long long)std::ceil(win_edge(g.tau, Tc, k + 1));
                 if (lo >= (long long)n) break;
                 const long long j = (long long)std::nearbyint(e0);
                 lo = lo < 0 ? 0 : lo;
@@ -239,13 +227,10 @@ inline int cancel_plan(int cs, size_t n, const gpsmi_cancel_sat* sats, int nsat,
                 p.wins.push_back(CancelWin{lo, (int)(hi - lo), (int)r0});
             }
             p.first.push_back((int)p.wins.size());
-        } catch (const std::bad_alloc&) {
-            return fail(GPSMI_E_NOMEM, "gpsmi_acq_cancel: out of host memory");
+            p.max_windows = std::max(p.max_windows, p.first[s + 1] - p.first[s]);
         }
-        const int nw = p.first[s + 1] - p.first[s];
-        if (nw > p.max_windows) p.max_windows = nw;
-    }
-    return GPSMI_OK;
+        return GPSMI_OK;
+    });
 }
 
 }  // namespace gpsmi

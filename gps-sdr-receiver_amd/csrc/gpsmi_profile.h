@@ -23,7 +23,7 @@
 #include "gpsmi_common.h"
 #include "gpsmi_cancel.h"
 #include "gpsmi_refine.h"
-#include "gpsmi_sig.h"
+#include "gpsmi_windows.h"
 
 namespace gpsmi {
 
@@ -31,11 +31,6 @@ constexpr int kProfMaxSats = 64;
 constexpr int kProfMaxHalf = 32;                  // Lh
 constexpr int kProfMaxCoh = 20;                   // windows of a run
 constexpr int kProfChunk = 1024;                  // samples of a window wiped at a time: 4 steps of 256
-
-struct ProfRec {                                  // one record as the kernels see it
-    unsigned long long inc;                       // f_hz / fs in 0.64 fixed point
-    int prn, n_runs;
-};
 
 // the wiped samples of one wave: kProfChunk + 2 LH of them in four planes (index mod 4), one item of
 // padding per plane so that the planes start in different banks
@@ -52,15 +47,15 @@ struct ProfLds {
 // j_k - Lh >= 0 and j_k + Lh + cs <= n); S is [nsat][2 Lh + 1][max_runs], zeroed by the caller.
 template <int FMT, int LH>
 __global__ __launch_bounds__(256) void prof_sum_kernel(
-    const void* __restrict__ iq, const float* __restrict__ rep_time, const ProfRec* __restrict__ recs,
+    const void* __restrict__ iq, const float* __restrict__ rep_time, const WinRec* __restrict__ recs,
     const long long* __restrict__ start, int cs, int Lh, int coh, int max_runs, float2* __restrict__ S) {
     using L = ProfLds<LH>;
     __shared__ __attribute__((aligned(16))) L lds;
     constexpr int KT = L::kTaps;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int rec = blockIdx.y, run = blockIdx.x;
-    const ProfRec rr = recs[rec];
-    if (run >= rr.n_runs) return;                 // (the whole workgroup: nothing of it is waited for)
+    const WinRec rr = recs[rec];
+    if (run >= rr.count) return;                 // (the whole workgroup: nothing of it is waited for)
     const float* R = rep_time + (size_t)rr.prn * cs;
     const long long* st = start + ((size_t)rec * max_runs + run) * coh;
     float2* wv = lds.w[wave];
@@ -134,9 +129,9 @@ __global__ __launch_bounds__(256) void prof_sum_kernel(
 }
 
 // Q[rec][l][l'] = sum_m S[rec][l][m] conj(S[rec][l'][m]), float64 [nsat][K][K][2]
-__global__ __launch_bounds__(256) void prof_cov_kernel(const float2* __restrict__ S, const ProfRec* __restrict__ recs,
+__global__ __launch_bounds__(256) void prof_cov_kernel(const float2* __restrict__ S, const WinRec* __restrict__ recs,
                                                        int K, int max_runs, double* __restrict__ cov) {
-    const int rec = blockIdx.x, n_runs = recs[rec].n_runs;
+    const int rec = blockIdx.x, n_runs = recs[rec].count;
     const float2* Sr = S + (size_t)rec * K * max_runs;
     double* c = cov + (size_t)rec * K * K * 2;
     for (int p = threadIdx.x; p < K * (K + 1) / 2; p += 256) {
@@ -164,86 +159,55 @@ __global__ __launch_bounds__(256) void prof_cov_kernel(const float2* __restrict_
 }
 
 // ---- the plan: everything a call derives from its arguments, on the host, no GPU --------------
-struct ProfPlan {
+struct ProfPlan : WinTable {                      // recs[].count: a record's runs; start [nsat][max_runs][coh]
     int cs = 0, Lh = 0, coh = 0, max_runs = 0;
-    std::vector<ProfRec> recs;                    // [nsat]
-    std::vector<long long> start;                 // [nsat][max_runs][coh], 0 past a record's last run
 };
 
-#define PROF_REQUIRE(cond, msg)                                                          \
-    do {                                                                                 \
-        if (!(cond)) return ::gpsmi::fail(GPSMI_E_ARG, "gpsmi_acq_profile: %s", msg);    \
-    } while (0)
-
 // Validates the arguments of gpsmi_acq_profile (the handle and the buffers aside) and fills the plan
-// (pl may be null).
+// (pl may be null).  The windows are the window rule's (gpsmi_windows.h) with half_taps samples of
+// guard, skip_ms of them dropped; what is the profiles' own is the run: coh_ms windows in a row, the
+// windows behind the last whole run left out.
 inline int prof_plan(int cs, size_t n, const gpsmi_prof_sat* sats, int nsat, const gpsmi_prof_cfg* c, ProfPlan* pl) {
-    PROF_REQUIRE(nsat >= 1 && nsat <= kProfMaxSats, "nsat out of range 1..64");
-    PROF_REQUIRE(sats, "null argument");
-    double carrier = 1575.42e6, f_offset = 0.0;
-    int Lh = 0, coh = kProfMaxCoh, want_runs = 0;
-    if (c) {
-        PROF_REQUIRE(c->half_taps >= 0 && c->half_taps <= kProfMaxHalf, "half_taps out of range 1..32 (0: the default)");
-        PROF_REQUIRE(c->coh_ms >= 0 && c->coh_ms <= kProfMaxCoh, "coh_ms out of range 1..20 (0: 20)");
-        PROF_REQUIRE(c->n_runs >= 0, "n_runs must be >= 1 (0: every run that fits)");
-        PROF_REQUIRE(c->reserved == 0, "a reserved field is not 0");
-        PROF_REQUIRE(std::isfinite(c->carrier_hz) && c->carrier_hz >= 0.0, "carrier_hz must be positive (0: L1)");
-        PROF_REQUIRE(std::isfinite(c->f_offset_hz), "f_offset_hz must be finite");
-        Lh = c->half_taps;
-        if (c->coh_ms > 0) coh = c->coh_ms;
-        want_runs = c->n_runs;
-        if (c->carrier_hz > 0.0) carrier = c->carrier_hz;
-        f_offset = c->f_offset_hz;
-    }
-    PROF_REQUIRE(n >= 1 && n <= ((size_t)1 << 40), "n out of range 1..2^40");
-    if (cs != 2048 && cs != 16368)
-        return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_profile: code_samples 2048 and 16368 only (%d)", cs);
-    if (Lh == 0) Lh = cs == 2048 ? 8 : 32;        // +- 4 chips, +- 2 chips
-    const double fs = 1000.0 * cs;
-    ProfPlan tmp;
-    ProfPlan& p = pl ? *pl : tmp;
-    p.cs = cs; p.Lh = Lh; p.coh = coh; p.max_runs = 0;
-    std::vector<std::vector<long long>> wins;
-    try {
-        p.recs.assign(nsat, ProfRec{0ull, 0, 0});
-        wins.resize(nsat);
-    } catch (const std::bad_alloc&) {
-        return fail(GPSMI_E_NOMEM, "gpsmi_acq_profile: out of host memory");
-    }
-    for (int s = 0; s < nsat; ++s) {
-        const gpsmi_prof_sat& g = sats[s];
-        PROF_REQUIRE(g.prn >= 1 && g.prn <= GPSMI_MAX_PRN, "prn out of range 1..37");
-        PROF_REQUIRE(g.skip_ms >= 0 && g.skip_ms < kProfMaxCoh, "skip_ms out of range 0..19");
-        PROF_REQUIRE(std::isfinite(g.f_hz) && std::fabs(g.f_hz) < 0.5 * fs, "f_hz out of range");
-        PROF_REQUIRE(std::isfinite(g.tau) && std::fabs(g.tau) < 1e15, "tau out of range");
-        const double scale = 1.0 + (g.f_hz - f_offset) / carrier;
-        PROF_REQUIRE(scale > 0.99 && scale < 1.01, "f_hz - f_offset_hz beyond 1 % of carrier_hz");
-        const double Tc = (double)cs / scale;
-        long long k = sig_first_window(g.tau, Tc, Lh) + g.skip_ms;
-        try {
-            for (;; ++k) {
-                const long long j = (long long)std::nearbyint(cancel_edge(g.tau, Tc, k));
-                if ((unsigned long long)(j + cs + Lh) > (unsigned long long)n) break;
-                if (want_runs > 0 && (long long)wins[s].size() >= (long long)want_runs * coh) break;
-                wins[s].push_back(j);
-            }
-        } catch (const std::bad_alloc&) {
-            return fail(GPSMI_E_NOMEM, "gpsmi_acq_profile: out of host memory");
+    WinCall w{"gpsmi_acq_profile"};
+    return win_guarded(w.fn, [&]() -> int {
+        GPSMI_REQUIRE_IN(w.fn, nsat >= 1 && nsat <= kProfMaxSats, "nsat out of range 1..64");
+        GPSMI_REQUIRE_IN(w.fn, sats, "null argument");
+        int rc, Lh = 0, coh = kProfMaxCoh, want_runs = 0;
+        if (c) {
+            GPSMI_REQUIRE_IN(w.fn, c->half_taps >= 0 && c->half_taps <= kProfMaxHalf,
+                             "half_taps out of range 1..32 (0: the default)");
+            GPSMI_REQUIRE_IN(w.fn, c->coh_ms >= 0 && c->coh_ms <= kProfMaxCoh, "coh_ms out of range 1..20 (0: 20)");
+            GPSMI_REQUIRE_IN(w.fn, c->n_runs >= 0, "n_runs must be >= 1 (0: every run that fits)");
+            GPSMI_REQUIRE_IN(w.fn, c->reserved == 0, "a reserved field is not 0");
+            if ((rc = win_cfg(w, c->carrier_hz, c->f_offset_hz))) return rc;
+            Lh = c->half_taps;
+            if (c->coh_ms > 0) coh = c->coh_ms;
+            want_runs = c->n_runs;
         }
-        const int runs = (int)(wins[s].size() / (size_t)coh);
-        PROF_REQUIRE(runs >= 1, "a record has no run inside iq");
-        p.recs[s] = ProfRec{ref_phase_inc(g.f_hz, fs), g.prn, runs};
-        if (runs > p.max_runs) p.max_runs = runs;
-    }
-    try {
-        p.start.assign((size_t)nsat * p.max_runs * coh, 0ll);
-    } catch (const std::bad_alloc&) {
-        return fail(GPSMI_E_NOMEM, "gpsmi_acq_profile: out of host memory");
-    }
-    for (int s = 0; s < nsat; ++s)
-        for (size_t k = 0; k < (size_t)p.recs[s].n_runs * coh; ++k)
-            p.start[(size_t)s * p.max_runs * coh + k] = wins[s][k];
-    return GPSMI_OK;
+        GPSMI_REQUIRE_IN(w.fn, n >= 1 && n <= ((size_t)1 << 40), "n out of range 1..2^40");
+        if ((rc = win_code(w, cs))) return rc;
+        if (Lh == 0) Lh = cs == 2048 ? 8 : 32;    // +- 4 chips, +- 2 chips
+        ProfPlan tmp;
+        ProfPlan& p = pl ? *pl : tmp;
+        p.cs = cs; p.Lh = Lh; p.coh = coh;
+        p.recs.assign(nsat, WinRec{0ull, 0, 0});
+        std::vector<std::vector<long long>> wins(nsat);
+        for (int s = 0; s < nsat; ++s) {
+            const gpsmi_prof_sat& g = sats[s];
+            const bool skip_ok = g.skip_ms >= 0 && g.skip_ms < kProfMaxCoh;
+            double Tc;
+            if ((rc = win_record(w, g.prn, skip_ok ? nullptr : "skip_ms out of range 0..19", g.f_hz, g.tau, &Tc,
+                                 &p.recs[s].inc)))
+                return rc;
+            win_starts(g.tau, Tc, cs, n, Lh, g.skip_ms, (long long)want_runs * coh, wins[s]);
+            const int runs = (int)(wins[s].size() / (size_t)coh);
+            GPSMI_REQUIRE_IN(w.fn, runs >= 1, "a record has no run inside iq");
+            p.recs[s].prn = g.prn;
+            p.recs[s].count = runs;
+        }
+        p.max_runs = win_pad(wins, coh, p);
+        return GPSMI_OK;
+    });
 }
 
 }  // namespace gpsmi

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "gpsmi_common.h"
+#include "gpsmi_windows.h"
 
 namespace gpsmi {
 
@@ -261,45 +262,33 @@ struct RefPlan {
     std::vector<double> dfs;                      // [n_df]
 };
 
-// f / rate mod 1 in 0.64 fixed point (two's complement), as the front end's mixer increment
-inline unsigned long long ref_phase_inc(double f, double rate) {
-    double x = f / rate;
-    x -= std::floor(x);
-    long double scaled = std::ldexp((long double)x, 64);
-    if (scaled >= std::ldexp((long double)1.0, 64)) scaled = 0.0L;
-    return (unsigned long long)scaled;
-}
-
-#define REF_REQUIRE(cond, msg)                                                          \
-    do {                                                                                \
-        if (!(cond)) return ::gpsmi::fail(GPSMI_E_ARG, "gpsmi_acq_refine: %s", msg);    \
-    } while (0)
-
 // Validates the arguments of gpsmi_acq_refine (the handle aside) and fills the plan (pl may be null).
 inline int ref_plan(int cs, size_t n, const gpsmi_refine_hit* hits, int nhits, const gpsmi_refine_cfg* c,
                     RefPlan* pl) {
-    REF_REQUIRE(hits && c, "null argument");
-    REF_REQUIRE(nhits >= 1 && nhits <= kRefMaxHits, "nhits out of range 1..64");
-    REF_REQUIRE(c->n_ms >= 40 && c->n_ms % 20 == 0, "n_ms must be a multiple of 20, >= 40");
-    REF_REQUIRE(std::isfinite(c->carrier_hz) && c->carrier_hz > 0.0, "carrier_hz must be positive");
-    REF_REQUIRE(std::isfinite(c->f_offset_hz), "f_offset_hz must be finite");
-    REF_REQUIRE(c->df_step_hz >= 0.0 && std::isfinite(c->df_step_hz), "df_step_hz must be >= 0 (0: 2 Hz)");
-    REF_REQUIRE(c->df_half_hz >= 0.0 && std::isfinite(c->df_half_hz), "df_half_hz must be >= 0 (0: 120 Hz)");
-    REF_REQUIRE(c->tap_samples >= 0, "tap_samples must be >= 1 (0: the default)");
-    REF_REQUIRE(c->min_ratio >= 0.f, "min_ratio must be >= 0 (0: 2.5), not NaN");
+    static const char* const fn = "gpsmi_acq_refine";
+    GPSMI_REQUIRE_IN(fn, hits && c, "null argument");
+    GPSMI_REQUIRE_IN(fn, nhits >= 1 && nhits <= kRefMaxHits, "nhits out of range 1..64");
+    GPSMI_REQUIRE_IN(fn, c->n_ms >= 40 && c->n_ms % 20 == 0, "n_ms must be a multiple of 20, >= 40");
+    GPSMI_REQUIRE_IN(fn, std::isfinite(c->carrier_hz) && c->carrier_hz > 0.0, "carrier_hz must be positive");
+    GPSMI_REQUIRE_IN(fn, std::isfinite(c->f_offset_hz), "f_offset_hz must be finite");
+    GPSMI_REQUIRE_IN(fn, c->df_step_hz >= 0.0 && std::isfinite(c->df_step_hz), "df_step_hz must be >= 0 (0: 2 Hz)");
+    GPSMI_REQUIRE_IN(fn, c->df_half_hz >= 0.0 && std::isfinite(c->df_half_hz), "df_half_hz must be >= 0 (0: 120 Hz)");
+    GPSMI_REQUIRE_IN(fn, c->tap_samples >= 0, "tap_samples must be >= 1 (0: the default)");
+    GPSMI_REQUIRE_IN(fn, c->min_ratio >= 0.f, "min_ratio must be >= 0 (0: 2.5), not NaN");
     const double step = c->df_step_hz > 0.0 ? c->df_step_hz : 2.0;
     const double half = c->df_half_hz > 0.0 ? c->df_half_hz : 120.0;
     const double pts = std::floor(2.0 * half / step + 1e-9) + 1.0;
-    REF_REQUIRE(pts <= (double)kRefMaxDf, "more than 1024 grid points");
-    REF_REQUIRE(half < 500.0, "df_half_hz must stay below 500 Hz (the prompts are 1 ms apart)");
+    GPSMI_REQUIRE_IN(fn, pts <= (double)kRefMaxDf, "more than 1024 grid points");
+    GPSMI_REQUIRE_IN(fn, half < 500.0, "df_half_hz must stay below 500 Hz (the prompts are 1 ms apart)");
     if (cs != 2048 && cs != 16368)
         return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_refine: code_samples 2048 and 16368 only (%d)", cs);
     if (c->n_ms > GPSMI_REFINE_MAX_MS)
         return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_refine: n_ms %d beyond the %d the grid kernel's LDS holds",
                     c->n_ms, GPSMI_REFINE_MAX_MS);
     const int tap = c->tap_samples > 0 ? c->tap_samples : (cs == 2048 ? 1 : 8);
-    REF_REQUIRE(tap <= cs / 4, "tap_samples beyond a quarter of the code");
-    REF_REQUIRE(n >= ((size_t)c->n_ms + 2) * cs + tap, "iq shorter than (n_ms + 2) code periods + tap_samples");
+    GPSMI_REQUIRE_IN(fn, tap <= cs / 4, "tap_samples beyond a quarter of the code");
+    GPSMI_REQUIRE_IN(fn, n >= ((size_t)c->n_ms + 2) * cs + tap,
+                     "iq shorter than (n_ms + 2) code periods + tap_samples");
     const double fs = 1000.0 * cs;
     RefPlan tmp;
     RefPlan& p = pl ? *pl : tmp;
@@ -320,17 +309,17 @@ inline int ref_plan(int cs, size_t n, const gpsmi_refine_hit* hits, int nhits, c
     }
     for (int hdx = 0; hdx < nhits; ++hdx) {
         const gpsmi_refine_hit& g = hits[hdx];
-        REF_REQUIRE(g.prn >= 1 && g.prn <= GPSMI_MAX_PRN, "prn out of range 1..37");
-        REF_REQUIRE(g.delay >= 0 && g.delay < cs, "delay out of range 0..code_samples - 1");
-        REF_REQUIRE(std::isfinite(g.freq_hz) && std::fabs(g.freq_hz) < 0.5 * fs, "freq_hz out of range");
+        GPSMI_REQUIRE_IN(fn, g.prn >= 1 && g.prn <= GPSMI_MAX_PRN, "prn out of range 1..37");
+        GPSMI_REQUIRE_IN(fn, g.delay >= 0 && g.delay < cs, "delay out of range 0..code_samples - 1");
+        GPSMI_REQUIRE_IN(fn, std::isfinite(g.freq_hz) && std::fabs(g.freq_hz) < 0.5 * fs, "freq_hz out of range");
         const long long d0 = g.delay < tap ? (long long)g.delay + cs : g.delay;
         p.hits[hdx] = RefHit{ref_phase_inc(g.freq_hz, fs), g.freq_hz, g.prn, g.delay};
         for (int k = 0; k < c->n_ms; ++k) {
             // m[k] of gpsmi.h: float64 left to right, ties to even
             const double m = std::nearbyint(-(g.freq_hz - c->f_offset_hz) / c->carrier_hz * (double)k * (double)cs);
-            REF_REQUIRE(std::fabs(m) < 1e15, "code slide out of range");
+            GPSMI_REQUIRE_IN(fn, std::fabs(m) < 1e15, "code slide out of range");
             const long long nk = (long long)k * cs + d0 + (long long)m;
-            REF_REQUIRE(nk - tap >= 0 && (unsigned long long)(nk + cs + tap) <= (unsigned long long)n,
+            GPSMI_REQUIRE_IN(fn, nk - tap >= 0 && (unsigned long long)(nk + cs + tap) <= (unsigned long long)n,
                         "a window of the code slide leaves iq");
             p.start[(size_t)hdx * c->n_ms + k] = nk;
             if ((size_t)(nk + cs + tap) > p.hi) p.hi = (size_t)(nk + cs + tap);

@@ -19,6 +19,7 @@
 #include "gpsmi_common.h"
 #include "gpsmi_cancel.h"
 #include "gpsmi_refine.h"
+#include "gpsmi_windows.h"
 
 namespace gpsmi {
 
@@ -26,11 +27,6 @@ constexpr int kSigMaxAnt = 8;
 constexpr int kSigMaxSats = 64;
 constexpr int kSigWinPerWg = 8;
 constexpr int kSigPairs = kSigMaxAnt * (kSigMaxAnt + 1) / 2;
-
-struct SigRec {                                   // one record as the kernels see it
-    unsigned long long inc;                       // f_hz / fs in 0.64 fixed point
-    int prn, n_win;
-};
 
 // LDS of sig_prompt_kernel: the replica [cs], then the waves' partial sums [kSigWinPerWg][4][2 kSigMaxAnt]
 inline size_t sig_lds_bytes(int cs) {
@@ -42,19 +38,19 @@ inline size_t sig_lds_bytes(int cs) {
 template <int FMT>
 __global__ __launch_bounds__(256) void sig_prompt_kernel(
     const void* __restrict__ iq, size_t n, int A, const float* __restrict__ rep_time,
-    const SigRec* __restrict__ recs, const long long* __restrict__ start, int cs, int max_w,
+    const WinRec* __restrict__ recs, const long long* __restrict__ start, int cs, int max_w,
     float2* __restrict__ P) {
     extern __shared__ __attribute__((aligned(16))) float sig_lds[];
     float* rep = sig_lds;
     float* red = sig_lds + cs;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int rec = blockIdx.y, k0 = blockIdx.x * kSigWinPerWg;
-    const SigRec rr = recs[rec];
-    if (k0 >= rr.n_win) return;                   // (the whole workgroup: nothing of it is waited for)
+    const WinRec rr = recs[rec];
+    if (k0 >= rr.count) return;                   // (the whole workgroup: nothing of it is waited for)
     const float* R = rep_time + (size_t)rr.prn * cs;
     for (int i = t; i < cs; i += 256) rep[i] = R[i];
     __syncthreads();
-    const int nk = rr.n_win - k0 < kSigWinPerWg ? rr.n_win - k0 : kSigWinPerWg;
+    const int nk = rr.count - k0 < kSigWinPerWg ? rr.count - k0 : kSigWinPerWg;
     for (int q = 0; q < nk; ++q) {
         const long long j0 = start[(size_t)rec * max_w + k0 + q];
         float acc[2 * kSigMaxAnt];
@@ -106,11 +102,11 @@ __device__ __forceinline__ double sig_wave_sum(double v) {
 }
 
 // C[rec][a][b] = sum_k P[rec][a][k] conj(P[rec][b][k]), float64 [nsat][A][A][2]
-__global__ __launch_bounds__(256) void sig_cov_kernel(const float2* __restrict__ P, const SigRec* __restrict__ recs,
+__global__ __launch_bounds__(256) void sig_cov_kernel(const float2* __restrict__ P, const WinRec* __restrict__ recs,
                                                       int A, int max_w, double* __restrict__ cov) {
     __shared__ double red[4][2 * kSigPairs];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, rec = blockIdx.x;
-    const int n_win = recs[rec].n_win;
+    const int n_win = recs[rec].count;
     const float2* Pr = P + (size_t)rec * A * max_w;
     int p = 0;
     for (int a = 0; a < A; ++a) {
@@ -149,90 +145,48 @@ __global__ __launch_bounds__(256) void sig_cov_kernel(const float2* __restrict__
 }
 
 // ---- the plan: everything a call derives from its arguments, on the host, no GPU --------------
-struct SigPlan {
+struct SigPlan : WinTable {                       // recs[].count: a record's windows; start [nsat][max_windows]
     int cs = 0, A = 0, max_windows = 0;
-    std::vector<SigRec> recs;                     // [nsat]
-    std::vector<long long> start;                 // [nsat][max_windows], 0 past a record's last window
 };
 
-// the first k with lo <= j_k = rint(tau + k Tc) (cancellation's edges: float64, unfused); shared with
-// the profiles (gpsmi_profile.h), whose windows keep lo = half_taps samples in hand
-inline long long sig_first_window(double tau, double Tc, int lo) {
-    long long k = (long long)std::floor(((double)lo - tau) / Tc);
-    while (std::nearbyint(cancel_edge(tau, Tc, k)) >= (double)lo) --k;
-    while (std::nearbyint(cancel_edge(tau, Tc, k)) < (double)lo) ++k;
-    return k;
-}
-
-#define SIG_REQUIRE(cond, msg)                                                             \
-    do {                                                                                   \
-        if (!(cond)) return ::gpsmi::fail(GPSMI_E_ARG, "gpsmi_acq_signature: %s", msg);    \
-    } while (0)
-
 // Validates the arguments of gpsmi_acq_signature (the handle and the buffers aside) and fills the plan
-// (pl may be null).
+// (pl may be null).  The windows are the window rule's (gpsmi_windows.h) with no guard: whole periods
+// at their rounded starts, n_ms of them at the most.
 inline int sig_plan(int cs, size_t n, const gpsmi_sig_sat* sats, int nsat, const gpsmi_sig_cfg* c, SigPlan* pl) {
-    SIG_REQUIRE(nsat >= 1 && nsat <= kSigMaxSats, "nsat out of range 1..64");
-    SIG_REQUIRE(sats, "null argument");
-    double carrier = 1575.42e6, f_offset = 0.0;
-    int A = 2, n_ms = 0;
-    if (c) {
-        SIG_REQUIRE(c->antennas == 0 || (c->antennas >= 2 && c->antennas <= kSigMaxAnt),
-                    "antennas out of range 2..8 (0: 2)");
-        SIG_REQUIRE(c->n_ms >= 0, "n_ms must be >= 1 (0: every window that fits)");
-        SIG_REQUIRE(std::isfinite(c->carrier_hz) && c->carrier_hz >= 0.0, "carrier_hz must be positive (0: L1)");
-        SIG_REQUIRE(std::isfinite(c->f_offset_hz), "f_offset_hz must be finite");
-        if (c->antennas > 0) A = c->antennas;
-        n_ms = c->n_ms;
-        if (c->carrier_hz > 0.0) carrier = c->carrier_hz;
-        f_offset = c->f_offset_hz;
-    }
-    SIG_REQUIRE(n >= 1 && n <= ((size_t)1 << 40) / (size_t)A, "n out of range 1..2^40 / antennas");
-    if (cs != 2048 && cs != 16368)
-        return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_signature: code_samples 2048 and 16368 only (%d)", cs);
-    const double fs = 1000.0 * cs;
-    SigPlan tmp;
-    SigPlan& p = pl ? *pl : tmp;
-    p.cs = cs; p.A = A; p.max_windows = 0;
-    std::vector<std::vector<long long>> wins;
-    try {
-        p.recs.assign(nsat, SigRec{0ull, 0, 0});
-        wins.resize(nsat);
-    } catch (const std::bad_alloc&) {
-        return fail(GPSMI_E_NOMEM, "gpsmi_acq_signature: out of host memory");
-    }
-    for (int s = 0; s < nsat; ++s) {
-        const gpsmi_sig_sat& g = sats[s];
-        SIG_REQUIRE(g.prn >= 1 && g.prn <= GPSMI_MAX_PRN, "prn out of range 1..37");
-        SIG_REQUIRE(g.reserved == 0, "a reserved field is not 0");
-        SIG_REQUIRE(std::isfinite(g.f_hz) && std::fabs(g.f_hz) < 0.5 * fs, "f_hz out of range");
-        SIG_REQUIRE(std::isfinite(g.tau) && std::fabs(g.tau) < 1e15, "tau out of range");
-        const double scale = 1.0 + (g.f_hz - f_offset) / carrier;
-        SIG_REQUIRE(scale > 0.99 && scale < 1.01, "f_hz - f_offset_hz beyond 1 % of carrier_hz");
-        const double Tc = (double)cs / scale;
-        long long k = sig_first_window(g.tau, Tc, 0);
-        try {
-            for (;; ++k) {
-                const long long j = (long long)std::nearbyint(cancel_edge(g.tau, Tc, k));
-                if ((unsigned long long)(j + cs) > (unsigned long long)n) break;
-                if (n_ms > 0 && (long long)wins[s].size() >= n_ms) break;
-                wins[s].push_back(j);
-            }
-        } catch (const std::bad_alloc&) {
-            return fail(GPSMI_E_NOMEM, "gpsmi_acq_signature: out of host memory");
+    WinCall w{"gpsmi_acq_signature"};
+    return win_guarded(w.fn, [&]() -> int {
+        GPSMI_REQUIRE_IN(w.fn, nsat >= 1 && nsat <= kSigMaxSats, "nsat out of range 1..64");
+        GPSMI_REQUIRE_IN(w.fn, sats, "null argument");
+        int rc, A = 2, n_ms = 0;
+        if (c) {
+            GPSMI_REQUIRE_IN(w.fn, c->antennas == 0 || (c->antennas >= 2 && c->antennas <= kSigMaxAnt),
+                             "antennas out of range 2..8 (0: 2)");
+            GPSMI_REQUIRE_IN(w.fn, c->n_ms >= 0, "n_ms must be >= 1 (0: every window that fits)");
+            if ((rc = win_cfg(w, c->carrier_hz, c->f_offset_hz))) return rc;
+            if (c->antennas > 0) A = c->antennas;
+            n_ms = c->n_ms;
         }
-        SIG_REQUIRE(!wins[s].empty(), "a record has no window inside iq");
-        p.recs[s] = SigRec{ref_phase_inc(g.f_hz, fs), g.prn, (int)wins[s].size()};
-        if ((int)wins[s].size() > p.max_windows) p.max_windows = (int)wins[s].size();
-    }
-    try {
-        p.start.assign((size_t)nsat * p.max_windows, 0ll);
-    } catch (const std::bad_alloc&) {
-        return fail(GPSMI_E_NOMEM, "gpsmi_acq_signature: out of host memory");
-    }
-    for (int s = 0; s < nsat; ++s)
-        for (size_t k = 0; k < wins[s].size(); ++k) p.start[(size_t)s * p.max_windows + k] = wins[s][k];
-    return GPSMI_OK;
+        GPSMI_REQUIRE_IN(w.fn, n >= 1 && n <= ((size_t)1 << 40) / (size_t)A, "n out of range 1..2^40 / antennas");
+        if ((rc = win_code(w, cs))) return rc;
+        SigPlan tmp;
+        SigPlan& p = pl ? *pl : tmp;
+        p.cs = cs; p.A = A;
+        p.recs.assign(nsat, WinRec{0ull, 0, 0});
+        std::vector<std::vector<long long>> wins(nsat);
+        for (int s = 0; s < nsat; ++s) {
+            const gpsmi_sig_sat& g = sats[s];
+            double Tc;
+            if ((rc = win_record(w, g.prn, g.reserved != 0 ? "a reserved field is not 0" : nullptr, g.f_hz, g.tau, &Tc,
+                                 &p.recs[s].inc)))
+                return rc;
+            win_starts(g.tau, Tc, cs, n, 0, 0, n_ms, wins[s]);
+            GPSMI_REQUIRE_IN(w.fn, !wins[s].empty(), "a record has no window inside iq");
+            p.recs[s].prn = g.prn;
+            p.recs[s].count = (int)wins[s].size();
+        }
+        p.max_windows = win_pad(wins, 1, p);
+        return GPSMI_OK;
+    });
 }
 
 }  // namespace gpsmi

@@ -206,40 +206,37 @@ __global__ __launch_bounds__(256) void wtrk_kernel(
 }
 
 // ---- the plan: the argument checks and the gains, on the host, no GPU ---------------------------
-#define WTRK_REQUIRE(cond, msg)                                                         \
-    do {                                                                                \
-        if (!(cond)) return ::gpsmi::fail(GPSMI_E_ARG, "gpsmi_acq_track: %s", msg);     \
-    } while (0)
-
 inline int wtrk_default_tap(int cs) { return cs == 2048 ? 1 : 8; }
 
 // Validates the arguments of gpsmi_acq_track (the handle aside) and fills the kernel's parameters.
 inline int wtrk_plan(int cs, size_t n, const gpsmi_wtrk_state* st, int nhits, const gpsmi_wtrk_cfg* c,
                      WtrkPar* par) {
-    WTRK_REQUIRE(st && c, "null argument");
-    WTRK_REQUIRE(nhits >= 1 && nhits <= kWtrkMaxHits, "nhits out of range 1..64");
-    WTRK_REQUIRE(c->n_bits >= 1 && c->n_bits <= kWtrkMaxBits, "n_bits out of range 1..2^20");
-    WTRK_REQUIRE(std::isfinite(c->carrier_hz) && c->carrier_hz > 0.0, "carrier_hz must be positive");
-    WTRK_REQUIRE(std::isfinite(c->f_offset_hz), "f_offset_hz must be finite");
-    WTRK_REQUIRE(std::isfinite(c->pll_bw_hz) && std::isfinite(c->fll_bw_hz), "pll_bw_hz / fll_bw_hz must be finite");
-    WTRK_REQUIRE(std::isfinite(c->dll_bw_hz) && c->dll_bw_hz >= 0.0, "dll_bw_hz must be >= 0 (0: the default)");
-    WTRK_REQUIRE(c->tap_samples >= 0, "tap_samples must be >= 1 (0: the default)");
-    WTRK_REQUIRE(n >= 1 && n < (size_t(1) << 52), "n out of range");
-    WTRK_REQUIRE(c->first_sample > -(int64_t(1) << 52) && c->first_sample < (int64_t(1) << 52),
+    static const char* const fn = "gpsmi_acq_track";
+    GPSMI_REQUIRE_IN(fn, st && c, "null argument");
+    GPSMI_REQUIRE_IN(fn, nhits >= 1 && nhits <= kWtrkMaxHits, "nhits out of range 1..64");
+    GPSMI_REQUIRE_IN(fn, c->n_bits >= 1 && c->n_bits <= kWtrkMaxBits, "n_bits out of range 1..2^20");
+    GPSMI_REQUIRE_IN(fn, std::isfinite(c->carrier_hz) && c->carrier_hz > 0.0, "carrier_hz must be positive");
+    GPSMI_REQUIRE_IN(fn, std::isfinite(c->f_offset_hz), "f_offset_hz must be finite");
+    GPSMI_REQUIRE_IN(fn, std::isfinite(c->pll_bw_hz) && std::isfinite(c->fll_bw_hz),
+                     "pll_bw_hz / fll_bw_hz must be finite");
+    GPSMI_REQUIRE_IN(fn, std::isfinite(c->dll_bw_hz) && c->dll_bw_hz >= 0.0, "dll_bw_hz must be >= 0 (0: the default)");
+    GPSMI_REQUIRE_IN(fn, c->tap_samples >= 0, "tap_samples must be >= 1 (0: the default)");
+    GPSMI_REQUIRE_IN(fn, n >= 1 && n < (size_t(1) << 52), "n out of range");
+    GPSMI_REQUIRE_IN(fn, c->first_sample > -(int64_t(1) << 52) && c->first_sample < (int64_t(1) << 52),
                  "first_sample out of range");
     if (cs != 2048 && cs != 16368)
         return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_track: code_samples 2048 and 16368 only (%d)", cs);
     const int tap = c->tap_samples > 0 ? c->tap_samples : wtrk_default_tap(cs);
-    WTRK_REQUIRE((double)tap < (double)cs / 1023.0, "tap_samples must stay below one chip");
+    GPSMI_REQUIRE_IN(fn, (double)tap < (double)cs / 1023.0, "tap_samples must stay below one chip");
     const double fs = 1000.0 * cs;
     for (int i = 0; i < nhits; ++i) {
         const gpsmi_wtrk_state& s = st[i];
-        WTRK_REQUIRE(s.prn >= 1 && s.prn <= GPSMI_MAX_PRN, "prn out of range 1..37");
-        WTRK_REQUIRE(s.bit_no >= 0, "bit_no must be >= 0");
-        WTRK_REQUIRE(std::isfinite(s.f_hz) && std::fabs(s.f_hz) < 0.5 * fs, "f_hz out of range");
-        WTRK_REQUIRE(std::isfinite(s.f_acc), "f_acc must be finite");
-        WTRK_REQUIRE(std::isfinite(s.tau) && std::fabs(s.tau) < 0x1p52, "tau out of range");
-        WTRK_REQUIRE(std::floor(s.tau) - (double)tap >= (double)c->first_sample,
+        GPSMI_REQUIRE_IN(fn, s.prn >= 1 && s.prn <= GPSMI_MAX_PRN, "prn out of range 1..37");
+        GPSMI_REQUIRE_IN(fn, s.bit_no >= 0, "bit_no must be >= 0");
+        GPSMI_REQUIRE_IN(fn, std::isfinite(s.f_hz) && std::fabs(s.f_hz) < 0.5 * fs, "f_hz out of range");
+        GPSMI_REQUIRE_IN(fn, std::isfinite(s.f_acc), "f_acc must be finite");
+        GPSMI_REQUIRE_IN(fn, std::isfinite(s.tau) && std::fabs(s.tau) < 0x1p52, "tau out of range");
+        GPSMI_REQUIRE_IN(fn, std::floor(s.tau) - (double)tap >= (double)c->first_sample,
                      "a state's next bit starts before first_sample");
     }
     if (!par) return GPSMI_OK;

@@ -162,10 +162,7 @@ class Acquisition:
         order cancelled)."""
         rec = np.atleast_1d(np.asarray(rec))
         order = np.argsort(-np.nan_to_num(rec['cn0_dbhz'].astype(np.float64), nan=-np.inf), kind='stable')
-        start = rec['sample'].astype(np.float64) if 'sample' in rec.dtype.names else 0.0
-        tau = start + rec['code_phase'].astype(np.float64)
-        sats = [(int(rec['prn'][i]), float(rec['f_hz'][i]), float(tau[i])) for i in order]
-        return self.engine.cancel(data, sats, out=out, f_offset=f_offset)
+        return self.engine.cancel(data, signature_sats(rec[order]), out=out, f_offset=f_offset)
 
     def signatureHits(self, data, rec, antennas, f_offset=0.0, **cfg):
         """The spatial signatures of the records `rec` over `antennas` coherent channels
@@ -206,13 +203,19 @@ class Acquisition:
         return self.engine.search(data, prns, freqs, n_avg)
 
 
-def signature_sats(rec):
-    """(prn, f_hz, tau) of records of refineHits or snapshot.MEAS_DTYPE, tau = sample + code_phase
-    as in cancelHits, in the order given.  Host only."""
+def code_starts(rec):
+    """tau float64 [R] of records of refineHits (code_phase is the code start at the first sample) or
+    snapshot.MEAS_DTYPE (a code start lies at sample + code_phase).  Host only."""
     rec = np.atleast_1d(np.asarray(rec))
     start = rec['sample'].astype(np.float64) if 'sample' in rec.dtype.names else 0.0
-    tau = start + rec['code_phase'].astype(np.float64)
-    return [(int(rec['prn'][i]), float(rec['f_hz'][i]), float(tau[i])) for i in range(len(rec))]
+    return start + rec['code_phase'].astype(np.float64)
+
+
+def signature_sats(rec):
+    """(prn, f_hz, tau) of records of refineHits or snapshot.MEAS_DTYPE, tau as code_starts gives
+    it, in the order given.  Host only."""
+    rec = np.atleast_1d(np.asarray(rec))
+    return [(int(r['prn']), float(r['f_hz']), float(t)) for r, t in zip(rec, code_starts(rec))]
 
 
 def profile_sats(rec, cs, half_taps=0, f_offset=0.0, carrier_hz=L1_HZ):
@@ -225,10 +228,9 @@ def profile_sats(rec, cs, half_taps=0, f_offset=0.0, carrier_hz=L1_HZ):
     Lh = int(half_taps) or (8 if cs == 2048 else 32)
     meas = 'sample' in rec.dtype.names
     out = []
-    for r in rec:
+    for r, tau in zip(rec, code_starts(rec).tolist()):
         f = float(r['f_hz'])
         Tc = cs / (1.0 + (f - f_offset) / carrier_hz)
-        tau = float(r['sample']) + float(r['code_phase']) if meas else float(r['code_phase'])
         edge = float(r['edge']) if meas else tau + float(r['edge_ms']) * Tc if r['edge_ms'] >= 0 else np.nan
         k = int(np.floor((Lh - tau) / Tc))
         while np.rint(tau + float(k) * Tc) >= Lh:

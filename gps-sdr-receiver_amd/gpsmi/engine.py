@@ -182,48 +182,49 @@ def peaks_plan(code_samples, nsv_rows, nbins, k=4, guard_lags=-1, bins=None):
     return scratch.value, wgs.value
 
 
-def _sig_args(sats, antennas, n_ms, f_offset, carrier_hz):
-    """The records and the options of a signature call (gpsmi_sig_sat [R], gpsmi_sig_cfg)."""
-    s_a = np.zeros(len(sats), dtype=_lib.SIG_SAT_DTYPE)
-    for i, (prn, f_hz, tau) in enumerate(sats):
-        s_a[i] = (int(prn), 0, float(f_hz), float(tau))
-    return s_a, _lib.SigCfg(int(antennas), int(n_ms), float(carrier_hz), float(f_offset))
+def _records(sats, dtype):
+    """Refined records as the table a stage takes: (prn, f_hz, tau), or (prn, skip_ms, f_hz, tau)
+    where the stage has a second int32 (CANCEL_SAT_DTYPE, SIG_SAT_DTYPE and PROF_SAT_DTYPE are one
+    layout; the field is `reserved`, 0, in the first two)."""
+    s_a = np.zeros(len(sats), dtype=dtype)
+    for i, s in enumerate(sats):
+        prn, second, f_hz, tau = s if len(s) == 4 else (s[0], 0, s[1], s[2])
+        s_a[i] = (int(prn), int(second), float(f_hz), float(tau))
+    return s_a
+
+
+def _sig_cfg(antennas, n_ms, f_offset, carrier_hz):
+    return _lib.SigCfg(int(antennas), int(n_ms), float(carrier_hz), float(f_offset))
+
+
+def _prof_cfg(half_taps, coh_ms, n_runs, f_offset, carrier_hz):
+    return _lib.ProfCfg(int(half_taps), int(coh_ms), int(n_runs), 0, float(carrier_hz), float(f_offset))
+
+
+def _counts_plan(lib, name, code_samples, n, s_a, cfg, n_extra):
+    """A `_plan` export that writes a count per record and n_extra ints behind them -> (counts int32
+    [R], the ints...)."""
+    counts = np.zeros(max(len(s_a), 1), np.int32)
+    extra = [C.c_int(0) for _ in range(n_extra)]
+    check(getattr(lib, name)(int(code_samples), int(n), ptr(s_a), len(s_a), C.byref(cfg), ptr(counts),
+                             *map(C.byref, extra)), name)
+    return (counts[:len(s_a)], *(e.value for e in extra))
 
 
 def signature_plan(code_samples, n, sats, antennas, n_ms=0, f_offset=0.0, carrier_hz=1575.42e6):
     """gpsmi_acq_signature_plan: the argument checks of AcqEngine.signatures without a GPU, for
     rows of `n` samples.  -> (n_win int32 [R], max_windows); EngineError where the call would
     refuse."""
-    s_a, cfg = _sig_args(sats, antennas, n_ms, f_offset, carrier_hz)
-    n_win = np.zeros(max(len(s_a), 1), np.int32)
-    max_w = C.c_int(0)
-    check(_lib.load().gpsmi_acq_signature_plan(int(code_samples), int(n), ptr(s_a), len(s_a), C.byref(cfg),
-                                               ptr(n_win), C.byref(max_w)), 'gpsmi_acq_signature_plan')
-    return n_win[:len(s_a)], max_w.value
-
-
-def _prof_args(sats, half_taps, coh_ms, n_runs, f_offset, carrier_hz):
-    """The records and the options of a profile call (gpsmi_prof_sat [R], gpsmi_prof_cfg)."""
-    s_a = np.zeros(len(sats), dtype=_lib.PROF_SAT_DTYPE)
-    for i, (prn, skip_ms, f_hz, tau) in enumerate(sats):
-        s_a[i] = (int(prn), int(skip_ms), float(f_hz), float(tau))
-    return s_a, _lib.ProfCfg(int(half_taps), int(coh_ms), int(n_runs), 0, float(carrier_hz), float(f_offset))
-
-
-def _prof_plan(lib, code_samples, n, s_a, cfg):
-    n_runs = np.zeros(max(len(s_a), 1), np.int32)
-    max_r, taps = C.c_int(0), C.c_int(0)
-    check(lib.gpsmi_acq_profile_plan(int(code_samples), int(n), ptr(s_a), len(s_a), C.byref(cfg), ptr(n_runs),
-                                     C.byref(max_r), C.byref(taps)), 'gpsmi_acq_profile_plan')
-    return n_runs[:len(s_a)], max_r.value, taps.value
+    return _counts_plan(_lib.load(), 'gpsmi_acq_signature_plan', code_samples, n, _records(sats, _lib.SIG_SAT_DTYPE),
+                        _sig_cfg(antennas, n_ms, f_offset, carrier_hz), 1)
 
 
 def profiles_plan(code_samples, n, sats, half_taps=0, coh_ms=0, n_runs=0, f_offset=0.0, carrier_hz=1575.42e6):
     """gpsmi_acq_profile_plan: the argument checks of AcqEngine.profiles without a GPU, for `n`
     samples.  sats: [(prn, skip_ms, f_hz, tau)].  -> (n_runs int32 [R], max_runs, taps K);
     EngineError where the call would refuse."""
-    s_a, cfg = _prof_args(sats, half_taps, coh_ms, n_runs, f_offset, carrier_hz)
-    return _prof_plan(_lib.load(), code_samples, n, s_a, cfg)
+    return _counts_plan(_lib.load(), 'gpsmi_acq_profile_plan', code_samples, n, _records(sats, _lib.PROF_SAT_DTYPE),
+                        _prof_cfg(half_taps, coh_ms, n_runs, f_offset, carrier_hz), 2)
 
 
 def _iq_dtype(raw_u8):
@@ -281,15 +282,22 @@ class AcqEngine:
     def _host_iq(self, iq):
         return _host_block(iq, self.raw_u8, 'iq')
 
-    def _input(self, iq, nbr=False):
+    def _input(self, iq, nbr=False, lead=None):
         """iq of any entry point -> (pointer, n, host?): a host array in the input format, or a
-        (c_void_p, n) device pair as it is (the neighbours `nbr` come back for host input only)."""
+        (c_void_p, n) device pair as it is (the neighbours `nbr` come back for host input only).
+        lead: the shape a host array must have in front of its n samples -- () for one row, (A,) for
+        one row per antenna; None: any shape, n all its samples."""
         if isinstance(iq, tuple):
             if nbr:
                 raise ValueError('nbr is returned for host input only')
-            return iq[0], iq[1], False
+            return iq[0], int(iq[1]), False
         iq = self._host_iq(iq)
-        return ptr(iq), iq.size, True              # (the pointer keeps the array alive)
+        if lead is None:
+            return ptr(iq), iq.size, True          # (the pointer keeps the array alive)
+        if iq.ndim != len(lead) + 1 or iq.shape[:-1] != lead:
+            raise ValueError('data must be ' + (f'[{lead[0]}][n], one row per antenna' if lead else
+                                                'one row of samples'))
+        return ptr(iq), iq.shape[-1], True
 
     @staticmethod
     def _tables(prns, freqs, nbr=False):
@@ -489,9 +497,7 @@ class AcqEngine:
         [n], None = in place (complex64 input only).  Returns (out, records CANCEL_OUT_DTYPE
         [nsat]), and with coef=True the windows' coefficients complex64 [nsat, max_windows, 3]
         behind them."""
-        s_a = np.zeros(len(sats), dtype=CANCEL_SAT_DTYPE)
-        for i, (prn, f_hz, tau) in enumerate(sats):
-            s_a[i] = (int(prn), 0, float(f_hz), float(tau))
+        s_a = _records(sats, CANCEL_SAT_DTYPE)
         self._need_time_replicas(s_a['prn'])
         cfg = _lib.CancelCfg(float(carrier_hz), float(f_offset), int(min_window), 0)
         d_iq, n, host = self._input(data)
@@ -523,25 +529,24 @@ class AcqEngine:
         Returns (cov complex128 [R][A][A], n_win int32 [R]) and with prompts=True the prompts
         complex64 [R][A][max_windows] behind them (zero past a record's last window)."""
         A = int(antennas)
-        s_a, cfg = _sig_args(sats, A, n_ms, f_offset, carrier_hz)
+        return self._cov_stage('gpsmi_acq_signature', data, (A,), _records(sats, _lib.SIG_SAT_DTYPE),
+                               _sig_cfg(A, n_ms, f_offset, carrier_hz), A, prompts)
+
+    def _cov_stage(self, name, data, lead, s_a, cfg, D, sums):
+        """signatures and profiles behind their arguments: the `_plan` export sizes the results (the
+        width of the sums, and behind it the order D of the covariances where D is None), then the
+        call.  -> (cov complex128 [R][D][D], counts int32 [R]) and with `sums` the sums complex64
+        [R][D][width] behind them."""
         self._need_time_replicas(s_a['prn'])
-        if isinstance(data, tuple):
-            d_iq, n, host = data[0], int(data[1]), False
-        else:
-            rows = self._host_iq(data)
-            if rows.ndim != 2 or rows.shape[0] != A:
-                raise ValueError(f'data must be [{A}][n], one row per antenna')
-            d_iq, n, host = ptr(rows), rows.shape[1], True
-        n_win = np.zeros(max(len(s_a), 1), np.int32)
-        max_w = C.c_int(0)
-        check(self.lib.gpsmi_acq_signature_plan(self.cfg.code_samples, n, ptr(s_a), len(s_a), C.byref(cfg),
-                                                ptr(n_win), C.byref(max_w)), 'gpsmi_acq_signature_plan')
-        n_win = n_win[:len(s_a)]
-        cov = np.zeros((len(s_a), A, A), np.complex128)
-        pr = np.zeros((len(s_a), A, max_w.value), np.complex64) if prompts else None
-        fn, name = self._export('gpsmi_acq_signature', host)
-        check(fn(self.h, d_iq, n, ptr(s_a), len(s_a), C.byref(cfg), ptr(cov), ptr(n_win), ptr(pr)), name)
-        return (cov, n_win, pr) if prompts else (cov, n_win)
+        d_iq, n, host = self._input(data, lead=lead)
+        counts, width, *order = _counts_plan(self.lib, name + '_plan', self.cfg.code_samples, n, s_a, cfg,
+                                             2 if D is None else 1)
+        D = order[0] if D is None else D
+        cov = np.zeros((len(s_a), D, D), np.complex128)
+        sm = np.zeros((len(s_a), D, width), np.complex64) if sums else None
+        fn, name = self._export(name, host)
+        check(fn(self.h, d_iq, n, ptr(s_a), len(s_a), C.byref(cfg), ptr(cov), ptr(counts), ptr(sm)), name)
+        return (cov, counts, sm) if sums else (cov, counts)
 
     def profiles(self, data, sats, half_taps=0, coh_ms=0, n_runs=0, f_offset=0.0, carrier_hz=L1_HZ, sums=False):
         """Multi-tap correlation profiles on one antenna (gpsmi_acq_profile): per
@@ -553,21 +558,9 @@ class AcqEngine:
         default (8 taps either side at 2048, 32 at 16368; 20 ms; every run that fits).
         Returns (cov complex128 [R][K][K], n_runs int32 [R]) and with sums=True the sums complex64
         [R][K][max_runs] behind them (zero past a record's last run)."""
-        s_a, cfg = _prof_args(sats, half_taps, coh_ms, n_runs, f_offset, carrier_hz)
-        self._need_time_replicas(s_a['prn'])
-        if isinstance(data, tuple):
-            d_iq, n, host = data[0], int(data[1]), False
-        else:
-            row = self._host_iq(data)
-            if row.ndim != 1:
-                raise ValueError('data must be one row of samples')
-            d_iq, n, host = ptr(row), row.shape[0], True
-        runs, max_r, K = _prof_plan(self.lib, self.cfg.code_samples, n, s_a, cfg)
-        cov = np.zeros((len(s_a), K, K), np.complex128)
-        sm = np.zeros((len(s_a), K, max_r), np.complex64) if sums else None
-        fn, name = self._export('gpsmi_acq_profile', host)
-        check(fn(self.h, d_iq, n, ptr(s_a), len(s_a), C.byref(cfg), ptr(cov), ptr(runs), ptr(sm)), name)
-        return (cov, runs, sm) if sums else (cov, runs)
+        return self._cov_stage('gpsmi_acq_profile', data, (), _records(sats, _lib.PROF_SAT_DTYPE),
+                               _prof_cfg(half_taps, coh_ms, n_runs, f_offset, carrier_hz),
+                               None, sums)
 
     def search_async(self, d_iq, n, prns, freqs, n_avg, out, out_dev=None):
         """Enqueue a search on device-resident iq; `out` is a pinned PEAK_DTYPE

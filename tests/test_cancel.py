@@ -124,23 +124,31 @@ def test_argument_errors_need_no_gpu():
     ok = [(4, 3094.0, 17.5)]
     n = 5 * 2048
     assert _plan(2048, n, ok)[0] == 0
-    assert _plan(2048, n, ok * 33)[0] == E_ARG                    # nsat beyond 32 (and a PRN twice)
-    assert _plan(2048, n, [(p, 0.0, 0.0) for p in range(1, 34)])[0] == E_ARG
+    def refused(code, reason, *args):              # (max_windows is left as it was)
+        assert _plan(*args) == (code, -7, 'gpsmi_acq_cancel: ' + reason), (args, _plan(*args))
+    refused(E_ARG, 'nsat out of range 0..32', 2048, n, ok * 33)   # nsat beyond 32 (and a PRN twice)
+    refused(E_ARG, 'nsat out of range 0..32', 2048, n, [(p, 0.0, 0.0) for p in range(1, 34)])
     assert _plan(2048, n, [(p, 0.0, 0.0) for p in range(1, 33)])[0] == 0
-    for bad in ((0, 0.0, 0.0), (38, 0.0, 0.0), (4, np.nan, 0.0), (4, np.inf, 0.0), (4, 0.0, np.nan),
-                (4, 0.0, -np.inf), (4, 1.1e6, 0.0)):
-        rc, _, msg = _plan(2048, n, [bad])
-        assert rc == E_ARG and 'gpsmi_acq_cancel' in msg, (bad, msg)
-    rc, _, msg = _plan(2048, n, [(4, 0.0, 0.0), (5, 1.0, 2.0), (4, 3.0, 4.0)])
-    assert rc == E_ARG and 'twice' in msg
-    assert _plan(2048, 0, ok)[0] == E_ARG
+    for bad, reason in (((0, 0.0, 0.0), 'prn out of range 1..37'), ((38, 0.0, 0.0), 'prn out of range 1..37'),
+                        ((4, np.nan, 0.0), 'f_hz out of range'), ((4, np.inf, 0.0), 'f_hz out of range'),
+                        ((4, 0.0, np.nan), 'tau out of range'), ((4, 0.0, -np.inf), 'tau out of range'),
+                        ((4, 1.1e6, 0.0), 'f_hz out of range')):
+        refused(E_ARG, reason, 2048, n, [bad])
+    refused(E_ARG, 'a PRN appears twice', 2048, n, [(4, 0.0, 0.0), (5, 1.0, 2.0), (4, 3.0, 4.0)])
+    refused(E_ARG, 'n out of range 1..2^40', 2048, 0, ok)
+    refused(E_ARG, 'f_hz - f_offset_hz beyond 1 % of carrier_hz', 2048, n, [(4, 900000.0, 0.0)],
+            _lib.CancelCfg(1.0e7, 0.0, 0, 0))
     for cs in (1024, 4096, 16384):
-        assert _plan(cs, n, ok)[0] == E_UNSUPPORTED
+        refused(E_UNSUPPORTED, f'code_samples 2048 and 16368 only ({cs})', cs, n, ok)
     assert _plan(16368, n, ok)[0] == 0
-    for cfg in (_lib.CancelCfg(-1.0, 0.0, 0, 0), _lib.CancelCfg(np.nan, 0.0, 0, 0),
-                _lib.CancelCfg(0.0, np.inf, 0, 0), _lib.CancelCfg(0.0, 0.0, -1, 0)):
-        assert _plan(2048, n, ok, cfg)[0] == E_ARG
+    for cfg, reason in ((_lib.CancelCfg(-1.0, 0.0, 0, 0), 'carrier_hz must be positive (0: L1)'),
+                        (_lib.CancelCfg(np.nan, 0.0, 0, 0), 'carrier_hz must be positive (0: L1)'),
+                        (_lib.CancelCfg(0.0, np.inf, 0, 0), 'f_offset_hz must be finite'),
+                        (_lib.CancelCfg(0.0, 0.0, -1, 0), 'min_window must be >= 1 (0: 16)')):
+        refused(E_ARG, reason, 2048, n, ok, cfg)
     assert _plan(2048, n, ok, _lib.CancelCfg(0.0, 0.0, 0, 0))[0] == 0
     lib = _lib.load()
     assert lib.gpsmi_acq_cancel_plan(2048, n, None, 1, None, None) == E_ARG
+    assert lib.gpsmi_last_error().decode() == 'gpsmi_acq_cancel: null argument'
     assert lib.gpsmi_acq_cancel_plan(2048, n, None, -1, None, None) == E_ARG
+    assert lib.gpsmi_last_error().decode() == 'gpsmi_acq_cancel: nsat out of range 0..32'

@@ -52,16 +52,23 @@ def test_plan_refuses():
            ('coh_ms', ok, cfg(coh_ms=21)), ('n_runs', ok, cfg(n_runs=-1)), ('reserved', ok, cfg(reserved=1)),
            ('carrier_hz', ok, cfg(carrier_hz=nan)), ('carrier_hz', ok, cfg(carrier_hz=-1.0)),
            ('f_offset_hz', ok, cfg(f_offset_hz=inf)), ('no run', [(4, 19, 0.0, 0.0)], cfg(coh_ms=20, half_taps=8))]
+    reason = {'nsat': 'nsat out of range 1..64', 'prn': 'prn out of range 1..37', 'skip_ms': 'skip_ms out of range 0..19',
+              'f_hz': 'f_hz out of range', 'tau': 'tau out of range', '1 %': 'f_hz - f_offset_hz beyond 1 % of carrier_hz',
+              'half_taps': 'half_taps out of range 1..32 (0: the default)', 'coh_ms': 'coh_ms out of range 1..20 (0: 20)',
+              'n_runs': 'n_runs must be >= 1 (0: every run that fits)', 'reserved': 'a reserved field is not 0',
+              'carrier_hz': 'carrier_hz must be positive (0: L1)', 'f_offset_hz': 'f_offset_hz must be finite',
+              'no run': 'a record has no run inside iq'}
     for word, sats, c in bad:
         n_here = 38 * 2048 if word == 'no run' else n          # 37 windows fit, 19 are skipped: 18 < 20
         rc, msg = _plan_rc(2048, n_here, sats, c)
-        assert rc == -1 and word in msg, (word, rc, msg)
-    assert _plan_rc(2048, 0, ok, None)[0] == -1 and _plan_rc(2048, (1 << 40) + 1, ok, None)[0] == -1
+        assert rc == -1 and msg == 'gpsmi_acq_profile: ' + reason[word], (word, rc, msg)
+    for n_bad in (0, (1 << 40) + 1):
+        assert _plan_rc(2048, n_bad, ok, None) == (-1, 'gpsmi_acq_profile: n out of range 1..2^40')
     lib = _lib.load()
     assert lib.gpsmi_acq_profile_plan(2048, n, None, 1, None, None, None, None) == -1
+    assert lib.gpsmi_last_error().decode() == 'gpsmi_acq_profile: null argument'
     for cs in (4096, 1024, 16384):
-        rc, msg = _plan_rc(cs, n, ok, None)
-        assert rc == -5 and 'code_samples' in msg, (cs, rc, msg)
+        assert _plan_rc(cs, n, ok, None) == (-5, f'gpsmi_acq_profile: code_samples 2048 and 16368 only ({cs})')
     with pytest.raises(engine.EngineError):
         engine.profiles_plan(2048, n, ok, half_taps=40)
 

@@ -62,6 +62,14 @@ def test_plan_accepts_defaults():
     assert raw_plan(16368, R.KERNEL_N[16368], GOOD, cfg(8))[0] == 0
 
 
+# the whole text behind "gpsmi_acq_signature: " of the refusal that holds the word
+REASON = {'null': 'null argument', 'antennas': 'antennas out of range 2..8 (0: 2)', 'nsat': 'nsat out of range 1..64',
+          'prn': 'prn out of range 1..37', 'f_hz': 'f_hz out of range', 'tau': 'tau out of range',
+          '1 %': 'f_hz - f_offset_hz beyond 1 % of carrier_hz', 'n out of range': 'n out of range 1..2^40 / antennas',
+          'reserved': 'a reserved field is not 0', 'n_ms': 'n_ms must be >= 1 (0: every window that fits)',
+          'no window': 'a record has no window inside iq'}
+
+
 @pytest.mark.parametrize('name,call,word', [
     ('null sats', lambda: raw_plan(2048, N, GOOD, cfg(), null_sats=True), 'null'),
     ('one antenna', lambda: raw_plan(2048, N, GOOD, cfg(1)), 'antennas'),
@@ -87,12 +95,12 @@ def test_plan_accepts_defaults():
 ], ids=lambda v: v if isinstance(v, str) else '')
 def test_plan_argument_errors(name, call, word):
     rc, msg = call()
-    assert rc == -1 and word in msg, (name, rc, msg)
+    assert rc == -1 and msg == 'gpsmi_acq_signature: ' + REASON[word], (name, rc, msg)
 
 
 def test_plan_unsupported_code_length():
     rc, msg = raw_plan(4096, N, GOOD, cfg())
-    assert rc == -5 and '2048 and 16368' in msg
+    assert rc == -5 and msg == 'gpsmi_acq_signature: code_samples 2048 and 16368 only (4096)'
     with pytest.raises(engine.EngineError):
         engine.signature_plan(2048, N, [(4, np.nan, 0.0)], 4)
 
