@@ -350,7 +350,7 @@ int gpsmi_ifx_apply(gpsmi_ifx* h, const void* iq, float* out, int nb, int32_t* c
     if (rc) return rc;
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     return h->blk.apply_host(
-        iq, out, nb, h->sync.stream, "excision staging",
+        iq, out, nb, h->blk.out_bytes(nb), h->sync.stream, "excision staging",
         [&](const void* d_iq, void* d_out) { return ifx_run(h, d_iq, d_out, nb); },
         [&] { return ifx_finish(h, nb, counts, masks); });
 }

@@ -7,7 +7,9 @@
 // whose R has no Cholesky factor) passes antenna 0 through.  With cfg.taps = 3, 5 or 7 every antenna has a
 // filter of that many taps instead: the kernels of gpsmi_nul_stap.h, dispatched from nul_run below.
 // gpsmi_nul_beams forms per-satellite beams from the same covariance: the kernels of gpsmi_nul_beam.h,
-// dispatched from beam_run below; it shares nul_cov_kernel and leaves everything else here alone.
+// dispatched from beam_run below.  What the three forms share stands here, once: NulSamples (a row's
+// samples in either input format), nul_slice_sum, nul_factor (R = L L^H) and nul_back on the device;
+// NulResults, nul_launch and nul_finish (a call's results and its one body) on the host.
 //
 //   nul_cov_kernel<FMT, A>    one workgroup per (block, slice of 8192 samples): lane t takes the samples
 //                             2048 r + 8 t .. + 7, r = 0 .. 3, as b128 loads (two complex64 or
@@ -27,6 +29,7 @@
 // fused multiply-adds of the covariance are products that are exact before the add: they round as a
 // multiply and an add would.  The solve and the apply are compiled with contraction off.
 #include <cmath>
+#include <type_traits>
 
 #include "gpsmi_common.h"
 #include "gpsmi_stage.h"
@@ -49,8 +52,36 @@ __host__ __device__ constexpr bool nul_diag_im(int v) {
     return false;
 }
 
-// 16 bytes of raw samples, 4-byte aligned
+// 16 and 8 bytes of raw samples, 4-byte aligned
 typedef uint32_t nul_u32x4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t nul_u32x2 __attribute__((ext_vector_type(2), aligned(4)));
+
+// sample q of a call's raw samples from the word w that holds it: the even sample in the low half
+__device__ __forceinline__ float2 nul_raw(uint32_t w, int q) { return decode_u8iq(q % 2 ? w >> 16 : w & 0xFFFFu); }
+
+// V samples of the call's input in format FMT as a thread holds them: loaded as b128 words (two complex64
+// or eight raw samples each; four raw samples: one b64 word), a raw sample decoded where it is used.
+template <int FMT, int V>
+struct NulSamples {
+    static_assert(V % 2 == 0 && (FMT == 0 || V == 4 || V == 8));
+    using Raw = std::conditional_t<V == 8, nul_u32x4, nul_u32x2>;
+    std::conditional_t<FMT == 0, float4[V / 2], Raw> v;
+
+    // samples at .. at + V - 1 (at: a multiple of V) of the row that starts `row` samples into the input
+    __device__ __forceinline__ void load(const void* __restrict__ iq, size_t at, size_t row = 0) {
+        if constexpr (FMT == 0) {
+#pragma unroll
+            for (int q = 0; q < V; q += 2)
+                v[q / 2] = *reinterpret_cast<const float4*>(static_cast<const float2*>(iq) + at + row + q);
+        } else {
+            v = *reinterpret_cast<const Raw*>(static_cast<const uint16_t*>(iq) + at + row);
+        }
+    }
+    __device__ __forceinline__ float2 operator[](int q) const {
+        if constexpr (FMT == 0) return q % 2 ? make_float2(v[q / 2].z, v[q / 2].w) : make_float2(v[q / 2].x, v[q / 2].y);
+        else return nul_raw(v[q / 2], q);
+    }
+};
 
 template <int A>
 __device__ __forceinline__ void nul_accumulate(double (&acc)[nul_values(A)], const float2 (&x)[A]) {
@@ -88,6 +119,8 @@ __global__ __launch_bounds__(kNulThreads) void nul_cov_kernel(const void* __rest
     double acc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = 0.0;
+    // (the loads written out, not NulSamples: at A = 8 this kernel fills the register file, and the
+    // complex64 form measured 6 % slower with the address arithmetic of the shared loader)
     for (int o = kNulGroup * t; o < len; o += kNulGroup * kNulThreads) {
         if constexpr (FMT == 0) {
             const float2* src = static_cast<const float2*>(iq) + base + o;
@@ -113,10 +146,7 @@ __global__ __launch_bounds__(kNulThreads) void nul_cov_kernel(const void* __rest
             for (int q = 0; q < kNulGroup; ++q) {
                 float2 x[A];
 #pragma unroll
-                for (int a = 0; a < A; ++a) {
-                    const uint32_t w = v[a][q / 2];
-                    x[a] = decode_u8iq(q % 2 ? w >> 16 : w & 0xFFFFu);
-                }
+                for (int a = 0; a < A; ++a) x[a] = nul_raw(v[a][q / 2], q);
                 nul_accumulate<A>(acc, x);
             }
         }
@@ -144,26 +174,23 @@ __device__ __forceinline__ NulZ nul_mul(NulZ a, NulZ b) {             // a * b
 __device__ __forceinline__ NulZ nul_conj(NulZ a) { return {a.re, -a.im}; }
 __device__ __forceinline__ NulZ nul_sub(NulZ a, NulZ b) { return {a.re - b.re, a.im - b.im}; }
 
-// w32: [nb][8] (A used), w64: [nb][A][2]
+// value v (of nv) of block b: its ns slice sums, added in ascending slice order
+__device__ __forceinline__ double nul_slice_sum(const double* __restrict__ part, int b, int ns, int nv, int v) {
+    const double* src = part + (size_t)b * ns * nv + v;
+    double c = src[0];
+    for (int s = 1; s < ns; ++s) c += src[(size_t)s * nv];
+    return c;
+}
+
+// R = C / n + delta I = L L^H, column by column, from the values Cs of a block of n samples; delta = load
+// times the mean of R's diagonal.  -> every pivot was positive and finite.  tr, r00: the trace and
+// R[0][0] ahead of the loading.  L: the lower triangle; only constants index it (registers).
 template <int A>
-__global__ __launch_bounds__(128) void nul_solve_kernel(const double* __restrict__ part, int n, int ns,
-                                                        double load, double min_db,
-                                                        float2* __restrict__ w32, double* __restrict__ w64,
-                                                        int32_t* __restrict__ flags, float* __restrict__ gain) {
-    constexpr int NV = nul_values(A);
-    __shared__ double Cs[NV];
-    const int t = threadIdx.x, b = blockIdx.x;
-    if (t < NV) {
-        const double* src = part + (size_t)b * ns * NV + t;
-        double c = src[0];
-        for (int s = 1; s < ns; ++s) c += src[(size_t)s * NV];
-        Cs[t] = c;
-    }
-    __syncthreads();
-    if (t != 0) return;
+__device__ __forceinline__ bool nul_factor(const double* Cs, int n, double load, NulZ (&L)[A][A], double& tr,
+                                           double& r00) {
     const double dn = (double)n;
     NulZ R[A][A];                                      // lower triangle
-    double tr = 0.0;
+    tr = 0.0;
 #pragma unroll
     for (int a = 0; a < A; ++a) {
 #pragma unroll
@@ -173,12 +200,10 @@ __global__ __launch_bounds__(128) void nul_solve_kernel(const double* __restrict
         }
         tr += R[a][a].re;
     }
-    const double p00 = R[0][0].re;
+    r00 = R[0][0].re;
     const double delta = load * tr / (double)A;
 #pragma unroll
     for (int a = 0; a < A; ++a) R[a][a].re += delta;
-    // R = L L^H, column by column
-    NulZ L[A][A];
     bool ok = true;
 #pragma unroll
     for (int j = 0; j < A; ++j) {
@@ -196,7 +221,37 @@ __global__ __launch_bounds__(128) void nul_solve_kernel(const double* __restrict
             L[i][j] = {v.re / l, v.im / l};
         }
     }
-    NulZ y[A], u[A];
+    return ok;
+}
+
+// L^H x = y for a lower triangle L (registers or LDS): rows descending, each sum in ascending column order
+template <int A, typename Tri>
+__device__ __forceinline__ void nul_back(const Tri& L, const NulZ (&y)[A], NulZ (&x)[A]) {
+#pragma unroll
+    for (int i = A - 1; i >= 0; --i) {
+        NulZ v = y[i];
+#pragma unroll
+        for (int k = i + 1; k < A; ++k) v = nul_sub(v, nul_mul(nul_conj(L[k][i]), x[k]));
+        x[i] = {v.re / L[i][i].re, v.im / L[i][i].re};
+    }
+}
+
+// w32: [nb][8] (A used), w64: [nb][A][2]
+template <int A>
+__global__ __launch_bounds__(128) void nul_solve_kernel(const double* __restrict__ part, int n, int ns,
+                                                        double load, double min_db,
+                                                        float2* __restrict__ w32, double* __restrict__ w64,
+                                                        int32_t* __restrict__ flags, float* __restrict__ gain) {
+    constexpr int NV = nul_values(A);
+    __shared__ double Cs[NV];
+    const int t = threadIdx.x, b = blockIdx.x;
+    if (t < NV) Cs[t] = nul_slice_sum(part, b, ns, NV, t);
+    __syncthreads();
+    if (t != 0) return;
+    NulZ L[A][A];
+    double tr, p00;
+    bool ok = nul_factor<A>(Cs, n, load, L, tr, p00);
+    NulZ y[A], u[A];                                   // L y = e0, L^H u = y
     y[0] = {1.0 / L[0][0].re, 0.0};
 #pragma unroll
     for (int i = 1; i < A; ++i) {
@@ -205,13 +260,7 @@ __global__ __launch_bounds__(128) void nul_solve_kernel(const double* __restrict
         for (int k = 0; k < i; ++k) v = nul_sub(v, nul_mul(L[i][k], y[k]));
         y[i] = {v.re / L[i][i].re, v.im / L[i][i].re};
     }
-#pragma unroll
-    for (int i = A - 1; i >= 0; --i) {
-        NulZ v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < A; ++k) v = nul_sub(v, nul_mul(nul_conj(L[k][i]), u[k]));
-        u[i] = {v.re / L[i][i].re, v.im / L[i][i].re};
-    }
+    nul_back<A>(L, y, u);
     double gdb = 0.0;
     if (ok) {
         gdb = 10.0 * log10(p00 * u[0].re);
@@ -251,37 +300,19 @@ __global__ __launch_bounds__(kNulThreads) void nul_apply_kernel(const void* __re
     float2 w[A];
 #pragma unroll
     for (int a = 0; a < A; ++a) w[a] = w32[(size_t)b * kNulMaxA + a];
+    NulSamples<FMT, V> x;
+    x.load(iq, at);
     float2 y[V];
-    if constexpr (FMT == 0) {
-        const float2* src = static_cast<const float2*>(iq) + at;
-        const float4 v0 = *reinterpret_cast<const float4*>(src);
-        y[0] = make_float2(v0.x, v0.y);
-        y[1] = make_float2(v0.z, v0.w);
-        if (on) {
-            y[0] = nul_term(w[0], y[0]);
-            y[1] = nul_term(w[0], y[1]);
 #pragma unroll
-            for (int a = 1; a < A; ++a) {
-                const float4 v = *reinterpret_cast<const float4*>(src + a * astride);
-                y[0] = nul_add(y[0], nul_term(w[a], make_float2(v.x, v.y)));
-                y[1] = nul_add(y[1], nul_term(w[a], make_float2(v.z, v.w)));
-            }
-        }
-    } else {
-        const uint16_t* src = static_cast<const uint16_t*>(iq) + at;
-        const nul_u32x4 v0 = *reinterpret_cast<const nul_u32x4*>(src);
+    for (int q = 0; q < V; ++q) y[q] = x[q];
+    if (on) {
 #pragma unroll
-        for (int q = 0; q < V; ++q) y[q] = decode_u8iq(q % 2 ? v0[q / 2] >> 16 : v0[q / 2] & 0xFFFFu);
-        if (on) {
+        for (int q = 0; q < V; ++q) y[q] = nul_term(w[0], y[q]);
 #pragma unroll
-            for (int q = 0; q < V; ++q) y[q] = nul_term(w[0], y[q]);
+        for (int a = 1; a < A; ++a) {
+            x.load(iq, at, a * astride);
 #pragma unroll
-            for (int a = 1; a < A; ++a) {
-                const nul_u32x4 v = *reinterpret_cast<const nul_u32x4*>(src + a * astride);
-#pragma unroll
-                for (int q = 0; q < V; ++q)
-                    y[q] = nul_add(y[q], nul_term(w[a], decode_u8iq(q % 2 ? v[q / 2] >> 16 : v[q / 2] & 0xFFFFu)));
-            }
+            for (int q = 0; q < V; ++q) y[q] = nul_add(y[q], nul_term(w[a], x[q]));
         }
     }
 #pragma unroll
@@ -296,24 +327,35 @@ __global__ __launch_bounds__(kNulThreads) void nul_apply_kernel(const void* __re
 
 using namespace gpsmi;
 
+// What a call leaves besides the samples, a row per block (gpsmi_nul_apply) or per beam of a block
+// (gpsmi_nul_beams): what the solve kernel writes, and the device time of the three kernels.
+struct NulResults {
+    DevBuf<float2> w32;                                   // [rows][8] (taps: [rows][56]): what the apply reads
+    DevBuf<double> w64;                                   // [rows][A][2] (taps: [rows][A][T][2])
+    DevBuf<int32_t> flags; DevBuf<float> gain;            // [rows]
+    size_t rows = 0, w64_row = 0;                         // of the last call: rows, doubles of a row of w64
+    float ms[3] = {0.f, 0.f, 0.f};                        // covariance, solve, apply of the last finished call
+
+    int reserve(size_t rows_, size_t w32_row, size_t w64_row_, const char* what) {
+        rows = rows_;
+        w64_row = w64_row_;
+        int rc = w32.reserve(rows * w32_row, what);
+        if (!rc) rc = w64.reserve(rows * w64_row, what);
+        if (!rc) rc = flags.reserve(rows, what);
+        if (!rc) rc = gain.reserve(rows, what);
+        return rc;
+    }
+};
+
 struct gpsmi_nul {
     gpsmi_nul_cfg cfg;
     DevBuf<double> d_part;                                // [blocks][slices][A (A + 1)] (taps: stap_values)
-    DevBuf<float2> d_w32;                                 // [blocks][8] (taps: [blocks][56])
-    DevBuf<double> d_w64;                                 // [blocks][A][2] (taps: [blocks][A][T][2])
-    DevBuf<int32_t> d_flags; DevBuf<float> d_gain;        // [blocks]
     double load = 0.0, min_db = 0.0;                      // the cfg's, defaults filled in
     int taps = 1;                                         // 1: one weight per antenna, else 3, 5 or 7
     DevEvent ev_cov, ev_solve;                            // stamps behind the first and the second kernel
-    float kernel_ms[3] = {0.f, 0.f, 0.f};                 // covariance, solve, apply of the last finished call
-    // gpsmi_nul_beams: its own results, so that a call leaves gpsmi_nul_apply's alone
+    NulResults res, beam;                                 // gpsmi_nul_apply's; gpsmi_nul_beams', which leaves res alone
     DevBuf<double> d_bvec;                                // [nbeam + nnull][A][2]: steer, then nulls
     DevBuf<uint32_t> d_bmask;                             // [nbeam]
-    DevBuf<float2> d_bw32;                                // [blocks][nbeam][8]
-    DevBuf<double> d_bw64;                                // [blocks][nbeam][A][2]
-    DevBuf<int32_t> d_bflags; DevBuf<float> d_bgain;      // [blocks][nbeam]
-    DevBuf<char> d_bout;                                  // host entry: the staged beams
-    float beam_ms[3] = {0.f, 0.f, 0.f};                   // covariance, solve, apply of the last finished beams call
     BlockStage blk;
     StageSync sync;                                       // last: see gpsmi_stage.h
 };
@@ -329,67 +371,96 @@ static int nul_build(gpsmi_nul* h) {
     return rc;
 }
 
+// One call's three kernels on the handle's stream with the stamps between them; cov, solve and apply
+// launch one kernel each.
+template <typename Cov, typename Solve, typename Apply>
+static int nul_launch(gpsmi_nul* h, Cov&& cov, Solve&& solve, Apply&& apply) {
+    const hipStream_t st = h->sync.stream;
+    const int rc = h->sync.begin();
+    if (rc) return rc;
+    cov();
+    (void)hipEventRecord(h->ev_cov, st);
+    solve();
+    (void)hipEventRecord(h->ev_solve, st);
+    apply();
+    return h->sync.end();
+}
+
 // The three passes over nb blocks of every antenna at d_iq (device, the handle's input format) into d_out.
 static int nul_run(gpsmi_nul* h, const void* d_iq, void* d_out, int nb) {
     const int n = h->cfg.block_samples, A = h->cfg.antennas, T = h->taps;
     const int ns = (n + kNulSlice - 1) / kNulSlice;
     const size_t astride = (size_t)nb * n;
+    NulResults& r = h->res;
     int rc = h->d_part.reserve((size_t)nb * ns * stap_values(A, T), "null steering slice sums");   // (T = 1: nul_values)
-    if (!rc) rc = h->d_w32.reserve((size_t)nb * (T == 1 ? kNulMaxA : kStapMaxK), "null steering results");
-    if (!rc) rc = h->d_w64.reserve((size_t)nb * A * T * 2, "null steering results");
-    if (!rc) rc = h->d_flags.reserve(nb, "null steering results");
-    if (!rc) rc = h->d_gain.reserve(nb, "null steering results");
+    if (!rc) rc = r.reserve(nb, T == 1 ? kNulMaxA : kStapMaxK, (size_t)A * T * 2, "null steering results");
     if (rc) return rc;
     const hipStream_t st = h->sync.stream;
     float2* out = static_cast<float2*>(d_out);
-    if ((rc = h->sync.begin())) return rc;
     with_fmt(h->blk.fmt, [&](auto fmt) {
         constexpr int FMT = decltype(fmt)::value;
         constexpr int V = FMT == 0 ? kNulApplyC64 : kNulApplyU8;
         const int nc = (n + kNulThreads * V - 1) / (kNulThreads * V);
+        const dim3 slices((unsigned)(nb * ns)), chunks((unsigned)(nb * nc)), blocks((unsigned)nb), wg(kNulThreads);
         if (T > 1) {
             with_value<3, 5, 7>(T, [&](auto nt) {
                 constexpr int NT = decltype(nt)::value;
-                hipLaunchKernelGGL((stap_cov_kernel<FMT, NT>), dim3((unsigned)(nb * ns)), dim3(kNulThreads), 0, st,
-                                   d_iq, n, ns, A, astride, h->d_part.p);
-                (void)hipEventRecord(h->ev_cov, st);
-                hipLaunchKernelGGL(stap_solve_kernel, dim3((unsigned)nb), dim3(64), 0, st, h->d_part.p, n, ns, A,
-                                   NT, h->load, h->min_db, h->d_w32.p, h->d_w64.p, h->d_flags.p, h->d_gain.p);
-                (void)hipEventRecord(h->ev_solve, st);
-                hipLaunchKernelGGL((stap_apply_kernel<FMT, NT>), dim3((unsigned)(nb * nc)), dim3(kNulThreads), 0,
-                                   st, d_iq, n, nc, A, astride, h->d_w32.p, h->d_flags.p, out);
+                rc = nul_launch(
+                    h,
+                    [&] {
+                        hipLaunchKernelGGL((stap_cov_kernel<FMT, NT>), slices, wg, 0, st, d_iq, n, ns, A, astride,
+                                           h->d_part.p);
+                    },
+                    [&] {
+                        hipLaunchKernelGGL(stap_solve_kernel, blocks, dim3(64), 0, st, h->d_part.p, n, ns, A, NT,
+                                           h->load, h->min_db, r.w32.p, r.w64.p, r.flags.p, r.gain.p);
+                    },
+                    [&] {
+                        hipLaunchKernelGGL((stap_apply_kernel<FMT, NT>), chunks, wg, 0, st, d_iq, n, nc, A, astride,
+                                           r.w32.p, r.flags.p, out);
+                    });
             });
             return;
         }
         with_value<2, 3, 4, 5, 6, 7, 8>(A, [&](auto na) {
             constexpr int NA = decltype(na)::value;
-            hipLaunchKernelGGL((nul_cov_kernel<FMT, NA>), dim3((unsigned)(nb * ns)), dim3(kNulThreads), 0, st,
-                               d_iq, n, ns, astride, h->d_part.p);
-            (void)hipEventRecord(h->ev_cov, st);
-            hipLaunchKernelGGL(nul_solve_kernel<NA>, dim3((unsigned)nb), dim3(128), 0, st, h->d_part.p, n, ns,
-                               h->load, h->min_db, h->d_w32.p, h->d_w64.p, h->d_flags.p, h->d_gain.p);
-            (void)hipEventRecord(h->ev_solve, st);
-            hipLaunchKernelGGL((nul_apply_kernel<FMT, NA>), dim3((unsigned)(nb * nc)), dim3(kNulThreads), 0, st,
-                               d_iq, n, nc, astride, h->d_w32.p, h->d_flags.p, out);
+            rc = nul_launch(
+                h,
+                [&] {
+                    hipLaunchKernelGGL((nul_cov_kernel<FMT, NA>), slices, wg, 0, st, d_iq, n, ns, astride, h->d_part.p);
+                },
+                [&] {
+                    hipLaunchKernelGGL(nul_solve_kernel<NA>, blocks, dim3(128), 0, st, h->d_part.p, n, ns, h->load,
+                                       h->min_db, r.w32.p, r.w64.p, r.flags.p, r.gain.p);
+                },
+                [&] {
+                    hipLaunchKernelGGL((nul_apply_kernel<FMT, NA>), chunks, wg, 0, st, d_iq, n, nc, astride, r.w32.p,
+                                       r.flags.p, out);
+                });
         });
     });
-    return h->sync.end();
+    return rc;
 }
 
-static int nul_finish(gpsmi_nul* h, int nb, int32_t* flags, float* gain_db, double* weights) {
+// Behind nul_launch: the results of r the caller asked for on their way down, the end of the call
+// (StageSync::finish), the device time of its three kernels.
+static int nul_finish(gpsmi_nul* h, NulResults& r, int32_t* flags, float* gain_db, double* weights) {
     const hipStream_t st = h->sync.stream;
-    if (flags)
-        GPSMI_HIP(hipMemcpyAsync(flags, h->d_flags.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (gain_db)
-        GPSMI_HIP(hipMemcpyAsync(gain_db, h->d_gain.p, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (flags) GPSMI_HIP(hipMemcpyAsync(flags, r.flags.p, r.rows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (gain_db) GPSMI_HIP(hipMemcpyAsync(gain_db, r.gain.p, r.rows * sizeof(float), hipMemcpyDeviceToHost, st));
     if (weights)
-        GPSMI_HIP(hipMemcpyAsync(weights, h->d_w64.p, (size_t)nb * h->cfg.antennas * h->taps * 2 * sizeof(double),
-                                 hipMemcpyDeviceToHost, st));
+        GPSMI_HIP(hipMemcpyAsync(weights, r.w64.p, r.rows * r.w64_row * sizeof(double), hipMemcpyDeviceToHost, st));
     const int rc = h->sync.finish();
     if (rc) return rc;
-    GPSMI_HIP(hipEventElapsedTime(&h->kernel_ms[0], h->sync.ev0, h->ev_cov));
-    GPSMI_HIP(hipEventElapsedTime(&h->kernel_ms[1], h->ev_cov, h->ev_solve));
-    GPSMI_HIP(hipEventElapsedTime(&h->kernel_ms[2], h->ev_solve, h->sync.ev1));
+    GPSMI_HIP(hipEventElapsedTime(&r.ms[0], h->sync.ev0, h->ev_cov));
+    GPSMI_HIP(hipEventElapsedTime(&r.ms[1], h->ev_cov, h->ev_solve));
+    GPSMI_HIP(hipEventElapsedTime(&r.ms[2], h->ev_solve, h->sync.ev1));
+    return GPSMI_OK;
+}
+
+static int nul_kernel_ms(const gpsmi_nul* h, NulResults gpsmi_nul::*of, float* ms, const char* fn) {
+    if (!h || !ms) return fail(GPSMI_E_ARG, "%s: null argument", fn);
+    for (int k = 0; k < 3; ++k) ms[k] = (h->*of).ms[k];
     return GPSMI_OK;
 }
 
@@ -468,21 +539,19 @@ static int beam_check_plan(const char* fn, int A, const BeamPlan& p) {
     return GPSMI_OK;
 }
 
-// The checks of a beams call on a live handle, before any GPU work.  Strides in samples, 0 filled in.
+// What a beams call checks on a live handle behind stage_check_blocks, before any GPU work: the handle's
+// taps, the beams, and the rows' strides (in samples, 0 filled in), alignment and overlap.
 static int beam_check_call(const gpsmi_nul* h, const char* fn, const void* iq, size_t in_stride, const void* out,
                            size_t out_stride, int nb, const BeamPlan& p, bool dev) {
-    if (!h || !iq || !out) return fail(GPSMI_E_ARG, "%s: null argument", fn);
+    int rc = stage_check_blocks(h, iq, out, nb, fn);
+    if (rc) return rc;
     if (h->taps != 1) return fail(GPSMI_E_STATE, "%s: the handle is a space-time one (taps %d)", fn, h->taps);
     const int n = h->cfg.block_samples, A = h->cfg.antennas;
-    if (nb < 1 || (size_t)nb * n > ((size_t)1 << 31))
-        return fail(GPSMI_E_ARG, "%s: nb out of range: 1 .. 2^31 samples per call", fn);
-    const int rc = beam_check_plan(fn, A, p);
-    if (rc) return rc;
+    if ((rc = beam_check_plan(fn, A, p))) return rc;
     const size_t row = (size_t)nb * n, ss = h->blk.fmt == GPSMI_IQ_U8 ? sizeof(uint16_t) : sizeof(float2);
     if (in_stride < row || out_stride < row || in_stride > ((size_t)1 << 40) || out_stride > ((size_t)1 << 40))
         return fail(GPSMI_E_ARG, "%s: a row stride is shorter than the nb * n samples of a row", fn);
-    if (dev && ((uintptr_t)iq % (ss == 2 ? 4 : 16) != 0 || (uintptr_t)out % 16 != 0 || in_stride % 2 != 0 ||
-                out_stride % 2 != 0))
+    if (dev && (!stage_aligned(h->blk, iq, out) || in_stride % 2 != 0 || out_stride % 2 != 0))
         return fail(GPSMI_E_ARG,
                     "%s: device input / output rows not aligned (4 bytes for u8, 16 for complex64: even strides)", fn);
     const char* i0 = static_cast<const char*>(iq);
@@ -504,13 +573,11 @@ static int beam_run(gpsmi_nul* h, const void* d_iq, size_t in_stride, void* d_ou
     const int n = h->cfg.block_samples, A = h->cfg.antennas, B = p.nbeam, Q = p.nnull;
     const int ns = (n + kNulSlice - 1) / kNulSlice;
     const char* what = "beam results";
+    NulResults& r = h->beam;
     int rc = h->d_part.reserve((size_t)nb * ns * nul_values(A), "null steering slice sums");
     if (!rc) rc = h->d_bvec.reserve((size_t)(kBeamMax + kBeamMaxNull) * kNulMaxA * 2, what);
     if (!rc) rc = h->d_bmask.reserve(kBeamMax, what);
-    if (!rc) rc = h->d_bw32.reserve((size_t)nb * B * kNulMaxA, what);
-    if (!rc) rc = h->d_bw64.reserve((size_t)nb * B * A * 2, what);
-    if (!rc) rc = h->d_bflags.reserve((size_t)nb * B, what);
-    if (!rc) rc = h->d_bgain.reserve((size_t)nb * B, what);
+    if (!rc) rc = r.reserve((size_t)nb * B, kNulMaxA, (size_t)A * 2, what);
     if (rc) return rc;
     const hipStream_t st = h->sync.stream;
     uint32_t mask[kBeamMax];
@@ -521,41 +588,29 @@ static int beam_run(gpsmi_nul* h, const void* d_iq, size_t in_stride, void* d_ou
         GPSMI_HIP(hipMemcpyAsync(d_nulls, p.nulls, (size_t)Q * A * 2 * sizeof(double), hipMemcpyHostToDevice, st));
     GPSMI_HIP(hipMemcpyAsync(h->d_bmask.p, mask, (size_t)B * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     GPSMI_HIP(hipStreamSynchronize(st));                  // (mask is on this stack)
-    if ((rc = h->sync.begin())) return rc;
     const int nc = (n + kNulThreads * kBeamApply - 1) / (kNulThreads * kBeamApply);
+    const dim3 slices((unsigned)(nb * ns)), chunks((unsigned)(nb * nc)), blocks((unsigned)nb), wg(kNulThreads);
     with_fmt(h->blk.fmt, [&](auto fmt) {
         constexpr int FMT = decltype(fmt)::value;
         with_value<2, 3, 4, 5, 6, 7, 8>(A, [&](auto na) {
             constexpr int NA = decltype(na)::value;
-            hipLaunchKernelGGL((nul_cov_kernel<FMT, NA>), dim3((unsigned)(nb * ns)), dim3(kNulThreads), 0, st,
-                               d_iq, n, ns, in_stride, h->d_part.p);
-            (void)hipEventRecord(h->ev_cov, st);
-            hipLaunchKernelGGL(beam_solve_kernel<NA>, dim3((unsigned)nb), dim3(kBeamSolveThreads), 0, st,
-                               h->d_part.p, n, ns, h->load, B, Q, h->d_bvec.p, d_nulls, h->d_bmask.p, h->d_bw32.p,
-                               h->d_bw64.p, h->d_bflags.p, h->d_bgain.p);
-            (void)hipEventRecord(h->ev_solve, st);
-            hipLaunchKernelGGL((beam_apply_kernel<FMT, NA>), dim3((unsigned)(nb * nc)), dim3(kNulThreads), 0, st,
-                               d_iq, n, nc, in_stride, B, h->d_bw32.p, h->d_bflags.p, static_cast<float2*>(d_out),
-                               out_stride);
+            rc = nul_launch(
+                h,
+                [&] {
+                    hipLaunchKernelGGL((nul_cov_kernel<FMT, NA>), slices, wg, 0, st, d_iq, n, ns, in_stride, h->d_part.p);
+                },
+                [&] {
+                    hipLaunchKernelGGL(beam_solve_kernel<NA>, blocks, dim3(kBeamSolveThreads), 0, st, h->d_part.p, n, ns,
+                                       h->load, B, Q, h->d_bvec.p, d_nulls, h->d_bmask.p, r.w32.p, r.w64.p, r.flags.p,
+                                       r.gain.p);
+                },
+                [&] {
+                    hipLaunchKernelGGL((beam_apply_kernel<FMT, NA>), chunks, wg, 0, st, d_iq, n, nc, in_stride, B,
+                                       r.w32.p, r.flags.p, static_cast<float2*>(d_out), out_stride);
+                });
         });
     });
-    return h->sync.end();
-}
-
-static int beam_finish(gpsmi_nul* h, int nb, int B, int32_t* flags, float* gain_db, double* weights) {
-    const hipStream_t st = h->sync.stream;
-    const size_t r = (size_t)nb * B;
-    if (flags) GPSMI_HIP(hipMemcpyAsync(flags, h->d_bflags.p, r * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (gain_db) GPSMI_HIP(hipMemcpyAsync(gain_db, h->d_bgain.p, r * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (weights)
-        GPSMI_HIP(hipMemcpyAsync(weights, h->d_bw64.p, r * h->cfg.antennas * 2 * sizeof(double),
-                                 hipMemcpyDeviceToHost, st));
-    const int rc = h->sync.finish();
-    if (rc) return rc;
-    GPSMI_HIP(hipEventElapsedTime(&h->beam_ms[0], h->sync.ev0, h->ev_cov));
-    GPSMI_HIP(hipEventElapsedTime(&h->beam_ms[1], h->ev_cov, h->ev_solve));
-    GPSMI_HIP(hipEventElapsedTime(&h->beam_ms[2], h->ev_solve, h->sync.ev1));
-    return GPSMI_OK;
+    return rc;
 }
 
 extern "C" {
@@ -586,7 +641,7 @@ int gpsmi_nul_apply_dev(gpsmi_nul* h, const void* d_iq, void* d_out, int nb, int
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     rc = nul_run(h, d_iq, d_out, nb);
     if (rc) return rc;
-    return nul_finish(h, nb, flags, gain_db, weights);
+    return nul_finish(h, h->res, flags, gain_db, weights);
 }
 
 int gpsmi_nul_apply(gpsmi_nul* h, const void* iq, float* out, int nb, int32_t* flags, float* gain_db,
@@ -595,18 +650,14 @@ int gpsmi_nul_apply(gpsmi_nul* h, const void* iq, float* out, int nb, int32_t* f
     if (rc) return rc;
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     return h->blk.apply_host(
-        iq, out, nb, h->sync.stream, "null steering staging",
+        iq, out, nb, h->blk.out_bytes(nb), h->sync.stream, "null steering staging",
         [&](const void* d_iq, void* d_out) { return nul_run(h, d_iq, d_out, nb); },
-        [&] { return nul_finish(h, nb, flags, gain_db, weights); });
+        [&] { return nul_finish(h, h->res, flags, gain_db, weights); });
 }
 
 int gpsmi_nul_last_ms(gpsmi_nul* h, float* ms) { return stage_last_ms(h, ms, __func__); }
 
-int gpsmi_nul_last_kernel_ms(gpsmi_nul* h, float* ms) {
-    GPSMI_REQUIRE(h && ms, "null argument");
-    for (int k = 0; k < 3; ++k) ms[k] = h->kernel_ms[k];
-    return GPSMI_OK;
-}
+int gpsmi_nul_last_kernel_ms(gpsmi_nul* h, float* ms) { return nul_kernel_ms(h, &gpsmi_nul::res, ms, __func__); }
 
 int gpsmi_nul_beams_plan(int antennas, int nbeam, const double* steer, int nnull, const double* nulls,
                          const uint32_t* null_mask) {
@@ -626,7 +677,7 @@ int gpsmi_nul_beams_dev(gpsmi_nul* h, const void* d_iq, int64_t in_stride, void*
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     rc = beam_run(h, d_iq, is, d_out, os, nb, p);
     if (rc) return rc;
-    return beam_finish(h, nb, nbeam, flags, gain_db, weights);
+    return nul_finish(h, h->beam, flags, gain_db, weights);
 }
 
 int gpsmi_nul_beams(gpsmi_nul* h, const void* iq, float* out, int nb, int nbeam, const double* steer, int nnull,
@@ -638,22 +689,14 @@ int gpsmi_nul_beams(gpsmi_nul* h, const void* iq, float* out, int nb, int nbeam,
     int rc = beam_check_call(h, __func__, iq, row, out, row, nb, p, false);
     if (rc) return rc;
     GPSMI_HIP(hipSetDevice(h->cfg.device));
-    const hipStream_t st = h->sync.stream;
-    const size_t ib = h->blk.in_bytes(nb), ob = (size_t)nbeam * row * sizeof(float2);
-    rc = h->blk.io.in.reserve(ib, "beam staging");
-    if (!rc) rc = h->d_bout.reserve(ob, "beam staging");
-    if (rc) return rc;
-    GPSMI_HIP(hipMemcpyAsync(h->blk.io.in.p, iq, ib, hipMemcpyHostToDevice, st));
-    rc = beam_run(h, h->blk.io.in.p, row, h->d_bout.p, row, nb, p);
-    if (rc) return rc;
-    GPSMI_HIP(hipMemcpyAsync(out, h->d_bout.p, ob, hipMemcpyDeviceToHost, st));
-    return beam_finish(h, nb, nbeam, flags, gain_db, weights);
+    return h->blk.apply_host(
+        iq, out, nb, (size_t)nbeam * h->blk.out_bytes(nb), h->sync.stream, "beam staging",
+        [&](const void* d_iq, void* d_out) { return beam_run(h, d_iq, row, d_out, row, nb, p); },
+        [&] { return nul_finish(h, h->beam, flags, gain_db, weights); });
 }
 
 int gpsmi_nul_last_beam_kernel_ms(gpsmi_nul* h, float* ms) {
-    GPSMI_REQUIRE(h && ms, "null argument");
-    for (int k = 0; k < 3; ++k) ms[k] = h->beam_ms[k];
-    return GPSMI_OK;
+    return nul_kernel_ms(h, &gpsmi_nul::beam, ms, __func__);
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 // Per-satellite beams on the null-steering handle (gpsmi_nul_beams*, include/gpsmi.h; DESIGN.md 4.2q;
-// restatement: tests/beam_ref.py).  Included by gpsmi_nul.hip behind the kernels of gpsmi_nul_apply, which
-// it leaves untouched: the covariance of a block is nul_cov_kernel's, from the same slice sums.
+// restatement: tests/beam_ref.py).  Included by gpsmi_nul.hip behind the kernels of gpsmi_nul_apply: the
+// covariance of a block is nul_cov_kernel's, and the slice sums, the factor of R, the back substitution
+// and the loading of a row's samples are the helpers that stand there.
 //
-// Per block, alone: R = C / n + delta I = L L^H as in gpsmi_nul_apply, and per beam b the linearly
+// Per block, alone: R = C / n + delta I = L L^H (nul_factor), and per beam b the linearly
 // constrained minimum-variance weights w = R^-1 G (G^H R^-1 G)^-1 e0 with G = [s_b, u_q ...]: the
 // steering vector of the beam held at one, the null vectors its mask names at zero.
 //
@@ -49,47 +50,12 @@ __global__ __launch_bounds__(kBeamSolveThreads) void beam_solve_kernel(
     __shared__ double s_tr;
     __shared__ int s_ok;
     const int t = threadIdx.x, b = blockIdx.x;
-    if (t < NV) {
-        const double* src = part + (size_t)b * ns * NV + t;
-        double c = src[0];
-        for (int s = 1; s < ns; ++s) c += src[(size_t)s * NV];
-        Cs[t] = c;
-    }
+    if (t < NV) Cs[t] = nul_slice_sum(part, b, ns, NV, t);
     __syncthreads();
-    if (t == 0) {                                      // R = L L^H as nul_solve_kernel
-        const double dn = (double)n;
-        NulZ R[A][A];
-        double tr = 0.0;
-#pragma unroll
-        for (int a = 0; a < A; ++a) {
-#pragma unroll
-            for (int c = 0; c <= a; ++c) {
-                const int p = a * (a + 1) / 2 + c;
-                R[a][c] = {Cs[2 * p] / dn, a == c ? 0.0 : Cs[2 * p + 1] / dn};
-            }
-            tr += R[a][a].re;
-        }
-        const double delta = load * tr / (double)A;
-#pragma unroll
-        for (int a = 0; a < A; ++a) R[a][a].re += delta;
+    if (t == 0) {
         NulZ L[A][A];
-        bool ok = true;
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-            double d = R[j][j].re;
-#pragma unroll
-            for (int k = 0; k < j; ++k) d -= L[j][k].re * L[j][k].re + L[j][k].im * L[j][k].im;
-            if (!(d > 0.0) || !(d < INFINITY)) ok = false;
-            const double l = sqrt(d);
-            L[j][j] = {l, 0.0};
-#pragma unroll
-            for (int i = j + 1; i < A; ++i) {
-                NulZ v = R[i][j];
-#pragma unroll
-                for (int k = 0; k < j; ++k) v = nul_sub(v, nul_mul(L[i][k], nul_conj(L[j][k])));
-                L[i][j] = {v.re / l, v.im / l};
-            }
-        }
+        double tr, r00;
+        const bool ok = nul_factor<A>(Cs, n, load, L, tr, r00);
 #pragma unroll
         for (int i = 0; i < A; ++i) {
 #pragma unroll
@@ -200,13 +166,7 @@ __global__ __launch_bounds__(kBeamSolveThreads) void beam_solve_kernel(
             if (j < m) acc = beam_add(acc, nul_mul(Zs[col(j)][a], q[j]));
         tq[a] = acc;
     }
-#pragma unroll
-    for (int i = A - 1; i >= 0; --i) {
-        NulZ v = tq[i];
-#pragma unroll
-        for (int k = i + 1; k < A; ++k) v = nul_sub(v, nul_mul(nul_conj(Ls[k][i]), w[k]));
-        w[i] = {v.re / Ls[i][i].re, v.im / Ls[i][i].re};
-    }
+    nul_back<A>(Ls, tq, w);
     double s2 = 0.0;
 #pragma unroll
     for (int a = 0; a < A; ++a) {
@@ -240,26 +200,12 @@ __global__ __launch_bounds__(kNulThreads) void beam_apply_kernel(const void* __r
     if (i >= n) return;                                // (n is a multiple of 32: whole groups)
     const size_t at = (size_t)b * n + i;
     float2 x[A][V];
-    if constexpr (FMT == 0) {
-        const float2* src = static_cast<const float2*>(iq) + at;
 #pragma unroll
-        for (int a = 0; a < A; ++a) {
+    for (int a = 0; a < A; ++a) {
+        NulSamples<FMT, V> v;
+        v.load(iq, at, a * istride);
 #pragma unroll
-            for (int q = 0; q < V; q += 2) {
-                const float4 v = *reinterpret_cast<const float4*>(src + a * istride + q);
-                x[a][q] = make_float2(v.x, v.y);
-                x[a][q + 1] = make_float2(v.z, v.w);
-            }
-        }
-    } else {
-        typedef uint32_t u32x2 __attribute__((ext_vector_type(2), aligned(4)));
-        const uint16_t* src = static_cast<const uint16_t*>(iq) + at;
-#pragma unroll
-        for (int a = 0; a < A; ++a) {
-            const u32x2 v = *reinterpret_cast<const u32x2*>(src + a * istride);
-#pragma unroll
-            for (int q = 0; q < V; ++q) x[a][q] = decode_u8iq(q % 2 ? v[q / 2] >> 16 : v[q / 2] & 0xFFFFu);
-        }
+        for (int q = 0; q < V; ++q) x[a][q] = v[q];
     }
     const float2* wb = w32 + (size_t)b * nbeam * kNulMaxA;
     const int32_t* fb = flags + (size_t)b * nbeam;

@@ -1,6 +1,6 @@
 // Space-time null steering: T = 3, 5 or 7 taps per antenna (gpsmi_nul_cfg.taps, include/gpsmi.h;
 // DESIGN.md 4.2o; restatement: tests/stap_ref.py).  Included by gpsmi_nul.hip behind the kernels of
-// the one-weight form, which keep serving taps <= 1 untouched.
+// the one-weight form, whose nul_slice_sum, NulSamples, nul_raw, nul_term and nul_add it uses.
 //
 //   stap_cov_kernel<FMT, T>    one workgroup per (block, slice of 8192 samples), four waves.  The slice
 //                              is staged 256 samples at a time (and the 8 before them: the halo of
@@ -153,12 +153,7 @@ __global__ __launch_bounds__(64) void stap_solve_kernel(const double* __restrict
     __shared__ double Yr[kStapMaxK], Yi[kStapMaxK], Ur[kStapMaxK], Ui[kStapMaxK];
     const int t = threadIdx.x, b = blockIdx.x;
     const int K = A * T, kc = (T - 1) / 2, NV = stap_values(A, T);
-    for (int v = t; v < NV; v += 64) {
-        const double* src = part + (size_t)b * ns * NV + v;
-        double c = src[0];
-        for (int s = 1; s < ns; ++s) c += src[(size_t)s * NV];
-        Cs[v] = c;
-    }
+    for (int v = t; v < NV; v += 64) Cs[v] = nul_slice_sum(part, b, ns, NV, v);
     __syncthreads();
     const double dn = (double)n;
     auto lag = [&](int a, int c, int l) -> NulZ {      // r_ac(l) / n, l >= 0
@@ -306,22 +301,17 @@ __global__ __launch_bounds__(kNulThreads) void stap_apply_kernel(const void* __r
                 win[p] = win[p + 1] = make_float2(0.f, 0.f);
                 if (in) {
                     const uint32_t v = *reinterpret_cast<const uint32_t*>(src + (p - H));
-                    win[p] = decode_u8iq(v & 0xFFFFu);
-                    win[p + 1] = decode_u8iq(v >> 16);
+                    win[p] = nul_raw(v, 0);
+                    win[p + 1] = nul_raw(v, 1);
                 }
             }
         }
     };
     if (!on) {
-        if constexpr (FMT == 0) {
-            const float4 v0 = *reinterpret_cast<const float4*>(static_cast<const float2*>(iq) + at);
-            y[0] = make_float2(v0.x, v0.y);
-            y[1] = make_float2(v0.z, v0.w);
-        } else {
-            const nul_u32x4 v0 = *reinterpret_cast<const nul_u32x4*>(static_cast<const uint16_t*>(iq) + at);
+        NulSamples<FMT, V> x;
+        x.load(iq, at);
 #pragma unroll
-            for (int q = 0; q < V; ++q) y[q] = decode_u8iq(q % 2 ? v0[q / 2] >> 16 : v0[q / 2] & 0xFFFFu);
-        }
+        for (int q = 0; q < V; ++q) y[q] = x[q];
     } else {
         for (int a = 0; a < A; ++a) {
             float2 win[W];

@@ -445,7 +445,7 @@ int gpsmi_pb_apply(gpsmi_pb* h, const void* iq, float* out, int nb, int32_t* cou
     if (rc) return rc;
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     return h->blk.apply_host(
-        iq, out, nb, h->sync.stream, "pulse blanking staging",
+        iq, out, nb, h->blk.out_bytes(nb), h->sync.stream, "pulse blanking staging",
         [&](const void* d_iq, void* d_out) { return pb_run(h, d_iq, d_out, nb, masks != nullptr); },
         [&] { return pb_finish(h, nb, counts, floors, masks); });
 }

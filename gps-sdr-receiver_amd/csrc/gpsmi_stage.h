@@ -104,12 +104,12 @@ struct BlockStage {
     }
     size_t out_bytes(int nb) const { return (size_t)nb * block_samples * sizeof(float2); }
 
-    // The host entry: upload, run(d_in, d_out) on the staged buffers, the output on its way down,
-    // finish() (the handle's result copies and StageSync::finish).
+    // The host entry: upload, run(d_in, d_out) on the staged buffers, the ob bytes of output (out_bytes(nb)
+    // per output row of the call) on their way down, finish() (the handle's result copies and
+    // StageSync::finish).
     template <typename Run, typename Finish>
-    int apply_host(const void* iq, void* out, int nb, hipStream_t stream, const char* what, Run&& run,
+    int apply_host(const void* iq, void* out, int nb, size_t ob, hipStream_t stream, const char* what, Run&& run,
                    Finish&& finish) {
-        const size_t ob = out_bytes(nb);
         int rc = io.upload(iq, in_bytes(nb), ob, stream, what);
         if (!rc) rc = run(static_cast<const void*>(io.in.p), static_cast<void*>(io.out.p));
         if (rc) return rc;
@@ -118,6 +118,20 @@ struct BlockStage {
     }
 };
 
+// What every call on nb blocks checks first: the pointers, and nb against the samples a call may hold.
+template <typename H>
+int stage_check_blocks(const H* h, const void* iq, const void* out, int nb, const char* fn) {
+    if (!h || !iq || !out) return fail(GPSMI_E_ARG, "%s: null argument", fn);
+    if (nb < 1 || (size_t)nb * h->blk.block_samples > ((size_t)1 << 31))
+        return fail(GPSMI_E_ARG, "%s: nb out of range: 1 .. 2^31 samples per call", fn);
+    return GPSMI_OK;
+}
+
+// Device pointers as the kernels read them: 4-byte (u8) / 16-byte (complex64) words in, 16-byte words out.
+inline bool stage_aligned(const BlockStage& b, const void* iq, const void* out) {
+    return (uintptr_t)iq % (b.fmt == GPSMI_IQ_U8 ? 4 : 16) == 0 && (uintptr_t)out % 16 == 0;
+}
+
 // The argument checks of a call on nb blocks, before any GPU work.  no_overlap: the filter's name
 // when input and output must not overlap (the output of one block is made of the input of the block
 // before it), null where that is not checked; aligned: the pointers are device pointers that the
@@ -125,15 +139,14 @@ struct BlockStage {
 template <typename H>
 int stage_check_call(const H* h, const void* iq, const void* out, int nb, const char* fn, const char* no_overlap,
                      bool aligned) {
-    if (!h || !iq || !out) return fail(GPSMI_E_ARG, "%s: null argument", fn);
+    const int rc = stage_check_blocks(h, iq, out, nb, fn);
+    if (rc) return rc;
     const BlockStage& b = h->blk;
-    if (nb < 1 || (size_t)nb * b.block_samples > ((size_t)1 << 31))
-        return fail(GPSMI_E_ARG, "%s: nb out of range: 1 .. 2^31 samples per call", fn);
     const char* i0 = static_cast<const char*>(iq);
     const char* o0 = static_cast<const char*>(out);
     if (no_overlap && !(o0 + b.out_bytes(nb) <= i0 || i0 + b.in_bytes(nb) <= o0))
         return fail(GPSMI_E_ARG, "%s: input and output overlap (no in-place %s)", fn, no_overlap);
-    if (aligned && ((uintptr_t)iq % (b.fmt == GPSMI_IQ_U8 ? 4 : 16) != 0 || (uintptr_t)out % 16 != 0))
+    if (aligned && !stage_aligned(b, iq, out))
         return fail(GPSMI_E_ARG, "%s: device input / output not aligned (4 bytes for u8, 16 for complex64)", fn);
     return GPSMI_OK;
 }

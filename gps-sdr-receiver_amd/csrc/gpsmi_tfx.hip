@@ -499,7 +499,7 @@ int gpsmi_tfx_apply(gpsmi_tfx* h, const void* iq, float* out, int nb, int32_t* c
     if (rc) return rc;
     GPSMI_HIP(hipSetDevice(h->cfg.device));
     return h->blk.apply_host(
-        iq, out, nb, h->sync.stream, "sweep excision staging",
+        iq, out, nb, h->blk.out_bytes(nb), h->sync.stream, "sweep excision staging",
         [&](const void* d_iq, void* d_out) { return tfx_run(h, d_iq, d_out, nb); },
         [&] { return tfx_finish(h, nb, counts, floors, masks); });
 }

@@ -56,9 +56,8 @@ class NullSteer(BlockFilter):
         self.last_weights = np.zeros(shape, dtype=np.complex128)
         return self.last_flags, self.last_gain_db, self.last_weights
 
-    def apply(self, blocks, out=None):
-        """Host blocks in ([antennas, n], [antennas, nb * n] or [antennas, nb, n]; complex64, or
-        uint16 with raw_u8), complex64 out ([n] for one block, else [nb, n]; into `out` when given)."""
+    def _input(self, blocks):
+        """Host blocks of every antenna, checked against the input format -> (C-contiguous array, nb)."""
         want = np.uint16 if self.raw_u8 else np.complex64
         x = np.asarray(blocks)
         if x.dtype != want:
@@ -66,8 +65,17 @@ class NullSteer(BlockFilter):
                             f'({np.dtype(want).name})')
         if x.ndim < 2 or x.shape[0] != self.antennas or x.size == 0 or (x.size // self.antennas) % self.n:
             raise ValueError(f'{self.antennas} antennas of blocks of {self.n} samples expected, got {x.shape}')
-        x = np.ascontiguousarray(x)
-        nb = x.size // self.antennas // self.n
+        return np.ascontiguousarray(x), x.size // self.antennas // self.n
+
+    def _kernel_ms(self, name):
+        ms = (C.c_float * 3)()
+        self._call(name, self.h, ms)
+        return tuple(float(v) for v in ms)
+
+    def apply(self, blocks, out=None):
+        """Host blocks in ([antennas, n], [antennas, nb * n] or [antennas, nb, n]; complex64, or
+        uint16 with raw_u8), complex64 out ([n] for one block, else [nb, n]; into `out` when given)."""
+        x, nb = self._input(blocks)
         shape = (self.n,) if x.shape[1:] == (self.n,) else (nb, self.n)
         if out is None:
             out = np.empty(shape, dtype=np.complex64)
@@ -105,15 +113,7 @@ class NullSteer(BlockFilter):
         power under those constraints, per block.  last_beam_flags [nb, nbeam] (1 adaptive, 0
         quiescent, -1 no weights: zeros out), last_beam_gain_db and last_beam_weights
         [nb, nbeam, antennas] describe the call.  One weight per antenna only (taps <= 1)."""
-        want = np.uint16 if self.raw_u8 else np.complex64
-        x = np.asarray(blocks)
-        if x.dtype != want:
-            raise TypeError(f'blocks dtype {x.dtype} does not match the input format '
-                            f'({np.dtype(want).name})')
-        if x.ndim < 2 or x.shape[0] != self.antennas or x.size == 0 or (x.size // self.antennas) % self.n:
-            raise ValueError(f'{self.antennas} antennas of blocks of {self.n} samples expected, got {x.shape}')
-        x = np.ascontiguousarray(x)
-        nb = x.size // self.antennas // self.n
+        x, nb = self._input(blocks)
         args = self._beam_args(nb, steer, nulls, mask)
         if out is None:
             out = np.empty((args[0], nb * self.n), dtype=np.complex64)
@@ -130,15 +130,11 @@ class NullSteer(BlockFilter):
 
     def last_beam_kernel_ms(self):
         """Device time of the last beams call's three kernels: (covariance, solve, apply) in ms."""
-        ms = (C.c_float * 3)()
-        self._call('last_beam_kernel_ms', self.h, ms)
-        return tuple(float(v) for v in ms)
+        return self._kernel_ms('last_beam_kernel_ms')
 
     def reset(self):
         """Nothing to reset: every block is worked on alone."""
 
     def last_kernel_ms(self):
         """Device time of the last call's three kernels: (covariance, solve, apply) in ms."""
-        ms = (C.c_float * 3)()
-        self._call('last_kernel_ms', self.h, ms)
-        return tuple(float(v) for v in ms)
+        return self._kernel_ms('last_kernel_ms')

@@ -37,12 +37,13 @@ def _cfg(n):
     raise ValueError(n)
 
 
-def _case_blocks(A, n, nb, raw_u8):
+def _case_blocks(A, n, nb, raw_u8, mix=None):
     """[A][nb * n] of the matrix: by block length and blocks per call the jammer counts 0, 1 and A - 1,
     an all-zero block among noisy ones (raw input cannot hold a zero: the recorder's mid level on every
-    antenna instead, copies as well) and a block whose antennas are exact copies of one another."""
+    antenna instead, copies as well) and a block whose antennas are exact copies of one another.
+    mix: which of the three mixes (default: the one of the matrix's block length n)."""
     rng = np.random.default_rng(1000 * A + n % 997 + 7 * nb + raw_u8)
-    k = NS.index(n)
+    k = NS.index(n) if mix is None else mix
     counts = (0, 1, A - 1)
 
     def noisy(j):
