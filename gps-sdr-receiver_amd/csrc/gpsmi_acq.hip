@@ -6,6 +6,8 @@
 //                         correlation kernel in three modes
 //   gpsmi_longcorr.h      the correlations of the other code lengths (gpsmi_pfa.h, gpsmi_bigfft.h,
 //                         gpsmi_direct.h), shared with the tracking handle
+//   gpsmi_acq_array.h     the array search (gpsmi_acq_search_array*): the deep search
+//                         over 2 .. 4 antennas, their complex correlations combined per lag
 //   gpsmi_refine.h        refinement of weak / deep hits (gpsmi_acq_refine): fine
 //                         Doppler, bit edge, sub-sample code phase, C/N0
 //   gpsmi_wtrk.h          bit-synchronous tracking of refined hits (gpsmi_acq_track)
@@ -40,6 +42,7 @@
 #include "gpsmi_sig.h"
 #include "gpsmi_profile.h"
 #include "gpsmi_acq_search.h"
+#include "gpsmi_acq_array.h"
 
 using namespace gpsmi;
 
@@ -615,6 +618,126 @@ int gpsmi_acq_search_deep_rows_dev(gpsmi_acq* h, const void* d_iq, size_t n, con
     const DeepShift d{carrier_hz, f_offset_hz};
     return acq_search(h, d_iq, false, n, prn, nsv, freqs_hz, nbins,
                       {n_coh, n_seg, &d, true, true, static_cast<float*>(d_rows)}, out, out_dev, nullptr);
+}
+
+// ---- the array search (kernel: gpsmi_acq_array.h) ----------------------------------------------
+// What gpsmi_acq_search_array_plan checks and sizes, without a handle: the scratch of one launch (the
+// spectra of all segments and antennas of its bins) and how many bins a launch takes.
+struct ArrayPlan { size_t count, scratch_bytes; int nbc; };
+
+static int array_plan(int cs, size_t n, int antennas, int nbins, int n_coh, int n_seg, double carrier_hz,
+                      double f_offset_hz, ArrayPlan* pl) {
+    GPSMI_REQUIRE(cs >= 1024 && cs <= 65536 && cs % 16 == 0, "code_samples must be a multiple of 16 in 1024..65536");
+    GPSMI_REQUIRE(antennas >= 2 && antennas <= 4, "antennas out of range 2..4");
+    GPSMI_REQUIRE(n <= (size_t(1) << 40) / (size_t)antennas, "n * antennas beyond 2^40 samples");
+    GPSMI_REQUIRE(nbins >= 0 && nbins <= 65535, "nbins out of range");
+    GPSMI_REQUIRE(n_coh >= 1 && n_coh <= 64, "n_coh out of range");
+    GPSMI_REQUIRE(n_seg >= 1 && n_seg <= 65535, "n_seg out of range 1..65535");
+    GPSMI_REQUIRE(n / ((size_t)n_coh * cs) >= (size_t)n_seg, "rows shorter than n_seg * n_coh code periods");
+    GPSMI_REQUIRE(std::isfinite(carrier_hz) && carrier_hz > 0.0, "carrier_hz must be positive");
+    GPSMI_REQUIRE(std::isfinite(f_offset_hz), "f_offset_hz must be finite");
+    if (cs != kFftN)
+        return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_search_array: code_samples 2048 only (not the native 16368 "
+                                         "correlation, nor a time-domain path)");
+    const size_t per_bin = (size_t)antennas * n_seg * cs * sizeof(float2);
+    if (per_bin > kNcScratchMax)
+        return fail(GPSMI_E_UNSUPPORTED, "gpsmi_acq_search_array: the %d segments of one bin over %d antennas "
+                                         "exceed the %zu MiB of scratch", n_seg, antennas, kNcScratchMax >> 20);
+    size_t nbc = kNcScratchMax / per_bin;
+    nbc = nbc > (size_t)nbins ? (size_t)nbins : nbc;
+    pl->count = (size_t)n_seg * n_coh * cs;
+    pl->nbc = (int)nbc;
+    pl->scratch_bytes = nbc * per_bin;
+    return GPSMI_OK;
+}
+
+// iq: [antennas][n] in the handle's input format, host or device; rows: optional, on the device
+static int acq_search_array(gpsmi_acq* h, const void* iq, bool on_host, size_t n, int antennas, const int32_t* prn,
+                            int nsv, const double* freqs, int nbins, int n_coh, int n_seg, double carrier_hz,
+                            double f_offset_hz, gpsmi_peak* out, void* out_dev, float* nbr, float* rows) {
+    GPSMI_REQUIRE(h && iq && prn && freqs && (out || !on_host), "null argument");
+    GPSMI_REQUIRE(out || out_dev, "no output requested");
+    GPSMI_REQUIRE(nsv >= 0 && nsv <= GPSMI_MAX_PRN, "nsv out of range");
+    ArrayPlan pl;
+    int rc = array_plan(h->cfg.code_samples, n, antennas, nbins, n_coh, n_seg, carrier_hz, f_offset_hz, &pl);
+    if (rc) return rc;
+    GPSMI_REQUIRE(n_coh <= h->cfg.n_cyc, "n_coh out of range 1..n_cyc");
+    for (int b = 0; b < nbins; ++b) GPSMI_REQUIRE(std::isfinite(freqs[b]), "freqs_hz must be finite");
+    for (int i = 0; i < nsv; ++i) {
+        GPSMI_REQUIRE(prn[i] >= 1 && prn[i] <= GPSMI_MAX_PRN, "prn out of range 1..37");
+        if (!h->have_rep[prn[i]]) return fail(GPSMI_E_STATE, "no replica set for PRN %d", (int)prn[i]);
+    }
+    if ((rc = acq_enter(h)) || nsv == 0 || nbins == 0) return rc;            // empty search: nothing to do
+    // host rows go up packed, only what the search reads of each: [antennas][count]
+    const char* d_iq = static_cast<const char*>(iq);
+    size_t stride = n;
+    if (on_host) {
+        if ((rc = h->d_iq.reserve((size_t)antennas * pl.count, "gpsmi_acq input block"))) return rc;
+        for (int a = 0; a < antennas; ++a)
+            GPSMI_HIP(hipMemcpyAsync(reinterpret_cast<char*>(h->d_iq.p) + a * h->iq_bytes(pl.count),
+                                     d_iq + a * h->iq_bytes(n), h->iq_bytes(pl.count), hipMemcpyHostToDevice,
+                                     h->stream));
+        d_iq = reinterpret_cast<const char*>(h->d_iq.p);
+        stride = pl.count;
+    }
+    const int cs = h->cfg.code_samples;
+    const size_t ns = (size_t)nbins * n_seg;
+    std::vector<int> shift;
+    try { shift.resize(ns); } catch (const std::bad_alloc&) {
+        return fail(GPSMI_E_NOMEM, "gpsmi_acq_search_array: out of host memory");
+    }
+    const DeepShift ds{carrier_hz, f_offset_hz};
+    for (int b = 0; b < nbins; ++b)
+        for (int sg = 0; sg < n_seg; ++sg) shift[(size_t)b * n_seg + sg] = deep_shift(freqs[b], ds, sg, n_coh, cs);
+    if ((rc = acq_reserve(h, nbins, nsv)) ||
+        (rc = h->d_nc.reserve(pl.scratch_bytes / sizeof(float2), "gpsmi_acq segment scratch")) ||
+        (rc = acq_stage(h, prn, nsv, freqs, nbins)) || (rc = h->d_shift.reserve(ns, "gpsmi_acq lag rotations")) ||
+        (rc = acq_tables(h, {{h->d_shift.p, shift.data(), ns * sizeof(int)}})) || (rc = acq_begin(h)))
+        return rc;
+    float2* d_nbr = nbr ? h->d_nbr.p : nullptr;
+    for (int b0 = 0; b0 < nbins; b0 += pl.nbc) {
+        const int nb = nbins - b0 < pl.nbc ? nbins - b0 : pl.nbc;
+        for (int a = 0; a < antennas; ++a)       // the single-antenna search's spectra of row a
+            with_value<4, 1>(n_coh >= 4 ? 4 : 1, [&](auto g) { with_fmt(h->iq_fmt, [&](auto fmt) {
+                constexpr int G = decltype(g)::value;
+                hipLaunchKernelGGL((acq_spectrum_kernel<G, decltype(fmt)::value>), dim3(nb, n_seg), dim3(256 * G), 0,
+                                   h->stream, static_cast<const void*>(d_iq + a * h->iq_bytes(stride)), h->d_t32.p,
+                                   h->d_omega.p + b0, n_coh, n_seg, h->d_nc.p + (size_t)a * nb * n_seg * cs,
+                                   h->d_tw.p);
+            }); });
+        with_value<2, 3, 4>(antennas, [&](auto na) {
+            hipLaunchKernelGGL(acq_corr_array_kernel<decltype(na)::value>, dim3(nsv, nb), dim3(256), 0, h->stream,
+                               h->d_nc.p, h->d_rep.p, h->d_slot.p, h->d_peaks.p, nsv, n_seg, b0, nb, h->d_tw.p, d_nbr,
+                               h->d_shift.p + (size_t)b0 * n_seg, rows, nbins);
+        });
+    }
+    if ((rc = acq_end(h)) || (rc = acq_copy_out(h, nbins, nsv, out, out_dev, nbr))) return rc;
+    return gpsmi_acq_wait(h);
+}
+
+int gpsmi_acq_search_array(gpsmi_acq* h, const void* iq, size_t n, int antennas, const int32_t* prn, int nsv,
+                           const double* freqs_hz, int nbins, int n_coh, int n_seg, double carrier_hz,
+                           double f_offset_hz, gpsmi_peak* out, float* nbr) {
+    return acq_search_array(h, iq, true, n, antennas, prn, nsv, freqs_hz, nbins, n_coh, n_seg, carrier_hz,
+                            f_offset_hz, out, nullptr, nbr, nullptr);
+}
+
+int gpsmi_acq_search_array_dev(gpsmi_acq* h, const void* d_iq, size_t n, int antennas, const int32_t* prn, int nsv,
+                               const double* freqs_hz, int nbins, int n_coh, int n_seg, double carrier_hz,
+                               double f_offset_hz, gpsmi_peak* out, void* out_dev, void* d_rows) {
+    return acq_search_array(h, d_iq, false, n, antennas, prn, nsv, freqs_hz, nbins, n_coh, n_seg, carrier_hz,
+                            f_offset_hz, out, out_dev, nullptr, static_cast<float*>(d_rows));
+}
+
+int gpsmi_acq_search_array_plan(int code_samples, size_t n, int antennas, int nbins, int n_coh, int n_seg,
+                                double carrier_hz, double f_offset_hz, size_t* scratch_bytes,
+                                int* bins_per_launch) {
+    ArrayPlan pl;
+    const int rc = array_plan(code_samples, n, antennas, nbins, n_coh, n_seg, carrier_hz, f_offset_hz, &pl);
+    if (rc) return rc;
+    if (scratch_bytes) *scratch_bytes = pl.scratch_bytes;
+    if (bins_per_launch) *bins_per_launch = pl.nbc;
+    return GPSMI_OK;
 }
 
 // ---- refinement of weak / deep hits (kernels and plan: gpsmi_refine.h) ------------------------

@@ -194,6 +194,7 @@ EXPORTS = [
     'gpsmi_acq_search_dev_async', 'gpsmi_acq_wait',
     'gpsmi_acq_search_nc', 'gpsmi_acq_search_nc_dev',
     'gpsmi_acq_search_deep', 'gpsmi_acq_search_deep_dev', 'gpsmi_acq_search_deep_rows_dev',
+    'gpsmi_acq_search_array', 'gpsmi_acq_search_array_dev', 'gpsmi_acq_search_array_plan',
     'gpsmi_acq_collective_dev', 'gpsmi_acq_collective_plan',
     'gpsmi_acq_peaks_dev', 'gpsmi_acq_peaks_plan',
     'gpsmi_acq_refine', 'gpsmi_acq_refine_dev', 'gpsmi_acq_refine_plan',
@@ -283,6 +284,12 @@ def load():
                                       C.c_double, C.c_double, vp, vp],
         'gpsmi_acq_search_deep_rows_dev': [vp, vp, sz, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                            C.c_double, C.c_double, vp, vp, vp],
+        'gpsmi_acq_search_array': [vp, vp, sz, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                   C.c_double, C.c_double, vp, vp],
+        'gpsmi_acq_search_array_dev': [vp, vp, sz, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                       C.c_double, C.c_double, vp, vp, vp],
+        'gpsmi_acq_search_array_plan': [C.c_int, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                        P(sz), P(C.c_int)],
         'gpsmi_acq_collective_dev': [vp, vp, C.c_int, C.c_int, vp, C.c_int, P(CollectiveGrid), vp, vp],
         'gpsmi_acq_collective_plan': [C.c_int, C.c_int, C.c_int, vp, C.c_int, P(CollectiveGrid),
                                       P(sz), P(C.c_int)],

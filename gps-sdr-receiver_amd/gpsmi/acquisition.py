@@ -125,6 +125,31 @@ class Acquisition:
                     satLst.remove(s)
         return sorted(satFound, reverse=True)
 
+    def sweepArraySats(self, data, antennas, freqs, satLst, satFound, n_coh=4, n_seg=250, f_offset=0.0):
+        """sweepDeepSats's first-hit contract over the array surface (AcqEngine.search_array: the
+        deep search over `antennas` = 2 .. 4 rows whose complex correlations are combined per lag,
+        DESIGN.md 4.2s), for satellites that no single antenna shows.  `data`: [antennas][n] on
+        the host or a (device pointer, n) pair with the rows n samples apart.  The same hit rule
+        (bins scanned in order, the first normMaxCorr > CORR_MIN claims an SV) and the same hit
+        format as sweepDeepSats; normMaxCorr is that of T, a power."""
+        c = self.cfg
+        freqs = list(freqs)
+        if freqs and satLst:
+            prns = list(satLst)
+            table = self.engine.search_array(data, antennas, prns, freqs, n_coh, n_seg, f_offset=f_offset)
+            for b, f in enumerate(freqs):
+                hit = []
+                for j, s in enumerate(prns):
+                    if s not in satLst:
+                        continue
+                    nmc = norm_max_corr(table[b, j])
+                    if nmc > c.corr_min:
+                        satFound.append((nmc, s, f, int(table[b, j]['argmax'])))
+                        hit.append(s)
+                for s in hit:
+                    satLst.remove(s)
+        return sorted(satFound, reverse=True)
+
     def refineHits(self, data, found, n_ms=None, f_offset=0.0, **cfg):
         """Refines the ``(normMaxCorr, satNo, freq, delay)`` entries that sweepWeakSats /
         sweepDeepSats return (AcqEngine.refine: fine Doppler, bit edge, sub-sample code phase,

@@ -182,6 +182,17 @@ def peaks_plan(code_samples, nsv_rows, nbins, k=4, guard_lags=-1, bins=None):
     return scratch.value, wgs.value
 
 
+def search_array_plan(code_samples, n, antennas, nbins, n_coh, n_seg, f_offset=0.0, carrier_hz=1575.42e6):
+    """gpsmi_acq_search_array_plan: the argument checks of AcqEngine.search_array that need no
+    handle, without a GPU, for rows of `n` samples.  -> (scratch_bytes of a launch, bins a launch
+    takes); EngineError where the call would refuse."""
+    scratch, nbc = C.c_size_t(), C.c_int()
+    check(_lib.load().gpsmi_acq_search_array_plan(
+        int(code_samples), int(n), int(antennas), int(nbins), int(n_coh), int(n_seg), float(carrier_hz),
+        float(f_offset), C.byref(scratch), C.byref(nbc)), 'gpsmi_acq_search_array_plan')
+    return scratch.value, nbc.value
+
+
 def _records(sats, dtype):
     """Refined records as the table a stage takes: (prn, f_hz, tau), or (prn, skip_ms, f_hz, tau)
     where the stage has a second int32 (CANCEL_SAT_DTYPE, SIG_SAT_DTYPE and PROF_SAT_DTYPE are one
@@ -369,6 +380,41 @@ class AcqEngine:
         try:
             check(getattr(self.lib, name)(self.h, d_iq, n, *tab, int(n_coh), int(n_seg), float(carrier_hz),
                                           float(f_offset), ptr(out), *last), name)
+        finally:
+            if held is not None:
+                held.free()
+        return (out, nb) if nbr else out
+
+    def search_array(self, data, antennas, prns, freqs, n_coh, n_seg, f_offset=0.0, carrier_hz=L1_HZ,
+                     out_dev=None, nbr=False, rows=None):
+        """Array search (gpsmi_acq_search_array): search_deep over `antennas` = 2 .. 4 rows at once,
+        the complex correlations of the rows combined per lag,
+            T = (sum_s sum_a |c_a|^2 + 2 sum_{a<b} |sum_s c_a conj(c_b)|) / (antennas n_seg),
+        so that a satellite no single row shows stands out by the gain of the array.  data: [A][n]
+        on the host in the input format, antenna 0 first, or a (c_void_p, n) device pair of such
+        rows of n samples.  Arguments and returns otherwise as search_deep; the table holds the
+        records of T, a power.  rows: a DeviceBuffer that receives T of every cell, float32
+        [nsv][nbins][code_samples] (host input is uploaded first; not together with nbr)."""
+        A = int(antennas)
+        tab, out, nb = self._tables(prns, freqs, nbr)
+        if rows is not None:
+            if nbr:
+                raise ValueError('nbr is not returned together with rows')
+            need = out.size * self.cfg.code_samples * 4
+            if rows.nbytes < need:
+                raise ValueError(f'rows holds {rows.nbytes} bytes, the surfaces need {need}')
+        d_iq, n, host = self._input(data, nbr, lead=None if isinstance(data, tuple) else (A,))
+        held = None
+        if rows is not None and host:              # only the device entry point keeps rows
+            nbytes = A * n * np.dtype(_iq_dtype(self.raw_u8)).itemsize
+            held = DeviceBuffer(max(nbytes, 1), self.cfg.device)
+            check(self.lib.gpsmi_dev_upload(held.device, held.ptr, d_iq, nbytes), 'gpsmi_dev_upload')
+            d_iq, host = held.ptr, False
+        fn, name = self._export('gpsmi_acq_search_array', host)
+        last = (ptr(nb),) if host else (out_dev, None if rows is None else rows.ptr)
+        try:
+            check(fn(self.h, d_iq, n, A, *tab, int(n_coh), int(n_seg), float(carrier_hz), float(f_offset),
+                     ptr(out), *last), name)
         finally:
             if held is not None:
                 held.free()

@@ -199,6 +199,19 @@ def largest_peak_hits(acq, data, prns, freqs, n_coh=4, n_seg=250, f_offset=0.0, 
             for j, (s, b) in enumerate(zip(prns, best)) if over[b, j]]
 
 
+def array_peak_hits(acq, data, antennas, prns, freqs, n_coh=4, n_seg=250, f_offset=0.0, corr_min=None):
+    """largest_peak_hits over the array surface (AcqEngine.search_array over `antennas` rows,
+    DESIGN.md 4.2s): hits ``(normMaxCorr, satNo, freq, delay)``, one per PRN at the bin of its
+    largest peak, with `corr_min` only among the bins whose normMaxCorr exceeds it.  `data`:
+    [antennas][n] on the host or a (device pointer, n) pair with the rows n samples apart."""
+    tab = acq.engine.search_array(data, antennas, list(prns), list(freqs), n_coh, n_seg, f_offset=f_offset)
+    nmc = (tab['peak'].astype(np.float64) - tab['mean']) / tab['std']
+    over = nmc > corr_min if corr_min is not None else np.ones(nmc.shape, bool)
+    best = np.where(over, tab['peak'], -np.inf).argmax(axis=0)
+    return [(float(nmc[b, j]), s, freqs[b], int(tab[b, j]['argmax']))
+            for j, (s, b) in enumerate(zip(prns, best)) if over[b, j]]
+
+
 def hits_of_picks(picks, cols, prns, freqs, corr_min):
     """The hits ``(z, satNo, freq, lag)`` of AcqEngine.peaks' picks [nsv][k] and columns
     [nsv][k][2][nbins]: one per pick with z > corr_min, in pick order.  The bin is

@@ -759,6 +759,69 @@ def _beam_pass(acq, dev, n, found, out, cov, v, rho, antennas, source, freqs, f_
         ns.close()
 
 
+def _array_pass(acq, dev, n, prns, freqs, n_coh, n_seg, corr_min, antennas, source, f_offset, track_cfg, st):
+    """measure's array=True: the array search over all rows, per PRN the largest peak
+    over `corr_min` (pipeline.array_peak_hits); the hits' signatures at tau = the argmax and f = the
+    bin (AcqEngine.signatures); one beam per hit steered at its signature, no null (NullSteer.beams over
+    the whole blocks of the snapshot, complex64); every hit refined on its own beam; the confirmed
+    records with a code phase, ghosts dropped over all of them together; with source 'track' each
+    tracked on its beam.  A hit whose refinement on the beam is not confirmed is dropped.
+    -> records.  Fills st: array_ms, signature_ms, beams_ms, hits, beams, found, refined."""
+    from .engine import DeviceBuffer
+    from .nulling import NullSteer
+    from .pipeline import array_peak_hits, refine_centred
+    c = acq.cfg
+    cs = c.code_samples
+    st.update(array_ms=0.0, signature_ms=0.0, beams_ms=0.0, hits=[], beams=[])
+    none = np.zeros(0, MEAS_DTYPE)
+    hits = array_peak_hits(acq, dev, antennas, prns, freqs, n_coh, n_seg, f_offset=f_offset, corr_min=corr_min)
+    st['array_ms'] = acq.engine.last_ms()
+    st['device_ms'] += st['array_ms']
+    st['hits'] = list(hits)
+    nb = n // c.ngps
+    nn = nb * c.ngps
+    if not hits or nn < min_samples(cs):
+        return none
+    cov = acq.engine.signatures(dev, [(s, f, float(d)) for _, s, f, d in hits], antennas, f_offset=f_offset)[0]
+    st['signature_ms'] = acq.engine.last_ms()
+    st['device_ms'] += st['signature_ms']
+    v, quality = signature_vectors(cov)
+    st['signature'], st['quality'] = v, quality
+    was_raw = acq.engine.raw_u8
+    ns = NullSteer(c, antennas=antennas, raw_u8=was_raw)
+    rows = DeviceBuffer(len(hits) * nn * 8, c.device)       # (one hit per PRN: 37 rows at the most, <= BEAM_MAX)
+    try:                                            # the beams are complex64 whatever the data is
+        if was_raw:
+            acq.engine.set_input_format(False)
+        ns.beams_dev(dev[0], rows.ptr, nb, v, None, np.zeros(len(hits), dtype=np.uint32), in_stride=n, out_stride=nn)
+        st['beams_ms'] = ns.last_ms()
+        st['device_ms'] += st['beams_ms']
+        gain, flags = ns.last_beam_gain_db, ns.last_beam_flags
+        row = [(rows.at(j * nn * 8), nn) for j in range(len(hits))]
+        found, recs = [], []
+        for j, hit in enumerate(hits):
+            f1, rec1, ms = refine_centred(acq, row[j], [hit], f_offset=f_offset)
+            st['device_ms'] += ms
+            found, recs = found + f1, recs + [rec1]
+        rec = np.concatenate(recs)
+        st['found'], st['refined'] = found, rec
+        good = np.flatnonzero((rec['confirmed'] == 1) & (rec['code_phase'] >= 0) & ~drop_ghosts(rec))
+        for j, hit in enumerate(hits):
+            st['beams'].append({'prn': int(hit[1]), 'confirmed': bool(rec['confirmed'][j] == 1), 'kept': j in good,
+                                'gain_db': float(np.mean(gain[:, j])), 'flags': sorted(set(flags[:, j].tolist()))})
+        rec, _, out = refined_records(rec, found, cs, f_offset)
+        assert len(out) == len(good)
+        if source == 'track':
+            for k, j in enumerate(good):
+                _track_records(acq, row[j], rec[k:k + 1], out[k:k + 1], nn, f_offset, track_cfg, st)
+        return out
+    finally:
+        if was_raw:
+            acq.engine.set_input_format(True)
+        rows.free()
+        ns.close()
+
+
 def authentic_first(report):
     """With a verdict (spoof_resolve) the authentic fix goes first in report.fixes, whatever order
     twin_fixes gave them; sets and one_source follow and authentic becomes 0.  -> fixes[0]."""
@@ -885,7 +948,7 @@ def _track_records(acq, dev, rec, out, n, f_offset, track_cfg, st):
 
 
 def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=None, spoof=False, antennas=None,
-            beams=False, profile=False, **cfg):
+            beams=False, profile=False, array=False, **cfg):
     """The satellites of one snapshot: MEAS_DTYPE records, one per satellite found, sorted by PRN.
 
     `acq`: an acquisition.Acquisition; `data`: the samples in its input format (complex64, or the
@@ -913,7 +976,7 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
     spoof_keep: a PRN that is in the air twice comes back with two records.  -> (records,
     SpoofReport); `min_doubled`: the doubled PRNs that set its alarm; stats also receives spoof
     (the report) and peaks_ms.  With the option off nothing of this runs.
-    `antennas` (with `spoof` only): A = 2 .. 8 -- `data` is [A][n] on the host, or
+    `antennas` (with `spoof`, or with `array` below): A = 2 .. 8 -- `data` is [A][n] on the host, or
     (pointer, n) with A rows n samples apart behind the pointer.  Every stage above reads row 0, the
     first n samples, exactly as without the option; after spoof_keep (and tracking) the kept records'
     signatures are taken once over all rows (Acquisition.signatureHits) and spoof_resolve fills the
@@ -931,7 +994,16 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
     (Acquisition.profileHits: the default taps, 20-ms runs from the record's bit edge) and
     profile_verdict fills the report's profile_t, distorted and profile; the alarm is then raised as
     well when the PRNs doubled or distorted count `min_doubled` -- a copy within the guard of the peaks shows here.  stats receives
-    profile_ms.  Without the option nothing of this runs."""
+    profile_ms.  Without the option nothing of this runs.
+    `array` (with `antennas` = 2 .. 4, not together with `spoof` or `cancel`): True --
+    the satellites are searched for over all rows at once, so that one no single antenna shows is
+    found by the gain of the array: pipeline.array_peak_hits over `prns` x the bins, per PRN the
+    largest peak over `corr_min`; the hits' signatures at their argmax and bin; one beam per hit
+    steered at its signature (NullSteer.beams, no null) over the n // ngps whole blocks; refinement
+    of every hit on its own beam and, with source 'track', tracking there; confirmed records, ghosts
+    dropped.  A hit whose refinement on the beam is not confirmed is dropped.  stats receives array_ms,
+    signature_ms, beams_ms, hits and beams (per hit: prn, confirmed, kept, mean gain_db, flags).
+    Without the option nothing of this runs."""
     from .acquisition import SAT_ALL
     from .engine import CANCEL_OUT_DTYPE, DeviceBuffer
     c = acq.cfg
@@ -945,12 +1017,16 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
         raise TypeError(f'unknown options {sorted(cfg)}')
     if spoof and cancel not in (None, False):
         raise ValueError('spoof and cancel are not combined')
+    if array and antennas is None:
+        raise ValueError('array goes with antennas=A (the search combines the antennas)')
+    if array and (spoof or cancel not in (None, False)):
+        raise ValueError('array is not combined with spoof or cancel')
     if antennas is not None:
-        if not spoof:
+        if not spoof and not array:
             raise ValueError('antennas goes with spoof=True (the signatures serve the spoofing check)')
         antennas = int(antennas)
-        if not 2 <= antennas <= 8:
-            raise ValueError('antennas must be 2 .. 8')
+        if not 2 <= antennas <= (4 if array else 8):
+            raise ValueError('antennas must be 2 .. 4' if array else 'antennas must be 2 .. 8')
     elif beams:
         raise ValueError('beams goes with antennas=A (the beams combine the antennas)')
     if profile and not spoof:
@@ -978,6 +1054,12 @@ def measure(acq, data, prns=None, f_offset=0.0, source=None, stats=None, cancel=
             buf.upload(host)
             dev = (buf.ptr, n)
         st = {'device_ms': 0.0, 'found': [], 'refined': None}
+        if array:
+            out = _array_pass(acq, dev, n, prns, freqs, n_coh, n_seg, corr_min, antennas, source, f_offset, track_cfg, st)
+            out = out[np.argsort(out['prn'], kind='stable')]
+            if stats is not None:
+                stats.update(st)
+            return out
         if spoof:
             rec, found, out, report = _spoof_pass(acq, dev, n, prns, freqs, n_coh, n_seg, corr_min, f_offset, st,
                                                   min_doubled)
@@ -1287,7 +1369,7 @@ def _collective_fix(acq, data, ephs, t_gps, pos, f_offset, cfg, stats):
 
 def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, cancel=None, stats=None,
                  collective=None, collective_cfg=None, spoof=False, antennas=None, beams=False, profile=False,
-                 **cfg):
+                 array=False, **cfg):
     """measure -> (doppler_fix when `pos` is None) -> coarse_time_fix.  `t_gps`: the GPS seconds
     of week of the first sample as far as known; `cancel`, `stats`: measure's.  -> (Fix,
     measurements, device ms).  The Fix's t_gps is that of its `sample`.
@@ -1311,14 +1393,19 @@ def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, ca
     were measured on their own beams.
     `profile` (with `spoof` only): measure's -- report.distorted and profile_t, and an
     alarm that is raised as well when the PRNs doubled or distorted count `min_doubled`; the fixes are
-    made as without it."""
+    made as without it.
+    `array` (with `antennas` = 2 .. 4, without `spoof`, `cancel`, `beams` and
+    `collective`): measure's -- the satellites are found over all antennas at once and measured on
+    their own beams."""
+    if array and (antennas is None or spoof or beams or profile or collective):
+        raise ValueError('array goes with antennas=A alone (not with spoof, beams, profile or collective)')
     if collective not in (None, False, True, 'always'):
         raise ValueError(f"collective {collective!r}: None, False, True or 'always'")
     if collective and pos is None:
         raise ValueError('collective detection needs an a-priori position')
     if spoof and collective:
         raise ValueError('spoof and collective are not combined')
-    if antennas is not None and not spoof:
+    if antennas is not None and not spoof and not array:
         raise ValueError('antennas goes with spoof=True (the signatures serve the spoofing check)')
     if beams and antennas is None:
         raise ValueError('beams goes with antennas=A (the beams combine the antennas)')
@@ -1332,7 +1419,7 @@ def snapshot_fix(acq, data, ephs, t_gps, pos=None, f_offset=0.0, source=None, ca
                                **({'profile': True} if profile else {}), **cfg)
     else:
         meas = measure(acq, data, prns=sorted(ephs), f_offset=f_offset, source=source, stats=stats, cancel=cancel,
-                       **cfg)
+                       **({'antennas': antennas, 'array': True} if array else {}), **cfg)
     ms = stats.get('device_ms', 0.0)
     if report is not None and report.doubled:
         if len(set(meas['prn'].tolist())) < MIN_SAT:

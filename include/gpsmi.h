@@ -286,6 +286,56 @@ int gpsmi_acq_search_deep_rows_dev(gpsmi_acq* h, const void* d_iq, size_t n,
                                    const double* freqs_hz, int nbins, int n_coh, int n_seg,
                                    double carrier_hz, double f_offset_hz,
                                    gpsmi_peak* out, void* out_dev, void* d_rows);
+/* Array search (float64 restatement: tests/array_ref.py): the deep search over
+ * antennas = A in 2 .. 4 antenna rows at once, for satellites that no single row shows.  The complex
+ * correlations of the rows are combined per lag before anything is detected: a satellite's spatial
+ * signature does not change over the span, so the cross products between antennas add coherently over
+ * all segments, while the data bits, the residual carrier phase and the bin's frequency error are
+ * common to the antennas and drop out of them.
+ * Arguments as gpsmi_acq_search_deep[_dev], plus antennas.  iq is A rows of n samples, [A][n] with
+ * antenna 0 first (the layout of gpsmi_nul_apply and gpsmi_acq_signature), in the handle's input
+ * format; of each row the first n_seg * n_coh * code_samples samples are read.
+ * For antenna a, bin b and segment s the wipe-off, the fold and the spectrum are exactly the deep
+ * search's for that row alone (the same kernel, launched per row).  Let c[a][s][n] be the complex
+ * circular correlation with the PRN's replica scaled by 1 / 2048, the value whose magnitude the deep
+ * search takes, and m = m[b][s] the deep search's shift table, the same for all antennas.  Per cell
+ *     D[i]    = sum_s sum_a |c[a][s][(i + m) mod cs]|^2
+ *     R_ab[i] = sum_s c[a][s][(i + m) mod cs] * conj(c[b][s][(i + m) mod cs])           (a < b)
+ *     T[i]    = (D[i] + 2 * sum_{a<b} |R_ab[i]|) * float32(1 / (A * n_seg))
+ * in float32 in one fixed order: ascending s, then ascending a, then the pairs in lexicographic order
+ * (0,1) (0,2) .. (1,2) ..; |R| is a float32 square root good to 1 ulp.  With C = sum_s c c^H,
+ * T n_seg bounds w^H C w / A over weight vectors w of unit-modulus entries from above and reaches it
+ * where every pair can be phased at once (always for A = 2, and for a satellite alone in its cell).
+ * out / nbr / out_dev are the deep search's records of T: first-index argmax, peak, mean, population
+ * std, and T[argmax -+ 1] circularly.  d_rows (gpsmi_acq_search_array_dev; may be NULL) receives T of
+ * every cell as float32 [nsv][nbins][code_samples] on the device, and the rows are what the records are
+ * statistics of: argmax and peak exactly.  T is a power, the deep search's S a magnitude: they are
+ * not on one scale and no byte equality between the two searches is claimed.  The same arguments give
+ * the same bytes from either entry point; GPSMI_IQ_U8 input gives the bytes of its complex64 decode; a
+ * cell's record and row do not depend on which bins or PRNs share the call.
+ * Bins are taken in chunks as in the deep search; the segments of ONE bin over all antennas must fit
+ * the scratch of 512 MiB (A * n_seg * 2048 * 8 bytes), beyond that GPSMI_E_UNSUPPORTED.  Errors as
+ * the deep search's; antennas outside 2 .. 4 and n * A beyond 2^40 are GPSMI_E_ARG; code_samples
+ * other than 2048 -- the native 16368 path, whose sixteen lags per thread leave no registers for the
+ * accumulators, and every time-domain path -- is GPSMI_E_UNSUPPORTED.  gpsmi_acq_last_ms reports the
+ * call.  gpsmi_acq_search_array_plan makes the argument checks that need no handle (everything but
+ * n_coh <= n_cyc, the replicas and the bin frequencies) without a GPU, and reports the scratch of a
+ * launch and how many bins a launch takes.
+ * Not done: more than four antennas (coherent groups of up to four, added non-coherently, would be
+ * the way), spatial whitening against a jammer (a jammer raises every lag alike).                  */
+int gpsmi_acq_search_array(gpsmi_acq* h, const void* iq, size_t n, int antennas,
+                           const int32_t* prn, int nsv,
+                           const double* freqs_hz, int nbins, int n_coh, int n_seg,
+                           double carrier_hz, double f_offset_hz,
+                           gpsmi_peak* out, float* nbr);
+int gpsmi_acq_search_array_dev(gpsmi_acq* h, const void* d_iq, size_t n, int antennas,
+                               const int32_t* prn, int nsv,
+                               const double* freqs_hz, int nbins, int n_coh, int n_seg,
+                               double carrier_hz, double f_offset_hz,
+                               gpsmi_peak* out, void* out_dev, void* d_rows);
+int gpsmi_acq_search_array_plan(int code_samples, size_t n, int antennas, int nbins, int n_coh, int n_seg,
+                                double carrier_hz, double f_offset_hz,
+                                size_t* scratch_bytes, int* bins_per_launch);
 /* Collective detection (numpy restatement: tests/collective_ref.py): instead of a
  * decision per satellite, the normalised surfaces of all satellites are added at the lags that a
  * candidate receiver state (east, north, coarse time, clock) predicts, and the state where the sum

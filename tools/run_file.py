@@ -7,7 +7,7 @@ gpseval) as one command on the GPU path.
                              [--ephemeris gpsEphem.json] [--cpu-acq] [--excise] [--sweep [L]] [--blank] [--json]
                              [--antenna FILE ... --null [--null-taps T]]
                              [--format FMT --fs HZ --if HZ --conjugate] [--deep-acq SECONDS [--refine [--track [--weak-fix]]]]
-                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]] [--spoof-check [K] [--profile-check]] [--antenna FILE ... [--beams]]]]
+                             [--save-ephemeris PATH] [--snapshot SECONDS --ephemeris E --time T [--near LAT,LON[,H]] [--cancel [DBHZ]] [--collective [RADIUS_KM]] [--spoof-check [K] [--profile-check]] [--antenna FILE ... [--beams]]] [--antenna FILE ... --array-search]]
 
     <recording.bin>   what gpsbin.py records and streamData reads (gpsrecv.py:162-173):
                       little-endian uint16 per sample, low byte I, high byte Q, 2.048 Msps
@@ -83,7 +83,10 @@ is the spoofer's, and the report names the authentic fix (first) and says whethe
 direction ('authentic', 'one_source', 'one_direction').  --beams on top of that measures every
 record again on a beam of its own over the antennas, steered at its signature and with a null at the spoofer
 where one is found and the null costs at most 3 dB; the report gains a 'beams' entry with one line per record
-(the null, the predicted gain, C/N0 on antenna 0).  --profile-check (with --spoof-check; one
+(the null, the predicted gain, C/N0 on antenna 0).  --array-search (with --snapshot and one to three --antenna FILE, without --spoof-check) searches for the satellites
+over all antennas at once (gpsmi_acq_search_array) and measures every hit on a beam of its own: a
+four-antenna recording then finds what no single antenna shows; the report names the satellites antenna 0 alone would
+have found beside those of the array.  --profile-check (with --spoof-check; one
 antenna is enough) takes every record's multi-tap correlation profile and tests whether one code replica
 explains it: a copy within two chips of the authentic code, which the peaks cannot separate, shows as a
 distorted profile; such PRNs are listed ('distorted') and count towards the alarm like doubled ones, and the
@@ -280,7 +283,8 @@ def parse_time(text, ephs):
 
 
 def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, frontend=None, excise=False,
-             blank=False, cancel=None, collective_km=None, spoof_k=None, antennas=(), beams=False, profile=False):
+             blank=False, cancel=None, collective_km=None, spoof_k=None, antennas=(), beams=False, profile=False,
+             array=False):
     """--snapshot: gpsmi.snapshot.snapshot_fix on the first `seconds` behind `start_stream`, read
     and filtered block by block as run() feeds its receiver.  `cancel`: --cancel's C/N0 threshold
     (snapshot.measure's `cancel`); None leaves everything as it is without the flag.
@@ -292,8 +296,11 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
     `beams` (with `antennas`): --beams, every record is measured again on a beam of its own over the antennas, with
     a null at the spoofer where one is found (snapshot_fix's beams=True).
     `profile` (with `spoof_k`): --profile-check, every record's multi-tap correlation profile is tested for a second
-    copy of the code within the guard of the peaks (snapshot_fix's profile=True)."""
-    from gpsmi import ingest, position as P, snapshot as S
+    copy of the code within the guard of the peaks (snapshot_fix's profile=True).
+    `array` (with one to three `antennas`, without `spoof_k`): --array-search, the satellites are searched for
+    over all antennas at once and measured on their own beams (snapshot_fix's array=True); one
+    further deep search of antenna 0 alone tells the report which of them that antenna would have found."""
+    from gpsmi import ingest, pipeline, position as P, snapshot as S
     from gpsmi.acquisition import Acquisition
     from gpsmi.conditioning import Conditioner
     from gpsmi.engine import Config
@@ -324,9 +331,16 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
                                            **({'antennas': 1 + len(antennas)} if antennas else {}),
                                            **({'beams': True} if beams else {}),
                                            **({'profile': True} if profile else {}),
+                                           **({'array': True} if array else {}),
                                            **({} if collective_km is None else
                                               {'collective': True, 'collective_cfg': {'radius_m': 1.0e3 * collective_km}}))
             wall = time.perf_counter() - t0
+            alone = None
+            if array:                                # for the report only: what antenna 0 shows by itself
+                freqs = [cfg.min_freq + cfg.step_freq * i
+                         for i in range(int(round((cfg.max_freq - cfg.min_freq) / cfg.step_freq)))]
+                alone = pipeline.largest_peak_hits(acq, np.ascontiguousarray(data[0]), sorted(ephemerides), freqs, 4,
+                                                   need // cfg.code_samples // 4, corr_min=cfg.corr_min)
         finally:
             cond.close()
             if acq is not None:
@@ -384,6 +398,15 @@ def snapshot(path, seconds, ephemerides, t_gps, near=None, start_stream=0, front
                                      'cn0_before_dbhz': None if np.isnan(before['cn0_dbhz'][i])
                                      else round(float(before['cn0_dbhz'][i]), 2)}
                                     for i, b in enumerate(stats.get('beams', []))]}
+    if array:
+        out['array'] = {'antennas': 1 + len(antennas), 'array_ms': round(float(stats.get('array_ms', 0.0)), 3),
+                        'signature_ms': round(float(stats.get('signature_ms', 0.0)), 3),
+                        'beams_ms': round(float(stats.get('beams_ms', 0.0)), 3),
+                        'hits': [{'prn': int(h[1]), 'norm_max_corr': round(float(h[0]), 2), 'f_hz': float(h[2]),
+                                  'delay': int(h[3])} for h in stats.get('hits', [])],
+                        'beams': [{'prn': b['prn'], 'confirmed': b['confirmed'], 'kept': b['kept'],
+                                   'gain_db': round(b['gain_db'], 2), 'flags': b['flags']} for b in stats.get('beams', [])],
+                        'antenna0_alone': sorted(int(h[1]) for h in alone)}
     if cancel is not None:
         out['cancelled'] = [{'prn': int(r['prn']), 'n_windows': int(r['n_windows']), 'n_skipped': int(r['n_skipped']),
                              'removed': round(float(r['energy_removed'] / r['energy_in']), 5) if r['energy_in'] > 0 else 0.0}
@@ -445,6 +468,18 @@ def print_snapshot(out):
                       f"second path {f['rel_power']:.3f} of the first  {'DISTORTED' if f['prn'] in sp['distorted'] else 'one path'}")
             print(f"  PRNs with a distorted profile {sp['distorted']}; doubled or distorted: "
                   f"{'ALARM' if sp['alarm'] else 'no alarm'}")
+    ar = s.get('array')
+    if ar is not None:
+        print(f"  array search over {ar['antennas']} antennas ({ar['array_ms']} ms on the device; signatures "
+              f"{ar['signature_ms']} ms, beams {ar['beams_ms']} ms): PRNs {[h['prn'] for h in ar['hits']]}; antenna 0 "
+              f"alone would have found {ar['antenna0_alone']}")
+        kept = {b['prn']: b for b in ar['beams']}
+        for h in ar['hits']:
+            b = kept.get(h['prn'])
+            how = 'no beam' if b is None else f"beam gain {b['gain_db']:5.2f} dB  " + (
+                'measured on the beam' if b['kept'] else 'not confirmed on the beam: dropped')
+            print(f"  array PRN {h['prn']:2d}  normMaxCorr {h['norm_max_corr']:6.2f}  bin {h['f_hz']:+8.1f} Hz  "
+                  f"delay {h['delay']:4d}  {how}")
     bm = s.get('beams')
     if bm is not None:
         print(f"  beams over the antennas ({bm['beams_ms']} ms on the device), one per record:")
@@ -644,6 +679,9 @@ def main():
     ap.add_argument('--beams', action='store_true',
                     help='with --snapshot --spoof-check --antenna FILE ...: measure every record again on a beam of '
                          'its own over the antennas, with a null at the spoofer where one is found (DESIGN.md 4.2q)')
+    ap.add_argument('--array-search', action='store_true',
+                    help='with --snapshot --antenna FILE ... (one to three): search for the satellites over all antennas '
+                         'at once and measure each on a beam of its own (DESIGN.md 4.2s)')
     ap.add_argument('--json', action='store_true', help='one JSON line instead of text')
     a = ap.parse_args()
     if a.refine and not a.deep_acq:
@@ -672,16 +710,21 @@ def main():
             ap.error('--collective [RADIUS_KM]: needs --near, 0.1 .. 100 km')
         if a.spoof_check is not None and (a.spoof_check < 1 or a.cancel is not None or a.collective is not None):
             ap.error('--spoof-check [K]: K from 1 on, without --cancel / --collective')
-        if a.antenna and (a.spoof_check is None or a.null or a.null_taps != 1 or frontend is not None or a.excise
+        if a.array_search and (not 1 <= len(a.antenna) <= 3 or a.spoof_check is not None or a.cancel is not None
+                               or a.collective is not None or a.beams):
+            ap.error('--array-search: with one to three --antenna FILE, without --spoof-check / --cancel / --collective '
+                     '/ --beams')
+        if a.antenna and ((a.spoof_check is None and not a.array_search) or a.null or a.null_taps != 1 or frontend is not None or a.excise
                           or a.blank or len(a.antenna) > 7):
-            ap.error('--antenna FILE with --snapshot: up to seven further channels, with --spoof-check, in the '
+            ap.error('--antenna FILE with --snapshot: up to seven further channels, with --spoof-check or --array-search, in the '
                      'recorder\'s own format, without --null / --null-taps / --excise / --blank')
         if a.beams and not a.antenna:
             ap.error('--beams needs --antenna FILE ... (the beams combine the antennas)')
         if a.profile_check and a.spoof_check is None:
             ap.error('--profile-check needs --spoof-check (the profiles serve the spoofing check)')
         out = snapshot(a.recording, a.snapshot, eph, parse_time(a.time, eph), near, a.start_stream, frontend,
-                       a.excise, a.blank, a.cancel, a.collective, a.spoof_check, a.antenna, a.beams, a.profile_check)
+                       a.excise, a.blank, a.cancel, a.collective, a.spoof_check, a.antenna, a.beams, a.profile_check,
+                       a.array_search)
         if a.json:
             print(json.dumps(out))
         else:
@@ -693,6 +736,8 @@ def main():
         ap.error('--beams needs --snapshot SECONDS')
     if a.profile_check:
         ap.error('--profile-check needs --snapshot SECONDS')
+    if a.array_search:
+        ap.error('--array-search needs --snapshot SECONDS')
     if bool(a.antenna) != a.null:
         ap.error('--antenna FILE (the further channels) and --null go together')
     if a.null_taps != 1 and not a.null:
